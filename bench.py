@@ -10,9 +10,11 @@ torch.distributed.run (a plain `python bench.py --gpus N` re-launches itself tha
 horizontal bands with the halo exchanges running INSIDE the library over RCCL (hk_comm_*; include/hikari_hip.h) - if RCCL
 does not come up on every rank the run FAILS, it never falls back to staging halos through the host.  Rank 0 prints ONE JSON line.
 
-Timing: W warm-up frames, then B (default 5) timed blocks of EXACTLY K frames each, every block bracketed by
-barrier + device synchronisation on both sides, MAX over ranks per block.  `value` / `ms_per_step` are the
-MEDIAN block; `blocks_ms_per_step` lists all of them, `min_ms_per_step` the fastest.
+Timing: W warm-up frames, then EXACTLY K timed frames, split into B (default 5) blocks of nearly equal length, every block
+bracketed by barrier + device synchronisation on both sides, MAX over ranks per block.  `ms_per_step` = the time of the K frames / K
+(`value` = rays of the K frames / their time); `blocks_ms_per_step` lists the blocks, `min_ms_per_step` the fastest.  The HIP events of
+`roofline` ride on a block of min(K, 48) frames of its own after the timed ones.  --dump-outputs DIR writes what the last timed frame
+computed (the tone-mapped image, f32) to DIR/tone_mapped.npy.
 
 Ray accounting: rays = primary rays (one per pixel) + traverse_top invocations + stand-alone
 traverse_bottom invocations.  They are counted by replaying the same frames on a second
@@ -46,6 +48,7 @@ sys.path.insert(0, ROOT)
 # variance 4 + render 8.
 INDIRECT_BYTES_PER_PIXEL = (44 + 4 + 64) + (64 + 4 + 8)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 
 def cgroup_cpus():
@@ -159,12 +162,14 @@ def pmc_traffic_in_run(timeout_s=150):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="frames per timed block (default 48; 12 for --config 3/4/5)")
+    ap.add_argument("--steps", type=int, default=None, help="timed frames in all (default 240; 60 for --config 3/4/5); ms_per_step = their time / --steps")
     ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up frames (default 512 for the headline config: half a second, enough for the clocks to settle "
                     "- with 16 the five timed blocks of a run still drifted 2.5 %% downwards; 16 for --config 3/4/5)")
-    ap.add_argument("--blocks", type=int, default=None, help="timed blocks of --steps frames each; the median is reported (default: 5, and as many more as it "
-                    "takes to time 240 frames in all - the default run's 5 x 48 - when --steps is smaller: the figure is then the median over the same "
-                    "number of frames whatever --steps is)")
+    ap.add_argument("--blocks", type=int, default=5, help="the --steps timed frames run in this many blocks of (nearly) equal length, each between a barrier + "
+                    "device synchronisation on both sides (default 5, at most --steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed frames write what the last of them computed - the tone-mapped image a "
+                    "caller receives, f32 [H][W][4]; beyond 64 MB every s-th row and column - to DIR/tone_mapped.npy (inputs are seeded: the same arguments give the same "
+                    "inputs on every run)")
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4, 5))
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
@@ -196,15 +201,15 @@ def main():
     args = ap.parse_args()
     if args.no_wide_walk:
         args.ctx_flags |= 256  # HK_CTX_NO_WIDE_WALK
+    if args.dump_outputs and args.no_gather and args.gpus > 1:
+        sys.exit("bench.py --dump-outputs needs the gathered image (drop --no-gather)")
     if args.steps is None:
-        args.steps = 48 if args.config == 2 else 12
+        args.steps = 240 if args.config == 2 else 60
     if args.warmup is None:
         args.warmup = 512 if args.config == 2 else 16
-    if args.blocks is None:
-        # the default run of the headline config times 5 blocks of 48 frames; a caller that asks for shorter blocks gets as many as time the
-        # same 240 frames (each block still EXACTLY --steps frames between a barrier + device synchronisation on both sides): the frames of a
-        # young history are dearer (profiles/r06_history_age.txt), and five short blocks would be a median over the first hundred of them
-        args.blocks = max(5, -(-240 // max(1, args.steps))) if args.config == 2 else 5
+    if args.steps < 1 or args.warmup < 0 or args.blocks < 1:
+        sys.exit("bench.py: --steps and --blocks must be >= 1, --warmup >= 0")
+    args.blocks = min(args.blocks, args.steps)
 
     import numpy as np
     import torch
@@ -265,8 +270,8 @@ def main():
         return float(t.item())
 
     def measure(config, steps, warmup, n_blocks, width=None, height=None, bounces=None, alone=True, passes=False, sustained_s=0.0):
-        """The timed protocol on one BASELINE config: warm-up, n_blocks timed blocks of EXACTLY `steps` frames (barrier + device
-        synchronisation on both sides, max over ranks), the ray count by a deterministic replay, optionally the dominant
+        """The timed protocol on one BASELINE config: warm-up, EXACTLY `steps` timed frames in n_blocks blocks (barrier + device
+        synchronisation on both sides, max over ranks), an instrumented block after them, the ray count by a deterministic replay, optionally the dominant
         dispatch alone on the GPU and a sustained block.  Returns a dict; the engines stay alive in it under "_engines"."""
         scene, camera, settings, lights, description = workload(hk, config, width, height, bounces)
         W, H = camera.width, camera.height
@@ -320,32 +325,54 @@ def main():
         rebalance_at = tuple(sorted({max(2, (k + 1) * (warmup - 4) // (rounds + 1)) for k in range(rounds)})) if rounds > 0 else ()
         run_frames(eng, rend, 1, warmup, rebalance_at=rebalance_at)
         eng.wait()
-        eng.reset_stats()
-        # HIP events ON the two long dispatches of the frame (hipExtLaunchKernelGGL: no extra stream operation) + each trace launch of the
-        # queue-based schedule; scenes beyond LDS (configs 3 / 4) also bracket their two direct-light dispatches on the side stream
-        mask = (1 << F.PASS_INDIRECT) | (1 << F.PASS_INDIRECT_SPATIAL_REUSE) | (1 << F.TIMING_TRACE_STAGES)
-        if config in (3, 4):
-            mask |= (1 << F.PASS_DIRECT_LIT) | (1 << F.PASS_DIRECT_EMISSIVE)
+        # The timed region: EXACTLY `steps` frames, in n_blocks blocks of (nearly) equal length, each bracketed by barrier + device
+        # synchronisation; no HIP events on any of them.  elapsed = the sum of the blocks = the time of all `steps` frames.
+        eng.set_timing_mask(0)
+        n_blocks = max(1, min(n_blocks, steps))
+        block_frames = [steps // n_blocks + (1 if k < steps % n_blocks else 0) for k in range(n_blocks)]
         blocks = []
         n0 = warmup
-        for k in range(max(1, n_blocks)):
-            # The events ride on the FIRST timed block only.  An event on a dispatch is a completion signal the host can observe, and the
-            # frame pays for it (presumably the wider release such a dispatch ends with) - measured in one run: 0.942 ms per frame with the
-            # two long dispatches instrumented against 0.904 without (round 6; rounds 4 / 5 saw 0.945 against 0.928).  The roofline figures
-            # come from that block (K frames of the timed region, HIP events on the dispatches' own stream), `value` is the MEDIAN block -
-            # with the default five blocks an un-instrumented one; blocks_ms_per_step lists all of them, the instrumented one first.
-            eng.set_timing_mask(mask if k == 0 else 0)
+        for k in block_frames:
             barrier()
             t0 = time.perf_counter()
-            run_frames(eng, rend, n0 + 1, n0 + steps)
+            run_frames(eng, rend, n0 + 1, n0 + k)
             eng.wait()
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             barrier()
             blocks.append(max_over_ranks(t1 - t0))
-            n0 += steps
+            n0 += k
         last_frame = n0
-        elapsed = float(np.median(blocks))
+        elapsed = float(sum(blocks))
+        tone = eng.read(F.BUF_TONE_MAPPED)
+        # what a caller of the timed path receives after its last step: the tone-mapped image (f16 on the device, f32 here); larger than
+        # DUMP_BYTES (4K), every s-th row and column of it
+        outputs = None
+        if args.dump_outputs and config == args.config:
+            s = 1
+            while tone.size * 4 > DUMP_BYTES * s * s:
+                s += 1
+            outputs = {"tone_mapped": tone[::s, ::s].view(np.float16).astype(np.float32)}
+        # HIP events ON the two long dispatches of the frame (hipExtLaunchKernelGGL: no extra stream operation) + each trace launch of the
+        # queue-based schedule; scenes beyond LDS (configs 3 / 4) also bracket their two direct-light dispatches on the side stream.
+        # They ride on a block of their own AFTER the timed frames: an event on a dispatch is a completion signal the host can observe,
+        # and the frame pays for it (presumably the wider release such a dispatch ends with) - measured in one run: 0.942 ms per frame
+        # with the two long dispatches instrumented against 0.904 without (round 6).  The roofline figures come from that block.
+        mask = (1 << F.PASS_INDIRECT) | (1 << F.PASS_INDIRECT_SPATIAL_REUSE) | (1 << F.TIMING_TRACE_STAGES)
+        if config in (3, 4):
+            mask |= (1 << F.PASS_DIRECT_LIT) | (1 << F.PASS_DIRECT_EMISSIVE)
+        eng.reset_stats()
+        eng.set_timing_mask(mask)
+        n_instr = min(steps, 48)
+        barrier()
+        t0 = time.perf_counter()
+        run_frames(eng, rend, n0 + 1, n0 + n_instr)
+        eng.wait()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        barrier()
+        instrumented = {"frames": n_instr, "first_frame": n0 + 1, "ms_per_step": round(max_over_ranks(t1 - t0) / n_instr * 1e3, 4)}
+        n0 += n_instr
         st = eng.stats()
         schedule = eng.indirect_schedule()
         traversal = eng.traversal_mode() + (eng.wide_walk(),)
@@ -356,7 +383,6 @@ def main():
         trace_launches = int(st.pass_launches[F.TIMING_TRACE_STAGES])
         trace_ms = st.pass_ms_total[F.TIMING_TRACE_STAGES] / max(1, trace_launches)   # average TRACE launch of the queue-based indirect pass (0 launches: fused schedule)
         eng.set_timing_mask(0)
-        tone = eng.read(F.BUF_TONE_MAPPED)
 
         # a sustained block of the same frames (>= sustained_s seconds, one barrier-bracketed region): long enough for the
         # driver's GPU-activity sampling and for the clock to settle under load; reported beside `value`, never as `value`
@@ -365,7 +391,7 @@ def main():
             n_frames = max(steps, int(1.1 * sustained_s / (elapsed / steps)) + 1)  # (+10 %: frames run a little faster in one long block)
             barrier()
             t0 = time.perf_counter()
-            run_frames(eng, rend, last_frame + 1, last_frame + n_frames)
+            run_frames(eng, rend, n0 + 1, n0 + n_frames)
             eng.wait()
             torch.cuda.synchronize()
             t1 = time.perf_counter()
@@ -376,7 +402,7 @@ def main():
         # frame LATENCY: one frame, wait, repeat (the timed blocks keep three streams full - frame n's a-trous levels run beside frame
         # n + 1's light passes - so ms_per_step is a THROUGHPUT figure; this is what one frame takes from its first dispatch to its image).
         # After everything that is compared with the replay: these frames are not part of any count.
-        lat, nl = [], last_frame + (sustained["frames"] if sustained else 0)
+        lat, nl = [], n0 + (sustained["frames"] if sustained else 0)
         for k in range(min(steps, 16)):
             barrier()
             t0 = time.perf_counter()
@@ -445,7 +471,8 @@ def main():
                                     "tail_fraction_of_trace_time": round(sum(st_["ticks_after_the_queue_ran_dry"] for st_ in stages) / max(1, sum(st_["ticks"] for st_ in stages)), 4)}
             del weng
 
-        res = {"config": config, "description": description, "W": W, "H": H, "steps": steps, "warmup": warmup, "blocks": blocks, "elapsed": elapsed,
+        res = {"config": config, "description": description, "W": W, "H": H, "steps": steps, "warmup": warmup, "blocks": blocks, "block_frames": block_frames, "elapsed": elapsed,
+               "instrumented": instrumented, "outputs": outputs,
                "band_bounds": (rend.bounds if rend is not None else None), "band_bounds_history": {str(k): v for k, v in bounds_log.items()},
                "last_frame": last_frame, "schedule": schedule, "traversal": traversal, "ind_ms": ind_ms, "ind_launches": ind_launches, "sp_ms": sp_ms, "direct_ms": direct_ms,
                "frame_latency_ms": frame_latency_ms, "trace_ms": trace_ms, "trace_launches": trace_launches,
@@ -504,6 +531,10 @@ def main():
     m = measure(args.config, args.steps, args.warmup, args.blocks, args.width, args.height, args.bounces, alone=True, passes=args.passes,
                 sustained_s=args.sustained_seconds if default_run or args.sustained_seconds_forced else 0.0)
     W, H, blocks, elapsed, last_frame, schedule = m["W"], m["H"], m["blocks"], m["elapsed"], m["last_frame"], m["schedule"]
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in m["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
     ind_ms, ind_ms_alone, total_rays, same, description = m["ind_ms"], m["ind_ms_alone"], m["total_rays"], m["same"], m["description"]
     passes = m.get("passes")
     xeng = m["_probe_engine"]
@@ -586,11 +617,11 @@ def main():
 
         m.pop("_engines", None)
         gc.collect()
-        for cfg, steps_x in ((3, 8), (4, 6), (5, 8)):
+        for cfg, steps_x in ((3, 24), (4, 18), (5, 24)):
             x = measure(cfg, steps_x, 6, 3, alone=False)
             extra[str(cfg)] = {"workload": x["description"], "value": round(x["total_rays"] / x["elapsed"] / 1e6, 3), "unit": "Mray/s",
                                "ms_per_step": round(x["elapsed"] / steps_x * 1e3, 4), "steps": steps_x, "warmup": 6,
-                               "blocks_ms_per_step": [round(b / steps_x * 1e3, 4) for b in x["blocks"]], "rays_per_frame": round(x["total_rays"] / steps_x, 1),
+                               "blocks_ms_per_step": [round(b / k * 1e3, 4) for b, k in zip(x["blocks"], x["block_frames"])], "rays_per_frame": round(x["total_rays"] / steps_x, 1),
                                "indirect_schedule": x["schedule"], "traversal": x["traversal"][0], "wide_walk": x["traversal"][2], "indirect_avg_launch_ms": round(x["ind_ms"], 5),
                                "trace_avg_launch_ms": round(x["trace_ms"], 5), "replay_bit_identical": x["same"]}
             if "ray_count_replay_bit_identical" in x["walk"]:   # (scenes beyond LDS: `replay_bit_identical` is the counting twin of the timed kernels; this is the fused ray-counting replay)
@@ -635,7 +666,7 @@ def main():
     band_rows = m["band_rows"]
     algo_bytes = INDIRECT_BYTES_PER_PIXEL * W * band_rows
     achieved = algo_bytes / (ind_ms * 1e-3) / 1e9 if ind_ms > 0 else 0.0
-    ms_blocks = [round(b / args.steps * 1e3, 4) for b in blocks]
+    ms_blocks = [round(b / k * 1e3, 4) for b, k in zip(blocks, m["block_frames"])]
 
     out = {
         "metric": "Mray/s (Cornell 1080p 2-bounce, whole job) + frame ms",
@@ -653,8 +684,8 @@ def main():
         "config": {
             "workload": description,
             "baseline_config": args.config,
-            "frames": f"warmup 1..{args.warmup}, then {len(blocks)} timed blocks of {args.steps} frames ({args.warmup + 1}..{last_frame}); value = median block; "
-                      "the roofline's HIP events ride on the first block",
+            "frames": f"warmup 1..{args.warmup}, then {args.steps} timed frames in {len(blocks)} blocks ({args.warmup + 1}..{last_frame}); ms_per_step = their time / "
+                      f"{args.steps}; the roofline's HIP events ride on frames {m['instrumented']['first_frame']}..{m['instrumented']['first_frame'] + m['instrumented']['frames'] - 1}",
             "parallelism": f"band{world}" if world > 1 else "single",
             **({"band_split": ("measured" if m["band_bounds_history"] else ("balanced" if m["band_bounds"] else "equal")), "band_bounds": m["band_bounds"],
                 "band_rebalancing": {"rounds_during_warmup": args.band_rebalance_rounds, "splits_taken": m["band_bounds_history"],
@@ -666,12 +697,12 @@ def main():
             "traversal": {"mode": m["traversal"][0], "orderings": m["traversal"][1], "wide_walk": m["traversal"][2]},
         },
         "blocks_ms_per_step": ms_blocks,
-        "blocks": {"count": len(ms_blocks), "frames_each": args.steps, "first_timed_frame": args.warmup + 1, "last_timed_frame": args.warmup + len(ms_blocks) * args.steps,
-                   "note": "every block is EXACTLY --steps frames between a barrier + device synchronisation on both sides; ms_per_step / value = the MEDIAN block.  Without "
-                           "--blocks the run times 240 frames in all whatever --steps is (5 x 48 by default): the workload gets cheaper while its reservoirs age "
-                           "(frames 6-25 of a fresh context 0.96 ms, 0.90 from frame 200 on; profiles/r06_history_age.txt), so the blocks are listed in frame order"},
-        "instrumented_block": {"index": 0, "ms_per_step": ms_blocks[0], "note": "the HIP events of `roofline` (on the two long dispatches; configs 3 / 4: + every trace launch and the "
-                               "direct-light dispatches) ride on this timed block only - they cost the frames that carry them 2-4 %; `value` is the median block"},
+        "blocks": {"count": len(ms_blocks), "frames_each": m["block_frames"], "first_timed_frame": args.warmup + 1, "last_timed_frame": last_frame,
+                   "note": "the --steps timed frames in blocks between a barrier + device synchronisation on both sides; ms_per_step / value = all of them.  "
+                           "The workload gets cheaper while its reservoirs age (frames 6-25 of a fresh context 0.96 ms, 0.90 from frame 200 on; "
+                           "profiles/r06_history_age.txt), so the blocks are listed in frame order"},
+        "instrumented_block": {**m["instrumented"], "note": "the HIP events of `roofline` (on the two long dispatches; configs 3 / 4: + every trace launch and the "
+                               "direct-light dispatches) ride on these frames after the timed ones, not on any timed frame - they cost the frames that carry them 2-4 %"},
         "min_ms_per_step": min(ms_blocks),
         "mray_per_s_per_gpu": round(total_rays / elapsed / 1e6 / world, 3),
         "rays_per_frame": round(total_rays / args.steps, 1),

@@ -283,6 +283,9 @@ int ensure_parked(hk_ctx* c, uint32_t channels) {
       // dispatch - while another stream is about to use ITS channel's planes)
       if (e == hipSuccess) e = hipMemset(plane[j], j == 0 ? 0xFF : 0, plane_bytes[j]);
     }
+    // hipMemset goes to the null stream, which does not order itself with the context's non-blocking streams: without this wait it
+    // could land after the first dispatch that parks into these planes (the first frame after hk_resize re-allocates them)
+    if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
       if (winner) (void)hipFree(winner);
       for (void* q : plane)

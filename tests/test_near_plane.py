@@ -1,6 +1,6 @@
 """The near-plane clip of the ray-cast G-buffer (VERDICT r05 missing 2 / next 6).
 
-The reference RASTERISES its G-buffer with `unclipped_depth: false` (/root/reference/src/prepass.rs:242-266; perspective camera, near =
+The reference RASTERISES its G-buffer with `unclipped_depth: false` (the reference's src/prepass.rs:242-266; perspective camera, near =
 0.1, infinite reverse-Z far plane): geometry between the eye and the near plane never reaches a fragment, a triangle that straddles the
 plane is cut at it.  Primary rays start at the eye, so without a clip such geometry would enter the G-buffer - in the oracle as in the
 kernels, which is why no parity test could see it.  Both now trace a pixel whose nearest surface lies in front of the plane once more

@@ -1,5 +1,5 @@
 import os, sys, time
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+_R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, _R); sys.path.insert(0, os.path.join(_R, 'tests'))
 print("nproc", os.cpu_count(), "affinity", len(os.sched_getaffinity(0)))
 try:
     print("cpu.max", open('/sys/fs/cgroup/cpu.max').read().strip())

@@ -8,7 +8,7 @@ tests/tools/wgsl/runtime.py) and this script runs every compute entry point on t
 corresponding dispatch and compares what the shader writes with what the oracle wrote, byte for byte.  The G-buffer
 comes from the oracle (prepass.wgsl is a raster shader; the ray-cast G-buffer is this project's contract).
 
-  python tests/tools/wgsl_pin.py [--size W H] [--frames N] [--write]      (needs /root/reference; minutes of pure Python)
+  [HIKARI_REFERENCE_DIR=<bevy-hikari checkout>] python tests/tools/wgsl_pin.py [--size W H] [--frames N] [--write]      (minutes of pure Python)
 
 --write stores the inputs and the shader-produced outputs of every dispatch under tests/golden/wgsl_pin.npz, which
 tests/test_wgsl_pin.py replays against the oracle without the reference."""
@@ -31,7 +31,9 @@ from wgsl import runtime as R
 from wgsl import types as T
 from wgsl.engine import Module
 
-SHADERS = "/root/reference/src/shaders"
+# the reference checkout (bevy-hikari) is not part of this repository: HIKARI_REFERENCE_DIR names it, else its usual place
+REFERENCE_DIR = os.environ.get("HIKARI_REFERENCE_DIR") or "/root/reference"
+SHADERS = os.path.join(REFERENCE_DIR, "src", "shaders")
 f32 = np.float32
 
 

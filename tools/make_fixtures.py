@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the data fixtures this repo ships, from the read-only reference checkout.
 
-Run once in the build container (``/root/reference`` does not exist on the GPU box):
+Run once where a reference checkout is at hand (HIKARI_REFERENCE_DIR, else its usual place):
 
     python tools/make_fixtures.py
 
@@ -26,7 +26,7 @@ import sys
 
 import numpy as np
 
-REF = "/root/reference"
+REF = os.environ.get("HIKARI_REFERENCE_DIR") or "/root/reference"   # (the reference checkout: not part of this repository)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "bevy-hikari_amd", "assets")
 
