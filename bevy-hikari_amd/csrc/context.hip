@@ -129,8 +129,6 @@ int free_screen(hk_ctx* c) {
   }
   if (c->wf_mem) (void)hipFree(c->wf_mem);
   c->wf_mem = nullptr;
-  if (c->wf_paths_mem) (void)hipFree(c->wf_paths_mem);
-  c->wf_paths_mem = nullptr;
   if (c->wf.timeline) (void)hipFree(c->wf.timeline);
   c->wf = hkd::WfBuffers{};
   if (c->depth_plane) (void)hipFree(c->depth_plane);
@@ -615,38 +613,6 @@ int ensure_wavefront(hk_ctx* c) {
   const bool tl_twin = c->wf_timeline, count_twin = (c->flags & HK_CTX_COUNT_WALKS) != 0u;
   if ((tl_twin || count_twin) && !w.timeline) HK_HIP(hipMalloc((void**)&w.timeline, 64 * 32 * sizeof(unsigned long long)));  // tools/wf_timeline.py, bench.py
   w.timeline_mode = count_twin ? 2u : (tl_twin ? 1u : 0u);
-  w.pb_add = nullptr; w.pb_sh = nullptr; w.local = nullptr; w.pb_bounces = 0u;   // (re-carved below for the new size)
-  if (c->wf_paths_mem) { HK_HIP(hipFree(c->wf_paths_mem)); c->wf_paths_mem = nullptr; }
-  return HK_OK;
-}
-// whether the queue-based schedule runs every bounce in one launch (kernels_wavefront.hip k_wf_trace_wide<.., PATHS>):
-// hk_debug_set_option(HK_DEBUG_OPT_PERSISTENT_PATHS), -1 = the rule
-#ifndef HK_PERSISTENT_PATHS_RULE
-#define HK_PERSISTENT_PATHS_RULE false   // (measured: no faster than the stages on a full frame or a band - DESIGN 8.1c, profiles/r06_persistent_paths_ab.json)
-#endif
-static bool persistent_paths(const hk_ctx* c) {
-  if (!(c->persistent_paths < 0 ? HK_PERSISTENT_PATHS_RULE : c->persistent_paths != 0)) return false;
-  return use_wide(c) && !(c->flags & HK_CTX_COUNT_WALKS) && c->frame.indirect_bounces >= 1u && c->frame.indirect_bounces <= 16u &&
-         (size_t)c->RW * c->RH <= ((size_t)1 << 26);
-}
-// ... its planes per bounce (36 B per path and bounce) and the waves' own lists (4 KB per wave of the launch), for at least `bounces`
-int ensure_wavefront_paths(hk_ctx* c, uint32_t bounces) {
-  hkd::WfBuffers& w = c->wf;
-  if (c->wf_paths_mem && w.pb_bounces >= bounces) return HK_OK;
-  if (c->wf_paths_mem) {
-    HK_HIP(hipStreamSynchronize(c->stream));
-    HK_HIP(hipFree(c->wf_paths_mem));
-    c->wf_paths_mem = nullptr;
-    w.pb_bounces = 0u;
-  }
-  const size_t n = w.cap, waves = hk::wide_trace_lanes(c->compute_units) / 64u;
-  const size_t bytes = (size_t)bounces * n * (2 * 16 + 4) + waves * 1024 * sizeof(uint32_t);
-  HK_HIP(hipMalloc(&c->wf_paths_mem, bytes));
-  uint8_t* p = (uint8_t*)c->wf_paths_mem;
-  w.pb_add = (float4*)p; p += (size_t)bounces * n * 32;
-  w.pb_sh = (uint32_t*)p; p += (size_t)bounces * n * 4;
-  w.local = (uint32_t*)p;
-  w.pb_bounces = bounces;
   return HK_OK;
 }
 
@@ -682,15 +648,10 @@ int join_all(hk_ctx* c) {
   return rc;
 }
 #define HK_FRAME_INTERNAL_LATE_JOIN 0x80000000u   // hk_frame_render -> hk_frame_stage: the caller puts exchange B behind the side stream itself (post_begin)
-#ifndef HK_POST_DEMODULATION_RULE
-#define HK_POST_DEMODULATION_RULE true
-#endif
 // Stage POST_PROCESS on the post stream (hk_context.hpp "Frame pipelining"): the main stream waits for the side stream, then the post
 // stream takes over behind everything the main stream holds - demodulation, the a-trous levels and tone mapping of this frame (on a
 // band with a communicator also exchange B) run there while the main stream goes on to the next frame.  `pipelined` = false: the frame
 // stays on the main stream, which then waits for what the post stream still holds (timed passes, no denoiser, verification contexts).
-// whether demodulation goes to the post stream with the levels (hk_debug_set_option(HK_DEBUG_OPT_POST_DEMODULATION): -1 = the rule)
-static bool demod_on_post(const hk_ctx* c) { return c->post_demodulation < 0 ? HK_POST_DEMODULATION_RULE : c->post_demodulation != 0; }
 int post_begin(hk_ctx* c, const HkSettings* st, bool* pipelined) {
   *pipelined = false;
   int rc;
@@ -703,7 +664,6 @@ int post_begin(hk_ctx* c, const HkSettings* st, bool* pipelined) {
     if ((rc = join_side(c))) return rc;
     return join_post(c);  // the denoiser's internal planes: last frame's levels come first
   }
-  if (c->side_join_each_frame && (rc = join_side(c))) return rc;   // (hk_debug_set_option: the order of rounds 1-5, for the A/B)
   // the post stream waits for the main stream AND (round 6) for the side stream itself: the main stream goes on to the next frame without
   // either wait (the direct-light dispatches stay "not joined": c->forked)
   if (c->forked) {
@@ -800,14 +760,12 @@ int run_pass(hk_ctx* c, uint32_t pass, uint32_t arg, int y0, int y1) {
           wide.spill = c->wide_spill;
           wide.lost = c->d_counters + 8;
         }
-        const bool persistent = persistent_paths(c);
-        if (persistent) { const int rc_ = ensure_wavefront_paths(c, c->frame.indirect_bounces); if (rc_) return rc_; }
-        // (HK_TIMING_TRACE_STAGES: every trace launch of the pass between its own pair of events; the persistent schedule has one)
+        // (HK_TIMING_TRACE_STAGES: every trace launch of the pass between its own pair of events)
         std::vector<hipEvent_t> trace_events;
         if ((c->timing_mask >> HK_TIMING_TRACE_STAGES) & 1u)
-          for (uint32_t k = 0; k < (persistent ? 2u : 2u * (c->frame.indirect_bounces + 1u)); ++k) trace_events.push_back(get_event(c));
+          for (uint32_t k = 0; k < 2u * (c->frame.indirect_bounces + 1u); ++k) trace_events.push_back(get_event(c));
         launch_indirect_wavefront(c->stream, c->scene, fr, g, t, c->wf, y0, y1, c->compute_units, timer.on ? timer.t.start : nullptr,
-                                  timer.on ? timer.t.stop : nullptr, &wide, trace_events.empty() ? nullptr : trace_events.data(), persistent);
+                                  timer.on ? timer.t.stop : nullptr, &wide, trace_events.empty() ? nullptr : trace_events.data());
         for (size_t k = 0; k + 1 < trace_events.size(); k += 2) c->pending.push_back(TimedLaunch{HK_TIMING_TRACE_STAGES, trace_events[k], trace_events[k + 1]});
       } else if (pass == HK_PASS_INDIRECT)  // MULTIPLE_BOUNCES pipeline iff bounces >= 2, light.rs:663-666
         launch_indirect(c->stream, c->frame.indirect_bounces >= 2u, c->scene, fr, g, t, y0, y1, counters, timer.on ? timer.t.start : nullptr,
@@ -1057,9 +1015,6 @@ int hk_debug_set_option(hk_ctx* c, uint32_t option, int64_t value) {
     case HK_DEBUG_OPT_FLAT_WALK: c->flat_walk = value != 0; c->dynamic_dirty = true; break;
     case HK_DEBUG_OPT_FLAT_ORDERINGS: c->flat_orderings = (int)std::max<int64_t>(0, std::min<int64_t>(8, value)); c->dynamic_dirty = true; break;
     case HK_DEBUG_OPT_TRACE_UPDATE: c->trace_update = value != 0; break;
-    case HK_DEBUG_OPT_SIDE_JOIN: c->side_join_each_frame = value != 0; break;
-    case HK_DEBUG_OPT_POST_DEMODULATION: c->post_demodulation = value < 0 ? -1 : (value ? 1 : 0); break;
-    case HK_DEBUG_OPT_PERSISTENT_PATHS: c->persistent_paths = value < 0 ? -1 : (value ? 1 : 0); break;
     case HK_DEBUG_OPT_PREPASS_PIPELINE: c->prepass_pipeline = value < 0 ? -1 : (value ? 1 : 0); break;
     case HK_DEBUG_OPT_MAIN_PRIORITY: c->main_priority = value < 0 ? -1 : (value ? 1 : 0); return pick_main_stream(c, true);
     default: HK_REQUIRE(false, HK_E_INVALID, "unknown option %u", option);
@@ -1534,18 +1489,7 @@ int hk_frame_stage(hk_ctx* c, uint32_t stage, const HkSettings* st, uint32_t fla
       // the reference's per-channel loop, with the channels of each step fused into one launch.  Round 6: demodulation too runs on
       // the post stream - the render / variance planes it reads are double-buffered by frame parity, the next frame's light passes
       // write the other set - so a frame's main stream ends with its spatial pass (a band: with exchange A and its spatial pass)
-      if (pipelined && !demod_on_post(c)) {  // (demodulation stays on the main stream, the levels follow it on the post stream)
-        hipStream_t post = c->stream;
-        c->stream = c->post_saved_main;
-        rc = join_side(c);  // (demodulation on the main stream reads the direct-light channels)
-        if (!rc) rc = join_post(c);  // the denoiser's internal planes: last frame's levels come first
-        if (!rc) rc = run_demodulation_fused(c, nch, clampr(b0 - 15), clampr(b1 + 15));
-        if (!rc && hipEventRecord(c->post_fork, c->stream) != hipSuccess) rc = HK_E_HIP;
-        if (!rc && hipStreamWaitEvent(post, c->post_fork, 0) != hipSuccess) rc = HK_E_HIP;
-        c->stream = post;
-      } else {
-        rc = run_demodulation_fused(c, nch, clampr(b0 - 15), clampr(b1 + 15));
-      }
+      rc = run_demodulation_fused(c, nch, clampr(b0 - 15), clampr(b1 + 15));
       if (!rc) rc = run_denoise_fused(c, nch, 0, clampr(b0 - 7), clampr(b1 + 7));
       if (!rc) rc = run_denoise_fused(c, nch, 1, clampr(b0 - 3), clampr(b1 + 3));
       if (!rc) rc = run_denoise_fused(c, nch, 2, clampr(b0 - 1), clampr(b1 + 1));

@@ -432,15 +432,11 @@ HKD uint32_t ray_octant(f3 d) { return (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u
 // mesh (select_light_candidate, light.wgsl:687): round 5 walks it in the reference's order (ordering 0) whatever the ray's octant -
 // two triangles of the emitter that tie exactly (a sampled point on a shared edge) then resolve as in the reference, and with the
 // wide walk's rank rule (hk_wide.hpp) and traverse_top<true> every hit of the product default is the reference's.
-// HK_EMITTER_WALK_REF_ORDER=0 is the A/B (the octant's ordering: the visits front to back).
-#ifndef HK_EMITTER_WALK_REF_ORDER
-#define HK_EMITTER_WALK_REF_ORDER 1
-#endif
 HKD bool traverse_bottom(const DScene& sc, Hit& hit, const Ray& ray, uint32_t node_offset, uint32_t node_count, uint32_t primitive_offset,
                          float early_distance, RayCounters& rc) {
   bool intersected = false;
   uint32_t index = 0u;
-  const uint32_t nbase = sc.blas_base + (HK_EMITTER_WALK_REF_ORDER ? 0u : ray_octant(ray.direction) * sc.blas_stride) + node_offset;
+  const uint32_t nbase = sc.blas_base + node_offset;
   while (index < node_count) {
     const float4* __restrict__ nd = sc.nodes + 2u * (nbase + index);
     const float4 lo = nd[0];
@@ -609,12 +605,8 @@ HKD Hit traverse_flat(const DScene& sc, const Ray& ray, float max_distance, floa
 template <bool REF_ORDER = false>
 HKD Hit traverse_top(const DScene& sc, const Ray& ray, float max_distance, float early_distance, uint32_t exclude_instance, RayCounters& rc) {
   // (a ray whose occluder is kept does not take the one-level walk either: that is ANOTHER tree - whichever of its orderings is
-  // walked, the first occluder it meets need not be the reference's; the two-level walk below in ordering 0 is the reference's walk.
-  // HK_FLAT_KEPT_OCCLUDERS = 1 is the A/B: round 3-4's behaviour, the one-level walk for these rays too.)
-#ifndef HK_FLAT_KEPT_OCCLUDERS
-#define HK_FLAT_KEPT_OCCLUDERS 0
-#endif
-  if (sc.flat_mode && (!REF_ORDER || HK_FLAT_KEPT_OCCLUDERS)) return traverse_flat<REF_ORDER>(sc, ray, max_distance, early_distance, exclude_instance, rc);
+  // walked, the first occluder it meets need not be the reference's; the two-level walk below in ordering 0 is the reference's walk.)
+  if (sc.flat_mode && !REF_ORDER) return traverse_flat<REF_ORDER>(sc, ray, max_distance, early_distance, exclude_instance, rc);
   rc.tlas++;
 #ifdef HK_PROFILE_SECTIONS
   uint32_t wev_[5] = {0u, 0u, 0u, 0u, 0u};

@@ -97,7 +97,6 @@ HKD f3 mul(const mat3& m, f3 v) {
 }
 
 // ---- transcendental routines
-HKD float pow2i(int n) { return u2f((uint32_t)(n + 127) << 23); }
 HKD float sin_poly(float r) {
   float z = r * r;
   float p = fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f);
@@ -143,14 +142,7 @@ HKD void sincos_(float x, float* sn, float* cs) {  // same values as sin_ / cos_
 // y * 2^k rounded once.  The contract writes it as (y * 2^(k/2)) * 2^(k - k/2): for the k that exp_ / exp2_ produce (-150..128) and
 // their y in [0.7, 1.42] the first product is exact and normal, so the second is the only rounding (to a subnormal, or an overflow
 // to infinity, included) - which is v_ldexp_f32, one instruction instead of eight (tests/test_math_contract.py sweeps the edges).
-HKD float scale2(float y, int k) {
-#ifdef HK_SCALE2_MUL
-  int k1 = k / 2, k2 = k - k1;
-  return (y * pow2i(k1)) * pow2i(k2);
-#else
-  return __builtin_ldexpf(y, k);
-#endif
-}
+HKD float scale2(float y, int k) { return __builtin_ldexpf(y, k); }
 // (exp2_ / exp_ keep their early returns: turning them into selects after the polynomial removes ~250 scalar instructions from
 // k_denoise but made k_spatial_reuse 4 % slower - measured, round 2)
 HKD float exp2_(float x) {

@@ -215,16 +215,9 @@ __device__ __forceinline__ uint32_t wide_node(WideWalk& k, const WideTrees& wt, 
 }
 // the reference's tie rule between two candidates at exactly the same distance: the one its stackless walk meets first wins, i.e. the
 // leaf of smaller position in ordering 0 - instance leaves first, triangle leaves inside one instance (hk_kernels.hpp WideTrees ranks)
-#ifndef HK_WIDE_TIE_BY_RANK
-#define HK_WIDE_TIE_BY_RANK 1  // (0: round 4's rule - the smaller (instance, primitive); the A/B of what the rank loads cost)
-#endif
 __device__ __forceinline__ bool wide_tie_goes_to(const WideTrees& wt, uint32_t instance, uint32_t primitive, uint32_t best_instance, uint32_t best_primitive) {
-#if HK_WIDE_TIE_BY_RANK
   if (instance != best_instance) return wt.tlas_rank[instance] < wt.tlas_rank[best_instance];
   return wt.blas_rank[primitive] < wt.blas_rank[best_primitive];
-#else
-  return instance < best_instance || (instance == best_instance && primitive < best_primitive);
-#endif
 }
 __device__ __forceinline__ uint32_t wide_triangle_test(WideWalk& k, const WideTrees& wt, uint32_t primitive_index, f3 v0, f3 v1, f3 v2) {
   Ray lr;

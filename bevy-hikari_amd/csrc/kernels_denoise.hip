@@ -115,11 +115,7 @@ __device__ __forceinline__ bool nan_or_above_max(f3 v) { return !(v.x <= HK_F32_
 #endif
 template <int LEVEL, int NCH, int FFMASK>
 __global__ __launch_bounds__(256, HK_DENOISE_WAVES) void k_denoise(DFrame fr, DenoiseTargets d, int row_begin, int row_end) {  // denoise.wgsl:164-319
-#if defined(HK_DENOISE_TILES_RR)
-  const Pixel px = pixel_of_thread<false>(fr.rw, row_begin, row_end);
-#else
   const Pixel px = pixel_of_thread_rows<HK_DENOISE_W, false>(fr.rw, row_begin, row_end);
-#endif
   if (!px.valid) return;
   constexpr int STEP = 8 >> LEVEL;
   const int x = px.x, y = px.y, index = x + fr.rw * y;
@@ -189,9 +185,7 @@ __global__ __launch_bounds__(256, HK_DENOISE_WAVES) void k_denoise(DFrame fr, De
     }
     const float lum = luminance(irradiance);
     const float lum_denominator = 4.0f * pow_quarter_(variance) + 0.001f;  // luminance_weight, denoise.wgsl:56-61
-#ifndef HK_DN_F32_DIV
     const double inv_lum_denominator = 1.0 / (double)lum_denominator;  // the eight taps of a channel divide by the same number: see quotient_by_reciprocal
-#endif
     uint2 tap[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) tap[k] = tap_inside[k] ? d.input[ch][index + OX[k] * STEP + fr.rw * (OY[k] * STEP)] : make_uint2(0u, 0u);
@@ -206,9 +200,6 @@ __global__ __launch_bounds__(256, HK_DENOISE_WAVES) void k_denoise(DFrame fr, De
     bool black = (centre.x | (centre.y & 0xFFFFu)) == 0u && lum_denominator == lum_denominator;
 #pragma unroll
     for (int k = 0; k < 8; ++k) black = black && (tap[k].x | (tap[k].y & 0xFFFFu)) == 0u;
-#if defined(HK_DN_F32_DIV) || defined(HK_DN_NO_BLACK)
-    black = false;
-#endif
     if (__ballot(!black) == 0ull) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
@@ -225,11 +216,7 @@ __global__ __launch_bounds__(256, HK_DENOISE_WAVES) void k_denoise(DFrame fr, De
         const f3 irr = xyz(unpack_f16x4(tap[k]));
         if (nan_or_above_max(irr)) continue;  // any_is_nan(irr) || any(irr > F32_MAX)
         const float sample_luminance = luminance(irr);
-#ifdef HK_DN_F32_DIV
-        const float w_luminance = exp_nonpositive_((-fabsf(lum - sample_luminance)) / lum_denominator);
-#else
         const float w_luminance = exp_nonpositive_(quotient_by_reciprocal(-fabsf(lum - sample_luminance), inv_lum_denominator));
-#endif
         const float w = clamp_(w_geometry[k] * w_luminance, 0.0f, 1.0f) * fr.kernel[(OY[k] + 1) * 3 + (OX[k] + 1)];
         sum_irradiance = sum_irradiance + irr * w;
         sum_w += w;
@@ -290,11 +277,7 @@ void launch_demodulation(hipStream_t st, int nch, const DFrame& fr, const DemodT
 
 template <int LEVEL>
 static void launch_denoise_level(hipStream_t st, int nch, int ffmask, const DFrame& fr, const DenoiseTargets& d, int y0, int y1) {
-#if defined(HK_DENOISE_TILES_RR)
-  dim3 grid = grid_for(fr.rw, y1 - y0);
-#else
   dim3 grid = grid_for_rows(HK_DENOISE_W, fr.rw, y1 - y0);
-#endif
   if (nch == 1 && ffmask == 0) hipLaunchKernelGGL((k_denoise<LEVEL, 1, 0>), grid, dim3(256), 0, st, fr, d, y0, y1);
   else if (nch == 1) hipLaunchKernelGGL((k_denoise<LEVEL, 1, 1>), grid, dim3(256), 0, st, fr, d, y0, y1);
   else if (nch == 2) hipLaunchKernelGGL((k_denoise<LEVEL, 2, 2>), grid, dim3(256), 0, st, fr, d, y0, y1);  // sun, emissive

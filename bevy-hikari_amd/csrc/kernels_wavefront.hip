@@ -520,7 +520,7 @@ __global__ __launch_bounds__(256) void k_build_wide(const float4* __restrict__ n
                              // (4 x 35 KB with a 32-entry LDS stack: indirect pass +2.4 % / +6 %, profiles/r04_wide_share_ab.txt)
 #endif
 // k_wf_trace with the wide walk: the same queue, the same refill, the same three phases - a NODE step is one record.
-// Work sharing inside a wave (round 4, HK_WF_WIDE_SHARE): tools/wf_timeline.py shows a trace stage ending with 0.5-1.1 ms in which
+// Work sharing inside a wave (round 4): tools/wf_timeline.py shows a trace stage ending with 0.5-1.1 ms in which
 // the queue is dry and a few long walks finish - 200-500 records at 3-6 us each - while the other lanes of their waves idle.  What a
 // walk still has to do sits on its stack as INDEPENDENT subtrees, and the bottom entry is the farthest (largest, last to be
 // visited) of them.  Once the wave can no longer be refilled, every idle lane takes the bottom entry of a busy lane's stack and
@@ -531,22 +531,13 @@ __global__ __launch_bounds__(256) void k_build_wide(const float4* __restrict__ n
 // neither on who walked what nor on timing; an any-hit ray is occluded iff any piece found an occluder.  Handed over: the bottom
 // of the lane's instance-tree entries (below its WIDE_LEAVE marker, or its whole stack outside a mesh tree), else the bottom entry
 // of the mesh tree it is in (a tombstone stays); the walk's context - ray, local ray, closest distance, 22 dwords - travels through
-// the TAKER's unused stack column.  A dry wave also serves every parked lane every turn (HK_WF_DRY_ALL_PHASES): with many lanes of
+// the TAKER's unused stack column.  A dry wave also serves every parked lane every turn: with many lanes of
 // a wave at work again, waiting a turn for one's phase is what makes the stage longer.  profiles/r04_wide_share_ab.txt.
-#ifndef HK_WF_WIDE_SHARE
-#define HK_WF_WIDE_SHARE 1
-#endif
-#ifndef HK_WF_DRY_ALL_PHASES
-#define HK_WF_DRY_ALL_PHASES 1
-#endif
 // The wide trace kernel hands its queue out in a permuted order (round 5): what ends a stage is the waves whose blocks of 64 rays
 // happened to be expensive, and a block of consecutive entries is one small region of the image.  Runs of 2^HK_WF_QUEUE_RUN
 // consecutive entries stay together (neighbouring pixels: coherent rays).  Config 3 (4 stages of 0.2-1.4 M rays: four blocks per
 // wave) indirect pass 3.67 -> 3.56 ms, frame 6.51 -> 6.43; config 4 (up to 5 M rays per stage: the law of large numbers already
 // balances) unchanged with runs of 16, +1 % / +4 % with runs of 4 / 1 - coherence matters there (profiles/r05_interleave_ab.txt).
-#ifndef HK_WF_QUEUE_INTERLEAVE
-#define HK_WF_QUEUE_INTERLEAVE 1
-#endif
 #ifndef HK_WF_QUEUE_RUN
 #define HK_WF_QUEUE_RUN 4      // log2 of the run of consecutive queue entries the permutation keeps together
 #endif
@@ -556,22 +547,7 @@ __global__ __launch_bounds__(256) void k_build_wide(const float4* __restrict__ n
 #ifndef HK_WF_SHARE_STEPS
 #define HK_WF_SHARE_STEPS 8u  // ... and records a lane must have visited for its piece before it does: only the long walks end a stage
 #endif
-namespace {
-template <bool PATHS>
-__device__ __forceinline__ void shade_bounce(const DScene& sc, const DFrame& fr, const WfBuffers& w, uint32_t slot, uint32_t n, bool& want_shadow, bool& want_next);  // (below, with k_wf_shade)
-}
-enum : uint32_t { PH_WAIT = 4u, PH_HELPED = 5u, PH_READY = 6u };  // a root whose helpers are still out / a helper whose piece is done (merged at the next turn) / PATHS: a closest hit found, the path goes to the wave's shading list at the next turn
-// PATHS: a queue entry = slot | bounce << 26 | WF_SHADOW
-constexpr uint32_t WF_SLOT_BITS = 26u, WF_SLOT_MASK = (1u << WF_SLOT_BITS) - 1u, WF_BOUNCE_MASK = 31u;
-#ifndef HK_WF_PATHS_SHADE_EARLY
-#define HK_WF_PATHS_SHADE_EARLY 48u  // PATHS: paths waiting for shading from which on a wave shades them rather than take new paths from the global queue
-#endif
-#ifndef HK_WF_PATHS_BLOCK
-#define HK_WF_PATHS_BLOCK 64u       // PATHS: paths a wave reserves at a time (the staged stages reserve 256 rays until near the end)
-#endif
-#ifndef HK_WF_PATHS_SHADE_MIN
-#define HK_WF_PATHS_SHADE_MIN 16u  // PATHS, a dry wave: paths that must wait for shading before the wave shades them (or as many as half its working lanes)
-#endif
+enum : uint32_t { PH_WAIT = 4u, PH_HELPED = 5u };  // a root whose helpers are still out / a helper whose piece is done (merged at the next turn)
 __device__ __forceinline__ uint32_t lane_u32(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
 
 // TL: the instrumented twin, as for k_wf_trace - tools/wf_timeline.py.  COUNT (round 5; HK_CTX_COUNT_WALKS): the COUNTING twin of
@@ -580,25 +556,9 @@ __device__ __forceinline__ uint32_t lane_u32(uint32_t v, int lane) { return (uin
 // wave in, queue first seen dry, last wave out) from which bench.py takes the stage's tail fraction.  The product launches
 // <false, false>; the three differ in bookkeeping only: a ray's walk and result are the same.
 //
-// PATHS (round 6): EVERY bounce of the dispatch in this one launch - `stage` is not read.  The global
-// queue holds the paths themselves (bounce 0's closest-hit rays, k_wf_setup's slots); a wave that claims a path keeps it to its end:
-// when the closest hit of bounce n is found the path goes to the wave's own SHADING list, the wave shades 64 of them at a time with all
-// its lanes (shade_bounce<true>: the same code the staged schedule's k_wf_shade runs), and the rays that emits - the shadow ray of
-// bounce n, the closest-hit ray of bounce n + 1 - go to the wave's own RAY list, which idle lanes are refilled from before they take
-// new paths.  Both lists are the wave's private memory (WfBuffers::local), every plane of a path is written and read by ONE wave, in
-// program order: no hand-off between workgroups, no flag, no fence, nothing to wait for - and so nothing that could hang.  What this
-// buys: a stage's end (the queue dry, a few long walks left: 42-70 % of a stage's time on configs 3 / 4) exists once per
-// dispatch instead of once per bounce, the walks of bounce n + 1 start while those of bounce n are still out, a shadow ray is off
-// its path's chain (nothing waits for its outcome before k_wf_final), and the dispatch is three launches instead of 2 x bounces + 3.
-// A ray's walk, a bounce's arithmetic and the order of a path's additions are the staged schedule's: the same bytes in every buffer
-// (tests/test_parity_schedules_gpu.py).  The shadow ray's RECORD (sr0 / sr1 / sr2) stays one per path: the ray list is first in,
-// first out and bounce n's shadow ray enters it before bounce n + 1's closest-hit ray, so its walk has begun (the record is in
-// registers) before bounce n + 1 can be shaded; its RESULT has a plane per bounce.
-#ifndef HK_WF_PATHS_WAVES
-#define HK_WF_PATHS_WAVES 4  // waves per SIMD the PATHS instantiation is compiled for: the shading needs 116 VGPRs on its own, the walk 93 - at five waves
-                             // (96) 113 are spilled and the dispatch is 1.33x the staged one; the shading as a CALL (the walk saved around it, the kernel's
-                             // arguments read from its argument segment by the callee) 1.17-1.20x; four waves (128, 22 spilled) 1.04-1.10x (profiles/r06_persistent_paths_ab.json)
-#endif
+// One launch per trace stage (launch_indirect_wavefront): bounce n's closest-hit rays and bounce n - 1's shadow rays are one queue,
+// and the stage ends when its last walk does.  A persistent form that ran every bounce of the dispatch in one launch, each path
+// kept by one wave from its first ray to its last, was no faster than the stages and was retired (profiles/r06_persistent_paths_ab.json).
 struct WideTraceArgs {
   DScene sc;
   DFrame fr;
@@ -606,10 +566,9 @@ struct WideTraceArgs {
   WideTrees wt;
   uint32_t stage;
 };
-template <bool TL, bool COUNT, bool PATHS>
-__global__ __launch_bounds__(256, (PATHS ? HK_WF_PATHS_WAVES : HK_WF_WIDE_WAVES)) void k_wf_trace_wide(const WideTraceArgs args) {
+template <bool TL, bool COUNT>
+__global__ __launch_bounds__(256, HK_WF_WIDE_WAVES) void k_wf_trace_wide(const WideTraceArgs args) {
   const DScene& sc = args.sc;
-  const DFrame& fr = args.fr;
   const WfBuffers& w = args.w;
   const WideTrees& wt = args.wt;
   uint32_t stage = args.stage;
@@ -629,22 +588,12 @@ __global__ __launch_bounds__(256, (PATHS ? HK_WF_PATHS_WAVES : HK_WF_WIDE_WAVES)
     if ((threadIdx.x & 63u) == 0u) atomicMax(&w.timeline[32u * stage + 0u], ~tl_start);
   }
   WideStackSpill stack{stack_lds, wt.spill, (size_t)gridDim.x * 256u, (size_t)blockIdx.x * 256u + threadIdx.x, wt.lost};
-  if (PATHS) stage = 0u;
-  const uint32_t n_alive = w.ctr[WF_ALIVE + stage], q_count = PATHS ? n_alive : n_alive + w.ctr[WF_SHADOWS + stage];
-  // PATHS: the wave's own lists, rings of 512 (positions count up, taken mod 512).  The ray list holds at most 256 (shading needs room
-  // for 128), the shading list at most 63 + the 192 closest hits that can come in while the ray list drains from 256 to 128
-  uint32_t* const rayq = PATHS ? w.local + ((size_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * 1024u : nullptr;
-  uint32_t* const shadeq = PATHS ? rayq + 512u : nullptr;
-  uint32_t rq_head = 0u, rq_count = 0u, sq_head = 0u, sq_count = 0u;
-#if HK_WF_QUEUE_INTERLEAVE
+  const uint32_t n_alive = w.ctr[WF_ALIVE + stage], q_count = n_alive + w.ctr[WF_SHADOWS + stage];
   // the queue is handed out in a PERMUTED order: runs of 8 consecutive entries (neighbouring pixels: coherent rays) from places a
   // large odd stride apart, so that a wave's block of 64 samples eight regions of the image instead of one - the cost of a block
   // depends on where it lies (sky edge, dense geometry), and what ends a stage is the waves with an expensive draw
   const uint32_t q_chunks = (q_count + ((1u << HK_WF_QUEUE_RUN) - 1u)) >> HK_WF_QUEUE_RUN, tail = q_chunks << HK_WF_QUEUE_RUN;
   const uint32_t q_stride = (q_chunks % 7919u) ? 7919u : 7907u;  // coprime with q_chunks: chunk j -> (j x stride) mod chunks is a bijection
-#else
-  const uint32_t tail = q_count;
-#endif
   const uint32_t* __restrict__ alive = w.alive[stage & 1u];
   const uint32_t* __restrict__ shadow = w.shadow[stage & 1u];
   uint32_t* head_ptr = &w.ctr[WF_QHEAD + stage];
@@ -664,7 +613,7 @@ __global__ __launch_bounds__(256, (PATHS ? HK_WF_PATHS_WAVES : HK_WF_WIDE_WAVES)
   WideWalk k;
   wide_begin(k, wt, F3(0, 0, 0), F3(1, 1, 1), 0.0f, 0.0f, HK_DONT_EXCLUDE);
   auto begin_ray = [&](uint32_t id, float bound) {  // the ray of queue entry `id`, from its planes
-    const uint32_t slot = PATHS ? id & WF_SLOT_MASK : id & ~WF_SHADOW;
+    const uint32_t slot = id & ~WF_SHADOW;
     if (id & WF_SHADOW) {
       const float4 a = w.sr0[slot], b4 = w.sr1[slot];
       wide_begin(k, wt, F3(a.x, a.y, a.z), F3(b4.x, b4.y, b4.z), fminf(a.w, bound), b4.w, w.sr2[slot]);
@@ -674,15 +623,13 @@ __global__ __launch_bounds__(256, (PATHS ? HK_WF_PATHS_WAVES : HK_WF_WIDE_WAVES)
     }
   };
   auto write_result = [&]() -> uint32_t {  // (root) the ray is done: its result goes to the slot; returns the lane's next phase
-    const uint32_t slot = PATHS ? entry_id & WF_SLOT_MASK : entry_id & ~WF_SHADOW;
+    const uint32_t slot = entry_id & ~WF_SHADOW;
     if (entry_id & WF_SHADOW) {
-      if (PATHS) w.pb_sh[(size_t)((entry_id >> WF_SLOT_BITS) & WF_BOUNCE_MASK) * w.cap + slot] = k.hit.instance_index;
-      else w.sh[slot] = k.hit.instance_index;
+      w.sh[slot] = k.hit.instance_index;
     } else {
       w.ch0[slot] = make_float4(k.hit.distance, k.hit.uv.x, k.hit.uv.y, u2f(k.hit.primitive_index));
       w.ch1[slot] = k.hit.instance_index;
       if (COUNT) cn.hits += k.hit.instance_index != HK_U32_MAX ? 1u : 0u;
-      if (PATHS) return PH_READY;
     }
     return PH_IDLE;
   };
@@ -712,7 +659,6 @@ __global__ __launch_bounds__(256, (PATHS ? HK_WF_PATHS_WAVES : HK_WF_WIDE_WAVES)
     }
   };
   for (;;) {
-#if HK_WF_WIDE_SHARE
     // helpers whose piece ended since the last turn: their hits go to their roots (one at a time: the wave runs in lock step,
     // so a root's registers can be written from here)
     for (unsigned long long done = __ballot(phase == PH_HELPED); done != 0ull; done &= done - 1ull) {
@@ -738,77 +684,23 @@ __global__ __launch_bounds__(256, (PATHS ? HK_WF_PATHS_WAVES : HK_WF_WIDE_WAVES)
     }
     if (phase == PH_HELPED) phase = PH_IDLE;
     if (phase == PH_WAIT && share_help[threadIdx.x] == 0u) phase = write_result();
-#endif
-    if (PATHS) {  // closest hits found since the last turn: their paths wait for shading
-      const unsigned long long ready = __ballot(phase == PH_READY);
-      if (ready != 0ull) {
-        if (phase == PH_READY) {
-          shadeq[(sq_head + sq_count + lane_rank(ready)) & 511u] = entry_id;
-          phase = PH_IDLE;
-        }
-        sq_count += (uint32_t)__popcll(ready);
-      }
-      // Shade: 64 paths with all 64 lanes (a lane in the middle of a walk keeps its walk in its registers and takes a turn at shading
-      // like the others) as soon as 64 wait and the ray list has room for what they may emit; a wave with no other source of rays left
-      // shades what it has once that is worth stopping its working lanes for.
-      const uint32_t n_working = 64u - (uint32_t)__popcll(__ballot(phase == PH_IDLE));
-      const bool starving = exhausted && res_count == 0u && rq_count == 0u;
-      // (... and BEFORE it takes new paths from the global queue for its idle lanes: a wave that hoards paths - 64 walking, 63 waiting for
-      // shading, 128 rays listed - leaves nothing for the queue to balance: 5 120 waves x 250 paths is a whole 1080p frame)
-      const uint32_t n_idle_now = 64u - n_working;
-      const bool would_claim = n_idle_now >= HK_WF_REFILL_MIN && rq_count < n_idle_now;
-      const bool shade_now = sq_count >= 64u ? rq_count <= 128u
-                                             : ((would_claim && sq_count >= HK_WF_PATHS_SHADE_EARLY) ||
-                                                (starving && sq_count != 0u && (sq_count >= HK_WF_PATHS_SHADE_MIN || n_working <= 2u * sq_count)));
-      if (shade_now) {
-        const uint32_t batch = min(sq_count, 64u);
-        bool want_shadow = false, want_next = false;
-        uint32_t e = 0u;
-        if (lane < batch) {
-          e = shadeq[(sq_head + lane) & 511u];
-          shade_bounce<true>(sc, fr, w, e & WF_SLOT_MASK, (e >> WF_SLOT_BITS) & WF_BOUNCE_MASK, want_shadow, want_next);
-        }
-        sq_head += batch;
-        sq_count -= batch;
-        // (first in, first out, and a bounce's shadow ray ahead of the next bounce's closest-hit ray: see the header)
-        const unsigned long long ms = __ballot(want_shadow), mn = __ballot(want_next);
-        if (want_shadow) rayq[(rq_head + rq_count + lane_rank(ms)) & 511u] = e | WF_SHADOW;
-        rq_count += (uint32_t)__popcll(ms);
-        if (want_next) rayq[(rq_head + rq_count + lane_rank(mn)) & 511u] = e + (1u << WF_SLOT_BITS);
-        rq_count += (uint32_t)__popcll(mn);
-      }
-    }
     const unsigned long long idle_mask = __ballot(phase == PH_IDLE);
     const uint32_t n_idle = (uint32_t)__popcll(idle_mask);
-    const bool dry = exhausted && res_count == 0u && (!PATHS || rq_count == 0u);
+    const bool dry = exhausted && res_count == 0u;
     if ((TL || COUNT) && exhausted && !tl_seen_dry) {
       tl_seen_dry = true;
       if ((threadIdx.x & 63u) == 0u) atomicMax(&w.timeline[32u * stage + 1u], ~wall_clock64());
     }
-    if (dry && n_idle == 64u && (!PATHS || sq_count == 0u)) break;
+    if (dry && n_idle == 64u) break;
     if (!dry && (n_idle >= HK_WF_REFILL_MIN || n_idle == 64u)) {
       const bool idle = phase == PH_IDLE;
-      uint32_t rank = lane_rank(idle_mask);
+      const uint32_t rank = lane_rank(idle_mask);
       uint32_t mine = HK_U32_MAX;
       uint32_t given = 0u;
-      uint32_t n_idle_q = n_idle;  // idle lanes the global queue is asked for
-      bool local_ray = false;
-      if (PATHS) {  // the wave's own rays first
-        const uint32_t take = min(n_idle, rq_count);
-        if (idle && rank < take) {
-          entry_id = rayq[(rq_head + rank) & 511u];
-          local_ray = true;
-        }
-        rq_head += take;
-        rq_count -= take;
-        n_idle_q = n_idle - take;
-        rank -= take;  // (wraps for the lanes served above: they ask the global queue for nothing)
-      }
-      const bool ask = idle && !local_ray;
-      if (res_count < n_idle_q && !exhausted) {
+      if (res_count < n_idle && !exhausted) {
         given = res_count;
-        if (ask && rank < given) mine = res_base + rank;
-        const uint32_t block = PATHS ? HK_WF_PATHS_BLOCK : ((res_base + given + 4u * all_lanes < tail) ? 256u : HK_WF_BLOCK_SMALL);
+        if (idle && rank < given) mine = res_base + rank;
+        const uint32_t block = (res_base + given + 4u * all_lanes < tail) ? 256u : HK_WF_BLOCK_SMALL;
         uint32_t b = 0u;
         if ((threadIdx.x & 63u) == 0u) b = atomicAdd(head_ptr, block);
         b = __builtin_amdgcn_readfirstlane(b);
@@ -816,19 +708,17 @@ __global__ __launch_bounds__(256, (PATHS ? HK_WF_PATHS_WAVES : HK_WF_WIDE_WAVES)
         res_count = b < tail ? min(block, tail - b) : 0u;
         if (b + block >= tail) exhausted = true;
       }
-      if (ask && rank >= given && rank - given < res_count) mine = res_base + (rank - given);
-      const uint32_t used = min(n_idle_q - given, res_count);
+      if (idle && rank >= given && rank - given < res_count) mine = res_base + (rank - given);
+      const uint32_t used = min(n_idle - given, res_count);
       res_base += used;
       res_count -= used;
-#if HK_WF_QUEUE_INTERLEAVE
       if (mine != HK_U32_MAX) {
         const uint32_t chunk = (uint32_t)(((unsigned long long)(mine >> HK_WF_QUEUE_RUN) * q_stride) % q_chunks);
         mine = (chunk << HK_WF_QUEUE_RUN) | (mine & ((1u << HK_WF_QUEUE_RUN) - 1u));
         if (mine >= q_count) mine = HK_U32_MAX;  // (the padding of the last run)
       }
-#endif
-      if (mine != HK_U32_MAX || local_ray) {
-        if (!local_ray) entry_id = PATHS ? mine : (mine < n_alive ? alive[mine] : (shadow[mine - n_alive] | WF_SHADOW));  // (PATHS: bounce 0 of path `mine`, k_wf_setup's slots are their own list)
+      if (mine != HK_U32_MAX) {
+        entry_id = mine < n_alive ? alive[mine] : (shadow[mine - n_alive] | WF_SHADOW);
         begin_ray(entry_id, HK_F32_MAX);
         if (COUNT) {
           cn.tlas += 1u;
@@ -841,7 +731,6 @@ __global__ __launch_bounds__(256, (PATHS ? HK_WF_PATHS_WAVES : HK_WF_WIDE_WAVES)
         if (TL) tl_claimed = (uint32_t)(wall_clock64() - tl_start);
       }
     }
-#if HK_WF_WIDE_SHARE
     if (dry && n_idle >= HK_WF_SHARE_MIN) {
       // who can give: a lane at work with a pending entry that is nobody's current business - the bottom of its instance-tree
       // entries (the farthest, largest subtree), else, inside a mesh tree, the bottom of that tree's entries
@@ -930,18 +819,15 @@ __global__ __launch_bounds__(256, (PATHS ? HK_WF_PATHS_WAVES : HK_WF_WIDE_WAVES)
         }
       }
     }
-#endif
     const uint32_t n_node = (uint32_t)__popcll(__ballot(phase == PH_NODE));
     const uint32_t n_tri = (uint32_t)__popcll(__ballot(phase == PH_TRI));
     const uint32_t n_entry = (uint32_t)__popcll(__ballot(phase == PH_ENTRY));
     // While the queue lasts the phase with the most lanes waiting runs (lane utilisation: an idle lane is refilled).  Once the wave
-    // is dry every parked lane is served every turn: what is left are the walks that end the stage, and (HK_WF_WIDE_SHARE) the
+    // is dry every parked lane is served every turn: what is left are the walks that end the stage, and the
     // lanes that help them - a lane that waits a turn for its phase makes the stage a turn longer.
-    const bool all_phases = HK_WF_DRY_ALL_PHASES && dry;
+    const bool all_phases = dry;
     if (all_phases ? n_node != 0u : (n_node >= n_tri && n_node >= n_entry && n_node != 0u)) {
-#if HK_WF_WIDE_SHARE
       if (dry) k.limit = u2f(share_best[(threadIdx.x & ~63u) + root]);  // (what the other pieces of the ray have found meanwhile)
-#endif
 #pragma unroll 1
       for (int s = 0; s < HK_WIDE_STEPS; ++s) {
         if (phase == PH_NODE) {
@@ -957,9 +843,7 @@ __global__ __launch_bounds__(256, (PATHS ? HK_WF_PATHS_WAVES : HK_WF_WIDE_WAVES)
         const float before = k.hit.distance;
         if (COUNT) cn.tris += 1u;
         phase = wide_triangle(k, sc, wt, pending);
-#if HK_WF_WIDE_SHARE
         if (dry && k.hit.distance < before) atomicMin(&share_best[(threadIdx.x & ~63u) + root], f2u(k.hit.distance));  // (distances are >= 0: their bits order like they do)
-#endif
         if (phase == PH_IDLE) finish();
       }
     }
@@ -1012,10 +896,7 @@ __global__ __launch_bounds__(256, (PATHS ? HK_WF_PATHS_WAVES : HK_WF_WIDE_WAVES)
 #endif
 namespace {
 // Bounce `n` of the path in `slot`, from its closest hit on: light.wgsl:1313-1394, one iteration (bounce_step of kernels.hip).
-// PATHS = false, the staged schedule: the shadow ray of bounce n - 1 has been traced by the stage before, its outcome is added first.
-// PATHS = true, k_wf_paths: nothing here waits for a shadow ray - the two outcomes of bounce n's go to the planes OF THAT BOUNCE
-// (WfBuffers::pb_add), the bounce's bit to the path's pending mask, and k_wf_final<true> adds what the walks selected, in bounce order.
-template <bool PATHS>
+// The shadow ray of bounce n - 1 has been traced by the stage before, its outcome is added first.
 __device__ __forceinline__ void shade_bounce(const DScene& sc, const DFrame& fr, const WfBuffers& w, uint32_t slot, uint32_t n, bool& want_shadow, bool& want_next) {
   RayCounters rc{0, 0};
   f4 random = F4(plane(w, PL_RANDOM)[slot]);
@@ -1027,10 +908,9 @@ __device__ __forceinline__ void shade_bounce(const DScene& sc, const DFrame& fr,
   f4 radiance = F4(0.0f, 0.0f, 0.0f, 0.0f);
   if (n != 0u) {
     transport = xyz(F4(plane(w, PL_TRANSPORT)[slot]));
-    if (!PATHS) radiance = F4(plane(w, PL_RADIANCE)[slot]);
+    radiance = F4(plane(w, PL_RADIANCE)[slot]);
   }
-  uint32_t mask = PATHS ? f2u(np.w) : 0u;  // PATHS: bit k = bounce k has a shadow ray out, bit 31 = the path left the scene (its sky term: PL_RADIANCE)
-  if (!PATHS && np.w != 0.0f) {  // the shadow ray of bounce n - 1 has been traced by now: add the outcome it selected
+  if (np.w != 0.0f) {  // the shadow ray of bounce n - 1 has been traced by now: add the outcome it selected
     const float4 add = (w.sh[slot] != HK_U32_MAX) ? plane(w, PL_ADD_OCCLUDED)[slot] : plane(w, PL_ADD_CLEAR)[slot];
     radiance = radiance + F4(add.x, add.y, add.z, 1.0f);
   }
@@ -1082,12 +962,9 @@ __device__ __forceinline__ void shade_bounce(const DScene& sc, const DFrame& fr,
         if (out_luminance > fr.max_indirect_luminance) out_radiance = out_radiance * fr.max_indirect_luminance / out_luminance;
         add[o] = transport * out_radiance;
       }
-      float4* add_clear = PATHS ? w.pb_add + (size_t)(2u * n) * w.cap : plane(w, PL_ADD_CLEAR);
-      float4* add_occluded = PATHS ? w.pb_add + (size_t)(2u * n + 1u) * w.cap : plane(w, PL_ADD_OCCLUDED);
-      add_clear[slot] = make_float4(add[0].x, add[0].y, add[0].z, 0.0f);
-      add_occluded[slot] = make_float4(add[1].x, add[1].y, add[1].z, 0.0f);
+      plane(w, PL_ADD_CLEAR)[slot] = make_float4(add[0].x, add[0].y, add[0].z, 0.0f);
+      plane(w, PL_ADD_OCCLUDED)[slot] = make_float4(add[1].x, add[1].y, add[1].z, 0.0f);
       pending = 1.0f;
-      mask |= 1u << n;
       want_shadow = true;
     }
     transport = transport * env_brdf(bounce_view_direction, sample_normal, surface);
@@ -1099,18 +976,13 @@ __device__ __forceinline__ void shade_bounce(const DScene& sc, const DFrame& fr,
     if (want_next) emit_bounce_ray(w, slot, random, position, normal);
   } else {
     const f3 out_radiance = xyz(input_radiance(sc, fr, ray, info, false, HK_DONT_SAMPLE_EMISSIVE, true));
-    if (PATHS) {  // (the last addition of the path: after every shadow ray's outcome - k_wf_final<true>)
-      radiance = F4(transport * out_radiance, 0.0f);
-      mask |= 0x80000000u;
-    } else {
-      radiance = radiance + F4(transport * out_radiance, 0.0f);
-    }
+    radiance = radiance + F4(transport * out_radiance, 0.0f);
   }
   plane(w, PL_RANDOM)[slot] = to_float4(random);
   plane(w, PL_POSITION_PDF)[slot] = make_float4(position.x, position.y, position.z, pdf);
-  plane(w, PL_NORMAL_PENDING)[slot] = make_float4(normal.x, normal.y, normal.z, PATHS ? u2f(mask) : pending);
+  plane(w, PL_NORMAL_PENDING)[slot] = make_float4(normal.x, normal.y, normal.z, pending);
   plane(w, PL_TRANSPORT)[slot] = make_float4(transport.x, transport.y, transport.z, 0.0f);
-  if (!PATHS || (mask & 0x80000000u)) plane(w, PL_RADIANCE)[slot] = to_float4(radiance);
+  plane(w, PL_RADIANCE)[slot] = to_float4(radiance);
 }
 }  // namespace
 template <bool LDS>
@@ -1128,7 +1000,7 @@ __global__ __launch_bounds__(256, HK_WF_SHADE_WAVES) void k_wf_shade(DScene gsc,
     uint32_t slot = 0u;
     if (valid) {
       slot = alive_in[i];
-      shade_bounce<false>(sc, fr, w, slot, n, want_shadow, want_next);
+      shade_bounce(sc, fr, w, slot, n, want_shadow, want_next);
     }
     // survivors and shadow rays of the next trace stage: one atomic per workgroup and list
     const uint32_t a = block_push(&w.ctr[WF_ALIVE + n + 1u], want_next, push_lds);
@@ -1139,7 +1011,6 @@ __global__ __launch_bounds__(256, HK_WF_SHADE_WAVES) void k_wf_shade(DScene gsc,
 }
 
 // ------------------------------------------------------------------ final: last shadow result + the temporal-reuse tail
-template <bool PATHS>
 __global__ __launch_bounds__(256, 4) void k_wf_final(DScene sc, DFrame fr, GBuffer g, LightTargets t, WfBuffers w) {
   const uint32_t count = w.ctr[WF_ALIVE];
   for (uint32_t slot = blockIdx.x * 256u + threadIdx.x; slot < count; slot += gridDim.x * 256u) {
@@ -1161,21 +1032,10 @@ __global__ __launch_bounds__(256, 4) void k_wf_final(DScene sc, DFrame fr, GBuff
     s.visible_position = F4(position, position_depth.w);
     s.visible_normal = normalize(xyz(unpack4x8snorm(g.normal[didx])));
     s.visible_instance = im_x;
-    f4 radiance = F4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (PATHS) {  // the path's additions in bounce order (shade_bounce<true>): what each bounce's shadow ray selected, then the sky term if it left the scene
-      const uint32_t mask = f2u(plane(w, PL_NORMAL_PENDING)[slot].w);
-      for (uint32_t m = mask & 0x7FFFFFFFu; m != 0u; m &= m - 1u) {
-        const uint32_t n = (uint32_t)__ffs((int)m) - 1u;
-        const float4 add = w.pb_add[(size_t)(2u * n + (w.pb_sh[(size_t)n * w.cap + slot] != HK_U32_MAX ? 1u : 0u)) * w.cap + slot];
-        radiance = radiance + F4(add.x, add.y, add.z, 1.0f);
-      }
-      if (mask & 0x80000000u) radiance = radiance + F4(plane(w, PL_RADIANCE)[slot]);
-    } else {
-      radiance = F4(plane(w, PL_RADIANCE)[slot]);
-      if (plane(w, PL_NORMAL_PENDING)[slot].w != 0.0f) {
-        const float4 add = (w.sh[slot] != HK_U32_MAX) ? plane(w, PL_ADD_OCCLUDED)[slot] : plane(w, PL_ADD_CLEAR)[slot];
-        radiance = radiance + F4(add.x, add.y, add.z, 1.0f);
-      }
+    f4 radiance = F4(plane(w, PL_RADIANCE)[slot]);
+    if (plane(w, PL_NORMAL_PENDING)[slot].w != 0.0f) {
+      const float4 add = (w.sh[slot] != HK_U32_MAX) ? plane(w, PL_ADD_OCCLUDED)[slot] : plane(w, PL_ADD_CLEAR)[slot];
+      radiance = radiance + F4(add.x, add.y, add.z, 1.0f);
     }
     s.radiance = radiance;
     s.sample_position = F4(plane(w, PL_FIRST_POSITION)[slot]);
@@ -1198,7 +1058,7 @@ void launch_build_wide(hipStream_t st, const float4* nodes, uint32_t count, floa
 }
 
 void launch_indirect_wavefront(hipStream_t st, const DScene& sc, const DFrame& fr, const GBuffer& g, const LightTargets& t, const WfBuffers& w, int y0,
-                               int y1, int compute_units, hipEvent_t start, hipEvent_t stop, const WideTrees* wide, hipEvent_t* trace_events, bool persistent) {
+                               int y1, int compute_units, hipEvent_t start, hipEvent_t stop, const WideTrees* wide, hipEvent_t* trace_events) {
   if (y1 <= y0) return;
   (void)hipMemsetAsync(w.ctr, 0, 192 * sizeof(uint32_t), st);
   if (w.timeline) (void)hipMemsetAsync(w.timeline, 0, 64 * 32 * sizeof(unsigned long long), st);
@@ -1213,19 +1073,11 @@ void launch_indirect_wavefront(hipStream_t st, const DScene& sc, const DFrame& f
   const uint32_t bounces = fr.indirect_bounces;
   const bool use_wide = wide && wide->tlas && !lds;
   const uint32_t twin = w.timeline ? w.timeline_mode : 0u;
-  // every bounce in one launch (k_wf_trace_wide<.., PATHS>): the wide walk's scenes, no instrumented twin, the per-bounce planes in place
-  if (persistent && use_wide && twin <= 1u && w.local && bounces >= 1u && w.pb_bounces >= bounces && w.cap <= (1u << 26)) {
-    hipEvent_t e0 = trace_events ? trace_events[0] : nullptr, e1 = trace_events ? trace_events[1] : nullptr;
-    if (twin == 1u) hipExtLaunchKernelGGL((k_wf_trace_wide<true, false, true>), dim3((unsigned)(compute_units * HK_WF_PATHS_WAVES)), dim3(256), 0, st, e0, e1, 0, WideTraceArgs{sc, fr, w, *wide, 0u});
-    else hipExtLaunchKernelGGL((k_wf_trace_wide<false, false, true>), dim3((unsigned)(compute_units * HK_WF_PATHS_WAVES)), dim3(256), 0, st, e0, e1, 0, WideTraceArgs{sc, fr, w, *wide, 0u});
-    hipExtLaunchKernelGGL(k_wf_final<true>, persistent_grid, dim3(256), 0, st, nullptr, stop, 0, sc, fr, g, t, w);
-    return;
-  }
   for (uint32_t n = 0; n <= bounces; ++n) {
     hipEvent_t e0 = trace_events ? trace_events[2u * n] : nullptr, e1 = trace_events ? trace_events[2u * n + 1u] : nullptr;
-    if (use_wide && twin == 1u) hipExtLaunchKernelGGL((k_wf_trace_wide<true, false, false>), wide_tracers, dim3(256), 0, st, e0, e1, 0, WideTraceArgs{sc, fr, w, *wide, n});
-    else if (use_wide && twin == 2u) hipExtLaunchKernelGGL((k_wf_trace_wide<false, true, false>), wide_tracers, dim3(256), 0, st, e0, e1, 0, WideTraceArgs{sc, fr, w, *wide, n});
-    else if (use_wide) hipExtLaunchKernelGGL((k_wf_trace_wide<false, false, false>), wide_tracers, dim3(256), 0, st, e0, e1, 0, WideTraceArgs{sc, fr, w, *wide, n});
+    if (use_wide && twin == 1u) hipExtLaunchKernelGGL((k_wf_trace_wide<true, false>), wide_tracers, dim3(256), 0, st, e0, e1, 0, WideTraceArgs{sc, fr, w, *wide, n});
+    else if (use_wide && twin == 2u) hipExtLaunchKernelGGL((k_wf_trace_wide<false, true>), wide_tracers, dim3(256), 0, st, e0, e1, 0, WideTraceArgs{sc, fr, w, *wide, n});
+    else if (use_wide) hipExtLaunchKernelGGL((k_wf_trace_wide<false, false>), wide_tracers, dim3(256), 0, st, e0, e1, 0, WideTraceArgs{sc, fr, w, *wide, n});
     else if (twin == 1u && !lds) hipExtLaunchKernelGGL((k_wf_trace<false, true>), tracers, dim3(256), 0, st, e0, e1, 0, sc, w, n);
     else if (lds) hipExtLaunchKernelGGL((k_wf_trace<true, false>), tracers, dim3(256), lds, st, e0, e1, 0, sc, w, n);
     else hipExtLaunchKernelGGL((k_wf_trace<false, false>), tracers, dim3(256), 0, st, e0, e1, 0, sc, w, n);
@@ -1233,7 +1085,7 @@ void launch_indirect_wavefront(hipStream_t st, const DScene& sc, const DFrame& f
     if (lds) hipLaunchKernelGGL((k_wf_shade<true>), persistent_grid, dim3(256), lds, st, sc, fr, w, n);
     else hipLaunchKernelGGL((k_wf_shade<false>), persistent_grid, dim3(256), 0, st, sc, fr, w, n);
   }
-  hipExtLaunchKernelGGL(k_wf_final<false>, persistent_grid, dim3(256), 0, st, nullptr, stop, 0, sc, fr, g, t, w);
+  hipExtLaunchKernelGGL(k_wf_final, persistent_grid, dim3(256), 0, st, nullptr, stop, 0, sc, fr, g, t, w);
 }
 
 }  // namespace hk

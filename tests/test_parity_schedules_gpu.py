@@ -193,19 +193,18 @@ def test_windowed_spatial_reuse_changes_no_byte(name):
 def test_the_side_stream_may_lag_a_frame_behind_and_no_bit_changes():
     """Round 6: the main stream no longer waits for the direct-light dispatches (side stream) at the end of a frame - the post-processing
     does, on its own stream; the next frame's primary rays and indirect pass touch nothing they read or write (normal / instance_material
-    planes double-buffered like the rest of the G-buffer).  Against HK_DEBUG_OPT_SIDE_JOIN = 1 (the order of rounds 1-5) and against the
-    single-stream context: Cornell back to back, frames of one parity in a row, stages driven by hand without a post-processing stage, a
-    scene beyond LDS whose instances move through the two-slot upload AND the device refit between frames."""
+    planes double-buffered like the rest of the G-buffer).  Against the single-stream context: Cornell back to back, frames of one parity
+    in a row, stages driven by hand without a post-processing stage, a scene beyond LDS whose instances move through the two-slot upload
+    AND the device refit between frames."""
     from bevy_hikari_amd.scenes import animate, synthetic_camera, synthetic_scene
 
     case = make_case("cornell_b2")
     s, cam = case.settings, case.camera
     view, pview = cam.view_uniform(), cam.previous_view_uniform()
     engines = []
-    for flags, join in ((0, 0), (0, 1), (F.CTX_SINGLE_STREAM, 0)):
+    for flags in (0, F.CTX_SINGLE_STREAM):
         e = hk.Engine(device=0, flags=flags)
         e.upload_noise(); e.upload_scene(case.scene); e.resize(cam.width, cam.height, s.upscale.ratio())
-        e.set_debug_option(F.DEBUG_OPT_SIDE_JOIN, join)
         engines.append(e)
     n = 0
     for step in [1] * 9 + [2, 2, 2] + ["temporal_only"] * 4 + [1, 1, 2, 1]:
@@ -230,10 +229,9 @@ def test_the_side_stream_may_lag_a_frame_behind_and_no_bit_changes():
     s = hk.HikariSettings(indirect_bounces=2, upscale=hk.Upscale.SMAA_TU_1_0, emissive_spatial_reuse=True)
     lights = hk.lights_uniform(directional=sun)
     plugins = []
-    for join in (0, 1):
-        p = hk.HikariPlugin(device=0, flags=F.CTX_DETERMINISTIC_SCATTER if False else 0)
-        p.engine.set_debug_option(F.DEBUG_OPT_SIDE_JOIN, join)
-        p.set_scene(scenes[join])
+    for k, flags in enumerate((0, F.CTX_SINGLE_STREAM)):
+        p = hk.HikariPlugin(device=0, flags=flags)
+        p.set_scene(scenes[k])
         plugins.append(p)
     cur = list(scenes)
     for n in range(1, 11):
@@ -242,7 +240,7 @@ def test_the_side_stream_may_lag_a_frame_behind_and_no_bit_changes():
                 cur[k] = animate(cur[k], n - 1)
                 p.update_instances(cur[k])
             p.render(cam, s, lights=lights, frame_number=n)
-    # (the racing default: the two contexts run the SAME kernels in the same order per stream - what is compared is every rendered plane)
+    # (the racing default: the two contexts run the SAME kernels - what is compared is every rendered plane)
     a, b = snapshot(plugins[0]), snapshot(plugins[1])
     bad = {k: v for k, v in diff_buffers(a, b).items() if not k.startswith("reservoir")}
     assert bad == {}, bad
