@@ -2,7 +2,14 @@
 """Headline benchmark: Mray/s + frame ms on Cornell 1920x1080, 2 indirect bounces, ReSTIR
 (temporal + indirect spatial) on, denoise on, upscale ratio 1.0 (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}] [--blocks B]
+    python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}] [--blocks B] [--full]
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, replays them once to count their rays
+(below), writes --dump-outputs if asked and prints the line.  Everything else the benchmark measures or checks runs with --full
+only: the instrumented block and `roofline`, `frame_latency_ms`, the sustained block, the kernel alone on a single-stream context,
+the counting twin of configs 3 / 4, `extra_configs` (+ `motion`), the in-run HBM / VALU / gather ceilings, the in-run PMC passes
+and `cpu_baseline`.  The --no-* options below leave parts of a --full run out.  --passes, --sustained and --motion run what they
+name with or without --full.
 
 One "step" is one frame of the hot path (prepass rays -> light passes -> ReSTIR -> denoise) over
 synthetic input that is resident in HBM before the timed region.  N > 1 runs one rank per GPU under
@@ -21,18 +28,19 @@ traverse_bottom invocations.  They are counted by replaying the same
 context created with HK_CTX_COUNT_RAYS (the path is deterministic, so the replay traces exactly the
 rays of the timed run) - the timed region itself carries no counters.
 
-Scenes beyond LDS (configs 3, 4; also measured briefly inside the default run: `extra_configs`): `roofline` is the TIMED trace kernel's
+Scenes beyond LDS (configs 3, 4; also measured briefly inside the default --full run: `extra_configs`): `roofline` is the TIMED trace kernel's
 (k_wf_trace_wide) - every trace launch between its own HIP events (HK_TIMING_TRACE_STAGES), its walks counted by its own counting twin
 on a third context (HK_CTX_COUNT_WALKS: same schedule, same walks, same bytes out - `replay_bit_identical` refers to it; the fused
-ray-counting replay, which may resolve an exact tie differently, is `ray_count_replay_bit_identical`) - as algorithmic bytes / HBM
+ray-counting replay, which may resolve an exact tie differently, is `ray_count_replay_bit_identical`; a plain run, which has no twin,
+reports only the latter for these configs) - as algorithmic bytes / HBM
 peak, record fetches / the 128-B gather roof measured in the same run, HBM-side counter bytes / HBM peak, and the fraction of the
 trace time after a stage's queue first runs dry.
 
 --config selects the other BASELINE.json configs on ONE GPU (3: Sponza-class stand-in 1080p 3 bounces;
 4: city-class stand-in 4K 2 bounces; 5: Cornell 4K 8 bounces, both spatial passes, denoise off).  The
-default (2) is the configuration the metric is quoted on; the default single-GPU invocation also measures configs 3 and 5
-briefly after the headline (`extra_configs`, same protocol, fewer frames) and runs a sustained block of >= 3 s of headline
-frames (`sustained`; `value` stays the median of the short blocks).
+default (2) is the configuration the metric is quoted on; the default single-GPU invocation with --full also measures configs 3, 4
+and 5 briefly after the headline (`extra_configs`, same protocol, fewer frames) and runs a sustained block of >= 3 s of headline
+frames (`sustained`; `value` stays the time of the timed blocks).
 """
 import argparse
 import json
@@ -110,7 +118,7 @@ def pmc_traffic_in_run(timeout_s=150):
     # this process is itself being profiled (rocprofv3 exports these to its application): no profiler inside a profiler
     if any(k.startswith(("ROCPROF_", "ROCP_TOOL_", "ROCPROFILER_")) for k in os.environ):
         return None
-    child = [sys.executable, os.path.abspath(__file__), "--config", "2", "--steps", "6", "--warmup", "4", "--blocks", "1", "--no-cpu-baseline", "--no-hbm-probe",
+    child = [sys.executable, os.path.abspath(__file__), "--config", "2", "--steps", "6", "--warmup", "4", "--blocks", "1", "--full", "--no-cpu-baseline", "--no-hbm-probe",
              "--no-extra-configs", "--sustained-seconds", "0", "--no-pmc"]
     per = {}
     try:
@@ -155,7 +163,7 @@ def pmc_traffic_in_run(timeout_s=150):
           for short, v in per.items() if short.startswith("k_") and all(k in v for k in ("SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU", "SQ_THREAD_CYCLES_VALU")) and v["SQ_ACTIVE_INST_VALU"] > 0}
     return {"per_kernel": out, "frame_bytes": frame, "sq": sq,
             "source": "measured in this invocation: rocprofv3 --kernel-trace --pmc FETCH_SIZE, then WRITE_SIZE, then SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU, on "
-                      "three child runs of `bench.py --config 2 --steps 6 --warmup 4`; bytes = 2 x FETCH_SIZE + WRITE_SIZE (gfx950: a 128-B read request is tallied as 64 B), "
+                      "three child runs of `bench.py --config 2 --steps 6 --warmup 4 --full`; bytes = 2 x FETCH_SIZE + WRITE_SIZE (gfx950: a 128-B read request is tallied as 64 B), "
                       "lane utilisation = SQ_THREAD_CYCLES_VALU / (64 x SQ_ACTIVE_INST_VALU); per-launch averages"}
 
 
@@ -183,20 +191,22 @@ def main():
                     "change owner travel (hk_migrate_bands); the split then stays fixed through the timed blocks.  0 = off")
     ap.add_argument("--no-gather", action="store_true", help="--gpus N: leave every band's rows of the tone-mapped image on the GPU that rendered them (default: rank 0 "
                     "collects them every frame, HK_FRAME_GATHER - SURVEY 8e step 7)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-hbm-probe", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline (module docstring); a plain run only times the steps, "
+                    "counts their rays and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
+    ap.add_argument("--no-hbm-probe", action="store_true", help="--full: no in-run HBM / VALU / gather ceilings")
     ap.add_argument("--no-pmc", action="store_true", help="do not collect the HBM-side bytes of the headline's kernels in this invocation (two child runs of a short config-2 bench "
-                    "under rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE after the timed region; default for the plain single-GPU config-2 run); the committed profile "
+                    "under rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE after the timed region; default for the single-GPU config-2 run with --full); the committed profile "
                     "under profiles/ is used instead")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--ctx-flags", type=int, default=0, help="OR-ed into the flags of the timed contexts (64 = HK_CTX_WAVEFRONT, 128 = HK_CTX_FUSED_INDIRECT, 32 = HK_CTX_EXACT_TRAVERSAL, 256 = HK_CTX_NO_WIDE_WALK)")
     ap.add_argument("--no-wide-walk", action="store_true", help="A/B: scenes beyond LDS keep the threaded skip-link walk for closest-hit rays too (HK_CTX_NO_WIDE_WALK)")
     ap.add_argument("--passes", action="store_true", help="also report a per-pass time breakdown (extra untimed frames)")
-    ap.add_argument("--no-extra-configs", action="store_true", help="skip the short config-3 / config-5 measurements of the default run")
+    ap.add_argument("--no-extra-configs", action="store_true", help="skip the short config-3 / 4 / 5 measurements of the default run with --full")
     ap.add_argument("--motion", action="store_true", help="ONLY the frames under motion (tools/motion_bench.py): config 2 with an orbiting camera (two speeds), config 3 with the orbit + "
                     "instances moving through hk_refit_scene_instances - ms per frame with HK_CTX_RACING_SCATTER, in the default (race resolved) and with HK_CTX_DETERMINISTIC_SCATTER, their deviation from each other "
                     "and from the CPU oracle per frame; the default run carries a shorter version of the same in extra_configs['motion']")
-    ap.add_argument("--sustained-seconds", type=float, default=3.0, help="length of the sustained block of the default run (0 = none)")
+    ap.add_argument("--sustained-seconds", type=float, default=3.0, help="length of the sustained block of the default run with --full, or of --sustained (0 = none)")
     ap.add_argument("--sustained", dest="sustained_seconds_forced", action="store_true", help="run the sustained block for any config / rank count")
     args = ap.parse_args()
     if args.no_wide_walk:
@@ -269,10 +279,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    def measure(config, steps, warmup, n_blocks, width=None, height=None, bounces=None, alone=True, passes=False, sustained_s=0.0):
+    def measure(config, steps, warmup, n_blocks, width=None, height=None, bounces=None, alone=True, passes=False, sustained_s=0.0, full=True):
         """The timed protocol on one BASELINE config: warm-up, EXACTLY `steps` timed frames in n_blocks blocks (barrier + device
-        synchronisation on both sides, max over ranks), an instrumented block after them, the ray count by a deterministic replay, optionally the dominant
-        dispatch alone on the GPU and a sustained block.  Returns a dict; the engines stay alive in it under "_engines"."""
+        synchronisation on both sides, max over ranks) and the ray count by a deterministic replay; `full` adds an instrumented block
+        after them, the frame latency, the indirect pass's walks and the counting twin; optionally the dominant dispatch alone on the GPU
+        and a sustained block.  Returns a dict; the engines stay alive in it under "_engines"."""
         scene, camera, settings, lights, description = workload(hk, config, width, height, bounces)
         W, H = camera.width, camera.height
         sc = settings.to_c()
@@ -358,31 +369,33 @@ def main():
         # They ride on a block of their own AFTER the timed frames: an event on a dispatch is a completion signal the host can observe,
         # and the frame pays for it (presumably the wider release such a dispatch ends with) - measured in one run: 0.942 ms per frame
         # with the two long dispatches instrumented against 0.904 without (round 6).  The roofline figures come from that block.
-        mask = (1 << F.PASS_INDIRECT) | (1 << F.PASS_INDIRECT_SPATIAL_REUSE) | (1 << F.TIMING_TRACE_STAGES)
-        if config in (3, 4):
-            mask |= (1 << F.PASS_DIRECT_LIT) | (1 << F.PASS_DIRECT_EMISSIVE)
-        eng.reset_stats()
-        eng.set_timing_mask(mask)
-        n_instr = min(steps, 48)
-        barrier()
-        t0 = time.perf_counter()
-        run_frames(eng, rend, n0 + 1, n0 + n_instr)
-        eng.wait()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        barrier()
-        instrumented = {"frames": n_instr, "first_frame": n0 + 1, "ms_per_step": round(max_over_ranks(t1 - t0) / n_instr * 1e3, 4)}
-        n0 += n_instr
-        st = eng.stats()
         schedule = eng.indirect_schedule()
         traversal = eng.traversal_mode() + (eng.wide_walk(),)
-        ind_ms = st.pass_ms_total[F.PASS_INDIRECT] / max(1, st.pass_launches[F.PASS_INDIRECT])
-        ind_launches = int(st.pass_launches[F.PASS_INDIRECT])
-        sp_ms = st.pass_ms_total[F.PASS_INDIRECT_SPATIAL_REUSE] / max(1, st.pass_launches[F.PASS_INDIRECT_SPATIAL_REUSE])
-        direct_ms = {F.PASS_NAMES[k]: round(st.pass_ms_total[k] / max(1, st.pass_launches[k]), 5) for k in (F.PASS_DIRECT_LIT, F.PASS_DIRECT_EMISSIVE) if st.pass_launches[k]}
-        trace_launches = int(st.pass_launches[F.TIMING_TRACE_STAGES])
-        trace_ms = st.pass_ms_total[F.TIMING_TRACE_STAGES] / max(1, trace_launches)   # average TRACE launch of the queue-based indirect pass (0 launches: fused schedule)
-        eng.set_timing_mask(0)
+        instrumented, ind_ms, ind_launches, sp_ms, direct_ms, trace_launches, trace_ms = None, 0.0, 0, 0.0, {}, 0, 0.0
+        if full:
+            mask = (1 << F.PASS_INDIRECT) | (1 << F.PASS_INDIRECT_SPATIAL_REUSE) | (1 << F.TIMING_TRACE_STAGES)
+            if config in (3, 4):
+                mask |= (1 << F.PASS_DIRECT_LIT) | (1 << F.PASS_DIRECT_EMISSIVE)
+            eng.reset_stats()
+            eng.set_timing_mask(mask)
+            n_instr = min(steps, 48)
+            barrier()
+            t0 = time.perf_counter()
+            run_frames(eng, rend, n0 + 1, n0 + n_instr)
+            eng.wait()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            barrier()
+            instrumented = {"frames": n_instr, "first_frame": n0 + 1, "ms_per_step": round(max_over_ranks(t1 - t0) / n_instr * 1e3, 4)}
+            n0 += n_instr
+            st = eng.stats()
+            ind_ms = st.pass_ms_total[F.PASS_INDIRECT] / max(1, st.pass_launches[F.PASS_INDIRECT])
+            ind_launches = int(st.pass_launches[F.PASS_INDIRECT])
+            sp_ms = st.pass_ms_total[F.PASS_INDIRECT_SPATIAL_REUSE] / max(1, st.pass_launches[F.PASS_INDIRECT_SPATIAL_REUSE])
+            direct_ms = {F.PASS_NAMES[k]: round(st.pass_ms_total[k] / max(1, st.pass_launches[k]), 5) for k in (F.PASS_DIRECT_LIT, F.PASS_DIRECT_EMISSIVE) if st.pass_launches[k]}
+            trace_launches = int(st.pass_launches[F.TIMING_TRACE_STAGES])
+            trace_ms = st.pass_ms_total[F.TIMING_TRACE_STAGES] / max(1, trace_launches)   # average TRACE launch of the queue-based indirect pass (0 launches: fused schedule)
+            eng.set_timing_mask(0)
 
         # a sustained block of the same frames (>= sustained_s seconds, one barrier-bracketed region): long enough for the
         # driver's GPU-activity sampling and for the clock to settle under load; reported beside `value`, never as `value`
@@ -402,15 +415,17 @@ def main():
         # frame LATENCY: one frame, wait, repeat (the timed blocks keep three streams full - frame n's a-trous levels run beside frame
         # n + 1's light passes - so ms_per_step is a THROUGHPUT figure; this is what one frame takes from its first dispatch to its image).
         # After everything that is compared with the replay: these frames are not part of any count.
-        lat, nl = [], n0 + (sustained["frames"] if sustained else 0)
-        for k in range(min(steps, 16)):
-            barrier()
-            t0 = time.perf_counter()
-            run_frames(eng, rend, nl + 1, nl + 1)
-            eng.wait()
-            lat.append(max_over_ranks(time.perf_counter() - t0))
-            nl += 1
-        frame_latency_ms = float(np.median(lat)) * 1e3
+        frame_latency_ms = None
+        if full:
+            lat, nl = [], n0 + (sustained["frames"] if sustained else 0)
+            for k in range(min(steps, 16)):
+                barrier()
+                t0 = time.perf_counter()
+                run_frames(eng, rend, nl + 1, nl + 1)
+                eng.wait()
+                lat.append(max_over_ranks(time.perf_counter() - t0))
+                nl += 1
+            frame_latency_ms = float(np.median(lat)) * 1e3
 
         # ray count by deterministic replay (one block's worth of frames: the camera is static and the rays per frame are
         # counted over the LAST timed block)
@@ -432,7 +447,7 @@ def main():
         # and for the indirect pass alone (its dispatch repeated once on the last frame's inputs: same rays, same walks)
         walk = {"per_frame": {k: getattr(cst, "walk_" + k) / steps for k in ("node_steps", "triangle_tests", "instance_entries", "closest_hits", "top_node_steps")},
                 "rays_per_frame": (cst.rays_tlas + cst.rays_blas + cst.rays_primary) / steps}
-        if crend is None:
+        if crend is None and full:
             ceng.reset_stats()
             ceng.pass_run(F.PASS_INDIRECT)
             ist = ceng.stats()
@@ -441,7 +456,10 @@ def main():
         del ceng, crend
         # Scenes beyond LDS, product default: what the TIMED trace kernel's walks do, counted by its own counting twin (HK_CTX_COUNT_WALKS:
         # same schedule, same walks, same bytes out) - the same frames once more, then the indirect pass alone on the last frame's inputs
-        if schedule == "wavefront" and traversal[2] and rend is None:
+        if schedule == "wavefront" and traversal[2] and rend is None and not full:
+            # (no counting twin in a plain run: what the fused ray-counting replay reproduced goes under its own name)
+            walk["ray_count_replay_bit_identical"], same = same, None
+        elif schedule == "wavefront" and traversal[2] and rend is None:
             import ctypes as C
 
             weng, _ = make_engine(F.CTX_COUNT_WALKS | args.ctx_flags)
@@ -505,6 +523,20 @@ def main():
         res["_engines"] = (eng, rend)
         return res
 
+    def emit(out):
+        # the JSON line is the LAST thing on stdout: what C libraries (RCCL's start-up banner ...) left in their stdio buffers goes out
+        # first, and whatever they print later goes to stderr
+        import ctypes
+        try:
+            ctypes.CDLL(None).fflush(None)
+        except Exception:
+            pass
+        print(json.dumps(out), flush=True)
+        os.dup2(2, 1)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
     def motion_lines(short):
         """frames under motion + the price of determinism: tools/motion_bench.py"""
         sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -528,16 +560,16 @@ def main():
 
     # ------------------------------------------------------------------ timed run (headline)
     default_run = world == 1 and args.config == 2 and args.width is None and args.height is None and args.bounces is None and not args.ctx_flags
-    m = measure(args.config, args.steps, args.warmup, args.blocks, args.width, args.height, args.bounces, alone=True, passes=args.passes,
-                sustained_s=args.sustained_seconds if default_run or args.sustained_seconds_forced else 0.0)
+    m = measure(args.config, args.steps, args.warmup, args.blocks, args.width, args.height, args.bounces, alone=args.full or args.passes, passes=args.passes,
+                sustained_s=args.sustained_seconds if (args.full and default_run) or args.sustained_seconds_forced else 0.0, full=args.full)
     W, H, blocks, elapsed, last_frame, schedule = m["W"], m["H"], m["blocks"], m["elapsed"], m["last_frame"], m["schedule"]
     if args.dump_outputs and rank == 0:
         os.makedirs(args.dump_outputs, exist_ok=True)
         for name, a in m["outputs"].items():
             np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
-    ind_ms, ind_ms_alone, total_rays, same, description = m["ind_ms"], m["ind_ms_alone"], m["total_rays"], m["same"], m["description"]
+    ind_ms, ind_ms_alone, total_rays, same, description = m["ind_ms"], m.get("ind_ms_alone"), m["total_rays"], m["same"], m["description"]
     passes = m.get("passes")
-    xeng = m["_probe_engine"]
+    xeng = m.get("_probe_engine")
 
     # ------------------------------------------------------------------ the other single-GPU configs, briefly, in the same invocation
     def walk_roofline(x, probe_engine):
@@ -608,7 +640,7 @@ def main():
         return r
 
     extra = None
-    if default_run and not args.no_extra_configs:
+    if args.full and default_run and not args.no_extra_configs:
         extra = {}
         # The headline's timed engine is done: free it before the other configs' engines are created.  A HIP process has few hardware queues
         # per stream priority; with the headline's engines still alive the extra configs' high-priority chains shared one and config 3 read
@@ -648,7 +680,7 @@ def main():
     # ------------------------------------------------------------------ empirical HBM ceiling, same run
     hbm = None
     valu = None
-    if rank == 0 and not args.no_hbm_probe:
+    if args.full and rank == 0 and not args.no_hbm_probe:
         copy_gbs, triad_gbs = xeng.measure_hbm(1 << 30, 8)
         hbm = {"copy_gbs": round(copy_gbs, 1), "triad_gbs": round(triad_gbs, 1), "bytes_per_array": 1 << 30, "guide_copy_gbs": 6290.0,
                "note": "float4 copy (2 x 1 GiB per pass) / triad (3 x 1 GiB per pass), best of three access shapes (grid-stride loop; one-shot with 4 accesses per "
@@ -685,7 +717,8 @@ def main():
             "workload": description,
             "baseline_config": args.config,
             "frames": f"warmup 1..{args.warmup}, then {args.steps} timed frames in {len(blocks)} blocks ({args.warmup + 1}..{last_frame}); ms_per_step = their time / "
-                      f"{args.steps}; the roofline's HIP events ride on frames {m['instrumented']['first_frame']}..{m['instrumented']['first_frame'] + m['instrumented']['frames'] - 1}",
+                      f"{args.steps}" + (f"; the roofline's HIP events ride on frames {m['instrumented']['first_frame']}..{m['instrumented']['first_frame'] + m['instrumented']['frames'] - 1}"
+                                         if args.full else ""),
             "parallelism": f"band{world}" if world > 1 else "single",
             **({"band_split": ("measured" if m["band_bounds_history"] else ("balanced" if m["band_bounds"] else "equal")), "band_bounds": m["band_bounds"],
                 "band_rebalancing": {"rounds_during_warmup": args.band_rebalance_rounds, "splits_taken": m["band_bounds_history"],
@@ -701,17 +734,28 @@ def main():
                    "note": "the --steps timed frames in blocks between a barrier + device synchronisation on both sides; ms_per_step / value = all of them.  "
                            "The workload gets cheaper while its reservoirs age (frames 6-25 of a fresh context 0.96 ms, 0.90 from frame 200 on; "
                            "profiles/r06_history_age.txt), so the blocks are listed in frame order"},
-        "instrumented_block": {**m["instrumented"], "note": "the HIP events of `roofline` (on the two long dispatches; configs 3 / 4: + every trace launch and the "
-                               "direct-light dispatches) ride on these frames after the timed ones, not on any timed frame - they cost the frames that carry them 2-4 %"},
+        **({"instrumented_block": {**m["instrumented"], "note": "the HIP events of `roofline` (on the two long dispatches; configs 3 / 4: + every trace launch and the "
+                                   "direct-light dispatches) ride on these frames after the timed ones, not on any timed frame - they cost the frames that carry them 2-4 %"}}
+           if args.full else {}),
         "min_ms_per_step": min(ms_blocks),
         "mray_per_s_per_gpu": round(total_rays / elapsed / 1e6 / world, 3),
         "rays_per_frame": round(total_rays / args.steps, 1),
-        "replay_bit_identical": same,
+        **({"replay_bit_identical": same} if same is not None else {}),
         **({"ray_count_replay_bit_identical": m["walk"]["ray_count_replay_bit_identical"]} if "ray_count_replay_bit_identical" in m["walk"] else {}),
-        "frame_latency_ms": round(m["frame_latency_ms"], 4),
-        "ms_per_step_is": "throughput: frames enqueued back to back, frame n's a-trous levels (third stream) beside frame n + 1's light passes; frame_latency_ms = one frame, wait, repeat",
-        "roofline": None,
+        **({"frame_latency_ms": round(m["frame_latency_ms"], 4)} if args.full else {}),
+        "ms_per_step_is": "throughput: frames enqueued back to back, frame n's a-trous levels (third stream) beside frame n + 1's light passes; frame_latency_ms (--full) = one "
+                          "frame, wait, repeat",
+        **({"roofline": None} if args.full else {}),
     }
+    if m["sustained"]:
+        out["sustained"] = m["sustained"]
+    if transport_used[0]:
+        out["config"]["halo_transport"] = transport_used[0]
+    if passes:
+        out["pass_ms"] = passes
+    if not args.full:
+        emit(out)
+        return
     # The dominant kernel is the LONGER of the frame's two long dispatches AS TIMED IN THIS RUN (HIP events on both dispatches inside the
     # timed region: in the pipelined frame their durations stretch differently - rocprofv3 of round 5: k_spatial_reuse 521 us against
     # k_indirect 331 us - while alone on the GPU they tie).  `second_kernel` is the other one, same arithmetic.
@@ -844,8 +888,6 @@ def main():
         out["roofline"]["bvh_walk"] = walk_roofline(m, xeng)
     if m.get("direct_ms"):
         out["direct_passes_in_run_ms"] = m["direct_ms"]
-    if m["sustained"]:
-        out["sustained"] = m["sustained"]
     if extra is not None and rank == 0:
         try:
             extra["motion"] = motion_lines(True)
@@ -853,10 +895,6 @@ def main():
             extra["motion"] = {"error": repr(e)}
     if extra:
         out["extra_configs"] = extra
-    if transport_used[0]:
-        out["config"]["halo_transport"] = transport_used[0]
-    if passes:
-        out["pass_ms"] = passes
 
     # ------------------------------------------------------------------ CPU baseline (oracle = port of the reference WGSL)
     if world == 1 and not args.no_cpu_baseline:
@@ -887,18 +925,7 @@ def main():
                       "the reference itself (wgpu + lavapipe) cannot be built or run here",
             "ms_per_frame": round(cdt / done * 1e3, 1),
         }
-    # the JSON line is the LAST thing on stdout: what C libraries (RCCL's start-up banner ...) left in their stdio buffers goes out
-    # first, and whatever they print later goes to stderr
-    import ctypes
-    try:
-        ctypes.CDLL(None).fflush(None)
-    except Exception:
-        pass
-    print(json.dumps(out), flush=True)
-    os.dup2(2, 1)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    emit(out)
 
 
 if __name__ == "__main__":

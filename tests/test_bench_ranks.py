@@ -26,7 +26,7 @@ def test_bench_band_path_runs_with_several_ranks_on_one_gpu(world, launcher):
         cmd = [sys.executable]
         if launcher in ("torchrun", "balanced", "rebalanced"):
             cmd += ["-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1", "--master-port", str(port)]
-        cmd += [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "3", "--blocks", "2", "--width", "640", "--height", "360"]
+        cmd += [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "3", "--blocks", "2", "--width", "640", "--height", "360", "--full"]
         if launcher == "balanced":   # the split by cost, derived by every rank on frame 1 (HK_FRAME_BALANCE_BANDS / hk_balance_bands)
             cmd += ["--band-split", "balanced"]
         if launcher == "rebalanced":   # round 6: the split follows measured band times during a longer warm-up (all-gather of N floats, migration of the moved rows)

@@ -5,7 +5,7 @@ OUT=$PWD/gpurun_out; mkdir -p $OUT
 for V in "$@"; do
   for C in 3 4; do
     if [ "$V" = default ]; then LIB=""; else LIB="$PWD/build_ab/$V.so"; fi
-    env ${LIB:+HIKARI_HIP_LIB=$LIB} timeout 300 python bench.py --config $C --no-cpu-baseline --no-hbm-probe --no-extra-configs --blocks 3 > $OUT/ab_$V_$C.json 2> $OUT/ab_$V_$C.err
+    env ${LIB:+HIKARI_HIP_LIB=$LIB} timeout 300 python bench.py --config $C --full --no-cpu-baseline --no-hbm-probe --no-extra-configs --blocks 3 > $OUT/ab_$V_$C.json 2> $OUT/ab_$V_$C.err
     python - <<PY
 import json
 try:

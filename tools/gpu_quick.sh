@@ -8,7 +8,7 @@ if [ -n "$KEXPR" ]; then
   tail -15 $OUT/${TAG}_pytest.log
 fi
 for C in $CONFIGS; do
-  EXTRA="--no-cpu-baseline --blocks 3"; [ $C != 2 ] && EXTRA="$EXTRA --no-hbm-probe"
+  EXTRA="--full --no-cpu-baseline --blocks 3"; [ $C != 2 ] && EXTRA="$EXTRA --no-hbm-probe"
   timeout 900 python bench.py --config $C --passes $EXTRA > $OUT/${TAG}_bench_config$C.json 2> $OUT/${TAG}_bench_config$C.err
   python - <<PY
 import json

@@ -4,7 +4,7 @@
 C=${1:-4}; TAG=${2:-fetch}
 OUT=$PWD/gpurun_out; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $OLDPWD/bench.py --config $C --steps 3 --warmup 4 --blocks 1 --no-cpu-baseline --no-hbm-probe --no-extra-configs --sustained-seconds 0"
+CMD="python $OLDPWD/bench.py --config $C --steps 3 --warmup 4 --blocks 1 --full --no-cpu-baseline --no-hbm-probe --no-extra-configs --sustained-seconds 0"
 for K in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 200 rocprofv3 --kernel-trace --pmc $K -d $OUT/prof_${K}_$C -- $CMD > /dev/null 2>&1
   DB=$(find $OUT/prof_${K}_$C -name "*.db" | head -1)

@@ -4,7 +4,7 @@
 C=${1:-4}; TAG=${2:-lanes}
 OUT=$PWD/gpurun_out; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $OLDPWD/bench.py --config $C --steps 3 --warmup 4 --blocks 1 --no-cpu-baseline --no-hbm-probe --no-extra-configs --sustained-seconds 0"
+CMD="python $OLDPWD/bench.py --config $C --steps 3 --warmup 4 --blocks 1 --full --no-cpu-baseline --no-hbm-probe --no-extra-configs --sustained-seconds 0"
 timeout -s KILL 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES -d $OUT/prof_lanes_$C -- $CMD > /dev/null 2>&1
 cd $OLDPWD
 DB=$(find $OUT/prof_lanes_$C -name "*.db" | head -1)

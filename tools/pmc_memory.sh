@@ -2,7 +2,7 @@
 # which unit of the memory pipeline the large-scene ray kernels saturate: TLB (UTCL1), address / data path (TA, TCP), L2 (TCC), fabric credits
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 OUT=gpurun_out; mkdir -p $OUT
-CMD="python bench.py --config ${1:-3} --steps 4 --warmup 4 --blocks 1 --no-cpu-baseline --no-hbm-probe --no-extra-configs --sustained-seconds 0"
+CMD="python bench.py --config ${1:-3} --steps 4 --warmup 4 --blocks 1 --full --no-cpu-baseline --no-hbm-probe --no-extra-configs --sustained-seconds 0"
 # NEVER RUN AS IT WAS FIRST WRITTEN: eight counters of one block in a pass made rocprofv3 abort (signal 6) and then sit in its
 # finalizer until the timeout - three passes ate the last 15 GPU-minutes of round 3 without a number.  At most FOUR counters of a
 # block per pass, a short timeout per pass, and the whole script stops at the first pass that yields no database.

@@ -4,10 +4,10 @@
 TAG=${1:-r01_final}
 OUT=$PWD/gpurun_out
 mkdir -p $OUT
-python bench.py --passes > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python bench.py --full --passes > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 tail -1 $OUT/${TAG}_bench.json | cut -c1-400
 cd /tmp && export TMPDIR=/tmp
-CMD="python $OLDPWD/bench.py --steps 6 --warmup 4 --no-cpu-baseline"
+CMD="python $OLDPWD/bench.py --steps 6 --warmup 4 --full --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats -d $OUT/prof_trace -- $CMD > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES -d $OUT/prof_sq -- $CMD > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/prof_fetch -- $CMD > /dev/null 2>&1

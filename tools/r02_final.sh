@@ -5,7 +5,7 @@ TAG=${1:-r02_final}
 bash tools/gpu_round.sh $TAG $2
 OUT=$PWD/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-CMD="python $OLDPWD/bench.py --config 3 --steps 3 --warmup 4 --blocks 1 --no-cpu-baseline --no-hbm-probe"
+CMD="python $OLDPWD/bench.py --config 3 --steps 3 --warmup 4 --blocks 1 --full --no-cpu-baseline --no-hbm-probe"
 timeout 600 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES -d $OUT/prof_sq3 -- $CMD > /dev/null 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/prof_fetch3 -- $CMD > /dev/null 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/prof_write3 -- $CMD > /dev/null 2>&1

@@ -14,5 +14,5 @@ timeout 300 python tools/wf_timeline.py --no-wide-walk 3 4 > $OUT/${TAG}_wf_time
 bash tools/pmc_calibrate.sh $TAG > /dev/null 2>&1
 # the wide walk's A/B on the scenes it serves: the same bench lines with HK_CTX_NO_WIDE_WALK (threaded skip-link walk for every ray)
 for C in 3 4; do
-  timeout 600 python bench.py --config $C --no-wide-walk --passes --no-cpu-baseline --no-hbm-probe --blocks 3 > $OUT/${TAG}_bench_config${C}_no_wide_walk.json 2> /dev/null
+  timeout 600 python bench.py --config $C --no-wide-walk --full --passes --no-cpu-baseline --no-hbm-probe --blocks 3 > $OUT/${TAG}_bench_config${C}_no_wide_walk.json 2> /dev/null
 done
