@@ -205,6 +205,8 @@ _SIGNATURES = {
 _DEBUG = {
     "debug_math": [_vp, u32, P(f32), P(f32), P(f32), C.c_size_t],
     "debug_read_trees": [_vp, P(HkNode), u32, P(HkNode), u32],
+    "debug_read_mesh_nodes": [_vp, P(HkNode), u32, P(u32), P(u32)],
+    "debug_read_emitters": [_vp, P(f32), u32, P(u32), P(f32), u32, P(u32)],
     "debug_comm_loopback": [_vp, u32, u32, u32, u32, u32],
     "debug_read_wf_timeline": [_vp, P(C.c_uint64), u32],
     "debug_set_option": [_vp, u32, C.c_int64],
@@ -241,11 +243,16 @@ _PRODUCT_ONLY = {
     "scene_builder_emissives": [_vp, P(P(HkEmissive)), P(u32)],
     "scene_builder_emissive_nodes": [_vp, P(P(HkNode)), P(u32)],
     "scene_builder_alias_table": [_vp, P(P(HkAliasEntry)), P(u32)],
+    "scene_builder_set_mesh_vertices": [_vp, u32, P(f32), P(f32)],
+    "scene_builder_mesh_index": [_vp, u32, P(HkMeshIndex)],
     "upload_scene": [_vp, _vp],
     "upload_scene_instances": [_vp, _vp],
     "refit_scene_instances": [_vp, _vp, P(u32)],
     "rebuild_scene_trees": [_vp, u32],
     "update_scene_instances": [_vp, _vp, u32],
+    "update_mesh_vertices": [_vp, P(HkMeshIndex), u32, P(f32), P(f32)],
+    "set_mesh_skin": [_vp, P(HkMeshIndex), u32, P(f32), P(f32), P(C.c_uint16), P(f32)],
+    "skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],
     "band_rows": [u32, u32, u32, P(u32), P(u32)],
     "balanced_band_bounds": [P(u32), u32, u32, u32, u32, u32, f32, P(u32)],
     "balance_bands": [_vp, u32, P(u32), u32],
@@ -285,6 +292,9 @@ _PRODUCT_ONLY = {
     "multi_refit_scene_instances": [_vp, _vp, P(u32)],
     "multi_rebuild_scene_trees": [_vp, u32],
     "multi_update_scene_instances": [_vp, _vp, u32],
+    "multi_update_mesh_vertices": [_vp, P(HkMeshIndex), u32, P(f32), P(f32)],
+    "multi_set_mesh_skin": [_vp, P(HkMeshIndex), u32, P(f32), P(f32), P(C.c_uint16), P(f32)],
+    "multi_skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],
     "multi_set_band_bounds": [_vp, P(u32), u32],
     "multi_upload_textures": [_vp, P(HkImageDesc), u32],
     "multi_upload_noise": [_vp, _vp, C.c_size_t],

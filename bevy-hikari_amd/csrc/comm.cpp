@@ -813,6 +813,14 @@ int hk_multi_context(hk_multi* m, uint32_t i, hk_ctx** out) {
 int hk_multi_upload_scene(hk_multi* m, const hk_scene_builder* b) { HK_EACH(hk_upload_scene(c, b)); }
 int hk_multi_upload_scene_instances(hk_multi* m, const hk_scene_builder* b) { HK_EACH(hk_upload_scene_instances(c, b)); }
 int hk_multi_rebuild_scene_trees(hk_multi* m, uint32_t mode) { HK_EACH(hk_rebuild_scene_trees(c, mode)); }
+int hk_multi_update_mesh_vertices(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vertices, const float* positions, const float* normals) {
+  HK_EACH(hk_update_mesh_vertices(c, mesh, n_vertices, positions, normals));
+}
+int hk_multi_set_mesh_skin(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vertices, const float* bind_positions, const float* bind_normals,
+                           const uint16_t* joint_indices, const float* joint_weights) {
+  HK_EACH(hk_set_mesh_skin(c, mesh, n_vertices, bind_positions, bind_normals, joint_indices, joint_weights));
+}
+int hk_multi_skin_mesh(hk_multi* m, const HkMeshIndex* mesh, const float* joint_matrices, uint32_t n_joints) { HK_EACH(hk_skin_mesh(c, mesh, joint_matrices, n_joints)); }
 // the same explicit split on every band's context (all of them must agree: the schedules are derived per context)
 int hk_multi_set_band_bounds(hk_multi* m, const uint32_t* bounds, uint32_t n_bounds) { HK_EACH(hk_set_band_bounds(c, bounds, n_bounds)); }
 // the rows of the history reservoirs that change owner travel between the bands' contexts, then every band takes the new split

@@ -394,7 +394,8 @@ int ready(hk_ctx* c) {
   HK_REQUIRE(c->have_frame, HK_E_NOT_READY, "hk_frame_begin has not been called");
   HK_REQUIRE(c->have_noise, HK_E_NOT_READY, "noise textures not uploaded");
   HK_HIP(hipSetDevice(c->device));
-  return finalize_scene(c);
+  const int rc = finalize_scene(c);
+  return rc ? rc : flush_deform(c);   // (the instance level of meshes deformed since the last frame: once, whatever the number of calls)
 }
 
 struct Jitter { float x, y; };
@@ -968,6 +969,7 @@ void hk_destroy(hk_ctx* c) {
     if (c->staging_done[k]) (void)hipEventDestroy(c->staging_done[k]);
   }
   free_refit(c);
+  free_deform(c);
   for (void* q : {(void*)c->wide_tlas, (void*)c->wide_blas, (void*)c->wide_spill, (void*)c->wide_tlas_rank, (void*)c->wide_blas_rank})
     if (q) (void)hipFree(q);
   c->d_tex_data.release();

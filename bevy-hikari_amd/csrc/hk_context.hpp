@@ -233,6 +233,15 @@ struct hk_ctx {
   int rf_k = 0;
   std::vector<uint32_t> rf_last_moved;    // instances whose `moved` flag is set on the device
   bool mirrors_stale = false;             // the host copies of emissives / tree boxes no longer describe the device scene
+  // mesh deformation (mesh_deform.hip): per deformable mesh its tree topology, refit planes and skin, created on first use and dropped by
+  // hk_upload_meshes; a pool of pinned staging buffers for the vertex / joint data, each reused once the event after its last reader has
+  // passed (a call never waits on the host: with none free it adds one)
+  std::vector<struct DeformMesh*> deform;
+  struct DeformStage { uint8_t* p = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool pending = false; };
+  std::vector<DeformStage> df_stage;
+  bool deform_pending = false;            // deformed meshes whose new boxes have not reached the instance level yet (flush_deform)
+  bool meshes_deformed = false;           // a mesh was deformed on the device since the last hk_upload_meshes: its host copies are stale
+  uint64_t instances_generation = 0;      // counts hk_upload_instances (the instance lists of the deformable meshes follow it)
   uint64_t device_refits = 0, device_tree_builds = 0;
   void* lbvh_scratch = nullptr;           // hk_rebuild_scene_trees
   size_t lbvh_scratch_cap = 0;
@@ -322,4 +331,11 @@ void update_shared_transform(hk_ctx* c);
 void point_scene_at_slot(hk_ctx* c);
 // ---- scene_refit.hip
 void free_refit(hk_ctx* c);
+int begin_device_update(hk_ctx* c);
+int prepare_refit(hk_ctx* c);
+hkd::RefitScene refit_scene(hk_ctx* c);
+// ---- mesh_deform.hip
+void free_deform(hk_ctx* c);
+int repropagate_deformed(hk_ctx* c);   // after an instance refit: the deformed meshes' current boxes again (hk_refit_scene_instances)
+int flush_deform(hk_ctx* c);           // the instance level of the meshes deformed since the last flush, once (frames, tree rebuilds, reads)
 }  // namespace hk

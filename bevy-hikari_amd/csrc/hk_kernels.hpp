@@ -116,6 +116,18 @@ struct RefitUpdate {       // one record per instance whose transform changed (r
   float model[16];         // new model matrix, column-major
   float aabb_center[3], aabb_half[3];  // the mesh's local box (bevy Aabb), instance.rs:286-296
 };
+// Mesh deformation (kernels_deform.hip, kernels_scene.hip; host side mesh_deform.hip): one mesh BLAS of n triangles as the binary tree
+// behind its flat layout - internal nodes in the preorder of ordering 0 (root 0), leaves in ordering 0's order as tree nodes n - 1 + j -
+// with the work planes of a bottom-up refit.
+struct MeshTree {
+  uint32_t n;
+  uint32_t *parent, *left, *right, *first, *last;  // per internal node (left = the child ordering 0 puts first)
+  uint32_t *leaf_parent, *leaf_shape;              // per leaf: its parent, its triangle (local index)
+  uint32_t* arrived;                               // per internal node: bottom-up visit counter (zeroed before every refit)
+  uint8_t* swap;                                   // per internal node: bit o set = the second child comes first in ordering o
+  float4 *node_lo, *node_hi;                       // per tree node (2n - 1)
+  float4 *tri_lo, *tri_hi;                         // per triangle: its box
+};
 struct RefitScene {
   DInstance* instances;
   float4* prev_models;                   // 4 columns per instance
@@ -309,6 +321,18 @@ void launch_refit(hipStream_t st, const hkd::RefitScene& s, const hkd::RefitUpda
 size_t lbvh_scratch_bytes(uint32_t n, size_t* sort_temp_bytes);
 int launch_tree_build(hipStream_t st, int mode /* 0 LBVH, 1 the reference's binned SAH */, bool light, const hkd::RefitScene& s, uint32_t n, const float4* box_lo,
                       const float4* box_hi, void* scratch, float4* lo, float4* hi, uint32_t stride, uint32_t orderings);
+// mesh deformation: the BLAS refit of one mesh tree into `orderings` orderings of its flat layout (`lo` = its node 0 of ordering 0,
+// interleaved lo / hi pairs, `ord_stride` float4 between orderings); the propagation of a new mesh box (`box`: 6 order-preserving
+// words, kernels_deform.hip) to the instances `ids` (emitters first) of the mesh, their emitters (`records`: device scratch, one per
+// instance) and both trees
+void launch_mesh_tree_refit(hipStream_t st, const hkd::MeshTree& t, float4* lo, size_t ord_stride, uint32_t orderings);
+void launch_mesh_propagate(hipStream_t st, const hkd::RefitScene& s, const uint32_t* box, const uint32_t* ids, uint32_t n_ids, hkd::RefitUpdate* records,
+                           uint32_t n_emitters, uint32_t emitter_triangles, float4* tlas, uint32_t tlas_count, uint32_t orderings, float4* light_lo, float4* light_hi,
+                           uint32_t light_count);
+void launch_mesh_stage(hipStream_t st, const float* positions, const float* normals, uint32_t n, float4* pos, float4* vn, uint32_t* box);
+void launch_mesh_skin(hipStream_t st, const float4* bind_pos, const float4* bind_nrm, const uint2* joints, const float4* weights, const float4* joint_mats, uint32_t n,
+                      float4* pos, float4* vn, uint32_t* box);
+void launch_mesh_triangles(hipStream_t st, const float4* pos, float4* v0, float4* v1, float4* v2, uint32_t n_tris, float4* tri_lo, float4* tri_hi);
 // windowed: 0 the plain form, 1 the windowed form (depth window + tap lists in LDS: kernels.hip), -1 by the size of the launch; returns
 // whether the windowed form was launched
 bool launch_spatial(hipStream_t st, bool emissive_lit, const hkd::DScene& sc, const hkd::DFrame& fr, const hkd::GBuffer& g, const hkd::LightTargets& t,

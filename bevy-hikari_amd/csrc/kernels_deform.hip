@@ -1,0 +1,162 @@
+// kernels_deform.hip - new vertex data of one mesh on the device (hk_update_mesh_vertices, hk_skin_mesh; host side mesh_deform.hip):
+// the vertices of the mesh land in its normal plane and in a position scratch plane, the mesh box is reduced on the way, then every
+// triangle of the mesh takes its three positions into the triangle planes and its box into the refit's leaf boxes (kernels_scene.hip
+// launch_mesh_tree_refit carries on from there).  Streaming kernels, one thread per vertex / per triangle.
+#include <hip/hip_runtime.h>
+
+#include "hk_device.hpp"
+#include "hk_kernels.hpp"
+
+namespace hkd {
+
+namespace {
+// the host's hmin / hmax (hk_context.hpp: IEEE minNum / maxNum with -0 < +0): the leaf boxes of build_static_region, operation for operation
+__device__ __forceinline__ float leaf_min(float a, float b) {
+  if (a != a) return b;
+  if (b != b) return a;
+  if (a == b) return signbit(a) ? a : b;
+  return a < b ? a : b;
+}
+__device__ __forceinline__ float leaf_max(float a, float b) {
+  if (a != a) return b;
+  if (b != b) return a;
+  if (a == b) return signbit(a) ? b : a;
+  return a > b ? a : b;
+}
+// mesh box words: a float mapped to a u32 whose unsigned order is the float order with -0 < +0, so that atomicMin / atomicMax give the
+// min / max over the vertices whatever order they arrive in (decoded by kernels_scene.hip k_mesh_instances)
+__device__ __forceinline__ uint32_t box_word(float f) {
+  const uint32_t u = f2u(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// one wave reduces its lanes' positions, lane 0 adds them to the six words (words 0-2 min, 3-5 max)
+__device__ __forceinline__ void reduce_box(uint32_t* box, bool valid, float x, float y, float z) {
+  uint32_t mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0u, 0u, 0u};
+  if (valid) {
+    const float p[3] = {x, y, z};
+    for (int k = 0; k < 3; ++k) mn[k] = mx[k] = box_word(p[k]);
+  }
+  for (int off = 32; off > 0; off >>= 1)
+    for (int k = 0; k < 3; ++k) {
+      mn[k] = min(mn[k], (uint32_t)__shfl_xor((int)mn[k], off));
+      mx[k] = max(mx[k], (uint32_t)__shfl_xor((int)mx[k], off));
+    }
+  if ((threadIdx.x & 63u) == 0u && mx[0] != 0u)
+    for (int k = 0; k < 3; ++k) {
+      atomicMin(&box[k], mn[k]);
+      atomicMax(&box[3 + k], mx[k]);
+    }
+}
+}  // namespace
+
+// hk_update_mesh_vertices: positions / normals (3 floats per vertex, pinned host memory, read once)
+__global__ __launch_bounds__(256) void k_mesh_stage(const float* __restrict__ positions, const float* __restrict__ normals, uint32_t n, float4* __restrict__ pos,
+                                                    float4* __restrict__ vn, uint32_t* __restrict__ box) {
+  const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+  const bool valid = v < n;
+  float x = 0.0f, y = 0.0f, z = 0.0f;
+  if (valid) {
+    x = positions[3u * v];
+    y = positions[3u * v + 1u];
+    z = positions[3u * v + 2u];
+    pos[v] = make_float4(x, y, z, 0.0f);
+    if (normals) vn[v] = make_float4(normals[3u * v], normals[3u * v + 1u], normals[3u * v + 2u], 0.0f);
+  }
+  reduce_box(box, valid, x, y, z);
+}
+
+// Linear-blend skinning, Bevy 0.9 skinning.wgsl (hikari_hip.h hk_skin_mesh; DESIGN "Mesh deformation"): fixed order, no contraction.
+//   M  = ((w.x J[i.x] + w.y J[i.y]) + w.z J[i.z]) + w.w J[i.w]               element by element
+//   p' = ((M0 x + M1 y) + M2 z) + M3                                           (M0..M3: columns)
+//   n' = ((c0 n.x + c1 n.y) + c2 n.z),  (c0, c1, c2) = (M1 x M2, M2 x M0, M0 x M1) / dot(M2, M0 x M1)   (inverse_transpose_3x3)
+// n' is stored as it comes out (hit_info normalises, as for any uploaded normal).
+__global__ __launch_bounds__(256) void k_mesh_skin(const float4* __restrict__ bind_pos, const float4* __restrict__ bind_nrm, const uint2* __restrict__ joints,
+                                                   const float4* __restrict__ weights, const float4* __restrict__ joint_mats, uint32_t n, float4* __restrict__ pos,
+                                                   float4* __restrict__ vn, uint32_t* __restrict__ box) {
+  const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+  const bool valid = v < n;
+  float px = 0.0f, py = 0.0f, pz = 0.0f;
+  if (valid) {
+    const uint2 jw = joints[v];
+    const uint32_t j[4] = {jw.x & 0xFFFFu, jw.x >> 16, jw.y & 0xFFFFu, jw.y >> 16};
+    const float4 w4 = weights[v];
+    const float w[4] = {w4.x, w4.y, w4.z, w4.w};
+    float m[4][4];  // m[column][row]
+    for (int c = 0; c < 4; ++c) {
+      const float4 a = joint_mats[4u * j[0] + c];
+      m[c][0] = w[0] * a.x;
+      m[c][1] = w[0] * a.y;
+      m[c][2] = w[0] * a.z;
+      m[c][3] = w[0] * a.w;
+    }
+    for (int t = 1; t < 4; ++t)
+      for (int c = 0; c < 4; ++c) {
+        const float4 a = joint_mats[4u * j[t] + c];
+        m[c][0] = m[c][0] + w[t] * a.x;
+        m[c][1] = m[c][1] + w[t] * a.y;
+        m[c][2] = m[c][2] + w[t] * a.z;
+        m[c][3] = m[c][3] + w[t] * a.w;
+      }
+    const float4 p = bind_pos[v];
+    px = ((m[0][0] * p.x + m[1][0] * p.y) + m[2][0] * p.z) + m[3][0];
+    py = ((m[0][1] * p.x + m[1][1] * p.y) + m[2][1] * p.z) + m[3][1];
+    pz = ((m[0][2] * p.x + m[1][2] * p.y) + m[2][2] * p.z) + m[3][2];
+    pos[v] = make_float4(px, py, pz, 0.0f);
+    auto cross = [](const float* a, const float* b, float* o) {
+      o[0] = a[1] * b[2] - a[2] * b[1];
+      o[1] = a[2] * b[0] - a[0] * b[2];
+      o[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    const float* c0 = m[0];
+    const float* c1 = m[1];
+    const float* c2 = m[2];
+    float x[3], y[3], z[3];
+    cross(c1, c2, x);
+    cross(c2, c0, y);
+    cross(c0, c1, z);
+    const float det = (c2[0] * z[0] + c2[1] * z[1]) + c2[2] * z[2];
+    for (int k = 0; k < 3; ++k) {
+      x[k] = x[k] / det;
+      y[k] = y[k] / det;
+      z[k] = z[k] / det;
+    }
+    const float4 q = bind_nrm[v];
+    vn[v] = make_float4((x[0] * q.x + y[0] * q.y) + z[0] * q.z, (x[1] * q.x + y[1] * q.y) + z[1] * q.z, (x[2] * q.x + y[2] * q.y) + z[2] * q.z, 0.0f);
+  }
+  reduce_box(box, valid, px, py, pz);
+}
+
+// every triangle of the mesh: its three positions (the w words - vertex indices - stay) and its box (light.wgsl:408-412, the leaf box)
+__global__ __launch_bounds__(256) void k_mesh_triangles(const float4* __restrict__ pos, float4* __restrict__ v0, float4* __restrict__ v1, float4* __restrict__ v2,
+                                                        uint32_t n_tris, float4* __restrict__ tri_lo, float4* __restrict__ tri_hi) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= n_tris) return;
+  float4 q[3] = {v0[t], v1[t], v2[t]};
+  for (int k = 0; k < 3; ++k) {
+    const float4 p = pos[f2u(q[k].w)];
+    q[k] = make_float4(p.x, p.y, p.z, q[k].w);
+  }
+  v0[t] = q[0];
+  v1[t] = q[1];
+  v2[t] = q[2];
+  tri_lo[t] = make_float4(leaf_min(q[0].x, leaf_min(q[1].x, q[2].x)), leaf_min(q[0].y, leaf_min(q[1].y, q[2].y)), leaf_min(q[0].z, leaf_min(q[1].z, q[2].z)), 0.0f);
+  tri_hi[t] = make_float4(leaf_max(q[0].x, leaf_max(q[1].x, q[2].x)), leaf_max(q[0].y, leaf_max(q[1].y, q[2].y)), leaf_max(q[0].z, leaf_max(q[1].z, q[2].z)), 0.0f);
+}
+
+}  // namespace hkd
+
+namespace hk {
+using namespace hkd;
+
+void launch_mesh_stage(hipStream_t st, const float* positions, const float* normals, uint32_t n, float4* pos, float4* vn, uint32_t* box) {
+  if (n) hipLaunchKernelGGL(k_mesh_stage, dim3((n + 255u) / 256u), dim3(256), 0, st, positions, normals, n, pos, vn, box);
+}
+void launch_mesh_skin(hipStream_t st, const float4* bind_pos, const float4* bind_nrm, const uint2* joints, const float4* weights, const float4* joint_mats, uint32_t n,
+                      float4* pos, float4* vn, uint32_t* box) {
+  if (n) hipLaunchKernelGGL(k_mesh_skin, dim3((n + 255u) / 256u), dim3(256), 0, st, bind_pos, bind_nrm, joints, weights, joint_mats, n, pos, vn, box);
+}
+void launch_mesh_triangles(hipStream_t st, const float4* pos, float4* v0, float4* v1, float4* v2, uint32_t n_tris, float4* tri_lo, float4* tri_hi) {
+  if (n_tris) hipLaunchKernelGGL(k_mesh_triangles, dim3((n_tris + 255u) / 256u), dim3(256), 0, st, pos, v0, v1, v2, n_tris, tri_lo, tri_hi);
+}
+
+}  // namespace hk

@@ -61,6 +61,39 @@ __device__ bool inverse_transpose(const float* m, float* out) {
 }
 __device__ __forceinline__ float hmin(float a, float b) { return b < a ? b : a; }  // std::min / std::max of the host builder
 __device__ __forceinline__ float hmax(float a, float b) { return a < b ? b : a; }
+// world AABB of an instance (instance.rs:286-305, scene_builder.cpp instance_world_record): the mesh box's 8 corners as vectors, min /
+// max seeded at zero, then the centre added.  k_mesh_instances' form of k_refit_instances' arithmetic (which writes it out: keep both in step).
+__device__ __forceinline__ void instance_world_box(const float* m, const float* aabb_center, const float* aabb_half, float* mn, float* mx) {
+  float center[3];
+  mat_point(m, aabb_center, center);
+  for (int k = 0; k < 3; ++k) mn[k] = mx[k] = 0.0f;
+  for (int corner = 0; corner < 8; ++corner) {
+    const float e[3] = {aabb_half[0] * (float)(2 * (corner & 1) - 1), aabb_half[1] * (float)(2 * ((corner >> 1) & 1) - 1),
+                        aabb_half[2] * (float)(2 * ((corner >> 2) & 1) - 1)};
+    float t[3];
+    mat_vector(m, e, t);
+    for (int k = 0; k < 3; ++k) {
+      mn[k] = hmin(mn[k], t[k]);
+      mx[k] = hmax(mx[k], t[k]);
+    }
+  }
+  for (int k = 0; k < 3; ++k) {
+    mn[k] = mn[k] + center[k];
+    mx[k] = mx[k] + center[k];
+  }
+}
+// the emitter record's position and radius from the instance's world AABB and its material's emissive colour (instance.rs:380-420)
+__device__ __forceinline__ float4 emitter_position_radius(const float4 col, const float* mn, const float* mx) {
+  const float intensity = 255.0f * col.w * sqrtf(col.x * col.x + col.y * col.y + col.z * col.z);
+  float pos[3], d2 = 0.0f;
+  for (int k = 0; k < 3; ++k) {
+    pos[k] = 0.5f * (mx[k] + mn[k]);
+    const float dd = mx[k] - mn[k];
+    d2 += dd * dd;
+  }
+  const float radius = 0.5f * sqrtf(d2) + sqrtf(intensity);
+  return make_float4(pos[0], pos[1], pos[2], radius);
+}
 }  // namespace
 
 // ------------------------------------------------------------------ per moved instance (instance.rs:286-325,380-420)
@@ -99,6 +132,8 @@ __global__ __launch_bounds__(64) void k_refit_instances(RefitScene s, const Refi
   d.n2 = make_float4(itm[8], itm[9], itm[10], 0.0f);
   d.moved = 1u;
   // world AABB: the mesh box's 8 corners as vectors, min / max seeded at zero, then the centre added (instance.rs:286-305)
+  // (the same arithmetic as instance_world_box / emitter_position_radius, which k_mesh_instances uses: a change here goes there too -
+  // written out here because the shared form costs this kernel two VGPRs over its budget, tests/test_kernel_resources.py)
   float center[3];
   mat_point(m, up.aabb_center, center);
   float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
@@ -459,12 +494,12 @@ __global__ __launch_bounds__(256) void k_lbvh_boxes(RefitScene s, LbvhBuffers b)
   }
 }
 // every tree node except the root writes the navigator in front of its subtree; leaves also write their own slot
-__global__ __launch_bounds__(256) void k_lbvh_emit(LbvhBuffers b, float4* lo, float4* hi, uint32_t stride, uint32_t orderings) {
+__global__ __launch_bounds__(256) void k_lbvh_emit(LbvhBuffers b, float4* lo, float4* hi, uint32_t stride, size_t ord_stride /* float4 between orderings */, uint32_t orderings) {
   const uint32_t t = blockIdx.x * 256u + threadIdx.x, n = b.n, total = 2u * n - 1u;
   if (t >= total * orderings) return;
-  const uint32_t o = t / total, v = t - o * total, count = 3u * n - 2u;
-  float4* nlo = lo + (size_t)o * count * stride;
-  float4* nhi = hi + (size_t)o * count * stride;
+  const uint32_t o = t / total, v = t - o * total;
+  float4* nlo = lo + (size_t)o * ord_stride;
+  float4* nhi = hi + (size_t)o * ord_stride;
   const bool leaf = v >= n - 1u;
   const uint32_t shape = leaf ? b.ids_sorted[v - (n - 1u)] : 0u;
   const float4 blo = b.node_lo[v], bhi = b.node_hi[v];
@@ -878,6 +913,44 @@ __global__ __launch_bounds__(1024) void k_sah_subtrees(RefitScene s, LbvhBuffers
   }
 }
 
+// ------------------------------------------------------------------ a deformed mesh's new box, carried to its instances
+// One thread per instance of the mesh: the mesh box (order-preserving words of kernels_deform.hip k_mesh_*) as bevy's Aabb, the world
+// AABB and emitter record with k_refit_instances' arithmetic (instance_world_box, emitter_position_radius: keep both in step) - but the pose, its previous model and its `moved` flag stay as they are
+// (a deformation is no motion: velocity_uv keeps the reference's formula).  Emitters (the first n_emitters ids) also get an update
+// record for k_refit_emitters: their triangle areas and alias table follow the new triangles.
+__device__ __forceinline__ float mesh_box_word(uint32_t e) { return u2f((e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e); }
+__global__ __launch_bounds__(64) void k_mesh_instances(RefitScene s, const uint32_t* __restrict__ box, const uint32_t* __restrict__ ids, uint32_t n_ids,
+                                                       RefitUpdate* __restrict__ records, uint32_t n_emitters) {
+  const uint32_t u = blockIdx.x * 64u + threadIdx.x;
+  if (u >= n_ids) return;
+  const uint32_t id = ids[u];
+  const DInstance& d = s.instances[id];
+  const float m[16] = {d.m0.x, d.m0.y, d.m0.z, d.m0.w, d.m1.x, d.m1.y, d.m1.z, d.m1.w, d.m2.x, d.m2.y, d.m2.z, d.m2.w, d.m3.x, d.m3.y, d.m3.z, d.m3.w};
+  float ac[3], ah[3];
+  for (int k = 0; k < 3; ++k) {  // bevy Aabb::from_min_max (scene_builder.cpp hk_scene_builder_add_mesh)
+    const float mn = mesh_box_word(box[k]), mx = mesh_box_word(box[3 + k]);
+    ac[k] = 0.5f * (mx + mn);
+    ah[k] = 0.5f * (mx - mn);
+  }
+  float mn[3], mx[3];
+  instance_world_box(m, ac, ah, mn, mx);
+  s.inst_lo[id] = make_float4(mn[0], mn[1], mn[2], 0.0f);
+  s.inst_hi[id] = make_float4(mx[0], mx[1], mx[2], 0.0f);
+  if (u >= n_emitters) return;
+  const uint32_t e = s.emissive_of_instance[id];
+  if (e == HK_U32_MAX) return;
+  s.emissives[e].position_radius = emitter_position_radius(s.materials[4u * d.material + 1u], mn, mx);
+  RefitUpdate r;
+  r.instance = id;
+  r.moved = 1u;
+  for (int k = 0; k < 16; ++k) r.model[k] = m[k];
+  for (int k = 0; k < 3; ++k) {
+    r.aabb_center[k] = ac[k];
+    r.aabb_half[k] = ah[k];
+  }
+  records[u] = r;
+}
+
 }  // namespace hkd
 
 namespace hk {
@@ -912,6 +985,41 @@ void launch_refit(hipStream_t st, const RefitScene& s, const RefitUpdate* update
   if (light_count) hipLaunchKernelGGL((k_refit_flat_bvh<true>), dim3((light_count + 3u) / 4u), dim3(256), 0, st, s, light_lo, light_hi, 1u, light_count, 1u);
 }
 
+void launch_mesh_propagate(hipStream_t st, const RefitScene& s, const uint32_t* box, const uint32_t* ids, uint32_t n_ids, RefitUpdate* records, uint32_t n_emitters,
+                           uint32_t emitter_triangles, float4* tlas, uint32_t tlas_count, uint32_t orderings, float4* light_lo, float4* light_hi, uint32_t light_count) {
+  if (n_ids) hipLaunchKernelGGL(k_mesh_instances, dim3((n_ids + 63u) / 64u), dim3(64), 0, st, s, box, ids, n_ids, records, n_emitters);
+  if (n_emitters) {
+    const uint32_t lds_triangles = std::min(emitter_triangles, HK_EMITTER_LDS_TRIANGLES);
+    hipLaunchKernelGGL(k_refit_emitters, dim3(n_emitters), dim3(64), lds_triangles * 5u * 4u, st, s, (const RefitUpdate*)records, n_emitters, lds_triangles);
+  }
+  if (tlas_count) {
+    const uint32_t waves = tlas_count * orderings;
+    hipLaunchKernelGGL((k_refit_flat_bvh<false>), dim3((waves + 3u) / 4u), dim3(256), 0, st, s, tlas, tlas + 1, 2u, tlas_count, orderings);
+  }
+  if (light_count) hipLaunchKernelGGL((k_refit_flat_bvh<true>), dim3((light_count + 3u) / 4u), dim3(256), 0, st, s, light_lo, light_hi, 1u, light_count, 1u);
+}
+// the refit of a mesh tree is the last two steps of a tree build over its fixed topology: boxes bottom-up (k_lbvh_boxes: leaf boxes =
+// the triangle boxes, every internal node by the second child to arrive, child order per ordering by the rule of hk_bvh_rethread with
+// ordering 0 kept as it is), then every node written at its place in every ordering (k_lbvh_emit)
+void launch_mesh_tree_refit(hipStream_t st, const MeshTree& t, float4* lo, size_t ord_stride, uint32_t orderings) {
+  LbvhBuffers b{};
+  b.n = t.n;
+  b.box_lo = t.tri_lo;
+  b.box_hi = t.tri_hi;
+  b.ids_sorted = t.leaf_shape;
+  b.parent = t.parent; b.left = t.left; b.right = t.right; b.first = t.first; b.last = t.last;
+  b.leaf_parent = t.leaf_parent;
+  b.node_lo = t.node_lo;
+  b.node_hi = t.node_hi;
+  b.arrived = t.arrived;
+  b.swap = t.swap;
+  b.keep_order0 = 1u;
+  if (t.n > 1u) (void)hipMemsetAsync(t.arrived, 0, (size_t)(t.n - 1u) * 4, st);
+  const RefitScene none{};
+  hipLaunchKernelGGL((k_lbvh_boxes<false>), dim3((t.n + 255u) / 256u), dim3(256), 0, st, none, b);
+  const uint32_t threads = (2u * t.n - 1u) * orderings;
+  hipLaunchKernelGGL(k_lbvh_emit, dim3((threads + 255u) / 256u), dim3(256), 0, st, b, lo, lo + 1, 2u, ord_stride, orderings);
+}
 
 // scratch of one tree build over n shapes: bytes, and the carving of a single allocation
 size_t lbvh_scratch_bytes(uint32_t n, size_t* sort_temp_bytes) {
@@ -983,7 +1091,7 @@ int launch_tree_build(hipStream_t st, int mode, bool light, const RefitScene& s,
   if (light) hipLaunchKernelGGL((k_lbvh_boxes<true>), per_shape, dim3(256), 0, st, s, b);
   else hipLaunchKernelGGL((k_lbvh_boxes<false>), per_shape, dim3(256), 0, st, s, b);
   const uint32_t threads = (2u * n - 1u) * orderings;
-  hipLaunchKernelGGL(k_lbvh_emit, dim3((threads + 255u) / 256u), dim3(256), 0, st, b, lo, hi, stride, orderings);
+  hipLaunchKernelGGL(k_lbvh_emit, dim3((threads + 255u) / 256u), dim3(256), 0, st, b, lo, hi, stride, (size_t)(3u * n - 2u) * stride, orderings);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

@@ -1,0 +1,452 @@
+// mesh_deform.hip - mesh deformation on the device (hikari_hip.h hk_update_mesh_vertices / hk_set_mesh_skin / hk_skin_mesh; kernels in
+// kernels_deform.hip and kernels_scene.hip; DESIGN "Mesh deformation").  The reference re-prepares a changed mesh on the CPU
+// (mesh.rs:76-166: a BVH build and a re-layout of the whole mesh level); here the new vertices are written into the mesh-level region,
+// the mesh tree is REFIT in every ordering that holds it (same links, every box the union of the triangle boxes below it), and the
+// new mesh box goes up to the instances, emitters and both instance-level trees - all stream-ordered behind the frames enqueued before.
+#include "hk_context.hpp"
+
+using namespace hk;
+using namespace hkd;
+
+struct DeformMesh {
+  HkMeshIndex mesh{};
+  uint32_t n_tris = 0, max_vertices = 0, min_vertices = 0;   // vertex count accepted: [min_vertices, max_vertices]
+  uint32_t n_vertices = 0;                                     // the count of the last update / of the skin (0: none yet)
+  void* mem = nullptr;                                         // topology + refit planes, one allocation
+  MeshTree tree{};
+  float4* pos = nullptr;                                       // positions of the last update (per vertex; max_vertices)
+  uint32_t* box = nullptr;                                     // the mesh box, 6 order-preserving words (kernels_deform.hip)
+  uint32_t* ids = nullptr;                                     // the instances of the mesh, emitters first
+  RefitUpdate* records = nullptr;                              // k_refit_emitters' records, one per instance
+  uint32_t n_ids = 0, n_emitters = 0;
+  uint64_t ids_generation = ~0ull;
+  bool deformed = false;                                       // `box` holds the current mesh box
+  bool pending = false;                                        // ... and its instances have not been given it yet
+  // skin (hk_set_mesh_skin)
+  void* skin_mem = nullptr;
+  float4 *bind_pos = nullptr, *bind_nrm = nullptr, *weights = nullptr, *joint_mats = nullptr;
+  uint2* joints = nullptr;
+  uint32_t skin_vertices = 0, max_joint = 0, joint_cap = 0;
+};
+
+namespace hk {
+void free_deform(hk_ctx* c) {
+  for (DeformMesh* d : c->deform) {
+    for (void* q : {d->mem, d->skin_mem, (void*)d->joint_mats})
+      if (q) (void)hipFree(q);
+    delete d;
+  }
+  c->deform.clear();
+  for (hk_ctx::DeformStage& s : c->df_stage) {
+    if (s.p) (void)hipHostFree(s.p);
+    if (s.done) (void)hipEventDestroy(s.done);
+  }
+  c->df_stage.clear();
+  c->deform_pending = false;
+}
+}  // namespace hk
+
+namespace {
+// The binary tree behind a mesh tree in the `bvh` 0.7.1 flatten_custom layout (ordering 0, links local to the range): a subtree over
+// [b, e) is one leaf (e = b + 1) or [navigator a][subtree of a][navigator b][subtree of b] with b = exit(a), e = exit(b).
+bool mesh_topology(const HkNode* nodes, uint32_t count, uint32_t n_tris, std::vector<uint32_t>& parent, std::vector<uint32_t>& left, std::vector<uint32_t>& right,
+                   std::vector<uint32_t>& first, std::vector<uint32_t>& last, std::vector<uint32_t>& leaf_parent, std::vector<uint32_t>& leaf_shape) {
+  if (count != 3 * n_tris - 2) return false;
+  const uint32_t ni = n_tris - 1;
+  parent.assign(ni, HK_U32_MAX); left.assign(ni, 0); right.assign(ni, 0); first.assign(ni, 0); last.assign(ni, 0);
+  leaf_parent.assign(n_tris, HK_U32_MAX); leaf_shape.assign(n_tris, 0);
+  std::vector<uint8_t> shape_seen(n_tris, 0);
+  uint32_t next_internal = 0, next_leaf = 0;
+  struct Frame { uint32_t b, e, id, stage, second; };
+  std::vector<Frame> stack;
+  // returns the tree node of [b, e): pushes a frame for an internal node, resolves a leaf at once
+  auto open = [&](uint32_t b, uint32_t e, uint32_t par, bool& ok) -> uint32_t {
+    if (e - b == 1) {
+      if (nodes[b].entry_index < HK_BVH_LEAF_FLAG || nodes[b].exit_index != e || next_leaf >= n_tris) { ok = false; return 0; }
+      const uint32_t shape = nodes[b].entry_index - HK_BVH_LEAF_FLAG;
+      if (shape >= n_tris || shape_seen[shape]) { ok = false; return 0; }
+      shape_seen[shape] = 1;
+      leaf_shape[next_leaf] = shape;
+      leaf_parent[next_leaf] = par;
+      return ni + next_leaf++;
+    }
+    const uint32_t a = b, bb = nodes[a].exit_index;
+    if (next_internal >= ni || nodes[a].entry_index != a + 1 || !(bb > a + 1 && bb < e) || nodes[bb].entry_index != bb + 1 || nodes[bb].exit_index != e) { ok = false; return 0; }
+    const uint32_t id = next_internal++;
+    parent[id] = par;
+    first[id] = next_leaf;
+    stack.push_back({b, e, id, 0, bb});
+    return id;
+  };
+  bool ok = true;
+  if (n_tris == 1) {
+    (void)open(0, 1, HK_U32_MAX, ok);
+    return ok && next_leaf == 1;
+  }
+  (void)open(0, count, HK_U32_MAX, ok);
+  while (ok && !stack.empty()) {
+    Frame& f = stack.back();
+    if (f.stage == 0) {
+      f.stage = 1;
+      const uint32_t id = f.id, b = f.b, bb = f.second;
+      left[id] = open(b + 1, bb, id, ok);
+    } else if (f.stage == 1) {
+      f.stage = 2;
+      const uint32_t id = f.id, bb = f.second, e = f.e;
+      right[id] = open(bb + 1, e, id, ok);
+    } else {
+      last[f.id] = next_leaf - 1;
+      stack.pop_back();
+    }
+  }
+  return ok && next_internal == ni && next_leaf == n_tris;
+}
+
+// the deformable mesh named by `m` (created on first use); validates the record against the uploaded instances and the tree
+int find_mesh(hk_ctx* c, const HkMeshIndex* m, DeformMesh** out) {
+  bool known = false;
+  uint32_t next_vertex = (uint32_t)c->vertices.size();
+  for (const HkInstance& in : c->instances) {
+    if (memcmp(&in.mesh, m, sizeof(HkMeshIndex)) == 0) known = true;
+    if (in.mesh.vertex > m->vertex) next_vertex = std::min(next_vertex, in.mesh.vertex);
+  }
+  HK_REQUIRE(known, HK_E_INVALID, "no uploaded instance carries the mesh record (%u, %u, %u, %u)", m->vertex, m->primitive, m->node_offset, m->node_count);
+  for (DeformMesh* d : c->deform)
+    if (memcmp(&d->mesh, m, sizeof(HkMeshIndex)) == 0) { *out = d; return HK_OK; }
+  HK_REQUIRE(m->node_count >= 1 && (m->node_count + 2) % 3 == 0, HK_E_UNSUPPORTED, "the mesh tree is not a binary tree in the flatten_custom layout (%u nodes)", m->node_count);
+  const uint32_t n_tris = (m->node_count + 2) / 3;
+  HK_REQUIRE((size_t)m->primitive + n_tris <= c->primitives.size() && (size_t)m->node_offset + m->node_count <= c->asset_nodes.size() && m->vertex < c->vertices.size(),
+             HK_E_INVALID, "the mesh record lies outside the uploaded mesh arrays");
+  uint32_t max_ref = 0;
+  for (uint32_t t = 0; t < n_tris; ++t)
+    for (int k = 0; k < 3; ++k) max_ref = std::max(max_ref, c->primitives[m->primitive + t].vertices[k].index);
+  HK_REQUIRE((size_t)m->vertex + max_ref < next_vertex, HK_E_INVALID, "the mesh's triangles name vertices beyond the mesh");
+  std::vector<uint32_t> parent, left, right, first, last, leaf_parent, leaf_shape;
+  HK_REQUIRE(mesh_topology(c->asset_nodes.data() + m->node_offset, m->node_count, n_tris, parent, left, right, first, last, leaf_parent, leaf_shape), HK_E_UNSUPPORTED,
+             "the mesh tree is not a binary tree in the flatten_custom layout");
+  DeformMesh* d = new (std::nothrow) DeformMesh();
+  HK_REQUIRE(d, HK_E_NOMEM, "allocation failed");
+  d->mesh = *m;
+  d->n_tris = n_tris;
+  d->min_vertices = d->max_vertices = max_ref + 1;  // the vertices the mesh's triangles span: nothing beyond them is ever written
+  const size_t n = n_tris, ni = std::max<size_t>(n - 1, 1), nv = d->max_vertices;
+  (void)next_vertex;
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t bytes = al(5 * ni * 4) + al(2 * n * 4) + al(ni * 4) + al(ni) + 2 * al((2 * n - 1) * 16) + 2 * al(n * 16) + al(nv * 16) + al(32);
+  if (hipMalloc(&d->mem, bytes) != hipSuccess) {
+    delete d;
+    HK_REQUIRE(false, HK_E_NOMEM, "device allocation of %zu bytes failed", bytes);
+  }
+  uint8_t* p = (uint8_t*)d->mem;
+  auto take = [&](size_t b) { uint8_t* q = p; p += al(b); return q; };
+  uint32_t* topo = (uint32_t*)take(5 * ni * 4);
+  d->tree.n = n_tris;
+  d->tree.parent = topo; d->tree.left = topo + ni; d->tree.right = topo + 2 * ni; d->tree.first = topo + 3 * ni; d->tree.last = topo + 4 * ni;
+  uint32_t* leaves = (uint32_t*)take(2 * n * 4);
+  d->tree.leaf_parent = leaves; d->tree.leaf_shape = leaves + n;
+  d->tree.arrived = (uint32_t*)take(ni * 4);
+  d->tree.swap = take(ni);
+  d->tree.node_lo = (float4*)take((2 * n - 1) * 16);
+  d->tree.node_hi = (float4*)take((2 * n - 1) * 16);
+  d->tree.tri_lo = (float4*)take(n * 16);
+  d->tree.tri_hi = (float4*)take(n * 16);
+  d->pos = (float4*)take(nv * 16);
+  d->box = (uint32_t*)take(32);
+  c->deform.push_back(d);  // (owned by the context from here on, freed by free_deform)
+  std::vector<uint32_t> host(5 * ni + 2 * n, 0);
+  auto put = [&](const std::vector<uint32_t>& v, size_t at) { std::copy(v.begin(), v.end(), host.begin() + at); };
+  put(parent, 0); put(left, ni); put(right, 2 * ni); put(first, 3 * ni); put(last, 4 * ni);
+  HK_HIP(hipMemcpy(topo, host.data(), 5 * ni * 4, hipMemcpyHostToDevice));
+  std::copy(leaf_parent.begin(), leaf_parent.end(), host.begin());
+  std::copy(leaf_shape.begin(), leaf_shape.end(), host.begin() + n);
+  HK_HIP(hipMemcpy(leaves, host.data(), 2 * n * 4, hipMemcpyHostToDevice));
+  *out = d;
+  return HK_OK;
+}
+
+// the instances of the mesh (emitters first) as the uploaded scene has them; redone after every hk_upload_instances
+int mesh_instances(hk_ctx* c, DeformMesh* d) {
+  if (d->ids_generation == c->instances_generation) return HK_OK;
+  std::vector<uint8_t> is_emitter(c->instances.size(), 0);
+  for (const HkEmissive& e : c->emissives)
+    if (e.instance < c->instances.size()) is_emitter[e.instance] = 1;
+  std::vector<uint32_t> ids;
+  for (int pass = 0; pass < 2; ++pass)
+    for (uint32_t i = 0; i < c->instances.size(); ++i)
+      if (memcmp(&c->instances[i].mesh, &d->mesh, sizeof(HkMeshIndex)) == 0 && is_emitter[i] == (pass == 0 ? 1 : 0)) ids.push_back(i);
+  uint32_t n_emitters = 0;
+  for (uint32_t i : ids) n_emitters += is_emitter[i];
+  if (ids.size() > d->n_ids || !d->ids) {  // (grows rarely: the old arrays may still be read by what is enqueued)
+    int rc = sync_all(c);
+    if (rc) return rc;
+    if (d->ids) (void)hipFree(d->ids);
+    d->ids = nullptr;
+    d->records = nullptr;
+    d->n_ids = 0;
+    const size_t cap = std::max<size_t>(ids.size(), 1);
+    HK_HIP(hipMalloc((void**)&d->ids, cap * (4 + sizeof(RefitUpdate)) + 256));
+    d->records = (RefitUpdate*)((uint8_t*)d->ids + ((cap * 4 + 255) & ~(size_t)255));
+  } else {
+    int rc = sync_all(c);
+    if (rc) return rc;
+  }
+  if (!ids.empty()) HK_HIP(hipMemcpy(d->ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
+  d->n_ids = (uint32_t)ids.size();
+  d->n_emitters = n_emitters;
+  d->ids_generation = c->instances_generation;
+  return HK_OK;
+}
+
+// a pinned staging buffer of at least `bytes`: one whose last reader has passed (hipEventQuery: no host wait), or a new one
+int stage(hk_ctx* c, size_t bytes, uint8_t** out, int* k_out) {
+  int k = -1;
+  for (size_t i = 0; i < c->df_stage.size() && k < 0; ++i) {
+    hk_ctx::DeformStage& s = c->df_stage[i];
+    if (s.pending && hipEventQuery(s.done) != hipSuccess) continue;
+    s.pending = false;
+    if (s.cap >= bytes) k = (int)i;
+  }
+  if (k < 0) {
+    for (size_t i = 0; i < c->df_stage.size() && k < 0; ++i)
+      if (!c->df_stage[i].pending) k = (int)i;  // (free but too small: grown below)
+    if (k < 0) {
+      c->df_stage.emplace_back();
+      k = (int)c->df_stage.size() - 1;
+    }
+    hk_ctx::DeformStage& s = c->df_stage[(size_t)k];
+    if (s.p) (void)hipHostFree(s.p);
+    s.p = nullptr;
+    s.cap = 0;
+    const size_t cap = bytes + bytes / 4 + 256;
+    HK_HIP(hipHostMalloc((void**)&s.p, cap, hipHostMallocDefault));
+    s.cap = cap;
+  }
+  hk_ctx::DeformStage& s = c->df_stage[(size_t)k];
+  if (!s.done) HK_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+  *out = s.p;
+  *k_out = k;
+  return HK_OK;
+}
+
+// common front of the three calls: the scene as laid out, the refit's side arrays, the mesh
+int begin(hk_ctx* c, const HkMeshIndex* m, DeformMesh** d) {
+  HK_REQUIRE(c->have_meshes && c->have_materials && c->have_instances, HK_E_NOT_READY, "hk_upload_scene must come first");
+  HK_HIP(hipSetDevice(c->device));
+  int rc;
+  if ((rc = finalize_scene(c))) return rc;
+  if ((rc = find_mesh(c, m, d))) return rc;
+  return mesh_instances(c, *d);
+}
+
+// the device work after the vertices of `d` are in `d->pos` (and its normals in the normal plane): triangles, the mesh tree in every
+// ordering.  The instance level follows once for all meshes deformed before the next frame (flush_deform).
+int refit_mesh(hk_ctx* c, DeformMesh* d) {
+  const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
+  uint8_t* sbase = c->scene_mem + slots;
+  const uint32_t p0 = d->mesh.primitive;
+  launch_mesh_triangles(c->stream, d->pos, (float4*)(sbase + c->st_v0) + p0, (float4*)(sbase + c->st_v1) + p0, (float4*)(sbase + c->st_v2) + p0, d->n_tris, d->tree.tri_lo,
+                        d->tree.tri_hi);
+  const size_t n_nodes = c->asset_nodes.size();
+  launch_mesh_tree_refit(c->stream, d->tree, (float4*)(sbase + c->st_nodes) + 2 * (size_t)d->mesh.node_offset, 2 * n_nodes, c->threaded ? 8u : 1u);
+  HK_HIP(hipGetLastError());
+  d->deformed = d->pending = true;
+  c->deform_pending = true;
+  return HK_OK;
+}
+
+// one deformation: `fill` enqueues the vertex kernel (positions into d->pos, normals into the normal plane, the mesh box into d->box)
+template <typename Fill>
+int deform(hk_ctx* c, DeformMesh* d, int k, Fill fill) {
+  int rc;
+  // the mesh-level region has ONE copy: the writes go behind every frame enqueued so far on every stream that reads the scene (the
+  // side stream's direct-light dispatches, the post stream; the pipelined primary rays are behind the main stream already) - stream
+  // waits, not host waits
+  if ((rc = join_all(c))) return rc;
+  const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
+  float4* vn = (float4*)(c->scene_mem + slots + c->st_vn) + d->mesh.vertex;
+  HK_HIP(hipMemsetAsync(d->box, 0xFF, 12, c->stream));
+  HK_HIP(hipMemsetAsync(d->box + 3, 0, 12, c->stream));
+  fill(vn);
+  HK_HIP(hipGetLastError());
+  if ((rc = refit_mesh(c, d))) return rc;
+  hk_ctx::DeformStage& st = c->df_stage[(size_t)k];
+  HK_HIP(hipEventRecord(st.done, c->stream));
+  st.pending = true;
+  c->meshes_deformed = true;
+  c->mirrors_stale = true;
+  update_shared_transform(c);  // (the one-level tree is not walked from here on)
+  // the wide records of this mesh tree are derived again (context.hip ensure_wide), the instance tree's too
+  const std::pair<uint32_t, uint32_t> key(d->mesh.node_offset, d->mesh.node_count);
+  c->wide_meshes.erase(std::remove(c->wide_meshes.begin(), c->wide_meshes.end(), key), c->wide_meshes.end());
+  c->wide_mesh_check = true;
+  c->wide_tlas_dirty = true;
+  return HK_OK;
+}
+
+// the new boxes of the meshes selected by `which` to their instances and emitters, then ONE refit of the instance tree and the light tree
+template <typename Which>
+int propagate(hk_ctx* c, Which which) {
+  const hkd::RefitScene r = refit_scene(c);
+  uint8_t* base = c->scene_mem + (size_t)c->slot * c->dyn_capacity;
+  for (DeformMesh* d : c->deform) {
+    if (!which(d)) continue;
+    int rc = mesh_instances(c, d);
+    if (rc) return rc;
+    launch_mesh_propagate(c->stream, r, d->box, d->ids, d->n_ids, d->records, d->n_emitters, d->n_tris, nullptr, 0u, 1u, nullptr, nullptr, 0u);
+    d->pending = false;
+  }
+  launch_mesh_propagate(c->stream, r, nullptr, nullptr, 0u, nullptr, 0u, 0u, (float4*)(base + c->dyn_off.tlas), (uint32_t)c->instance_nodes.size(), c->threaded ? 8u : 1u,
+                        (float4*)(base + c->dyn_off.light_lo), (float4*)(base + c->dyn_off.light_hi), (uint32_t)c->emissive_nodes.size());
+  HK_HIP(hipGetLastError());
+  c->deform_pending = false;
+  return HK_OK;
+}
+}  // namespace
+
+// hk_refit_scene_instances has just refit the instance level from the builder's mesh boxes: every deformed mesh's device box again
+int hk::repropagate_deformed(hk_ctx* c) { return propagate(c, [](const DeformMesh* d) { return d->deformed; }); }
+
+// Once before whatever reads the instance level next (context.hip ready: every frame path; hk_rebuild_scene_trees; the read hooks):
+// the instances, emitters and trees of every mesh deformed since the last flush, however many deformation calls came in between.
+int hk::flush_deform(hk_ctx* c) {
+  if (!c->deform_pending) return HK_OK;
+  int rc;
+  if ((rc = prepare_refit(c))) return rc;
+  if ((rc = begin_device_update(c))) return rc;   // (frames in flight keep the instance-level slot they were enqueued with)
+  return propagate(c, [](const DeformMesh* d) { return d->pending; });
+}
+
+extern "C" {
+
+int hk_update_mesh_vertices(hk_ctx* c, const HkMeshIndex* mesh, uint32_t n_vertices, const float* positions, const float* normals) {
+  if (c) c->scene_epoch += 1;   // (scene memory is written: hk_context.hpp, primary-ray pipelining)
+  HK_REQUIRE(c && mesh && positions && n_vertices, HK_E_INVALID, "NULL argument or no vertices");
+  DeformMesh* d = nullptr;
+  int rc;
+  if ((rc = begin(c, mesh, &d))) return rc;
+  HK_REQUIRE(n_vertices >= d->min_vertices && n_vertices <= d->max_vertices, HK_E_INVALID, "the mesh has between %u and %u vertices, not %u", d->min_vertices,
+             d->max_vertices, n_vertices);
+  uint8_t* st = nullptr;
+  int k = 0;
+  const size_t plane = (size_t)n_vertices * 12, nplane = (plane + 15) & ~(size_t)15;
+  if ((rc = stage(c, nplane + (normals ? plane : 0), &st, &k))) return rc;
+  memcpy(st, positions, plane);
+  if (normals) memcpy(st + nplane, normals, plane);
+  d->n_vertices = n_vertices;
+  return deform(c, d, k, [&](float4* vn) {
+    launch_mesh_stage(c->stream, (const float*)st, normals ? (const float*)(st + nplane) : nullptr, n_vertices, d->pos, vn, d->box);
+  });
+}
+
+int hk_set_mesh_skin(hk_ctx* c, const HkMeshIndex* mesh, uint32_t n_vertices, const float* bind_positions, const float* bind_normals, const uint16_t* joint_indices,
+                     const float* joint_weights) {
+  HK_REQUIRE(c && mesh && bind_positions && bind_normals && joint_indices && joint_weights && n_vertices, HK_E_INVALID, "NULL argument or no vertices");
+  DeformMesh* d = nullptr;
+  int rc;
+  if ((rc = begin(c, mesh, &d))) return rc;
+  HK_REQUIRE(n_vertices >= d->min_vertices && n_vertices <= d->max_vertices, HK_E_INVALID, "the mesh has between %u and %u vertices, not %u", d->min_vertices,
+             d->max_vertices, n_vertices);
+  const size_t n = n_vertices;
+  std::vector<float4> bp(n), bn(n), w(n);
+  std::vector<uint2> j(n);
+  uint32_t max_joint = 0;
+  for (size_t v = 0; v < n; ++v) {
+    bp[v] = make_float4(bind_positions[3 * v], bind_positions[3 * v + 1], bind_positions[3 * v + 2], 0.0f);
+    bn[v] = make_float4(bind_normals[3 * v], bind_normals[3 * v + 1], bind_normals[3 * v + 2], 0.0f);
+    w[v] = make_float4(joint_weights[4 * v], joint_weights[4 * v + 1], joint_weights[4 * v + 2], joint_weights[4 * v + 3]);
+    const uint16_t* q = joint_indices + 4 * v;
+    j[v] = make_uint2((uint32_t)q[0] | ((uint32_t)q[1] << 16), (uint32_t)q[2] | ((uint32_t)q[3] << 16));
+    for (int t = 0; t < 4; ++t) max_joint = std::max<uint32_t>(max_joint, q[t]);
+  }
+  if ((rc = sync_all(c))) return rc;  // (a skin set again: the kernels enqueued so far may still read the old one)
+  if (d->skin_mem) (void)hipFree(d->skin_mem);
+  d->skin_mem = nullptr;
+  d->skin_vertices = 0;
+  HK_HIP(hipMalloc(&d->skin_mem, n * (16 * 3 + 8)));
+  d->bind_pos = (float4*)d->skin_mem;
+  d->bind_nrm = d->bind_pos + n;
+  d->weights = d->bind_nrm + n;
+  d->joints = (uint2*)(d->weights + n);
+  HK_HIP(hipMemcpy(d->bind_pos, bp.data(), n * 16, hipMemcpyHostToDevice));
+  HK_HIP(hipMemcpy(d->bind_nrm, bn.data(), n * 16, hipMemcpyHostToDevice));
+  HK_HIP(hipMemcpy(d->weights, w.data(), n * 16, hipMemcpyHostToDevice));
+  HK_HIP(hipMemcpy(d->joints, j.data(), n * 8, hipMemcpyHostToDevice));
+  d->skin_vertices = n_vertices;
+  d->max_joint = max_joint;
+  return HK_OK;
+}
+
+int hk_skin_mesh(hk_ctx* c, const HkMeshIndex* mesh, const float* joint_matrices, uint32_t n_joints) {
+  if (c) c->scene_epoch += 1;   // (scene memory is written: hk_context.hpp, primary-ray pipelining)
+  HK_REQUIRE(c && mesh && joint_matrices && n_joints, HK_E_INVALID, "NULL argument or no joints");
+  DeformMesh* d = nullptr;
+  for (DeformMesh* q : c->deform)
+    if (memcmp(&q->mesh, mesh, sizeof(HkMeshIndex)) == 0) d = q;
+  HK_REQUIRE(d && d->skin_vertices, HK_E_INVALID, "no skin set for this mesh (hk_set_mesh_skin)");
+  HK_REQUIRE(d->max_joint < n_joints, HK_E_INVALID, "the skin names joint %u but only %u joint matrices were given", d->max_joint, n_joints);
+  int rc;
+  if ((rc = begin(c, mesh, &d))) return rc;
+  if (n_joints > d->joint_cap) {
+    if ((rc = sync_all(c))) return rc;
+    if (d->joint_mats) (void)hipFree(d->joint_mats);
+    d->joint_mats = nullptr;
+    d->joint_cap = 0;
+    HK_HIP(hipMalloc((void**)&d->joint_mats, (size_t)n_joints * 64));
+    d->joint_cap = n_joints;
+  }
+  uint8_t* st = nullptr;
+  int k = 0;
+  if ((rc = stage(c, (size_t)n_joints * 64, &st, &k))) return rc;
+  memcpy(st, joint_matrices, (size_t)n_joints * 64);
+  d->n_vertices = d->skin_vertices;
+  return deform(c, d, k, [&](float4* vn) {
+    launch_copy_region(c->stream, d->joint_mats, st, (size_t)n_joints * 64);  // (a copy kernel: the matrices are read per vertex)
+    launch_mesh_skin(c->stream, d->bind_pos, d->bind_nrm, d->joints, d->weights, d->joint_mats, d->skin_vertices, d->pos, vn, d->box);
+  });
+}
+
+// Test hook (hikari_hip_debug.h): the emitter records and the alias table of the slot in use
+int hk_debug_read_emitters(hk_ctx* c, float* records, uint32_t records_cap, uint32_t* n_records, float* alias, uint32_t alias_cap, uint32_t* n_alias) {
+  HK_REQUIRE(c && n_records && n_alias, HK_E_INVALID, "NULL argument");
+  HK_HIP(hipSetDevice(c->device));
+  int rc;
+  if ((rc = finalize_scene(c))) return rc;
+  if ((rc = flush_deform(c))) return rc;
+  if ((rc = sync_all(c))) return rc;
+  const uint32_t ne = (uint32_t)c->emissives.size(), na = (uint32_t)c->alias_table.size();
+  *n_records = ne;
+  *n_alias = na;
+  if (!records && !alias) return HK_OK;
+  HK_REQUIRE(records && alias && records_cap >= ne && alias_cap >= na, HK_E_INVALID, "need room for %u records and %u alias entries", ne, na);
+  const uint8_t* base = c->scene_mem + (size_t)c->slot * c->dyn_capacity;
+  std::vector<DEmissive> de(ne);
+  if (ne) HK_HIP(hipMemcpy(de.data(), base + c->dyn_off.emissives, (size_t)ne * sizeof(DEmissive), hipMemcpyDeviceToHost));
+  for (uint32_t e = 0; e < ne; ++e) {
+    float* r = records + 8 * (size_t)e;
+    r[0] = de[e].position_radius.x; r[1] = de[e].position_radius.y; r[2] = de[e].position_radius.z; r[3] = de[e].position_radius.w;
+    r[4] = de[e].surface_area;
+    memcpy(r + 5, &de[e].instance, 4); memcpy(r + 6, &de[e].alias_offset, 4); memcpy(r + 7, &de[e].alias_count, 4);
+  }
+  if (na) HK_HIP(hipMemcpy(alias, base + c->dyn_off.alias, (size_t)na * 8, hipMemcpyDeviceToHost));
+  return HK_OK;
+}
+
+// Test hook (hikari_hip_debug.h): the mesh-level node array, every ordering
+int hk_debug_read_mesh_nodes(hk_ctx* c, HkNode* out, uint32_t cap, uint32_t* count, uint32_t* orderings) {
+  HK_REQUIRE(c && (out || !cap), HK_E_INVALID, "NULL argument");
+  HK_HIP(hipSetDevice(c->device));
+  int rc;
+  if ((rc = finalize_scene(c))) return rc;
+  if ((rc = sync_all(c))) return rc;
+  const uint32_t n = (uint32_t)c->asset_nodes.size(), o = c->threaded ? 8u : 1u;
+  if (count) *count = n;
+  if (orderings) *orderings = o;
+  if (!out) return HK_OK;
+  HK_REQUIRE(cap >= n * o, HK_E_INVALID, "need room for %u nodes", n * o);
+  const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
+  static_assert(sizeof(HkNode) == 32, "HkNode is two float4");
+  HK_HIP(hipMemcpy(out, c->scene_mem + slots + c->st_nodes, (size_t)n * o * 32, hipMemcpyDeviceToHost));
+  return HK_OK;
+}
+
+}  // extern "C"

@@ -522,6 +522,99 @@ int hk_scene_builder_set_instance_transform(hk_scene_builder* b, uint32_t instan
   return HK_OK;
 }
 
+// The host twin of the device refit (mesh_deform.hip): same topology, every navigator box the union of the triangle boxes below it -
+// a triangle's box with the leaf-box arithmetic of the device layout (scene_layout.hip build_static_region: IEEE min / max with -0 < +0),
+// the union of two children as std::min / std::max of (first child, second child), as kernels_scene.hip k_lbvh_boxes forms it.
+namespace {
+float leaf_min(float a, float b) {
+  if (a != a) return b;
+  if (b != b) return a;
+  if (a == b) return signbit(a) ? a : b;
+  return a < b ? a : b;
+}
+float leaf_max(float a, float b) {
+  if (a != a) return b;
+  if (b != b) return a;
+  if (a == b) return signbit(a) ? b : a;
+  return a > b ? a : b;
+}
+// every navigator box of a flatten_custom array refit, back to front (a navigator's subtree lies behind it: no recursion, whatever the
+// depth); false if the array is not in that layout
+bool refit_nodes(std::vector<HkNode>& nodes, const std::vector<HkPrimitive>& prims) {
+  const uint32_t n = (uint32_t)nodes.size();
+  if (n == 0) return false;
+  auto leaf = [&](uint32_t i) { return nodes[i].entry_index >= HK_BVH_LEAF_FLAG; };
+  if (n == 1) return leaf(0) && nodes[0].entry_index - HK_BVH_LEAF_FLAG < prims.size();
+  if (leaf(0) || nodes[0].exit_index >= n || nodes[nodes[0].exit_index].exit_index != n) return false;
+  std::vector<float> lo(3 * (size_t)n), hi(3 * (size_t)n);  // the box of the subtree that starts at node i
+  for (uint32_t i = n; i-- > 0;) {
+    HkNode& nd = nodes[i];
+    if (leaf(i)) {
+      if (nd.entry_index - HK_BVH_LEAF_FLAG >= prims.size() || nd.exit_index != i + 1) return false;
+      const HkPrimitiveVertex* v = prims[nd.entry_index - HK_BVH_LEAF_FLAG].vertices;
+      for (int k = 0; k < 3; ++k) {
+        lo[3 * i + k] = leaf_min(v[0].position[k], leaf_min(v[1].position[k], v[2].position[k]));
+        hi[3 * i + k] = leaf_max(v[0].position[k], leaf_max(v[1].position[k], v[2].position[k]));
+      }
+      continue;
+    }
+    const uint32_t a = i + 1, e = nd.exit_index;  // the subtree [a, e): one leaf, or [navigator a][..][navigator bb][..]
+    if (nd.entry_index != a || !(e > a && e <= n)) return false;
+    if (leaf(a)) {
+      if (e != a + 1) return false;
+      for (int k = 0; k < 3; ++k) { lo[3 * i + k] = lo[3 * a + k]; hi[3 * i + k] = hi[3 * a + k]; }
+    } else {
+      const uint32_t bb = nodes[a].exit_index;
+      if (!(bb > a + 1 && bb < e) || leaf(bb) || nodes[bb].entry_index != bb + 1 || nodes[bb].exit_index != e) return false;
+      for (int k = 0; k < 3; ++k) {
+        lo[3 * i + k] = std::min(lo[3 * a + k], lo[3 * bb + k]);
+        hi[3 * i + k] = std::max(hi[3 * a + k], hi[3 * bb + k]);
+      }
+    }
+    memcpy(nd.min, &lo[3 * i], 12);
+    memcpy(nd.max, &hi[3 * i], 12);
+  }
+  return true;
+}
+}  // namespace
+
+int hk_scene_builder_set_mesh_vertices(hk_scene_builder* b, uint32_t mesh_id, const float* positions, const float* normals) {
+  HK_REQUIRE(b && positions, HK_E_INVALID, "NULL argument");
+  HK_REQUIRE(mesh_id < b->meshes.size(), HK_E_INVALID, "unknown mesh id");
+  BuilderMesh mesh = b->meshes[mesh_id];  // (a copy: an error leaves the builder as it was)
+  for (size_t i = 0; i < mesh.vertices.size(); ++i)
+    for (int k = 0; k < 3; ++k) {
+      mesh.vertices[i].position[k] = positions[3 * i + k];
+      if (normals) mesh.vertices[i].normal[k] = normals[3 * i + k];
+    }
+  for (HkPrimitive& p : mesh.primitives)
+    for (int k = 0; k < 3; ++k) memcpy(p.vertices[k].position, mesh.vertices[p.vertices[k].index].position, 12);
+  HK_REQUIRE(refit_nodes(mesh.nodes, mesh.primitives), HK_E_UNSUPPORTED, "the mesh tree is not in the flatten_custom layout");
+  float mn[3], mx[3];
+  // the mesh box over all vertices, as the device reduces it (order-free: -0 < +0)
+  for (int k = 0; k < 3; ++k) mn[k] = mx[k] = mesh.vertices[0].position[k];
+  for (const HkVertex& v : mesh.vertices)
+    for (int k = 0; k < 3; ++k) {
+      mn[k] = leaf_min(mn[k], v.position[k]);
+      mx[k] = leaf_max(mx[k], v.position[k]);
+    }
+  for (int k = 0; k < 3; ++k) {  // bevy Aabb::from_min_max
+    mesh.aabb_center[k] = 0.5f * (mx[k] + mn[k]);
+    mesh.aabb_half[k] = 0.5f * (mx[k] - mn[k]);
+  }
+  b->meshes[mesh_id] = std::move(mesh);
+  b->meshes_dirty = true;
+  b->finished = false;
+  return HK_OK;
+}
+
+int hk_scene_builder_mesh_index(const hk_scene_builder* b, uint32_t mesh_id, HkMeshIndex* out) {
+  HK_REQUIRE(b && out, HK_E_INVALID, "NULL argument");
+  HK_REQUIRE(!b->meshes_dirty && mesh_id < b->mesh_index.size(), HK_E_INVALID, "unknown mesh id, or the builder was not finished since the mesh was added");
+  *out = b->mesh_index[mesh_id];
+  return HK_OK;
+}
+
 static int finish_impl(hk_scene_builder* b, bool build_trees);
 int hk_scene_builder_finish(hk_scene_builder* b) { return finish_impl(b, true); }
 int hk_scene_builder_finish_instances(hk_scene_builder* b) { return finish_impl(b, false); }

@@ -476,6 +476,8 @@ void update_shared_transform(hk_ctx* c) {
   // the one-level BVH lives in the shared LOCAL space: it stays valid while the instances move together and is simply not
   // walked once one of them moves on its own
   c->scene.flat_mode = (c->dyn_off.flat_count && c->scene.shared_xform) ? 1u : 0u;
+  // ... nor once a mesh deformed on the device: the tree was built over the host's triangles (hikari_hip.h hk_update_mesh_vertices)
+  if (c->meshes_deformed) c->scene.flat_mode = 0u;
 }
 
 // point c->scene at the arrays of the slot in use
@@ -546,6 +548,9 @@ int finalize_scene(hk_ctx* c) {
   HK_REQUIRE(!(c->mirrors_stale && c->dynamic_dirty), HK_E_NOT_READY,
              "the instance-level arrays were last changed on the device (hk_refit_scene_instances): upload the instances again (hk_upload_scene_instances) "
              "before a change that rebuilds them on the host");
+  HK_REQUIRE(!c->meshes_deformed, HK_E_NOT_READY,
+             "a mesh was deformed on the device (hk_update_mesh_vertices / hk_skin_mesh): upload the host's mirror of it (hk_upload_scene) "
+             "before a change that lays the scene out again on the host");
   Blob st;  // (the mesh-level region first: whether the one-level BVH still fits the LDS copy depends on its size)
   if (need_static && (rc = build_static_region(c, st, c->st_nodes, c->st_v0, c->st_v1, c->st_v2, c->st_vn, c->st_vuv))) return rc;
   Blob& dyn = c->dyn_blob;
@@ -635,6 +640,12 @@ extern "C" {
 int hk_upload_meshes(hk_ctx* c, const HkVertex* v, uint32_t nv, const HkPrimitive* p, uint32_t np, const HkNode* n, uint32_t nn) {
   if (c) c->scene_epoch += 1;   // (scene memory is written: hk_context.hpp, primary-ray pipelining)
   HK_REQUIRE(c && v && p && n && nv && np && nn, HK_E_INVALID, "NULL or empty mesh buffers");
+  if (!c->deform.empty()) {  // (the trees and skins of the deformable meshes name the old topology; frames in flight may still use them)
+    const int rc = sync_all(c);
+    if (rc) return rc;
+    free_deform(c);
+  }
+  c->meshes_deformed = false;
   c->vertices.assign(v, v + nv);
   c->primitives.assign(p, p + np);
   c->asset_nodes.assign(n, n + nn);
@@ -655,12 +666,14 @@ int hk_upload_instances(hk_ctx* c, const HkInstance* inst, uint32_t ni, const Hk
   if (c) c->scene_epoch += 1;   // (scene memory is written: hk_context.hpp, primary-ray pipelining)
   HK_REQUIRE(c && inst && inodes && ni && nin, HK_E_INVALID, "NULL or empty instance buffers");
   HK_REQUIRE((em || !ne) && (enodes || !nen) && (alias || !na), HK_E_INVALID, "NULL emissive buffers");
+  HK_REQUIRE(!c->meshes_deformed, HK_E_NOT_READY, "a mesh was deformed on the device: upload the host's mirror of it (hk_upload_scene) first");
   c->instances.assign(inst, inst + ni);
   c->instance_nodes.assign(inodes, inodes + nin);
   c->emissives.assign(em, em + ne);
   c->emissive_nodes.assign(enodes, enodes + nen);
   c->alias_table.assign(alias, alias + na);
   c->prev_models.clear();
+  c->instances_generation += 1;
   c->have_instances = true;
   c->dynamic_dirty = true;
   c->mirrors_stale = false;

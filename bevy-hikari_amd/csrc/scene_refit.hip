@@ -17,6 +17,7 @@ int hk_update_scene_instances(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode
   if (c) c->scene_epoch += 1;   // (scene memory is written: hk_context.hpp, primary-ray pipelining)
   HK_REQUIRE(c && b, HK_E_INVALID, "NULL argument");
   HK_REQUIRE(tree_mode == HK_TREE_SAH || tree_mode == HK_TREE_LBVH, HK_E_INVALID, "unknown tree build mode %u", tree_mode);
+  HK_REQUIRE(!c->meshes_deformed, HK_E_NOT_READY, "a mesh was deformed on the device: upload the host's mirror of it (hk_upload_scene) first");
   int rc;
   const bool trace = c->trace_update;
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -125,12 +126,9 @@ int prepare_refit(hk_ctx* c) {
   return HK_OK;
 }
 }  // namespace hk
-extern "C" {
-
-namespace {
 // frames in flight keep reading the slot they were enqueued with: a device-side update works on a copy in the spare slot
 // (two-slot scenes), or in place behind everything enqueued so far (scenes small enough for the LDS copy have one slot)
-int begin_device_update(hk_ctx* c) {
+int hk::begin_device_update(hk_ctx* c) {
   const int rc = join_side(c);
   if (rc) return rc;
   if (c->two_slots) {
@@ -144,7 +142,7 @@ int begin_device_update(hk_ctx* c) {
   }
   return HK_OK;
 }
-}  // namespace
+extern "C" {
 
 int hk_rebuild_scene_trees(hk_ctx* c, uint32_t mode) {
   if (c) c->scene_epoch += 1;   // (scene memory is written: hk_context.hpp, primary-ray pipelining)
@@ -154,6 +152,7 @@ int hk_rebuild_scene_trees(hk_ctx* c, uint32_t mode) {
   HK_HIP(hipSetDevice(c->device));
   int rc;
   if ((rc = finalize_scene(c))) return rc;
+  if ((rc = flush_deform(c))) return rc;   // (the trees are built over the instances' current boxes)
   const uint32_t ni = (uint32_t)c->instances.size(), ne = (uint32_t)c->emissives.size();
   HK_REQUIRE(c->instance_nodes.size() == 3 * (size_t)ni - 2 && (ne == 0 || c->emissive_nodes.size() == 3 * (size_t)ne - 2), HK_E_UNSUPPORTED,
              "the uploaded trees are not in the flatten_custom layout of a binary tree (3n - 2 nodes): nothing to rebuild in place");
@@ -189,6 +188,7 @@ int hk_debug_read_trees(hk_ctx* c, HkNode* tlas, uint32_t tlas_cap, HkNode* ligh
   HK_HIP(hipSetDevice(c->device));
   int rc;
   if ((rc = finalize_scene(c))) return rc;
+  if ((rc = flush_deform(c))) return rc;
   if ((rc = sync_all(c))) return rc;
   const uint32_t nt = (uint32_t)c->instance_nodes.size(), nl = (uint32_t)c->emissive_nodes.size();
   HK_REQUIRE(tlas_cap >= nt && light_cap >= nl, HK_E_INVALID, "need room for %u + %u nodes", nt, nl);
@@ -306,6 +306,8 @@ static int refit_impl(hk_ctx* c, hk_scene_builder* b, uint32_t* moved_out, bool 
   launch_refit(c->stream, r, c->rf_updates[k], (uint32_t)records.size(), n_emitter_updates, emitter_triangles, nullptr, (float4*)(base + c->dyn_off.tlas), (uint32_t)c->instance_nodes.size(),
                c->threaded ? 8u : 1u, (float4*)(base + c->dyn_off.light_lo), (float4*)(base + c->dyn_off.light_hi), (uint32_t)c->emissive_nodes.size());
   HK_HIP(hipGetLastError());
+  // a deformed mesh's box is the device's, not the builder's: its instances' boxes, emitters and both trees once more from it
+  if (c->meshes_deformed && (rc = repropagate_deformed(c))) return rc;
   HK_HIP(hipEventRecord(c->rf_done[k], c->stream));
   c->rf_pending[k] = true;
   // the update is enqueued: now the host mirrors of the moved instances follow (an error above leaves host and device agreeing)

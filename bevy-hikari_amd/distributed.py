@@ -492,6 +492,25 @@ class MultiEngine:
     def rebuild_trees(self, mode=F.TREE_SAH):
         self.api.call("multi_rebuild_scene_trees", self.h, mode)
 
+    def update_mesh_vertices(self, mesh, positions, normals=None):
+        """hk_multi_update_mesh_vertices: the same deformation on every band's copy of the scene."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        self.api.call("multi_update_mesh_vertices", self.h, C.byref(mesh), len(pos), pos.ctypes.data_as(C.POINTER(F.f32)),
+                      None if nrm is None else nrm.ctypes.data_as(C.POINTER(F.f32)))
+
+    def set_mesh_skin(self, mesh, bind_positions, bind_normals, joint_indices, joint_weights):
+        pos = np.ascontiguousarray(bind_positions, dtype=np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(bind_normals, dtype=np.float32).reshape(-1, 3)
+        idx = np.ascontiguousarray(joint_indices, dtype=np.uint16).reshape(-1, 4)
+        w = np.ascontiguousarray(joint_weights, dtype=np.float32).reshape(-1, 4)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(F.f32))
+        self.api.call("multi_set_mesh_skin", self.h, C.byref(mesh), len(pos), fp(pos), fp(nrm), idx.ctypes.data_as(C.POINTER(C.c_uint16)), fp(w))
+
+    def skin_mesh(self, mesh, joint_matrices):
+        j = np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1, 16)
+        self.api.call("multi_skin_mesh", self.h, C.byref(mesh), j.ctypes.data_as(C.POINTER(F.f32)), len(j))
+
     def update_instances_on_device(self, builder, mode=F.TREE_SAH):
         self.api.call("multi_update_scene_instances", self.h, builder.h, mode)
 

@@ -306,6 +306,7 @@ class SceneBuilder:
         self.api = F.api()
         self.h = C.c_void_p()
         self.api.call("scene_builder_create", C.byref(self.h))
+        self.mesh_vertices = []  # vertex count per mesh id (set_mesh_vertices checks its arrays against it)
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -317,6 +318,7 @@ class SceneBuilder:
         nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
         uv = np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1, 2)
         out = F.u32()
+        self.mesh_vertices.append(len(pos))
         fp = lambda a: a.ctypes.data_as(C.POINTER(F.f32))
         if indices is None:
             self.api.call("scene_builder_add_mesh", self.h, fp(pos), fp(nrm), fp(uv), len(pos), None, 0, topology, C.byref(out))
@@ -348,6 +350,22 @@ class SceneBuilder:
 
     def set_instance_material(self, instance_id, material_id):
         self.api.call("scene_builder_set_instance_material", self.h, instance_id, material_id)
+
+    def set_mesh_vertices(self, mesh_id, positions, normals=None):
+        """The host mirror of a deformation (hk_scene_builder_set_mesh_vertices): same topology, tree boxes refit; finish() + upload next."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1)
+        nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1)
+        n = self.mesh_vertices[mesh_id] if 0 <= mesh_id < len(self.mesh_vertices) else None
+        if n is None or len(pos) != 3 * n or (nrm is not None and len(nrm) != 3 * n):
+            raise ValueError(f"mesh {mesh_id}: expected {n} positions (and normals) of 3 floats")
+        self.api.call("scene_builder_set_mesh_vertices", self.h, mesh_id, pos.ctypes.data_as(C.POINTER(F.f32)),
+                      None if nrm is None else nrm.ctypes.data_as(C.POINTER(F.f32)))
+
+    def mesh_index(self, mesh_id):
+        """The HkMeshIndex of a mesh after a finish (what Engine.update_mesh_vertices / skin_mesh take)."""
+        out = F.HkMeshIndex()
+        self.api.call("scene_builder_mesh_index", self.h, mesh_id, C.byref(out))
+        return out
 
     def finish(self, build_trees=True):
         """hk_scene_builder_finish; build_trees=False: hk_scene_builder_finish_instances (stand-in trees, for a device-side build)."""
@@ -458,6 +476,49 @@ class Engine:
         """New instance tree and light tree over the current boxes, built on the device (hk_rebuild_scene_trees): F.TREE_SAH = the
         reference's own binned-SAH tree, F.TREE_LBVH = the quick Morton-order tree."""
         self.api.call("rebuild_scene_trees", self.ctx, mode)
+
+    def update_mesh_vertices(self, mesh, positions, normals=None):
+        """New positions (and normals, None = keep) of one uploaded mesh, written and refit on the device (hk_update_mesh_vertices)."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if nrm is not None and nrm.shape != pos.shape:
+            raise ValueError("normals must match positions")
+        self.api.call("update_mesh_vertices", self.ctx, C.byref(mesh), len(pos), pos.ctypes.data_as(C.POINTER(F.f32)),
+                      None if nrm is None else nrm.ctypes.data_as(C.POINTER(F.f32)))
+
+    def set_mesh_skin(self, mesh, bind_positions, bind_normals, joint_indices, joint_weights):
+        """Linear-blend skin of one uploaded mesh (hk_set_mesh_skin): bind pose, 4 joint indices (uint16) and 4 weights per vertex."""
+        pos = np.ascontiguousarray(bind_positions, dtype=np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(bind_normals, dtype=np.float32).reshape(-1, 3)
+        idx = np.ascontiguousarray(joint_indices, dtype=np.uint16).reshape(-1, 4)
+        w = np.ascontiguousarray(joint_weights, dtype=np.float32).reshape(-1, 4)
+        if not (len(pos) == len(nrm) == len(idx) == len(w)):
+            raise ValueError("bind positions, normals, joint indices and weights must have one row per vertex")
+        fp = lambda a: a.ctypes.data_as(C.POINTER(F.f32))
+        self.api.call("set_mesh_skin", self.ctx, C.byref(mesh), len(pos), fp(pos), fp(nrm), idx.ctypes.data_as(C.POINTER(C.c_uint16)), fp(w))
+
+    def skin_mesh(self, mesh, joint_matrices):
+        """Per frame: column-major 4x4 joint matrices (n x 16 floats); the device skins and refits (hk_skin_mesh)."""
+        j = np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1, 16)
+        self.api.call("skin_mesh", self.ctx, C.byref(mesh), j.ctypes.data_as(C.POINTER(F.f32)), len(j))
+
+    def read_mesh_nodes(self):
+        """(nodes, count, orderings): the mesh-level node array as the device holds it, every ordering (test hook)."""
+        n, o = F.u32(), F.u32()
+        self.api.call("debug_read_mesh_nodes", self.ctx, None, 0, C.byref(n), C.byref(o))
+        out = (F.HkNode * max(1, n.value * o.value))()
+        self.api.call("debug_read_mesh_nodes", self.ctx, out, n.value * o.value, C.byref(n), C.byref(o))
+        return out, n.value, o.value
+
+    def read_emitters(self):
+        """(records float32[n][8]: position xyz, radius, surface area, instance / alias offset / alias count as u32 bits; alias float32[m][2]:
+        probability, index bits) as the device holds them (test hook)."""
+        n, m = F.u32(), F.u32()
+        self.api.call("debug_read_emitters", self.ctx, None, 0, C.byref(n), None, 0, C.byref(m))
+        rec, al = np.zeros((max(1, n.value), 8), np.float32), np.zeros((max(1, m.value), 2), np.float32)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(F.f32))
+        self.api.call("debug_read_emitters", self.ctx, fp(rec), n.value, C.byref(n), fp(al), m.value, C.byref(m))
+        return rec[:n.value], al[:m.value]
 
     def read_trees(self, n_instance_nodes, n_emissive_nodes):
         """(instance_nodes, emissive_nodes) as the device holds them, in the reference layout (test hook)."""

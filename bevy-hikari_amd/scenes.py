@@ -267,3 +267,136 @@ def flight_helmet_scene():
         return Camera(look_at_transform(eye, tuple(centre)), width, height)
 
     return scene, sun, camera
+
+
+# ---------------------------------------------------------------------------------------------
+# deforming meshes (hk_update_mesh_vertices / hk_skin_mesh): geometry and its motion, pure numpy
+# ---------------------------------------------------------------------------------------------
+def cloth_grid(nx=12, nz=12, size=1.0):
+    """A flat (nx x nz)-quad grid in the xz plane around the origin, +Y normals: positions, normals, uvs, indices."""
+    xs, zs = np.meshgrid(np.linspace(-0.5, 0.5, nx + 1), np.linspace(-0.5, 0.5, nz + 1), indexing="xy")
+    p = np.stack([xs * size, np.zeros_like(xs), zs * size], -1).reshape(-1, 3).astype(np.float32)
+    n = np.tile(np.array([0, 1, 0], np.float32), (len(p), 1))
+    uv = np.stack([xs + 0.5, zs + 0.5], -1).reshape(-1, 2).astype(np.float32)
+    idx = []
+    for j in range(nz):
+        for i in range(nx):
+            a, b, c, d = j * (nx + 1) + i, j * (nx + 1) + i + 1, (j + 1) * (nx + 1) + i, (j + 1) * (nx + 1) + i + 1
+            idx += [a, c, b, b, c, d]
+    return p, n, uv, np.array(idx, np.uint32)
+
+
+def waving_cloth(rest, frame, amplitude=0.08):
+    """The cloth's positions and normals at `frame`: a travelling wave along x (normals from the height field's gradient)."""
+    x, z = rest[:, 0].astype(np.float64), rest[:, 2].astype(np.float64)
+    ph = 0.6 * frame
+    h = amplitude * np.sin(6.0 * x + ph) * np.cos(4.0 * z + 0.5 * ph)
+    dx = amplitude * 6.0 * np.cos(6.0 * x + ph) * np.cos(4.0 * z + 0.5 * ph)
+    dz = -amplitude * 4.0 * np.sin(6.0 * x + ph) * np.sin(4.0 * z + 0.5 * ph)
+    p = rest.astype(np.float64).copy()
+    p[:, 1] += h
+    n = np.stack([-dx, np.ones_like(dx), -dz], -1)
+    n /= np.linalg.norm(n, axis=1, keepdims=True)
+    return p.astype(np.float32), n.astype(np.float32)
+
+
+def pulsing_sphere(rest, frame):
+    """The sphere's positions at `frame`: scaled by a pulse around its centre (the normals keep their directions)."""
+    return (rest * np.float32(1.0 + 0.25 * math.sin(0.9 * frame))).astype(np.float32)
+
+
+def bending_cylinder(rings=10, segs=12, radius=0.15, height=1.2):
+    """A cylinder along +y built for two-bone skinning: positions, normals, uvs, indices, joint indices (uint16 x 4) and weights (x 4).
+    Bottom vertices follow joint 0 alone, top ones joint 1 alone (single-joint vertices); in between the weights blend and do NOT sum to
+    one exactly (0.95-1.05) - the skinning contract uses them as given."""
+    p, n, uv, ji, jw = [], [], [], [], []
+    for r in range(rings + 1):
+        t = r / rings
+        for s in range(segs + 1):
+            a = 2 * math.pi * s / segs
+            p.append((radius * math.cos(a), height * t, radius * math.sin(a)))
+            n.append((math.cos(a), 0.0, math.sin(a)))
+            uv.append((s / segs, t))
+            if t <= 0.2:
+                ji.append((0, 0, 0, 0)); jw.append((1.0, 0.0, 0.0, 0.0))
+            elif t >= 0.8:
+                ji.append((1, 2, 0, 0)); jw.append((1.0, 0.0, 0.0, 0.0))
+            else:
+                w1 = (t - 0.2) / 0.6
+                ji.append((0, 1, 2, 0)); jw.append((1.0 - w1, w1 * (0.95 + 0.1 * (s % 3) / 2), 0.0, 0.0))
+    idx = []
+    for r in range(rings):
+        for s in range(segs):
+            a, b = r * (segs + 1) + s, r * (segs + 1) + s + 1
+            c, d = a + segs + 1, b + segs + 1
+            idx += [a, c, b, b, c, d]
+    return (np.array(p, np.float32), np.array(n, np.float32), np.array(uv, np.float32), np.array(idx, np.uint32), np.array(ji, np.uint16),
+            np.array(jw, np.float32))
+
+
+def bend_joints(frame, origin=(0.0, 0.0, 0.0), height=1.2):
+    """Three column-major joint matrices for `frame`: 0 = the root (a translation), 1 = bent about z at mid-height, 2 = a slight scale."""
+    o = np.array(origin, np.float64)
+    j0 = np.eye(4); j0[:3, 3] = o
+    ang = 0.35 * math.sin(0.5 * frame)
+    c, s = math.cos(ang), math.sin(ang)
+    rot = np.array([[c, -s, 0, 0], [s, c, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]], np.float64)
+    pivot, back = np.eye(4), np.eye(4)
+    pivot[1, 3], back[1, 3] = 0.5 * height, -0.5 * height
+    j1 = j0 @ pivot @ rot @ back
+    j2 = j0 @ np.diag([1.1, 1.0, 0.9, 1.0])
+    return np.stack([m.T.reshape(-1) for m in (j0, j1, j2)]).astype(np.float32)
+
+
+def skin_reference(bind_p, bind_n, ji, jw, joints):
+    """numpy float32 restatement of the skinning contract (hikari_hip.h hk_skin_mesh, Bevy 0.9 skinning.wgsl), operation for operation."""
+    J = joints.reshape(-1, 4, 4)  # [joint][column][row]
+    w = jw.astype(np.float32)
+    M = w[:, 0, None, None] * J[ji[:, 0]]
+    for t in range(1, 4):
+        M = M + w[:, t, None, None] * J[ji[:, t]]
+    x, y, z = bind_p[:, 0:1], bind_p[:, 1:2], bind_p[:, 2:3]
+    pos = ((M[:, 0, :3] * x + M[:, 1, :3] * y) + M[:, 2, :3] * z) + M[:, 3, :3]
+    c0, c1, c2 = M[:, 0, :3], M[:, 1, :3], M[:, 2, :3]
+
+    def cross(a, b):
+        return np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], -1)
+
+    cx, cy, cz = cross(c1, c2), cross(c2, c0), cross(c0, c1)
+    det = ((c2[:, 0] * cz[:, 0] + c2[:, 1] * cz[:, 1]) + c2[:, 2] * cz[:, 2])[:, None]
+    cx, cy, cz = cx / det, cy / det, cz / det
+    nrm = (cx * bind_n[:, 0:1] + cy * bind_n[:, 1:2]) + cz * bind_n[:, 2:3]
+    return pos.astype(np.float32), nrm.astype(np.float32)
+
+
+def deforming_scene(base="yard", cloth=(12, 12)):
+    """A scene with three deforming meshes on top of `base` ("yard": synthetic_scene beyond the LDS copy, "small": one that fits it):
+    a waving cloth, a bending cylinder (skinned) and a pulsing emissive sphere.  Returns (SceneData with .builder, sun, meshes) where
+    meshes maps "cloth" / "cylinder" / "sphere" to dict(id=builder mesh id, rest=positions, normals=..., + the skin of the cylinder)."""
+    if base == "yard":
+        scene, sun = synthetic_scene(n_boxes=20, n_spheres=5, n_emitters=2, sphere_rings=12, sphere_segs=16)
+    else:
+        scene, sun = synthetic_scene(n_boxes=2, n_spheres=1, n_emitters=1, sphere_rings=4, sphere_segs=5)
+    b = scene.builder
+    cp, cn, cuv, cidx = cloth_grid(*cloth, size=2.0)
+    yp, yn, yuv, yidx, ji, jw = bending_cylinder()
+    sp, sn, suv, sidx = _sphere(6, 8)
+    meshes = dict(cloth=dict(id=b.add_mesh(cp, cn, cuv, cidx), rest=cp, normals=cn),
+                  cylinder=dict(id=b.add_mesh(yp, yn, yuv, yidx), rest=yp, normals=yn, joints=ji, weights=jw),
+                  sphere=dict(id=b.add_mesh(sp, sn, suv, sidx), rest=sp, normals=sn))
+    cloth_mat = b.add_material(standard_material((0.7, 0.2, 0.2, 1.0), (0, 0, 0), 0.7, 0.0, 0.5))
+    glow = b.add_material(standard_material((0.9, 0.9, 0.9, 1.0), (1.0, 0.8, 0.5), 1.0, 0.0, 0.5))
+    b.add_instance(meshes["cloth"]["id"], cloth_mat, _trs((0.5, 1.2, 0.3), (0.2, 0.4, 0.0), (1.0, 1.0, 1.0)))
+    b.add_instance(meshes["cylinder"]["id"], cloth_mat, _trs((-1.0, 0.0, 0.8), (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)))
+    b.add_instance(meshes["sphere"]["id"], glow, _trs((1.2, 2.0, -0.6), (0.0, 0.0, 0.0), (0.4, 0.4, 0.4)))
+    scene = b.finish()
+    scene.builder = b
+    for m in meshes.values():
+        m["index"] = b.mesh_index(m["id"])
+    return scene, sun, meshes
+
+
+def large_cloth(triangles=1_000_000, size=2.0):
+    """One cloth grid of about `triangles` triangles (tools/deform_probe.py: 10^4 - 10^6): positions, normals, uvs, indices."""
+    side = max(2, int(round((triangles / 2) ** 0.5)))
+    return cloth_grid(side, side, size=size)

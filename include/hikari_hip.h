@@ -502,6 +502,12 @@ int hk_scene_builder_instance_nodes(const hk_scene_builder* b, const HkNode** p,
 int hk_scene_builder_emissives(const hk_scene_builder* b, const HkEmissive** p, uint32_t* n);
 int hk_scene_builder_emissive_nodes(const hk_scene_builder* b, const HkNode** p, uint32_t* n);
 int hk_scene_builder_alias_table(const hk_scene_builder* b, const HkAliasEntry** p, uint32_t* n);
+/* The host twin of hk_update_mesh_vertices: new positions (n_vertices x 3 floats, the mesh's own count) and normals (or NULL: keep)
+ * of a finished mesh.  Topology and tree links are kept; every tree box becomes the union of the triangle boxes below it (what the
+ * device refit computes), the mesh box is re-derived.  The next finish lays the instance level out again from them. */
+int hk_scene_builder_set_mesh_vertices(hk_scene_builder* b, uint32_t mesh_id, const float* positions, const float* normals);
+/* the HkMeshIndex of a mesh after a finish (what its instances carry, and what the hk_*_mesh_* calls take) */
+int hk_scene_builder_mesh_index(const hk_scene_builder* b, uint32_t mesh_id, HkMeshIndex* out);
 
 /* The layout conversion behind HK_CTX_EXACT_TRAVERSAL's opposite (see there): `nodes[0..count)` is ONE flat BVH in the `bvh`
  * 0.7.1 flatten_custom layout the reference produces (mod.rs:185-201,458-459; entry / exit indices local to the array);
@@ -564,6 +570,32 @@ int hk_refit_scene_instances(hk_ctx* ctx, hk_scene_builder* b, uint32_t* moved);
  * hk_upload_scene_instances gives (the reference's path), minus the two host-side SAH builds that dominate it. */
 int hk_update_scene_instances(hk_ctx* ctx, hk_scene_builder* b, uint32_t tree_mode);
 int hk_rebuild_scene_trees(hk_ctx* ctx, uint32_t mode);
+/* Mesh deformation on the DEVICE: new vertex data for one uploaded mesh, its BLAS refit in every layout that holds it, the change
+ * carried up to the instances of the mesh (world AABBs, emitter records and alias tables) and to the instance tree and the light tree.
+ * A mesh is named by the HkMeshIndex its instances carry (it must equal an uploaded instance's record); its topology (index buffer,
+ * triangles, uvs, tree links) never changes, only positions and normals do.  Stream-ordered like
+ * hk_refit_scene_instances: host data goes through pinned staging, frames enqueued before the call see the old mesh and frames enqueued
+ * after it the new one; there is no host wait (pinned staging from a pool, reused once the device has read it).  The mesh level is
+ * written at the call; the instances, emitters and both instance-level trees follow once, before whatever reads them next (the next
+ * frame), for all meshes deformed in between.  `n_vertices` must be exactly the vertices the mesh's triangles span (highest index + 1).
+ * Argument errors return HK_E_INVALID with nothing written.
+ * After a deformation the host copies of the mesh (vertices, BLAS boxes, the mesh box behind the instance boxes) are stale: what would
+ * lay scene memory out again from them is refused with HK_E_NOT_READY until hk_upload_scene brings the host's mirror of the change
+ * (hk_scene_builder_set_mesh_vertices) back - hk_upload_instances / hk_upload_scene_instances / hk_update_scene_instances at the call,
+ * hk_upload_materials / hk_upload_textures at the next frame (as after hk_refit_scene_instances); hk_rebuild_scene_trees and
+ * hk_refit_scene_instances work from the device's current boxes.  A scene walked through its one-level
+ * tree (HK_TRAVERSAL_ONE_LEVEL) walks its two-level trees from the first deformation until that upload (hk_traversal_mode reports it).
+ * hk_upload_meshes (and so hk_upload_scene) drops every skin set below. */
+/* positions: n_vertices x 3 floats; normals: n_vertices x 3 floats or NULL (keep the current ones) */
+int hk_update_mesh_vertices(hk_ctx* ctx, const HkMeshIndex* mesh, uint32_t n_vertices, const float* positions, const float* normals);
+/* Linear-blend skinning (Bevy 0.9 skinning.wgsl), set once per mesh: bind-pose positions and normals (n_vertices x 3 floats), up to
+ * four joints per vertex (n_vertices x 4 uint16, Bevy's JOINT_INDEX) and their weights (n_vertices x 4 floats, JOINT_WEIGHT; used as
+ * given, not renormalised). */
+int hk_set_mesh_skin(hk_ctx* ctx, const HkMeshIndex* mesh, uint32_t n_vertices, const float* bind_positions, const float* bind_normals,
+                     const uint16_t* joint_indices, const float* joint_weights);
+/* per frame: n_joints column-major 4x4 joint matrices; the device skins the mesh (positions and normals, mesh-local) and refits as
+ * hk_update_mesh_vertices does.  A joint index >= n_joints in the skin is refused (HK_E_INVALID, nothing written). */
+int hk_skin_mesh(hk_ctx* ctx, const HkMeshIndex* mesh, const float* joint_matrices, uint32_t n_joints);
 int hk_upload_textures(hk_ctx* ctx, const HkImageDesc* images, uint32_t n_images);
 /* InstanceRenderAssets::set + write_buffer, instance.rs:82-108 */
 int hk_upload_instances(hk_ctx* ctx, const HkInstance* instances, uint32_t n_instances, const HkNode* instance_nodes,
@@ -810,6 +842,11 @@ int hk_multi_upload_scene(hk_multi* m, const hk_scene_builder* b);
 int hk_multi_upload_scene_instances(hk_multi* m, const hk_scene_builder* b);
 int hk_multi_refit_scene_instances(hk_multi* m, hk_scene_builder* b, uint32_t* moved); /* hk_refit_scene_instances on every band's replica */
 int hk_multi_rebuild_scene_trees(hk_multi* m, uint32_t mode);
+/* hk_update_mesh_vertices / hk_set_mesh_skin / hk_skin_mesh on every band's replica */
+int hk_multi_update_mesh_vertices(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vertices, const float* positions, const float* normals);
+int hk_multi_set_mesh_skin(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vertices, const float* bind_positions, const float* bind_normals,
+                           const uint16_t* joint_indices, const float* joint_weights);
+int hk_multi_skin_mesh(hk_multi* m, const HkMeshIndex* mesh, const float* joint_matrices, uint32_t n_joints);
 int hk_multi_set_band_bounds(hk_multi* m, const uint32_t* bounds, uint32_t n_bounds);
 /* hk_migrate_bands for the one-process form: the rows that change owner travel as peer copies, then every band takes the new split */
 int hk_multi_migrate_bands(hk_multi* m, const uint32_t* new_bounds, uint32_t n_bounds, uint32_t next_frame_number, const HkSettings* settings);

@@ -16,6 +16,12 @@ extern "C" {
 
 /* Test hook: the instance tree (ordering 0) and the light tree as the device holds them, in the reference's HkNode layout. */
 int hk_debug_read_trees(hk_ctx* ctx, HkNode* instance_nodes, uint32_t instance_cap, HkNode* emissive_nodes, uint32_t emissive_cap);
+/* Test hook: the mesh-level node array as the device holds it - every ordering (1, or 8 for threaded scenes) of every mesh tree,
+ * leaf boxes filled in and navigators folded, ordering-major, entry / exit words as stored - and the orderings count. */
+int hk_debug_read_mesh_nodes(hk_ctx* ctx, HkNode* out, uint32_t cap, uint32_t* count, uint32_t* orderings);
+/* Test hook: the emitter records (8 floats each: position xyz, radius, surface area, then instance, alias offset, alias count as u32
+ * bits) and the alias table (probability, index bits) as the device holds them; *n_records / *n_alias receive the counts. */
+int hk_debug_read_emitters(hk_ctx* ctx, float* records, uint32_t records_cap, uint32_t* n_records, float* alias, uint32_t alias_cap, uint32_t* n_alias);
 
 /* Measurement hook ("measure the empirical HBM ceiling with a device copy/triad kernel in the same run"): streams
  * three private arrays of `bytes_per_array` bytes (use >= 1 GiB: the 256 MB Infinity Cache must not hold them) `reps` times
