@@ -207,6 +207,7 @@ _DEBUG = {
     "debug_read_trees": [_vp, P(HkNode), u32, P(HkNode), u32],
     "debug_read_mesh_nodes": [_vp, P(HkNode), u32, P(u32), P(u32)],
     "debug_read_emitters": [_vp, P(f32), u32, P(u32), P(f32), u32, P(u32)],
+    "debug_read_mesh_geometry": [_vp, P(HkMeshIndex), P(f32), P(f32), u32, P(f32), u32, P(f32), P(u32), P(u32)],
     "debug_comm_loopback": [_vp, u32, u32, u32, u32, u32],
     "debug_read_wf_timeline": [_vp, P(C.c_uint64), u32],
     "debug_set_option": [_vp, u32, C.c_int64],

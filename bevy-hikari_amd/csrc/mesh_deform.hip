@@ -449,4 +449,41 @@ int hk_debug_read_mesh_nodes(hk_ctx* c, HkNode* out, uint32_t cap, uint32_t* cou
   return HK_OK;
 }
 
+// Test hook (hikari_hip_debug.h): the geometry of one deformed mesh as the device holds it (reads only)
+int hk_debug_read_mesh_geometry(hk_ctx* c, const HkMeshIndex* mesh, float* positions, float* normals, uint32_t vertex_cap, float* triangles, uint32_t triangle_cap,
+                                float* box, uint32_t* n_vertices, uint32_t* n_triangles) {
+  HK_REQUIRE(c && mesh && n_vertices && n_triangles, HK_E_INVALID, "NULL argument");
+  HK_HIP(hipSetDevice(c->device));
+  int rc;
+  if ((rc = finalize_scene(c))) return rc;
+  DeformMesh* d = nullptr;
+  for (DeformMesh* q : c->deform)
+    if (memcmp(&q->mesh, mesh, sizeof(HkMeshIndex)) == 0) d = q;
+  HK_REQUIRE(d && d->deformed, HK_E_INVALID, "the mesh has not been deformed on this context");
+  if ((rc = flush_deform(c))) return rc;
+  if ((rc = sync_all(c))) return rc;
+  const uint32_t nv = d->n_vertices, nt = d->n_tris;
+  *n_vertices = nv;
+  *n_triangles = nt;
+  if (!positions && !normals && !triangles && !box) return HK_OK;
+  HK_REQUIRE(positions && normals && triangles && box && vertex_cap >= nv && triangle_cap >= nt, HK_E_INVALID, "need room for %u vertices and %u triangles", nv, nt);
+  const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
+  const uint8_t* sbase = c->scene_mem + slots;
+  HK_HIP(hipMemcpy(positions, d->pos, (size_t)nv * 16, hipMemcpyDeviceToHost));
+  HK_HIP(hipMemcpy(normals, (const float4*)(sbase + c->st_vn) + d->mesh.vertex, (size_t)nv * 16, hipMemcpyDeviceToHost));
+  std::vector<float4> plane(nt);
+  const size_t planes[3] = {c->st_v0, c->st_v1, c->st_v2};
+  for (int k = 0; k < 3; ++k) {
+    HK_HIP(hipMemcpy(plane.data(), (const float4*)(sbase + planes[k]) + d->mesh.primitive, (size_t)nt * 16, hipMemcpyDeviceToHost));
+    for (uint32_t t = 0; t < nt; ++t) memcpy(triangles + 12 * (size_t)t + 4 * k, &plane[t], 16);
+  }
+  uint32_t words[6];
+  HK_HIP(hipMemcpy(words, d->box, sizeof(words), hipMemcpyDeviceToHost));
+  for (int k = 0; k < 6; ++k) {  // (kernels_deform.hip box_word, inverted)
+    const uint32_t u = (words[k] & 0x80000000u) ? (words[k] & 0x7FFFFFFFu) : ~words[k];
+    memcpy(box + k, &u, 4);
+  }
+  return HK_OK;
+}
+
 }  // extern "C"

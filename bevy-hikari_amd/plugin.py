@@ -520,6 +520,17 @@ class Engine:
         self.api.call("debug_read_emitters", self.ctx, fp(rec), n.value, C.byref(n), fp(al), m.value, C.byref(m))
         return rec[:n.value], al[:m.value]
 
+    def read_mesh_geometry(self, mesh):
+        """dict(positions, normals: float32[n][3]; triangles: float32[t][3][4] - v0, v1, v2 with the vertex-index words as float bits;
+        box: float32[2][3]) of one mesh deformed on this context, as the device holds it (test hook)."""
+        nv, nt = F.u32(), F.u32()
+        self.api.call("debug_read_mesh_geometry", self.ctx, C.byref(mesh), None, None, 0, None, 0, None, C.byref(nv), C.byref(nt))
+        pos, nrm = np.zeros((max(1, nv.value), 4), np.float32), np.zeros((max(1, nv.value), 4), np.float32)
+        tri, box = np.zeros((max(1, nt.value), 3, 4), np.float32), np.zeros((2, 3), np.float32)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(F.f32))
+        self.api.call("debug_read_mesh_geometry", self.ctx, C.byref(mesh), fp(pos), fp(nrm), nv.value, fp(tri), nt.value, fp(box), C.byref(nv), C.byref(nt))
+        return dict(positions=pos[:nv.value, :3], normals=nrm[:nv.value, :3], triangles=tri[:nt.value], box=box)
+
     def read_trees(self, n_instance_nodes, n_emissive_nodes):
         """(instance_nodes, emissive_nodes) as the device holds them, in the reference layout (test hook)."""
         a, b = (F.HkNode * max(1, n_instance_nodes))(), (F.HkNode * max(1, n_emissive_nodes))()

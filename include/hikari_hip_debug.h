@@ -19,6 +19,12 @@ int hk_debug_read_trees(hk_ctx* ctx, HkNode* instance_nodes, uint32_t instance_c
 /* Test hook: the mesh-level node array as the device holds it - every ordering (1, or 8 for threaded scenes) of every mesh tree,
  * leaf boxes filled in and navigators folded, ordering-major, entry / exit words as stored - and the orderings count. */
 int hk_debug_read_mesh_nodes(hk_ctx* ctx, HkNode* out, uint32_t cap, uint32_t* count, uint32_t* orderings);
+/* Test hook: one mesh deformed on this context (hk_update_mesh_vertices / hk_skin_mesh) as the device holds it after the pending
+ * deformations: the positions of the last deformation and the vertex-plane normals (4 floats per vertex), the triangle planes (12
+ * floats per triangle: v0, v1, v2 as xyz + the vertex-index word) and the mesh box (min xyz, max xyz) decoded from its six words.
+ * *n_vertices / *n_triangles receive the counts; all four arrays NULL asks for the counts alone.  Reads only. */
+int hk_debug_read_mesh_geometry(hk_ctx* ctx, const HkMeshIndex* mesh, float* positions, float* normals, uint32_t vertex_cap, float* triangles,
+                                uint32_t triangle_cap, float box[6], uint32_t* n_vertices, uint32_t* n_triangles);
 /* Test hook: the emitter records (8 floats each: position xyz, radius, surface area, then instance, alias offset, alias count as u32
  * bits) and the alias table (probability, index bits) as the device holds them; *n_records / *n_alias receive the counts. */
 int hk_debug_read_emitters(hk_ctx* ctx, float* records, uint32_t records_cap, uint32_t* n_records, float* alias, uint32_t alias_cap, uint32_t* n_alias);
