@@ -47,7 +47,7 @@ CTX_NO_WIDE_WALK = 256  # closest-hit walks of scenes beyond LDS keep the thread
 CTX_COUNT_WALKS = 512   # the trace stages run the counting twin of their kernel (same schedule, same walks): hk_debug_read_wf_timeline
 CTX_RACING_SCATTER = 1024   # hikari_hip.h HK_CTX_RACING_SCATTER: the reference's own race on previous_spatial (round 6: the default resolves it)
 DEBUG_OPT_SPATIAL_WINDOW, DEBUG_OPT_FRAME_PIPELINE, DEBUG_OPT_WF_TIMELINE, DEBUG_OPT_FLAT_WALK, DEBUG_OPT_FLAT_ORDERINGS, DEBUG_OPT_TRACE_UPDATE = 0, 1, 2, 3, 4, 5  # hikari_hip_debug.h hk_debug_set_option
-DEBUG_OPT_MAIN_PRIORITY, DEBUG_OPT_PREPASS_PIPELINE = 9, 10  # (6, 7 and 8 are retired)
+DEBUG_OPT_MAIN_PRIORITY, DEBUG_OPT_PREPASS_PIPELINE, DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP = 9, 10, 11  # (6, 7 and 8 are retired)
 TIMING_TRACE_STAGES = 18  # hk_set_timing_mask bit / HkStats slot: every trace launch of the queue-based indirect pass
 TRAVERSAL_WIDE = 0x100
 FRAME_EXTERNAL_GBUFFER, FRAME_ANTIALIAS, FRAME_BALANCE_BANDS, FRAME_GATHER, FRAME_TIME_BAND = 1, 2, 4, 8, 16
@@ -245,6 +245,7 @@ _PRODUCT_ONLY = {
     "scene_builder_emissive_nodes": [_vp, P(P(HkNode)), P(u32)],
     "scene_builder_alias_table": [_vp, P(P(HkAliasEntry)), P(u32)],
     "scene_builder_set_mesh_vertices": [_vp, u32, P(f32), P(f32)],
+    "scene_builder_rebuild_mesh_tree": [_vp, u32],
     "scene_builder_mesh_index": [_vp, u32, P(HkMeshIndex)],
     "upload_scene": [_vp, _vp],
     "upload_scene_instances": [_vp, _vp],
@@ -254,6 +255,7 @@ _PRODUCT_ONLY = {
     "update_mesh_vertices": [_vp, P(HkMeshIndex), u32, P(f32), P(f32)],
     "set_mesh_skin": [_vp, P(HkMeshIndex), u32, P(f32), P(f32), P(C.c_uint16), P(f32)],
     "skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],
+    "rebuild_mesh_tree": [_vp, P(HkMeshIndex), u32],
     "band_rows": [u32, u32, u32, P(u32), P(u32)],
     "balanced_band_bounds": [P(u32), u32, u32, u32, u32, u32, f32, P(u32)],
     "balance_bands": [_vp, u32, P(u32), u32],
@@ -296,6 +298,7 @@ _PRODUCT_ONLY = {
     "multi_update_mesh_vertices": [_vp, P(HkMeshIndex), u32, P(f32), P(f32)],
     "multi_set_mesh_skin": [_vp, P(HkMeshIndex), u32, P(f32), P(f32), P(C.c_uint16), P(f32)],
     "multi_skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],
+    "multi_rebuild_mesh_tree": [_vp, P(HkMeshIndex), u32],
     "multi_set_band_bounds": [_vp, P(u32), u32],
     "multi_upload_textures": [_vp, P(HkImageDesc), u32],
     "multi_upload_noise": [_vp, _vp, C.c_size_t],

@@ -245,6 +245,7 @@ struct hk_ctx {
   uint64_t device_refits = 0, device_tree_builds = 0;
   void* lbvh_scratch = nullptr;           // hk_rebuild_scene_trees
   size_t lbvh_scratch_cap = 0;
+  bool mesh_rebuild_one_workgroup = false;  // HK_DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP: the SAH build's top levels in one workgroup (A/B)
   const float4* d_prev_models = nullptr;  // 4 columns per instance, valid where DInstance::moved
   DevArray<uint32_t> d_noise;
   DevArray<uint32_t> d_tex_data;

@@ -319,8 +319,11 @@ void launch_refit(hipStream_t st, const hkd::RefitScene& s, const hkd::RefitUpda
 // LBVH rebuild of a flat skip-link BVH over n shapes (kernels_scene.hip): scratch size, and the build into `lo` / `hi` (`stride`
 // float4 between consecutive nodes: 2 for the interleaved TLAS, 1 for the two planes of the light BVH)
 size_t lbvh_scratch_bytes(uint32_t n, size_t* sort_temp_bytes);
+// `ord_stride`: float4 between orderings (0: the tree's own 3n - 2 nodes); `keep`: a mesh tree that takes the new topology over (and whose
+// ordering 0 stays left before right in either mode); `one_workgroup_top`: the SAH build's top levels in one workgroup at any n (A/B)
 int launch_tree_build(hipStream_t st, int mode /* 0 LBVH, 1 the reference's binned SAH */, bool light, const hkd::RefitScene& s, uint32_t n, const float4* box_lo,
-                      const float4* box_hi, void* scratch, float4* lo, float4* hi, uint32_t stride, uint32_t orderings);
+                      const float4* box_hi, void* scratch, float4* lo, float4* hi, uint32_t stride, uint32_t orderings, size_t ord_stride = 0,
+                      const hkd::MeshTree* keep = nullptr, bool one_workgroup_top = false);
 // mesh deformation: the BLAS refit of one mesh tree into `orderings` orderings of its flat layout (`lo` = its node 0 of ordering 0,
 // interleaved lo / hi pairs, `ord_stride` float4 between orderings); the propagation of a new mesh box (`box`: 6 order-preserving
 // words, kernels_deform.hip) to the instances `ids` (emitters first) of the mesh, their emitters (`records`: device scratch, one per
@@ -333,6 +336,8 @@ void launch_mesh_stage(hipStream_t st, const float* positions, const float* norm
 void launch_mesh_skin(hipStream_t st, const float4* bind_pos, const float4* bind_nrm, const uint2* joints, const float4* weights, const float4* joint_mats, uint32_t n,
                       float4* pos, float4* vn, uint32_t* box);
 void launch_mesh_triangles(hipStream_t st, const float4* pos, float4* v0, float4* v1, float4* v2, uint32_t n_tris, float4* tri_lo, float4* tri_hi);
+// the triangle boxes alone, from the triangle planes as they are (a mesh rebuilt before its first deformation)
+void launch_mesh_triangle_boxes(hipStream_t st, const float4* v0, const float4* v1, const float4* v2, uint32_t n_tris, float4* tri_lo, float4* tri_hi);
 // windowed: 0 the plain form, 1 the windowed form (depth window + tap lists in LDS: kernels.hip), -1 by the size of the launch; returns
 // whether the windowed form was launched
 bool launch_spatial(hipStream_t st, bool emissive_lit, const hkd::DScene& sc, const hkd::DFrame& fr, const hkd::GBuffer& g, const hkd::LightTargets& t,

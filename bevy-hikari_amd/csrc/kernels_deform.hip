@@ -143,6 +143,16 @@ __global__ __launch_bounds__(256) void k_mesh_triangles(const float4* __restrict
   tri_hi[t] = make_float4(leaf_max(q[0].x, leaf_max(q[1].x, q[2].x)), leaf_max(q[0].y, leaf_max(q[1].y, q[2].y)), leaf_max(q[0].z, leaf_max(q[1].z, q[2].z)), 0.0f);
 }
 
+// ... the boxes alone, of triangles nobody has moved yet (hk_rebuild_mesh_tree on a mesh never deformed)
+__global__ __launch_bounds__(256) void k_mesh_triangle_boxes(const float4* __restrict__ v0, const float4* __restrict__ v1, const float4* __restrict__ v2, uint32_t n_tris,
+                                                             float4* __restrict__ tri_lo, float4* __restrict__ tri_hi) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= n_tris) return;
+  const float4 q[3] = {v0[t], v1[t], v2[t]};
+  tri_lo[t] = make_float4(leaf_min(q[0].x, leaf_min(q[1].x, q[2].x)), leaf_min(q[0].y, leaf_min(q[1].y, q[2].y)), leaf_min(q[0].z, leaf_min(q[1].z, q[2].z)), 0.0f);
+  tri_hi[t] = make_float4(leaf_max(q[0].x, leaf_max(q[1].x, q[2].x)), leaf_max(q[0].y, leaf_max(q[1].y, q[2].y)), leaf_max(q[0].z, leaf_max(q[1].z, q[2].z)), 0.0f);
+}
+
 }  // namespace hkd
 
 namespace hk {
@@ -157,6 +167,9 @@ void launch_mesh_skin(hipStream_t st, const float4* bind_pos, const float4* bind
 }
 void launch_mesh_triangles(hipStream_t st, const float4* pos, float4* v0, float4* v1, float4* v2, uint32_t n_tris, float4* tri_lo, float4* tri_hi) {
   if (n_tris) hipLaunchKernelGGL(k_mesh_triangles, dim3((n_tris + 255u) / 256u), dim3(256), 0, st, pos, v0, v1, v2, n_tris, tri_lo, tri_hi);
+}
+void launch_mesh_triangle_boxes(hipStream_t st, const float4* v0, const float4* v1, const float4* v2, uint32_t n_tris, float4* tri_lo, float4* tri_hi) {
+  if (n_tris) hipLaunchKernelGGL(k_mesh_triangle_boxes, dim3((n_tris + 255u) / 256u), dim3(256), 0, st, v0, v1, v2, n_tris, tri_lo, tri_hi);
 }
 
 }  // namespace hk

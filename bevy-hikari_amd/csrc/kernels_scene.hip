@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <utility>
 
 #include <rocprim/rocprim.hpp>
 
@@ -639,6 +640,103 @@ __device__ __forceinline__ void block_scan_buckets_and_heads(uint32_t bk, uint32
   for (int k = 0; k < 3; ++k) pre[k] = lds[17 * k + wave] + inc[k] - v[k];
   head = max(lds[51 + wave], hmax);
 }
+// step C of a level: the split axis of `node` from its centre bounds (Box::largest_axis), and whether its shapes are too close together
+__device__ __forceinline__ void sah_split_axis(const SahBuffers& q, uint32_t node) {
+  const uint32_t* acc = q.acc + (size_t)node * 54u;
+  float cmn[3], cmx[3];
+  for (int k = 0; k < 3; ++k) {
+    cmn[k] = funkey(acc[6 + k]);
+    cmx[k] = funkey(acc[9 + k]);
+  }
+  const float x = cmx[0] - cmn[0], y = cmx[1] - cmn[1], z = cmx[2] - cmn[2];
+  const int axis = (x > y && x > z) ? 0 : (y > z ? 1 : 2);  // Box::largest_axis
+  const float axis_size = cmx[axis] - cmn[axis];
+  float* sp = q.split + (size_t)node * 4u;
+  sp[0] = cmn[axis];
+  sp[1] = axis_size;
+  sp[2] = u2f((uint32_t)axis);
+  sp[3] = u2f(axis_size < 0.00001f ? 1u : 0u);  // shapes too close together: the index list is cut in half
+}
+// step E of a level: the cheapest of the five splits of `node` (the host's float expressions term for term), its bucket offsets and its
+// children - `child` receives their tree nodes.  A child to split at the next level is appended to active_out[*n_out]
+__device__ __forceinline__ void sah_split_node(const LbvhBuffers& b, const SahBuffers& q, uint32_t node, uint32_t level, uint32_t defer, uint32_t* active_out,
+                                               uint32_t* n_out, uint32_t child[2]) {
+  const uint32_t n = b.n;
+  const uint32_t* acc = q.acc + (size_t)node * 54u;
+  const float* sp = q.split + (size_t)node * 4u;
+  uint32_t* off = q.offsets + (size_t)node * 14u;
+  const uint32_t begin = b.first[node], count = b.last[node] - begin + 1u;
+  uint32_t n_left = count / 2u, split_bucket = 6u;  // 6: cut the list in half
+  if (f2u(sp[3]) == 0u) {
+    float bounds_mn[3], bounds_mx[3];
+    for (int k = 0; k < 3; ++k) {
+      bounds_mn[k] = funkey(acc[k]);
+      bounds_mx[k] = funkey(acc[3 + k]);
+    }
+    const float total_area = box_area(bounds_mn, bounds_mx);
+    float min_cost = INFINITY;
+    uint32_t min_bucket = 0u;
+    for (uint32_t i = 0; i < 5u; ++i) {
+      float lmn[3] = {INFINITY, INFINITY, INFINITY}, lmx[3] = {-INFINITY, -INFINITY, -INFINITY};
+      float rmn[3] = {INFINITY, INFINITY, INFINITY}, rmx[3] = {-INFINITY, -INFINITY, -INFINITY};
+      uint32_t ln = 0u, rn = 0u;
+      for (uint32_t k6 = 0; k6 < 6u; ++k6) {
+        const uint32_t* bb = acc + 12u + 6u * k6;
+        float* tmn = k6 <= i ? lmn : rmn;
+        float* tmx = k6 <= i ? lmx : rmx;
+        for (int k = 0; k < 3; ++k) {
+          tmn[k] = hmin(tmn[k], funkey(bb[k]));
+          tmx[k] = hmax(tmx[k], funkey(bb[3 + k]));
+        }
+        if (k6 <= i) ln += acc[48u + k6]; else rn += acc[48u + k6];
+      }
+      const float cost = ((float)ln * box_area(lmn, lmx) + (float)rn * box_area(rmn, rmx)) / total_area;
+      if (cost < min_cost) {
+        min_bucket = i;
+        min_cost = cost;
+      }
+    }
+    uint32_t best_left = 0u;  // (all costs NaN: the host keeps bucket 0 as the split)
+    for (uint32_t k6 = 0; k6 <= min_bucket; ++k6) best_left += acc[48u + k6];
+    if (best_left != 0u && best_left != count) {
+      n_left = best_left;
+      split_bucket = min_bucket;
+    }  // (an empty side - NaN costs - falls back to the half cut, like the host)
+  }
+  uint32_t run = begin;
+  for (uint32_t k6 = 0; k6 < 6u; ++k6) {
+    off[k6] = run;
+    run += acc[48u + k6];
+    off[6u + k6] = 0u;
+  }
+  off[12] = n_left;
+  off[13] = split_bucket;
+  // children: a side with one shape is a leaf at its position, a larger one an internal node - split at the next level, or
+  // handed to a workgroup of its own when it is small enough
+  const uint32_t n_right = count - n_left;
+  for (int side = 0; side < 2; ++side) {
+    const uint32_t c_begin = side == 0 ? begin : begin + n_left, c_count = side == 0 ? n_left : n_right;
+    if (c_count == 1u) {
+      child[side] = (n - 1u) + c_begin;
+      b.leaf_parent[c_begin] = node;
+    } else {
+      const uint32_t id = atomicAdd(&q.counters[0], 1u);
+      child[side] = id;
+      b.first[id] = c_begin;
+      b.last[id] = c_begin + c_count - 1u;
+      b.parent[id] = node;
+      if (c_count <= defer) {
+        q.node_level[id] = SAH_DONE;  // (not a level of this loop)
+        q.roots[atomicAdd(&q.counters[1], 1u)] = id;
+      } else {
+        q.node_level[id] = level + 1u;
+        active_out[atomicAdd(n_out, 1u)] = id;
+      }
+    }
+  }
+  b.left[node] = child[0];
+  b.right[node] = child[1];
+}
 }  // namespace
 
 // The level loop over one range [r0, r1) of item positions, run by ONE workgroup of 1024 threads: every node of a level at once.
@@ -698,23 +796,7 @@ __device__ uint32_t sah_levels(const RefitScene& s, const LbvhBuffers& b, const 
     }
     __syncthreads();
     // C: split axis
-    for (uint32_t a = tid; a < n_active; a += 1024u) {
-      const uint32_t node = active[a];
-      const uint32_t* acc = q.acc + (size_t)node * 54u;
-      float cmn[3], cmx[3];
-      for (int k = 0; k < 3; ++k) {
-        cmn[k] = funkey(acc[6 + k]);
-        cmx[k] = funkey(acc[9 + k]);
-      }
-      const float x = cmx[0] - cmn[0], y = cmx[1] - cmn[1], z = cmx[2] - cmn[2];
-      const int axis = (x > y && x > z) ? 0 : (y > z ? 1 : 2);  // Box::largest_axis
-      const float axis_size = cmx[axis] - cmn[axis];
-      float* sp = q.split + (size_t)node * 4u;
-      sp[0] = cmn[axis];
-      sp[1] = axis_size;
-      sp[2] = u2f((uint32_t)axis);
-      sp[3] = u2f(axis_size < 0.00001f ? 1u : 0u);  // shapes too close together: the index list is cut in half
-    }
+    for (uint32_t a = tid; a < n_active; a += 1024u) sah_split_axis(q, active[a]);
     __syncthreads();
     // D: buckets
     for (uint32_t p0 = r0; p0 < r1; p0 += 1024u) {
@@ -747,82 +829,8 @@ __device__ uint32_t sah_levels(const RefitScene& s, const LbvhBuffers& b, const 
     __syncthreads();
     // E: the cheapest split, the children
     for (uint32_t a = tid; a < n_active; a += 1024u) {
-      const uint32_t node = active[a];
-      const uint32_t* acc = q.acc + (size_t)node * 54u;
-      const float* sp = q.split + (size_t)node * 4u;
-      uint32_t* off = q.offsets + (size_t)node * 14u;
-      const uint32_t begin = b.first[node], count = b.last[node] - begin + 1u;
-      uint32_t n_left = count / 2u, split_bucket = 6u;  // 6: cut the list in half
-      if (f2u(sp[3]) == 0u) {
-        float bounds_mn[3], bounds_mx[3];
-        for (int k = 0; k < 3; ++k) {
-          bounds_mn[k] = funkey(acc[k]);
-          bounds_mx[k] = funkey(acc[3 + k]);
-        }
-        const float total_area = box_area(bounds_mn, bounds_mx);
-        float min_cost = INFINITY;
-        uint32_t min_bucket = 0u;
-        for (uint32_t i = 0; i < 5u; ++i) {
-          float lmn[3] = {INFINITY, INFINITY, INFINITY}, lmx[3] = {-INFINITY, -INFINITY, -INFINITY};
-          float rmn[3] = {INFINITY, INFINITY, INFINITY}, rmx[3] = {-INFINITY, -INFINITY, -INFINITY};
-          uint32_t ln = 0u, rn = 0u;
-          for (uint32_t k6 = 0; k6 < 6u; ++k6) {
-            const uint32_t* bb = acc + 12u + 6u * k6;
-            float* tmn = k6 <= i ? lmn : rmn;
-            float* tmx = k6 <= i ? lmx : rmx;
-            for (int k = 0; k < 3; ++k) {
-              tmn[k] = hmin(tmn[k], funkey(bb[k]));
-              tmx[k] = hmax(tmx[k], funkey(bb[3 + k]));
-            }
-            if (k6 <= i) ln += acc[48u + k6]; else rn += acc[48u + k6];
-          }
-          const float cost = ((float)ln * box_area(lmn, lmx) + (float)rn * box_area(rmn, rmx)) / total_area;
-          if (cost < min_cost) {
-            min_bucket = i;
-            min_cost = cost;
-          }
-        }
-        uint32_t best_left = 0u;  // (all costs NaN: the host keeps bucket 0 as the split)
-        for (uint32_t k6 = 0; k6 <= min_bucket; ++k6) best_left += acc[48u + k6];
-        if (best_left != 0u && best_left != count) {
-          n_left = best_left;
-          split_bucket = min_bucket;
-        }  // (an empty side - NaN costs - falls back to the half cut, like the host)
-      }
-      uint32_t run = begin;
-      for (uint32_t k6 = 0; k6 < 6u; ++k6) {
-        off[k6] = run;
-        run += acc[48u + k6];
-        off[6u + k6] = 0u;
-      }
-      off[12] = n_left;
-      off[13] = split_bucket;
-      // children: a side with one shape is a leaf at its position, a larger one an internal node - split at the next level, or
-      // handed to a workgroup of its own when it is small enough
-      const uint32_t n_right = count - n_left;
       uint32_t child[2];
-      for (int side = 0; side < 2; ++side) {
-        const uint32_t c_begin = side == 0 ? begin : begin + n_left, c_count = side == 0 ? n_left : n_right;
-        if (c_count == 1u) {
-          child[side] = (n - 1u) + c_begin;
-          b.leaf_parent[c_begin] = node;
-        } else {
-          const uint32_t id = atomicAdd(&q.counters[0], 1u);
-          child[side] = id;
-          b.first[id] = c_begin;
-          b.last[id] = c_begin + c_count - 1u;
-          b.parent[id] = node;
-          if (c_count <= defer) {
-            q.node_level[id] = SAH_DONE;  // (not a level of this loop)
-            q.roots[atomicAdd(&q.counters[1], 1u)] = id;
-          } else {
-            q.node_level[id] = level + 1u;
-            active_out[atomicAdd(&n_active_lds[cur ^ 1u], 1u)] = id;
-          }
-        }
-      }
-      b.left[node] = child[0];
-      b.right[node] = child[1];
+      sah_split_node(b, q, active[a], level, defer, active_out, &n_active_lds[cur ^ 1u], child);
     }
     __syncthreads();
     // F: stable re-order, bucket by bucket inside every segment; chunk after chunk so that the running counts stay in order
@@ -911,6 +919,210 @@ __global__ __launch_bounds__(1024) void k_sah_subtrees(RefitScene s, LbvhBuffers
     for (uint32_t i = r0 + threadIdx.x; i < r1; i += 1024u) b.ids_sorted[i] = q.order[cur][i];
     __syncthreads();
   }
+}
+
+// ------------------------------------------------------------------ the top of the SAH tree on the whole chip
+// k_sah_build runs every level above SAH_SUBTREE-shape nodes in ONE workgroup: sized for 2 * 10^4 instances, not for the 10^5 - 10^6
+// triangles of a mesh (hk_rebuild_mesh_tree).  Here a level is five stream-ordered launches over 1024-item chunks, one workgroup per
+// chunk - bounds (B), axis (C), buckets (D), split (E), re-order (F) - with sah_levels' arithmetic (sah_split_axis / sah_split_node are
+// shared, B / D / F restate its item steps).  What changes is only how the order-free reductions travel:
+//   - the segments of the nodes are contiguous, so a chunk whose first and last item share a node belongs to that node alone: its
+//     workgroup reduces in LDS (wave_box_accumulate on LDS words) and adds ONE set of atomics per chunk to the node's accumulators -
+//     at the top levels that is every chunk, and the hot addresses see a thousand atomics instead of a million;
+//   - the stable re-order needs, per item, the count of its bucket in its node BEFORE the chunk.  Only the run at the head of a chunk
+//     can have begun earlier, and in each earlier chunk its node is the tail run (first chunk) or the whole chunk: D leaves the six
+//     bucket counts of every chunk's head run and tail run in `chunk_counts`, F sums the ones it needs (integers: any order).
+// The host launches a FIXED number of levels (it reads nothing back); nodes still unsplit after them go to k_sah_subtrees like the
+// small ones, which is correct at any node size.  counters[8 + level] = nodes to split at `level`.
+constexpr uint32_t SAH_WIDE_MIN = 32768u;       // shapes from which the top of the tree is built this way
+constexpr uint32_t SAH_WIDE_MAX_LEVELS = 48u;   // counters[] holds 64 words
+namespace {
+__device__ __forceinline__ uint32_t sah_acc_init(uint32_t w) { return w < 48u ? ((w % 6u) < 3u ? fkey(INFINITY) : fkey(-INFINITY)) : 0u; }
+__device__ __forceinline__ bool sah_splitting(const SahBuffers& q, uint32_t node, uint32_t level) { return node != SAH_DONE && q.node_level[node] == level; }
+}  // namespace
+__global__ __launch_bounds__(1024) void k_sahw_setup(LbvhBuffers b, SahBuffers q, uint32_t levels) {
+  const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
+  if (i < b.n) {
+    q.order[0][i] = i;
+    q.item_node[0][i] = 0u;
+  }
+  if (blockIdx.x != 0u) return;
+  if (threadIdx.x < 54u) q.acc[threadIdx.x] = sah_acc_init(threadIdx.x);
+  if (threadIdx.x < 64u) {
+    uint32_t v = 0u;
+    if (threadIdx.x == 0u || threadIdx.x == 8u) v = 1u;  // internal nodes allocated; one node to split at level 0
+    if (threadIdx.x == 2u) v = levels & 1u;              // the ping-pong side the subtree workgroups start from
+    q.counters[threadIdx.x] = v;
+  }
+  if (threadIdx.x == 0u) {
+    b.first[0] = 0u;
+    b.last[0] = b.n - 1u;
+    b.parent[0] = HK_U32_MAX;
+    q.active[0][0] = 0u;
+    q.node_level[0] = 0u;
+  }
+}
+// B: bounds of the shapes and of their centres
+__global__ __launch_bounds__(1024) void k_sahw_bounds(LbvhBuffers b, SahBuffers q, uint32_t level) {
+  __shared__ uint32_t lacc[12];
+  const RefitScene none{};
+  const uint32_t tid = threadIdx.x, n = b.n, side = level & 1u, c0 = blockIdx.x * 1024u, p = c0 + tid;
+  const uint32_t* item_node = q.item_node[side];
+  const uint32_t hn = item_node[c0], tn = item_node[min(c0 + 1023u, n - 1u)];
+  const bool uniform = hn == tn;
+  if (uniform && !sah_splitting(q, hn, level)) return;  // (block-uniform)
+  if (tid < 12u) lacc[tid] = sah_acc_init(tid);
+  __syncthreads();
+  const uint32_t node = p < n ? item_node[p] : SAH_DONE;
+  const bool take = sah_splitting(q, node, level);
+  float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0}, cc[3] = {0, 0, 0};
+  if (take) {
+    f3 lo, hi;
+    lbvh_shape_box<false>(none, b, q.order[side][p], lo, hi);
+    mn[0] = lo.x; mn[1] = lo.y; mn[2] = lo.z;
+    mx[0] = hi.x; mx[1] = hi.y; mx[2] = hi.z;
+    for (int k = 0; k < 3; ++k) cc[k] = box_center(mn[k], mx[k]);
+  }
+  uint32_t* acc = uniform ? lacc : q.acc + (size_t)(take ? node : 0u) * 54u;
+  wave_box_accumulate(acc, take, mn, mx, nullptr);
+  wave_box_accumulate(acc + 6, take, cc, cc, nullptr);
+  if (!uniform) return;
+  __syncthreads();
+  if (tid < 12u) {
+    uint32_t* g = q.acc + (size_t)hn * 54u + tid;
+    if ((tid % 6u) < 3u) atomicMin(g, lacc[tid]); else atomicMax(g, lacc[tid]);
+  }
+}
+// C: split axis
+__global__ __launch_bounds__(256) void k_sahw_axis(SahBuffers q, uint32_t level) {
+  const uint32_t n_active = q.counters[8u + level];
+  const uint32_t* active = q.active[level & 1u];
+  for (uint32_t a = blockIdx.x * 256u + threadIdx.x; a < n_active; a += gridDim.x * 256u) sah_split_axis(q, active[a]);
+}
+// D: buckets; chunk_counts[12 * chunk ..]: the six bucket counts of the chunk's head run, then of its tail run
+__global__ __launch_bounds__(1024) void k_sahw_buckets(LbvhBuffers b, SahBuffers q, uint32_t level, uint32_t* __restrict__ chunk_counts) {
+  __shared__ uint32_t lacc[42];  // six bucket boxes, six counts
+  __shared__ uint32_t runs[12];
+  const RefitScene none{};
+  const uint32_t tid = threadIdx.x, n = b.n, side = level & 1u, c0 = blockIdx.x * 1024u, p = c0 + tid;
+  const uint32_t* item_node = q.item_node[side];
+  const uint32_t hn = item_node[c0], tn = item_node[min(c0 + 1023u, n - 1u)];
+  const bool uniform = hn == tn;
+  if (uniform && !sah_splitting(q, hn, level)) return;  // (block-uniform; F never reads this chunk's counts)
+  if (tid < 42u) lacc[tid] = tid < 36u ? sah_acc_init(tid) : 0u;
+  if (tid < 12u) runs[tid] = 0u;
+  __syncthreads();
+  const uint32_t node = p < n ? item_node[p] : SAH_DONE;
+  bool take = sah_splitting(q, node, level);
+  float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
+  int bk = 0;
+  if (take) {
+    const float* sp = q.split + (size_t)node * 4u;
+    take = f2u(sp[3]) == 0u;
+    if (take) {
+      f3 lo, hi;
+      lbvh_shape_box<false>(none, b, q.order[side][p], lo, hi);
+      mn[0] = lo.x; mn[1] = lo.y; mn[2] = lo.z;
+      mx[0] = hi.x; mx[1] = hi.y; mx[2] = hi.z;
+      const int axis = (int)f2u(sp[2]);
+      const float rel = (box_center(mn[axis], mx[axis]) - sp[0]) / sp[1];
+      bk = (int)(rel * (6.0f - 0.01f));
+      bk = min(max(bk, 0), 5);
+      q.item_bucket[p] = (uint8_t)bk;
+    }
+  }
+  for (int k6 = 0; k6 < 6; ++k6) {
+    const bool mine = take && bk == k6;
+    uint32_t* acc = q.acc + (size_t)(mine ? node : 0u) * 54u;
+    wave_box_accumulate(uniform ? lacc + 6 * k6 : acc + 12 + 6 * k6, mine, mn, mx, uniform ? lacc + 36 + k6 : acc + 48 + k6);
+    if (!uniform) {
+      const unsigned long long mh = __ballot(mine && node == hn), mt = __ballot(mine && node == tn);
+      if ((tid & 63u) == 0u) {
+        if (mh) atomicAdd(&runs[k6], (uint32_t)__popcll(mh));
+        if (mt) atomicAdd(&runs[6 + k6], (uint32_t)__popcll(mt));
+      }
+    }
+  }
+  __syncthreads();
+  if (uniform && tid < 42u) {
+    uint32_t* g = q.acc + (size_t)hn * 54u + 12u + tid;
+    if (tid >= 36u) atomicAdd(g, lacc[tid]);
+    else if ((tid % 6u) < 3u) atomicMin(g, lacc[tid]);
+    else atomicMax(g, lacc[tid]);
+  }
+  if (tid < 12u) chunk_counts[12u * blockIdx.x + tid] = uniform ? lacc[36u + tid % 6u] : runs[tid];
+}
+// E: the cheapest split, the children (their accumulators start empty: there is no step A here)
+__global__ __launch_bounds__(256) void k_sahw_split(LbvhBuffers b, SahBuffers q, uint32_t level, uint32_t defer) {
+  const uint32_t n_active = q.counters[8u + level];
+  const uint32_t* active = q.active[level & 1u];
+  for (uint32_t a = blockIdx.x * 256u + threadIdx.x; a < n_active; a += gridDim.x * 256u) {
+    uint32_t child[2];
+    sah_split_node(b, q, active[a], level, defer, q.active[(level + 1u) & 1u], &q.counters[9u + level], child);
+    for (int side = 0; side < 2; ++side)
+      if (child[side] < b.n - 1u)
+        for (uint32_t w = 0; w < 54u; ++w) q.acc[(size_t)child[side] * 54u + w] = sah_acc_init(w);
+  }
+}
+// F: stable re-order, bucket by bucket inside every segment
+__global__ __launch_bounds__(1024) void k_sahw_reorder(LbvhBuffers b, SahBuffers q, uint32_t level, const uint32_t* __restrict__ chunk_counts) {
+  __shared__ uint32_t scan_lds[68];
+  __shared__ uint16_t pre[6][1024];
+  __shared__ uint32_t carry[6];  // per bucket: items of the head run's node in the chunks before this one
+  const uint32_t tid = threadIdx.x, n = b.n, side = level & 1u, c0 = blockIdx.x * 1024u, p = c0 + tid;
+  const uint32_t* order = q.order[side];
+  const uint32_t* item_node = q.item_node[side];
+  uint32_t* order_out = q.order[side ^ 1u];
+  uint32_t* item_node_out = q.item_node[side ^ 1u];
+  const bool in = p < n;
+  const uint32_t node = in ? item_node[p] : SAH_DONE;
+  const uint32_t hn = item_node[c0], tn = item_node[min(c0 + 1023u, n - 1u)];
+  if (hn == tn && !sah_splitting(q, hn, level)) {  // (block-uniform) nothing of this chunk is split at this level
+    if (in) {
+      order_out[p] = order[p];
+      item_node_out[p] = node;
+    }
+    return;
+  }
+  const bool split_now = in && sah_splitting(q, node, level);
+  const bool moving = split_now && q.offsets[(size_t)node * 14u + 13u] != 6u;
+  const uint32_t bk = moving ? q.item_bucket[p] : 7u;
+  const bool head = tid == 0u || !in || item_node[p - 1u] != node;
+  uint32_t packed[3], h;
+  block_scan_buckets_and_heads(bk, head ? tid : 0u, scan_lds, packed, h);
+  for (uint32_t k6 = 0; k6 < 6u; ++k6) pre[k6][tid] = (uint16_t)((packed[k6 >> 1] >> (16u * (k6 & 1u))) & 0xFFFFu);
+  if (tid < 6u) carry[tid] = 0u;
+  __syncthreads();
+  if (sah_splitting(q, hn, level) && q.offsets[(size_t)hn * 14u + 13u] != 6u) {  // (block-uniform)
+    const uint32_t begin = b.first[hn];
+    if (begin < c0 && tid < 1020u) {
+      const uint32_t f = begin >> 10, k6 = tid % 6u, g = tid / 6u;  // the node's first chunk: there it is the tail run
+      uint32_t sum = g == 0u ? chunk_counts[12u * f + 6u + k6] : 0u;
+      for (uint32_t c = f + 1u + g; c < blockIdx.x; c += 170u) sum += chunk_counts[12u * c + k6];  // ... and every chunk between is its alone
+      if (sum) atomicAdd(&carry[k6], sum);
+    }
+  }
+  __syncthreads();
+  if (split_now) {
+    const uint32_t* off = q.offsets + (size_t)node * 14u;
+    const uint32_t begin = b.first[node], n_left = off[12];
+    uint32_t target = p;
+    if (moving) target = off[bk] + (h == 0u ? carry[bk] : 0u) + ((uint32_t)pre[bk][tid] - (uint32_t)pre[bk][h]);
+    const bool goes_left = target < begin + n_left;
+    const uint32_t child = goes_left ? b.left[node] : b.right[node];
+    order_out[target] = order[p];
+    item_node_out[target] = child >= n - 1u ? SAH_DONE : child;
+  } else if (in) {  // a leaf already, or a node that waits for a workgroup of its own
+    order_out[p] = order[p];
+    item_node_out[p] = node;
+  }
+}
+// after the last level: the nodes still unsplit join the deferred ones; leaves fixed so far are final
+__global__ __launch_bounds__(256) void k_sahw_finish(LbvhBuffers b, SahBuffers q, uint32_t levels) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x, side = levels & 1u;
+  const uint32_t n_left = q.counters[8u + levels];
+  for (uint32_t a = i; a < n_left; a += gridDim.x * 256u) q.roots[atomicAdd(&q.counters[1], 1u)] = q.active[side][a];
+  if (i < b.n && q.item_node[side][i] == SAH_DONE) b.ids_sorted[i] = q.order[side][i];
 }
 
 // ------------------------------------------------------------------ a deformed mesh's new box, carried to its instances
@@ -1029,12 +1241,13 @@ size_t lbvh_scratch_bytes(uint32_t n, size_t* sort_temp_bytes) {
   if (sort_temp_bytes) *sort_temp_bytes = temp;
   const size_t nn = ((size_t)n + 63) & ~(size_t)63;
   return 256 + temp + nn * (4 * 4 /* codes, ids x2 */ + 5 * 4 /* parent, left, right, first, last */ + 4 /* leaf_parent */ + 4 /* arrived */ + 4 /* swap (padded) */) +
-         2 * nn * 2 * 16 /* node boxes, 2n - 1 */ + nn * (4 /* item_node[1] */ + 4 /* item_bucket, padded */ + 2 * 4 /* active lists */ + 54 * 4 + 4 * 4 + 14 * 4 + 2 * 4) /* SAH build */;
+         2 * nn * 2 * 16 /* node boxes, 2n - 1 */ + nn * (4 /* item_node[1] */ + 4 /* item_bucket, padded */ + 2 * 4 /* active lists */ + 54 * 4 + 4 * 4 + 14 * 4 + 2 * 4) /* SAH build */ +
+         (nn / 1024 + 1) * 12 * 4 /* chunk_counts */;
 }
 // mode 0: LBVH (Morton order), mode 1: the reference's binned SAH (`bvh` 0.7.1).  `lo` / `hi` = the node array to overwrite,
 // `stride` float4 between consecutive nodes (2: interleaved pairs, 1: two planes)
 int launch_tree_build(hipStream_t st, int mode, bool light, const RefitScene& s, uint32_t n, const float4* box_lo, const float4* box_hi, void* scratch, float4* lo,
-                      float4* hi, uint32_t stride, uint32_t orderings) {
+                      float4* hi, uint32_t stride, uint32_t orderings, size_t ord_stride, const MeshTree* keep, bool one_workgroup_top) {
   if (n == 0) return 0;
   size_t temp = 0;
   (void)lbvh_scratch_bytes(n, &temp);
@@ -1044,7 +1257,7 @@ int launch_tree_build(hipStream_t st, int mode, bool light, const RefitScene& s,
   b.n = n;
   b.box_lo = box_lo;
   b.box_hi = box_hi;
-  b.keep_order0 = mode == 1 ? 1u : 0u;
+  b.keep_order0 = (mode == 1 || keep) ? 1u : 0u;  // (a mesh tree's ordering 0 is what its refit keeps: left before right)
   b.bounds = (float*)p; p += 256;
   void* sort_temp = p; p += temp;
   auto u32 = [&]() { uint32_t* q = (uint32_t*)p; p += nn * 4; return q; };
@@ -1069,8 +1282,26 @@ int launch_tree_build(hipStream_t st, int mode, bool light, const RefitScene& s,
     q.node_level = (uint32_t*)p; p += nn * 4;
     q.roots = (uint32_t*)p; p += nn * 4;
     q.counters = (uint32_t*)b.bounds;                        // (256 B, unused by this mode)
+    uint32_t* chunk_counts = (uint32_t*)p; p += (size_t)((n + 1023u) / 1024u) * 12 * 4;
     const dim3 subtrees((unsigned)std::min<size_t>(std::max<size_t>(n / 2, 1), 4096));
-    if (light) {
+    if (keep && n >= SAH_WIDE_MIN && !one_workgroup_top) {  // (mesh trees only: the instance tree and the light tree keep the one-workgroup top at any size)
+      // the levels a balanced tree needs down to SAH_SUBTREE shapes per node, and six more for the lopsided splits of a real one
+      uint32_t levels = 6u;
+      while (((size_t)SAH_SUBTREE << (levels - 6u)) < n) ++levels;
+      levels = std::min(levels, SAH_WIDE_MAX_LEVELS);
+      const dim3 chunks((n + 1023u) / 1024u);
+      hipLaunchKernelGGL(k_sahw_setup, chunks, dim3(1024), 0, st, b, q, levels);
+      for (uint32_t level = 0; level < levels; ++level) {
+        const dim3 per_node((unsigned)std::min<size_t>(((size_t)1 << std::min(level, 20u)) / 256 + 1, 256));  // (at most 2^level nodes)
+        hipLaunchKernelGGL(k_sahw_bounds, chunks, dim3(1024), 0, st, b, q, level);
+        hipLaunchKernelGGL(k_sahw_axis, per_node, dim3(256), 0, st, q, level);
+        hipLaunchKernelGGL(k_sahw_buckets, chunks, dim3(1024), 0, st, b, q, level, chunk_counts);
+        hipLaunchKernelGGL(k_sahw_split, per_node, dim3(256), 0, st, b, q, level, SAH_SUBTREE);
+        hipLaunchKernelGGL(k_sahw_reorder, chunks, dim3(1024), 0, st, b, q, level, (const uint32_t*)chunk_counts);
+      }
+      hipLaunchKernelGGL(k_sahw_finish, per_shape, dim3(256), 0, st, b, q, levels);
+      hipLaunchKernelGGL((k_sah_subtrees<false>), subtrees, dim3(1024), 0, st, s, b, q);
+    } else if (light) {
       hipLaunchKernelGGL((k_sah_build<true>), dim3(1), dim3(1024), 0, st, s, b, q);
       if (n > SAH_SUBTREE) hipLaunchKernelGGL((k_sah_subtrees<true>), subtrees, dim3(1024), 0, st, s, b, q);
     } else {
@@ -1091,7 +1322,15 @@ int launch_tree_build(hipStream_t st, int mode, bool light, const RefitScene& s,
   if (light) hipLaunchKernelGGL((k_lbvh_boxes<true>), per_shape, dim3(256), 0, st, s, b);
   else hipLaunchKernelGGL((k_lbvh_boxes<false>), per_shape, dim3(256), 0, st, s, b);
   const uint32_t threads = (2u * n - 1u) * orderings;
-  hipLaunchKernelGGL(k_lbvh_emit, dim3((threads + 255u) / 256u), dim3(256), 0, st, b, lo, hi, stride, (size_t)(3u * n - 2u) * stride, orderings);
+  hipLaunchKernelGGL(k_lbvh_emit, dim3((threads + 255u) / 256u), dim3(256), 0, st, b, lo, hi, stride, ord_stride ? ord_stride : (size_t)(3u * n - 2u) * stride, orderings);
+  if (keep) {  // the topology a later refit of this tree climbs (launch_mesh_tree_refit)
+    const size_t ni = (size_t)(n - 1u) * 4;
+    const std::pair<uint32_t*, const uint32_t*> planes[5] = {{keep->parent, b.parent}, {keep->left, b.left}, {keep->right, b.right}, {keep->first, b.first}, {keep->last, b.last}};
+    for (const auto& pl : planes)
+      if (ni) (void)hipMemcpyAsync(pl.first, pl.second, ni, hipMemcpyDeviceToDevice, st);
+    if (ni) (void)hipMemcpyAsync(keep->leaf_parent, b.leaf_parent, (size_t)n * 4, hipMemcpyDeviceToDevice, st);
+    (void)hipMemcpyAsync(keep->leaf_shape, b.ids_sorted, (size_t)n * 4, hipMemcpyDeviceToDevice, st);
+  }
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

@@ -21,6 +21,7 @@ struct DeformMesh {
   uint32_t n_ids = 0, n_emitters = 0;
   uint64_t ids_generation = ~0ull;
   bool deformed = false;                                       // `box` holds the current mesh box
+  bool have_boxes = false;                                     // tree.tri_lo / tri_hi hold the current triangle boxes
   bool pending = false;                                        // ... and its instances have not been given it yet
   // skin (hk_set_mesh_skin)
   void* skin_mem = nullptr;
@@ -249,7 +250,7 @@ int refit_mesh(hk_ctx* c, DeformMesh* d) {
   const size_t n_nodes = c->asset_nodes.size();
   launch_mesh_tree_refit(c->stream, d->tree, (float4*)(sbase + c->st_nodes) + 2 * (size_t)d->mesh.node_offset, 2 * n_nodes, c->threaded ? 8u : 1u);
   HK_HIP(hipGetLastError());
-  d->deformed = d->pending = true;
+  d->deformed = d->pending = d->have_boxes = true;
   c->deform_pending = true;
   return HK_OK;
 }
@@ -403,6 +404,58 @@ int hk_skin_mesh(hk_ctx* c, const HkMeshIndex* mesh, const float* joint_matrices
     launch_copy_region(c->stream, d->joint_mats, st, (size_t)n_joints * 64);  // (a copy kernel: the matrices are read per vertex)
     launch_mesh_skin(c->stream, d->bind_pos, d->bind_nrm, d->joints, d->weights, d->joint_mats, d->skin_vertices, d->pos, vn, d->box);
   });
+}
+
+// A new tree over the current triangles of one mesh, in place (hikari_hip.h).  The build is the instance level's (kernels_scene.hip
+// launch_tree_build) fed from the mesh's triangle boxes; its topology replaces the one the refit climbs.  The mesh box and the triangle
+// order stay, so nothing at the instance level moves: no propagation, only the staleness a deformation brings.
+int hk_rebuild_mesh_tree(hk_ctx* c, const HkMeshIndex* mesh, uint32_t mode) {
+  HK_REQUIRE(c && mesh, HK_E_INVALID, "NULL argument");
+  HK_REQUIRE(mode == HK_TREE_SAH || mode == HK_TREE_LBVH, HK_E_INVALID, "unknown tree build mode %u", mode);
+  HK_REQUIRE(c->have_meshes && c->have_materials && c->have_instances, HK_E_NOT_READY, "hk_upload_scene must come first");
+  {  // the size limit holds for an UPLOADED mesh record, before anything is allocated for it (find_mesh repeats the first check)
+    bool known = false;
+    for (const HkInstance& in : c->instances) known = known || memcmp(&in.mesh, mesh, sizeof(HkMeshIndex)) == 0;
+    HK_REQUIRE(known, HK_E_INVALID, "no uploaded instance carries the mesh record (%u, %u, %u, %u)", mesh->vertex, mesh->primitive, mesh->node_offset, mesh->node_count);
+    HK_REQUIRE((mesh->node_count + 2) / 3 <= HK_MESH_REBUILD_MAX_TRIANGLES, HK_E_UNSUPPORTED, "a mesh of %u triangles is beyond the %u the device build takes",
+               (mesh->node_count + 2) / 3, HK_MESH_REBUILD_MAX_TRIANGLES);
+  }
+  DeformMesh* d = nullptr;
+  int rc;
+  if ((rc = begin(c, mesh, &d))) return rc;
+  const uint32_t n = d->n_tris;
+  const size_t need = lbvh_scratch_bytes(n, nullptr);
+  if (need > c->lbvh_scratch_cap) {  // (grows rarely: what is enqueued may still use the old one)
+    if ((rc = sync_all(c))) return rc;
+    if (c->lbvh_scratch) (void)hipFree(c->lbvh_scratch);
+    c->lbvh_scratch = nullptr;
+    c->lbvh_scratch_cap = 0;
+    HK_HIP(hipMalloc(&c->lbvh_scratch, need + need / 4));
+    c->lbvh_scratch_cap = need + need / 4;
+  }
+  if ((rc = join_all(c))) return rc;  // (the mesh-level region has one copy: behind every frame enqueued so far, as a deformation)
+  c->scene_epoch += 1;                // (scene memory is written from here on: hk_context.hpp, primary-ray pipelining)
+  const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
+  uint8_t* sbase = c->scene_mem + slots;
+  if (!d->have_boxes) {
+    const uint32_t p0 = d->mesh.primitive;
+    launch_mesh_triangle_boxes(c->stream, (const float4*)(sbase + c->st_v0) + p0, (const float4*)(sbase + c->st_v1) + p0, (const float4*)(sbase + c->st_v2) + p0, n,
+                               d->tree.tri_lo, d->tree.tri_hi);
+    d->have_boxes = true;
+  }
+  float4* lo = (float4*)(sbase + c->st_nodes) + 2 * (size_t)d->mesh.node_offset;
+  const hkd::RefitScene none{};
+  HK_REQUIRE(launch_tree_build(c->stream, mode == HK_TREE_SAH ? 1 : 0, false, none, n, d->tree.tri_lo, d->tree.tri_hi, c->lbvh_scratch, lo, lo + 1, 2u, c->threaded ? 8u : 1u,
+                               2 * c->asset_nodes.size(), &d->tree, c->mesh_rebuild_one_workgroup) == 0,
+             HK_E_HIP, "device build of the mesh tree failed: %s", hipGetErrorString(hipGetLastError()));
+  c->meshes_deformed = true;
+  c->mirrors_stale = true;
+  update_shared_transform(c);  // (the one-level tree is not walked from here on)
+  const std::pair<uint32_t, uint32_t> key(d->mesh.node_offset, d->mesh.node_count);
+  c->wide_meshes.erase(std::remove(c->wide_meshes.begin(), c->wide_meshes.end(), key), c->wide_meshes.end());
+  c->wide_mesh_check = true;
+  c->wide_tlas_dirty = true;
+  return HK_OK;
 }
 
 // Test hook (hikari_hip_debug.h): the emitter records and the alias table of the slot in use

@@ -608,6 +608,29 @@ int hk_scene_builder_set_mesh_vertices(hk_scene_builder* b, uint32_t mesh_id, co
   return HK_OK;
 }
 
+// The host twin of the device rebuild (mesh_deform.hip hk_rebuild_mesh_tree, HK_TREE_SAH): the tree hk_scene_builder_add_mesh would
+// build over the mesh's CURRENT triangles - `bvh` 0.7.1 BVH::build over their boxes, formed with add_mesh's arithmetic - and then the
+// canonical navigator boxes of refit_nodes, so that the result is what the device writes and what a later refit leaves alone.
+int hk_scene_builder_rebuild_mesh_tree(hk_scene_builder* b, uint32_t mesh_id) {
+  HK_REQUIRE(b, HK_E_INVALID, "builder is NULL");
+  HK_REQUIRE(mesh_id < b->meshes.size(), HK_E_INVALID, "unknown mesh id");
+  const BuilderMesh& mesh = b->meshes[mesh_id];
+  std::vector<float> boxes;
+  boxes.reserve(mesh.primitives.size() * 6);
+  for (const HkPrimitive& p : mesh.primitives) {
+    Box bx = Box::empty();
+    for (int k = 0; k < 3; ++k) bx.grow(p.vertices[k].position);
+    boxes.insert(boxes.end(), bx.mn, bx.mn + 3);
+    boxes.insert(boxes.end(), bx.mx, bx.mx + 3);
+  }
+  std::vector<HkNode> nodes = build_flat_bvh(boxes);  // (a copy: an error leaves the builder as it was)
+  HK_REQUIRE(nodes.size() == mesh.nodes.size() && refit_nodes(nodes, mesh.primitives), HK_E_UNSUPPORTED, "the rebuilt mesh tree is not in the flatten_custom layout");
+  b->meshes[mesh_id].nodes.swap(nodes);
+  b->meshes_dirty = true;
+  b->finished = false;
+  return HK_OK;
+}
+
 int hk_scene_builder_mesh_index(const hk_scene_builder* b, uint32_t mesh_id, HkMeshIndex* out) {
   HK_REQUIRE(b && out, HK_E_INVALID, "NULL argument");
   HK_REQUIRE(!b->meshes_dirty && mesh_id < b->mesh_index.size(), HK_E_INVALID, "unknown mesh id, or the builder was not finished since the mesh was added");

@@ -511,6 +511,10 @@ class MultiEngine:
         j = np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1, 16)
         self.api.call("multi_skin_mesh", self.h, C.byref(mesh), j.ctypes.data_as(C.POINTER(F.f32)), len(j))
 
+    def rebuild_mesh_tree(self, mesh, mode=F.TREE_SAH):
+        """hk_multi_rebuild_mesh_tree: the mesh's tree built again on every band's copy of the scene."""
+        self.api.call("multi_rebuild_mesh_tree", self.h, C.byref(mesh), mode)
+
     def read_mesh_geometry(self, mesh):
         """Engine.read_mesh_geometry of every band's context (test hook)."""
         return [e.read_mesh_geometry(mesh) for e in self.contexts]

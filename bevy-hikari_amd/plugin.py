@@ -361,6 +361,11 @@ class SceneBuilder:
         self.api.call("scene_builder_set_mesh_vertices", self.h, mesh_id, pos.ctypes.data_as(C.POINTER(F.f32)),
                       None if nrm is None else nrm.ctypes.data_as(C.POINTER(F.f32)))
 
+    def rebuild_mesh_tree(self, mesh_id):
+        """The host mirror of Engine.rebuild_mesh_tree (hk_scene_builder_rebuild_mesh_tree): the mesh's tree built again over its current
+        triangles, as add_mesh would build it; finish() + upload next."""
+        self.api.call("scene_builder_rebuild_mesh_tree", self.h, mesh_id)
+
     def mesh_index(self, mesh_id):
         """The HkMeshIndex of a mesh after a finish (what Engine.update_mesh_vertices / skin_mesh take)."""
         out = F.HkMeshIndex()
@@ -501,6 +506,11 @@ class Engine:
         """Per frame: column-major 4x4 joint matrices (n x 16 floats); the device skins and refits (hk_skin_mesh)."""
         j = np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1, 16)
         self.api.call("skin_mesh", self.ctx, C.byref(mesh), j.ctypes.data_as(C.POINTER(F.f32)), len(j))
+
+    def rebuild_mesh_tree(self, mesh, mode=F.TREE_SAH):
+        """A new tree over the current triangles of one uploaded mesh, built on the device in place (hk_rebuild_mesh_tree): F.TREE_SAH = the
+        tree SceneBuilder.rebuild_mesh_tree builds, F.TREE_LBVH = the quick Morton-order tree.  Later deformations refit the new shape."""
+        self.api.call("rebuild_mesh_tree", self.ctx, C.byref(mesh), mode)
 
     def read_mesh_nodes(self):
         """(nodes, count, orderings): the mesh-level node array as the device holds it, every ordering (test hook)."""

@@ -300,6 +300,22 @@ def waving_cloth(rest, frame, amplitude=0.08):
     return p.astype(np.float32), n.astype(np.float32)
 
 
+def folded_cloth(rest, fold=1.0, gap=0.02):
+    """The cloth folded onto itself along its middle line x = 0: the half x > 0 is turned about the z axis by `fold` x 180 degrees (fold 1:
+    it lies `gap` above the other half, triangles that were a cloth's width apart now on top of each other).  Positions and normals.
+    What a refit handles badly: the bind-pose tree pairs neighbours of the FLAT sheet, whose boxes now overlap the other half's."""
+    p = rest.astype(np.float64).copy()
+    n = np.tile(np.array([0.0, 1.0, 0.0]), (len(p), 1))
+    ang = math.pi * fold
+    c, s = math.cos(ang), math.sin(ang)
+    right = p[:, 0] > 0.0
+    x, y = p[right, 0], p[right, 1]
+    p[right, 0] = c * x - s * y
+    p[right, 1] = s * x + c * y + gap * fold
+    n[right] = [-s, c, 0.0]
+    return p.astype(np.float32), n.astype(np.float32)
+
+
 def pulsing_sphere(rest, frame):
     """The sphere's positions at `frame`: scaled by a pulse around its centre (the normals keep their directions)."""
     return (rest * np.float32(1.0 + 0.25 * math.sin(0.9 * frame))).astype(np.float32)

@@ -348,6 +348,8 @@ class HikariPlugin {
     return moved;
   }
   void rebuild_trees(uint32_t mode = HK_TREE_SAH) { check(hk_rebuild_scene_trees(ctx_.get(), mode), "hk_rebuild_scene_trees"); }
+  // a new tree over the current triangles of one deformed mesh, built on the device in place (later deformations refit the new shape)
+  void rebuild_mesh_tree(const HkMeshIndex& mesh, uint32_t mode = HK_TREE_SAH) { check(hk_rebuild_mesh_tree(ctx_.get(), &mesh, mode), "hk_rebuild_mesh_tree"); }
 
   // one frame of the camera's render graph; by_nodes = dispatch by dispatch through the three nodes,
   // otherwise one hk_frame_render call.  Returns the frame number used.
@@ -418,6 +420,7 @@ class HikariMultiGpuPlugin {
     return moved;
   }
   void rebuild_trees(uint32_t mode = HK_TREE_SAH) { check(hk_multi_rebuild_scene_trees(m_, mode), "hk_multi_rebuild_scene_trees"); }
+  void rebuild_mesh_tree(const HkMeshIndex& mesh, uint32_t mode = HK_TREE_SAH) { check(hk_multi_rebuild_mesh_tree(m_, &mesh, mode), "hk_multi_rebuild_mesh_tree"); }
   // rows of last frame's reservoirs fetched across the band borders before reprojection (0 for a static camera)
   void set_history_rows(uint32_t rows) { check(hk_multi_set_history_rows(m_, rows), "hk_multi_set_history_rows"); }
   // bands of unequal height: explicit boundaries (scaled render rows, bands + 1 entries; empty = the equal split) ...

@@ -506,6 +506,11 @@ int hk_scene_builder_alias_table(const hk_scene_builder* b, const HkAliasEntry**
  * of a finished mesh.  Topology and tree links are kept; every tree box becomes the union of the triangle boxes below it (what the
  * device refit computes), the mesh box is re-derived.  The next finish lays the instance level out again from them. */
 int hk_scene_builder_set_mesh_vertices(hk_scene_builder* b, uint32_t mesh_id, const float* positions, const float* normals);
+/* The host twin of hk_rebuild_mesh_tree (HK_TREE_SAH): the mesh's tree built again over its CURRENT triangles, as
+ * hk_scene_builder_add_mesh would build it for these positions (`bvh` 0.7.1 BVH::build), every navigator box then the union of the two
+ * boxes below it as hk_scene_builder_set_mesh_vertices forms them.  Primitives, vertices and the mesh box are untouched; the node
+ * count stays (3n - 2).  An error leaves the builder as it was.  The next finish lays the mesh level out again. */
+int hk_scene_builder_rebuild_mesh_tree(hk_scene_builder* b, uint32_t mesh_id);
 /* the HkMeshIndex of a mesh after a finish (what its instances carry, and what the hk_*_mesh_* calls take) */
 int hk_scene_builder_mesh_index(const hk_scene_builder* b, uint32_t mesh_id, HkMeshIndex* out);
 
@@ -596,6 +601,22 @@ int hk_set_mesh_skin(hk_ctx* ctx, const HkMeshIndex* mesh, uint32_t n_vertices, 
 /* per frame: n_joints column-major 4x4 joint matrices; the device skins the mesh (positions and normals, mesh-local) and refits as
  * hk_update_mesh_vertices does.  A joint index >= n_joints in the skin is refused (HK_E_INVALID, nothing written). */
 int hk_skin_mesh(hk_ctx* ctx, const HkMeshIndex* mesh, const float* joint_matrices, uint32_t n_joints);
+/* ... and the REBUILD of one mesh's tree on the device, for when refits have degraded it (a skinned character far from its bind pose,
+ * a cloth folded onto itself): a new tree over the mesh's current triangle boxes, written in place over the mesh's nodes in the
+ * mesh-level region - ordering 0 in the builder's left-before-right order, orderings 1-7 by the rule of hk_bvh_rethread, single-leaf
+ * navigators folded - and the topology the refit climbs replaced by the new tree's, so that the next hk_update_mesh_vertices /
+ * hk_skin_mesh refits the NEW shape.  Skins stay.  The mesh box and the triangle order do not change: nothing at the instance level moves.
+ *   HK_TREE_SAH   the tree hk_scene_builder_rebuild_mesh_tree builds, node for node and byte for byte.  Meshes above 32 768 triangles
+ *                 run the top levels of the build on the whole chip (a fixed number of multi-workgroup levels, the rest one workgroup
+ *                 per subtree); smaller ones in one workgroup as the instance tree does.
+ *   HK_TREE_LBVH  the Morton build: a valid tree, not the host's.
+ * Contract of a deformation (see above): stream-ordered behind everything enqueued, no host wait except a rare growth of the build
+ * scratch (about 330 B per triangle, kept in the context); the host mirrors are stale afterwards - re-layouts are refused with
+ * HK_E_NOT_READY and the one-level walk is off until hk_upload_scene brings the builder's twin.  A mesh never deformed works too.
+ * Refused with nothing written: an unknown mesh record or mode (HK_E_INVALID), no scene (HK_E_NOT_READY), a mesh of more than
+ * HK_MESH_REBUILD_MAX_TRIANGLES triangles (HK_E_UNSUPPORTED). */
+#define HK_MESH_REBUILD_MAX_TRIANGLES 4194304u
+int hk_rebuild_mesh_tree(hk_ctx* ctx, const HkMeshIndex* mesh, uint32_t mode);
 int hk_upload_textures(hk_ctx* ctx, const HkImageDesc* images, uint32_t n_images);
 /* InstanceRenderAssets::set + write_buffer, instance.rs:82-108 */
 int hk_upload_instances(hk_ctx* ctx, const HkInstance* instances, uint32_t n_instances, const HkNode* instance_nodes,
@@ -847,6 +868,7 @@ int hk_multi_update_mesh_vertices(hk_multi* m, const HkMeshIndex* mesh, uint32_t
 int hk_multi_set_mesh_skin(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vertices, const float* bind_positions, const float* bind_normals,
                            const uint16_t* joint_indices, const float* joint_weights);
 int hk_multi_skin_mesh(hk_multi* m, const HkMeshIndex* mesh, const float* joint_matrices, uint32_t n_joints);
+int hk_multi_rebuild_mesh_tree(hk_multi* m, const HkMeshIndex* mesh, uint32_t mode);
 int hk_multi_set_band_bounds(hk_multi* m, const uint32_t* bounds, uint32_t n_bounds);
 /* hk_migrate_bands for the one-process form: the rows that change owner travel as peer copies, then every band takes the new split */
 int hk_multi_migrate_bands(hk_multi* m, const uint32_t* new_bounds, uint32_t n_bounds, uint32_t next_frame_number, const HkSettings* settings);

@@ -95,6 +95,7 @@ int hk_debug_comm_lanes(hk_ctx* ctx, uint32_t* lanes);
 /* 6, 7 and 8 belonged to retired options and are not reused: hk_debug_set_option rejects them (HK_E_INVALID) */
 #define HK_DEBUG_OPT_MAIN_PRIORITY 9u /* the priority of the context's own main stream, created again at once: -1 by the library's rule (the highest if the context dispatches at most 6 Mi pixels per frame; what the context's first frame decides by itself), 0 the default priority, 1 the highest.  A/B and tests: a stream created again several times ends up sharing a hardware queue */
 #define HK_DEBUG_OPT_PREPASS_PIPELINE 10u /* a frame's primary rays on a stream of their own beside the previous frame's spatial pass, where the order allows (context.hip stage TEMPORAL): -1 by the library's rule (default: scenes beyond the LDS copy in frames of up to 3 Mi pixels, on a context whose chain runs at the highest priority), 0 never, 1 whenever the order allows */
+#define HK_DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP 11u /* 1: hk_rebuild_mesh_tree (HK_TREE_SAH) runs the top levels of its build in one workgroup at any mesh size, as the instance tree's build does (default 0: on the whole chip from 32 768 triangles); the same tree either way - the A/B of tools/deform_probe.py */
 int hk_debug_set_option(hk_ctx* ctx, uint32_t option, int64_t value);
 /* hk_multi_*: 1 = the calling thread enqueues every band's launches one after another instead of one thread per band (process-wide) */
 int hk_debug_multi_serial(int on);

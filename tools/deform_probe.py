@@ -4,7 +4,7 @@ mesh.rs:76-166) against the device path (hk_update_mesh_vertices / hk_skin_mesh:
 ordering, the instance level) for one cloth mesh of ~10^4 / 10^5 / 10^6 triangles in a scene beyond the LDS copy (eight orderings).
 Device times: host wall clock of the call plus the wait for everything it enqueued (hk_debug_read_emitters flushes and synchronises),
 median of the repeats.  Also the SAH cost (node area / root area, summed) of the refit tree against a fresh host build over the same
-deformed triangles.   Usage: python tools/deform_probe.py [--out FILE] [triangles ...]"""
+deformed triangles; then the fold (rebuild_probe): a deformation a refit handles badly, and hk_rebuild_mesh_tree against it.   Usage: python tools/deform_probe.py [--out FILE] [triangles ...]"""
 import ctypes as C
 import json
 import os
@@ -102,9 +102,88 @@ def probe(triangles, repeats=10):
     fe.upload_scene(f)
     fn, fc, _ = fe.read_mesh_nodes()
     out["sah_fresh_build"] = round(sah_cost(fn, fc), 3)
-    eng.close()
     fe.close()
+    rebuild_probe(eng, index, p, uv, idx, out, sun)
+    eng.close()
     return out
+
+
+def frame_ms(eng, sun, frames=8, warmup=6, size=(960, 540), first=1):
+    """mean time of `frames` frames looking at the scene's middle (where the cloth lies) after `warmup` frames, host wall clock; the same
+    frame numbers for every tree (the caller resizes once)"""
+    from bevy_hikari_amd.plugin import Camera, look_at_transform
+
+    cam = Camera(look_at_transform((0.0, 2.0, 2.4), (0.0, 0.0, 0.0)), *size)   # (the cloth lies around the origin)
+    lights, s = hk.lights_uniform(directional=sun), hk.HikariSettings(indirect_bounces=1, upscale=hk.Upscale.SMAA_TU_1_0)
+    view, pview = cam.view_uniform(), cam.previous_view_uniform()
+    for n in range(first, first + warmup):
+        eng.frame_render(hk.frame_uniform(s, n), view, pview, lights, s.to_c())
+    eng.wait()
+    t0 = time.perf_counter()
+    for n in range(first + warmup, first + warmup + frames):
+        eng.frame_render(hk.frame_uniform(s, n), view, pview, lights, s.to_c())
+    eng.wait()
+    return round(1e3 * (time.perf_counter() - t0) / frames, 3)
+
+
+def rebuild_probe(eng, index, rest, uv, idx, out, sun, repeats=5):
+    """A deformation a refit handles badly - the cloth folded onto itself along its middle line (S.folded_cloth) - and the rebuild of its
+    tree on the device (hk_rebuild_mesh_tree): SAH cost of the refit tree, of the rebuilt tree and of a fresh host build, the time of the
+    rebuild (call + flush + full synchronisation), and of a frame with either tree; the same for HK_TREE_LBVH."""
+    q, qn = S.folded_cloth(rest)
+    cost = lambda: round(sah_cost(eng.read_mesh_nodes()[0], index.node_count, index.node_offset), 3)
+
+    def refit_state():   # the device's tree still has the bind pose's shape (only refits so far): deforming refits it to the fold
+        eng.update_mesh_vertices(index, q, qn)
+        sync(eng)
+
+    eng.resize(960, 540, 1.0)
+    refit_state()
+    out["fold_sah_refit"] = cost()
+    out["fold_frame_refit_ms"] = frame_ms(eng, sun)
+    fresh = SceneBuilder()
+    t0 = time.perf_counter()
+    fid = fresh.add_mesh(q, qn, uv, idx)
+    out["fold_host_bvh_build_ms"] = round(1e3 * (time.perf_counter() - t0), 2)
+    fresh.add_instance(fid, fresh.add_material(standard_material()), np.eye(4, dtype=np.float32).reshape(-1))
+    fe = hk.Engine(device=0, flags=F.CTX_EXACT_TRAVERSAL)
+    fe.upload_scene(fresh.finish())
+    fn, fc, _ = fe.read_mesh_nodes()
+    out["fold_sah_fresh_build"] = round(sah_cost(fn, fc), 3)
+    fe.close()
+    times = []
+    for r in range(repeats):   # (the first call grows the scratch: the median leaves it out)
+        t0 = time.perf_counter()
+        eng.rebuild_mesh_tree(index, F.TREE_SAH)
+        sync(eng)
+        eng.wait()
+        times.append(1e3 * (time.perf_counter() - t0))
+    out["device_rebuild_ms"] = round(float(np.median(times)), 3)
+    out["fold_sah_device_rebuild"] = cost()
+    out["fold_frame_rebuilt_ms"] = frame_ms(eng, sun)
+    if out["triangles"] <= 200_000:   # once: the top of the build in one workgroup, as the instance tree's build runs it
+        eng.set_debug_option(F.DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP, 1)
+        times = []
+        for r in range(3):
+            t0 = time.perf_counter()
+            eng.rebuild_mesh_tree(index, F.TREE_SAH)
+            sync(eng)
+            eng.wait()
+            times.append(1e3 * (time.perf_counter() - t0))
+        out["device_rebuild_one_workgroup_top_ms"] = round(float(np.median(times)), 3)
+        eng.set_debug_option(F.DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP, 0)
+    times = []
+    for r in range(repeats):
+        t0 = time.perf_counter()
+        eng.rebuild_mesh_tree(index, F.TREE_LBVH)
+        sync(eng)
+        eng.wait()
+        times.append(1e3 * (time.perf_counter() - t0))
+    out["device_rebuild_lbvh_ms"] = round(float(np.median(times)), 3)
+    out["fold_sah_lbvh"] = cost()
+    out["fold_frame_lbvh_ms"] = frame_ms(eng, sun)
+    out["rebuild_over_host_build"] = round(out["device_rebuild_ms"] / out["fold_host_bvh_build_ms"], 4)
+    out["rebuild_over_device_update"] = round(out["device_rebuild_ms"] / out["device_update_ms"], 2)
 
 
 if __name__ == "__main__":
