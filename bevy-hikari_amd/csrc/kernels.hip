@@ -904,7 +904,10 @@ __global__ __launch_bounds__(256) void k_tone_mapping(DFrame fr, const uint2* __
 __global__ void k_debug_math(uint32_t op, const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ out, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float a = (op >= 16 && op <= 19) ? 0.0f : x[i], b = y ? y[i] : 0.0f, r = 0.0f;
+  const bool wide = (op >= 16 && op <= 19) || (op >= 35 && op <= 52);  // 16 floats of x per item
+  const bool y4 = op >= 46 && op <= 49;                                 // 4 floats of y per item
+  float a = wide ? 0.0f : x[i], b = (y && !y4) ? y[i] : 0.0f, r = 0.0f;
+  const float* q = x + (wide ? 16 * i : 0);
   switch (op) {
     case 0: r = sin_(a); break;
     case 1: r = cos_(a); break;
@@ -923,8 +926,47 @@ __global__ void k_debug_math(uint32_t op, const float* __restrict__ x, const flo
     case 14: r = unpack2x16unorm(f32_to_u32(a)).x; break;        // decode of the integer a in 0..65535
     case 15: r = unsnorm8(f32_to_u32(a)); break;                 // a = the byte 0..255
     case 20: r = unorm8(f32_to_u32(a)); break;                   // a = the byte 0..255
+    // 21.. : the routines the kernels call where they differ from the contract's spelling, and the rest of hk_device_math.hpp
+    case 21: case 22: { float sn, cs; sincos_(a, &sn, &cs); r = (op == 21) ? sn : cs; break; }
+    case 23: r = exp_nonpositive_(a); break;
+    case 24: r = quotient_by_reciprocal(a, 1.0 / (double)b); break;
+    case 25: r = exp_nonpositive_(quotient_by_reciprocal(-fabsf(a), 1.0 / (double)b)); break;  // the denoiser's luminance weight
+    case 26: r = pow2_(a); break;
+    case 27: r = pow5_(a); break;
+    case 28: r = pow16_(a); break;
+    case 29: r = pow_quarter_(a); break;
+    case 30: r = f16_to_f32(f32_to_f16(a * b)); break;           // two roundings: f32 product, then f16
+    case 31: r = (float)unorm16(a); break;
+    case 32: r = (float)snorm8(a); break;
+    case 33: r = u2f(f32_to_u32(a)); break;
+    case 34: r = u2f((uint32_t)f32_to_i32(a)); break;
+    case 35: r = dot(F3(q[0], q[1], q[2]), F3(q[3], q[4], q[5])); break;
+    case 36: r = dot(F4(q[0], q[1], q[2], q[3]), F4(q[4], q[5], q[6], q[7])); break;
+    case 37: case 38: case 39: {
+      f3 o = cross(F3(q[0], q[1], q[2]), F3(q[3], q[4], q[5]));
+      r = (op == 38) ? o.y : ((op == 39) ? o.z : o.x);
+      break;
+    }
+    case 40: case 41: case 42: {
+      f3 o = normalize(F3(q[0], q[1], q[2]));
+      r = (op == 41) ? o.y : ((op == 42) ? o.z : o.x);
+      break;
+    }
+    case 43: case 44: case 45: {
+      f3 o = mul(mat3{F3(q[0], q[1], q[2]), F3(q[3], q[4], q[5]), F3(q[6], q[7], q[8])}, F3(q[9], q[10], q[11]));
+      r = (op == 44) ? o.y : ((op == 45) ? o.z : o.x);
+      break;
+    }
+    case 46: case 47: case 48: case 49: {  // columns c0..c3 = q[0..15], v = 4 floats of y (the host entry point requires y here)
+      f4 o = mul(make_float4(q[0], q[1], q[2], q[3]), make_float4(q[4], q[5], q[6], q[7]), make_float4(q[8], q[9], q[10], q[11]),
+                 make_float4(q[12], q[13], q[14], q[15]), F4(y[4 * i], y[4 * i + 1], y[4 * i + 2], y[4 * i + 3]));
+      r = (op == 46) ? o.x : ((op == 47) ? o.y : ((op == 48) ? o.z : o.w));
+      break;
+    }
+    case 50: r = length(F3(q[0], q[1], q[2])); break;
+    case 51: r = mix(q[0], q[1], q[2]); break;
+    case 52: r = fract(q[0]); break;
     case 16: case 17: case 18: case 19: {  // shading()/env_brdf() on 16 floats per item: V N L base_color radiance
-      const float* q = x + 16 * i;
       DFrame fr;
       fr.amb_r = fr.amb_g = fr.amb_b = 0.05f;
       Surface sf;

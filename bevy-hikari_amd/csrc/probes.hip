@@ -295,10 +295,12 @@ int hk_measure_gather(hk_ctx* c, size_t footprint_bytes, uint32_t bytes_per_step
   return rc;
 }
 
-// Test hook of the numeric contract (tests/test_math_contract.py)
+// Test hook of the numeric contract (tests/test_math_contract.py, tests/test_math_contract_domain.py)
 int hk_debug_math(hk_ctx* c, uint32_t op, const float* x, const float* y, float* out, size_t n) {
-  HK_REQUIRE(c && x && out && op <= 20, HK_E_INVALID, "bad argument");
-  const size_t xin = (op >= 16 && op <= 19 ? 16 : 1) * n;
+  HK_REQUIRE(c && x && out && op <= 52, HK_E_INVALID, "bad argument");
+  const bool wide = (op >= 16 && op <= 19) || (op >= 35 && op <= 52), y4 = op >= 46 && op <= 49;
+  HK_REQUIRE(y || !y4, HK_E_INVALID, "ops 46..49 take their vector in y");
+  const size_t xin = (wide ? 16 : 1) * n, yin = (y4 ? 4 : 1) * n;
   if (n == 0) return HK_OK;
   PROBE_BEGIN(c);
   float *dx = nullptr, *dy = nullptr, *dout = nullptr;
@@ -306,8 +308,8 @@ int hk_debug_math(hk_ctx* c, uint32_t op, const float* x, const float* y, float*
   HK_HIP(hipMalloc((void**)&dout, n * 4));
   HK_HIP(hipMemcpy(dx, x, xin * 4, hipMemcpyHostToDevice));
   if (y) {
-    HK_HIP(hipMalloc((void**)&dy, n * 4));
-    HK_HIP(hipMemcpy(dy, y, n * 4, hipMemcpyHostToDevice));
+    HK_HIP(hipMalloc((void**)&dy, yin * 4));
+    HK_HIP(hipMemcpy(dy, y, yin * 4, hipMemcpyHostToDevice));
   }
   launch_debug_math(stream, op, dx, dy, dout, n);
   HK_HIP(hipStreamSynchronize(stream));

@@ -836,12 +836,29 @@ class Engine:
         return {1 << k: r[k] for k in range(4)}
 
     def debug_math(self, op, x, y=None):
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        out = np.empty_like(x)
-        fp = lambda a: a.ctypes.data_as(C.POINTER(F.f32))
-        yy = None if y is None else np.ascontiguousarray(y, dtype=np.float32)
-        self.api.call("debug_math", self.ctx, op, fp(x), None if yy is None else fp(yy), fp(out), x.size)
-        return out
+        """hk_debug_math: one f32 per item (include/hikari_hip_debug.h)."""
+        return debug_math_call(self.api, self.ctx, op, x, y)
+
+
+def debug_math_call(api, ctx, op, x, y=None):
+    """debug_math of `api` (the library's, or the oracle's with ctx None).  The op decides the layout, as in probes.hip: ops 16..19
+    and 35..52 read 16 floats of x per item, ops 46..49 four of y, every other op one of each.  Returns one f32 per item."""
+    op = int(op)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    width = 16 if 16 <= op <= 19 or 35 <= op <= 52 else 1
+    n, rest = divmod(x.size, width)
+    if rest:
+        raise ValueError(f"debug_math op {op} reads {width} floats of x per item, got {x.size}")
+    yy = None if y is None else np.ascontiguousarray(y, dtype=np.float32)
+    ywidth = 4 if 46 <= op <= 49 else 1
+    if ywidth == 4 and yy is None:
+        raise ValueError(f"debug_math op {op} takes its vector in y")
+    if yy is not None and yy.size != ywidth * n:
+        raise ValueError(f"debug_math op {op} reads {ywidth} floats of y per item: {ywidth * n} for {n} items, got {yy.size}")
+    out = np.empty(n, dtype=np.float32)
+    fp = lambda a: a.ctypes.data_as(C.POINTER(F.f32))
+    api.call("debug_math", ctx, op, fp(x), None if yy is None else fp(yy), fp(out), n)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

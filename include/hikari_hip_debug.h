@@ -41,8 +41,19 @@ int hk_measure_hbm(hk_ctx* ctx, size_t bytes_per_array, uint32_t reps, double* c
 int hk_measure_valu(hk_ctx* ctx, uint32_t iters, double ginstr_s[4]);
 
 /* Test hook: evaluate one of the library's device math routines elementwise (op: 0 sin, 1 cos,
- * 2 exp, 3 exp2, 4 log2, 5 pow(x, y), 6 min(x,y), 7 max(x,y), 8 f32->f16->f32, 9 x/y, 10 sqrt).
- * x, y, out are HOST arrays. */
+ * 2 exp, 3 exp2, 4 log2, 5 pow(x, y), 6 min(x,y), 7 max(x,y), 8 f32->f16->f32, 9 x/y, 10 sqrt,
+ * 11 saturate(x), 12 clamp(x, -1, 1), 13 saturate(x*y), 14 / 15 / 20 the unorm16 / snorm8 / unorm8 decode of the integer x;
+ * 21 / 22 the sine / cosine of sincos_, 23 exp_nonpositive_, 24 quotient_by_reciprocal(x, 1.0 / (double)y), 25 the denoiser's
+ * weight exp_nonpositive_(quotient_by_reciprocal(-|x|, 1.0 / (double)y)), 26 pow2_, 27 pow5_, 28 pow16_, 29 pow_quarter_,
+ * 30 f32->f16->f32 of the f32 product x*y, 31 unorm16(x) and 32 snorm8(x) (the code, as a float: exact), 33 f32_to_u32(x) and
+ * 34 f32_to_i32(x) (the 32 result bits, returned AS the bits of the float: read them back with a bit cast)).
+ * x, y, out are HOST arrays of n floats, one result per item.
+ * Ops 16..19 and 35..52 read SIXTEEN floats of x per item (x holds 16 n floats, q = x + 16 i):
+ * 16 / 17 / 18 shading().rgb and 19 env_brdf().r for V = q[0..2], N = q[3..5], L = q[6..8] (each normalised first), base colour
+ * q[9..11], radiance q[12..15] and the perceptual roughness y; 35 dot(q[0..2], q[3..5]), 36 dot(q[0..3], q[4..7]),
+ * 37 / 38 / 39 cross(q[0..2], q[3..5]).xyz, 40 / 41 / 42 normalize(q[0..2]).xyz, 43 / 44 / 45 (mat3 of columns q[0..2], q[3..5],
+ * q[6..8]) * q[9..11] .xyz, 46 / 47 / 48 / 49 (4x4 of columns q[0..3] .. q[12..15]) * v .xyzw where v is FOUR floats of y per
+ * item (y holds 4 n floats and is required), 50 length(q[0..2]), 51 mix(q[0], q[1], q[2]), 52 fract(q[0]). */
 int hk_debug_math(hk_ctx* ctx, uint32_t op, const float* x, const float* y, float* out, size_t n);
 
 /* Measurement hook for the roof of the BVH walks of scenes beyond the LDS copy (round 4): every lane of

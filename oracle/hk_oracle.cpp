@@ -365,17 +365,7 @@ struct Reservoir {
   Sample s;
   float count, lifetime, w, w_sum, w2_sum;
 };
-static inline uint32_t f32_to_u32(float f) {  // WGSL u32(f32): truncation, clamped
-  if (!(f > 0.0f)) return 0u;
-  if (f >= 4294967296.0f) return 0xFFFFFFFFu;
-  return (uint32_t)f;
-}
-static inline int f32_to_i32(float f) {  // WGSL i32(f32): truncation, clamped
-  if (f != f) return 0;
-  if (f >= 2147483648.0f) return 2147483647;
-  if (f <= -2147483648.0f) return (-2147483647 - 1);
-  return (int)f;
-}
+// (f32_to_u32 / f32_to_i32, the saturating WGSL conversions: hk_oracle_math.h)
 
 static Reservoir unpack_reservoir(const PackedReservoir& packed) {  // light.wgsl:77-109
   Reservoir r{};
@@ -2718,7 +2708,10 @@ int orc_reset_stats(orc_ctx* ctx) {
 int orc_debug_math(orc_ctx* ctx, uint32_t op, const float* x, const float* y, float* out, size_t n) {
   (void)ctx;
   for (size_t i = 0; i < n; ++i) {
-    float a = (op >= 16 && op <= 19) ? 0.0f : x[i], b = y ? y[i] : 0.0f, r = 0.0f;
+    const bool wide = (op >= 16 && op <= 19) || (op >= 35 && op <= 52);  // 16 floats of x per item
+    const bool y4 = op >= 46 && op <= 49;                                 // 4 floats of y per item
+    float a = wide ? 0.0f : x[i], b = (y && !y4) ? y[i] : 0.0f, r = 0.0f;
+    const float* q = x + (wide ? 16 * i : 0);
     switch (op) {
       case 0: r = sin_(a); break;
       case 1: r = cos_(a); break;
@@ -2737,8 +2730,49 @@ int orc_debug_math(orc_ctx* ctx, uint32_t op, const float* x, const float* y, fl
       case 14: r = unpack2x16unorm((uint32_t)a).x; break;
       case 15: r = unsnorm8((uint32_t)a); break;
       case 20: r = (float)((uint32_t)a & 0xffu) / 255.0f; break;
+      // 21.. : the contract form of what the device computes with its own shortcuts (sincos_, exp_nonpositive_,
+      // quotient_by_reciprocal) and the rest of hk_oracle_math.h (include/hikari_hip_debug.h lists the codes)
+      case 21: r = sin_(a); break;
+      case 22: r = cos_(a); break;
+      case 23: r = exp_(a); break;
+      case 24: r = a / b; break;
+      case 25: r = exp_((-fabsf(a)) / b); break;
+      case 26: r = pow2_(a); break;
+      case 27: r = pow5_(a); break;
+      case 28: r = pow16_(a); break;
+      case 29: r = pow_quarter_(a); break;
+      case 30: r = f16_to_f32(f32_to_f16(a * b)); break;
+      case 31: r = (float)unorm16(a); break;
+      case 32: r = (float)snorm8(a); break;
+      case 33: r = u2f(f32_to_u32(a)); break;
+      case 34: r = u2f((uint32_t)f32_to_i32(a)); break;
+      case 35: r = dot(V3(q[0], q[1], q[2]), V3(q[3], q[4], q[5])); break;
+      case 36: r = dot(V4(q[0], q[1], q[2], q[3]), V4(q[4], q[5], q[6], q[7])); break;
+      case 37: case 38: case 39: {
+        v3 o = cross(V3(q[0], q[1], q[2]), V3(q[3], q[4], q[5]));
+        r = (op == 38) ? o.y : ((op == 39) ? o.z : o.x);
+        break;
+      }
+      case 40: case 41: case 42: {
+        v3 o = normalize(V3(q[0], q[1], q[2]));
+        r = (op == 41) ? o.y : ((op == 42) ? o.z : o.x);
+        break;
+      }
+      case 43: case 44: case 45: {
+        v3 o = mul(m3{V3(q[0], q[1], q[2]), V3(q[3], q[4], q[5]), V3(q[6], q[7], q[8])}, V3(q[9], q[10], q[11]));
+        r = (op == 44) ? o.y : ((op == 45) ? o.z : o.x);
+        break;
+      }
+      case 46: case 47: case 48: case 49: {
+        if (!y) return HK_E_INVALID;
+        v4 o = mul(load_m4(q), V4(y[4 * i], y[4 * i + 1], y[4 * i + 2], y[4 * i + 3]));
+        r = (op == 46) ? o.x : ((op == 47) ? o.y : ((op == 48) ? o.z : o.w));
+        break;
+      }
+      case 50: r = length(V3(q[0], q[1], q[2])); break;
+      case 51: r = mix(q[0], q[1], q[2]); break;
+      case 52: r = fract(q[0]); break;
       case 16: case 17: case 18: case 19: {
-        const float* q = x + 16 * i;
         HkLights lights{};
         lights.ambient_color[0] = lights.ambient_color[1] = lights.ambient_color[2] = 0.05f;
         Scene sc{};

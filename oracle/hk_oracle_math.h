@@ -9,7 +9,7 @@
 // statement instead of a statistical one, this header FIXES every implementation-defined choice
 // using only operations that IEEE-754 defines exactly (+ - * / sqrt fma floor, integer bit
 // twiddling).  The HIP kernels implement the same contract independently
-// (bevy-hikari_amd/csrc/hk_device_math.hpp); tests/test_math_contract.py compares the two on the
+// (bevy-hikari_amd/csrc/hk_device_math.hpp); tests/test_math_contract*.py compare the two on the
 // GPU bit for bit and compares this file with libm within a few ulp.
 //
 // Contract
@@ -153,9 +153,23 @@ static inline float cos_poly(float r) {
   p = fmaf(p, z, 4.166664568298827e-2f);
   return fmaf(p * z, z, fmaf(-0.5f, z, 1.0f));
 }
+// WGSL u32(f32) / i32(f32): truncation, saturating, NaN -> 0 (what v_cvt_u32_f32 / v_cvt_i32_f32 do on gfx950; a plain C++ cast
+// is undefined out of range and x86 returns INT_MIN for it)
+static inline uint32_t f32_to_u32(float f) {
+  if (!(f > 0.0f)) return 0u;
+  if (f >= 4294967296.0f) return 0xFFFFFFFFu;
+  return (uint32_t)f;
+}
+static inline int f32_to_i32(float f) {
+  if (f != f) return 0;
+  if (f >= 2147483648.0f) return 2147483647;
+  if (f <= -2147483648.0f) return (-2147483647 - 1);
+  return (int)f;
+}
+
 static inline float reduce_pio2(float x, int* q) {
   float kf = floorf(fmaf(x, 0.63661977236758134308f, 0.5f));
-  *q = (int)kf;
+  *q = f32_to_i32(kf);  // saturating like the device's conversion: one quadrant for every f32, |x| > 3.4e9 included
   float r = fmaf(kf, -1.57079637050628662109375f, x);
   r = fmaf(kf, 4.37113882867379e-8f, r);
   return r;

@@ -6,18 +6,15 @@ import numpy as np
 import pytest
 
 from bevy_hikari_amd import _ffi as F
+from bevy_hikari_amd.plugin import debug_math_call
 from oracle_lib import oracle_api
 
 OPS = {"sin": 0, "cos": 1, "exp": 2, "exp2": 3, "log2": 4, "pow": 5, "min": 6, "max": 7, "f16": 8, "div": 9, "sqrt": 10}
 
 
 def oracle_math(op, x, y=None):
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    out = np.empty_like(x)
-    fp = lambda a: a.ctypes.data_as(C.POINTER(F.f32))
-    yy = None if y is None else np.ascontiguousarray(y, dtype=np.float32)
-    oracle_api().call("debug_math", None, OPS[op], fp(x), None if yy is None else fp(yy), fp(out), x.size)
-    return out
+    """orc_debug_math by name (OPS) or by op code; one f32 per item, in the layout Engine.debug_math takes."""
+    return debug_math_call(oracle_api(), None, OPS[op] if isinstance(op, str) else op, x, y)
 
 
 def ulp_diff(a, b):
