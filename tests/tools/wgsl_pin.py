@@ -410,7 +410,53 @@ def run_case(which, size=(24, 16), frames=2, log=None, patch=None, unguarded=Fal
     return pin.results
 
 
+def run_planes(name, render_size=(24, 16), ratio=1.0, frame_number=3, seed=7, log=None):
+    """The post chain on the synthetic planes of tests/post_planes.py: demodulation, four levels x three channels and tone mapping of
+    the reference's shaders, each on the state the oracle has before the dispatch.  Returns the per-dispatch records; what the shaders
+    wrote is in run_planes.recorded."""
+    import post_planes as PP
+
+    p = oracle_plugin()
+    dll = p.engine.api.dll
+    dll.orc_debug_math.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]
+
+    def contract(op, x, y):
+        xi, yi, out = (C.c_float * 1)(float(x)), (C.c_float * 1)(float(y)), (C.c_float * 1)()
+        assert dll.orc_debug_math(None, op, xi, yi, out, 1) == 0
+        return f32(out[0])
+
+    R.bind_contract(contract)
+    scene = hk.load_cornell()
+    p.set_scene(scene)
+    planes = PP.make_planes(name, seed, PP.window_for(render_size, ratio), ratio, 3, frame_number, compact=True)      # a small image that holds every special texel
+    pin = Pinner(p, scene, None, log or (lambda rec: None))
+    pin.settings, pin.patch = planes.settings, None
+    camera = hk.cornell_camera(*planes.window_size)
+    pin.begin(planes.frame, camera.view_uniform(), camera.previous_view_uniform(None), hk.lights_uniform())
+    PP.install(p.engine, planes)
+    p.post_process.run(planes.settings)
+    run_planes.recorded = pin.recorded
+    return pin.results
+
+
+PLANES_FIXTURES = [("nonfinite", (24, 16), 1.0, 3), ("thresholds", (24, 16), 1.5, 2), ("black", (24, 16), 1.0, 2), ("nonfinite", (17, 16), 1.5, 3)]
+
+
+def planes_fixture_path(name, render_size, ratio, frame_number):
+    return os.path.join(ROOT, "tests", "golden", f"wgsl_post_planes_{name}_{render_size[0]}x{render_size[1]}_r{int(ratio * 10)}_f{frame_number}.npz")
+
+
 def main():
+    if "--planes" in sys.argv:          # [--write]: the fixtures tests/test_post_chain_planes*.py replay
+        for case in PLANES_FIXTURES:
+            results = run_planes(*case, log=lambda rec: print(json.dumps(rec), flush=True))
+            bad = [r for r in results if r["mismatch"]]
+            if "--write" in sys.argv:
+                assert not bad
+                np.savez_compressed(planes_fixture_path(*case), **run_planes.recorded)
+                print("wrote", planes_fixture_path(*case), os.path.getsize(planes_fixture_path(*case)), "bytes")
+            print(json.dumps({"planes": case, "dispatches": len(results), "mismatching": len(bad)}))
+        return
     size = (24, 16)
     if "--size" in sys.argv:
         i = sys.argv.index("--size")
