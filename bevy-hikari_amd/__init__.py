@@ -14,6 +14,7 @@ from .plugin import (  # noqa: F401
     HikariSettings,
     HikariUniversalSettings,
     LightNode,
+    OverlayNode,
     PostProcessNode,
     PrepassNode,
     SceneBuilder,

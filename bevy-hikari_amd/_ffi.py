@@ -57,6 +57,8 @@ UPSCALE_FSR1, UPSCALE_SMAA_TU4X = 0, 1
 NO_TEXTURE = 0xFFFFFFFF
 ADDRESS_CLAMP_TO_EDGE, ADDRESS_REPEAT, ADDRESS_MIRROR_REPEAT = 0, 1, 2
 TIMING_SLOTS = 24
+FORMAT_RGBA16F, FORMAT_RGBA32F, FORMAT_RGBA8_UNORM_SRGB, FORMAT_BGRA8_UNORM_SRGB = range(4)  # HkPresentTarget.format
+PRESENT_HDR, PRESENT_CLEAR = 1, 2
 
 f32, u32, u64 = C.c_float, C.c_uint32, C.c_uint64
 
@@ -135,6 +137,10 @@ class HkSettings(C.Structure):
 class HkImageDesc(C.Structure):
     _fields_ = [("rgba8", C.c_void_p), ("width", u32), ("height", u32), ("is_srgb", u32), ("address_u", u32), ("address_v", u32),
                 ("filter_linear", u32)]
+
+
+class HkPresentTarget(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("width", u32), ("height", u32), ("pitch_bytes", u32), ("format", u32), ("flags", u32), ("clear", f32 * 4)]
 
 
 class HkHaloOp(C.Structure):
@@ -256,6 +262,7 @@ _PRODUCT_ONLY = {
     "set_mesh_skin": [_vp, P(HkMeshIndex), u32, P(f32), P(f32), P(C.c_uint16), P(f32)],
     "skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],
     "rebuild_mesh_tree": [_vp, P(HkMeshIndex), u32],
+    "present": [_vp, P(HkSettings), u32, P(HkPresentTarget), u32, u32],
     "band_rows": [u32, u32, u32, P(u32), P(u32)],
     "balanced_band_bounds": [P(u32), u32, u32, u32, u32, u32, f32, P(u32)],
     "balance_bands": [_vp, u32, P(u32), u32],

@@ -1621,6 +1621,45 @@ int hk_frame_wait(hk_ctx* c) {
   return HK_OK;
 }
 
+// The reference's OverlayNode (overlay.rs:311-395): the final image of the frame last begun into the host's target.
+// Ordering, without a host wait.  The planes the kernel reads are written on the post stream (tone mapping of a pipelined frame) or on
+// the main stream (everything else), and written AGAIN by the next frame of the same parity (tone-mapped, TAA output, albedo) or by
+// the next frame (the single upscale planes, on the main stream).
+//   - A pipelined frame's tone-mapped image: the present goes onto the post stream, behind the tone mapping, and post_done[parity] is
+//     recorded again behind it - whoever writes this parity's planes next (join_post_parity, the primary rays on their own stream)
+//     or looks at a buffer (join_all) waits for that event already, and the main stream goes on to the next frame beside it.
+//   - Otherwise the main stream joins every other stream (join_all: side, post, a gather on the communicator's) and takes the
+//     present; every later frame's streams fork from the main stream behind it (join_all cleared post_pending, so no primary rays
+//     start on their own stream before this frame's parity has been through the main stream again).
+int hk_present(hk_ctx* c, const HkSettings* st, uint32_t frame_flags, const HkPresentTarget* t, uint32_t row_begin, uint32_t row_end) {
+  HK_REQUIRE(c && st && t, HK_E_INVALID, "NULL argument");
+  HK_REQUIRE(t->format <= HK_FORMAT_BGRA8_UNORM_SRGB, HK_E_INVALID, "unknown target format %u", t->format);
+  HK_REQUIRE(!(t->flags & ~(HK_PRESENT_HDR | HK_PRESENT_CLEAR)), HK_E_INVALID, "unknown present flag 0x%x", t->flags);
+  const uint32_t pixel = t->format == HK_FORMAT_RGBA16F ? 8u : (t->format == HK_FORMAT_RGBA32F ? 16u : 4u);
+  HK_REQUIRE(t->ptr && ((uintptr_t)t->ptr % pixel) == 0, HK_E_INVALID, "the target is NULL or not aligned to its pixel size (%u bytes)", pixel);
+  HK_REQUIRE(t->width > 0 && t->height > 0 && t->width <= 65536u && t->height <= 65536u, HK_E_INVALID, "bad target size %u x %u", t->width, t->height);
+  HK_REQUIRE((uint64_t)t->pitch_bytes >= (uint64_t)t->width * pixel && (t->pitch_bytes % pixel) == 0, HK_E_INVALID,
+             "pitch_bytes %u: need a multiple of the pixel size (%u) and at least %llu", t->pitch_bytes, pixel, (unsigned long long)t->width * pixel);
+  HK_REQUIRE(row_begin <= row_end && row_end <= t->height, HK_E_INVALID, "rows [%u, %u) do not fit a target of %u rows", row_begin, row_end, t->height);
+  HK_REQUIRE(st->taa <= HK_TAA_NONE && st->upscale_kind <= HK_UPSCALE_SMAA_TU4X, HK_E_INVALID, "bad taa / upscale_kind in settings");
+  HK_REQUIRE(c->band_count == 1, HK_E_UNSUPPORTED, "hk_present on one band of %u: a band holds its own rows of the albedo only", c->band_count);
+  int rc = ready(c);   // (no frame begun yet: HK_E_NOT_READY)
+  if (rc) return rc;
+  const bool eight = pixel == 4u;
+  HK_REQUIRE(!eight || (t->flags & HK_PRESENT_CLEAR) || c->scene.srgb_lut, HK_E_NOT_READY, "no scene uploaded (the sRGB table lives with the material textures)");
+  const uint32_t final = hk_final_buffer(st, frame_flags);
+  int sw = c->RW, sh = c->RH;   // (buffer_dims under THESE settings: c->upscale_kind is whatever the last stage left)
+  if (final == HK_BUF_UPSCALE_SHARPENED) { sw = c->W; sh = c->H; }
+  else if (final != HK_BUF_TONE_MAPPED && st->upscale_kind == HK_UPSCALE_SMAA_TU4X) { sw = c->UW; sh = c->UH; }
+  const uint32_t parity = c->mapped_parity & 1u;
+  const bool on_post = final == HK_BUF_TONE_MAPPED && c->post_stream && c->post_pending[parity] && !c->comm;
+  if (!on_post && (rc = join_all(c))) return rc;
+  launch_present(on_post ? c->post_stream : c->stream, c->buf[final], sw, sh, c->buf[HK_BUF_ALBEDO], c->W, c->H, c->scene.srgb_lut, *t, (int)row_begin, (int)row_end);
+  HK_HIP(hipGetLastError());
+  if (on_post) HK_HIP(hipEventRecord(c->post_done[parity], c->post_stream));
+  return HK_OK;
+}
+
 int hk_buffer_info(hk_ctx* c, uint32_t buffer, uint32_t* w, uint32_t* h, uint32_t* bpp) {
   HK_REQUIRE(c && buffer < HK_BUF_COUNT && buffer_bpp(buffer), HK_E_INVALID, "bad buffer id");
   int bw, bh;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/hikari_hip.h"  // HkPresentTarget
 #include "hk_device.hpp"
 
 namespace hkd {
@@ -364,6 +365,9 @@ void launch_smaa_tu4x_extrapolate(hipStream_t st, void* output, int out_w, int o
 void launch_taa_jasmine(hipStream_t st, const AaBuffers& b, float blend, const float clear_color[4], int y0, int y1);
 void launch_fsr_easu(hipStream_t st, const void* input, int in_w, int in_h, void* output, int out_w, int out_h, int y0, int y1);
 void launch_fsr_rcas(hipStream_t st, const void* input, void* output, int w, int h, float sharpness, int y0, int y1);
+// hk_present: rows [y0, y1) of the host's target from the final image and the albedo (rgba16f planes of their own sizes)
+void launch_present(hipStream_t st, const void* src, int src_w, int src_h, const void* albedo, int albedo_w, int albedo_h, const float* srgb_lut,
+                    const HkPresentTarget& t, int y0, int y1);
 // apply the parked scatter stores of pixels [p0, p1); [own0, own1) = the pixels this context dispatched itself (their winners are
 // in), empty = all of them
 void launch_resolve_scatter(hipStream_t st, const hkd::LightTargets& t, int p0, int p1, int own0, int own1);

@@ -504,6 +504,64 @@ __global__ __launch_bounds__(256) void k_fsr_rcas(const uint2* __restrict__ inpu
   output[px.x + w * px.y] = pack_f16x4(F4(pixR, pixG, pixB, 1.0f));
 }
 
+// ------------------------------------------------------------------ present (OverlayNode, overlay.rs:311-395, overlay.wgsl:28-48)
+// One thread per TARGET pixel, 64 x 1 rows: a wave reads 512 B of the source row and writes 256 B (8-bit), 512 B (rgba16f) or 1 KiB
+// (rgba32f) of the target row, one vector store per lane.  A plane of the target's size is read at the texel (what an exact sampler
+// returns at a texel centre; the footprint arithmetic can land 1 ulp off and blend a neighbour in), any other plane through
+// sample_linear.  The albedo (the fallback for a NaN texel, overlay.wgsl any_is_nan_vec4) is read by the lanes that need it only.
+struct PresentArgs {
+  Plane16 src, albedo;
+  uint8_t* target;            // device memory of the host
+  const float* srgb_lut;      // the material textures' sRGB -> linear table (DScene::srgb_lut); read by the 8-bit formats without CLEAR
+  int w, h;
+  uint32_t pitch;             // bytes
+  uint32_t flags;             // HK_PRESENT_*
+  float4 clear;
+};
+HKD f4 present_sample(const Plane16& t, int x, int y, f2 uv, bool exact) { return exact ? texel(t, x, y) : sample_linear(t, uv); }
+HKD float srgb_encode(float v) { return v <= 0.0031308f ? 12.92f * v : 1.055f * pow_(v, 1.0f / 2.4f) - 0.055f; }
+HKD uint32_t unorm8_code(float v) { return (uint32_t)floorf(0.5f + 255.0f * clamp_(v, 0.0f, 1.0f)); }
+template <uint32_t FORMAT>
+__global__ void __launch_bounds__(256) k_present(PresentArgs a, int row_begin, int row_end) {
+  const Pixel px = pixel_of_thread_rows<64, true>(a.w, row_begin, row_end);
+  if (!px.valid) return;
+  const int x = px.x, y = px.y;
+  const f2 uv = F2(((float)x + 0.5f) / (float)a.w, ((float)y + 0.5f) / (float)a.h);
+  f4 c = present_sample(a.src, x, y, uv, a.src.w == a.w && a.src.h == a.h);
+  if (c.x != c.x || c.y != c.y || c.z != c.z || c.w != c.w) c = present_sample(a.albedo, x, y, uv, a.albedo.w == a.w && a.albedo.h == a.h);
+  if (a.flags & HK_PRESENT_HDR) {  // overlay.wgsl inverse_reintard_luminance + bevy_core_pipeline 0.9.1 tonemapping_change_luminance
+    const float l = luminance(rgb(c));
+    const float l_old = clamp_(l, 0.0005f, 0.995f);
+    const float l_new = l_old / (1.0f - l_old);
+    const float s = l_new / l;
+    c = F4(c.x * s, c.y * s, c.z * s, c.w);
+  }
+  uint8_t* at = a.target + (size_t)y * a.pitch;
+  constexpr bool EIGHT = FORMAT == HK_FORMAT_RGBA8_UNORM_SRGB || FORMAT == HK_FORMAT_BGRA8_UNORM_SRGB, BGR = FORMAT == HK_FORMAT_BGRA8_UNORM_SRGB;
+  f4 d = F4(a.clear);
+  if (!(a.flags & HK_PRESENT_CLEAR)) {
+    if (FORMAT == HK_FORMAT_RGBA16F) {
+      d = unpack_f16x4(reinterpret_cast<const uint2*>(at)[x]);
+    } else if (FORMAT == HK_FORMAT_RGBA32F) {
+      d = F4(reinterpret_cast<const float4*>(at)[x]);
+    } else {
+      const uint32_t t = reinterpret_cast<const uint32_t*>(at)[x];
+      const uint32_t b0 = t & 0xffu, b1 = (t >> 8) & 0xffu, b2 = (t >> 16) & 0xffu;
+      d = F4(a.srgb_lut[BGR ? b2 : b0], a.srgb_lut[b1], a.srgb_lut[BGR ? b0 : b2], unorm8(t >> 24));
+    }
+  }
+  const float k = 1.0f - c.w;  // BlendState::ALPHA_BLENDING: src * src.a + dst * (1 - src.a); alpha: src.a + dst.a * (1 - src.a)
+  const f4 o = F4(c.x * c.w + d.x * k, c.y * c.w + d.y * k, c.z * c.w + d.z * k, c.w + d.w * k);
+  if (FORMAT == HK_FORMAT_RGBA16F) {
+    reinterpret_cast<uint2*>(at)[x] = pack_f16x4(o);
+  } else if (FORMAT == HK_FORMAT_RGBA32F) {
+    reinterpret_cast<float4*>(at)[x] = to_float4(o);
+  } else if (EIGHT) {
+    const uint32_t r = unorm8_code(srgb_encode(o.x)), g = unorm8_code(srgb_encode(o.y)), b = unorm8_code(srgb_encode(o.z));
+    reinterpret_cast<uint32_t*>(at)[x] = (BGR ? b : r) | (g << 8) | ((BGR ? r : b) << 16) | (unorm8_code(o.w) << 24);
+  }
+}
+
 }  // namespace hkd
 
 namespace hk {
@@ -569,6 +627,28 @@ void launch_fsr_easu(hipStream_t st, const void* input, int in_w, int in_h, void
 void launch_fsr_rcas(hipStream_t st, const void* input, void* output, int w, int h, float sharpness, int y0, int y1) {
   if (y1 <= y0) return;
   hipLaunchKernelGGL(k_fsr_rcas, HK_FSR_GRID(w, y1 - y0), dim3(256), 0, st, (const uint2*)input, (uint2*)output, w, h, sharpness, y0, y1);
+}
+
+void launch_present(hipStream_t st, const void* src, int src_w, int src_h, const void* albedo, int albedo_w, int albedo_h, const float* srgb_lut,
+                    const HkPresentTarget& t, int y0, int y1) {
+  if (y1 <= y0) return;
+  PresentArgs a;
+  a.src = Plane16{(const uint2*)src, src_w, src_h};
+  a.albedo = Plane16{(const uint2*)albedo, albedo_w, albedo_h};
+  a.target = (uint8_t*)t.ptr;
+  a.srgb_lut = srgb_lut;
+  a.w = (int)t.width;
+  a.h = (int)t.height;
+  a.pitch = t.pitch_bytes;
+  a.flags = t.flags;
+  a.clear = make_float4(t.clear[0], t.clear[1], t.clear[2], t.clear[3]);
+  const dim3 grid = grid_for_rows(64, a.w, y1 - y0);
+  switch (t.format) {
+    case HK_FORMAT_RGBA16F: hipLaunchKernelGGL(k_present<HK_FORMAT_RGBA16F>, grid, dim3(256), 0, st, a, y0, y1); break;
+    case HK_FORMAT_RGBA32F: hipLaunchKernelGGL(k_present<HK_FORMAT_RGBA32F>, grid, dim3(256), 0, st, a, y0, y1); break;
+    case HK_FORMAT_RGBA8_UNORM_SRGB: hipLaunchKernelGGL(k_present<HK_FORMAT_RGBA8_UNORM_SRGB>, grid, dim3(256), 0, st, a, y0, y1); break;
+    default: hipLaunchKernelGGL(k_present<HK_FORMAT_BGRA8_UNORM_SRGB>, grid, dim3(256), 0, st, a, y0, y1); break;
+  }
 }
 
 }  // namespace hk

@@ -7,6 +7,7 @@ call order follow cryscan/bevy-hikari v0.3.15:
   HikariSettings / Taa / Upscale / HikariUniversalSettings   src/lib.rs:373-513
   graph.NAME + node names                                     src/lib.rs:43-51
   PrepassNode / LightNode / PostProcessNode  .run()           src/prepass.rs:769, src/light.rs:590, src/post_process.rs:1140
+  OverlayNode .run() / Engine.present                         src/overlay.rs:311-395
   FrameCounter                                                src/view.rs:75-103
   HikariPlugin                                                src/lib.rs:95-370
 
@@ -427,6 +428,13 @@ def load_noise():
 _BUF_DTYPES = {16: (np.float32, 4), 4: (np.uint32, 1), 8: (np.uint16, 4), 64: (np.uint32, 16)}
 
 
+def _present_formats():
+    import torch
+
+    return {"rgba16f": (F.FORMAT_RGBA16F, torch.float16), "rgba32f": (F.FORMAT_RGBA32F, torch.float32),
+            "rgba8-srgb": (F.FORMAT_RGBA8_UNORM_SRGB, torch.uint8), "bgra8-srgb": (F.FORMAT_BGRA8_UNORM_SRGB, torch.uint8)}
+
+
 class Engine:
     """One context of the C ABI (`hk_ctx`).  `api` defaults to the product library."""
 
@@ -435,6 +443,7 @@ class Engine:
         self.ctx = C.c_void_p()
         self.api.call("create", device, flags | F.DEFAULT_CTX_FLAGS, C.byref(self.ctx))
         self.width = self.height = 0
+        self.device = device
         self.owned = True
         self.generation = 0  # bumped by resize(): holders of device pointers / views compare it (distributed.BandRenderer)
 
@@ -442,7 +451,7 @@ class Engine:
     def borrowed(cls, api, ctx):
         """An Engine over a context somebody else owns (hk_multi_context): never destroyed from here."""
         e = cls.__new__(cls)
-        e.api, e.ctx, e.owned, e.generation, e.width, e.height = api, ctx, False, 0, 0, 0
+        e.api, e.ctx, e.owned, e.generation, e.width, e.height, e.device = api, ctx, False, 0, 0, 0, None
         return e
 
     def close(self):
@@ -706,6 +715,48 @@ class Engine:
     def allocated_bytes(self, buf):
         return self.device_ptr(buf)[1]
 
+    # -- present (the reference's OverlayNode)
+    def present_into(self, settings_c, frame_flags, device_ptr, width, height, pitch_bytes, fmt, flags=0, clear=None, rows=None):
+        """hk_present: rows of a host-owned target in device memory.  Asynchronous, like frame_render; wait() returns once it is written."""
+        t = F.HkPresentTarget(C.c_void_p(device_ptr), width, height, pitch_bytes, fmt, flags)
+        if clear is not None:
+            t.clear[:] = [float(v) for v in clear]
+        y0, y1 = (0, height) if rows is None else rows
+        self.api.call("present", self.ctx, C.byref(settings_c), frame_flags, C.byref(t), y0, y1)
+
+    def present(self, settings, *, antialias, format="rgba16f", hdr=False, clear=None, out=None, rows=None, wait=True):
+        """The frame last rendered as the camera's view target receives it (OverlayNode, overlay.rs:311-395): NaN texels replaced by
+        the albedo, the tone map undone for an HDR target (`hdr`), alpha-blended over `clear` (four linear floats) or over what `out`
+        holds (`clear=None`), in the target's format - "rgba16f", "rgba32f", "rgba8-srgb" or "bgra8-srgb".  Returns a torch tensor
+        [H][W][4] (float16 / float32 / uint8) on the context's device: `out`, or a new one of the final image's size (zeros
+        under clear=None).  The kernel writes `out.data_ptr()`; nothing passes through the host.  `rows` = (begin, end) presents
+        those rows only.  A new tensor has the size of the final image of the frame last rendered with these settings.
+        Synchronisation: torch and the context enqueue on different streams and share no event, so this call first waits on the
+        host for torch's current stream (whatever torch still has in flight on `out`), and by default (wait=True) for the present
+        itself, so that the tensor returned is safe to read from torch.  wait=False leaves the present enqueued, ordered against
+        the context's later frames inside the library (hk_present): call wait() before torch touches the tensor."""
+        import torch
+
+        fmt, dtype = _present_formats()[format]
+        sc = settings.to_c() if hasattr(settings, "to_c") else settings
+        frame_flags = F.FRAME_ANTIALIAS if antialias else 0
+        if out is None:
+            if getattr(self, "device", None) is None:
+                raise ValueError("present() on a borrowed context needs `out`")
+            w, h, _ = self.buffer_info(self.api.final_buffer(sc, frame_flags))   # (as the frame last rendered left it: render with THESE settings)
+            out = (torch.zeros if clear is None else torch.empty)((h, w, 4), dtype=dtype, device=torch.device("cuda", self.device))
+        device = out.device
+        if getattr(self, "device", None) is not None and device.type == "cuda" and device.index != self.device:
+            raise ValueError(f"present(): `out` lives on {device}, the context on cuda:{self.device}")
+        if out.dtype != dtype or out.dim() != 3 or out.shape[2] != 4 or out.stride(2) != 1 or out.stride(1) != 4 or device.type != "cuda":
+            raise ValueError(f"present(format={format!r}) needs a {dtype} tensor [H][W][4] with contiguous pixels in device memory")
+        torch.cuda.current_stream(device).synchronize()      # (what torch still has in flight on `out` comes first)
+        flags = (F.PRESENT_HDR if hdr else 0) | (F.PRESENT_CLEAR if clear is not None else 0)
+        self.present_into(sc, frame_flags, out.data_ptr(), out.shape[1], out.shape[0], out.stride(0) * out.element_size(), fmt, flags, clear, rows)
+        if wait:
+            self.wait()
+        return out
+
     # -- halo exchange inside the library (one process per GPU; bevy-hikari_amd/distributed.py does the rendezvous)
     def comm_available(self):
         """hk_comm_available as (ok, reason): never raises, so that every rank reaches the agreement step."""
@@ -933,6 +984,11 @@ class PostProcessNode(_Node):  # post_process.rs:1107-1312
             e.pass_run(F.PASS_FSR_RCAS)
 
 
+class OverlayNode(_Node):  # overlay.rs:311-395
+    def run(self, settings: HikariSettings, *, antialias, **kwargs):
+        return self.engine.present(settings, antialias=antialias, **kwargs)
+
+
 class HikariPlugin:
     """App::add_plugin(HikariPlugin): owns the context, uploads the noise tiles at start-up
     (lib.rs:189-219) and renders one camera with the `hikari` sub-graph order
@@ -943,6 +999,7 @@ class HikariPlugin:
         self.engine = Engine(api=api, device=device, flags=flags)
         self.engine.upload_noise()
         self.prepass, self.light, self.post_process = PrepassNode(self.engine), LightNode(self.engine), PostProcessNode(self.engine)
+        self.overlay = OverlayNode(self.engine)
         self.counter = FrameCounter(0)
         self._size = None
         self._previous_camera = None
@@ -975,6 +1032,10 @@ class HikariPlugin:
             self.engine.frame_render(frame, view, pview, lights, settings.to_c(), F.FRAME_ANTIALIAS if antialias else 0)
         self._previous_camera = camera
         return n
+
+    def present(self, settings: HikariSettings, *, antialias, **kwargs):
+        """OverlayNode::run: the frame last rendered into a view target in device memory (Engine.present)."""
+        return self.overlay.run(settings, antialias=antialias, **kwargs)
 
     def final_image(self, settings: HikariSettings):
         """What OverlayNode samples (overlay.rs:226-231), as f32 [H][W][4]."""

@@ -1,9 +1,11 @@
 // examples/cornell.cpp - the C++ twin of the reference's examples/cornell.rs (setup(): spawn
 // models/cornell.glb, camera at (0,1,4) looking at (0,1,0), HikariSettings::default()), driving
 // libhikari_hip.so through the C++ host mirror include/hikari.hpp.  Headless: renders N frames and
-// writes the tone-mapped image as a PPM and/or the raw rgba16f words.
+// writes the tone-mapped image as a PPM and/or the raw rgba16f words.  --present writes what the overlay hands the view target instead:
+// the frame presented (hk_present) into a bgra8-sRGB image in device memory, as bytes.
 //
 //   cornell [--size W H] [--frames N] [--bounces B] [--ratio R | --fsr R SHARPNESS] [--by-nodes] [--antialias] [--ppm out.ppm] [--raw out.bin] [--describe]
+//           [--present out.bgra]            OverlayNode: the last frame presented over its clear colour into a bgra8-sRGB target (W x H x 4 bytes)
 //           [--animate [--rebuild-at F]]   the boxes drift every frame; the poses go to the GPU, which redoes the instance records and refits
 //                                          both trees (hk_refit_scene_instances); at frame F the trees are rebuilt on the device (LBVH)
 //           [--gpus N [--devices a,b,..]]   band-sharded over N GPUs from this one process (hk_multi_*); --devices may repeat an id
@@ -16,6 +18,8 @@
 #include <iostream>
 #include <string>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>  // --present: the view target is device memory the HOST owns (hipMalloc / hipMemcpy / hipFree)
 
 #include "hikari.hpp"
 
@@ -87,7 +91,7 @@ int main(int argc, char** argv) {
   std::vector<int> devices;
   bool balance = false;  // --balance: split the bands by cost on the first frame (HK_FRAME_BALANCE_BANDS)
   bool gather = false;   // --gather: band 0's device collects the finished image every frame (HK_FRAME_GATHER); --raw then reads that one context
-  std::string ppm, raw, assets = "bevy-hikari_amd/assets";
+  std::string ppm, raw, present, assets = "bevy-hikari_amd/assets";
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     if (a == "--size" && i + 2 < argc) { w = (uint32_t)atoi(argv[++i]); h = (uint32_t)atoi(argv[++i]); }
@@ -99,6 +103,7 @@ int main(int argc, char** argv) {
     else if (a == "--antialias") antialias = true;  // SMAA Tu4x / TAA / FSR1 as the settings say; output = what the overlay presents
     else if (a == "--ppm" && i + 1 < argc) ppm = argv[++i];
     else if (a == "--raw" && i + 1 < argc) raw = argv[++i];
+    else if (a == "--present" && i + 1 < argc) present = argv[++i];
     else if (a == "--assets" && i + 1 < argc) assets = argv[++i];
     else if (a == "--describe") describe = true;
     else if (a == "--animate") animate = true;
@@ -200,6 +205,22 @@ int main(int argc, char** argv) {
           v = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
           f.put((char)(unsigned char)(std::pow(v, 1.0f / 2.2f) * 255.0f + 0.5f));
         }
+    }
+    if (!present.empty()) {  // OverlayNode::run into bevy's default view target format, cleared to the camera's clear colour
+      HkPresentTarget t{};
+      t.width = rw; t.height = rh; t.pitch_bytes = rw * 4u;
+      t.format = HK_FORMAT_BGRA8_UNORM_SRGB;
+      t.flags = HK_PRESENT_CLEAR;
+      const HkSettings sc = settings.to_c();
+      std::memcpy(t.clear, sc.clear_color, sizeof(t.clear));
+      std::vector<uint8_t> bytes((size_t)rw * rh * 4u);
+      if (hipMalloc(&t.ptr, bytes.size()) != hipSuccess) { std::fprintf(stderr, "hipMalloc failed\n"); return 1; }
+      plugin.present(settings, antialias, t);
+      plugin.wait();
+      const hipError_t rc = hipMemcpy(bytes.data(), t.ptr, bytes.size(), hipMemcpyDeviceToHost);
+      (void)hipFree(t.ptr);
+      if (rc != hipSuccess) { std::fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+      std::ofstream(present, std::ios::binary).write((const char*)bytes.data(), (std::streamsize)bytes.size());
     }
     std::printf("rendered %zu frames at %ux%u (output size %ux%u)\n", frames, w, h, rw, rh);
   } catch (const Error& e) {

@@ -328,13 +328,24 @@ struct PostProcessNode {  // post_process.rs:1107-1312
   }
 };
 
+struct OverlayNode {  // overlay.rs:311-395
+  Context& ctx;
+  // the frame last rendered into rows [row_begin, row_end) of the host's view target in device memory (hk_present): asynchronous,
+  // ordered against the frames around it inside the library; hk_frame_wait returns once the target is written
+  void run(const HikariSettings& s, bool antialias, const HkPresentTarget& target, uint32_t row_begin, uint32_t row_end) {
+    const HkSettings sc = s.to_c();
+    check(hk_present(ctx.get(), &sc, antialias ? HK_FRAME_ANTIALIAS : 0u, &target, row_begin, row_end), "hk_present");
+  }
+  void run(const HikariSettings& s, bool antialias, const HkPresentTarget& target) { run(s, antialias, target, 0u, target.height); }
+};
+
 // App::add_plugin(HikariPlugin): owns the context, uploads the noise tiles at start-up (lib.rs:189-219)
 // and renders one camera with the "hikari" sub-graph order PREPASS -> LIGHT -> POST_PROCESS.
 class HikariPlugin {
  public:
   HikariUniversalSettings universal_settings;
   HikariPlugin(const std::vector<uint8_t>& noise_rgba8_16x64x64, int device = 0, uint32_t flags = 0)
-      : ctx_(device, flags), prepass_{ctx_}, light_{ctx_}, post_process_{ctx_} {
+      : ctx_(device, flags), prepass_{ctx_}, light_{ctx_}, post_process_{ctx_}, overlay_{ctx_} {
     check(hk_upload_noise(ctx_.get(), noise_rgba8_16x64x64.data(), noise_rgba8_16x64x64.size()), "hk_upload_noise");
   }
   Context& context() { return ctx_; }
@@ -380,6 +391,8 @@ class HikariPlugin {
     return n;
   }
   void wait() { check(hk_frame_wait(ctx_.get()), "hk_frame_wait"); }
+  // OverlayNode::run: the frame last rendered into the host's view target (device memory)
+  void present(const HikariSettings& settings, bool antialias, const HkPresentTarget& target) { overlay_.run(settings, antialias, target); }
   // the image OverlayNode presents (overlay.rs:226-231)
   static uint32_t final_buffer(const HikariSettings& s, bool antialias) {
     if (!antialias) return HK_BUF_TONE_MAPPED;
@@ -392,6 +405,7 @@ class HikariPlugin {
   PrepassNode prepass_;
   LightNode light_;
   PostProcessNode post_process_;
+  OverlayNode overlay_;
   FrameCounter counter_;
   uint32_t width_ = 0, height_ = 0;
   float ratio_ = 0.0f;

@@ -679,6 +679,43 @@ int hk_frame_render(hk_ctx* ctx, const HkFrame* frame, const HkView* view, const
                     const HkLights* lights, const HkSettings* settings, uint32_t flags);
 int hk_frame_wait(hk_ctx* ctx);
 
+/* ------------------------------------------------------------------ present (the reference's OverlayNode, overlay.rs:311-395) */
+/* The one step between the internal rgba16f image and what the camera's view target receives (overlay.wgsl:28-48).  Per target
+ * pixel, in f32 under the numeric contract:
+ *   c   = the final image (hk_final_buffer(settings, frame_flags)) at the pixel: the texel itself when the plane has the target's
+ *         size, otherwise the bilinear clamp-to-edge sample at uv = ((x + 0.5) / width, (y + 0.5) / height)
+ *   c   = the albedo of the frame last rendered, sampled the same way, where any of c's four components is NaN
+ *   HK_PRESENT_HDR: l = dot(c.rgb, (0.2126, 0.7152, 0.0722)); l' = clamp(l, 0.0005, 0.995); c.rgb *= (l' / (1 - l')) / l
+ *         (inverse_reintard_luminance; a black texel gives 0 * inf = NaN, as in the reference)
+ *   d   = clear (HK_PRESENT_CLEAR) or the target's current content decoded to linear (overlay.rs:365-370)
+ *   out = (c.rgb * c.a + d.rgb * (1 - c.a), c.a + d.a * (1 - c.a))          BlendState::ALPHA_BLENDING, overlay.rs:133
+ * encoded to the target's format.  The 8-bit formats encode colour with the sRGB curve and every channel as
+ * floor(0.5 + 255 * clamp(v, 0, 1)) (a NaN becomes code 0) and decode colour with the material textures' sRGB table. */
+#define HK_FORMAT_RGBA16F 0u
+#define HK_FORMAT_RGBA32F 1u
+#define HK_FORMAT_RGBA8_UNORM_SRGB 2u
+#define HK_FORMAT_BGRA8_UNORM_SRGB 3u /* bevy's TextureFormat::bevy_default() */
+#define HK_PRESENT_HDR 1u   /* the view target is HDR: undo the Reinhard-luminance tone map */
+#define HK_PRESENT_CLEAR 2u /* blend over `clear` instead of the target's content */
+typedef struct HkPresentTarget {
+  void* ptr;            /* device memory the host owns (a torch tensor, an imported swapchain image), aligned to the pixel size */
+  uint32_t width, height;
+  uint32_t pitch_bytes; /* >= width * bytes per pixel, a multiple of the pixel size */
+  uint32_t format;      /* HK_FORMAT_* */
+  uint32_t flags;       /* HK_PRESENT_HDR | HK_PRESENT_CLEAR */
+  float clear[4];       /* linear rgba, read under HK_PRESENT_CLEAR */
+} HkPresentTarget;
+/* Rows [row_begin, row_end) of the target, asynchronously like hk_frame_render: the kernel runs behind everything that writes the
+ * final image and the albedo of the frame last begun (the post stream and a pending gather included), and the kernels of the frames
+ * that follow wait for it before they write a plane it reads - through the context's events, never through a host wait.
+ * hk_frame_wait returns once the target is written.  Refused with nothing written: a NULL or misaligned target or pitch, an unknown
+ * format or flag, row_begin > row_end or row_end > height (HK_E_INVALID); no hk_frame_begin yet (HK_E_NOT_READY); a context that is
+ * one band of several (HK_E_UNSUPPORTED: a band holds its own rows of the albedo only).
+ * The target must not overlap any of the context's own planes (hk_device_ptr): the kernel reads the final image and the albedo as
+ * memory nothing else writes while it runs. */
+int hk_present(hk_ctx* ctx, const HkSettings* settings, uint32_t frame_flags, const HkPresentTarget* target, uint32_t row_begin,
+               uint32_t row_end);
+
 /* ------------------------------------------------------------------ band sharding (multi-GPU) */
 /* Restrict this context to band `band_index` of `band_count` horizontal bands of the render image
  * (bands are contiguous row ranges, remainder rows spread over the first bands). */

@@ -405,3 +405,22 @@ pub fn final_image(context: &HipContext, settings: &HikariSettings) -> Result<(*
     check(unsafe { hk::hk_device_ptr(context.ctx, buffer, &mut pointer, &mut bytes) })?;
     Ok((pointer, bytes))
 }
+
+/// What `OverlayNode::run` does with that image (overlay.rs:311-395), on the device: the frame last rendered into the view target the
+/// host imported (`target`: device memory of `width` x `height` pixels in bevy's default `Bgra8UnormSrgb`, or `Rgba16Float` for an
+/// HDR view), NaN texels replaced by the albedo, alpha-blended over `clear` or over what the target holds (`LoadOp::Load`).
+/// Asynchronous like the frame itself; ordered against the frames around it inside the library.
+pub fn present(context: &HipContext, settings: &HikariSettings, target: *mut std::ffi::c_void, width: u32, height: u32, hdr: bool, clear: Option<[f32; 4]>) -> Result<(), HipError> {
+    let hk_settings = settings_to_hk(settings);
+    let pixel_bytes = if hdr { 8 } else { 4 };
+    let present_target = hk::HkPresentTarget {
+        ptr: target,
+        width: width,
+        height: height,
+        pitch_bytes: width * pixel_bytes,
+        format: if hdr { hk::HK_FORMAT_RGBA16F } else { hk::HK_FORMAT_BGRA8_UNORM_SRGB },
+        flags: (if hdr { hk::HK_PRESENT_HDR } else { 0 }) | (if clear.is_some() { hk::HK_PRESENT_CLEAR } else { 0 }),
+        clear: clear.unwrap_or([0.0; 4]),
+    };
+    check(unsafe { hk::hk_present(context.ctx, &hk_settings, hk::HK_FRAME_ANTIALIAS, &present_target, 0, height) })
+}
