@@ -10,6 +10,7 @@ from .plugin import (  # noqa: F401
     Camera,
     Engine,
     FrameCounter,
+    HIT_DTYPE,
     HikariPlugin,
     HikariSettings,
     HikariUniversalSettings,
@@ -17,6 +18,7 @@ from .plugin import (  # noqa: F401
     OverlayNode,
     PostProcessNode,
     PrepassNode,
+    RAY_DTYPE,
     SceneBuilder,
     SceneData,
     Taa,
@@ -28,6 +30,7 @@ from .plugin import (  # noqa: F401
     load_cornell,
     load_noise,
     look_at_transform,
+    make_rays,
     standard_material,
 )
 

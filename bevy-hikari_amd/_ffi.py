@@ -59,6 +59,9 @@ ADDRESS_CLAMP_TO_EDGE, ADDRESS_REPEAT, ADDRESS_MIRROR_REPEAT = 0, 1, 2
 TIMING_SLOTS = 24
 FORMAT_RGBA16F, FORMAT_RGBA32F, FORMAT_RGBA8_UNORM_SRGB, FORMAT_BGRA8_UNORM_SRGB = range(4)  # HkPresentTarget.format
 PRESENT_HDR, PRESENT_CLEAR = 1, 2
+RAYS_CLOSEST, RAYS_ANY, RAYS_ATTRIBUTES, RAYS_STACKLESS = 0, 1, 2, 4  # hk_cast_rays flags
+RAY_MISS, RAY_HIT, RAY_INVALID = 0, 1, 2                              # HkRayHit.status
+NO_INSTANCE = 0xFFFFFFFF                                              # HkRay.exclude_instance "nothing"; HkRayHit.instance / primitive of a miss
 
 f32, u32, u64 = C.c_float, C.c_uint32, C.c_uint64
 
@@ -143,6 +146,15 @@ class HkPresentTarget(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("width", u32), ("height", u32), ("pitch_bytes", u32), ("format", u32), ("flags", u32), ("clear", f32 * 4)]
 
 
+class HkRay(C.Structure):
+    _fields_ = [("origin", f32 * 3), ("max_distance", f32), ("direction", f32 * 3), ("exclude_instance", u32)]
+
+
+class HkRayHit(C.Structure):
+    _fields_ = [("distance", f32), ("instance", u32), ("primitive", u32), ("material", u32), ("barycentric", f32 * 2), ("uv", f32 * 2),
+                ("normal", f32 * 3), ("status", u32)]
+
+
 class HkHaloOp(C.Structure):
     _fields_ = [("buffer", u32), ("peer", u32), ("row_begin", u32), ("row_end", u32), ("row_bytes", u64)]
 
@@ -167,6 +179,7 @@ class HkStats(C.Structure):
 assert C.sizeof(HkVertex) == 32 and C.sizeof(HkPrimitive) == 48 and C.sizeof(HkNode) == 32 and C.sizeof(HkInstance) == 176
 assert C.sizeof(HkMaterial) == 80 and C.sizeof(HkEmissive) == 64 and C.sizeof(HkFrame) == 256 and C.sizeof(HkView) == 416
 assert C.sizeof(HkPreviousView) == 128 and C.sizeof(HkAliasEntry) == 8
+assert C.sizeof(HkRay) == 32 and C.sizeof(HkRayHit) == 48
 
 
 class HikariError(RuntimeError):
@@ -263,6 +276,8 @@ _PRODUCT_ONLY = {
     "skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],
     "rebuild_mesh_tree": [_vp, P(HkMeshIndex), u32],
     "present": [_vp, P(HkSettings), u32, P(HkPresentTarget), u32, u32],
+    "cast_rays": [_vp, P(HkRay), u32, u32, P(HkRayHit)],
+    "cast_rays_device": [_vp, _vp, u32, u32, _vp],
     "band_rows": [u32, u32, u32, P(u32), P(u32)],
     "balanced_band_bounds": [P(u32), u32, u32, u32, u32, u32, f32, P(u32)],
     "balance_bands": [_vp, u32, P(u32), u32],

@@ -968,6 +968,8 @@ void hk_destroy(hk_ctx* c) {
     if (c->staging[k]) (void)hipHostFree(c->staging[k]);
     if (c->staging_done[k]) (void)hipEventDestroy(c->staging_done[k]);
   }
+  if (c->query_staging) (void)hipHostFree(c->query_staging);
+  if (c->query_device) (void)hipFree(c->query_device);
   free_refit(c);
   free_deform(c);
   for (void* q : {(void*)c->wide_tlas, (void*)c->wide_blas, (void*)c->wide_spill, (void*)c->wide_tlas_rank, (void*)c->wide_blas_rank})
@@ -1657,6 +1659,79 @@ int hk_present(hk_ctx* c, const HkSettings* st, uint32_t frame_flags, const HkPr
   launch_present(on_post ? c->post_stream : c->stream, c->buf[final], sw, sh, c->buf[HK_BUF_ALBEDO], c->W, c->H, c->scene.srgb_lut, *t, (int)row_begin, (int)row_end);
   HK_HIP(hipGetLastError());
   if (on_post) HK_HIP(hipEventRecord(c->post_done[parity], c->post_stream));
+  return HK_OK;
+}
+
+// Ray queries (hikari_hip.h).  The launch goes onto the MAIN stream: uploads, refits, rebuilds and deformations write the scene there
+// (or behind join_all), so it reads what the next frame would read; the other streams only ever read the scene.  The records of the
+// wide walk are derived on the main stream as well (ensure_wide) - when a query is what derives them, the scene counts as written for
+// the primary-ray pipelining, exactly as when a frame does.
+static_assert(sizeof(HkRay) == 32 && sizeof(HkRayHit) == 48, "HkRay is two float4, HkRayHit three (kernels_query.hip)");
+static int cast_rays_checked(hk_ctx* c, const void* rays, uint32_t n, uint32_t flags, void* hits) {
+  HK_REQUIRE(!(flags & ~(HK_RAYS_ANY | HK_RAYS_ATTRIBUTES | HK_RAYS_STACKLESS)), HK_E_INVALID, "unknown ray query flag 0x%x", flags);
+  HK_REQUIRE(!((flags & HK_RAYS_ANY) && (flags & HK_RAYS_ATTRIBUTES)), HK_E_INVALID, "HK_RAYS_ATTRIBUTES needs the closest hit: not with HK_RAYS_ANY");
+  HK_REQUIRE(!n || (rays && hits), HK_E_INVALID, "NULL rays or hits with n = %u", n);
+  HK_REQUIRE(c, HK_E_INVALID, "ctx is NULL");
+  return HK_OK;
+}
+static int cast_rays_enqueue(hk_ctx* c, const void* d_rays, uint32_t n, uint32_t flags, void* d_hits) {
+  int rc = finalize_scene(c);
+  if (!rc) rc = flush_deform(c);   // (the instance level of meshes deformed since the last frame, as a frame would)
+  if (rc) return rc;
+  HK_REQUIRE(c->scene_mem, HK_E_NOT_READY, "no scene uploaded");
+  hkd::WideTrees wide{};
+  if (!(flags & (HK_RAYS_ANY | HK_RAYS_STACKLESS)) && wide_allowed(c)) {
+    const bool derives = c->wide_tlas_dirty || c->wide_blas_dirty || c->wide_mesh_check;
+    if ((rc = ensure_wide(c, true))) return rc;   // (with the spill area of the trace stages: the main stream serialises its users)
+    if (derives) c->scene_epoch += 1;
+    wide.tlas = c->wide_tlas;
+    wide.blas = c->wide_blas;
+    wide.tlas_rank = c->wide_tlas_rank;
+    wide.blas_rank = c->wide_blas_rank;
+    wide.tlas_count = c->scene.tlas_count;
+    wide.spill = c->wide_spill;
+    wide.lost = c->d_counters + 8;
+  }
+  launch_cast_rays(c->stream, c->scene, &wide, c->wide_spill_lanes, d_rays, n, flags, d_hits);
+  HK_HIP(hipGetLastError());
+  return HK_OK;
+}
+int hk_cast_rays_device(hk_ctx* c, const void* d_rays, uint32_t n, uint32_t flags, void* d_hits) {
+  int rc = cast_rays_checked(c, d_rays, n, flags, d_hits);
+  if (rc || !n) return rc;
+  HK_REQUIRE(((uintptr_t)d_rays % 16) == 0 && ((uintptr_t)d_hits % 16) == 0, HK_E_INVALID, "d_rays and d_hits must be aligned to 16 bytes");
+  HK_HIP(hipSetDevice(c->device));
+  return cast_rays_enqueue(c, d_rays, n, flags, d_hits);
+}
+int hk_cast_rays(hk_ctx* c, const HkRay* rays, uint32_t n, uint32_t flags, HkRayHit* hits) {
+  int rc = cast_rays_checked(c, rays, n, flags, hits);
+  if (rc || !n) return rc;
+  HK_HIP(hipSetDevice(c->device));
+  const size_t chunk = std::min<size_t>(n, (size_t)1 << 18);   // (rays per round trip: 20 MB of pinned memory at the most)
+  const size_t per_ray = sizeof(HkRay) + sizeof(HkRayHit);
+  if (chunk > c->query_capacity) {
+    HK_HIP(hipStreamSynchronize(c->stream));
+    if (c->query_staging) (void)hipHostFree(c->query_staging);
+    if (c->query_device) (void)hipFree(c->query_device);
+    c->query_staging = c->query_device = nullptr;
+    c->query_capacity = 0;
+    HK_HIP(hipHostMalloc((void**)&c->query_staging, chunk * per_ray, hipHostMallocDefault));
+    HK_HIP(hipMalloc((void**)&c->query_device, chunk * per_ray));
+    c->query_capacity = chunk;
+  }
+  uint8_t* const h_rays = c->query_staging;
+  uint8_t* const h_hits = c->query_staging + c->query_capacity * sizeof(HkRay);
+  uint8_t* const d_rays = c->query_device;
+  uint8_t* const d_hits = c->query_device + c->query_capacity * sizeof(HkRay);
+  for (size_t done = 0; done < n; done += chunk) {
+    const size_t m = std::min<size_t>(chunk, n - done);
+    memcpy(h_rays, rays + done, m * sizeof(HkRay));
+    HK_HIP(hipMemcpyAsync(d_rays, h_rays, m * sizeof(HkRay), hipMemcpyHostToDevice, c->stream));
+    if ((rc = cast_rays_enqueue(c, d_rays, (uint32_t)m, flags, d_hits))) return rc;
+    HK_HIP(hipMemcpyAsync(h_hits, d_hits, m * sizeof(HkRayHit), hipMemcpyDeviceToHost, c->stream));
+    HK_HIP(hipStreamSynchronize(c->stream));
+    memcpy(hits + done, h_hits, m * sizeof(HkRayHit));
+  }
   return HK_OK;
 }
 

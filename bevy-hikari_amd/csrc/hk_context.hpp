@@ -305,6 +305,11 @@ struct hk_ctx {
   hipEvent_t band_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // HK_FRAME_TIME_BAND: around stage TEMPORAL, around stage SPATIAL (main stream)
   bool band_timed = false;
 
+  // ray queries (hk_cast_rays): pinned staging and device memory for one chunk of rays and their records, grown on demand
+  uint8_t* query_staging = nullptr;
+  uint8_t* query_device = nullptr;
+  size_t query_capacity = 0;   // rays both hold
+
   // statistics
   unsigned long long* d_counters = nullptr;  // primary, tlas, blas, node steps, triangle tests, instance entries, closest hits (hk_light.hpp flush_counters)
   uint64_t frames = 0;

@@ -368,6 +368,10 @@ void launch_fsr_rcas(hipStream_t st, const void* input, void* output, int w, int
 // hk_present: rows [y0, y1) of the host's target from the final image and the albedo (rgba16f planes of their own sizes)
 void launch_present(hipStream_t st, const void* src, int src_w, int src_h, const void* albedo, int albedo_w, int albedo_h, const float* srgb_lut,
                     const HkPresentTarget& t, int y0, int y1);
+// hk_cast_rays: n host rays (HkRay) -> n records (HkRayHit), both in device memory; flags = HK_RAYS_*; wide = the records of the wide
+// walk (tlas and spill != nullptr, wide_lanes = the lanes the spill area serves) where closest hits of a scene in global memory are to
+// take it, or nullptr (kernels_query.hip)
+void launch_cast_rays(hipStream_t st, const hkd::DScene& sc, const hkd::WideTrees* wide, size_t wide_lanes, const void* rays, uint32_t n, uint32_t flags, void* hits);
 // apply the parked scatter stores of pixels [p0, p1); [own0, own1) = the pixels this context dispatched itself (their winners are
 // in), empty = all of them
 void launch_resolve_scatter(hipStream_t st, const hkd::LightTargets& t, int p0, int p1, int own0, int own1);

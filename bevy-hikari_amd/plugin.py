@@ -217,6 +217,51 @@ class Camera:
         v.viewport[:] = [0.0, 0.0, float(self.width), float(self.height)]
         return v
 
+    def ray_through(self, u, v):
+        """(origin, direction): the world-space ray through the point (u, v) of the image - (0, 0) its top left corner, (1, 1) its
+        bottom right one, pixel (x, y)'s centre at ((x + 0.5) / width, (y + 0.5) / height) - as float32[3] each, from the camera's
+        own inverse matrices: the point of the near plane under (u, v) is inverse_view_proj * (ndc, 1) (reverse-Z).  A perspective
+        ray starts at the eye and runs through that point; an orthographic one starts ON the near plane and runs along the view
+        direction, as the primary rays of the prepass do.  The direction is normalised, so a hit's distance is in world units.
+        Computed in doubles from the float32 uniforms: the prepass's ray to within rounding, not its bits."""
+        vu = self.view_uniform()
+        ivp = [float(x) for x in vu.inverse_view_proj]
+        ndc = (2.0 * float(u) - 1.0, 1.0 - 2.0 * float(v), 1.0, 1.0)
+        q = [0.0] * 4
+        for r in range(4):      # (explicit loops in a fixed order, like _mul4: include/hikari.hpp forms the same ray bit for bit)
+            s = 0.0
+            for c in range(4):
+                s += ivp[c * 4 + r] * ndc[c]
+            q[r] = s
+        near = [q[0] / q[3], q[1] / q[3], q[2] / q[3]]
+        if self.ortho_height is not None:
+            vp = [float(x) for x in vu.view_proj]
+            d = [-vp[2], -vp[6], -vp[10]]      # (light.wgsl:714-727: -normalize(view_proj[0].z, view_proj[1].z, view_proj[2].z))
+            origin = near
+        else:
+            origin = [float(x) for x in vu.world_position]
+            d = [near[0] - origin[0], near[1] - origin[1], near[2] - origin[2]]
+        l = math.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+        d = [d[0] / l, d[1] / l, d[2] / l]
+        origin, d = np.asarray(origin, dtype=np.float64), np.asarray(d, dtype=np.float64)
+        return origin.astype(np.float32), d.astype(np.float32)
+
+    def rays_through(self, u, v):
+        """ray_through for arrays of points: a RAY_DTYPE array (max_distance 3.4e38, nothing excluded), one ray per (u, v) pair.  The same
+        formulas evaluated by numpy in doubles - for batches (picking many points, probe grids), not for bit comparisons."""
+        vu = self.view_uniform()
+        ivp = np.asarray(list(vu.inverse_view_proj), dtype=np.float64).reshape(4, 4).T   # math layout
+        u, v = np.asarray(u, dtype=np.float64).reshape(-1), np.asarray(v, dtype=np.float64).reshape(-1)
+        q = np.stack([2.0 * u - 1.0, 1.0 - 2.0 * v, np.ones_like(u), np.ones_like(u)], axis=1) @ ivp.T
+        near = q[:, :3] / q[:, 3:4]
+        if self.ortho_height is not None:
+            vp = np.asarray(list(vu.view_proj), dtype=np.float64)
+            origin, d = near, np.broadcast_to(-np.array([vp[2], vp[6], vp[10]]), near.shape)
+        else:
+            origin = np.broadcast_to(np.asarray(list(vu.world_position), dtype=np.float64), near.shape)
+            d = near - origin
+        return make_rays(origin, d / np.linalg.norm(d, axis=1, keepdims=True))
+
     def previous_view_uniform(self, previous: Optional["Camera"] = None):
         cam = previous or self
         v = cam.view_uniform()
@@ -426,6 +471,22 @@ def load_noise():
 # engine: one hk_ctx
 # ---------------------------------------------------------------------------------------------
 _BUF_DTYPES = {16: (np.float32, 4), 4: (np.uint32, 1), 8: (np.uint16, 4), 64: (np.uint32, 16)}
+
+
+#: HkRay / HkRayHit as numpy record types (Engine.cast_rays)
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("max_distance", np.float32), ("direction", np.float32, 3), ("exclude_instance", np.uint32)])
+HIT_DTYPE = np.dtype([("distance", np.float32), ("instance", np.uint32), ("primitive", np.uint32), ("material", np.uint32),
+                      ("barycentric", np.float32, 2), ("uv", np.float32, 2), ("normal", np.float32, 3), ("status", np.uint32)])
+assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 48
+
+
+def make_rays(origins, directions, max_distance=3.4028234663852886e38, exclude_instance=F.NO_INSTANCE):
+    """A RAY_DTYPE array from (n, 3) origins and directions; max_distance / exclude_instance scalars or (n,) arrays."""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    r = np.zeros(len(o), dtype=RAY_DTYPE)
+    r["origin"], r["direction"] = o, np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    r["max_distance"], r["exclude_instance"] = max_distance, exclude_instance
+    return r
 
 
 def _present_formats():
@@ -755,6 +816,46 @@ class Engine:
         self.present_into(sc, frame_flags, out.data_ptr(), out.shape[1], out.shape[0], out.stride(0) * out.element_size(), fmt, flags, clear, rows)
         if wait:
             self.wait()
+        return out
+
+    # -- ray queries (picking, line of sight, probe rays)
+    def cast_rays(self, rays, *, any_hit=False, attributes=False, stackless=False, out=None, wait=True):
+        """hk_cast_rays / hk_cast_rays_device: one HkRayHit per HkRay, against the scene this context holds (no resize, no frame).
+        `rays`: a numpy array viewable as (n, 8) float32 - origin xyz, max_distance, direction xyz, exclude_instance as BITS - or a
+        structured array of RAY_DTYPE (make_rays builds one); returns a structured numpy array of HIT_DTYPE (`out`, if given).
+        A torch tensor of n x 32 bytes in device memory goes through hk_cast_rays_device without a copy: torch's current stream
+        is synchronised first, the context is waited for afterwards (unless wait=False: call wait() before torch reads), and the
+        result is a uint8 tensor [n][48] (`out`, or a new one) - view it as float32 / int32 columns as needed.
+        any_hit: occlusion only (status; identity and distance are not promised).  attributes: also material, uv, normal.
+        stackless: never the wide walk (F.RAYS_STACKLESS)."""
+        flags = (F.RAYS_ANY if any_hit else 0) | (F.RAYS_ATTRIBUTES if attributes else 0) | (F.RAYS_STACKLESS if stackless else 0)
+        if not isinstance(rays, np.ndarray) and hasattr(rays, "data_ptr"):
+            import torch
+
+            if rays.device.type != "cuda" or not rays.is_contiguous() or (rays.numel() * rays.element_size()) % 32:
+                raise ValueError("cast_rays(): a contiguous tensor of n x 32 bytes in device memory is needed")
+            n = rays.numel() * rays.element_size() // 32
+            if out is None:
+                out = torch.empty((n, 48), dtype=torch.uint8, device=rays.device)
+            if out.device != rays.device or not out.is_contiguous() or out.numel() * out.element_size() != n * 48:
+                raise ValueError("cast_rays(): `out` must be a contiguous tensor of n x 48 bytes on the rays' device")
+            torch.cuda.current_stream(rays.device).synchronize()
+            self.api.call("cast_rays_device", self.ctx, C.c_void_p(rays.data_ptr()), n, flags, C.c_void_p(out.data_ptr()))
+            if wait:
+                self.wait()
+            return out
+        r = np.ascontiguousarray(rays)
+        if r.dtype != RAY_DTYPE:
+            if r.dtype.itemsize != 4 or r.ndim != 2 or r.shape[1] != 8:
+                raise ValueError("cast_rays(): rays must be (n, 8) of a 4-byte type or a structured array of RAY_DTYPE")
+            r = r.view(RAY_DTYPE).reshape(-1)
+        r = r.reshape(-1)
+        if out is None:
+            out = np.zeros(len(r), dtype=HIT_DTYPE)
+        if out.dtype != HIT_DTYPE or out.shape != (len(r),) or not out.flags.c_contiguous:
+            raise ValueError("cast_rays(): `out` must be a contiguous HIT_DTYPE array with one record per ray")
+        self.api.call("cast_rays", self.ctx, C.cast(C.c_void_p(r.ctypes.data), C.POINTER(F.HkRay)), len(r), flags,
+                      C.cast(C.c_void_p(out.ctypes.data), C.POINTER(F.HkRayHit)))
         return out
 
     # -- halo exchange inside the library (one process per GPU; bevy-hikari_amd/distributed.py does the rendezvous)

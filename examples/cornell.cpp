@@ -6,6 +6,9 @@
 //
 //   cornell [--size W H] [--frames N] [--bounces B] [--ratio R | --fsr R SHARPNESS] [--by-nodes] [--antialias] [--ppm out.ppm] [--raw out.bin] [--describe]
 //           [--present out.bgra]            OverlayNode: the last frame presented over its clear colour into a bgra8-sRGB target (W x H x 4 bytes)
+//           [--pick U V]                    a ray query (hk_cast_rays) through the point (U, V) of the camera's image, 0..1 from its top left corner:
+//                                          prints `pick instance primitive distance` (4294967295 4294967295 3.40282347e+38 for a miss); the frames are
+//                                          the same with or without it
 //           [--animate [--rebuild-at F]]   the boxes drift every frame; the poses go to the GPU, which redoes the instance records and refits
 //                                          both trees (hk_refit_scene_instances); at frame F the trees are rebuilt on the device (LBVH)
 //           [--gpus N [--devices a,b,..]]   band-sharded over N GPUs from this one process (hk_multi_*); --devices may repeat an id
@@ -90,6 +93,8 @@ int main(int argc, char** argv) {
   int gpus = 1;
   std::vector<int> devices;
   bool balance = false;  // --balance: split the bands by cost on the first frame (HK_FRAME_BALANCE_BANDS)
+  bool pick = false;     // --pick U V: one closest-hit query through that point of the image
+  double pick_u = 0.5, pick_v = 0.5;
   bool gather = false;   // --gather: band 0's device collects the finished image every frame (HK_FRAME_GATHER); --raw then reads that one context
   std::string ppm, raw, present, assets = "bevy-hikari_amd/assets";
   for (int i = 1; i < argc; ++i) {
@@ -104,6 +109,7 @@ int main(int argc, char** argv) {
     else if (a == "--ppm" && i + 1 < argc) ppm = argv[++i];
     else if (a == "--raw" && i + 1 < argc) raw = argv[++i];
     else if (a == "--present" && i + 1 < argc) present = argv[++i];
+    else if (a == "--pick" && i + 2 < argc) { pick = true; pick_u = atof(argv[++i]); pick_v = atof(argv[++i]); }
     else if (a == "--assets" && i + 1 < argc) assets = argv[++i];
     else if (a == "--describe") describe = true;
     else if (a == "--animate") animate = true;
@@ -169,6 +175,11 @@ int main(int argc, char** argv) {
     load_cornell(assets + "/cornell.hkscene", scene);                      // asset_server.load("models/cornell.glb#Scene0")
     plugin.set_scene(scene);
     Camera camera = Camera::looking_at({0.0, 1.0, 4.0}, {0.0, 1.0, 0.0}, {0.0, 1.0, 0.0}, w, h);  // cornell.rs:49-50
+    if (pick) {  // picking: what is under this point of the image (needs the scene only - no size, no frame)
+      const HkRay ray = camera.ray_through(pick_u, pick_v);
+      const HkRayHit hit = plugin.context().cast_rays(&ray, 1)[0];
+      std::printf("pick %u %u %.9g\n", hit.instance, hit.primitive, hit.distance);
+    }
     std::vector<HkInstance> rest;
     if (animate) {  // the poses the asset was loaded with
       const HkInstance* inst; uint32_t n_inst;

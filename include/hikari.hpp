@@ -192,6 +192,31 @@ struct Camera {
     v.viewport[3] = (float)height;
     return v;
   }
+  // The world-space ray through the point (u, v) of the image - (0, 0) its top left corner, (1, 1) its bottom right one: from the eye
+  // through the point of the near plane under (u, v), inverse_view_proj * (ndc, 1) (reverse-Z); the direction is normalised.  In
+  // doubles from the float32 uniforms, the operations and their order those of plugin.py Camera.ray_through: the same ray bit for bit.
+  HkRay ray_through(double u, double v, float max_distance = 3.402823466e+38f, uint32_t exclude_instance = 0xFFFFFFFFu) const {
+    const HkView vu = view_uniform();
+    const double ndc[4] = {2.0 * u - 1.0, 1.0 - 2.0 * v, 1.0, 1.0};
+    double q[4];
+    for (int r = 0; r < 4; ++r) {
+      double s = 0.0;
+      for (int c = 0; c < 4; ++c) s += (double)vu.inverse_view_proj[c * 4 + r] * ndc[c];
+      q[r] = s;
+    }
+    const double near_point[3] = {q[0] / q[3], q[1] / q[3], q[2] / q[3]};
+    const double o[3] = {(double)vu.world_position[0], (double)vu.world_position[1], (double)vu.world_position[2]};
+    double d[3] = {near_point[0] - o[0], near_point[1] - o[1], near_point[2] - o[2]};
+    const double l = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    HkRay ray{};
+    for (int k = 0; k < 3; ++k) {
+      ray.origin[k] = (float)o[k];
+      ray.direction[k] = (float)(d[k] / l);
+    }
+    ray.max_distance = max_distance;
+    ray.exclude_instance = exclude_instance;
+    return ray;
+  }
   HkPreviousView previous_view_uniform() const {
     HkView v = view_uniform();
     HkPreviousView p{};
@@ -278,6 +303,13 @@ class Context {
     check(hk_read_buffer(c_, buffer, out.data(), out.size()), "hk_read_buffer");
     return out;
   }
+  // ray queries against the uploaded scene (hk_cast_rays): one record per ray, in order; flags = HK_RAYS_*.  No resize, no frame needed.
+  std::vector<HkRayHit> cast_rays(const HkRay* rays, uint32_t n, uint32_t flags = HK_RAYS_CLOSEST) const {
+    std::vector<HkRayHit> hits(n);
+    check(hk_cast_rays(c_, rays, n, flags, hits.data()), "hk_cast_rays");
+    return hits;
+  }
+  std::vector<HkRayHit> cast_rays(const std::vector<HkRay>& rays, uint32_t flags = HK_RAYS_CLOSEST) const { return cast_rays(rays.data(), (uint32_t)rays.size(), flags); }
 
  private:
   hk_ctx* c_ = nullptr;

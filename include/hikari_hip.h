@@ -716,6 +716,61 @@ typedef struct HkPresentTarget {
 int hk_present(hk_ctx* ctx, const HkSettings* settings, uint32_t frame_flags, const HkPresentTarget* target, uint32_t row_begin,
                uint32_t row_end);
 
+/* ------------------------------------------------------------------ ray queries (picking, line of sight, probe rays) */
+/* Rays of the host's own against the scene the context holds: what is under a cursor ray, is B visible from A, where does a probe
+ * land.  One record in, one record out, in the order given; no hk_resize, no frame and no band is involved, and a context that is one
+ * band of several answers like a single context (it holds the whole scene).
+ *   direction      used as given, NOT normalised; `distance` is in units of it (position = origin + distance * direction), as in the
+ *                  reference's traverse_top (light.wgsl:442-486).  There is no t_min: offset the origin.
+ *   max_distance   hits at or beyond it are not reported (+inf and 3.4e38 mean "any")
+ *   exclude_instance  an instance the ray passes through; 0xFFFFFFFF excludes nothing
+ * A miss has distance = max_distance, instance = primitive = 0xFFFFFFFF and status HK_RAY_MISS - what the reference's Hit holds.
+ * A ray is HK_RAY_INVALID, and is not walked, when a component of origin or direction is not finite, when direction is all zero, or
+ * when max_distance is NaN or negative: it is written as a miss with that status, decided per ray before any walk, and the rays
+ * around it are answered as usual.
+ * flags:
+ *   HK_RAYS_CLOSEST     the closest hit: the reference's traverse_top with early_distance = 0.  A context created with
+ *                       HK_CTX_EXACT_TRAVERSAL walks the reference's order and reports the reference's hit bit for bit; otherwise the
+ *                       walk is the one the frame's own closest-hit rays take on this scene (hk_traversal_mode), and the hit is the
+ *                       reference's except where two candidates tie or a box is grazed within rounding.
+ *   HK_RAYS_ANY         occlusion only: the walk stops at the first hit it meets (early_distance = +inf).  status says hit or miss;
+ *                       WHICH hit the record names, and its distance, are not promised.  Never the wide walk.
+ *   HK_RAYS_ATTRIBUTES  closest hits only: material, uv and normal are filled as the light passes see the hit (hit_info,
+ *                       light.wgsl:496-523: interpolated uv, interpolated normal through the inverse-transpose model, normalised; a miss
+ *                       has material 0xFFFFFFFF and zeros).  Without the flag the three fields are zero.
+ *   HK_RAYS_STACKLESS   never take the wide walk: scenes beyond the LDS copy are walked by skip links in the ray's ordering even where
+ *                       hk_traversal_mode reports HK_TRAVERSAL_WIDE.  (A pending subtree the wide walk has to drop is counted in
+ *                       HkStats.wide_stack_lost, as in frames.) */
+typedef struct HkRay {
+  float origin[3];
+  float max_distance;
+  float direction[3];
+  uint32_t exclude_instance;
+} HkRay; /* 32 bytes */
+typedef struct HkRayHit {
+  float distance;
+  uint32_t instance, primitive, material;
+  float barycentric[2]; /* of the hit inside its triangle: position = v0 + b[0] * (v1 - v0) + b[1] * (v2 - v0) */
+  float uv[2];
+  float normal[3];
+  uint32_t status; /* HK_RAY_* */
+} HkRayHit; /* 48 bytes */
+#define HK_RAYS_CLOSEST 0u
+#define HK_RAYS_ANY 1u
+#define HK_RAYS_ATTRIBUTES 2u
+#define HK_RAYS_STACKLESS 4u
+#define HK_RAY_MISS 0u
+#define HK_RAY_HIT 1u
+#define HK_RAY_INVALID 2u
+/* `rays` and `hits` in host memory: the same launch between two copies through pinned staging; returns when `hits` is written.
+ * n = 0 is HK_OK and launches nothing.  HK_E_INVALID (nothing written): a NULL context, a NULL pointer with n > 0, an unknown flag bit,
+ * HK_RAYS_ATTRIBUTES together with HK_RAYS_ANY.  HK_E_NOT_READY: no scene uploaded. */
+int hk_cast_rays(hk_ctx* ctx, const HkRay* rays, uint32_t n, uint32_t flags, HkRayHit* hits);
+/* `d_rays` (n x 32 bytes) and `d_hits` (n x 48 bytes) in device memory, both aligned to 16 bytes: enqueued on the context's main
+ * stream (hk_stream) with no wait - behind every scene upload, refit, rebuild, deformation and frame enqueued before it, reading the
+ * instance-level slot the next frame would read.  The caller orders its own stream against hk_stream (or calls hk_frame_wait). */
+int hk_cast_rays_device(hk_ctx* ctx, const void* d_rays, uint32_t n, uint32_t flags, void* d_hits);
+
 /* ------------------------------------------------------------------ band sharding (multi-GPU) */
 /* Restrict this context to band `band_index` of `band_count` horizontal bands of the render image
  * (bands are contiguous row ranges, remainder rows spread over the first bands). */

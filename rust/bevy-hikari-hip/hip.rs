@@ -424,3 +424,12 @@ pub fn present(context: &HipContext, settings: &HikariSettings, target: *mut std
     };
     check(unsafe { hk::hk_present(context.ctx, &hk_settings, hk::HK_FRAME_ANTIALIAS, &present_target, 0, height) })
 }
+
+/// Ray queries against the scene the context holds (`hk_cast_rays`): picking, line of sight, probe rays - what a
+/// `bevy_mod_raycast`-style backend binds.  One `HkRayHit` per `HkRay`, in order; `flags` = `hk::HK_RAYS_*`.  Needs no size and no frame.
+pub fn cast_rays(context: &HipContext, rays: &[hk::HkRay], flags: u32) -> Result<Vec<hk::HkRayHit>, HipError> {
+    let mut hits: Vec<hk::HkRayHit> = Vec::with_capacity(rays.len());
+    check(unsafe { hk::hk_cast_rays(context.ctx, rays.as_ptr(), rays.len() as u32, flags, hits.as_mut_ptr()) })?;
+    unsafe { hits.set_len(rays.len()) };
+    Ok(hits)
+}
