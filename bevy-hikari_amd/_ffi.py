@@ -48,6 +48,7 @@ CTX_COUNT_WALKS = 512   # the trace stages run the counting twin of their kernel
 CTX_RACING_SCATTER = 1024   # hikari_hip.h HK_CTX_RACING_SCATTER: the reference's own race on previous_spatial (round 6: the default resolves it)
 DEBUG_OPT_SPATIAL_WINDOW, DEBUG_OPT_FRAME_PIPELINE, DEBUG_OPT_WF_TIMELINE, DEBUG_OPT_FLAT_WALK, DEBUG_OPT_FLAT_ORDERINGS, DEBUG_OPT_TRACE_UPDATE = 0, 1, 2, 3, 4, 5  # hikari_hip_debug.h hk_debug_set_option
 DEBUG_OPT_MAIN_PRIORITY, DEBUG_OPT_PREPASS_PIPELINE, DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP = 9, 10, 11  # (6, 7 and 8 are retired)
+DEBUG_OPT_LOAD_DEVICE_LIMIT = 12
 TIMING_TRACE_STAGES = 18  # hk_set_timing_mask bit / HkStats slot: every trace launch of the queue-based indirect pass
 TRAVERSAL_WIDE = 0x100
 FRAME_EXTERNAL_GBUFFER, FRAME_ANTIALIAS, FRAME_BALANCE_BANDS, FRAME_GATHER, FRAME_TIME_BAND = 1, 2, 4, 8, 16
@@ -225,6 +226,8 @@ _DEBUG = {
     "debug_math": [_vp, u32, P(f32), P(f32), P(f32), C.c_size_t],
     "debug_read_trees": [_vp, P(HkNode), u32, P(HkNode), u32],
     "debug_read_mesh_nodes": [_vp, P(HkNode), u32, P(u32), P(u32)],
+    "debug_last_load": [_vp, P(u32)],
+    "debug_last_load_times": [_vp, P(C.c_double)],
     "debug_read_emitters": [_vp, P(f32), u32, P(u32), P(f32), u32, P(u32)],
     "debug_read_mesh_geometry": [_vp, P(HkMeshIndex), P(f32), P(f32), u32, P(f32), u32, P(f32), P(u32), P(u32)],
     "debug_comm_loopback": [_vp, u32, u32, u32, u32, u32],
@@ -246,6 +249,9 @@ _PRODUCT_ONLY = {
     "scaled_size": [u32, u32, f32, P(u32), P(u32)],
     "scene_builder_create": [P(_vp)],
     "scene_builder_add_mesh": [_vp, P(f32), P(f32), P(f32), u32, P(u32), u32, u32, P(u32)],
+    "scene_builder_add_mesh_deferred": [_vp, P(f32), P(f32), P(f32), u32, P(u32), u32, u32, P(u32)],
+    "scene_builder_pending_mesh_trees": [_vp, P(u32)],
+    "scene_builder_build_pending_mesh_trees": [_vp],
     "scene_builder_add_material": [_vp, P(HkMaterial), P(u32)],
     "scene_builder_add_instance": [_vp, u32, u32, P(f32), P(u32)],
     "scene_builder_finish": [_vp],
@@ -268,6 +274,7 @@ _PRODUCT_ONLY = {
     "scene_builder_mesh_index": [_vp, u32, P(HkMeshIndex)],
     "upload_scene": [_vp, _vp],
     "upload_scene_instances": [_vp, _vp],
+    "load_scene": [_vp, _vp, u32],
     "refit_scene_instances": [_vp, _vp, P(u32)],
     "rebuild_scene_trees": [_vp, u32],
     "update_scene_instances": [_vp, _vp, u32],
@@ -314,6 +321,7 @@ _PRODUCT_ONLY = {
     "multi_context": [_vp, u32, P(_vp)],
     "multi_upload_scene": [_vp, _vp],
     "multi_upload_scene_instances": [_vp, _vp],
+    "multi_load_scene": [_vp, _vp, u32],
     "multi_refit_scene_instances": [_vp, _vp, P(u32)],
     "multi_rebuild_scene_trees": [_vp, u32],
     "multi_update_scene_instances": [_vp, _vp, u32],

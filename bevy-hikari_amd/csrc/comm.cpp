@@ -811,6 +811,13 @@ int hk_multi_context(hk_multi* m, uint32_t i, hk_ctx** out) {
   return HK_OK
 
 int hk_multi_upload_scene(hk_multi* m, const hk_scene_builder* b) { HK_EACH(hk_upload_scene(c, b)); }
+// the trees are built once, on the first band's context, and written back into the builder: the other bands take the finished builder
+int hk_multi_load_scene(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode) {
+  HK_REQUIRE(m && b && !m->ctx.empty(), HK_E_INVALID, "NULL argument");
+  int rc = hk_load_scene(m->ctx[0], b, tree_mode);
+  for (size_t i = 1; i < m->ctx.size() && !rc; ++i) rc = hk_upload_scene(m->ctx[i], b);
+  return rc;
+}
 int hk_multi_upload_scene_instances(hk_multi* m, const hk_scene_builder* b) { HK_EACH(hk_upload_scene_instances(c, b)); }
 int hk_multi_rebuild_scene_trees(hk_multi* m, uint32_t mode) { HK_EACH(hk_rebuild_scene_trees(c, mode)); }
 int hk_multi_update_mesh_vertices(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vertices, const float* positions, const float* normals) {
@@ -850,6 +857,7 @@ int hk_multi_migrate_bands(hk_multi* m, const uint32_t* new_bounds, uint32_t n_b
 // the builder is finished ONCE (its transform bookkeeping advances once), every band's replica takes the records and builds its trees
 int hk_multi_update_scene_instances(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode) {
   HK_REQUIRE(m && b, HK_E_INVALID, "NULL argument");
+  HK_NO_PENDING_MESHES(b);
   const int rc = hk_scene_builder_finish_instances(b);
   if (rc) return rc;
   uint32_t ni = 0;

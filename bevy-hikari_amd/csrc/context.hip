@@ -1020,6 +1020,7 @@ int hk_debug_set_option(hk_ctx* c, uint32_t option, int64_t value) {
     case HK_DEBUG_OPT_FLAT_ORDERINGS: c->flat_orderings = (int)std::max<int64_t>(0, std::min<int64_t>(8, value)); c->dynamic_dirty = true; break;
     case HK_DEBUG_OPT_TRACE_UPDATE: c->trace_update = value != 0; break;
     case HK_DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP: c->mesh_rebuild_one_workgroup = value != 0; break;
+    case HK_DEBUG_OPT_LOAD_DEVICE_LIMIT: c->load_device_limit = value <= 0 ? HK_MESH_REBUILD_MAX_TRIANGLES : (uint32_t)std::min<int64_t>(value, HK_MESH_REBUILD_MAX_TRIANGLES); break;
     case HK_DEBUG_OPT_PREPASS_PIPELINE: c->prepass_pipeline = value < 0 ? -1 : (value ? 1 : 0); break;
     case HK_DEBUG_OPT_MAIN_PRIORITY: c->main_priority = value < 0 ? -1 : (value ? 1 : 0); return pick_main_stream(c, true);
     default: HK_REQUIRE(false, HK_E_INVALID, "unknown option %u", option);

@@ -245,6 +245,12 @@ struct hk_ctx {
   uint64_t device_refits = 0, device_tree_builds = 0;
   void* lbvh_scratch = nullptr;           // hk_rebuild_scene_trees
   size_t lbvh_scratch_cap = 0;
+  // hk_load_scene (scene_load.hip): the mesh ranges the device is about to build (build_static_region neither threads nor folds them),
+  // the size from which a deferred mesh is completed by the host instead, and what the last load did (hk_debug_last_load)
+  std::vector<std::pair<uint32_t, uint32_t>> load_pending_ranges;
+  uint32_t load_device_limit = HK_MESH_REBUILD_MAX_TRIANGLES;
+  uint32_t last_load[4] = {0, 0, 0, 0};
+  double last_load_ms[5] = {0, 0, 0, 0, 0};
   bool mesh_rebuild_one_workgroup = false;  // HK_DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP: the SAH build's top levels in one workgroup (A/B)
   const float4* d_prev_models = nullptr;  // 4 columns per instance, valid where DInstance::moved
   DevArray<uint32_t> d_noise;

@@ -39,6 +39,20 @@ uint32_t builder_instance_count(const hk_scene_builder* b);
 // the builder was finished by hk_scene_builder_finish_instances: its two trees are valid STAND-INS (index list halved recursively)
 // for a device-side build, not the reference's SAH trees - only hk_update_scene_instances may upload them
 bool builder_has_standin_trees(const hk_scene_builder* b);
+// meshes added by hk_scene_builder_add_mesh_deferred whose tree has not been built yet (their nodes are valid STAND-INS of the final size):
+// only hk_load_scene, which builds the trees on the device, may upload such a builder
+uint32_t builder_pending_mesh_count(const hk_scene_builder* b);
+uint32_t builder_mesh_count(const hk_scene_builder* b);
+bool builder_pending_mesh(const hk_scene_builder* b, uint32_t mesh_id, HkMeshIndex* index);  // index: filled in a finished builder
+// the final tree of a mesh (reference form, links local to the mesh) over its stand-in, in place; clears the mark
+int builder_store_mesh_nodes(hk_scene_builder* b, uint32_t mesh_id, const HkNode* nodes, uint32_t count);
+int builder_complete_mesh_on_host(hk_scene_builder* b, uint32_t mesh_id);  // ... built by the host (hk_scene_builder_rebuild_mesh_tree's tree)
+#define HK_NO_PENDING_MESHES(b)                                                                                                      \
+  HK_REQUIRE(::hk::builder_pending_mesh_count(b) == 0u, HK_E_NOT_READY,                                                              \
+             "the builder holds %u deferred meshes whose trees are stand-ins (hk_scene_builder_add_mesh_deferred): build them with " \
+             "hk_scene_builder_build_pending_mesh_trees, or use hk_load_scene, which builds them on the device",                     \
+             ::hk::builder_pending_mesh_count(b))
+int upload_scene_unchecked(hk_ctx* c, const hk_scene_builder* b);            // hk_upload_scene without the checks of the builder's trees (scene_layout.hip)
 int upload_scene_instances_unchecked(hk_ctx* c, const hk_scene_builder* b);  // hk_upload_scene_instances without that check (context.hip)
 bool builder_instance_decl(const hk_scene_builder* b, uint32_t i, InstanceDecl* out);
 // what hk_scene_builder_finish does to the PreviousMeshUniform bookkeeping, without building anything

@@ -129,6 +129,12 @@ struct MeshTree {
   float4 *node_lo, *node_hi;                       // per tree node (2n - 1)
   float4 *tri_lo, *tri_hi;                         // per triangle: its box
 };
+// One mesh of a forest build (kernels_scene.hip launch_forest_build; hk_load_scene): the trees of many meshes built together
+struct ForestMesh {
+  uint32_t tri_begin, n_tris;   // the mesh's positions in the batch: the meshes of a batch tile [0, all its triangles)
+  uint32_t primitive;           // its first triangle in the triangle planes
+  uint32_t node_offset;         // its first node in the mesh-level node array
+};
 struct RefitScene {
   DInstance* instances;
   float4* prev_models;                   // 4 columns per instance
@@ -324,7 +330,14 @@ size_t lbvh_scratch_bytes(uint32_t n, size_t* sort_temp_bytes);
 // ordering 0 stays left before right in either mode); `one_workgroup_top`: the SAH build's top levels in one workgroup at any n (A/B)
 int launch_tree_build(hipStream_t st, int mode /* 0 LBVH, 1 the reference's binned SAH */, bool light, const hkd::RefitScene& s, uint32_t n, const float4* box_lo,
                       const float4* box_hi, void* scratch, float4* lo, float4* hi, uint32_t stride, uint32_t orderings, size_t ord_stride = 0,
-                      const hkd::MeshTree* keep = nullptr, bool one_workgroup_top = false);
+                      const hkd::MeshTree* keep = nullptr, bool one_workgroup_top = false, bool mesh_tree = false, uint32_t* launches = nullptr);
+// `mesh_tree`: a mesh tree without a MeshTree to keep (hk_load_scene); `launches`: the kernel launches of the build are added to it.
+// The trees of MANY meshes in one build (`nodes` = the mesh-level node array, interleaved lo / hi pairs, `ord_stride` float4 between its
+// orderings): the number of launches does not depend on the number of meshes.  Every mesh below hkd's SAH_WIDE_MIN triangles.
+size_t forest_scratch_bytes(uint32_t n_tris, uint32_t n_meshes, int mode);
+int launch_forest_build(hipStream_t st, int mode /* 0 LBVH, 1 the reference's binned SAH */, const hkd::ForestMesh* meshes /* host */, uint32_t n_meshes, uint32_t n_tris,
+                        const float4* v0, const float4* v1, const float4* v2, void* scratch, float4* nodes, uint32_t orderings, size_t ord_stride, uint32_t* launches);
+constexpr uint32_t HK_FOREST_MESH_MAX_TRIANGLES = 32767u;  // (SAH_WIDE_MIN - 1: from there a mesh has the whole chip to itself)
 // mesh deformation: the BLAS refit of one mesh tree into `orderings` orderings of its flat layout (`lo` = its node 0 of ordering 0,
 // interleaved lo / hi pairs, `ord_stride` float4 between orderings); the propagation of a new mesh box (`box`: 6 order-preserving
 // words, kernels_deform.hip) to the instances `ids` (emitters first) of the mesh, their emitters (`records`: device scratch, one per

@@ -463,6 +463,7 @@ __global__ __launch_bounds__(256) void k_lbvh_boxes(RefitScene s, LbvhBuffers b)
   b.node_hi[b.n - 1u + j] = make_float4(mx.x, mx.y, mx.z, 0.0f);
   if (b.n == 1u) return;
   uint32_t p = b.leaf_parent[j];
+  if (p == HK_U32_MAX) return;  // (a forest build: the only leaf of a one-triangle tree)
   for (;;) {
     __threadfence();
     if (atomicAdd(&b.arrived[p], 1u) == 0u) return;  // the sibling subtree is not finished: its thread continues from here
@@ -1125,6 +1126,210 @@ __global__ __launch_bounds__(256) void k_sahw_finish(LbvhBuffers b, SahBuffers q
   if (i < b.n && q.item_node[side][i] == SAH_DONE) b.ids_sorted[i] = q.order[side][i];
 }
 
+// ------------------------------------------------------------------ a FOREST of mesh trees in one build (hk_load_scene)
+// A scene arrives with thousands of small meshes: one tree build per mesh is six to forty launches each.  Here the triangles of all the
+// meshes of a batch form ONE shape array (mesh m owns the positions [tri_begin, tri_begin + n_tris)), and the trees share the arrays of a
+// single build: tree nodes are numbered in one space (internal nodes below n - 1, the leaf at position j is n - 1 + j, n = all the
+// triangles of the batch), every mesh's root has no parent, and nothing ever crosses a mesh boundary because a node's segment never
+// does.  The binned-SAH trees are sah_levels' - the root of mesh m is internal node m; a mesh above SAH_SUBTREE triangles has its top
+// levels split by a workgroup of its own (k_forest_tops), then ALL nodes of at most SAH_SUBTREE triangles, whole small meshes among
+// them, are built by k_sah_subtrees at once.  The Morton-order trees sort all meshes' codes in one segmented sort.  Boxes bottom-up are
+// k_lbvh_boxes; k_forest_emit is k_lbvh_emit with the mesh's own node range as the target and the triangle index local to the mesh.
+// The number of launches depends on the mode, not on the number of meshes.
+constexpr uint32_t FOREST_UNUSED = 0xFEFEFEFEu;  // parent[] of an internal node id no tree uses: the array is filled with the BYTE 0xFE
+namespace {
+__device__ __forceinline__ float forest_leaf_min(float a, float b) {  // kernels_deform.hip leaf_min: IEEE minNum with -0 < +0
+  if (a != a) return b;
+  if (b != b) return a;
+  if (a == b) return signbit(a) ? a : b;
+  return a < b ? a : b;
+}
+__device__ __forceinline__ float forest_leaf_max(float a, float b) {
+  if (a != a) return b;
+  if (b != b) return a;
+  if (a == b) return signbit(a) ? b : a;
+  return a > b ? a : b;
+}
+}  // namespace
+// one workgroup per mesh: the triangle boxes (k_mesh_triangle_boxes' arithmetic), the identity order, the mesh of every position, the root
+__global__ __launch_bounds__(256) void k_forest_setup(const ForestMesh* __restrict__ meshes, uint32_t n_meshes, const float4* __restrict__ v0, const float4* __restrict__ v1,
+                                                      const float4* __restrict__ v2, float4* __restrict__ tri_lo, float4* __restrict__ tri_hi, uint32_t* __restrict__ item_mesh,
+                                                      LbvhBuffers b, SahBuffers q, uint32_t sah) {
+  const uint32_t m = blockIdx.x;
+  if (m >= n_meshes) return;
+  const ForestMesh fm = meshes[m];
+  for (uint32_t i = threadIdx.x; i < fm.n_tris; i += 256u) {
+    const uint32_t pos = fm.tri_begin + i;
+    const float4 a = v0[fm.primitive + i], c = v1[fm.primitive + i], d = v2[fm.primitive + i];
+    tri_lo[pos] = make_float4(forest_leaf_min(a.x, forest_leaf_min(c.x, d.x)), forest_leaf_min(a.y, forest_leaf_min(c.y, d.y)), forest_leaf_min(a.z, forest_leaf_min(c.z, d.z)), 0.0f);
+    tri_hi[pos] = make_float4(forest_leaf_max(a.x, forest_leaf_max(c.x, d.x)), forest_leaf_max(a.y, forest_leaf_max(c.y, d.y)), forest_leaf_max(a.z, forest_leaf_max(c.z, d.z)), 0.0f);
+    item_mesh[pos] = m;
+    if (sah) {
+      q.order[0][pos] = pos;
+      q.item_node[0][pos] = fm.n_tris > 1u ? m : SAH_DONE;
+    }
+    if (fm.n_tris == 1u) {  // a tree of one leaf: nothing to build
+      b.ids_sorted[pos] = pos;
+      b.leaf_parent[pos] = HK_U32_MAX;
+    }
+  }
+  if (!sah || threadIdx.x != 0u) return;
+  if (m == 0u) q.counters[0] = n_meshes;  // internal nodes allocated: the roots (counters[1], [2] were zeroed by the host)
+  if (fm.n_tris > 1u) {
+    b.first[m] = fm.tri_begin;
+    b.last[m] = fm.tri_begin + fm.n_tris - 1u;
+    b.parent[m] = HK_U32_MAX;
+    if (fm.n_tris <= SAH_SUBTREE) {
+      q.node_level[m] = SAH_DONE;
+      q.roots[atomicAdd(&q.counters[1], 1u)] = m;
+    }
+  }
+}
+// the top levels of every mesh above SAH_SUBTREE triangles, one workgroup each (k_sah_build's part); the range ends on ping-pong side 0,
+// where k_sah_subtrees starts from
+__global__ __launch_bounds__(1024) void k_forest_tops(const ForestMesh* __restrict__ meshes, const uint32_t* __restrict__ tops, LbvhBuffers b, SahBuffers q) {
+  const RefitScene none{};
+  const uint32_t m = tops[blockIdx.x];
+  const ForestMesh fm = meshes[m];
+  const uint32_t r0 = fm.tri_begin, r1 = fm.tri_begin + fm.n_tris;
+  const uint32_t cur = sah_levels<false>(none, b, q, r0, r1, m, 0u, 0u, SAH_SUBTREE);
+  for (uint32_t i = r0 + threadIdx.x; i < r1; i += 1024u) {
+    const uint32_t node = q.item_node[cur][i], shape = q.order[cur][i];
+    if (cur != 0u) {
+      q.item_node[0][i] = node;
+      q.order[0][i] = shape;
+    }
+    if (node == SAH_DONE) b.ids_sorted[i] = shape;  // leaves fixed at this stage are final
+  }
+}
+// Morton-order trees: the centre bounds of every mesh (one workgroup each), the codes inside them, Karras' hierarchy per segment
+__global__ __launch_bounds__(256) void k_forest_lbvh_bounds(const ForestMesh* __restrict__ meshes, LbvhBuffers b, float* __restrict__ mesh_bounds) {
+  __shared__ float red[6][4];
+  const ForestMesh fm = meshes[blockIdx.x];
+  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (uint32_t i = threadIdx.x; i < fm.n_tris; i += 256u) {
+    const float4 lo = b.box_lo[fm.tri_begin + i], hi = b.box_hi[fm.tri_begin + i];
+    const float c[3] = {lo.x + hi.x, lo.y + hi.y, lo.z + hi.z};
+    for (int k = 0; k < 3; ++k) {
+      mn[k] = fminf(mn[k], c[k]);
+      mx[k] = fmaxf(mx[k], c[k]);
+    }
+  }
+  for (int k = 0; k < 3; ++k)
+    for (int off = 32; off > 0; off >>= 1) {
+      mn[k] = fminf(mn[k], __shfl_xor(mn[k], off));
+      mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], off));
+    }
+  if ((threadIdx.x & 63u) == 0u)
+    for (int k = 0; k < 3; ++k) {
+      red[k][threadIdx.x >> 6] = mn[k];
+      red[3 + k][threadIdx.x >> 6] = mx[k];
+    }
+  __syncthreads();
+  if (threadIdx.x < 6u) {
+    float v = red[threadIdx.x][0];
+    for (int w = 1; w < 4; ++w) v = threadIdx.x < 3u ? fminf(v, red[threadIdx.x][w]) : fmaxf(v, red[threadIdx.x][w]);
+    mesh_bounds[6u * blockIdx.x + threadIdx.x] = v;
+  }
+}
+__global__ __launch_bounds__(256) void k_forest_lbvh_codes(const uint32_t* __restrict__ item_mesh, const float* __restrict__ mesh_bounds, LbvhBuffers b) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= b.n) return;
+  const float* bounds = mesh_bounds + 6u * item_mesh[i];
+  const float4 lo = b.box_lo[i], hi = b.box_hi[i];
+  const float c[3] = {lo.x + hi.x, lo.y + hi.y, lo.z + hi.z};
+  uint32_t qv[3];
+  for (int k = 0; k < 3; ++k) {
+    const float ext = bounds[3 + k] - bounds[k];
+    const float t = ext > 0.0f ? (c[k] - bounds[k]) / ext : 0.0f;
+    qv[k] = (uint32_t)fminf(fmaxf(t * 1024.0f, 0.0f), 1023.0f);
+  }
+  b.codes[i] = (expand_bits(qv[0]) << 2) | (expand_bits(qv[1]) << 1) | expand_bits(qv[2]);
+  b.ids[i] = i;
+}
+// k_lbvh_hierarchy inside the segment of the position's mesh: internal node i of a mesh is tree node tri_begin + i
+__global__ __launch_bounds__(256) void k_forest_lbvh_hierarchy(const ForestMesh* __restrict__ meshes, const uint32_t* __restrict__ item_mesh, LbvhBuffers b) {
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+  if (g >= b.n) return;
+  const ForestMesh fm = meshes[item_mesh[g]];
+  const int n = (int)fm.n_tris, i = (int)(g - fm.tri_begin);
+  if (i >= n - 1) return;
+  const uint32_t base = fm.tri_begin, leaf0 = b.n - 1u + fm.tri_begin;
+  const uint32_t* codes = b.codes_sorted + base;
+  const int d = (lbvh_delta(codes, n, i, i + 1) - lbvh_delta(codes, n, i, i - 1)) >= 0 ? 1 : -1;
+  const int dmin = lbvh_delta(codes, n, i, i - d);
+  int lmax = 2;
+  while (lbvh_delta(codes, n, i, i + lmax * d) > dmin) lmax <<= 1;
+  int l = 0;
+  for (int t = lmax >> 1; t >= 1; t >>= 1)
+    if (lbvh_delta(codes, n, i, i + (l + t) * d) > dmin) l += t;
+  const int j = i + l * d;
+  const int dnode = lbvh_delta(codes, n, i, j);
+  int sft = 0;
+  for (int t = (l + 1) >> 1;; t = (t + 1) >> 1) {
+    if (lbvh_delta(codes, n, i, i + (sft + t) * d) > dnode) sft += t;
+    if (t <= 1) break;
+  }
+  const int gamma = i + sft * d + min(d, 0);
+  const int lo = min(i, j), hi = max(i, j);
+  const bool l_leaf = lo == gamma, r_leaf = hi == gamma + 1;
+  const uint32_t lc = l_leaf ? leaf0 + (uint32_t)gamma : base + (uint32_t)gamma;
+  const uint32_t rc = r_leaf ? leaf0 + (uint32_t)gamma + 1u : base + (uint32_t)gamma + 1u;
+  b.left[g] = lc;
+  b.right[g] = rc;
+  b.first[g] = base + (uint32_t)lo;
+  b.last[g] = base + (uint32_t)hi;
+  if (l_leaf) b.leaf_parent[base + (uint32_t)gamma] = g; else b.parent[lc] = g;
+  if (r_leaf) b.leaf_parent[base + (uint32_t)gamma + 1u] = g; else b.parent[rc] = g;
+  if (i == 0) b.parent[g] = HK_U32_MAX;
+}
+// k_lbvh_emit for a forest: every tree node except the roots writes the navigator in front of its subtree into ITS mesh's node range,
+// links local to that range; leaves also write their own slot.  parent[] was filled with FOREST_UNUSED before the build
+__global__ __launch_bounds__(256) void k_forest_emit(const ForestMesh* __restrict__ meshes, const uint32_t* __restrict__ item_mesh, LbvhBuffers b, float4* nodes,
+                                                     size_t ord_stride /* float4 between orderings */, uint32_t orderings) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x, n = b.n, total = 2u * n - 1u;
+  if (t >= total * orderings) return;
+  const uint32_t o = t / total, v = t - o * total;
+  const bool leaf = v >= n - 1u;
+  uint32_t p;
+  if (leaf) {
+    p = b.leaf_parent[v - (n - 1u)];
+  } else {
+    p = b.parent[v];
+    if (p == FOREST_UNUSED || p == HK_U32_MAX) return;  // no such node; a root has no navigator
+  }
+  const ForestMesh fm = meshes[item_mesh[leaf ? v - (n - 1u) : b.first[v]]];
+  float4* nlo = nodes + (size_t)o * ord_stride + 2u * (size_t)fm.node_offset;
+  float4* nhi = nlo + 1;
+  const uint32_t shape = leaf ? b.ids_sorted[v - (n - 1u)] - fm.tri_begin : 0u;
+  const float4 blo = b.node_lo[v], bhi = b.node_hi[v];
+  if (fm.n_tris == 1u) {  // flatten_custom of a single leaf: the leaf alone
+    nlo[0] = make_float4(blo.x, blo.y, blo.z, u2f(HK_LEAF | shape));
+    nhi[0] = make_float4(bhi.x, bhi.y, bhi.z, u2f(1u));
+    return;
+  }
+  auto leaves_of = [&](uint32_t node) { return node >= n - 1u ? 1u : b.last[node] - b.first[node] + 1u; };
+  uint32_t start = 0u, c = v;
+  while (p < n - 1u) {  // (up to the root, whose parent is HK_U32_MAX)
+    const bool right_first = (b.swap[p] >> o) & 1u;
+    const uint32_t first_child = right_first ? b.right[p] : b.left[p];
+    start += (c == first_child) ? 1u : 2u + (3u * leaves_of(first_child) - 2u);
+    c = p;
+    p = b.parent[p];
+  }
+  const uint32_t size = 3u * leaves_of(v) - 2u;
+  if (start == 0u || start > 3u * fm.n_tris - 2u - size) return;  // (never outside the mesh's own range, whatever the arrays hold)
+  if (leaf) {  // folded navigator (scene_layout.hip fold_leaf_navigators) + the leaf slot
+    nlo[2u * (size_t)(start - 1u)] = make_float4(blo.x, blo.y, blo.z, u2f(HK_LEAF | shape));
+    nhi[2u * (size_t)(start - 1u)] = make_float4(bhi.x, bhi.y, bhi.z, u2f(start + 1u));
+    nlo[2u * (size_t)start] = make_float4(blo.x, blo.y, blo.z, u2f(HK_LEAF | shape));
+    nhi[2u * (size_t)start] = make_float4(bhi.x, bhi.y, bhi.z, u2f(start + 1u));
+  } else {
+    nlo[2u * (size_t)(start - 1u)] = make_float4(blo.x, blo.y, blo.z, u2f(start));
+    nhi[2u * (size_t)(start - 1u)] = make_float4(bhi.x, bhi.y, bhi.z, u2f(start + size));
+  }
+}
+
 // ------------------------------------------------------------------ a deformed mesh's new box, carried to its instances
 // One thread per instance of the mesh: the mesh box (order-preserving words of kernels_deform.hip k_mesh_*) as bevy's Aabb, the world
 // AABB and emitter record with k_refit_instances' arithmetic (instance_world_box, emitter_position_radius: keep both in step) - but the pose, its previous model and its `moved` flag stay as they are
@@ -1247,8 +1452,10 @@ size_t lbvh_scratch_bytes(uint32_t n, size_t* sort_temp_bytes) {
 // mode 0: LBVH (Morton order), mode 1: the reference's binned SAH (`bvh` 0.7.1).  `lo` / `hi` = the node array to overwrite,
 // `stride` float4 between consecutive nodes (2: interleaved pairs, 1: two planes)
 int launch_tree_build(hipStream_t st, int mode, bool light, const RefitScene& s, uint32_t n, const float4* box_lo, const float4* box_hi, void* scratch, float4* lo,
-                      float4* hi, uint32_t stride, uint32_t orderings, size_t ord_stride, const MeshTree* keep, bool one_workgroup_top) {
+                      float4* hi, uint32_t stride, uint32_t orderings, size_t ord_stride, const MeshTree* keep, bool one_workgroup_top, bool mesh_tree, uint32_t* launches) {
   if (n == 0) return 0;
+  mesh_tree = mesh_tree || keep;
+  uint32_t launched = 2u;  // boxes, emit
   size_t temp = 0;
   (void)lbvh_scratch_bytes(n, &temp);
   const size_t nn = ((size_t)n + 63) & ~(size_t)63;
@@ -1257,7 +1464,7 @@ int launch_tree_build(hipStream_t st, int mode, bool light, const RefitScene& s,
   b.n = n;
   b.box_lo = box_lo;
   b.box_hi = box_hi;
-  b.keep_order0 = (mode == 1 || keep) ? 1u : 0u;  // (a mesh tree's ordering 0 is what its refit keeps: left before right)
+  b.keep_order0 = (mode == 1 || mesh_tree) ? 1u : 0u;  // (a mesh tree's ordering 0 is what its refit keeps: left before right)
   b.bounds = (float*)p; p += 256;
   void* sort_temp = p; p += temp;
   auto u32 = [&]() { uint32_t* q = (uint32_t*)p; p += nn * 4; return q; };
@@ -1284,12 +1491,14 @@ int launch_tree_build(hipStream_t st, int mode, bool light, const RefitScene& s,
     q.counters = (uint32_t*)b.bounds;                        // (256 B, unused by this mode)
     uint32_t* chunk_counts = (uint32_t*)p; p += (size_t)((n + 1023u) / 1024u) * 12 * 4;
     const dim3 subtrees((unsigned)std::min<size_t>(std::max<size_t>(n / 2, 1), 4096));
-    if (keep && n >= SAH_WIDE_MIN && !one_workgroup_top) {  // (mesh trees only: the instance tree and the light tree keep the one-workgroup top at any size)
+    launched += n > SAH_SUBTREE ? 2u : 1u;
+    if (mesh_tree && n >= SAH_WIDE_MIN && !one_workgroup_top) {  // (mesh trees only: the instance tree and the light tree keep the one-workgroup top at any size)
       // the levels a balanced tree needs down to SAH_SUBTREE shapes per node, and six more for the lopsided splits of a real one
       uint32_t levels = 6u;
       while (((size_t)SAH_SUBTREE << (levels - 6u)) < n) ++levels;
       levels = std::min(levels, SAH_WIDE_MAX_LEVELS);
       const dim3 chunks((n + 1023u) / 1024u);
+      launched += 1u + 5u * levels;
       hipLaunchKernelGGL(k_sahw_setup, chunks, dim3(1024), 0, st, b, q, levels);
       for (uint32_t level = 0; level < levels; ++level) {
         const dim3 per_node((unsigned)std::min<size_t>(((size_t)1 << std::min(level, 20u)) / 256 + 1, 256));  // (at most 2^level nodes)
@@ -1318,7 +1527,9 @@ int launch_tree_build(hipStream_t st, int mode, bool light, const RefitScene& s,
     }
     if (rocprim::radix_sort_pairs(sort_temp, temp, (const uint32_t*)b.codes, b.codes_sorted, (const uint32_t*)b.ids, b.ids_sorted, (size_t)n, 0, 30, st) != hipSuccess) return 1;
     if (n > 1) hipLaunchKernelGGL(k_lbvh_hierarchy, dim3((n + 254u) / 256u), dim3(256), 0, st, b);
+    launched += 4u;  // (the sort counted as one)
   }
+  if (launches) *launches += launched;
   if (light) hipLaunchKernelGGL((k_lbvh_boxes<true>), per_shape, dim3(256), 0, st, s, b);
   else hipLaunchKernelGGL((k_lbvh_boxes<false>), per_shape, dim3(256), 0, st, s, b);
   const uint32_t threads = (2u * n - 1u) * orderings;
@@ -1331,6 +1542,106 @@ int launch_tree_build(hipStream_t st, int mode, bool light, const RefitScene& s,
     if (ni) (void)hipMemcpyAsync(keep->leaf_parent, b.leaf_parent, (size_t)n * 4, hipMemcpyDeviceToDevice, st);
     (void)hipMemcpyAsync(keep->leaf_shape, b.ids_sorted, (size_t)n * 4, hipMemcpyDeviceToDevice, st);
   }
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+// ---- a forest of mesh trees (hk_load_scene): scratch of one batch, and the build of every mesh of the batch into its own node range
+static_assert(HK_FOREST_MESH_MAX_TRIANGLES + 1u == SAH_WIDE_MIN, "the forest takes every mesh below the multi-workgroup build");
+static size_t forest_sort_temp(uint32_t n_tris, uint32_t n_meshes) {
+  size_t temp = 0;
+  (void)rocprim::segmented_radix_sort_pairs(nullptr, temp, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, n_tris, n_meshes,
+                                            (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0, 30);
+  return (temp + 255) & ~(size_t)255;
+}
+size_t forest_scratch_bytes(uint32_t n_tris, uint32_t n_meshes, int mode) {
+  const size_t nn = ((size_t)n_tris + 63) & ~(size_t)63, mm = ((size_t)n_meshes + 63) & ~(size_t)63;
+  size_t bytes = 256 + nn * (12 * 4) /* the arrays of launch_tree_build */ + 2 * nn * 2 * 16 /* node boxes */ + 2 * nn * 16 /* triangle boxes */ + nn * 4 /* item_mesh */ +
+                 mm * (sizeof(ForestMesh) + 3 * 4 /* tops, segment offsets */ + 6 * 4 /* centre bounds */);
+  if (mode == 1) bytes += nn * (4 + 4 + 2 * 4 + 54 * 4 + 4 * 4 + 14 * 4 + 2 * 4);
+  else bytes += forest_sort_temp(n_tris, n_meshes);
+  return bytes;
+}
+int launch_forest_build(hipStream_t st, int mode, const ForestMesh* meshes, uint32_t n_meshes, uint32_t n_tris, const float4* v0, const float4* v1, const float4* v2, void* scratch,
+                        float4* nodes, uint32_t orderings, size_t ord_stride, uint32_t* launches) {
+  if (n_meshes == 0 || n_tris == 0) return 0;
+  const uint32_t n = n_tris;
+  const size_t nn = ((size_t)n + 63) & ~(size_t)63, mm = ((size_t)n_meshes + 63) & ~(size_t)63;
+  uint8_t* p = (uint8_t*)scratch;
+  LbvhBuffers b;
+  b.n = n;
+  b.keep_order0 = 1u;  // (a mesh tree's ordering 0 is what its refit keeps: left before right)
+  b.bounds = (float*)p; p += 256;
+  auto u32 = [&](size_t count) { uint32_t* q = (uint32_t*)p; p += count * 4; return q; };
+  b.codes = u32(nn); b.codes_sorted = u32(nn); b.ids = u32(nn); b.ids_sorted = u32(nn);
+  b.parent = u32(nn); b.left = u32(nn); b.right = u32(nn); b.first = u32(nn); b.last = u32(nn); b.leaf_parent = u32(nn); b.arrived = u32(nn);
+  b.swap = (uint8_t*)u32(nn);
+  b.node_lo = (float4*)p; p += 2 * nn * 16;
+  b.node_hi = (float4*)p; p += 2 * nn * 16;
+  float4* tri_lo = (float4*)p; p += nn * 16;
+  float4* tri_hi = (float4*)p; p += nn * 16;
+  b.box_lo = tri_lo;
+  b.box_hi = tri_hi;
+  uint32_t* item_mesh = u32(nn);
+  ForestMesh* d_meshes = (ForestMesh*)p; p += mm * sizeof(ForestMesh);
+  uint32_t* d_tops = u32(mm);
+  uint32_t* d_seg_begin = u32(mm);
+  uint32_t* d_seg_end = u32(mm);
+  float* d_mesh_bounds = (float*)u32(6 * mm);
+  // (pageable sources: the copies have left the host buffers when the calls return)
+  if (hipMemcpyAsync(d_meshes, meshes, (size_t)n_meshes * sizeof(ForestMesh), hipMemcpyHostToDevice, st) != hipSuccess) return 1;
+  (void)hipMemsetAsync(b.arrived, 0, nn * 4, st);
+  (void)hipMemsetAsync(b.swap, 0, nn * 4, st);
+  (void)hipMemsetAsync(b.parent, (int)(FOREST_UNUSED & 0xFFu), nn * 4, st);
+  (void)hipMemsetAsync(b.leaf_parent, 0xFF, nn * 4, st);
+  (void)hipMemsetAsync(b.bounds, 0, 256, st);        // (the SAH build's counters)
+  const RefitScene none{};
+  const dim3 per_shape((n + 255u) / 256u);
+  uint32_t launched = 0u;
+  SahBuffers q{};
+  if (mode == 1) {
+    q.order[0] = b.codes; q.order[1] = b.codes_sorted;  // (the Morton arrays are free in this mode)
+    q.item_node[0] = b.ids; q.item_node[1] = u32(nn);
+    q.item_bucket = (uint8_t*)u32(nn);
+    q.active[0] = u32(nn);
+    q.active[1] = u32(nn);
+    q.acc = u32(nn * 54);
+    q.split = (float*)u32(nn * 4);
+    q.offsets = u32(nn * 14);
+    q.node_level = u32(nn);
+    q.roots = u32(nn);
+    q.counters = (uint32_t*)b.bounds;
+    std::vector<uint32_t> tops;
+    for (uint32_t m = 0; m < n_meshes; ++m)
+      if (meshes[m].n_tris > SAH_SUBTREE) tops.push_back(m);
+    if (!tops.empty() && hipMemcpyAsync(d_tops, tops.data(), tops.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return 1;
+    hipLaunchKernelGGL(k_forest_setup, dim3(n_meshes), dim3(256), 0, st, (const ForestMesh*)d_meshes, n_meshes, v0, v1, v2, tri_lo, tri_hi, item_mesh, b, q, 1u);
+    if (!tops.empty()) hipLaunchKernelGGL(k_forest_tops, dim3((unsigned)tops.size()), dim3(1024), 0, st, (const ForestMesh*)d_meshes, (const uint32_t*)d_tops, b, q);
+    hipLaunchKernelGGL((k_sah_subtrees<false>), dim3((unsigned)std::min<size_t>(std::max<size_t>(n / 2, 1), 4096)), dim3(1024), 0, st, none, b, q);
+    launched += tops.empty() ? 2u : 3u;
+  } else {
+    void* sort_temp = p;
+    size_t temp = forest_sort_temp(n, n_meshes);
+    std::vector<uint32_t> seg(2 * (size_t)n_meshes);
+    for (uint32_t m = 0; m < n_meshes; ++m) {
+      seg[m] = meshes[m].tri_begin;
+      seg[n_meshes + m] = meshes[m].tri_begin + meshes[m].n_tris;
+    }
+    if (hipMemcpyAsync(d_seg_begin, seg.data(), (size_t)n_meshes * 4, hipMemcpyHostToDevice, st) != hipSuccess) return 1;
+    if (hipMemcpyAsync(d_seg_end, seg.data() + n_meshes, (size_t)n_meshes * 4, hipMemcpyHostToDevice, st) != hipSuccess) return 1;
+    hipLaunchKernelGGL(k_forest_setup, dim3(n_meshes), dim3(256), 0, st, (const ForestMesh*)d_meshes, n_meshes, v0, v1, v2, tri_lo, tri_hi, item_mesh, b, q, 0u);
+    hipLaunchKernelGGL(k_forest_lbvh_bounds, dim3(n_meshes), dim3(256), 0, st, (const ForestMesh*)d_meshes, b, d_mesh_bounds);
+    hipLaunchKernelGGL(k_forest_lbvh_codes, per_shape, dim3(256), 0, st, (const uint32_t*)item_mesh, (const float*)d_mesh_bounds, b);
+    if (rocprim::segmented_radix_sort_pairs(sort_temp, temp, (const uint32_t*)b.codes, b.codes_sorted, (const uint32_t*)b.ids, b.ids_sorted, n, n_meshes,
+                                            (const uint32_t*)d_seg_begin, (const uint32_t*)d_seg_end, 0, 30, st) != hipSuccess)
+      return 1;
+    hipLaunchKernelGGL(k_forest_lbvh_hierarchy, per_shape, dim3(256), 0, st, (const ForestMesh*)d_meshes, (const uint32_t*)item_mesh, b);
+    launched += 5u;  // (the sort counted as one)
+  }
+  hipLaunchKernelGGL((k_lbvh_boxes<false>), per_shape, dim3(256), 0, st, none, b);
+  const uint32_t threads = (2u * n - 1u) * orderings;
+  hipLaunchKernelGGL(k_forest_emit, dim3((threads + 255u) / 256u), dim3(256), 0, st, (const ForestMesh*)d_meshes, (const uint32_t*)item_mesh, b, nodes, ord_stride, orderings);
+  launched += 2u;
+  if (launches) *launches += launched;
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

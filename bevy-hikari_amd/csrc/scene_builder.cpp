@@ -248,6 +248,7 @@ struct BuilderMesh {
   std::vector<HkPrimitive> primitives;
   std::vector<HkNode> nodes;
   float aabb_center[3], aabb_half[3];
+  bool pending = false;  // added by hk_scene_builder_add_mesh_deferred: `nodes` is a valid stand-in of the final size until the tree is built
 };
 struct BuilderInstance {
   uint32_t mesh, material;
@@ -424,8 +425,8 @@ int hk_scene_builder_create(hk_scene_builder** out) {
 }
 void hk_scene_builder_destroy(hk_scene_builder* b) { delete b; }
 
-int hk_scene_builder_add_mesh(hk_scene_builder* b, const float* positions, const float* normals, const float* uvs, uint32_t n_vertices,
-                              const uint32_t* indices, uint32_t n_indices, uint32_t topology, uint32_t* mesh_id) {
+static int add_mesh_impl(hk_scene_builder* b, const float* positions, const float* normals, const float* uvs, uint32_t n_vertices, const uint32_t* indices,
+                         uint32_t n_indices, uint32_t topology, uint32_t* mesh_id, bool deferred) {
   HK_REQUIRE(b, HK_E_INVALID, "builder is NULL");
   // mod.rs:383-397: position, normal and uv0 are all required
   HK_REQUIRE(positions && normals && uvs && n_vertices > 0, HK_E_INVALID, "mesh needs position, normal and uv attributes");
@@ -485,11 +486,27 @@ int hk_scene_builder_add_mesh(hk_scene_builder* b, const float* positions, const
     boxes.insert(boxes.end(), bx.mn, bx.mn + 3);
     boxes.insert(boxes.end(), bx.mx, bx.mx + 3);
   }
-  mesh.nodes = build_flat_bvh(boxes);  // mod.rs:458-459
+  // mod.rs:458-459; a deferred mesh gets a valid stand-in of the final size (any binary tree over n shapes has 3n - 2 nodes)
+  mesh.nodes = deferred ? build_flat_placeholder(boxes) : build_flat_bvh(boxes);
+  mesh.pending = deferred;
   b->meshes.push_back(std::move(mesh));
   b->meshes_dirty = true;
   b->finished = false;
   if (mesh_id) *mesh_id = (uint32_t)b->meshes.size() - 1;
+  return HK_OK;
+}
+
+int hk_scene_builder_add_mesh(hk_scene_builder* b, const float* positions, const float* normals, const float* uvs, uint32_t n_vertices,
+                              const uint32_t* indices, uint32_t n_indices, uint32_t topology, uint32_t* mesh_id) {
+  return add_mesh_impl(b, positions, normals, uvs, n_vertices, indices, n_indices, topology, mesh_id, false);
+}
+int hk_scene_builder_add_mesh_deferred(hk_scene_builder* b, const float* positions, const float* normals, const float* uvs, uint32_t n_vertices,
+                                       const uint32_t* indices, uint32_t n_indices, uint32_t topology, uint32_t* mesh_id) {
+  return add_mesh_impl(b, positions, normals, uvs, n_vertices, indices, n_indices, topology, mesh_id, true);
+}
+int hk_scene_builder_pending_mesh_trees(const hk_scene_builder* b, uint32_t* count) {
+  HK_REQUIRE(b && count, HK_E_INVALID, "NULL argument");
+  *count = builder_pending_mesh_count(b);
   return HK_OK;
 }
 
@@ -611,10 +628,7 @@ int hk_scene_builder_set_mesh_vertices(hk_scene_builder* b, uint32_t mesh_id, co
 // The host twin of the device rebuild (mesh_deform.hip hk_rebuild_mesh_tree, HK_TREE_SAH): the tree hk_scene_builder_add_mesh would
 // build over the mesh's CURRENT triangles - `bvh` 0.7.1 BVH::build over their boxes, formed with add_mesh's arithmetic - and then the
 // canonical navigator boxes of refit_nodes, so that the result is what the device writes and what a later refit leaves alone.
-int hk_scene_builder_rebuild_mesh_tree(hk_scene_builder* b, uint32_t mesh_id) {
-  HK_REQUIRE(b, HK_E_INVALID, "builder is NULL");
-  HK_REQUIRE(mesh_id < b->meshes.size(), HK_E_INVALID, "unknown mesh id");
-  const BuilderMesh& mesh = b->meshes[mesh_id];
+static int canonical_mesh_tree(const BuilderMesh& mesh, std::vector<HkNode>& nodes) {
   std::vector<float> boxes;
   boxes.reserve(mesh.primitives.size() * 6);
   for (const HkPrimitive& p : mesh.primitives) {
@@ -623,11 +637,33 @@ int hk_scene_builder_rebuild_mesh_tree(hk_scene_builder* b, uint32_t mesh_id) {
     boxes.insert(boxes.end(), bx.mn, bx.mn + 3);
     boxes.insert(boxes.end(), bx.mx, bx.mx + 3);
   }
-  std::vector<HkNode> nodes = build_flat_bvh(boxes);  // (a copy: an error leaves the builder as it was)
+  nodes = build_flat_bvh(boxes);
   HK_REQUIRE(nodes.size() == mesh.nodes.size() && refit_nodes(nodes, mesh.primitives), HK_E_UNSUPPORTED, "the rebuilt mesh tree is not in the flatten_custom layout");
+  return HK_OK;
+}
+int hk_scene_builder_rebuild_mesh_tree(hk_scene_builder* b, uint32_t mesh_id) {
+  HK_REQUIRE(b, HK_E_INVALID, "builder is NULL");
+  HK_REQUIRE(mesh_id < b->meshes.size(), HK_E_INVALID, "unknown mesh id");
+  std::vector<HkNode> nodes;  // (a copy: an error leaves the builder as it was)
+  const int rc = canonical_mesh_tree(b->meshes[mesh_id], nodes);
+  if (rc) return rc;
   b->meshes[mesh_id].nodes.swap(nodes);
+  b->meshes[mesh_id].pending = false;  // (a deferred mesh: this is its tree)
   b->meshes_dirty = true;
   b->finished = false;
+  return HK_OK;
+}
+
+// The host completion of the deferred meshes (hk_scene_builder_add_mesh_deferred): per pending mesh the tree of
+// hk_scene_builder_rebuild_mesh_tree, written over the stand-in IN PLACE - the mesh's own nodes and, in a finished builder, its range of
+// the concatenated array; the node count does not depend on the tree, so no offset moves and a finished builder stays finished.
+int hk_scene_builder_build_pending_mesh_trees(hk_scene_builder* b) {
+  HK_REQUIRE(b, HK_E_INVALID, "builder is NULL");
+  for (uint32_t id = 0; id < b->meshes.size(); ++id) {
+    if (!b->meshes[id].pending) continue;
+    const int rc = builder_complete_mesh_on_host(b, id);
+    if (rc) return rc;
+  }
   return HK_OK;
 }
 
@@ -767,3 +803,34 @@ int hk_scene_builder_previous_transforms(const hk_scene_builder* b, const float*
 }
 
 }  // extern "C"
+
+namespace hk {
+uint32_t builder_pending_mesh_count(const hk_scene_builder* b) {
+  uint32_t n = 0;
+  if (b)
+    for (const BuilderMesh& m : b->meshes) n += m.pending ? 1u : 0u;
+  return n;
+}
+bool builder_pending_mesh(const hk_scene_builder* b, uint32_t mesh_id, HkMeshIndex* index) {
+  if (!b || mesh_id >= b->meshes.size() || !b->meshes[mesh_id].pending) return false;
+  if (index && !b->meshes_dirty && mesh_id < b->mesh_index.size()) *index = b->mesh_index[mesh_id];
+  return true;
+}
+uint32_t builder_mesh_count(const hk_scene_builder* b) { return b ? (uint32_t)b->meshes.size() : 0u; }
+int builder_store_mesh_nodes(hk_scene_builder* b, uint32_t mesh_id, const HkNode* nodes, uint32_t count) {
+  HK_REQUIRE(b && nodes && mesh_id < b->meshes.size(), HK_E_INVALID, "unknown mesh id");
+  BuilderMesh& m = b->meshes[mesh_id];
+  HK_REQUIRE(count == m.nodes.size(), HK_E_INVALID, "a tree of %u nodes for a mesh of %zu", count, m.nodes.size());
+  std::copy(nodes, nodes + count, m.nodes.begin());
+  if (!b->meshes_dirty && mesh_id < b->mesh_index.size()) std::copy(nodes, nodes + count, b->asset_nodes.begin() + b->mesh_index[mesh_id].node_offset);
+  m.pending = false;
+  return HK_OK;
+}
+int builder_complete_mesh_on_host(hk_scene_builder* b, uint32_t mesh_id) {
+  HK_REQUIRE(b && mesh_id < b->meshes.size(), HK_E_INVALID, "unknown mesh id");
+  std::vector<HkNode> nodes;
+  const int rc = canonical_mesh_tree(b->meshes[mesh_id], nodes);
+  if (rc) return rc;
+  return builder_store_mesh_nodes(b, mesh_id, nodes.data(), (uint32_t)nodes.size());
+}
+}  // namespace hk

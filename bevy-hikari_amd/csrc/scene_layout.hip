@@ -105,6 +105,8 @@ int build_static_region(hk_ctx* c, Blob& blob, size_t& off_nodes, size_t& off_v0
   std::vector<std::pair<uint32_t, uint32_t>> ranges;  // distinct mesh ranges
   {
     std::vector<uint8_t> done(n_nodes + 1, 0);
+    for (const auto& r : c->load_pending_ranges)  // (hk_load_scene: stand-ins the device overwrites in every ordering)
+      if (r.first < n_nodes) done[r.first] = 1;
     for (const HkInstance& in : c->instances) {
       if (in.mesh.node_count == 0 || done[in.mesh.node_offset]) continue;
       done[in.mesh.node_offset] = 1;
@@ -695,6 +697,11 @@ int hk_upload_scene(hk_ctx* c, const hk_scene_builder* b) {
   if (c) c->scene_epoch += 1;   // (scene memory is written: hk_context.hpp, primary-ray pipelining)
   HK_REQUIRE(c && b, HK_E_INVALID, "NULL argument");
   HK_NO_STANDINS(b);  // (frames from stand-in trees would differ silently in tie-breaks and visit order)
+  HK_NO_PENDING_MESHES(b);
+  return hk::upload_scene_unchecked(c, b);
+}
+}  // extern "C"
+int hk::upload_scene_unchecked(hk_ctx* c, const hk_scene_builder* b) {
   const HkVertex* v; const HkPrimitive* p; const HkNode *an, *in_, *en; const HkMaterial* m; const HkInstance* inst; const HkEmissive* em; const HkAliasEntry* al;
   uint32_t nv, np, nan_, nm, ni, nin, ne, nen, nal;
   int rc;
@@ -714,10 +721,12 @@ int hk_upload_scene(hk_ctx* c, const hk_scene_builder* b) {
   if ((rc = hk_scene_builder_previous_transforms(b, &pm, &npm))) return rc;
   return hk_upload_previous_transforms(c, pm, npm);
 }
+extern "C" {
 int hk_upload_scene_instances(hk_ctx* c, const hk_scene_builder* b) {
   if (c) c->scene_epoch += 1;   // (scene memory is written: hk_context.hpp, primary-ray pipelining)
   HK_REQUIRE(c && b, HK_E_INVALID, "NULL argument");
   HK_NO_STANDINS(b);
+  HK_NO_PENDING_MESHES(b);
   return hk::upload_scene_instances_unchecked(c, b);
 }
 }  // extern "C"

@@ -18,6 +18,7 @@ int hk_update_scene_instances(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode
   HK_REQUIRE(c && b, HK_E_INVALID, "NULL argument");
   HK_REQUIRE(tree_mode == HK_TREE_SAH || tree_mode == HK_TREE_LBVH, HK_E_INVALID, "unknown tree build mode %u", tree_mode);
   HK_REQUIRE(!c->meshes_deformed, HK_E_NOT_READY, "a mesh was deformed on the device: upload the host's mirror of it (hk_upload_scene) first");
+  HK_NO_PENDING_MESHES(b);  // (before the builder is finished: a refusal changes nothing)
   int rc;
   const bool trace = c->trace_update;
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };

@@ -479,6 +479,14 @@ class MultiEngine:
         for e in self.contexts:
             e.upload_scene(scene)   # (textures included)
 
+    def load_scene(self, builder, mode=F.TREE_SAH, textures=()):
+        """hk_multi_load_scene: the deferred meshes' trees are built once on the device and written back into `builder`, every band's
+        context ends with the same scene.  Returns the refreshed SceneData."""
+        for e in self.contexts:
+            e.upload_textures(list(textures))
+        self.api.call("multi_load_scene", self.h, builder.h, mode)
+        return builder.scene()
+
     def upload_noise(self, noise=None):
         for e in self.contexts:
             e.upload_noise(noise)

@@ -359,7 +359,10 @@ class SceneBuilder:
             self.api.raw("scene_builder_destroy")(self.h)
             self.h = None
 
-    def add_mesh(self, positions, normals, uvs, indices=None, topology=F.TOPOLOGY_TRIANGLE_LIST):
+    def add_mesh(self, positions, normals, uvs, indices=None, topology=F.TOPOLOGY_TRIANGLE_LIST, build_tree=True):
+        """hk_scene_builder_add_mesh; build_tree=False: hk_scene_builder_add_mesh_deferred - the mesh gets a stand-in tree of the final
+        size and the real one is built by Engine.load_scene (on the device) or build_pending_mesh_trees (on the host)."""
+        fn = "scene_builder_add_mesh" if build_tree else "scene_builder_add_mesh_deferred"
         pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
         nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
         uv = np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1, 2)
@@ -367,12 +370,22 @@ class SceneBuilder:
         self.mesh_vertices.append(len(pos))
         fp = lambda a: a.ctypes.data_as(C.POINTER(F.f32))
         if indices is None:
-            self.api.call("scene_builder_add_mesh", self.h, fp(pos), fp(nrm), fp(uv), len(pos), None, 0, topology, C.byref(out))
+            self.api.call(fn, self.h, fp(pos), fp(nrm), fp(uv), len(pos), None, 0, topology, C.byref(out))
         else:
             idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
-            self.api.call("scene_builder_add_mesh", self.h, fp(pos), fp(nrm), fp(uv), len(pos), idx.ctypes.data_as(C.POINTER(F.u32)), len(idx),
-                          topology, C.byref(out))
+            self.api.call(fn, self.h, fp(pos), fp(nrm), fp(uv), len(pos), idx.ctypes.data_as(C.POINTER(F.u32)), len(idx), topology, C.byref(out))
         return out.value
+
+    def pending_mesh_trees(self):
+        """How many deferred meshes still carry a stand-in tree (hk_scene_builder_pending_mesh_trees)."""
+        n = F.u32()
+        self.api.call("scene_builder_pending_mesh_trees", self.h, C.byref(n))
+        return n.value
+
+    def build_pending_mesh_trees(self):
+        """The host completion of the deferred meshes (hk_scene_builder_build_pending_mesh_trees): in place, a finished builder stays
+        finished - scene() returns the final arrays."""
+        self.api.call("scene_builder_build_pending_mesh_trees", self.h)
 
     def add_material(self, material):
         out = F.u32()
@@ -421,6 +434,11 @@ class SceneBuilder:
     def finish(self, build_trees=True):
         """hk_scene_builder_finish; build_trees=False: hk_scene_builder_finish_instances (stand-in trees, for a device-side build)."""
         self.api.call("scene_builder_finish" if build_trees else "scene_builder_finish_instances", self.h)
+        return self.scene()
+
+    def scene(self):
+        """A SceneData from the getters of a finished builder, without finishing it again (after build_pending_mesh_trees or
+        Engine.load_scene the arrays of an earlier SceneData are stale by design)."""
         arrays = {}
         for name, typ in (("vertices", F.HkVertex), ("primitives", F.HkPrimitive), ("asset_nodes", F.HkNode), ("materials", F.HkMaterial),
                           ("instances", F.HkInstance), ("instance_nodes", F.HkNode), ("emissives", F.HkEmissive),
@@ -534,6 +552,21 @@ class Engine:
     def upload_instances(self, scene: SceneData):
         """Instance-level update of a scene whose meshes and materials are already uploaded."""
         scene.upload_instances(self.api, self.ctx)
+
+    def load_scene(self, builder, mode=F.TREE_SAH, textures=()):
+        """hk_load_scene: the upload of a FINISHED builder whose deferred meshes (SceneBuilder.add_mesh(build_tree=False)) get their trees
+        built on the device - F.TREE_SAH = the trees the host builds, F.TREE_LBVH = the quick Morton-order trees - and written back into
+        the builder.  Returns the refreshed SceneData."""
+        self.upload_textures(list(textures))
+        self.api.call("load_scene", self.ctx, builder.h, mode)
+        return builder.scene()
+
+    def last_load(self):
+        """(meshes built on the device, their triangles, kernel launches of the build, meshes completed on the host) of the last
+        load_scene (test hook)."""
+        out = (F.u32 * 4)()
+        self.api.call("debug_last_load", self.ctx, out)
+        return tuple(int(v) for v in out)
 
     def refit_instances(self, builder):
         """Instance motion on the device (hk_refit_scene_instances): the poses set on `builder` since the last upload / refit go to
@@ -1107,6 +1140,10 @@ class HikariPlugin:
 
     def set_scene(self, scene: SceneData):
         self.engine.upload_scene(scene)
+
+    def load_scene(self, builder, mode=F.TREE_SAH, textures=()):
+        """set_scene for a finished SceneBuilder with deferred meshes: their trees are built on the device (Engine.load_scene)."""
+        return self.engine.load_scene(builder, mode, textures)
 
     def update_instances(self, scene: SceneData):
         """Instances moved (prepare_instances, instance.rs:352-437): rewrite the instance-level buffers only."""

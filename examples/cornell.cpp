@@ -9,6 +9,8 @@
 //           [--pick U V]                    a ray query (hk_cast_rays) through the point (U, V) of the camera's image, 0..1 from its top left corner:
 //                                          prints `pick instance primitive distance` (4294967295 4294967295 3.40282347e+38 for a miss); the frames are
 //                                          the same with or without it
+//           [--device-trees]                the meshes are added without their trees (SceneBuilder::add_mesh_deferred) and the scene is loaded with
+//                                          load_scene: every mesh tree is built on the device (hk_load_scene); the frames are the same
 //           [--animate [--rebuild-at F]]   the boxes drift every frame; the poses go to the GPU, which redoes the instance records and refits
 //                                          both trees (hk_refit_scene_instances); at frame F the trees are rebuilt on the device (LBVH)
 //           [--gpus N [--devices a,b,..]]   band-sharded over N GPUs from this one process (hk_multi_*); --devices may repeat an id
@@ -35,7 +37,7 @@ static std::vector<uint8_t> read_file(const std::string& path) {
 }
 
 // assets/cornell.hkscene (tools/make_fixtures.py: make_cornell_bin) -> builder
-static void load_cornell(const std::string& path, SceneBuilder& b) {
+static void load_cornell(const std::string& path, SceneBuilder& b, bool deferred = false) {
   std::vector<uint8_t> d = read_file(path);
   size_t off = 0;
   auto u32 = [&]() { uint32_t v; std::memcpy(&v, d.data() + off, 4); off += 4; return v; };
@@ -62,7 +64,7 @@ static void load_cornell(const std::string& path, SceneBuilder& b) {
     material_ids.push_back(b.add_material(standard_material(&v[0], &v[4], v[7], v[8])));
   }
   std::vector<uint32_t> mesh_ids;
-  for (auto& m : meshes) mesh_ids.push_back(b.add_mesh(m.p, m.n, m.uv, m.idx));
+  for (auto& m : meshes) mesh_ids.push_back(deferred ? b.add_mesh_deferred(m.p, m.n, m.uv, m.idx) : b.add_mesh(m.p, m.n, m.uv, m.idx));
   for (uint32_t i = 0; i < n_instances; ++i) {
     uint32_t mesh = u32();
     std::vector<float> t = floats(16);
@@ -87,7 +89,7 @@ int main(int argc, char** argv) {
   uint32_t w = 256, h = 256;
   size_t frames = 8;
   HikariSettings settings;  // HikariSettings::default(), examples/cornell.rs:53
-  bool by_nodes = false, describe = false, antialias = false, animate = false;
+  bool by_nodes = false, describe = false, antialias = false, animate = false, device_trees = false;
   size_t rebuild_at = 0;
   uint32_t ctx_flags = 0;
   int gpus = 1;
@@ -113,6 +115,7 @@ int main(int argc, char** argv) {
     else if (a == "--assets" && i + 1 < argc) assets = argv[++i];
     else if (a == "--describe") describe = true;
     else if (a == "--animate") animate = true;
+    else if (a == "--device-trees") device_trees = true;
     else if (a == "--deterministic") ctx_flags |= HK_CTX_DETERMINISTIC_SCATTER;  // resolve the reference's scatter-store race reproducibly (motion)
     else if (a == "--rebuild-at" && i + 1 < argc) rebuild_at = (size_t)atoi(argv[++i]);
     else if (a == "--gpus" && i + 1 < argc) gpus = atoi(argv[++i]);
@@ -147,8 +150,8 @@ int main(int argc, char** argv) {
     if (devices.empty()) for (int d = 0; d < gpus; ++d) devices.push_back(d);
     HikariMultiGpuPlugin plugin(read_file(assets + "/noise_rgba8_16x64x64.bin"), devices);
     SceneBuilder scene;
-    load_cornell(assets + "/cornell.hkscene", scene);
-    plugin.set_scene(scene);
+    load_cornell(assets + "/cornell.hkscene", scene, device_trees);
+    if (device_trees) plugin.load_scene(scene); else plugin.set_scene(scene);
     Camera camera = Camera::looking_at({0.0, 1.0, 4.0}, {0.0, 1.0, 0.0}, {0.0, 1.0, 0.0}, w, h);
     if (balance) plugin.balance_bands_on_next_frame();
     plugin.set_gather(gather);
@@ -172,8 +175,13 @@ int main(int argc, char** argv) {
   try {
     HikariPlugin plugin(read_file(assets + "/noise_rgba8_16x64x64.bin"), 0, ctx_flags);  // App::new().add_plugin(HikariPlugin)
     SceneBuilder scene;
-    load_cornell(assets + "/cornell.hkscene", scene);                      // asset_server.load("models/cornell.glb#Scene0")
-    plugin.set_scene(scene);
+    load_cornell(assets + "/cornell.hkscene", scene, device_trees);        // asset_server.load("models/cornell.glb#Scene0")
+    if (device_trees) {
+      plugin.load_scene(scene);
+      if (scene.pending_mesh_trees() != 0u) { std::fprintf(stderr, "load_scene left %u mesh trees pending\n", scene.pending_mesh_trees()); return 1; }
+    } else {
+      plugin.set_scene(scene);
+    }
     Camera camera = Camera::looking_at({0.0, 1.0, 4.0}, {0.0, 1.0, 0.0}, {0.0, 1.0, 0.0}, w, h);  // cornell.rs:49-50
     if (pick) {  // picking: what is under this point of the image (needs the scene only - no size, no frame)
       const HkRay ray = camera.ray_through(pick_u, pick_v);

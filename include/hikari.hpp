@@ -265,6 +265,22 @@ class SceneBuilder {  // the Prepare-stage host work: mesh -> BLAS, TLAS, emissi
           "hk_scene_builder_add_mesh");
     return id;
   }
+  // a mesh whose tree is DEFERRED: a stand-in of the final size until load_scene (Context / HikariPlugin) builds the real one on the
+  // device, or build_pending_mesh_trees() on the host
+  uint32_t add_mesh_deferred(const std::vector<float>& positions, const std::vector<float>& normals, const std::vector<float>& uvs,
+                             const std::vector<uint32_t>& indices, uint32_t topology = HK_TOPOLOGY_TRIANGLE_LIST) {
+    uint32_t id = 0;
+    check(hk_scene_builder_add_mesh_deferred(h_, positions.data(), normals.data(), uvs.data(), (uint32_t)(positions.size() / 3),
+                                             indices.empty() ? nullptr : indices.data(), (uint32_t)indices.size(), topology, &id),
+          "hk_scene_builder_add_mesh_deferred");
+    return id;
+  }
+  uint32_t pending_mesh_trees() const {
+    uint32_t n = 0;
+    check(hk_scene_builder_pending_mesh_trees(h_, &n), "hk_scene_builder_pending_mesh_trees");
+    return n;
+  }
+  void build_pending_mesh_trees() { check(hk_scene_builder_build_pending_mesh_trees(h_), "hk_scene_builder_build_pending_mesh_trees"); }
   uint32_t add_material(const HkMaterial& m) {
     uint32_t id = 0;
     check(hk_scene_builder_add_material(h_, &m, &id), "hk_scene_builder_add_material");
@@ -291,6 +307,8 @@ class SceneBuilder {  // the Prepare-stage host work: mesh -> BLAS, TLAS, emissi
 class Context {
  public:
   explicit Context(int device = 0, uint32_t flags = 0) { check(hk_create(device, flags, &c_), "hk_create"); }
+  // the upload of a finished builder whose deferred meshes get their trees built on the device and written back (hk_load_scene)
+  void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_load_scene(c_, b.handle(), tree_mode), "hk_load_scene"); }
   ~Context() { hk_destroy(c_); }
   Context(const Context&) = delete;
   Context& operator=(const Context&) = delete;
@@ -382,6 +400,7 @@ class HikariPlugin {
   }
   Context& context() { return ctx_; }
   void set_scene(const SceneBuilder& b) { check(hk_upload_scene(ctx_.get(), b.handle()), "hk_upload_scene"); }
+  void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { ctx_.load_scene(b, tree_mode); }  // ... with deferred meshes: trees built on the device
   // after SceneBuilder::set_instance_transform + finish: rewrite the instance-level device arrays only
   void update_instances(const SceneBuilder& b) { check(hk_upload_scene_instances(ctx_.get(), b.handle()), "hk_upload_scene_instances"); }
   // instance motion on the device: the poses set on `b` since the last upload / refit; returns how many moved
@@ -459,6 +478,7 @@ class HikariMultiGpuPlugin {
   HikariMultiGpuPlugin(const HikariMultiGpuPlugin&) = delete;
   HikariMultiGpuPlugin& operator=(const HikariMultiGpuPlugin&) = delete;
   void set_scene(const SceneBuilder& b) { check(hk_multi_upload_scene(m_, b.handle()), "hk_multi_upload_scene"); }
+  void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_multi_load_scene(m_, b.handle(), tree_mode), "hk_multi_load_scene"); }
   void update_instances(const SceneBuilder& b) { check(hk_multi_upload_scene_instances(m_, b.handle()), "hk_multi_upload_scene_instances"); }
   uint32_t refit_instances(SceneBuilder& b) {
     uint32_t moved = 0;

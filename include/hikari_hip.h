@@ -511,6 +511,17 @@ int hk_scene_builder_set_mesh_vertices(hk_scene_builder* b, uint32_t mesh_id, co
  * boxes below it as hk_scene_builder_set_mesh_vertices forms them.  Primitives, vertices and the mesh box are untouched; the node
  * count stays (3n - 2).  An error leaves the builder as it was.  The next finish lays the mesh level out again. */
 int hk_scene_builder_rebuild_mesh_tree(hk_scene_builder* b, uint32_t mesh_id);
+/* A mesh whose tree is DEFERRED: hk_scene_builder_add_mesh with the same arguments, validation, primitives, vertices and mesh box, but
+ * without its `BVH::build` - the mesh gets a valid stand-in tree of the final size (3n - 2 nodes, flatten_custom layout, the index list
+ * halved recursively) and is marked pending.  Offsets and HkMeshIndex records are final at the next finish (the node count does not
+ * depend on the tree).  hk_load_scene builds the pending trees on the device; hk_scene_builder_build_pending_mesh_trees is the host
+ * completion (per pending mesh the tree of hk_scene_builder_rebuild_mesh_tree, written in place: a finished builder stays finished and
+ * its getters return the final trees).  Every other upload of a builder with pending meshes is refused (HK_E_NOT_READY). */
+int hk_scene_builder_add_mesh_deferred(hk_scene_builder* b, const float* positions, const float* normals, const float* uvs,
+                                       uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices, uint32_t topology,
+                                       uint32_t* mesh_id);
+int hk_scene_builder_pending_mesh_trees(const hk_scene_builder* b, uint32_t* count);
+int hk_scene_builder_build_pending_mesh_trees(hk_scene_builder* b);
 /* the HkMeshIndex of a mesh after a finish (what its instances carry, and what the hk_*_mesh_* calls take) */
 int hk_scene_builder_mesh_index(const hk_scene_builder* b, uint32_t mesh_id, HkMeshIndex* out);
 
@@ -617,6 +628,22 @@ int hk_skin_mesh(hk_ctx* ctx, const HkMeshIndex* mesh, const float* joint_matric
  * HK_MESH_REBUILD_MAX_TRIANGLES triangles (HK_E_UNSUPPORTED). */
 #define HK_MESH_REBUILD_MAX_TRIANGLES 4194304u
 int hk_rebuild_mesh_tree(hk_ctx* ctx, const HkMeshIndex* mesh, uint32_t mode);
+/* hk_upload_scene for a FINISHED builder that may hold deferred meshes (hk_scene_builder_add_mesh_deferred): synchronous, like an upload.
+ * Every pending tree - of a mesh no instance uses yet, too - is built on the device, straight into the mesh-level region in every
+ * ordering the scene keeps, single-leaf navigators folded (the form hk_rebuild_mesh_tree writes); all pending meshes below 32 768
+ * triangles are built TOGETHER, at a number of kernel launches that does not depend on how many there are, larger ones one by one on
+ * the whole chip.  Meshes that were not pending go through the host layout untouched.
+ *   HK_TREE_SAH   the mesh-level nodes equal, byte for byte in every ordering, those after hk_upload_scene of a twin builder that used
+ *                 hk_scene_builder_add_mesh + hk_scene_builder_rebuild_mesh_tree on the same meshes.
+ *   HK_TREE_LBVH  the Morton build: valid trees, not the host's.
+ * The trees are written back into the builder in reference form (the mesh's nodes and its range of the concatenated array, in place:
+ * the builder stays finished, the marks are cleared) and into the context's mirror, so the context is in the state hk_upload_scene
+ * leaves: nothing is stale, hk_upload_materials / hk_upload_textures / hk_update_mesh_vertices work at once, the traversal mode is the
+ * upload's.  A later load of the same builder builds only the trees of meshes deferred since.  A pending mesh of more than
+ * HK_MESH_REBUILD_MAX_TRIANGLES triangles is completed by the host inside the call.
+ * Argument errors (NULL, unknown mode: HK_E_INVALID; unfinished builder: HK_E_NOT_READY) write nothing; a failure after the upload has
+ * begun leaves the context WITHOUT a scene (HK_E_NOT_READY at the next frame), never with stand-in trees. */
+int hk_load_scene(hk_ctx* ctx, hk_scene_builder* b, uint32_t tree_mode);
 int hk_upload_textures(hk_ctx* ctx, const HkImageDesc* images, uint32_t n_images);
 /* InstanceRenderAssets::set + write_buffer, instance.rs:82-108 */
 int hk_upload_instances(hk_ctx* ctx, const HkInstance* instances, uint32_t n_instances, const HkNode* instance_nodes,
@@ -952,6 +979,8 @@ int hk_multi_create(uint32_t n, const int* device_ids, uint32_t flags, hk_multi*
 void hk_multi_destroy(hk_multi* m);
 int hk_multi_context(hk_multi* m, uint32_t i, hk_ctx** out); /* the i-th band's context (borrowed) */
 int hk_multi_upload_scene(hk_multi* m, const hk_scene_builder* b);
+/* hk_load_scene for every band: the trees are built once (on band 0's device) and written back, the other bands take the finished builder */
+int hk_multi_load_scene(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode);
 int hk_multi_upload_scene_instances(hk_multi* m, const hk_scene_builder* b);
 int hk_multi_refit_scene_instances(hk_multi* m, hk_scene_builder* b, uint32_t* moved); /* hk_refit_scene_instances on every band's replica */
 int hk_multi_rebuild_scene_trees(hk_multi* m, uint32_t mode);

@@ -19,6 +19,13 @@ int hk_debug_read_trees(hk_ctx* ctx, HkNode* instance_nodes, uint32_t instance_c
 /* Test hook: the mesh-level node array as the device holds it - every ordering (1, or 8 for threaded scenes) of every mesh tree,
  * leaf boxes filled in and navigators folded, ordering-major, entry / exit words as stored - and the orderings count. */
 int hk_debug_read_mesh_nodes(hk_ctx* ctx, HkNode* out, uint32_t cap, uint32_t* count, uint32_t* orderings);
+/* Test hook: what the last hk_load_scene of this context did - out[0] meshes whose trees the device built, out[1] their triangles,
+ * out[2] the kernel launches of that build (a library sort counted as one), out[3] pending meshes completed by the host instead. */
+int hk_debug_last_load(hk_ctx* ctx, uint32_t out[4]);
+/* Measurement hook (tools/load_probe.py): where the host time of the last hk_load_scene went, in ms - out[0] host completion of meshes
+ * beyond the device limit, out[1] the copy into the context's mirrors, out[2] layout of both regions and their upload, out[3] the device
+ * build from its first launch to the end of the stream, out[4] the read-back, its unfolding and the write-back into the builder. */
+int hk_debug_last_load_times(hk_ctx* ctx, double out[5]);
 /* Test hook: one mesh deformed on this context (hk_update_mesh_vertices / hk_skin_mesh) as the device holds it after the pending
  * deformations: the positions of the last deformation and the vertex-plane normals (4 floats per vertex), the triangle planes (12
  * floats per triangle: v0, v1, v2 as xyz + the vertex-index word) and the mesh box (min xyz, max xyz) decoded from its six words.
@@ -106,6 +113,7 @@ int hk_debug_comm_lanes(hk_ctx* ctx, uint32_t* lanes);
 /* 6, 7 and 8 belonged to retired options and are not reused: hk_debug_set_option rejects them (HK_E_INVALID) */
 #define HK_DEBUG_OPT_MAIN_PRIORITY 9u /* the priority of the context's own main stream, created again at once: -1 by the library's rule (the highest if the context dispatches at most 6 Mi pixels per frame; what the context's first frame decides by itself), 0 the default priority, 1 the highest.  A/B and tests: a stream created again several times ends up sharing a hardware queue */
 #define HK_DEBUG_OPT_PREPASS_PIPELINE 10u /* a frame's primary rays on a stream of their own beside the previous frame's spatial pass, where the order allows (context.hip stage TEMPORAL): -1 by the library's rule (default: scenes beyond the LDS copy in frames of up to 3 Mi pixels, on a context whose chain runs at the highest priority), 0 never, 1 whenever the order allows */
+#define HK_DEBUG_OPT_LOAD_DEVICE_LIMIT 12u /* hk_load_scene completes a deferred mesh of more than this many triangles on the host instead of the device (default 0: HK_MESH_REBUILD_MAX_TRIANGLES); tests reach that path without a mesh of four million triangles */
 #define HK_DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP 11u /* 1: hk_rebuild_mesh_tree (HK_TREE_SAH) runs the top levels of its build in one workgroup at any mesh size, as the instance tree's build does (default 0: on the whole chip from 32 768 triangles); the same tree either way - the A/B of tools/deform_probe.py */
 int hk_debug_set_option(hk_ctx* ctx, uint32_t option, int64_t value);
 /* hk_multi_*: 1 = the calling thread enqueues every band's launches one after another instead of one thread per band (process-wide) */
