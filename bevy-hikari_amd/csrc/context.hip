@@ -41,6 +41,33 @@ bool certify_uv_division(int size) {
   return true;
 }
 
+// Known results (hk_context.hpp empty_tiles): a kernel that skips its coordinate chain for a pixel of an empty tile assumes the chain
+// ends at the pixel itself.  At upscale ratio 1 (the jitter term is +-amount * texel * 0) that is true if, for every k < size,
+// coords_to_uv -> jittered_deferred_coords (the light kernels) and coords_to_uv -> jittered_deferred_uv -> nearest_coords (demodulation,
+// the a-trous levels) both return k, and the three variance taps of demodulation (uv + {-1, 0, 1} / size -> nearest_coords), where they
+// lie in [0, 1], return a coordinate at most one away from k: checked here in f32 with the kernels' own operations, x and y apart (the
+// chains are separable).  `fast`: the uv comes from div_by (certify_uv_division says it is the IEEE quotient; taken as the kernels do).
+bool certify_pixel_identity(int size, bool fast) {
+  const float b = (float)size, c = 1.0f / b;
+  for (int k = 0; k < size; ++k) {
+    const float x = (float)k + 0.5f, q = x * c;
+    const float uv = fast ? fmaf(fmaf(-q, b, x), c, q) : x / b;
+    for (int s = 0; s < 4; ++s) {
+      const float sgn = (s & 1) ? 0.25f : 0.5f, amount = (s & 2) ? -sgn : sgn;
+      const float duv = uv + amount * c * 0.0f;                                 // jittered_deferred_uv at ratio 1
+      if ((int)(duv * b) != k) return false;                                    // jittered_deferred_coords
+      if (std::min(std::max((int)floorf(duv * b), 0), size - 1) != k) return false;  // nearest_coords
+    }
+    for (int o = -1; o <= 1; ++o) {
+      const float su = uv + (float)o * c;
+      if (su < 0.0f || su > 1.0f) continue;   // (a tap outside the image reads the pixel's own address)
+      const int sx = std::min(std::max((int)floorf(su * b), 0), size - 1);
+      if (sx < k - 1 || sx > k + 1) return false;
+    }
+  }
+  return true;
+}
+
 // The main stream - primary rays, the indirect pass, spatial reuse: the frame's dependent chain - runs at the device's highest stream
 // priority when the context's frames are small, at the default priority otherwise (round 6; measured on three scenes x four sizes and
 // on bands, profiles/r06_stream_priority_ab.txt): with the chain ahead of the side stream's direct-light dispatches and the post
@@ -127,6 +154,12 @@ int free_screen(hk_ctx* c) {
     c->tile_meta[k] = nullptr;
     c->tile_meta_zero[k] = false;
   }
+  for (int k = 0; k < 2; ++k) {
+    if (c->empty_tiles[k]) (void)hipFree(c->empty_tiles[k]);
+    c->empty_tiles[k] = nullptr;
+    c->empty_ok[k] = c->lights_ok[k] = false;
+  }
+  c->pixel_identity = false;
   if (c->wf_mem) (void)hipFree(c->wf_mem);
   c->wf_mem = nullptr;
   if (c->wf.timeline) (void)hipFree(c->wf.timeline);
@@ -247,8 +280,32 @@ GBuffer make_gbuffer(const hk_ctx* c) {
   g.depth = c->depth_plane;
   g.dn_g = (float4*)c->dn_g;
   g.albedo_out = nullptr;
+  g.empty_out = nullptr;
+  g.empty_in = nullptr;
+  g.tiles_x = c->tiles_x;
   return g;
 }
+// The empty-tile plane for a launch over render rows [y0, y1) of the current frame, or nullptr (hk_context.hpp empty_tiles).  Handed over
+// only when ALL of this holds: the switch is on; hk_frame_stage launches (never a hand-driven hk_pass_run); the upscale ratio is exactly 1
+// and the coordinate chains are certified to map a pixel to itself (certify_pixel_identity); one band, whole tile rows (the `maintain`
+// rule of attach_tile_meta); the plane of this parity was written by THIS frame's primary rays, and no hk_write_buffer, host-rasterised
+// G-buffer or derived_dirty came since (each clears empty_ok).  `demodulation`: its shortcut also rests on the variance planes - this
+// frame's three light passes must have run over every row through hk_frame_stage - and on a finite kernel (0 * kernel = 0).
+const uint8_t* known_empty_plane(hk_ctx* c, int y0, int y1, bool demodulation = false) {
+  const uint32_t p = c->mapped_parity & 1u;
+  if (!c->known_results || !c->in_frame_stage || !c->empty_tiles[p] || !c->pixel_identity || c->W != c->RW || c->H != c->RH || c->frame.upscale_ratio != 1.0f) return nullptr;
+  if (c->band_count != 1 || (y0 % 8) != 0 || !((y1 % 8) == 0 || y1 == c->RH)) return nullptr;
+  if (!c->empty_ok[p] || c->empty_frame[p] != c->frame.number || c->derived_dirty || c->host_wrote) return nullptr;
+  if (demodulation) {
+    if (!c->lights_ok[p] || c->lights_frame[p] != c->frame.number) return nullptr;
+    for (int col = 0; col < 3; ++col)
+      for (int row = 0; row < 3; ++row)
+        if (!std::isfinite(c->frame.kernel[col][row])) return nullptr;
+  }
+  c->empty_plane_launches += 1;
+  return c->empty_tiles[p];
+}
+void forget_empty_tiles(hk_ctx* c) { c->empty_ok[0] = c->empty_ok[1] = c->lights_ok[0] = c->lights_ok[1] = false; }
 // A band of a sharded frame whose history halo is not empty parks the scatter stores of its temporal dispatches instead of
 // racing them into its local copy of previous_spatial: the neighbours need them (and this band theirs) before spatial_reuse
 bool parks_across_bands(const hk_ctx* c) { return c->band_count > 1 && c->history_now > 0; }
@@ -441,6 +498,8 @@ int run_demodulation_fused(hk_ctx* c, uint32_t nch, int y0, int y1) {
     d.output[ch] = (uint2*)dn_internal(c, nch, ch, 0);
     d.internal_variance[ch] = dn_variance(c, nch, ch);
   }
+  d.empty_tiles = known_empty_plane(c, y0, y1, true);
+  d.tiles_x = c->tiles_x;
   launch_demodulation(c->stream, (int)nch, fr, d, y0, y1);
   HK_HIP(hipGetLastError());
   return HK_OK;
@@ -463,6 +522,8 @@ int run_denoise_fused(hk_ctx* c, uint32_t nch, int level, int y0, int y1, bool w
     d.tone_mapped = (uint2*)c->buf[HK_BUF_TONE_MAPPED];
     memcpy(d.clear_color, c->frame.clear_color, sizeof(d.clear_color));
   }
+  d.empty_tiles = known_empty_plane(c, y0, y1);
+  d.tiles_x = c->tiles_x;
   launch_denoise(c->stream, level, (int)nch, 0, fr, d, y0, y1);
   HK_HIP(hipGetLastError());
   return HK_OK;
@@ -705,12 +766,16 @@ int run_pass_on_side(hk_ctx* c, uint32_t pass, uint32_t arg, int y0, int y1) {
 
 int run_pass(hk_ctx* c, uint32_t pass, uint32_t arg, int y0, int y1) {
   const DFrame fr = make_dframe(c);
-  const GBuffer g = make_gbuffer(c);
+  GBuffer g = make_gbuffer(c);
   unsigned long long* counters = (c->flags & HK_CTX_COUNT_RAYS) ? c->d_counters : nullptr;
   if (c->derived_dirty && pass != HK_PASS_PREPASS) {  // G-buffer planes were written by the host: refresh the derived planes
     launch_derive_planes(c->stream, g, c->depth_plane, c->dn_g, c->W, 0, c->H);
     c->derived_dirty = false;
   }
+  // the fused light kernels read the frame's empty-tile plane (the queue-based schedule of the indirect pass does not)
+  const bool fused_light = pass == HK_PASS_DIRECT_LIT || pass == HK_PASS_DIRECT_EMISSIVE || (pass == HK_PASS_INDIRECT && !use_wavefront(c)) ||
+                           pass == HK_PASS_EMISSIVE_SPATIAL_REUSE || pass == HK_PASS_INDIRECT_SPATIAL_REUSE;
+  if (fused_light) g.empty_in = known_empty_plane(c, y0, y1);
   // (the two long dispatches of a frame carry their events ON the dispatch - hipExtLaunchKernelGGL - so that timing them inside a
   // pipelined frame adds no stream operation; every other pass is bracketed by two records)
   ScopedTimer timer(c, pass, pass == HK_PASS_INDIRECT || pass == HK_PASS_INDIRECT_SPATIAL_REUSE || pass == HK_PASS_EMISSIVE_SPATIAL_REUSE);
@@ -1022,6 +1087,7 @@ int hk_debug_set_option(hk_ctx* c, uint32_t option, int64_t value) {
     case HK_DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP: c->mesh_rebuild_one_workgroup = value != 0; break;
     case HK_DEBUG_OPT_LOAD_DEVICE_LIMIT: c->load_device_limit = value <= 0 ? HK_MESH_REBUILD_MAX_TRIANGLES : (uint32_t)std::min<int64_t>(value, HK_MESH_REBUILD_MAX_TRIANGLES); break;
     case HK_DEBUG_OPT_PREPASS_PIPELINE: c->prepass_pipeline = value < 0 ? -1 : (value ? 1 : 0); break;
+    case HK_DEBUG_OPT_KNOWN_RESULTS: c->known_results = value != 0; forget_empty_tiles(c); break;
     case HK_DEBUG_OPT_MAIN_PRIORITY: c->main_priority = value < 0 ? -1 : (value ? 1 : 0); return pick_main_stream(c, true);
     default: HK_REQUIRE(false, HK_E_INVALID, "unknown option %u", option);
   }
@@ -1031,6 +1097,16 @@ int hk_debug_set_option(hk_ctx* c, uint32_t option, int64_t value) {
 int hk_debug_main_stream_priority(hk_ctx* c, uint32_t* out) {
   HK_REQUIRE(c && out, HK_E_INVALID, "bad argument");
   *out = (c->own_stream_high ? 1u : 0u) | (c->main_priority_decided ? 2u : 0u) | (c->pre_stream ? 4u : 0u) | ((uint32_t)std::min<uint64_t>(c->prepasses_pipelined, 0xFFFFFu) << 8);
+  return HK_OK;
+}
+
+int hk_debug_empty_tiles(hk_ctx* c, uint8_t* out_bytes, size_t n, uint64_t* launches_given_the_plane) {
+  HK_REQUIRE(c && out_bytes && launches_given_the_plane, HK_E_INVALID, "bad argument");
+  HK_REQUIRE(c->empty_tiles[0] && n == (size_t)c->tiles_x * c->tiles_y, HK_E_INVALID, "the plane has %d x %d tiles", c->tiles_x, c->tiles_y);
+  HK_HIP(hipSetDevice(c->device));
+  { const int rc = sync_all(c); if (rc) return rc; }
+  HK_HIP(hipMemcpy(out_bytes, c->empty_tiles[c->mapped_parity & 1u], n, hipMemcpyDeviceToHost));
+  *launches_given_the_plane = c->empty_plane_launches;
   return HK_OK;
 }
 
@@ -1090,6 +1166,10 @@ static int resize_resources(hk_ctx* c, uint32_t width, uint32_t height, float up
       HK_HIP(hipMemset(c->tile_meta[k], 0, mb));
       c->tile_meta_zero[k] = true;
     }
+    for (int k = 0; k < 2; ++k) {
+      HK_HIP(hipMalloc((void**)&c->empty_tiles[k], (size_t)c->tiles_x * c->tiles_y));
+      HK_HIP(hipMemset(c->empty_tiles[k], 0, (size_t)c->tiles_x * c->tiles_y));
+    }
   }
   HK_HIP(hipMalloc((void**)&c->depth_plane, nf * 4));
   HK_HIP(hipMemset(c->depth_plane, 0, nf * 4));
@@ -1126,6 +1206,8 @@ static int resize_resources(hk_ctx* c, uint32_t width, uint32_t height, float up
   }
   c->derived_dirty = false;
   c->uv_fast = !(c->flags & HK_CTX_PLAIN_DIVISION) && certify_uv_division(c->W) && certify_uv_division(c->H) && certify_uv_division(c->RW) && certify_uv_division(c->RH);
+  c->pixel_identity = c->W == c->RW && c->H == c->RH && certify_pixel_identity(c->RW, c->uv_fast) && certify_pixel_identity(c->RH, c->uv_fast);
+  c->host_wrote = false;
   HK_HIP(hipDeviceSynchronize());
   return HK_OK;
 }
@@ -1210,6 +1292,7 @@ int hk_pass_run(hk_ctx* c, uint32_t pass, uint32_t arg, uint32_t row_begin, uint
   if (pass == HK_PASS_FSR_EASU || pass == HK_PASS_FSR_RCAS) rows = c->H;
   const int y0 = (int)row_begin, y1 = row_end == 0 ? rows : (int)row_end;
   HK_REQUIRE(y0 >= 0 && y1 <= rows && y0 <= y1, HK_E_INVALID, "row range [%d,%d) outside 0..%d", y0, y1, rows);
+  forget_empty_tiles(c);   // (a hand-driven pass may rewrite what the plane or demodulation's shortcut vouches for)
   return run_pass(c, pass, arg, y0, y1);
 }
 
@@ -1359,6 +1442,8 @@ int hk_frame_stage(hk_ctx* c, uint32_t stage, const HkSettings* st, uint32_t fla
   auto clampr = [&](int v) { return std::min(std::max(v, 0), c->RH); };
   const Aprons ap = band_aprons(st);
   const int den = (int)ap.denoise, sp = (int)ap.spatial;
+  struct InStage { hk_ctx* c; ~InStage() { c->in_frame_stage = false; } } in_stage_{c};
+  c->in_frame_stage = true;
 #define HK_RUN(pass, arg, y0, y1)                    \
   do {                                               \
     int a_ = (y0), b_ = (y1);                        \
@@ -1402,11 +1487,22 @@ int hk_frame_stage(hk_ctx* c, uint32_t stage, const HkSettings* st, uint32_t fla
     }
     bool albedo_done = false;
     if (c->timing_mask) (void)hipEventRecord(c->frame_start, c->stream);
+    // the empty-tile plane of this parity: whatever it held is about to be out of date; these primary rays write it again where every
+    // launch that could be handed it would qualify (known_empty_plane) and the rays cover the whole image
+    c->empty_ok[parity] = c->lights_ok[parity] = false;
+    const bool write_plane = c->known_results && c->empty_tiles[parity] && c->pixel_identity && c->frame.upscale_ratio == 1.0f && c->band_count == 1 &&
+                             !(flags & HK_FRAME_EXTERNAL_GBUFFER) && !c->derived_dirty && !c->host_wrote && f0 == 0 && f1 == c->H;
+    c->host_wrote = false;
     if (!(flags & HK_FRAME_EXTERNAL_GBUFFER)) {
       if (f1 > f0) {  // the prepass also fills the albedo of every pixel it covers (a superset of the rows albedo needs)
         const DFrame fr = make_dframe(c);
         GBuffer g = make_gbuffer(c);
         g.albedo_out = (uint2*)c->buf[HK_BUF_ALBEDO];
+        if (write_plane) {
+          g.empty_out = c->empty_tiles[parity];
+          c->empty_ok[parity] = true;
+          c->empty_frame[parity] = c->frame.number;
+        }
         unsigned long long* counters = (c->flags & HK_CTX_COUNT_RAYS) ? c->d_counters : nullptr;
         const Jitter j = prepass_jitter(c);
         hkd::WideTrees wide{};
@@ -1453,6 +1549,10 @@ int hk_frame_stage(hk_ctx* c, uint32_t stage, const HkSettings* st, uint32_t fla
       HK_RUN(HK_PASS_DIRECT_LIT, 0, b0, b1);          // light.rs:656-688
       HK_RUN(HK_PASS_DIRECT_EMISSIVE, 0, b0, b1);
       HK_RUN(HK_PASS_INDIRECT, 0, b0, b1);
+    }
+    if (c->band_count == 1 && b0 == 0 && b1 == c->RH) {  // (demodulation's shortcut: the variance of every background pixel is this frame's 0.0f)
+      c->lights_ok[parity] = true;
+      c->lights_frame[parity] = c->frame.number;
     }
     c->pre_chain_ok = !(flags & (HK_FRAME_EXTERNAL_GBUFFER | HK_FRAME_ANTIALIAS));   // (the next frame's primary rays may run beside what follows of this one)
     c->pre_last_parity = parity;
@@ -1767,11 +1867,19 @@ int hk_write_buffer(hk_ctx* c, uint32_t buffer, const void* src, size_t bytes) {
     c->tile_meta_zero[k] = true;
   }
   if (buffer == HK_BUF_POSITION || buffer == HK_BUF_NORMAL || buffer == HK_BUF_INSTANCE_MATERIAL) c->derived_dirty = true;
+  forget_empty_tiles(c);   // (whatever plane was written: the host's bytes are not what the primary rays vouched for)
+  c->host_wrote = true;
   return HK_OK;
 }
 int hk_device_ptr(hk_ctx* c, uint32_t buffer, void** ptr, size_t* bytes) {
   HK_REQUIRE(c && ptr && buffer < HK_BUF_COUNT && c->buf[buffer], HK_E_INVALID, "bad argument");
   *ptr = c->buf[buffer];
+  // (a plane the empty-tile shortcuts vouch for, about to be in the host's hands: as hk_write_buffer - hikari_hip.h)
+  if (buffer == HK_BUF_POSITION || buffer == HK_BUF_NORMAL || buffer == HK_BUF_DEPTH_GRADIENT || buffer == HK_BUF_INSTANCE_MATERIAL || buffer == HK_BUF_VELOCITY_UV ||
+      buffer == HK_BUF_ALBEDO || (buffer >= HK_BUF_VARIANCE0 && buffer < HK_BUF_VARIANCE0 + 3) || (buffer >= HK_BUF_RENDER0 && buffer < HK_BUF_RENDER0 + 3)) {
+    forget_empty_tiles(c);
+    c->host_wrote = true;
+  }
   if (bytes) *bytes = c->buf_bytes[buffer];  // the ALLOCATION (independent of the upscale kind in effect), so a host may keep a view across settings changes
   return HK_OK;
 }

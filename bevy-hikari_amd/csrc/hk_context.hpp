@@ -219,6 +219,18 @@ struct hk_ctx {
   bool tile_meta_zero[10] = {};
   int tiles_x = 0, tiles_y = 0;
   uint32_t elide_serial = 0;
+  // Known results (DESIGN 4 "Empty tiles"): one byte per 8x8 tile and frame parity, written by the primary rays of hk_frame_stage - 1 where
+  // every ray of the tile missed - and handed to the launches of the same frame that may skip the arithmetic leading to a known result
+  // (context.hip known_empty_plane holds the rule).  empty_frame / lights_frame: the frame whose primary rays wrote the parity's plane /
+  // whose three light passes ran over every row (demodulation's shortcut rests on the variance they wrote); *_ok = that entry holds.
+  uint8_t* empty_tiles[2] = {nullptr, nullptr};
+  bool empty_ok[2] = {false, false}, lights_ok[2] = {false, false};
+  uint32_t empty_frame[2] = {0, 0}, lights_frame[2] = {0, 0};
+  bool pixel_identity = false;           // at ratio 1 the kernels' coordinate chains map every pixel to itself (certify_pixel_identity, per hk_resize)
+  bool host_wrote = false;               // hk_write_buffer since the last primary rays: the next frame keeps today's path
+  bool in_frame_stage = false;           // hk_frame_stage is launching (hk_pass_run's hand-driven passes never get the plane)
+  bool known_results = true;             // HK_DEBUG_OPT_KNOWN_RESULTS
+  uint64_t empty_plane_launches = 0;     // launches that were handed the plane (hk_debug_empty_tiles)
   // ---- instance motion on the device (hk_refit_scene_instances, kernels_scene.hip)
   DynOffsets dyn_off{};                   // where the arrays of the instance-level region are (the slot in use)
   float4 *rf_inst_lo = nullptr, *rf_inst_hi = nullptr, *rf_prev_models = nullptr;  // world AABB / previous model per instance

@@ -20,6 +20,12 @@ struct GBuffer {
   // optional: k_prepass also evaluates full_screen_albedo (light.wgsl:1019-1042) for the pixels it covers and
   // writes it here (the frame path); null = the separate k_full_screen_albedo dispatch does it
   uint2* __restrict__ albedo_out;
+  // the empty-tile plane of this frame's parity (one byte per 8x8 tile, tiles_x per row): k_prepass writes 1 where all the primary rays
+  // of a tile missed (empty_out); the light kernels read it (empty_in) and skip the arithmetic whose result is then known.  Either is
+  // null where the context cannot vouch for the plane (context.hip known_empty_plane)
+  uint8_t* empty_out;
+  const uint8_t* empty_in;
+  int tiles_x;
 };
 // Uniform-tile store elision.  The reference stores a packed reservoir to up to three buffers for EVERY pixel of EVERY light
 // dispatch, background included (light.wgsl:1058-1069,1279-1287,1527-1532) - on a frame that is 64 % sky that is ~1 GB of HBM
@@ -153,6 +159,8 @@ struct DemodTargets {
   const uint2* render[3];               // light render per channel
   uint2* output[3];                     // internal_texture_0 per channel
   float* internal_variance[3];
+  const uint8_t* empty_tiles;           // the frame's empty-tile plane (GBuffer), or null
+  int tiles_x;
 };
 struct DenoiseTargets {
   const uint2* __restrict__ albedo;
@@ -166,6 +174,8 @@ struct DenoiseTargets {
   // (f16-rounded) channel outputs and write tone_mapping_output (the frame path); null = separate dispatch
   uint2* tone_mapped;
   float clear_color[4];
+  const uint8_t* empty_tiles;                   // the frame's empty-tile plane (GBuffer), or null
+  int tiles_x;
 };
 
 // what an a-trous tap needs of a G-buffer pixel besides its depth: the normal exactly as the filter derives it
@@ -196,6 +206,24 @@ __device__ __forceinline__ bool wave_leader() { return (int)__lane_id() == __ffs
 __device__ __forceinline__ int wave_tile(const Pixel& px, int tiles_x) {
   const int lane = threadIdx.x & 63;
   return ((px.y - (lane >> 3)) >> 3) * tiles_x + ((px.x - (lane & 7)) >> 3);
+}
+// the empty-tile plane: is the 8x8 tile of this wave (pixel_of_thread; called by its valid lanes only - their tile lies in the image) one
+// whose primary rays all missed this frame?  Wave-uniform, and known to be: the byte is read through the first lane.
+__device__ __forceinline__ bool wave_tile_known_empty(const uint8_t* __restrict__ plane, const Pixel& px, int tiles_x) {
+  if (!plane) return false;
+  const int tile = __builtin_amdgcn_readfirstlane(wave_tile(px, tiles_x));
+  return __builtin_amdgcn_readfirstlane((int)plane[tile]) != 0;
+}
+// ... and for the row-shaped waves of the stencil kernels (pixel_of_thread_rows): do this pixel and its neighbours up to `reach` pixels
+// away that lie in the image (reach <= 8: the four corners of the window name every tile it touches) all lie in empty tiles?  Per lane
+// (a wave is one row of 64 pixels there: y and with it the two tile rows are wave-uniform and kept in scalar registers)
+__device__ __forceinline__ bool pixel_known_empty(const uint8_t* __restrict__ plane, int tiles_x, int x, int y, int reach, int width, int height) {
+  const int yu = __builtin_amdgcn_readfirstlane(y);
+  const uint8_t* __restrict__ row0 = plane + (max(yu - reach, 0) >> 3) * tiles_x;
+  const uint8_t* __restrict__ row1 = plane + (min(yu + reach, height - 1) >> 3) * tiles_x;
+  if (reach == 0) return row0[(uint32_t)x >> 3] != 0;
+  const uint32_t x0 = (uint32_t)max(x - reach, 0) >> 3, x1 = (uint32_t)min(x + reach, width - 1) >> 3;  // (unsigned: 32-bit offsets from the scalar row address)
+  return (row0[x0] & row0[x1] & row1[x0] & row1[x1]) != 0;
 }
 __device__ __forceinline__ bool tile_holds(const TileMeta* m, int tile, unsigned long long id) {
   const TileMeta v = m[tile];

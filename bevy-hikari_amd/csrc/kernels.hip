@@ -120,6 +120,10 @@ __global__ __launch_bounds__(256, (LDS == 4 ? HK_PREPASS_WIDE_WAVES : (LDS == 2 
     rc.tlas = 0;  // counted as a primary ray
     primary = 1;
     rc.hits += hit.instance_index != HK_U32_MAX ? 1u : 0u;
+    if (g.empty_out) {  // the empty-tile plane (hk_kernels.hpp GBuffer): did every primary ray of the wave's tile - its pixels inside the image - miss?
+      const bool all_missed = __ballot(hit.instance_index != HK_U32_MAX) == 0ull;   // (ahead of the stores: nothing of it stays live across them)
+      if (wave_leader()) g.empty_out[wave_tile(px, g.tiles_x)] = all_missed ? (uint8_t)1 : (uint8_t)0;
+    }
     prepass_store(sc, fr, pp, g, px.x, px.y, ray, hit);
   }
   flush_counters<COUNT>(rc, primary, counters);
@@ -169,13 +173,18 @@ __global__ __launch_bounds__(256, (LDS == 0 ? HK_DIRECT_GLOBAL_WAVES : (LDS == 2
   if (px.valid) {
     const int x = px.x, y = px.y;
     const int index = x + fr.rw * y;
-    const f2 uv = coords_to_uv(fr, x, y);
     Sample s = zero_sample();
-    int dcx, dcy;
-    jittered_deferred_coords(fr, uv, &dcx, &dcy);
-    const bool din = in_bounds(dcx, dcy, fr.dw, fr.dh);
+    // (a tile the primary rays proved empty: its G-buffer texels are the pixels' own and hold depth 0 - neither computed nor loaded;
+    // the uv is the geometry branch's alone)
+    f2 uv = F2(0.0f, 0.0f);
+    int dcx = 0, dcy = 0;
+    float4 position_depth = make_float4(0, 0, 0, 0);
+    if (!wave_tile_known_empty(g.empty_in, px, g.tiles_x)) {
+      uv = coords_to_uv(fr, x, y);
+      jittered_deferred_coords(fr, uv, &dcx, &dcy);
+      if (in_bounds(dcx, dcy, fr.dw, fr.dh)) position_depth = g.position[dcx + fr.dw * dcy];
+    }
     const int didx = dcx + fr.dw * dcy;
-    const float4 position_depth = din ? g.position[didx] : make_float4(0, 0, 0, 0);
     const f3 position = xyz(position_depth);
     const float depth = position_depth.w;
 
@@ -473,12 +482,16 @@ __global__ __launch_bounds__(256, (LDS == 2 && MULTIPLE_BOUNCES ? HK_INDIRECT_FL
   if (px.valid) {
     const int x = px.x, y = px.y;
     const int index = x + fr.rw * y;
-    const f2 uv = coords_to_uv(fr, x, y);
-    int dcx, dcy;
-    jittered_deferred_coords(fr, uv, &dcx, &dcy);
-    const bool din = in_bounds(dcx, dcy, fr.dw, fr.dh);
+    const f2 uv = coords_to_uv(fr, x, y);  // (the geometry branch's alone: the compiler sinks it there)
+    // (a tile the primary rays proved empty: as in k_direct_lit.  The one-level form only - LDS == 2, the headline's: with the test in
+    // them the other instantiations grow by 5 % of their static instructions, past the budget tests/test_kernel_resources.py keeps)
+    int dcx = 0, dcy = 0;
+    float4 position_depth = make_float4(0, 0, 0, 0);
+    if (LDS != 2 || !wave_tile_known_empty(g.empty_in, px, g.tiles_x)) {
+      jittered_deferred_coords(fr, uv, &dcx, &dcy);
+      if (in_bounds(dcx, dcy, fr.dw, fr.dh)) position_depth = g.position[dcx + fr.dw * dcy];
+    }
     const int didx = dcx + fr.dw * dcy;
-    const float4 position_depth = din ? g.position[didx] : make_float4(0, 0, 0, 0);
     const f3 position = xyz(position_depth);
     const float depth = position_depth.w;
 
@@ -746,12 +759,16 @@ __global__ __launch_bounds__(256, HK_SPATIAL_WGS) void k_spatial_reuse(DScene sc
   constexpr uint32_t SPATIAL_REUSE_COUNT = EMISSIVE_LIT ? 8u : 16u;
   const int x = px.x, y = px.y;
   const int index = x + fr.rw * y;
-  const f2 uv = coords_to_uv(fr, x, y);
-  int dcx, dcy;
-  jittered_deferred_coords(fr, uv, &dcx, &dcy);
-  const bool din = in_bounds(dcx, dcy, fr.dw, fr.dh) && px.valid;  // (px.valid: always, in the plain form)
+  f2 uv = F2(0.0f, 0.0f);
+  int dcx = 0, dcy = 0;
+  float4 position_depth = make_float4(0, 0, 0, 0);
+  // (a tile the primary rays proved empty, as in k_direct_lit; the plain form only - every lane here is a valid pixel of the wave's tile)
+  if (WINDOWED || !wave_tile_known_empty(g.empty_in, px, g.tiles_x)) {
+    uv = coords_to_uv(fr, x, y);
+    jittered_deferred_coords(fr, uv, &dcx, &dcy);
+    if (in_bounds(dcx, dcy, fr.dw, fr.dh) && px.valid) position_depth = g.position[dcx + fr.dw * dcy];  // (px.valid: always, in the plain form)
+  }
   const int didx = dcx + fr.dw * dcy;
-  const float4 position_depth = din ? g.position[didx] : make_float4(0, 0, 0, 0);
   const f3 position = xyz(position_depth);
   const float depth = position_depth.w;
   // the window of the depth plane this workgroup's taps reach (every thread arrives here; a workgroup of background pixels skips the fill)

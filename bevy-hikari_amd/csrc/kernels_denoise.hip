@@ -20,6 +20,7 @@
 #ifndef HK_DENOISE_W
 #define HK_DENOISE_W 64  // wave shape of the a-trous levels: 64 x 1 pixels (pixel_of_thread_rows)
 #endif
+static_assert(HK_DENOISE_W == 64, "pixel_known_empty (hk_kernels.hpp) takes a wave for one row of pixels");
 
 namespace hkd {
 
@@ -51,6 +52,20 @@ __global__ __launch_bounds__(256) void k_demodulation(DFrame fr, DemodTargets d,
   const Pixel px = pixel_of_thread_rows<64, true>(fr.rw, row_begin, row_end);
   if (!px.valid) return;
   const int x = px.x, y = px.y, index = x + fr.rw * y;
+  // A wave whose pixels AND their 3 x 3 neighbours inside the image all lie in tiles this frame's primary rays proved empty (the plane is
+  // handed over only where every texel and tap address below is certified to be the pixel's own or a neighbour's, and where this frame's
+  // light passes ran over these rows - context.hip known_empty_plane): the albedo is +0, so the albedo < 0.01 select yields 0 whatever
+  // the render plane holds, and every variance tap was written 0.0f by the three light kernels, so each sum + kernel * max(v, 0) stays +0.
+  if (d.empty_tiles && __ballot(!pixel_known_empty(d.empty_tiles, d.tiles_x, x, y, 1, fr.rw, fr.rh)) == 0ull) {
+    // (the stores take 32-bit byte offsets from the planes' scalar addresses: 8 x index < 2^32 for every size hk_resize accepts)
+    const uint32_t at8 = (uint32_t)index * 8u, at4 = (uint32_t)index * 4u;
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      *reinterpret_cast<uint2*>(reinterpret_cast<char*>(d.output[ch]) + at8) = make_uint2(0u, 0x3C000000u);  // pack_f16x4(0, 0, 0, 1)
+      *reinterpret_cast<float*>(reinterpret_cast<char*>(d.internal_variance[ch]) + at4) = 0.0f;
+    }
+    return;
+  }
   const f2 uv = coords_to_uv(fr, x, y);
   const f2 deferred_uv = jittered_deferred_uv(fr, uv, 0.5f);
   int ax, ay, rx, ry;
@@ -119,6 +134,14 @@ __global__ __launch_bounds__(256, HK_DENOISE_WAVES) void k_denoise(DFrame fr, De
   if (!px.valid) return;
   constexpr int STEP = 8 >> LEVEL;
   const int x = px.x, y = px.y, index = x + fr.rw * y;
+  // A wave whose pixels all lie in tiles this frame's primary rays proved empty: the centre texel is the pixel's own (certified by the
+  // context where it hands the plane over) and holds depth 0 - the background stores below, without the coordinate chains and the loads.
+  if (d.empty_tiles && __ballot(!pixel_known_empty(d.empty_tiles, d.tiles_x, x, y, 0, fr.rw, fr.rh)) == 0ull) {
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) d.output[ch][index] = make_uint2(0u, 0u);
+    if (LEVEL == 3 && d.tone_mapped) d.tone_mapped[index] = pack_f16x4(F4(d.clear_color[0], d.clear_color[1], d.clear_color[2], d.clear_color[3]));
+    return;
+  }
   // The stencil's three columns and three rows: the uv of a tap, whether it lies in the image and the G-buffer texel under it are
   // separable in x and y, so the chain coords -> uv -> jittered uv -> nearest texel is evaluated once per column and once per row
   // (on the diagonal (x + a, y + a): column a's x and row a's y in one call) instead of once per tap; the same expressions.

@@ -996,6 +996,14 @@ class Engine:
         self.api.call("debug_main_stream_priority", self.ctx, C.byref(v))
         return int(v.value >> 8)
 
+    def empty_tiles(self):
+        """hk_debug_empty_tiles: (the empty-tile plane of the current frame parity as a (tiles_y, tiles_x) uint8 array, launches handed a plane so far)."""
+        w, h, _ = self.buffer_info(F.BUF_TONE_MAPPED)
+        tiles = np.zeros(((h + 7) // 8, (w + 7) // 8), dtype=np.uint8)
+        n = C.c_uint64()
+        self.api.call("debug_empty_tiles", self.ctx, tiles.ctypes.data_as(C.POINTER(C.c_uint8)), tiles.size, C.byref(n))
+        return tiles, int(n.value)
+
     def spatial_windowed_launches(self):
         """spatial_reuse launches that took the windowed form of the kernel (hikari_hip_debug.h; F.DEBUG_OPT_SPATIAL_WINDOW)."""
         n = C.c_uint64()

@@ -1014,7 +1014,11 @@ int hk_read_buffer(hk_ctx* ctx, uint32_t buffer, void* dst, size_t bytes);
 int hk_write_buffer(hk_ctx* ctx, uint32_t buffer, const void* src, size_t bytes);
 /* raw device pointer for zero-copy views (a host that composites or exchanges the buffers itself).  *bytes = the size of the
  * ALLOCATION, which does not depend on the upscale kind in effect (hk_buffer_info gives the logical size); the pointer is
- * valid until the next hk_resize (and, for the double-buffered ids, names another plane after the next hk_frame_begin). */
+ * valid until the next hk_resize (and, for the double-buffered ids, names another plane after the next hk_frame_begin).
+ * A host that WRITES a G-buffer, albedo, render or variance plane through such a pointer does so before the frame's first stage (with
+ * HK_FRAME_EXTERNAL_GBUFFER for the G-buffer): between two hk_frame_stage calls of one frame the library may rely on what the stages
+ * before wrote there (the empty-tile plane of the primary rays).  Asking for the pointer of one of those ids makes the frame in
+ * progress and the next one take no such shortcut; a pointer kept for longer is the host's to use by this rule. */
 int hk_device_ptr(hk_ctx* ctx, uint32_t buffer, void** ptr, size_t* bytes);
 /* the HIP stream the context enqueues its frames on.  Without hk_set_stream it is the context's own; the context's FIRST frame may
  * create it again at the device's highest priority (round 6: the frame's dependent chain ahead of the direct-light and a-trous
