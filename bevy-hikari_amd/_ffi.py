@@ -260,6 +260,7 @@ _PRODUCT_ONLY = {
     "scene_builder_finish_instances": [_vp],
     "scene_builder_remove_instance": [_vp, u32],
     "scene_builder_set_instance_material": [_vp, u32, u32],
+    "scene_builder_set_material": [_vp, u32, P(HkMaterial)],
     "scene_builder_set_instance_transform": [_vp, u32, P(f32)],
     "scene_builder_previous_transforms": [_vp, P(P(f32)), P(u32)],
     "scene_builder_vertices": [_vp, P(P(HkVertex)), P(u32)],
@@ -280,6 +281,8 @@ _PRODUCT_ONLY = {
     "refit_scene_instances": [_vp, _vp, P(u32)],
     "rebuild_scene_trees": [_vp, u32],
     "update_scene_instances": [_vp, _vp, u32],
+    "update_materials": [_vp, _vp, u32, P(u32)],
+    "update_texture": [_vp, u32, P(HkImageDesc)],
     "update_mesh_vertices": [_vp, P(HkMeshIndex), u32, P(f32), P(f32)],
     "set_mesh_skin": [_vp, P(HkMeshIndex), u32, P(f32), P(f32), P(C.c_uint16), P(f32)],
     "skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],
@@ -333,6 +336,8 @@ _PRODUCT_ONLY = {
     "multi_rebuild_mesh_tree": [_vp, P(HkMeshIndex), u32],
     "multi_set_band_bounds": [_vp, P(u32), u32],
     "multi_upload_textures": [_vp, P(HkImageDesc), u32],
+    "multi_update_materials": [_vp, _vp, u32, P(u32)],
+    "multi_update_texture": [_vp, u32, P(HkImageDesc)],
     "multi_upload_noise": [_vp, _vp, C.c_size_t],
     "multi_resize": [_vp, u32, u32, f32],
     "multi_set_history_rows": [_vp, u32],

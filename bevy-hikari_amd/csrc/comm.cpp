@@ -860,18 +860,14 @@ int hk_multi_update_scene_instances(hk_multi* m, hk_scene_builder* b, uint32_t t
   HK_NO_PENDING_MESHES(b);
   const int rc = hk_scene_builder_finish_instances(b);
   if (rc) return rc;
-  uint32_t ni = 0;
-  const HkInstance* inst = nullptr;
-  const int rq = hk_scene_builder_instances(b, &inst, &ni);
-  if (rq) return rq;
   for (hk_ctx* c : m->ctx) {
-    int r = upload_scene_instances_unchecked(c, b);   // (stand-in trees: the device build follows)
-    if (!r && ni >= 2) r = hk_rebuild_scene_trees(c, tree_mode);
+    const int r = upload_instances_and_build_trees(c, b, tree_mode);   // (stand-in trees: the device build follows)
     if (r) return r;
   }
   return HK_OK;
 }
 int hk_multi_upload_textures(hk_multi* m, const HkImageDesc* images, uint32_t n) { HK_EACH(hk_upload_textures(c, images, n)); }
+int hk_multi_update_texture(hk_multi* m, uint32_t index, const HkImageDesc* image) { HK_EACH(hk_update_texture(c, index, image)); }
 int hk_multi_upload_noise(hk_multi* m, const uint8_t* rgba, size_t bytes) { HK_EACH(hk_upload_noise(c, rgba, bytes)); }
 int hk_multi_resize(hk_multi* m, uint32_t w, uint32_t h, float ratio) {
   HK_REQUIRE(m, HK_E_INVALID, "multi is NULL");
@@ -885,6 +881,15 @@ int hk_multi_refit_scene_instances(hk_multi* m, hk_scene_builder* b, uint32_t* m
   HK_REQUIRE(m && b, HK_E_INVALID, "NULL argument");
   for (size_t i = 0; i < m->ctx.size(); ++i) {
     const int rc = hk::refit_instances_impl(m->ctx[i], b, moved, i + 1 == m->ctx.size());
+    if (rc) return rc;
+  }
+  return HK_OK;
+}
+// every band's context edits its own replica of the scene; an edit that switches an emitter finishes the builder once
+int hk_multi_update_materials(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode, uint32_t* changed) {
+  HK_REQUIRE(m && b, HK_E_INVALID, "NULL argument");
+  for (size_t i = 0; i < m->ctx.size(); ++i) {
+    const int rc = hk::update_materials_impl(m->ctx[i], b, tree_mode, changed, i == 0);
     if (rc) return rc;
   }
   return HK_OK;

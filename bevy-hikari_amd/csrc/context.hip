@@ -451,6 +451,7 @@ int ready(hk_ctx* c) {
   HK_REQUIRE(c->have_frame, HK_E_NOT_READY, "hk_frame_begin has not been called");
   HK_REQUIRE(c->have_noise, HK_E_NOT_READY, "noise textures not uploaded");
   HK_HIP(hipSetDevice(c->device));
+  c->rf_motion_taken = false;   // a frame: the next hk_refit_scene_instances is a new update again (scene_refit.hip refit_impl, update_materials_impl case B)
   const int rc = finalize_scene(c);
   return rc ? rc : flush_deform(c);   // (the instance level of meshes deformed since the last frame: once, whatever the number of calls)
 }

@@ -95,6 +95,13 @@ inline uint32_t hash_u32(uint32_t value) {  // utils.wgsl:15-24
   return state;
 }
 inline float as_f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+// a material as the device holds it: four float4 (base colour, emissive, roughness / metallic / reflectance, the four texture ids)
+inline void material_rows(const HkMaterial& m, float4 rows[4]) {
+  rows[0] = make_float4(m.base_color[0], m.base_color[1], m.base_color[2], m.base_color[3]);
+  rows[1] = make_float4(m.emissive[0], m.emissive[1], m.emissive[2], m.emissive[3]);
+  rows[2] = make_float4(m.perceptual_roughness, m.metallic, m.reflectance, 0.0f);
+  rows[3] = make_float4(as_f(m.base_color_texture), as_f(m.emissive_texture), as_f(m.metallic_roughness_texture), as_f(m.occlusion_texture));
+}
 
 }  // namespace hk
 
@@ -244,6 +251,15 @@ struct hk_ctx {
   bool rf_pending[2] = {false, false};
   int rf_k = 0;
   std::vector<uint32_t> rf_last_moved;    // instances whose `moved` flag is set on the device
+  // material edits on the device (hk_update_materials): pinned records (the MaterialUpdate array, then the ids of the emitters to
+  // re-derive), double-buffered against the kernels that read them like rf_updates
+  uint8_t* mt_updates[2] = {nullptr, nullptr};
+  size_t mt_updates_cap[2] = {0, 0};      // bytes
+  hipEvent_t mt_done[2] = {nullptr, nullptr};
+  bool mt_pending[2] = {false, false};
+  int mt_k = 0;
+  bool rf_motion_taken = false;           // a case-B material edit took the builder's poses along since the last frame: a refit that finds
+                                          // no pose left to change has nothing to do (it would clear the `moved` flags of this frame's movers)
   bool mirrors_stale = false;             // the host copies of emissives / tree boxes no longer describe the device scene
   // mesh deformation (mesh_deform.hip): per deformable mesh its tree topology, refit planes and skin, created on first use and dropped by
   // hk_upload_meshes; a pool of pinned staging buffers for the vertex / joint data, each reused once the event after its last reader has
@@ -360,6 +376,7 @@ int prepare_refit(hk_ctx* c);
 hkd::RefitScene refit_scene(hk_ctx* c);
 // ---- mesh_deform.hip
 void free_deform(hk_ctx* c);
+int stage(hk_ctx* c, size_t bytes, uint8_t** out, int* k);   // a pinned staging buffer from the pool (c->df_stage[*k]: record its `done` event behind the reader)
 int repropagate_deformed(hk_ctx* c);   // after an instance refit: the deformed meshes' current boxes again (hk_refit_scene_instances)
 int flush_deform(hk_ctx* c);           // the instance level of the meshes deformed since the last flush, once (frames, tree rebuilds, reads)
 }  // namespace hk

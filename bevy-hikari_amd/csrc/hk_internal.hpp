@@ -61,6 +61,15 @@ void builder_commit_transforms(hk_scene_builder* b);
 // false for a singular transform
 bool instance_world_record(const float transform[16], const float aabb_center[3], const float aabb_half[3], float mn[3], float mx[3], float inverse_transpose_model[16]);
 
+// material edits (hk_update_materials): the builder's materials whether it is finished or not, and the builder's own rule for which
+// instances emit (instance.rs:380-382: 255 a |rgb| > 0)
+void builder_materials(const hk_scene_builder* b, const HkMaterial** p, uint32_t* n);
+float emissive_intensity(const float emissive[4]);
+bool material_emits(const HkMaterial& m);
+// hk_update_materials on one context; `finish`: a case-B edit finishes the builder here (once per update, whichever context sees it first)
+int update_materials_impl(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode, uint32_t* changed, bool finish);
+
+int upload_instances_and_build_trees(hk_ctx* c, const hk_scene_builder* b, uint32_t tree_mode);  // scene_refit.hip
 int refit_instances_impl(hk_ctx* c, hk_scene_builder* b, uint32_t* moved, bool commit);  // hk_refit_scene_instances
 
 // bytes per pixel / full-size flag of an HkBuffer id (0 = invalid id)

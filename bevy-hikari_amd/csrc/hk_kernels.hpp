@@ -123,6 +123,11 @@ struct RefitUpdate {       // one record per instance whose transform changed (r
   float model[16];         // new model matrix, column-major
   float aabb_center[3], aabb_half[3];  // the mesh's local box (bevy Aabb), instance.rs:286-296
 };
+struct MaterialUpdate {    // one record per material whose values changed (hk_update_materials; read from pinned host memory)
+  uint32_t material;
+  uint32_t pad[3];
+  float4 rows[4];          // the material's four float4 of the device layout (scene_layout.hip build_dynamic_region)
+};
 // Mesh deformation (kernels_deform.hip, kernels_scene.hip; host side mesh_deform.hip): one mesh BLAS of n triangles as the binary tree
 // behind its flat layout - internal nodes in the preorder of ordering 0 (root 0), leaves in ordering 0's order as tree nodes n - 1 + j -
 // with the work planes of a bottom-up refit.
@@ -351,6 +356,12 @@ void launch_gather_instance_boxes(hipStream_t st, const hkd::RefitScene& s, cons
 void launch_refit(hipStream_t st, const hkd::RefitScene& s, const hkd::RefitUpdate* updates, uint32_t n_updates, uint32_t n_emitter_updates, uint32_t emitter_triangles,
                   uint32_t* failed, float4* tlas,
                   uint32_t tlas_count, uint32_t orderings, float4* light_lo, float4* light_hi, uint32_t light_count);
+// hk_update_materials: the changed records into `materials` (the slot's array, which s.materials names too), then - n_emitters != 0 -
+// position_radius of the listed emitters again from their instances' boxes, and the light tree refit in its shape
+void launch_material_update(hipStream_t st, const hkd::RefitScene& s, float4* materials, const hkd::MaterialUpdate* updates, uint32_t n_updates, const uint32_t* emitters,
+                            uint32_t n_emitters, float4* light_lo, float4* light_hi, uint32_t light_count);
+// hk_update_texture: n texels from pinned memory to their place in the texel buffer, and the texture's descriptor into `info0` / `info1` (or NULL)
+void launch_texture_update(hipStream_t st, uint32_t* dst, const uint32_t* src, size_t n, uint4* info0, uint4* info1, uint4 info);
 // LBVH rebuild of a flat skip-link BVH over n shapes (kernels_scene.hip): scratch size, and the build into `lo` / `hi` (`stride`
 // float4 between consecutive nodes: 2 for the interleaved TLAS, 1 for the two planes of the light BVH)
 size_t lbvh_scratch_bytes(uint32_t n, size_t* sort_temp_bytes);

@@ -1368,10 +1368,50 @@ __global__ __launch_bounds__(64) void k_mesh_instances(RefitScene s, const uint3
   records[u] = r;
 }
 
+// ------------------------------------------------------------------ material and texture edits (hk_update_materials, hk_update_texture)
+// One thread per changed material: its four float4 from the pinned record into the slot's material array.
+__global__ __launch_bounds__(64) void k_write_materials(float4* __restrict__ materials, const MaterialUpdate* __restrict__ updates, uint32_t n_updates) {
+  const uint32_t u = blockIdx.x * 64u + threadIdx.x;
+  if (u >= n_updates) return;
+  const uint32_t id = updates[u].material;
+  for (int k = 0; k < 4; ++k) materials[4u * id + (uint32_t)k] = updates[u].rows[k];
+}
+// One thread per emitter whose instance uses a material with a new emissive colour: position and radius again from the instance's
+// current box (the refit's side arrays) and the colour k_write_materials has just written - the arithmetic k_mesh_instances uses.
+__global__ __launch_bounds__(64) void k_material_emitters(RefitScene s, const uint32_t* __restrict__ emitters, uint32_t n_emitters) {
+  const uint32_t u = blockIdx.x * 64u + threadIdx.x;
+  if (u >= n_emitters) return;
+  const uint32_t e = emitters[u];
+  const uint32_t id = s.emissives[e].instance;
+  const float4 lo = s.inst_lo[id], hi = s.inst_hi[id];
+  const float mn[3] = {lo.x, lo.y, lo.z}, mx[3] = {hi.x, hi.y, hi.z};
+  s.emissives[e].position_radius = emitter_position_radius(s.materials[4u * s.instances[id].material + 1u], mn, mx);
+}
+// the texels of one texture from pinned memory (their place in the texel buffer is 4-B aligned, no more), and its descriptor
+__global__ __launch_bounds__(256) void k_update_texture(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, size_t n, uint4* info0, uint4* info1, uint4 info) {
+  for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) dst[i] = src[i];
+  if (blockIdx.x == 0u && threadIdx.x == 0u) {
+    if (info0) *info0 = info;
+    if (info1) *info1 = info;
+  }
+}
+
 }  // namespace hkd
 
 namespace hk {
 using namespace hkd;
+
+void launch_material_update(hipStream_t st, const RefitScene& s, float4* materials, const MaterialUpdate* updates, uint32_t n_updates, const uint32_t* emitters,
+                            uint32_t n_emitters, float4* light_lo, float4* light_hi, uint32_t light_count) {
+  if (n_updates) hipLaunchKernelGGL(k_write_materials, dim3((n_updates + 63u) / 64u), dim3(64), 0, st, materials, updates, n_updates);
+  if (!n_emitters) return;
+  hipLaunchKernelGGL(k_material_emitters, dim3((n_emitters + 63u) / 64u), dim3(64), 0, st, s, emitters, n_emitters);
+  if (light_count) hipLaunchKernelGGL((k_refit_flat_bvh<true>), dim3((light_count + 3u) / 4u), dim3(256), 0, st, s, light_lo, light_hi, 1u, light_count, 1u);
+}
+void launch_texture_update(hipStream_t st, uint32_t* dst, const uint32_t* src, size_t n, uint4* info0, uint4* info1, uint4 info) {
+  const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 4096));
+  hipLaunchKernelGGL(k_update_texture, dim3(blocks), dim3(256), 0, st, dst, src, n, info0, info1, info);
+}
 
 void launch_copy_region(hipStream_t st, void* dst, const void* src, size_t bytes) {
   const size_t n = bytes / 16;

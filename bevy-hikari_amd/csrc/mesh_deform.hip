@@ -198,8 +198,9 @@ int mesh_instances(hk_ctx* c, DeformMesh* d) {
   return HK_OK;
 }
 
+}  // namespace
 // a pinned staging buffer of at least `bytes`: one whose last reader has passed (hipEventQuery: no host wait), or a new one
-int stage(hk_ctx* c, size_t bytes, uint8_t** out, int* k_out) {
+int hk::stage(hk_ctx* c, size_t bytes, uint8_t** out, int* k_out) {
   int k = -1;
   for (size_t i = 0; i < c->df_stage.size() && k < 0; ++i) {
     hk_ctx::DeformStage& s = c->df_stage[i];
@@ -229,6 +230,7 @@ int stage(hk_ctx* c, size_t bytes, uint8_t** out, int* k_out) {
   return HK_OK;
 }
 
+namespace {
 // common front of the three calls: the scene as laid out, the refit's side arrays, the mesh
 int begin(hk_ctx* c, const HkMeshIndex* m, DeformMesh** d) {
   HK_REQUIRE(c->have_meshes && c->have_materials && c->have_instances, HK_E_NOT_READY, "hk_upload_scene must come first");

@@ -403,6 +403,13 @@ bool builder_instance_decl(const hk_scene_builder* b, uint32_t i, InstanceDecl* 
   out->aabb_half = b->meshes[d.mesh].aabb_half;
   return true;
 }
+// which instances emit (instance.rs:380-382): the intensity of a material's emissive colour, 255 a |rgb|; an instance is an emitter iff it is > 0
+float emissive_intensity(const float e[4]) { return 255.0f * e[3] * sqrtf(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]); }
+bool material_emits(const HkMaterial& m) { return emissive_intensity(m.emissive) > 0.0f; }
+void builder_materials(const hk_scene_builder* b, const HkMaterial** p, uint32_t* n) {
+  *p = b->materials.data();
+  *n = (uint32_t)b->materials.size();
+}
 void builder_commit_transforms(hk_scene_builder* b) {
   std::vector<float> now(b->instance_decl.size() * 16);
   for (size_t i = 0; i < b->instance_decl.size(); ++i) memcpy(&now[16 * i], b->instance_decl[i].transform, 64);
@@ -697,6 +704,14 @@ int hk_scene_builder_set_instance_material(hk_scene_builder* b, uint32_t instanc
   return HK_OK;
 }
 
+int hk_scene_builder_set_material(hk_scene_builder* b, uint32_t material_id, const HkMaterial* material) {
+  HK_REQUIRE(b && material, HK_E_INVALID, "NULL argument");
+  HK_REQUIRE(material_id < b->materials.size(), HK_E_INVALID, "unknown material id");
+  b->materials[material_id] = *material;
+  b->finished = false;
+  return HK_OK;
+}
+
 static int finish_impl(hk_scene_builder* b, bool build_trees) {
   HK_REQUIRE(b, HK_E_INVALID, "builder is NULL");
   if (b->meshes_dirty) {  // mesh.rs:141-163: concatenate, remember offsets (only when a mesh was added)
@@ -742,7 +757,7 @@ static int finish_impl(hk_scene_builder* b, bool build_trees) {
     const HkInstance& inst = b->instances[id];
     const HkMaterial& mat = b->materials[inst.material];
     const float* e = mat.emissive;
-    float intensity = 255.0f * e[3] * sqrtf(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+    float intensity = emissive_intensity(e);
     if (!(intensity > 0.0f)) continue;
     const BuilderMesh& mesh = b->meshes[b->instance_decl[id].mesh];
     std::vector<float> areas = primitive_areas(mesh, inst.model);

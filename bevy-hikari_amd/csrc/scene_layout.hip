@@ -402,10 +402,7 @@ int build_dynamic_region(hk_ctx* c, Blob& blob, DynOffsets& o, size_t static_byt
     const uint32_t ids[4] = {m.base_color_texture, m.emissive_texture, m.metallic_roughness_texture, m.occlusion_texture};
     for (uint32_t id : ids)  // MaterialTextures::id, material.rs:76-86: an index into the texture array or u32::MAX
       HK_REQUIRE(id == HK_NO_TEXTURE || id < n_tex, HK_E_INVALID, "material %zu references texture %u but only %u textures are uploaded", i, id, n_tex);
-    mats[4 * i] = make_float4(m.base_color[0], m.base_color[1], m.base_color[2], m.base_color[3]);
-    mats[4 * i + 1] = make_float4(m.emissive[0], m.emissive[1], m.emissive[2], m.emissive[3]);
-    mats[4 * i + 2] = make_float4(m.perceptual_roughness, m.metallic, m.reflectance, 0.0f);
-    mats[4 * i + 3] = make_float4(as_f(ids[0]), as_f(ids[1]), as_f(ids[2]), as_f(ids[3]));
+    material_rows(m, &mats[4 * i]);
   }
   o.materials = blob.add(mats);
   // material textures: a 16-B descriptor per texture + the sRGB decode table (texels live in their own buffer)
@@ -763,6 +760,50 @@ int hk_upload_textures(hk_ctx* c, const HkImageDesc* images, uint32_t n) {
   c->textures.swap(tex);
   c->textures_dirty = true;
   c->dynamic_dirty = true;
+  return HK_OK;
+}
+// One texture's texels and sampler, in place (hikari_hip.h).  The texel buffer has ONE copy, like the mesh-level region: the write goes
+// behind every frame enqueued so far on every stream that reads texels (stream waits through the context's events, no host wait).
+int hk_update_texture(hk_ctx* c, uint32_t index, const HkImageDesc* image) {
+  HK_REQUIRE(c && image && image->rgba8, HK_E_INVALID, "NULL argument");
+  HK_REQUIRE(!c->textures.empty(), HK_E_NOT_READY, "hk_upload_textures must come first");
+  HK_REQUIRE(index < c->textures.size(), HK_E_INVALID, "texture %u of %zu", index, c->textures.size());
+  hk_ctx::HostTexture& t = c->textures[index];
+  HK_REQUIRE(image->width == t.w && image->height == t.h, HK_E_INVALID, "texture %u is %u x %u, the image %u x %u: a texture that changes size goes through hk_upload_textures",
+             index, t.w, t.h, image->width, image->height);
+  HK_REQUIRE(image->address_u <= HK_ADDRESS_MIRROR_REPEAT && image->address_v <= HK_ADDRESS_MIRROR_REPEAT, HK_E_INVALID, "bad address mode");
+  c->scene_epoch += 1;   // (scene memory is written from here on: hk_context.hpp, primary-ray pipelining - a refusal above leaves it alone)
+  const uint32_t flags = (image->is_srgb ? 1u : 0u) | (image->filter_linear ? 2u : 0u) | (image->address_u << 4) | (image->address_v << 6);
+  const size_t n = t.texels.size();
+  size_t texel_offset = 0;
+  for (uint32_t i = 0; i < index; ++i) texel_offset += c->textures[i].texels.size();
+  // what a pending relayout (finalize_scene) is about to send anyway travels with it, from the mirror below
+  const bool texels_live = !c->textures_dirty && c->d_tex_data.p && c->d_tex_data.n >= texel_offset + n;
+  const bool info_live = !c->dynamic_dirty && !c->mesh_dirty && c->scene_mem;
+  if (texels_live || info_live) {
+    HK_HIP(hipSetDevice(c->device));
+    int rc, k = 0;
+    uint8_t* st = nullptr;
+    if (texels_live) {
+      if ((rc = stage(c, n * 4, &st, &k))) return rc;
+      memcpy(st, image->rgba8, n * 4);
+    }
+    if ((rc = join_all(c))) return rc;
+    uint4 *info0 = nullptr, *info1 = nullptr;
+    if (info_live) {
+      info0 = (uint4*)(c->scene_mem + c->dyn_off.tex_info) + index;
+      if (c->two_slots) info1 = (uint4*)(c->scene_mem + c->dyn_capacity + c->dyn_off.tex_info) + index;
+    }
+    launch_texture_update(c->stream, c->d_tex_data.p + texel_offset, (const uint32_t*)st, texels_live ? n : 0, info0, info1, make_uint4((uint32_t)texel_offset, t.w, t.h, flags));
+    HK_HIP(hipGetLastError());
+    if (texels_live) {
+      hk_ctx::DeformStage& s = c->df_stage[(size_t)k];
+      HK_HIP(hipEventRecord(s.done, c->stream));
+      s.pending = true;
+    }
+  }
+  memcpy(t.texels.data(), image->rgba8, n * 4);
+  t.flags = flags;
   return HK_OK;
 }
 int hk_upload_noise(hk_ctx* c, const uint8_t* rgba, size_t bytes) {

@@ -58,6 +58,14 @@ void free_refit(hk_ctx* c) {
   c->lbvh_scratch = nullptr;
   c->lbvh_scratch_cap = 0;
   for (int k = 0; k < 2; ++k) {
+    if (c->mt_updates[k]) (void)hipHostFree(c->mt_updates[k]);
+    if (c->mt_done[k]) (void)hipEventDestroy(c->mt_done[k]);
+    c->mt_updates[k] = nullptr;
+    c->mt_done[k] = nullptr;
+    c->mt_updates_cap[k] = 0;
+    c->mt_pending[k] = false;
+  }
+  for (int k = 0; k < 2; ++k) {
     if (c->rf_updates[k]) (void)hipHostFree(c->rf_updates[k]);
     if (c->rf_done[k]) (void)hipEventDestroy(c->rf_done[k]);
     c->rf_updates[k] = nullptr;
@@ -255,6 +263,10 @@ static int refit_impl(hk_ctx* c, hk_scene_builder* b, uint32_t* moved_out, bool 
     moved.push_back(i);
   }
   if (moved_out) *moved_out = (uint32_t)moved.size();
+  // hk_update_materials switched an emitter in this frame and took these poses along (hk_update_scene_instances' path): nothing is left
+  // to do - the instances that moved in it keep their `moved` flag until the next frame's refit
+  // (rf_motion_taken: set by update_materials_impl's case B, cleared by the next frame - context.hip ready())
+  if (moved.empty() && c->rf_motion_taken) return HK_OK;
   if ((rc = prepare_refit(c))) return rc;
   {  // instances that moved in the previous update and rest now: their `moved` flag goes (previous model = model)
     std::vector<uint8_t> now(ni, 0);
@@ -336,3 +348,120 @@ static int refit_impl(hk_ctx* c, hk_scene_builder* b, uint32_t* moved_out, bool 
 }
 int hk_refit_scene_instances(hk_ctx* c, hk_scene_builder* b, uint32_t* moved_out) { return refit_impl(c, b, moved_out, true); }}  // extern "C"
 int hk::refit_instances_impl(hk_ctx* c, hk_scene_builder* b, uint32_t* moved, bool commit) { return refit_impl(c, b, moved, commit); }
+
+// ---- material edits on the device (hikari_hip.h hk_update_materials; kernels in kernels_scene.hip) ---------------------------------
+// The reference re-runs prepare_instances when a material changes (instance.rs:352-437).  What a change of VALUES touches is the
+// material record and, for emitters, the radius (instance.rs:382,409) with the light tree's leaf boxes: a few records through pinned
+// memory, one kernel over the emitters concerned and the light-tree refit (case A).  Only an emitter switched on or off changes the
+// layout of the region: that edit takes the instance-set path, hk_update_scene_instances (case B).
+// The instance-level records of a builder finished with stand-in trees, then both trees built on the device - what every band but the
+// one that finished the builder does in hk_multi_update_scene_instances / hk_multi_update_materials.  Stand-in trees never stay
+// (hk_update_scene_instances): if the upload went through and the build did not, the next use lays the region out again.
+int hk::upload_instances_and_build_trees(hk_ctx* c, const hk_scene_builder* b, uint32_t tree_mode) {
+  uint32_t ni = 0;
+  const HkInstance* inst = nullptr;
+  int rc;
+  if ((rc = hk_scene_builder_instances(b, &inst, &ni))) return rc;
+  if ((rc = upload_scene_instances_unchecked(c, b))) return rc;   // (its refusals write nothing)
+  if (ni >= 2 && (rc = hk_rebuild_scene_trees(c, tree_mode))) c->dynamic_dirty = true;
+  return rc;
+}
+int hk::update_materials_impl(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode, uint32_t* changed_out, bool finish) {
+  HK_REQUIRE(c && b, HK_E_INVALID, "NULL argument");
+  HK_REQUIRE(tree_mode == HK_TREE_SAH || tree_mode == HK_TREE_LBVH, HK_E_INVALID, "unknown tree build mode %u", tree_mode);
+  HK_REQUIRE(c->have_meshes && c->have_materials && c->have_instances, HK_E_NOT_READY, "hk_upload_scene must come first");
+  {
+    InstanceDecl d;
+    HK_REQUIRE(builder_instance_count(b) == 0u || builder_instance_decl(b, 0u, &d), HK_E_NOT_READY,
+               "the builder has unfinished mesh changes (hk_scene_builder_finish + hk_upload_scene first)");
+  }
+  HK_NO_PENDING_MESHES(b);
+  HK_HIP(hipSetDevice(c->device));
+  int rc;
+  if ((rc = finalize_scene(c))) return rc;
+  const HkMaterial* mats = nullptr;
+  uint32_t nm = 0;
+  builder_materials(b, &mats, &nm);
+  HK_REQUIRE(nm == c->materials.size(), HK_E_INVALID, "the builder has %u materials, the uploaded scene %zu: materials were added (use hk_upload_scene)", nm, c->materials.size());
+  // which records differ from the ones the device holds; 1: values, 2: the emissive colour too (bit for bit)
+  std::vector<uint8_t> differs(nm, 0);
+  std::vector<uint32_t> ids;
+  const uint32_t n_tex = (uint32_t)c->textures.size();
+  for (uint32_t i = 0; i < nm; ++i) {
+    if (memcmp(&mats[i], &c->materials[i], sizeof(HkMaterial)) == 0) continue;
+    for (uint32_t id : {mats[i].base_color_texture, mats[i].emissive_texture, mats[i].metallic_roughness_texture, mats[i].occlusion_texture})
+      HK_REQUIRE(id == HK_NO_TEXTURE || id < n_tex, HK_E_INVALID, "material %u references texture %u but only %u textures are uploaded", i, id, n_tex);
+    differs[i] = memcmp(mats[i].emissive, c->materials[i].emissive, 16) == 0 ? 1 : 2;
+    ids.push_back(i);
+  }
+  if (changed_out) *changed_out = (uint32_t)ids.size();
+  if (ids.empty()) return HK_OK;
+  c->scene_epoch += 1;   // (scene memory is written from here on: hk_context.hpp, primary-ray pipelining - a refusal above leaves it alone)
+  // case B: an instance starts or stops emitting - the emitter list, the alias tables and the light tree change size - or the builder's
+  // instance set is not the uploaded one (instances added or removed, another mesh or material for one: what the refit refuses): case A
+  // works from the context's instance records and would drop such an edit, the instance-set path takes it along
+  const uint32_t ni = (uint32_t)c->instances.size();
+  bool set_changes = builder_instance_count(b) != ni;
+  for (uint32_t i = 0; i < ni && !set_changes; ++i) {
+    const HkInstance& in = c->instances[i];
+    InstanceDecl d;
+    set_changes = !builder_instance_decl(b, i, &d) || d.material != in.material || memcmp(&d.mesh, &in.mesh, sizeof(HkMeshIndex)) != 0 ||
+                  (differs[in.material] == 2 && material_emits(mats[in.material]) != material_emits(c->materials[in.material]));
+  }
+  if (set_changes) {
+    // (refusals - a mesh deformed on the device - come from the path taken, before it writes anything: the old materials then return)
+    std::vector<HkMaterial> old(mats, mats + nm);
+    c->materials.swap(old);
+    // a later band of hk_multi_update_materials finds the builder finished already, with stand-in trees
+    rc = finish ? hk_update_scene_instances(c, b, tree_mode) : upload_instances_and_build_trees(c, b, tree_mode);
+    if (rc) c->materials.swap(old);
+    else c->rf_motion_taken = true;   // (hk_context.hpp: poses set on the builder travelled with this update)
+    return rc;
+  }
+  // case A.  The device's current boxes first (a mesh deformed since the last frame), as hk_rebuild_scene_trees does
+  if ((rc = flush_deform(c))) return rc;
+  std::vector<uint32_t> emitters;  // whose instance uses a material with a new emissive colour
+  for (size_t e = 0; e < c->emissives.size(); ++e)
+    if (differs[c->instances[c->emissives[e].instance].material] == 2) emitters.push_back((uint32_t)e);
+  if (!emitters.empty() && (rc = prepare_refit(c))) return rc;
+  // pinned records - the materials, then the emitter ids - double-buffered against the kernels that read them
+  const size_t rec_bytes = ids.size() * sizeof(hkd::MaterialUpdate), bytes = rec_bytes + emitters.size() * 4;
+  const int k = c->mt_k;
+  c->mt_k ^= 1;
+  if (c->mt_pending[k]) {
+    HK_HIP(hipEventSynchronize(c->mt_done[k]));
+    c->mt_pending[k] = false;
+  }
+  if (c->mt_updates_cap[k] < bytes) {
+    if (c->mt_updates[k]) (void)hipHostFree(c->mt_updates[k]);
+    c->mt_updates[k] = nullptr;
+    c->mt_updates_cap[k] = 0;
+    const size_t cap = bytes + bytes / 2 + 256;
+    HK_HIP(hipHostMalloc((void**)&c->mt_updates[k], cap, hipHostMallocDefault));
+    c->mt_updates_cap[k] = cap;
+  }
+  if (!c->mt_done[k]) HK_HIP(hipEventCreateWithFlags(&c->mt_done[k], hipEventDisableTiming));
+  hkd::MaterialUpdate* records = (hkd::MaterialUpdate*)c->mt_updates[k];
+  for (size_t u = 0; u < ids.size(); ++u) {
+    records[u].material = ids[u];
+    records[u].pad[0] = records[u].pad[1] = records[u].pad[2] = 0u;
+    material_rows(mats[ids[u]], records[u].rows);
+  }
+  uint32_t* emitter_ids = (uint32_t*)(c->mt_updates[k] + rec_bytes);
+  if (!emitters.empty()) memcpy(emitter_ids, emitters.data(), emitters.size() * 4);
+  // frames in flight keep reading the slot they were enqueued with (begin_device_update)
+  if ((rc = begin_device_update(c))) return rc;
+  const hkd::RefitScene r = refit_scene(c);
+  uint8_t* base = c->scene_mem + (size_t)c->slot * c->dyn_capacity;
+  launch_material_update(c->stream, r, (float4*)(base + c->dyn_off.materials), records, (uint32_t)ids.size(), emitter_ids, (uint32_t)emitters.size(),
+                         (float4*)(base + c->dyn_off.light_lo), (float4*)(base + c->dyn_off.light_hi), (uint32_t)c->emissive_nodes.size());
+  HK_HIP(hipGetLastError());
+  HK_HIP(hipEventRecord(c->mt_done[k], c->stream));
+  c->mt_pending[k] = true;
+  // the update is enqueued: now the host mirror follows (an error above leaves host and device agreeing)
+  for (uint32_t e : emitters) memcpy(c->emissives[e].emissive, mats[c->instances[c->emissives[e].instance].material].emissive, 16);
+  c->materials.assign(mats, mats + nm);
+  if (!emitters.empty()) c->mirrors_stale = true;  // (radius and light-tree boxes are the device's from here on)
+  return HK_OK;
+}
+extern "C" int hk_update_materials(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode, uint32_t* changed) { return hk::update_materials_impl(c, b, tree_mode, changed, true); }

@@ -530,6 +530,18 @@ class MultiEngine:
     def update_instances_on_device(self, builder, mode=F.TREE_SAH):
         self.api.call("multi_update_scene_instances", self.h, builder.h, mode)
 
+    def update_materials(self, builder, mode=F.TREE_SAH):
+        """hk_multi_update_materials: the material values set on `builder` go to every band's device copy of the scene."""
+        changed = C.c_uint32()
+        self.api.call("multi_update_materials", self.h, builder.h, mode, C.byref(changed))
+        return changed.value
+
+    def update_texture(self, index, image):
+        """hk_multi_update_texture: one texture's texels and sampler, in place on every band's device."""
+        from .plugin import image_desc
+
+        self.api.call("multi_update_texture", self.h, index, C.byref(image_desc(image)))
+
     def gather(self, buffer, root=0):
         """hk_multi_gather: band `root`'s context collects every band's rows of `buffer` on its own device."""
         self.api.call("multi_gather", self.h, buffer, root)

@@ -410,6 +410,11 @@ class SceneBuilder:
     def set_instance_material(self, instance_id, material_id):
         self.api.call("scene_builder_set_instance_material", self.h, instance_id, material_id)
 
+    def set_material(self, material_id, material):
+        """New values for an existing material (hk_scene_builder_set_material): the next finish() redoes the instance-level work only;
+        Engine.update_materials(builder) is the device path of the same edit."""
+        self.api.call("scene_builder_set_material", self.h, material_id, C.byref(material))
+
     def set_mesh_vertices(self, mesh_id, positions, normals=None):
         """The host mirror of a deformation (hk_scene_builder_set_mesh_vertices): same topology, tree boxes refit; finish() + upload next."""
         pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1)
@@ -514,6 +519,18 @@ def _present_formats():
             "rgba8-srgb": (F.FORMAT_RGBA8_UNORM_SRGB, torch.uint8), "bgra8-srgb": (F.FORMAT_BGRA8_UNORM_SRGB, torch.uint8)}
 
 
+def image_desc(im):
+    """An HkImageDesc from dict(rgba=uint8[h][w][4], srgb, address_u, address_v, linear); the pixel array stays alive with the record."""
+    a = np.ascontiguousarray(im["rgba"], dtype=np.uint8)
+    assert a.ndim == 3 and a.shape[2] == 4
+    d = F.HkImageDesc()
+    d.rgba8, d.height, d.width = a.ctypes.data, a.shape[0], a.shape[1]
+    d.is_srgb, d.filter_linear = int(im.get("srgb", True)), int(im.get("linear", True))
+    d.address_u, d.address_v = im.get("address_u", F.ADDRESS_REPEAT), im.get("address_v", F.ADDRESS_REPEAT)
+    d._pixels = a
+    return d
+
+
 class Engine:
     """One context of the C ABI (`hk_ctx`).  `api` defaults to the product library."""
 
@@ -579,6 +596,15 @@ class Engine:
         """Instances added / removed / re-materialed on `builder`: hk_update_scene_instances (host lays out the records, the device
         builds both trees)."""
         self.api.call("update_scene_instances", self.ctx, builder.h, mode)
+
+    def update_materials(self, builder, mode=F.TREE_SAH):
+        """Material edits on the device (hk_update_materials): the values set on `builder` (SceneBuilder.set_material) since the materials
+        were last uploaded / updated.  Emitters that stay emitters are re-derived and the light tree refit in place; an emitter switched
+        on or off takes the path of update_instances_on_device (trees built in `mode`).  In a frame that also moves instances call this
+        before refit_instances.  Returns the number of material records that changed."""
+        changed = C.c_uint32()
+        self.api.call("update_materials", self.ctx, builder.h, mode, C.byref(changed))
+        return changed.value
 
     def rebuild_trees(self, mode=F.TREE_SAH):
         """New instance tree and light tree over the current boxes, built on the device (hk_rebuild_scene_trees): F.TREE_SAH = the
@@ -654,16 +680,14 @@ class Engine:
     def upload_textures(self, images):
         """images: list of dict(rgba=uint8[h][w][4], srgb=bool, address_u/address_v=F.ADDRESS_*, linear=bool) -
         the `textures` / `samplers` binding arrays (mod.rs:760-782).  Material *_texture ids index this list."""
-        descs = (F.HkImageDesc * max(len(images), 1))()
-        keep = []
-        for d, im in zip(descs, images):
-            a = np.ascontiguousarray(im["rgba"], dtype=np.uint8)
-            assert a.ndim == 3 and a.shape[2] == 4
-            keep.append(a)
-            d.rgba8, d.height, d.width = a.ctypes.data, a.shape[0], a.shape[1]
-            d.is_srgb, d.filter_linear = int(im.get("srgb", True)), int(im.get("linear", True))
-            d.address_u, d.address_v = im.get("address_u", F.ADDRESS_REPEAT), im.get("address_v", F.ADDRESS_REPEAT)
+        one = [image_desc(im) for im in images]   # (each keeps its pixel array alive until the call has copied it)
+        descs = (F.HkImageDesc * max(len(images), 1))(*one)
         self.api.call("upload_textures", self.ctx, descs, len(images))
+
+    def update_texture(self, index, image):
+        """New texels and sampler of ONE uploaded texture of the same size (hk_update_texture), in place and without a host wait; `image`
+        as in upload_textures."""
+        self.api.call("update_texture", self.ctx, index, C.byref(image_desc(image)))
 
     def upload_noise(self, noise=None):
         noise = load_noise() if noise is None else np.ascontiguousarray(noise, dtype=np.uint8)

@@ -296,6 +296,9 @@ class SceneBuilder {  // the Prepare-stage host work: mesh -> BLAS, TLAS, emissi
   void set_instance_transform(uint32_t instance, const float transform[16]) {
     check(hk_scene_builder_set_instance_transform(h_, instance, transform), "hk_scene_builder_set_instance_transform");
   }
+  // new values for an existing material (`materials.get_mut(handle)`): the next finish() redoes the instance-level work only;
+  // HikariPlugin::update_materials is the device path of the same edit
+  void set_material(uint32_t material, const HkMaterial& m) { check(hk_scene_builder_set_material(h_, material, &m), "hk_scene_builder_set_material"); }
   void finish() { check(hk_scene_builder_finish(h_), "hk_scene_builder_finish"); }
   const hk_scene_builder* handle() const { return h_; }
   hk_scene_builder* handle() { return h_; }
@@ -410,6 +413,15 @@ class HikariPlugin {
     return moved;
   }
   void rebuild_trees(uint32_t mode = HK_TREE_SAH) { check(hk_rebuild_scene_trees(ctx_.get(), mode), "hk_rebuild_scene_trees"); }
+  // material edits on the device: the values set on `b` (SceneBuilder::set_material) since the last upload / update; before
+  // refit_instances in a frame that also moves instances.  Returns how many records changed
+  uint32_t update_materials(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) {
+    uint32_t changed = 0;
+    check(hk_update_materials(ctx_.get(), b.handle(), tree_mode, &changed), "hk_update_materials");
+    return changed;
+  }
+  // new texels and sampler of one uploaded texture of the same size, in place
+  void update_texture(uint32_t index, const HkImageDesc& image) { check(hk_update_texture(ctx_.get(), index, &image), "hk_update_texture"); }
   // a new tree over the current triangles of one deformed mesh, built on the device in place (later deformations refit the new shape)
   void rebuild_mesh_tree(const HkMeshIndex& mesh, uint32_t mode = HK_TREE_SAH) { check(hk_rebuild_mesh_tree(ctx_.get(), &mesh, mode), "hk_rebuild_mesh_tree"); }
 
@@ -486,6 +498,12 @@ class HikariMultiGpuPlugin {
     return moved;
   }
   void rebuild_trees(uint32_t mode = HK_TREE_SAH) { check(hk_multi_rebuild_scene_trees(m_, mode), "hk_multi_rebuild_scene_trees"); }
+  uint32_t update_materials(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) {
+    uint32_t changed = 0;
+    check(hk_multi_update_materials(m_, b.handle(), tree_mode, &changed), "hk_multi_update_materials");
+    return changed;
+  }
+  void update_texture(uint32_t index, const HkImageDesc& image) { check(hk_multi_update_texture(m_, index, &image), "hk_multi_update_texture"); }
   void rebuild_mesh_tree(const HkMeshIndex& mesh, uint32_t mode = HK_TREE_SAH) { check(hk_multi_rebuild_mesh_tree(m_, &mesh, mode), "hk_multi_rebuild_mesh_tree"); }
   // rows of last frame's reservoirs fetched across the band borders before reprojection (0 for a static camera)
   void set_history_rows(uint32_t rows) { check(hk_multi_set_history_rows(m_, rows), "hk_multi_set_history_rows"); }

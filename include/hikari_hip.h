@@ -485,6 +485,12 @@ int hk_scene_builder_finish_instances(hk_scene_builder* b);
  * shifts the ids of the instances added after it down by one; its transform history goes with it. */
 int hk_scene_builder_remove_instance(hk_scene_builder* b, uint32_t instance_id);
 int hk_scene_builder_set_instance_material(hk_scene_builder* b, uint32_t instance_id, uint32_t material_id);
+/* New values for an existing material (Bevy: `materials.get_mut(handle)`, which makes prepare_instances run again, instance.rs:352-437).
+ * Like hk_scene_builder_set_instance_material it un-finishes the builder at the instance level only - meshes and their trees are kept -
+ * and the next finish gives exactly what a builder that had these values from the start gives (emitter radius, emitter list, alias
+ * tables and light tree included).  HK_E_INVALID for NULL or an unknown id: the builder is unchanged and still finished if it was.
+ * The device path of the same edit is hk_update_materials. */
+int hk_scene_builder_set_material(hk_scene_builder* b, uint32_t material_id, const HkMaterial* material);
 /* Dynamic scenes (instance.rs:352-437 re-runs whenever an instance changes): replace an instance's
  * transform after a finish; the next finish redoes only the instance-level work (world AABBs, TLAS,
  * emissive list, alias tables, light BVH) - meshes and their BLAS are kept.  The transform the
@@ -565,7 +571,9 @@ typedef struct HkImageDesc {
  * previous-transform bookkeeping advances as it would in hk_scene_builder_finish.
  * After a device-side update the host copies of the trees and emitter records are stale: an upload that re-lays the instance-level
  * region out from them (hk_upload_materials, hk_upload_textures) is refused with HK_E_NOT_READY at the next frame until
- * hk_upload_scene_instances / hk_upload_instances brings the host's version of the scene back. */
+ * hk_upload_scene_instances / hk_upload_instances brings the host's version of the scene back.
+ * After an hk_update_materials that switched an emitter (its case B took the builder's poses along) a refit called before the next
+ * frame with no pose left to change returns at once: the instances that moved in that update keep their `moved` flag for the frame. */
 int hk_refit_scene_instances(hk_ctx* ctx, hk_scene_builder* b, uint32_t* moved);
 /* ... and the REBUILD on the device, for when refits have degraded a tree: new trees over the instances' and the emitters' current
  * boxes, written in place in the flatten_custom layout (all direction-threaded orderings of the instance tree; child order of
@@ -586,6 +594,35 @@ int hk_refit_scene_instances(hk_ctx* ctx, hk_scene_builder* b, uint32_t* moved);
  * hk_upload_scene_instances gives (the reference's path), minus the two host-side SAH builds that dominate it. */
 int hk_update_scene_instances(hk_ctx* ctx, hk_scene_builder* b, uint32_t tree_mode);
 int hk_rebuild_scene_trees(hk_ctx* ctx, uint32_t mode);
+/* Material edits on the DEVICE.  The builder's materials (hk_scene_builder_set_material; the builder need not be finished) are diffed
+ * against the materials the context holds, as hk_refit_scene_instances diffs poses; *changed (optional) = the records that differ.
+ * With none the call returns HK_OK and enqueues nothing.  Otherwise one of two cases, decided inside the call by the builder's own rule
+ * for which instances emit (255 a |rgb| of the material's emissive colour > 0, instance.rs:380-382):
+ *   A  the set of emitting instances stays.  Everything happens on the device, stream-ordered like a refit: no host wait, in the spare
+ *      slot of a two-slot scene and in place behind everything enqueued in a one-slot scene, after the boxes of meshes deformed since
+ *      the last frame have reached the instance level.  The changed records (80 B each) are read by a kernel from pinned,
+ *      double-buffered memory and written into the slot's material array.  Only if a changed material's emissive colour differs bit for
+ *      bit, one more kernel re-derives position and radius (0.5 |max - min| + sqrt(255 a |rgb|), instance.rs:382,409) of every emitter
+ *      whose instance uses such a material, from the instance's CURRENT device box, and the light tree is refit in its current shape -
+ *      the rule of hk_refit_scene_instances; hk_rebuild_scene_trees brings the SAH shape back.  The instance tree, its wide records, the
+ *      alias tables and surface areas are untouched; `tree_mode` is validated and not used; the builder's previous-transform
+ *      bookkeeping does not advance.  The host copies become stale (see hk_refit_scene_instances) only if an emitter record changed:
+ *      an edit of base colours on a context never refit leaves hk_upload_textures and the other relayout paths usable.  Case A works
+ *      after refits, device tree rebuilds and mesh deformations - the states in which hk_upload_materials is refused.
+ *   B  an emitter is switched on or off: the emitter list, the alias tables and the light tree change size.  The context takes the new
+ *      materials and does what hk_update_scene_instances(ctx, b, tree_mode) does - hk_scene_builder_finish_instances, the asynchronous
+ *      upload into the spare slot, both trees built on the device - with that call's contract: HK_TREE_SAH gives the host builder's
+ *      trees link for link, HK_E_NOT_READY after a mesh deformation, poses set on the builder since the last update are taken along and
+ *      the transform bookkeeping advances.  A builder whose instance set is not the uploaded one (instances added or removed, another
+ *      mesh or material for one - what hk_refit_scene_instances refuses) takes this path too whenever a material record changed, so
+ *      the pending edit travels with it; with no record changed the call enqueues nothing and such edits wait for
+ *      hk_update_scene_instances.
+ * So in a frame that both moves instances and edits materials, call hk_update_materials BEFORE hk_refit_scene_instances: the refit then
+ * finds nothing left to do in case B and does the motion in case A.
+ * Refused with nothing written: NULL, an unknown tree_mode, a builder whose material count differs from the uploaded one (materials
+ * added go through hk_upload_scene), a changed record naming a texture id >= the uploaded texture count (HK_E_INVALID); no scene, a
+ * builder with unfinished mesh changes or deferred meshes (HK_E_NOT_READY). */
+int hk_update_materials(hk_ctx* ctx, hk_scene_builder* b, uint32_t tree_mode, uint32_t* changed);
 /* Mesh deformation on the DEVICE: new vertex data for one uploaded mesh, its BLAS refit in every layout that holds it, the change
  * carried up to the instances of the mesh (world AABBs, emitter records and alias tables) and to the instance tree and the light tree.
  * A mesh is named by the HkMeshIndex its instances carry (it must equal an uploaded instance's record); its topology (index buffer,
@@ -645,6 +682,13 @@ int hk_rebuild_mesh_tree(hk_ctx* ctx, const HkMeshIndex* mesh, uint32_t mode);
  * begun leaves the context WITHOUT a scene (HK_E_NOT_READY at the next frame), never with stand-in trees. */
 int hk_load_scene(hk_ctx* ctx, hk_scene_builder* b, uint32_t tree_mode);
 int hk_upload_textures(hk_ctx* ctx, const HkImageDesc* images, uint32_t n_images);
+/* New texels and sampler fields for ONE uploaded texture of the same width and height (an animated texture; hk_upload_textures replaces
+ * the whole array behind a host wait).  The texels go through the pinned staging pool of the deformations and land in place in the
+ * texel buffer, behind every enqueued kernel that can read texels on whichever stream (the context's events: no host wait); the 16-B
+ * descriptor (sRGB flag, address modes, filter) is rewritten in the slot in use - in both slots of a two-slot scene.  Works whatever
+ * was changed on the device before (refits, tree rebuilds, deformations).  HK_E_INVALID with nothing written for NULL, index >= the
+ * uploaded count, a size that differs or an address mode out of range; HK_E_NOT_READY when no textures have been uploaded. */
+int hk_update_texture(hk_ctx* ctx, uint32_t index, const HkImageDesc* image);
 /* InstanceRenderAssets::set + write_buffer, instance.rs:82-108 */
 int hk_upload_instances(hk_ctx* ctx, const HkInstance* instances, uint32_t n_instances, const HkNode* instance_nodes,
                         uint32_t n_instance_nodes, const HkEmissive* emissives, uint32_t n_emissives,
@@ -997,6 +1041,9 @@ int hk_multi_migrate_bands(hk_multi* m, const uint32_t* new_bounds, uint32_t n_b
 int hk_multi_gather(hk_multi* m, uint32_t buffer, uint32_t root);  /* hk_set_band_bounds on every band's context */
 int hk_multi_update_scene_instances(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode);  /* hk_update_scene_instances on every band's replica */
 int hk_multi_upload_textures(hk_multi* m, const HkImageDesc* images, uint32_t n_images);
+/* hk_update_materials / hk_update_texture on every band's replica (an emitter switched on or off finishes the builder once) */
+int hk_multi_update_materials(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode, uint32_t* changed);
+int hk_multi_update_texture(hk_multi* m, uint32_t index, const HkImageDesc* image);
 int hk_multi_upload_noise(hk_multi* m, const uint8_t* rgba, size_t bytes);
 int hk_multi_resize(hk_multi* m, uint32_t width, uint32_t height, float upscale_ratio);
 int hk_multi_set_history_rows(hk_multi* m, uint32_t rows);
