@@ -128,7 +128,7 @@ struct MaterialUpdate {    // one record per material whose values changed (hk_u
   uint32_t pad[3];
   float4 rows[4];          // the material's four float4 of the device layout (scene_layout.hip build_dynamic_region)
 };
-// Mesh deformation (kernels_deform.hip, kernels_scene.hip; host side mesh_deform.hip): one mesh BLAS of n triangles as the binary tree
+// Mesh deformation (kernels_deform.hip, kernels_tree.hip; host side mesh_deform.hip): one mesh BLAS of n triangles as the binary tree
 // behind its flat layout - internal nodes in the preorder of ordering 0 (root 0), leaves in ordering 0's order as tree nodes n - 1 + j -
 // with the work planes of a bottom-up refit.
 struct MeshTree {
@@ -140,7 +140,7 @@ struct MeshTree {
   float4 *node_lo, *node_hi;                       // per tree node (2n - 1)
   float4 *tri_lo, *tri_hi;                         // per triangle: its box
 };
-// One mesh of a forest build (kernels_scene.hip launch_forest_build; hk_load_scene): the trees of many meshes built together
+// One mesh of a forest build (kernels_tree.hip launch_forest_build; hk_load_scene): the trees of many meshes built together
 struct ForestMesh {
   uint32_t tri_begin, n_tris;   // the mesh's positions in the batch: the meshes of a batch tile [0, all its triangles)
   uint32_t primitive;           // its first triangle in the triangle planes
@@ -362,15 +362,27 @@ void launch_material_update(hipStream_t st, const hkd::RefitScene& s, float4* ma
                             uint32_t n_emitters, float4* light_lo, float4* light_hi, uint32_t light_count);
 // hk_update_texture: n texels from pinned memory to their place in the texel buffer, and the texture's descriptor into `info0` / `info1` (or NULL)
 void launch_texture_update(hipStream_t st, uint32_t* dst, const uint32_t* src, size_t n, uint4* info0, uint4* info1, uint4 info);
-// LBVH rebuild of a flat skip-link BVH over n shapes (kernels_scene.hip): scratch size, and the build into `lo` / `hi` (`stride`
-// float4 between consecutive nodes: 2 for the interleaved TLAS, 1 for the two planes of the light BVH)
-size_t lbvh_scratch_bytes(uint32_t n, size_t* sort_temp_bytes);
-// `ord_stride`: float4 between orderings (0: the tree's own 3n - 2 nodes); `keep`: a mesh tree that takes the new topology over (and whose
-// ordering 0 stays left before right in either mode); `one_workgroup_top`: the SAH build's top levels in one workgroup at any n (A/B)
-int launch_tree_build(hipStream_t st, int mode /* 0 LBVH, 1 the reference's binned SAH */, bool light, const hkd::RefitScene& s, uint32_t n, const float4* box_lo,
-                      const float4* box_hi, void* scratch, float4* lo, float4* hi, uint32_t stride, uint32_t orderings, size_t ord_stride = 0,
-                      const hkd::MeshTree* keep = nullptr, bool one_workgroup_top = false, bool mesh_tree = false, uint32_t* launches = nullptr);
-// `mesh_tree`: a mesh tree without a MeshTree to keep (hk_load_scene); `launches`: the kernel launches of the build are added to it.
+// A new tree over n shapes, built on the device into a flat skip-link BVH (kernels_tree.hip): the scratch one build needs in either
+// mode, and the build
+size_t lbvh_scratch_bytes(uint32_t n);
+struct TreeBuild {
+  int mode = 0;                            // 0 LBVH (Morton order), 1 the reference's binned SAH
+  uint32_t n = 0;                          // shapes
+  // the shapes: their boxes, or - box_lo == nullptr, the light tree - the emitters of `scene` (position -/+ radius)
+  const float4 *box_lo = nullptr, *box_hi = nullptr;
+  const hkd::RefitScene* scene = nullptr;
+  // the node array to overwrite: `stride` float4 between consecutive nodes (2: interleaved lo / hi pairs, 1: two planes), `ord_stride`
+  // float4 between orderings (0: the tree's own 3n - 2 nodes)
+  float4 *lo = nullptr, *hi = nullptr;
+  uint32_t stride = 2, orderings = 1;
+  size_t ord_stride = 0;
+  bool mesh_tree = false;                  // a mesh tree: ordering 0 stays left before right in either mode, the SAH top may take the whole chip
+  const hkd::MeshTree* keep = nullptr;     // a mesh tree (mesh_tree must be set) that takes the new topology over, for its later refits
+  bool one_workgroup_top = false;          // the SAH build's top levels in one workgroup at any n (A/B)
+  void* scratch = nullptr;                 // lbvh_scratch_bytes(n)
+  uint32_t* launches = nullptr;            // the kernel launches of the build are added to it
+};
+int launch_tree_build(hipStream_t st, const TreeBuild& d);
 // The trees of MANY meshes in one build (`nodes` = the mesh-level node array, interleaved lo / hi pairs, `ord_stride` float4 between its
 // orderings): the number of launches does not depend on the number of meshes.  Every mesh below hkd's SAH_WIDE_MIN triangles.
 size_t forest_scratch_bytes(uint32_t n_tris, uint32_t n_meshes, int mode);

@@ -1,35 +1,18 @@
 // kernels_deform.hip - new vertex data of one mesh on the device (hk_update_mesh_vertices, hk_skin_mesh; host side mesh_deform.hip):
 // the vertices of the mesh land in its normal plane and in a position scratch plane, the mesh box is reduced on the way, then every
-// triangle of the mesh takes its three positions into the triangle planes and its box into the refit's leaf boxes (kernels_scene.hip
+// triangle of the mesh takes its three positions into the triangle planes and its box into the refit's leaf boxes (kernels_tree.hip
 // launch_mesh_tree_refit carries on from there).  Streaming kernels, one thread per vertex / per triangle.
 #include <hip/hip_runtime.h>
 
+#include "hk_box.hpp"
 #include "hk_device.hpp"
 #include "hk_kernels.hpp"
 
 namespace hkd {
 
 namespace {
-// the host's hmin / hmax (hk_context.hpp: IEEE minNum / maxNum with -0 < +0): the leaf boxes of build_static_region, operation for operation
-__device__ __forceinline__ float leaf_min(float a, float b) {
-  if (a != a) return b;
-  if (b != b) return a;
-  if (a == b) return signbit(a) ? a : b;
-  return a < b ? a : b;
-}
-__device__ __forceinline__ float leaf_max(float a, float b) {
-  if (a != a) return b;
-  if (b != b) return a;
-  if (a == b) return signbit(a) ? b : a;
-  return a > b ? a : b;
-}
-// mesh box words: a float mapped to a u32 whose unsigned order is the float order with -0 < +0, so that atomicMin / atomicMax give the
-// min / max over the vertices whatever order they arrive in (decoded by kernels_scene.hip k_mesh_instances)
-__device__ __forceinline__ uint32_t box_word(float f) {
-  const uint32_t u = f2u(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-// one wave reduces its lanes' positions, lane 0 adds them to the six words (words 0-2 min, 3-5 max)
+// the mesh box as six order-preserving words (hk_box.hpp box_word; decoded by kernels_scene.hip k_mesh_instances): atomicMin / atomicMax
+// give the min / max over the vertices whatever order they arrive in.  One wave reduces its lanes' positions, lane 0 adds them to the six words (words 0-2 min, 3-5 max)
 __device__ __forceinline__ void reduce_box(uint32_t* box, bool valid, float x, float y, float z) {
   uint32_t mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0u, 0u, 0u};
   if (valid) {
@@ -139,8 +122,7 @@ __global__ __launch_bounds__(256) void k_mesh_triangles(const float4* __restrict
   v0[t] = q[0];
   v1[t] = q[1];
   v2[t] = q[2];
-  tri_lo[t] = make_float4(leaf_min(q[0].x, leaf_min(q[1].x, q[2].x)), leaf_min(q[0].y, leaf_min(q[1].y, q[2].y)), leaf_min(q[0].z, leaf_min(q[1].z, q[2].z)), 0.0f);
-  tri_hi[t] = make_float4(leaf_max(q[0].x, leaf_max(q[1].x, q[2].x)), leaf_max(q[0].y, leaf_max(q[1].y, q[2].y)), leaf_max(q[0].z, leaf_max(q[1].z, q[2].z)), 0.0f);
+  triangle_box(q[0], q[1], q[2], tri_lo[t], tri_hi[t]);
 }
 
 // ... the boxes alone, of triangles nobody has moved yet (hk_rebuild_mesh_tree on a mesh never deformed)
@@ -148,9 +130,7 @@ __global__ __launch_bounds__(256) void k_mesh_triangle_boxes(const float4* __res
                                                              float4* __restrict__ tri_lo, float4* __restrict__ tri_hi) {
   const uint32_t t = blockIdx.x * 256u + threadIdx.x;
   if (t >= n_tris) return;
-  const float4 q[3] = {v0[t], v1[t], v2[t]};
-  tri_lo[t] = make_float4(leaf_min(q[0].x, leaf_min(q[1].x, q[2].x)), leaf_min(q[0].y, leaf_min(q[1].y, q[2].y)), leaf_min(q[0].z, leaf_min(q[1].z, q[2].z)), 0.0f);
-  tri_hi[t] = make_float4(leaf_max(q[0].x, leaf_max(q[1].x, q[2].x)), leaf_max(q[0].y, leaf_max(q[1].y, q[2].y)), leaf_max(q[0].z, leaf_max(q[1].z, q[2].z)), 0.0f);
+  triangle_box(v0[t], v1[t], v2[t], tri_lo[t], tri_hi[t]);
 }
 
 }  // namespace hkd

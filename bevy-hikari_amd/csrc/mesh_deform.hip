@@ -1,5 +1,5 @@
 // mesh_deform.hip - mesh deformation on the device (hikari_hip.h hk_update_mesh_vertices / hk_set_mesh_skin / hk_skin_mesh; kernels in
-// kernels_deform.hip and kernels_scene.hip; DESIGN "Mesh deformation").  The reference re-prepares a changed mesh on the CPU
+// kernels_deform.hip, kernels_tree.hip and kernels_scene.hip; DESIGN "Mesh deformation").  The reference re-prepares a changed mesh on the CPU
 // (mesh.rs:76-166: a BVH build and a re-layout of the whole mesh level); here the new vertices are written into the mesh-level region,
 // the mesh tree is REFIT in every ordering that holds it (same links, every box the union of the triangle boxes below it), and the
 // new mesh box goes up to the instances, emitters and both instance-level trees - all stream-ordered behind the frames enqueued before.
@@ -408,7 +408,7 @@ int hk_skin_mesh(hk_ctx* c, const HkMeshIndex* mesh, const float* joint_matrices
   });
 }
 
-// A new tree over the current triangles of one mesh, in place (hikari_hip.h).  The build is the instance level's (kernels_scene.hip
+// A new tree over the current triangles of one mesh, in place (hikari_hip.h).  The build is the instance level's (kernels_tree.hip
 // launch_tree_build) fed from the mesh's triangle boxes; its topology replaces the one the refit climbs.  The mesh box and the triangle
 // order stay, so nothing at the instance level moves: no propagation, only the staleness a deformation brings.
 int hk_rebuild_mesh_tree(hk_ctx* c, const HkMeshIndex* mesh, uint32_t mode) {
@@ -426,7 +426,7 @@ int hk_rebuild_mesh_tree(hk_ctx* c, const HkMeshIndex* mesh, uint32_t mode) {
   int rc;
   if ((rc = begin(c, mesh, &d))) return rc;
   const uint32_t n = d->n_tris;
-  const size_t need = lbvh_scratch_bytes(n, nullptr);
+  const size_t need = lbvh_scratch_bytes(n);
   if (need > c->lbvh_scratch_cap) {  // (grows rarely: what is enqueued may still use the old one)
     if ((rc = sync_all(c))) return rc;
     if (c->lbvh_scratch) (void)hipFree(c->lbvh_scratch);
@@ -446,10 +446,16 @@ int hk_rebuild_mesh_tree(hk_ctx* c, const HkMeshIndex* mesh, uint32_t mode) {
     d->have_boxes = true;
   }
   float4* lo = (float4*)(sbase + c->st_nodes) + 2 * (size_t)d->mesh.node_offset;
-  const hkd::RefitScene none{};
-  HK_REQUIRE(launch_tree_build(c->stream, mode == HK_TREE_SAH ? 1 : 0, false, none, n, d->tree.tri_lo, d->tree.tri_hi, c->lbvh_scratch, lo, lo + 1, 2u, c->threaded ? 8u : 1u,
-                               2 * c->asset_nodes.size(), &d->tree, c->mesh_rebuild_one_workgroup) == 0,
-             HK_E_HIP, "device build of the mesh tree failed: %s", hipGetErrorString(hipGetLastError()));
+  TreeBuild build;  // over the mesh's triangle boxes, into its node range of every ordering; the refit's topology is replaced
+  build.mode = mode == HK_TREE_SAH ? 1 : 0;
+  build.n = n;
+  build.box_lo = d->tree.tri_lo; build.box_hi = d->tree.tri_hi;
+  build.lo = lo; build.hi = lo + 1; build.stride = 2u;
+  build.orderings = c->threaded ? 8u : 1u; build.ord_stride = 2 * c->asset_nodes.size();
+  build.mesh_tree = true; build.keep = &d->tree;
+  build.one_workgroup_top = c->mesh_rebuild_one_workgroup;
+  build.scratch = c->lbvh_scratch;
+  HK_REQUIRE(launch_tree_build(c->stream, build) == 0, HK_E_HIP, "device build of the mesh tree failed: %s", hipGetErrorString(hipGetLastError()));
   c->meshes_deformed = true;
   c->mirrors_stale = true;
   update_shared_transform(c);  // (the one-level tree is not walked from here on)

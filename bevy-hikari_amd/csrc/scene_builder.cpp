@@ -548,7 +548,7 @@ int hk_scene_builder_set_instance_transform(hk_scene_builder* b, uint32_t instan
 
 // The host twin of the device refit (mesh_deform.hip): same topology, every navigator box the union of the triangle boxes below it -
 // a triangle's box with the leaf-box arithmetic of the device layout (scene_layout.hip build_static_region: IEEE min / max with -0 < +0),
-// the union of two children as std::min / std::max of (first child, second child), as kernels_scene.hip k_lbvh_boxes forms it.
+// the union of two children as std::min / std::max of (first child, second child), as kernels_tree.hip k_lbvh_boxes forms it.
 namespace {
 float leaf_min(float a, float b) {
   if (a != a) return b;

@@ -1,4 +1,4 @@
-// scene_load.hip - mesh trees built on the device at scene load (hikari_hip.h hk_load_scene; kernels in kernels_scene.hip).
+// scene_load.hip - mesh trees built on the device at scene load (hikari_hip.h hk_load_scene; kernels in kernels_tree.hip).
 // The reference prepares an arriving mesh on the CPU (mesh.rs:76-166: `bvh` 0.7.1 BVH::build on one thread).  A builder may instead
 // hold DEFERRED meshes (hk_scene_builder_add_mesh_deferred: a valid stand-in tree of the final size); hk_load_scene uploads such a
 // builder, builds every deferred tree on the device - all meshes below 32 768 triangles together, as a forest, at a number of launches
@@ -95,7 +95,7 @@ int build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMesh>&
   }
   size_t need = 0;
   for (size_t k = 0; k < batches.size(); ++k) need = std::max(need, forest_scratch_bytes(batch_tris[k], (uint32_t)batches[k].size(), build));
-  auto boxes_at = [](uint32_t n) { return (lbvh_scratch_bytes(n, nullptr) + 255) & ~(size_t)255; };
+  auto boxes_at = [](uint32_t n) { return (lbvh_scratch_bytes(n) + 255) & ~(size_t)255; };
   for (const LoadMesh* m : large) need = std::max(need, boxes_at(m->n_tris) + 2 * (size_t)m->n_tris * 16);
   int rc;
   double t0 = now_ms();
@@ -109,7 +109,6 @@ int build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMesh>&
     HK_REQUIRE(launch_forest_build(c->stream, build, batches[k].data(), (uint32_t)batches[k].size(), batch_tris[k], v0, v1, v2, c->lbvh_scratch, nodes, orderings, 2 * n_nodes,
                                    launches) == 0,
                HK_E_HIP, "device build of the mesh trees failed: %s", hipGetErrorString(hipGetLastError()));
-  const hkd::RefitScene none{};
   for (const LoadMesh* m : large) {  // (from SAH_WIDE_MIN triangles a mesh has the whole chip to itself: the build of hk_rebuild_mesh_tree)
     float4* tri_lo = (float4*)((uint8_t*)c->lbvh_scratch + boxes_at(m->n_tris));
     float4* tri_hi = tri_lo + m->n_tris;
@@ -117,9 +116,17 @@ int build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMesh>&
     launch_mesh_triangle_boxes(c->stream, v0 + p0, v1 + p0, v2 + p0, m->n_tris, tri_lo, tri_hi);
     *launches += 1u;
     float4* lo = nodes + 2 * (size_t)m->index.node_offset;
-    HK_REQUIRE(launch_tree_build(c->stream, build, false, none, m->n_tris, tri_lo, tri_hi, c->lbvh_scratch, lo, lo + 1, 2u, orderings, 2 * n_nodes, nullptr,
-                                 c->mesh_rebuild_one_workgroup, true, launches) == 0,
-               HK_E_HIP, "device build of the tree of mesh %u failed: %s", m->id, hipGetErrorString(hipGetLastError()));
+    TreeBuild tree;  // over the boxes just made, into the mesh's node range of every ordering; nothing keeps the topology
+    tree.mode = build;
+    tree.n = m->n_tris;
+    tree.box_lo = tri_lo; tree.box_hi = tri_hi;
+    tree.lo = lo; tree.hi = lo + 1; tree.stride = 2u;
+    tree.orderings = orderings; tree.ord_stride = 2 * n_nodes;
+    tree.mesh_tree = true;
+    tree.one_workgroup_top = c->mesh_rebuild_one_workgroup;
+    tree.scratch = c->lbvh_scratch;
+    tree.launches = launches;
+    HK_REQUIRE(launch_tree_build(c->stream, tree) == 0, HK_E_HIP, "device build of the tree of mesh %u failed: %s", m->id, hipGetErrorString(hipGetLastError()));
   }
   HK_HIP(hipGetLastError());
   HK_HIP(hipStreamSynchronize(c->stream));

@@ -1,4 +1,4 @@
-// scene_refit.hip - instance motion and instance-set changes on the device (kernels in kernels_scene.hip): the
+// scene_refit.hip - instance motion and instance-set changes on the device (kernels in kernels_scene.hip, tree builds in kernels_tree.hip): the
 // reference re-runs prepare_instances on the host for ANY instance change (instance.rs:352-437); here moved instances are refit,
 // both trees rebuilt (the reference's SAH tree or an LBVH) and instance-set edits laid out without the host's two tree builds.
 #include "hk_context.hpp"
@@ -166,7 +166,7 @@ int hk_rebuild_scene_trees(hk_ctx* c, uint32_t mode) {
   HK_REQUIRE(c->instance_nodes.size() == 3 * (size_t)ni - 2 && (ne == 0 || c->emissive_nodes.size() == 3 * (size_t)ne - 2), HK_E_UNSUPPORTED,
              "the uploaded trees are not in the flatten_custom layout of a binary tree (3n - 2 nodes): nothing to rebuild in place");
   if ((rc = prepare_refit(c))) return rc;
-  const size_t need = std::max(lbvh_scratch_bytes(ni, nullptr), lbvh_scratch_bytes(std::max(ne, 1u), nullptr));
+  const size_t need = std::max(lbvh_scratch_bytes(ni), lbvh_scratch_bytes(std::max(ne, 1u)));
   if (need > c->lbvh_scratch_cap) {
     if ((rc = sync_all(c))) return rc;
     if (c->lbvh_scratch) (void)hipFree(c->lbvh_scratch);
@@ -179,12 +179,23 @@ int hk_rebuild_scene_trees(hk_ctx* c, uint32_t mode) {
   const hkd::RefitScene r = refit_scene(c);
   uint8_t* base = c->scene_mem + (size_t)c->slot * c->dyn_capacity;
   float4* tlas = (float4*)(base + c->dyn_off.tlas);
-  const int build = mode == HK_TREE_SAH ? 1 : 0;
-  HK_REQUIRE(launch_tree_build(c->stream, build, false, r, ni, c->rf_inst_lo, c->rf_inst_hi, c->lbvh_scratch, tlas, tlas + 1, 2u, c->threaded ? 8u : 1u) == 0, HK_E_HIP,
-             "device build of the instance tree failed: %s", hipGetErrorString(hipGetLastError()));
-  if (ne)
-    HK_REQUIRE(launch_tree_build(c->stream, build, true, r, ne, nullptr, nullptr, c->lbvh_scratch, (float4*)(base + c->dyn_off.light_lo), (float4*)(base + c->dyn_off.light_hi),
-                                 1u, 1u) == 0, HK_E_HIP, "device build of the light tree failed: %s", hipGetErrorString(hipGetLastError()));
+  TreeBuild instance_tree;  // over the instances' world boxes, into the interleaved node pairs of every ordering
+  instance_tree.mode = mode == HK_TREE_SAH ? 1 : 0;
+  instance_tree.n = ni;
+  instance_tree.box_lo = c->rf_inst_lo; instance_tree.box_hi = c->rf_inst_hi;
+  instance_tree.lo = tlas; instance_tree.hi = tlas + 1; instance_tree.stride = 2u;
+  instance_tree.orderings = c->threaded ? 8u : 1u;
+  instance_tree.scratch = c->lbvh_scratch;
+  HK_REQUIRE(launch_tree_build(c->stream, instance_tree) == 0, HK_E_HIP, "device build of the instance tree failed: %s", hipGetErrorString(hipGetLastError()));
+  if (ne) {
+    TreeBuild light_tree;  // over the emitters of the scene, into the two planes of the light tree's one ordering
+    light_tree.mode = instance_tree.mode;
+    light_tree.n = ne;
+    light_tree.scene = &r;
+    light_tree.lo = (float4*)(base + c->dyn_off.light_lo); light_tree.hi = (float4*)(base + c->dyn_off.light_hi); light_tree.stride = 1u;
+    light_tree.scratch = c->lbvh_scratch;
+    HK_REQUIRE(launch_tree_build(c->stream, light_tree) == 0, HK_E_HIP, "device build of the light tree failed: %s", hipGetErrorString(hipGetLastError()));
+  }
   c->mirrors_stale = true;
   c->wide_tlas_dirty = true;
   c->device_tree_builds += 1;

@@ -110,7 +110,7 @@ NODE = np.dtype([("min", "<f4", 3), ("entry", "<u4"), ("max", "<f4", 3), ("exit"
 
 
 def okey(a):
-    """float32 -> uint32 whose unsigned order is the float order with -0 < +0 (the mesh box words of kernels_deform.hip)"""
+    """float32 -> uint32 whose unsigned order is the float order with -0 < +0 (the mesh box words of hk_box.hpp, reduced by kernels_deform.hip)"""
     u = np.ascontiguousarray(a, np.float32).view(U32)
     return np.where(u & U32(0x80000000), ~u, u | U32(0x80000000)).astype(U32)
 
@@ -164,7 +164,7 @@ def check_union_fast(nodes, tris, filled_leaves=False, topology=None):
     tri_lo, tri_hi = triangle_boxes(tris)
     lo, hi = expected_node_keys(entry, exit_, tri_lo, tri_hi, filled_leaves)
     # leaves bit for bit; a navigator by value: its union takes std::min / std::max of the children in (left, right) order - the zero of
-    # the left child where the two children's bounds are -0 and +0 (scene_builder.cpp refit_nodes, kernels_scene.hip k_lbvh_boxes)
+    # the left child where the two children's bounds are -0 and +0 (scene_builder.cpp refit_nodes, kernels_tree.hip k_lbvh_boxes)
     leaf = entry >= LEAF
     same = lambda got, want: np.where(leaf[:, None], okey(got) == want, got == okey_float(want)).all(1)
     bad = np.flatnonzero(~(same(a["min"], lo) & same(a["max"], hi)))
