@@ -228,6 +228,8 @@ _DEBUG = {
     "debug_read_trees": [_vp, P(HkNode), u32, P(HkNode), u32],
     "debug_read_mesh_nodes": [_vp, P(HkNode), u32, P(u32), P(u32)],
     "debug_last_load": [_vp, P(u32)],
+    "debug_last_add": [_vp, P(u32)],
+    "debug_last_add_times": [_vp, P(C.c_double)],
     "debug_last_load_times": [_vp, P(C.c_double)],
     "debug_read_emitters": [_vp, P(f32), u32, P(u32), P(f32), u32, P(u32)],
     "debug_read_mesh_geometry": [_vp, P(HkMeshIndex), P(f32), P(f32), u32, P(f32), u32, P(f32), P(u32), P(u32)],
@@ -278,6 +280,7 @@ _PRODUCT_ONLY = {
     "upload_scene": [_vp, _vp],
     "upload_scene_instances": [_vp, _vp],
     "load_scene": [_vp, _vp, u32],
+    "add_meshes": [_vp, _vp, u32],
     "refit_scene_instances": [_vp, _vp, P(u32)],
     "rebuild_scene_trees": [_vp, u32],
     "update_scene_instances": [_vp, _vp, u32],
@@ -327,6 +330,7 @@ _PRODUCT_ONLY = {
     "multi_upload_scene": [_vp, _vp],
     "multi_upload_scene_instances": [_vp, _vp],
     "multi_load_scene": [_vp, _vp, u32],
+    "multi_add_meshes": [_vp, _vp, u32],
     "multi_refit_scene_instances": [_vp, _vp, P(u32)],
     "multi_rebuild_scene_trees": [_vp, u32],
     "multi_update_scene_instances": [_vp, _vp, u32],

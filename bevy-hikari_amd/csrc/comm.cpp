@@ -818,6 +818,14 @@ int hk_multi_load_scene(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode) {
   for (size_t i = 1; i < m->ctx.size() && !rc; ++i) rc = hk_upload_scene(m->ctx[i], b);
   return rc;
 }
+// hk_add_meshes for every band: deferred trees are built once, on the first band's context, and written back; the other bands find the new
+// meshes with their trees in the builder and lay out those ranges alone
+int hk_multi_add_meshes(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode) {
+  HK_REQUIRE(m && b && !m->ctx.empty(), HK_E_INVALID, "NULL argument");
+  int rc = HK_OK;
+  for (size_t i = 0; i < m->ctx.size() && !rc; ++i) rc = hk_add_meshes(m->ctx[i], b, tree_mode);
+  return rc;
+}
 int hk_multi_upload_scene_instances(hk_multi* m, const hk_scene_builder* b) { HK_EACH(hk_upload_scene_instances(c, b)); }
 int hk_multi_rebuild_scene_trees(hk_multi* m, uint32_t mode) { HK_EACH(hk_rebuild_scene_trees(c, mode)); }
 int hk_multi_update_mesh_vertices(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vertices, const float* positions, const float* normals) {

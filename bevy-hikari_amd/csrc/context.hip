@@ -557,8 +557,9 @@ int ensure_wide(hk_ctx* c, bool with_spill) {
   }
   if (blas_slots > c->wide_blas_slots) {
     if (c->wide_blas) { HK_HIP(hipStreamSynchronize(c->stream)); (void)hipFree(c->wide_blas); c->wide_blas = nullptr; }
-    HK_HIP(hipMalloc((void**)&c->wide_blas, blas_slots * 128));
-    c->wide_blas_slots = blas_slots;
+    const size_t cap = std::max(blas_slots, c->node_cap);  // (room for the trees hk_add_meshes may append: it copies these records, it does not derive them again)
+    HK_HIP(hipMalloc((void**)&c->wide_blas, cap * 128));
+    c->wide_blas_slots = cap;
     c->wide_blas_dirty = true;
   }
   // the leaves' ranks (hk_kernels.hpp WideTrees): one u32 per instance / per primitive, written with the records
@@ -572,9 +573,10 @@ int ensure_wide(hk_ctx* c, bool with_spill) {
   }
   if (n_prim > c->wide_rank_primitives) {
     if (c->wide_blas_rank) { HK_HIP(hipStreamSynchronize(c->stream)); (void)hipFree(c->wide_blas_rank); c->wide_blas_rank = nullptr; }
-    HK_HIP(hipMalloc((void**)&c->wide_blas_rank, std::max<size_t>(n_prim, 1) * sizeof(uint32_t)));
-    HK_HIP(hipMemsetAsync(c->wide_blas_rank, 0xFF, std::max<size_t>(n_prim, 1) * sizeof(uint32_t), c->stream));  // (a primitive no mesh tree names: a rank that is at least deterministic)
-    c->wide_rank_primitives = n_prim;
+    const size_t cap = std::max<size_t>(std::max(n_prim, c->prim_cap), 1);
+    HK_HIP(hipMalloc((void**)&c->wide_blas_rank, cap * sizeof(uint32_t)));
+    HK_HIP(hipMemsetAsync(c->wide_blas_rank, 0xFF, cap * sizeof(uint32_t), c->stream));  // (a primitive no mesh tree names: a rank that is at least deterministic)
+    c->wide_rank_primitives = cap;
     c->wide_blas_dirty = true;
   }
   if (!c->compute_units) {
@@ -1030,6 +1032,7 @@ void hk_destroy(hk_ctx* c) {
   if (c->frame_stop) (void)hipEventDestroy(c->frame_stop);
   free_screen(c);
   if (c->scene_mem) (void)hipFree(c->scene_mem);
+  poll_retired(c, true);
   for (int k = 0; k < 2; ++k) {
     if (c->staging[k]) (void)hipHostFree(c->staging[k]);
     if (c->staging_done[k]) (void)hipEventDestroy(c->staging_done[k]);

@@ -3,6 +3,7 @@
 //   context.hip       lifetime, screen-space resources, the frame graph (hk_frame_*, hk_pass_run), bands, buffers, statistics
 //   scene_layout.hip  uploads and the layout conversion: reference-layout scene arrays -> the device's scene blob (finalize_scene)
 //   scene_refit.hip   instance motion and instance-set changes on the device (hk_refit_scene_instances, hk_rebuild_scene_trees, ...)
+//   scene_load.hip    mesh trees built on the device at scene load (hk_load_scene); scene_append.hip: meshes appended later (hk_add_meshes)
 //   probes.hip        measurement hooks (hk_measure_*, hk_debug_math)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -210,6 +211,16 @@ struct hk_ctx {
   bool staging_pending[2] = {false, false};
   uint64_t async_instance_uploads = 0;
   size_t st_nodes = 0, st_v0 = 0, st_v1 = 0, st_v2 = 0, st_vn = 0, st_vuv = 0;  // offsets inside the mesh-level region
+  // Capacities of the mesh-level sub-arrays, in elements (hk_add_meshes, scene_append.hip): nodes per ordering - the stride between two
+  // orderings, DScene::blas_stride - primitives per triangle plane, vertices per vertex plane.  A host layout leaves them equal to the
+  // sizes of the mirrors; an append that does not fit moves the scene to a new allocation with room to spare (static_bytes covers the
+  // capacities).  What such a move replaces - or a grown build scratch - is freed once the event recorded behind the move has passed,
+  // polled at later calls: frames in flight go on reading it.
+  size_t node_cap = 0, prim_cap = 0, vert_cap = 0;
+  struct Retired { void* p; hipEvent_t done; };
+  std::vector<Retired> retired;
+  uint32_t last_add[5] = {0, 0, 0, 0, 0};   // hk_debug_last_add
+  double last_add_ms[4] = {0, 0, 0, 0};     // hk_debug_last_add_times
   uint64_t static_rebuilds = 0, dynamic_rebuilds = 0;
   // Parked previous_spatial stores (HK_CTX_DETERMINISTIC_SCATTER; every band of a sharded frame with a history halo: SURVEY 8e
   // step 6), one set per light channel.  `to` and the records are the HK_BUF_PARKED_* planes (c->buf: bands exchange their rows),
@@ -369,6 +380,25 @@ int sync_all(hk_ctx* c);
 int finalize_scene(hk_ctx* c);
 void update_shared_transform(hk_ctx* c);
 void point_scene_at_slot(hk_ctx* c);
+size_t fold_leaf_navigators(std::vector<float4>& lo, std::vector<float4>& hi, size_t begin, size_t count);
+void thread_orderings(const std::vector<HkNode>& src, const std::vector<std::pair<uint32_t, uint32_t>>& ranges, int orderings, std::vector<std::vector<HkNode>>& out);
+// whether a scene of these mirror sizes keeps eight direction-threaded orderings (the estimate finalize_scene decides by)
+bool wants_threaded(const hk_ctx* c, size_t n_nodes, size_t n_prims, size_t n_verts);
+// offsets of the mesh-level sub-arrays (nodes, v0, v1, v2, vn, vuv) for these capacities; returns the bytes of the region
+size_t mesh_region_layout(size_t node_cap, size_t prim_cap, size_t vert_cap, uint32_t orderings, size_t off[6]);
+// ---- scene_load.hip
+struct LoadMesh {
+  uint32_t id;
+  HkMeshIndex index;
+  uint32_t n_tris;
+};
+// the trees of `meshes` built into their node ranges of every ordering, then read back into the builder and the mirror; `reference_if_unused`:
+// a range no instance uses is left in reference form, as the host layout leaves it (hk_load_scene)
+int build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMesh>& meshes, uint32_t mode, uint32_t* launches, bool reference_if_unused);
+// ---- scene_append.hip
+void retire(hk_ctx* c, void* p, hipEvent_t done);   // free `p` once `done` has passed (takes the event over)
+void poll_retired(hk_ctx* c, bool wait);            // ... checked here, only behind a wait for the context's streams (hipFree may wait by itself); wait: free everything
+int take_appended_materials(hk_ctx* c, const hk_scene_builder* b);  // hk_update_scene_instances: materials the builder holds beyond the context's (the caller takes them back if the upload is refused)
 // ---- scene_refit.hip
 void free_refit(hk_ctx* c);
 int begin_device_update(hk_ctx* c);

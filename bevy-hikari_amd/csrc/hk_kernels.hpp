@@ -351,6 +351,25 @@ void launch_indirect_wavefront(hipStream_t st, const hkd::DScene& sc, const hkd:
                                const hkd::WfBuffers& w, int y0, int y1, int compute_units, hipEvent_t start = nullptr, hipEvent_t stop = nullptr,
                                const hkd::WideTrees* wide = nullptr, hipEvent_t* trace_events = nullptr);
 void launch_copy_region(hipStream_t st, void* dst, const void* src, size_t bytes);
+// hk_add_meshes: up to HK_COPY_SEGMENTS copies in ONE launch - the sub-arrays of a scene moved to a roomier allocation, the staged node
+// ranges of every ordering; dst / src 16-B aligned, `bytes` whole 4-B words
+#define HK_COPY_SEGMENTS 16u
+struct CopySegments {
+  struct Segment { uint4* dst; const uint4* src; size_t bytes; } seg[HK_COPY_SEGMENTS];
+  uint32_t count = 0;
+  bool overflow = false;  // add() was asked for more than the table holds: the caller must not launch
+  void add(void* dst, const void* src, size_t bytes) {
+    if (!bytes) return;
+    if (count >= HK_COPY_SEGMENTS) { overflow = true; return; }
+    seg[count].dst = (uint4*)dst; seg[count].src = (const uint4*)src; seg[count].bytes = bytes;
+    ++count;
+  }
+};
+void launch_copy_segments(hipStream_t st, const CopySegments& segments);
+// hk_add_meshes: n_prims HkPrimitive (48 B) and n_verts HkVertex (32 B) records in pinned memory into the triangle planes and the vertex
+// planes, from element 0 of the plane pointers given
+void launch_append_geometry(hipStream_t st, const uint4* prims, uint32_t n_prims, const uint4* verts, uint32_t n_verts, float4* v0, float4* v1, float4* v2, float4* vn,
+                            float2* vuv);
 void launch_gather_instance_boxes(hipStream_t st, const hkd::RefitScene& s, const float4* tlas, uint32_t tlas_count);
 // the first n_emitter_updates records are the moved emitters (the largest of their meshes has emitter_triangles triangles)
 void launch_refit(hipStream_t st, const hkd::RefitScene& s, const hkd::RefitUpdate* updates, uint32_t n_updates, uint32_t n_emitter_updates, uint32_t emitter_triangles,

@@ -313,6 +313,34 @@ __global__ __launch_bounds__(256) void k_refit_flat_bvh(RefitScene s, float4* lo
 __global__ __launch_bounds__(256) void k_copy_region_u4(uint4* __restrict__ dst, const uint4* __restrict__ src, size_t n) {
   for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) dst[i] = src[i];
 }
+// hk_add_meshes: several copies in one launch, blockIdx.y names the segment (hk_kernels.hpp CopySegments); a tail of whole 4-B words - a
+// rank array, the uv plane - goes with the segment's first workgroup
+__global__ __launch_bounds__(256) void k_copy_segments(hk::CopySegments t) {
+  const hk::CopySegments::Segment s = t.seg[blockIdx.y];
+  const size_t n = s.bytes / 16u;
+  for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) s.dst[i] = s.src[i];
+  const uint32_t tail = (uint32_t)(s.bytes % 16u) / 4u;
+  if (blockIdx.x == 0u && threadIdx.x < tail) ((uint32_t*)(s.dst + n))[threadIdx.x] = ((const uint32_t*)(s.src + n))[threadIdx.x];
+}
+// hk_add_meshes: reference-layout records (hikari_hip.h HkPrimitive: three 16-B corners; HkVertex: position + u, normal + v) into the
+// planes, with the arithmetic of the host layout (scene_layout.hip build_static_region) - pure moves, the normal plane's w is 0
+__global__ __launch_bounds__(256) void k_append_geometry(const uint4* __restrict__ prims, uint32_t n_prims, const uint4* __restrict__ verts, uint32_t n_verts,
+                                                         float4* __restrict__ v0, float4* __restrict__ v1, float4* __restrict__ v2, float4* __restrict__ vn,
+                                                         float2* __restrict__ vuv) {
+  auto f4 = [](uint4 u) { return make_float4(u2f(u.x), u2f(u.y), u2f(u.z), u2f(u.w)); };
+  const uint32_t step = gridDim.x * 256u;
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_prims; i += step) {
+    const uint4 a = prims[3u * (size_t)i], b = prims[3u * (size_t)i + 1u], c = prims[3u * (size_t)i + 2u];
+    v0[i] = f4(a);
+    v1[i] = f4(b);
+    v2[i] = f4(c);
+  }
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_verts; i += step) {
+    const uint4 a = verts[2u * (size_t)i], b = verts[2u * (size_t)i + 1u];
+    vn[i] = make_float4(u2f(b.x), u2f(b.y), u2f(b.z), 0.0f);
+    vuv[i] = make_float2(u2f(a.w), u2f(b.w));
+  }
+}
 // world AABB of every instance, from the TLAS leaves of ordering 0 (after a host upload: the refit reads them from here)
 __global__ __launch_bounds__(256) void k_gather_instance_boxes(RefitScene s, const float4* __restrict__ tlas, uint32_t count) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -420,6 +448,19 @@ void launch_copy_region(hipStream_t st, void* dst, const void* src, size_t bytes
   const size_t n = bytes / 16;
   if (!n) return;
   hipLaunchKernelGGL(k_copy_region_u4, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st, (uint4*)dst, (const uint4*)src, n);
+}
+void launch_copy_segments(hipStream_t st, const CopySegments& segments) {
+  if (!segments.count || segments.overflow) return;
+  size_t longest = 0;
+  for (uint32_t k = 0; k < segments.count; ++k) longest = std::max(longest, segments.seg[k].bytes / 16);
+  const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((longest + 255) / 256, 2048));
+  hipLaunchKernelGGL(k_copy_segments, dim3(blocks, segments.count), dim3(256), 0, st, segments);
+}
+void launch_append_geometry(hipStream_t st, const uint4* prims, uint32_t n_prims, const uint4* verts, uint32_t n_verts, float4* v0, float4* v1, float4* v2, float4* vn,
+                            float2* vuv) {
+  const uint32_t n = std::max(n_prims, n_verts);
+  if (!n) return;
+  hipLaunchKernelGGL(k_append_geometry, dim3(std::min((n + 255u) / 256u, 4096u)), dim3(256), 0, st, prims, n_prims, verts, n_verts, v0, v1, v2, vn, vuv);
 }
 void launch_gather_instance_boxes(hipStream_t st, const RefitScene& s, const float4* tlas, uint32_t tlas_count) {
   if (!tlas_count) return;

@@ -249,8 +249,7 @@ int refit_mesh(hk_ctx* c, DeformMesh* d) {
   const uint32_t p0 = d->mesh.primitive;
   launch_mesh_triangles(c->stream, d->pos, (float4*)(sbase + c->st_v0) + p0, (float4*)(sbase + c->st_v1) + p0, (float4*)(sbase + c->st_v2) + p0, d->n_tris, d->tree.tri_lo,
                         d->tree.tri_hi);
-  const size_t n_nodes = c->asset_nodes.size();
-  launch_mesh_tree_refit(c->stream, d->tree, (float4*)(sbase + c->st_nodes) + 2 * (size_t)d->mesh.node_offset, 2 * n_nodes, c->threaded ? 8u : 1u);
+  launch_mesh_tree_refit(c->stream, d->tree, (float4*)(sbase + c->st_nodes) + 2 * (size_t)d->mesh.node_offset, 2 * c->node_cap, c->threaded ? 8u : 1u);
   HK_HIP(hipGetLastError());
   d->deformed = d->pending = d->have_boxes = true;
   c->deform_pending = true;
@@ -451,7 +450,7 @@ int hk_rebuild_mesh_tree(hk_ctx* c, const HkMeshIndex* mesh, uint32_t mode) {
   build.n = n;
   build.box_lo = d->tree.tri_lo; build.box_hi = d->tree.tri_hi;
   build.lo = lo; build.hi = lo + 1; build.stride = 2u;
-  build.orderings = c->threaded ? 8u : 1u; build.ord_stride = 2 * c->asset_nodes.size();
+  build.orderings = c->threaded ? 8u : 1u; build.ord_stride = 2 * c->node_cap;
   build.mesh_tree = true; build.keep = &d->tree;
   build.one_workgroup_top = c->mesh_rebuild_one_workgroup;
   build.scratch = c->lbvh_scratch;
@@ -506,7 +505,8 @@ int hk_debug_read_mesh_nodes(hk_ctx* c, HkNode* out, uint32_t cap, uint32_t* cou
   HK_REQUIRE(cap >= n * o, HK_E_INVALID, "need room for %u nodes", n * o);
   const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
   static_assert(sizeof(HkNode) == 32, "HkNode is two float4");
-  HK_HIP(hipMemcpy(out, c->scene_mem + slots + c->st_nodes, (size_t)n * o * 32, hipMemcpyDeviceToHost));
+  for (uint32_t k = 0; k < o; ++k)  // (the orderings lie one node CAPACITY apart: hk_add_meshes)
+    HK_HIP(hipMemcpy(out + (size_t)k * n, c->scene_mem + slots + c->st_nodes + (size_t)k * c->node_cap * 32, (size_t)n * 32, hipMemcpyDeviceToHost));
   return HK_OK;
 }
 
@@ -520,7 +520,47 @@ int hk_debug_read_mesh_geometry(hk_ctx* c, const HkMeshIndex* mesh, float* posit
   DeformMesh* d = nullptr;
   for (DeformMesh* q : c->deform)
     if (memcmp(&q->mesh, mesh, sizeof(HkMeshIndex)) == 0) d = q;
-  HK_REQUIRE(d && d->deformed, HK_E_INVALID, "the mesh has not been deformed on this context");
+  if (!(d && d->deformed)) {  // never deformed here: what the planes hold for the mesh as the host's mirror describes it
+    HK_REQUIRE(mesh->node_count >= 1 && (mesh->node_count + 2) % 3 == 0, HK_E_INVALID, "the mesh record names a tree of %u nodes", mesh->node_count);
+    const uint32_t nt = (mesh->node_count + 2) / 3;
+    HK_REQUIRE((size_t)mesh->primitive + nt <= c->primitives.size() && (size_t)mesh->node_offset + mesh->node_count <= c->asset_nodes.size() &&
+                   mesh->vertex < c->vertices.size(),
+               HK_E_INVALID, "the mesh record lies outside the uploaded mesh arrays");
+    uint32_t nv = 0;
+    for (uint32_t t = 0; t < nt; ++t)
+      for (int k = 0; k < 3; ++k) nv = std::max(nv, c->primitives[mesh->primitive + t].vertices[k].index + 1u);
+    HK_REQUIRE((size_t)mesh->vertex + nv <= c->vertices.size(), HK_E_INVALID, "the mesh's triangles name vertices beyond the uploaded ones");
+    if ((rc = sync_all(c))) return rc;
+    *n_vertices = nv;
+    *n_triangles = nt;
+    if (!positions && !normals && !triangles && !box) return HK_OK;
+    HK_REQUIRE(positions && normals && triangles && box && vertex_cap >= nv && triangle_cap >= nt, HK_E_INVALID, "need room for %u vertices and %u triangles", nv, nt);
+    const uint8_t* sbase = c->scene_mem + (c->two_slots ? 2 : 1) * c->dyn_capacity;
+    HK_HIP(hipMemcpy(normals, (const float4*)(sbase + c->st_vn) + mesh->vertex, (size_t)nv * 16, hipMemcpyDeviceToHost));
+    std::vector<float4> plane(nt);
+    const size_t planes[3] = {c->st_v0, c->st_v1, c->st_v2};
+    memset(positions, 0, (size_t)nv * 16);
+    for (int k = 0; k < 3; ++k) {
+      HK_HIP(hipMemcpy(plane.data(), (const float4*)(sbase + planes[k]) + mesh->primitive, (size_t)nt * 16, hipMemcpyDeviceToHost));
+      for (uint32_t t = 0; t < nt; ++t) {
+        memcpy(triangles + 12 * (size_t)t + 4 * k, &plane[t], 16);
+        uint32_t index;
+        memcpy(&index, &plane[t].w, 4);
+        if (index < nv) {
+          const float p[4] = {plane[t].x, plane[t].y, plane[t].z, 0.0f};
+          memcpy(positions + 4 * (size_t)index, p, 16);
+        }
+      }
+    }
+    for (int k = 0; k < 3; ++k) { box[k] = INFINITY; box[3 + k] = -INFINITY; }
+    for (uint32_t t = 0; t < nt; ++t)
+      for (int v = 0; v < 3; ++v)
+        for (int k = 0; k < 3; ++k) {
+          box[k] = hmin(box[k], triangles[12 * (size_t)t + 4 * v + k]);
+          box[3 + k] = hmax(box[3 + k], triangles[12 * (size_t)t + 4 * v + k]);
+        }
+    return HK_OK;
+  }
   if ((rc = flush_deform(c))) return rc;
   if ((rc = sync_all(c))) return rc;
   const uint32_t nv = d->n_vertices, nt = d->n_tris;

@@ -263,7 +263,8 @@ struct hk_scene_builder {
   std::vector<hk::BuilderInstance> instance_decl;
   bool finished = false;
   bool standin_trees = false;             // finished by hk_scene_builder_finish_instances: the two trees are valid stand-ins, not the reference's
-  bool meshes_dirty = true;               // the concatenated mesh buffers must be rebuilt
+  bool meshes_dirty = true;               // the concatenated mesh buffers must be brought up to date
+  size_t concat_meshes = 0;               // ... from this mesh on: the earlier ones are in them as they stand (meshes added after a finish are appended)
   std::vector<float> finished_transforms;  // transforms at the last finish ...
   std::vector<float> previous_transforms;  // ... and at the one before (PreviousMeshUniform)
   // outputs
@@ -627,6 +628,7 @@ int hk_scene_builder_set_mesh_vertices(hk_scene_builder* b, uint32_t mesh_id, co
     mesh.aabb_half[k] = 0.5f * (mx[k] - mn[k]);
   }
   b->meshes[mesh_id] = std::move(mesh);
+  b->concat_meshes = std::min<size_t>(b->concat_meshes, mesh_id);
   b->meshes_dirty = true;
   b->finished = false;
   return HK_OK;
@@ -656,6 +658,7 @@ int hk_scene_builder_rebuild_mesh_tree(hk_scene_builder* b, uint32_t mesh_id) {
   if (rc) return rc;
   b->meshes[mesh_id].nodes.swap(nodes);
   b->meshes[mesh_id].pending = false;  // (a deferred mesh: this is its tree)
+  b->concat_meshes = std::min<size_t>(b->concat_meshes, mesh_id);
   b->meshes_dirty = true;
   b->finished = false;
   return HK_OK;
@@ -715,8 +718,16 @@ int hk_scene_builder_set_material(hk_scene_builder* b, uint32_t material_id, con
 static int finish_impl(hk_scene_builder* b, bool build_trees) {
   HK_REQUIRE(b, HK_E_INVALID, "builder is NULL");
   if (b->meshes_dirty) {  // mesh.rs:141-163: concatenate, remember offsets (only when a mesh was added)
-    b->vertices.clear(); b->primitives.clear(); b->asset_nodes.clear(); b->mesh_index.clear();
-    for (const BuilderMesh& m : b->meshes) {
+    // The reference concatenates every mesh again; the bytes in front of the first mesh that changed are what they were, so the work here
+    // starts there: meshes added since the last finish are appended, at a cost that follows them.
+    const size_t keep = std::min(b->concat_meshes, b->mesh_index.size());
+    if (keep < b->mesh_index.size()) {
+      const HkMeshIndex& cut = b->mesh_index[keep];
+      b->vertices.resize(cut.vertex); b->primitives.resize(cut.primitive); b->asset_nodes.resize(cut.node_offset);
+      b->mesh_index.resize(keep);
+    }
+    for (size_t id = keep; id < b->meshes.size(); ++id) {
+      const BuilderMesh& m = b->meshes[id];
       HkMeshIndex mi;
       mi.vertex = (uint32_t)b->vertices.size();
       mi.primitive = (uint32_t)b->primitives.size();
@@ -727,6 +738,7 @@ static int finish_impl(hk_scene_builder* b, bool build_trees) {
       b->asset_nodes.insert(b->asset_nodes.end(), m.nodes.begin(), m.nodes.end());
       b->mesh_index.push_back(mi);
     }
+    b->concat_meshes = b->meshes.size();
     b->meshes_dirty = false;
   }
   b->instances.clear(); b->instance_nodes.clear(); b->emissives.clear(); b->emissive_nodes.clear(); b->alias_table.clear();
@@ -837,7 +849,13 @@ int builder_store_mesh_nodes(hk_scene_builder* b, uint32_t mesh_id, const HkNode
   BuilderMesh& m = b->meshes[mesh_id];
   HK_REQUIRE(count == m.nodes.size(), HK_E_INVALID, "a tree of %u nodes for a mesh of %zu", count, m.nodes.size());
   std::copy(nodes, nodes + count, m.nodes.begin());
-  if (!b->meshes_dirty && mesh_id < b->mesh_index.size()) std::copy(nodes, nodes + count, b->asset_nodes.begin() + b->mesh_index[mesh_id].node_offset);
+  // the mesh's range of the concatenated array, where that array still holds the mesh as it stands (whether or not meshes were added
+  // since); otherwise the next finish concatenates again from this mesh on
+  if (mesh_id < b->concat_meshes && mesh_id < b->mesh_index.size() && b->mesh_index[mesh_id].node_count == count &&
+      (size_t)b->mesh_index[mesh_id].node_offset + count <= b->asset_nodes.size())
+    std::copy(nodes, nodes + count, b->asset_nodes.begin() + b->mesh_index[mesh_id].node_offset);
+  else
+    b->concat_meshes = std::min<size_t>(b->concat_meshes, mesh_id);
   m.pending = false;
   return HK_OK;
 }

@@ -462,6 +462,7 @@ int sync_all(hk_ctx* c) {
   const int rc = join_all(c);
   if (rc) return rc;
   HK_HIP(hipStreamSynchronize(c->stream));
+  poll_retired(c, false);  // (allocations an hk_add_meshes replaced: freed where the host has waited anyway)
   return HK_OK;
 }
 
@@ -504,12 +505,27 @@ void point_scene_at_slot(hk_ctx* c) {
   s.noise = c->d_noise.p;
   s.tlas_count = (uint32_t)c->instance_nodes.size();
   s.tlas_stride = c->threaded ? (uint32_t)c->instance_nodes.size() : 0u;
-  s.blas_stride = c->threaded ? (uint32_t)c->asset_nodes.size() : 0u;
+  s.blas_stride = c->threaded ? (uint32_t)c->node_cap : 0u;  // (the capacity: hk_add_meshes leaves room behind the last tree)
   s.light_count = (uint32_t)c->emissive_nodes.size();
   s.flat = (const float4*)(base + o.flat);
   s.flat_count = o.flat_count;
   s.flat_mask = o.flat_orderings ? o.flat_orderings - 1u : 0u;
   update_shared_transform(c);
+}
+
+bool wants_threaded(const hk_ctx* c, size_t n_nodes, size_t n_prims, size_t n_verts) {
+  const size_t est = n_nodes * 32 + n_prims * 48 + n_verts * 24 + c->instance_nodes.size() * 32 + c->instances.size() * 208 + c->materials.size() * 64 +
+                     c->emissive_nodes.size() * 32 + c->alias_table.size() * 8;
+  return !(c->flags & HK_CTX_EXACT_TRAVERSAL) && est > HK_LDS_SCENE_BYTES;
+}
+// (with the capacities equal to the sizes this is the layout build_static_region's blob has)
+size_t mesh_region_layout(size_t node_cap, size_t prim_cap, size_t vert_cap, uint32_t orderings, size_t off[6]) {
+  size_t at = 0;
+  off[0] = at; at += node_cap * orderings * 32;
+  for (int k = 1; k <= 3; ++k) { off[k] = at; at += prim_cap * 16; }
+  off[4] = at; at += vert_cap * 16;
+  off[5] = at; at += vert_cap * 8;
+  return (at + 15) & ~(size_t)15;
 }
 
 int finalize_scene(hk_ctx* c) {
@@ -520,9 +536,7 @@ int finalize_scene(hk_ctx* c) {
   bool need_static = c->mesh_dirty || !c->scene_mem || c->node_prim_offset.size() != n_nodes;
   {  // direction-threaded flattenings for everything that will not be traversed from the LDS copy (an estimate of the blob size decides;
      // a scene near the limit that ends up outside LDS without them merely walks in the reference's order)
-    const size_t est = n_nodes * 32 + c->primitives.size() * 48 + c->vertices.size() * 24 + c->instance_nodes.size() * 32 + c->instances.size() * 208 +
-                       c->materials.size() * 64 + c->emissive_nodes.size() * 32 + c->alias_table.size() * 8;
-    const bool want = !(c->flags & HK_CTX_EXACT_TRAVERSAL) && est > HK_LDS_SCENE_BYTES;
+    const bool want = wants_threaded(c, n_nodes, c->primitives.size(), c->vertices.size());
     if (want != c->threaded) {
       c->threaded = want;
       need_static = true;
@@ -567,6 +581,9 @@ int finalize_scene(hk_ctx* c) {
     if (c->scene_mem) { (void)hipFree(c->scene_mem); c->scene_mem = nullptr; }
     c->dyn_capacity = dyn.bytes.size();  // exact: a small scene stays small enough for the LDS copy
     c->static_bytes = st.bytes.size();
+    c->node_cap = n_nodes;  // (a host layout is exact: no room to spare)
+    c->prim_cap = c->primitives.size();
+    c->vert_cap = c->vertices.size();
     c->two_slots = c->dyn_capacity + c->static_bytes > HK_LDS_SCENE_BYTES;
     c->slot = 0;
     // room for the previous model matrix of every instance, so that the first moving frame already fits its slot

@@ -14,12 +14,6 @@ constexpr uint32_t FOREST_BATCH_TRIANGLES = 1u << 19;  // triangles built at onc
 
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-struct LoadMesh {
-  uint32_t id;
-  HkMeshIndex index;
-  uint32_t n_tris;
-};
-
 // reference form (hikari_hip.h HkNode: leaf boxes empty, every leaf behind a navigator of its own) of ordering 0 of a mesh tree as
 // k_forest_emit / k_lbvh_emit write it: the navigator of a leaf carries the leaf's entry, and the leaf slot the same record
 bool unfold_mesh_nodes(const HkNode* dev, uint32_t count, uint32_t n_tris, HkNode* out) {
@@ -61,21 +55,28 @@ bool unfold_mesh_nodes(const HkNode* dev, uint32_t count, uint32_t n_tris, HkNod
 
 int grow_scratch(hk_ctx* c, size_t need) {
   if (need <= c->lbvh_scratch_cap) return HK_OK;
-  int rc;
-  if ((rc = sync_all(c))) return rc;  // (what is enqueued may still use the old one)
-  if (c->lbvh_scratch) (void)hipFree(c->lbvh_scratch);
-  c->lbvh_scratch = nullptr;
-  c->lbvh_scratch_cap = 0;
-  HK_HIP(hipMalloc(&c->lbvh_scratch, need));
+  void* mem = nullptr;
+  HK_HIP(hipMalloc(&mem, need));
+  if (c->lbvh_scratch) {  // (what is enqueued may still use the old one - on the main stream only: it goes once an event behind that has passed)
+    hipEvent_t done = nullptr;
+    if (hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess || hipEventRecord(done, c->stream) != hipSuccess) {
+      if (done) (void)hipEventDestroy(done);
+      (void)hipFree(mem);
+      HK_REQUIRE(false, HK_E_HIP, "no event for the retired build scratch: %s", hipGetErrorString(hipGetLastError()));
+    }
+    retire(c, c->lbvh_scratch, done);
+  }
+  c->lbvh_scratch = mem;
   c->lbvh_scratch_cap = need;
   return HK_OK;
 }
+}  // namespace
 
-// the trees of `meshes` built into the mesh-level region just laid out, then read back into the builder and the mirror
-int build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMesh>& meshes, uint32_t mode, uint32_t* launches) {
+// the trees of `meshes` built into their ranges of the mesh-level region, then read back into the builder and the mirror
+int hk::build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMesh>& meshes, uint32_t mode, uint32_t* launches, bool reference_if_unused) {
   const int build = mode == HK_TREE_SAH ? 1 : 0;
   const uint32_t orderings = c->threaded ? 8u : 1u;
-  const size_t n_nodes = c->asset_nodes.size(), n_prims = c->primitives.size();
+  const size_t n_nodes = c->asset_nodes.size(), n_prims = c->primitives.size(), stride = c->node_cap;
   std::vector<const LoadMesh*> small, large;
   for (const LoadMesh& m : meshes) {
     HK_REQUIRE((size_t)m.index.node_offset + m.index.node_count <= n_nodes && (size_t)m.index.primitive + m.n_tris <= n_prims && m.index.node_count == 3u * m.n_tris - 2u,
@@ -106,7 +107,7 @@ int build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMesh>&
   float4* nodes = (float4*)(sbase + c->st_nodes);
   const float4 *v0 = (const float4*)(sbase + c->st_v0), *v1 = (const float4*)(sbase + c->st_v1), *v2 = (const float4*)(sbase + c->st_v2);
   for (size_t k = 0; k < batches.size(); ++k)
-    HK_REQUIRE(launch_forest_build(c->stream, build, batches[k].data(), (uint32_t)batches[k].size(), batch_tris[k], v0, v1, v2, c->lbvh_scratch, nodes, orderings, 2 * n_nodes,
+    HK_REQUIRE(launch_forest_build(c->stream, build, batches[k].data(), (uint32_t)batches[k].size(), batch_tris[k], v0, v1, v2, c->lbvh_scratch, nodes, orderings, 2 * stride,
                                    launches) == 0,
                HK_E_HIP, "device build of the mesh trees failed: %s", hipGetErrorString(hipGetLastError()));
   for (const LoadMesh* m : large) {  // (from SAH_WIDE_MIN triangles a mesh has the whole chip to itself: the build of hk_rebuild_mesh_tree)
@@ -121,7 +122,7 @@ int build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMesh>&
     tree.n = m->n_tris;
     tree.box_lo = tri_lo; tree.box_hi = tri_hi;
     tree.lo = lo; tree.hi = lo + 1; tree.stride = 2u;
-    tree.orderings = orderings; tree.ord_stride = 2 * n_nodes;
+    tree.orderings = orderings; tree.ord_stride = 2 * stride;
     tree.mesh_tree = true;
     tree.one_workgroup_top = c->mesh_rebuild_one_workgroup;
     tree.scratch = c->lbvh_scratch;
@@ -130,6 +131,7 @@ int build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMesh>&
   }
   HK_HIP(hipGetLastError());
   HK_HIP(hipStreamSynchronize(c->stream));
+  poll_retired(c, false);  // (behind join_all and this wait nothing of the context is in flight: a hipFree waits for nothing)
   c->last_load_ms[3] = now_ms() - t0;
   t0 = now_ms();
   // ---- back to the host: ordering 0 of the span that holds the built ranges, unfolded into the builder and the mirror
@@ -141,23 +143,25 @@ int build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMesh>&
   static_assert(sizeof(HkNode) == 32, "HkNode is two float4");
   std::vector<HkNode> dev((size_t)span1 - span0), ref;
   HK_HIP(hipMemcpy(dev.data(), nodes + 2 * (size_t)span0, dev.size() * 32, hipMemcpyDeviceToHost));
-  std::vector<uint8_t> used(n_nodes + 1, 0);
-  for (const HkInstance& in : c->instances)
-    if (in.mesh.node_count) used[in.mesh.node_offset] = 1;
+  std::vector<uint8_t> used;  // (hk_add_meshes does not ask: its cost must not follow the scene)
+  if (reference_if_unused) {
+    used.assign(n_nodes + 1, 0);
+    for (const HkInstance& in : c->instances)
+      if (in.mesh.node_count) used[in.mesh.node_offset] = 1;
+  }
   for (const LoadMesh& m : meshes) {
     ref.resize(m.index.node_count);
     HK_REQUIRE(unfold_mesh_nodes(dev.data() + (m.index.node_offset - span0), m.index.node_count, m.n_tris, ref.data()), HK_E_HIP,
                "the device build of mesh %u did not leave a tree in the flatten_custom layout", m.id);
     if ((rc = builder_store_mesh_nodes(b, m.id, ref.data(), m.index.node_count))) return rc;
     std::copy(ref.begin(), ref.end(), c->asset_nodes.begin() + m.index.node_offset);
-    if (!used[m.index.node_offset])  // no instance carries the mesh yet: the layout keeps such a range in reference form, in every ordering
+    if (reference_if_unused && !used[m.index.node_offset])  // no instance carries the mesh yet: the layout keeps such a range in reference form, in every ordering
       for (uint32_t o = 0; o < orderings; ++o)
-        HK_HIP(hipMemcpy(nodes + 2 * ((size_t)o * n_nodes + m.index.node_offset), ref.data(), (size_t)m.index.node_count * 32, hipMemcpyHostToDevice));
+        HK_HIP(hipMemcpy(nodes + 2 * ((size_t)o * stride + m.index.node_offset), ref.data(), (size_t)m.index.node_count * 32, hipMemcpyHostToDevice));
   }
   c->last_load_ms[4] = now_ms() - t0;
   return HK_OK;
 }
-}  // namespace
 
 extern "C" {
 
@@ -198,7 +202,7 @@ int hk_load_scene(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode) {
   c->load_pending_ranges.clear();
   c->last_load_ms[2] = now_ms() - t0;
   uint32_t launches = 0;
-  if (!rc) rc = build_on_device(c, b, device, tree_mode, &launches);
+  if (!rc) rc = build_on_device(c, b, device, tree_mode, &launches, true);
   if (rc) {  // never a scene with stand-in trees in it: the context is left without one
     c->have_meshes = false;
     c->mesh_dirty = true;

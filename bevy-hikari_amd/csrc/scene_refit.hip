@@ -25,7 +25,12 @@ int hk_update_scene_instances(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode
   const double t0 = now();
   if ((rc = hk_scene_builder_finish_instances(b))) return rc;
   const double t1 = now();
-  if ((rc = upload_scene_instances_unchecked(c, b))) return rc;
+  const size_t n_materials = c->materials.size();
+  if ((rc = take_appended_materials(c, b))) return rc;  // (a spawned object is a mesh, a material and an instance; refused ids write nothing)
+  if ((rc = upload_scene_instances_unchecked(c, b))) {  // (refused: the material mirror is what it was)
+    c->materials.resize(n_materials);
+    return rc;
+  }
   const double t2 = now();
   uint32_t ni = 0;
   const HkInstance* inst = nullptr;
@@ -373,7 +378,12 @@ int hk::upload_instances_and_build_trees(hk_ctx* c, const hk_scene_builder* b, u
   const HkInstance* inst = nullptr;
   int rc;
   if ((rc = hk_scene_builder_instances(b, &inst, &ni))) return rc;
-  if ((rc = upload_scene_instances_unchecked(c, b))) return rc;   // (its refusals write nothing)
+  const size_t n_materials = c->materials.size();
+  if ((rc = take_appended_materials(c, b))) return rc;
+  if ((rc = upload_scene_instances_unchecked(c, b))) {  // (its refusals write nothing: the material mirror is what it was)
+    c->materials.resize(n_materials);
+    return rc;
+  }
   if (ni >= 2 && (rc = hk_rebuild_scene_trees(c, tree_mode))) c->dynamic_dirty = true;
   return rc;
 }

@@ -487,6 +487,11 @@ class MultiEngine:
         self.api.call("multi_load_scene", self.h, builder.h, mode)
         return builder.scene()
 
+    def add_meshes(self, builder, mode=F.TREE_SAH):
+        """hk_multi_add_meshes: the meshes added to the loaded builder since are appended on every band's context; deferred trees are
+        built once, on band 0's device, and written back into `builder`."""
+        self.api.call("multi_add_meshes", self.h, builder.h, mode)
+
     def upload_noise(self, noise=None):
         for e in self.contexts:
             e.upload_noise(noise)

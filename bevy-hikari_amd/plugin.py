@@ -585,6 +585,27 @@ class Engine:
         self.api.call("debug_last_load", self.ctx, out)
         return tuple(int(v) for v in out)
 
+    def add_meshes(self, builder, mode=F.TREE_SAH):
+        """hk_add_meshes: the meshes added to the loaded, FINISHED `builder` since this context took its mesh level from it are appended to
+        the device scene - deferred ones (SceneBuilder.add_mesh(build_tree=False)) get their trees built on the device and written back -
+        without laying the scene out again.  Their instances follow through update_instances_on_device.  Returns nothing: the call's cost
+        follows the new meshes, and builder.scene() - a copy of every array of the builder - would make it follow the scene."""
+        self.api.call("add_meshes", self.ctx, builder.h, mode)
+
+    def last_add(self):
+        """(meshes built on the device, their triangles, kernel launches of the build, meshes whose trees the host had built, 1 if the scene
+        moved to a larger allocation) of the last add_meshes (test hook)."""
+        out = (F.u32 * 5)()
+        self.api.call("debug_last_add", self.ctx, out)
+        return tuple(int(v) for v in out)
+
+    def last_add_times(self):
+        """ms of the last add_meshes: (allocations of a relocation, its copy launch and switch, growth of the mirrors, staging + build +
+        read-back) - hk_debug_last_add_times (measurement hook)."""
+        out = (C.c_double * 4)()
+        self.api.call("debug_last_add_times", self.ctx, out)
+        return tuple(float(v) for v in out)
+
     def refit_instances(self, builder):
         """Instance motion on the device (hk_refit_scene_instances): the poses set on `builder` since the last upload / refit go to
         the GPU, which redoes the per-instance work and refits both trees.  Returns the number of instances that moved."""
@@ -1176,6 +1197,10 @@ class HikariPlugin:
     def load_scene(self, builder, mode=F.TREE_SAH, textures=()):
         """set_scene for a finished SceneBuilder with deferred meshes: their trees are built on the device (Engine.load_scene)."""
         return self.engine.load_scene(builder, mode, textures)
+
+    def add_meshes(self, builder, mode=F.TREE_SAH):
+        """Meshes added to the loaded builder since (glTF assets that arrive frame by frame): appended on the device (Engine.add_meshes)."""
+        self.engine.add_meshes(builder, mode)
 
     def update_instances(self, scene: SceneData):
         """Instances moved (prepare_instances, instance.rs:352-437): rewrite the instance-level buffers only."""

@@ -312,6 +312,8 @@ class Context {
   explicit Context(int device = 0, uint32_t flags = 0) { check(hk_create(device, flags, &c_), "hk_create"); }
   // the upload of a finished builder whose deferred meshes get their trees built on the device and written back (hk_load_scene)
   void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_load_scene(c_, b.handle(), tree_mode), "hk_load_scene"); }
+  // meshes added to the loaded, finished builder since: appended to the device scene without laying it out again (hk_add_meshes)
+  void add_meshes(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_add_meshes(c_, b.handle(), tree_mode), "hk_add_meshes"); }
   ~Context() { hk_destroy(c_); }
   Context(const Context&) = delete;
   Context& operator=(const Context&) = delete;
@@ -404,6 +406,7 @@ class HikariPlugin {
   Context& context() { return ctx_; }
   void set_scene(const SceneBuilder& b) { check(hk_upload_scene(ctx_.get(), b.handle()), "hk_upload_scene"); }
   void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { ctx_.load_scene(b, tree_mode); }  // ... with deferred meshes: trees built on the device
+  void add_meshes(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { ctx_.add_meshes(b, tree_mode); }  // meshes that arrive later: appended on the device
   // after SceneBuilder::set_instance_transform + finish: rewrite the instance-level device arrays only
   void update_instances(const SceneBuilder& b) { check(hk_upload_scene_instances(ctx_.get(), b.handle()), "hk_upload_scene_instances"); }
   // instance motion on the device: the poses set on `b` since the last upload / refit; returns how many moved
@@ -491,6 +494,7 @@ class HikariMultiGpuPlugin {
   HikariMultiGpuPlugin& operator=(const HikariMultiGpuPlugin&) = delete;
   void set_scene(const SceneBuilder& b) { check(hk_multi_upload_scene(m_, b.handle()), "hk_multi_upload_scene"); }
   void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_multi_load_scene(m_, b.handle(), tree_mode), "hk_multi_load_scene"); }
+  void add_meshes(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_multi_add_meshes(m_, b.handle(), tree_mode), "hk_multi_add_meshes"); }
   void update_instances(const SceneBuilder& b) { check(hk_multi_upload_scene_instances(m_, b.handle()), "hk_multi_upload_scene_instances"); }
   uint32_t refit_instances(SceneBuilder& b) {
     uint32_t moved = 0;

@@ -591,7 +591,10 @@ int hk_refit_scene_instances(hk_ctx* ctx, hk_scene_builder* b, uint32_t* moved);
  * _set_instance_material, any number of pose changes with them): hk_scene_builder_finish_instances lays the instance-level
  * records out on the host (O(instances); no tree build), the asynchronous upload puts them into the spare slot and both trees
  * are built on the device in `tree_mode` - with HK_TREE_SAH the result is what hk_scene_builder_finish +
- * hk_upload_scene_instances gives (the reference's path), minus the two host-side SAH builds that dominate it. */
+ * hk_upload_scene_instances gives (the reference's path), minus the two host-side SAH builds that dominate it.
+ * Materials APPENDED on the builder since the context took its materials travel with the call (a spawned object is a mesh - hk_add_meshes -
+ * a material and an instance); a texture id at or above the uploaded texture count is refused (HK_E_INVALID), as hk_update_materials
+ * refuses it.  Changed values of existing materials keep going through hk_update_materials. */
 int hk_update_scene_instances(hk_ctx* ctx, hk_scene_builder* b, uint32_t tree_mode);
 int hk_rebuild_scene_trees(hk_ctx* ctx, uint32_t mode);
 /* Material edits on the DEVICE.  The builder's materials (hk_scene_builder_set_material; the builder need not be finished) are diffed
@@ -681,6 +684,36 @@ int hk_rebuild_mesh_tree(hk_ctx* ctx, const HkMeshIndex* mesh, uint32_t mode);
  * Argument errors (NULL, unknown mode: HK_E_INVALID; unfinished builder: HK_E_NOT_READY) write nothing; a failure after the upload has
  * begun leaves the context WITHOUT a scene (HK_E_NOT_READY at the next frame), never with stand-in trees. */
 int hk_load_scene(hk_ctx* ctx, hk_scene_builder* b, uint32_t tree_mode);
+/* Meshes added to the builder since the context last took its mesh level from it (hk_upload_scene, hk_load_scene, hk_add_meshes), appended
+ * to the device scene without laying the scene out again.  The host adds them to the loaded builder (hk_scene_builder_add_mesh_deferred or
+ * hk_scene_builder_add_mesh) and finishes it: the builder concatenates in id order, so every existing HkMeshIndex keeps its value and the
+ * new ranges lie behind the old ones.  Instances of the new meshes - and materials appended on the builder - follow through
+ * hk_update_scene_instances, which then lays out the instance level only.
+ * A scene with two slots of the instance-level region (beyond the LDS copy) whose ordering count stays what it is: the mesh-level sub-arrays
+ * (node planes per ordering, triangle and vertex planes, the wide records and ranks) keep capacities.  The new HkPrimitive / HkVertex
+ * records go through the pinned staging pool of the deformations into the planes; deferred trees are built on the device as hk_load_scene
+ * builds them (all below 32 768 triangles together, larger ones on the whole chip; above HK_MESH_REBUILD_MAX_TRIANGLES by the host inside
+ * the call), trees the host built are threaded, boxed and folded for their ranges alone and sent through staging.  New ranges are in final
+ * form whether an instance uses them yet or not.  When they do not fit, the scene moves ONCE to an allocation with every capacity at
+ * least 1.5 times what is needed - both slots and every sub-array in one copy launch in stream order, existing wide records copied, not
+ * derived again; the old allocation is freed once an event behind that copy has passed - polled only where a later call has waited for
+ * the context's streams anyway (hipFree may wait for the device by itself), so until then it merely stays allocated.  No host wait for frames
+ * in flight: the one wait is on the call's own build, whose ordering 0 is read back, unfolded into the builder (which stays finished,
+ * marks cleared) and appended to the context's mirrors.  The cost follows the new meshes, plus one device-to-device move on growth.
+ * Nothing of the existing meshes or of the instance level is read or rewritten: the call is accepted after hk_refit_scene_instances,
+ * hk_rebuild_scene_trees, hk_update_materials, hk_update_mesh_vertices, hk_skin_mesh and hk_rebuild_mesh_tree; skins, deformed vertices,
+ * rebuilt trees, wide records and the stale or fresh state of the mirrors stay as they were.  (hk_update_scene_instances is still refused
+ * after a deformation: in that state the new meshes wait for their instances until the host's mirror is uploaded.)
+ * A scene walked from the LDS copy (one slot), or an addition that changes the ordering count: the call does what hk_load_scene does for
+ * the whole builder - small by definition; HK_E_NOT_READY when the mirrors are stale, as any re-layout.
+ *   HK_TREE_SAH / HK_TREE_LBVH as in hk_load_scene: with HK_TREE_SAH the context holds, byte for byte, what hk_upload_scene of a twin
+ *   builder that had every mesh from the start leaves.
+ * With nothing new: HK_OK, nothing enqueued.  HK_E_INVALID with nothing written for NULL, an unknown mode, or a builder whose first meshes
+ * are not the context's (counts of vertices, primitives and nodes, the HkMeshIndex records of the uploaded instances); HK_E_NOT_READY with
+ * nothing written for no scene, an unfinished builder or one finished with stand-in instance trees.  A HIP failure before the scene
+ * pointers are switched leaves the scene the context had; one after it leaves the context WITHOUT a scene, never with stand-in trees.
+ * HkStats: scene_mesh_builds does not move, scene_device_tree_builds counts the meshes built. */
+int hk_add_meshes(hk_ctx* ctx, hk_scene_builder* b, uint32_t tree_mode);
 int hk_upload_textures(hk_ctx* ctx, const HkImageDesc* images, uint32_t n_images);
 /* New texels and sampler fields for ONE uploaded texture of the same width and height (an animated texture; hk_upload_textures replaces
  * the whole array behind a host wait).  The texels go through the pinned staging pool of the deformations and land in place in the
@@ -1025,6 +1058,9 @@ int hk_multi_context(hk_multi* m, uint32_t i, hk_ctx** out); /* the i-th band's 
 int hk_multi_upload_scene(hk_multi* m, const hk_scene_builder* b);
 /* hk_load_scene for every band: the trees are built once (on band 0's device) and written back, the other bands take the finished builder */
 int hk_multi_load_scene(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode);
+/* hk_add_meshes for every band: deferred trees are built once (on band 0's device) and written back, the other bands take the finished
+ * builder's new ranges */
+int hk_multi_add_meshes(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode);
 int hk_multi_upload_scene_instances(hk_multi* m, const hk_scene_builder* b);
 int hk_multi_refit_scene_instances(hk_multi* m, hk_scene_builder* b, uint32_t* moved); /* hk_refit_scene_instances on every band's replica */
 int hk_multi_rebuild_scene_trees(hk_multi* m, uint32_t mode);

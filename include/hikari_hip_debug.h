@@ -22,12 +22,20 @@ int hk_debug_read_mesh_nodes(hk_ctx* ctx, HkNode* out, uint32_t cap, uint32_t* c
 /* Test hook: what the last hk_load_scene of this context did - out[0] meshes whose trees the device built, out[1] their triangles,
  * out[2] the kernel launches of that build (a library sort counted as one), out[3] pending meshes completed by the host instead. */
 int hk_debug_last_load(hk_ctx* ctx, uint32_t out[4]);
+/* Test hook: what the last hk_add_meshes of this context did - out[0] meshes whose trees the device built, out[1] their triangles, out[2]
+ * the kernel launches of that build, out[3] meshes whose trees the host had built (laid out for their ranges), out[4] 1 if the scene
+ * moved to a larger allocation.  All zero after a call that found nothing new. */
+int hk_debug_last_add(hk_ctx* ctx, uint32_t out[5]);
+/* Measurement hook (tools/add_mesh_probe.py): where the host time of the last hk_add_meshes went, in ms - out[0] the allocations of a
+ * relocation (the larger scene, wide records, events), out[1] its copy launch and the switch of the scene pointers, out[2] the growth of
+ * the context's mirrors, out[3] staging, host layout, the device build with its wait and the read-back.  Zero where a step did not run. */
+int hk_debug_last_add_times(hk_ctx* ctx, double out[4]);
 /* Measurement hook (tools/load_probe.py): where the host time of the last hk_load_scene went, in ms - out[0] host completion of meshes
  * beyond the device limit, out[1] the copy into the context's mirrors, out[2] layout of both regions and their upload, out[3] the device
  * build from its first launch to the end of the stream, out[4] the read-back, its unfolding and the write-back into the builder. */
 int hk_debug_last_load_times(hk_ctx* ctx, double out[5]);
-/* Test hook: one mesh deformed on this context (hk_update_mesh_vertices / hk_skin_mesh) as the device holds it after the pending
- * deformations: the positions of the last deformation and the vertex-plane normals (4 floats per vertex), the triangle planes (12
+/* Test hook: one mesh as the device holds it after the pending deformations: the positions of the last deformation (of a mesh never
+ * deformed on this context: gathered from the corners of its triangles, a vertex no triangle names zero; the box their extent) and the vertex-plane normals (4 floats per vertex), the triangle planes (12
  * floats per triangle: v0, v1, v2 as xyz + the vertex-index word) and the mesh box (min xyz, max xyz) decoded from its six words.
  * *n_vertices / *n_triangles receive the counts; all four arrays NULL asks for the counts alone.  Reads only. */
 int hk_debug_read_mesh_geometry(hk_ctx* ctx, const HkMeshIndex* mesh, float* positions, float* normals, uint32_t vertex_cap, float* triangles,
