@@ -889,6 +889,10 @@ int run_pass(hk_ctx* c, uint32_t pass, uint32_t arg, int y0, int y1) {
     }
     case HK_PASS_SMAA_TU4X:
     case HK_PASS_TAA_JASMINE: {  // bindings post_process.rs:983-1035
+      if (c->prev_depth_dirty) {  // the host wrote the previous frame's position plane: its depths go where the gathers read them
+        launch_depth_of_position(c->stream, c->buf[HK_BUF_PREVIOUS_POSITION], c->prev_depth_plane, c->W * c->H);
+        c->prev_depth_dirty = false;
+      }
       AaBuffers ab{};
       ab.position = c->buf[HK_BUF_POSITION]; ab.velocity_uv = c->buf[HK_BUF_VELOCITY_UV];
       ab.previous_position = c->buf[HK_BUF_PREVIOUS_POSITION]; ab.previous_velocity_uv = c->buf[HK_BUF_PREVIOUS_VELOCITY_UV];
@@ -1209,6 +1213,7 @@ static int resize_resources(hk_ctx* c, uint32_t width, uint32_t height, float up
     HK_HIP(hipMemset(c->dn_extra_var[k], 0, nr * 4));
   }
   c->derived_dirty = false;
+  c->prev_depth_dirty = false;
   c->uv_fast = !(c->flags & HK_CTX_PLAIN_DIVISION) && certify_uv_division(c->W) && certify_uv_division(c->H) && certify_uv_division(c->RW) && certify_uv_division(c->RH);
   c->pixel_identity = c->W == c->RW && c->H == c->RH && certify_pixel_identity(c->RW, c->uv_fast) && certify_pixel_identity(c->RH, c->uv_fast);
   c->host_wrote = false;
@@ -1238,6 +1243,9 @@ int hk_frame_begin(hk_ctx* c, const HkFrame* f, const HkView* v, const HkPreviou
   if ((f->number & 1u) != c->mapped_parity) {
     std::swap(c->buf[HK_BUF_POSITION], c->buf[HK_BUF_PREVIOUS_POSITION]);
     std::swap(c->depth_plane, c->prev_depth_plane);
+    // (a host-written position plane whose depths are not derived yet becomes the previous frame's, stale depth plane and all.  The
+    // other way round nothing is carried: this frame's primary rays, or the host with HK_FRAME_EXTERNAL_GBUFFER, fill the current planes)
+    c->prev_depth_dirty = c->derived_dirty;
     std::swap(c->buf[HK_BUF_VELOCITY_UV], c->buf[HK_BUF_PREVIOUS_VELOCITY_UV]);
     std::swap(c->buf[HK_BUF_TONE_MAPPED], c->buf[HK_BUF_PREVIOUS_TONE_MAPPED]);
     std::swap(c->buf[HK_BUF_TAA_OUTPUT], c->buf[HK_BUF_PREVIOUS_TAA_OUTPUT]);
@@ -1871,6 +1879,7 @@ int hk_write_buffer(hk_ctx* c, uint32_t buffer, const void* src, size_t bytes) {
     c->tile_meta_zero[k] = true;
   }
   if (buffer == HK_BUF_POSITION || buffer == HK_BUF_NORMAL || buffer == HK_BUF_INSTANCE_MATERIAL) c->derived_dirty = true;
+  if (buffer == HK_BUF_PREVIOUS_POSITION) c->prev_depth_dirty = true;   // (prev_depth_plane: the anti-aliasing kernels gather the depths there)
   forget_empty_tiles(c);   // (whatever plane was written: the host's bytes are not what the primary rays vouched for)
   c->host_wrote = true;
   return HK_OK;
@@ -1884,6 +1893,9 @@ int hk_device_ptr(hk_ctx* c, uint32_t buffer, void** ptr, size_t* bytes) {
     forget_empty_tiles(c);
     c->host_wrote = true;
   }
+  // (the previous frame's position plane in the host's hands: its depth plane is copied again in front of the next anti-aliasing
+  // dispatch.  The current frame's derived planes follow HK_FRAME_EXTERNAL_GBUFFER - hikari_hip.h)
+  if (buffer == HK_BUF_PREVIOUS_POSITION) c->prev_depth_dirty = true;
   if (bytes) *bytes = c->buf_bytes[buffer];  // the ALLOCATION (independent of the upscale kind in effect), so a host may keep a view across settings changes
   return HK_OK;
 }

@@ -313,6 +313,9 @@ struct hk_ctx {
   void* dn_extra[2][4] = {};
   float* dn_extra_var[2] = {};
   bool derived_dirty = false;
+  // the host wrote HK_BUF_PREVIOUS_POSITION (hk_write_buffer) or holds its pointer (hk_device_ptr): prev_depth_plane is copied from its
+  // .w again in front of the next anti-aliasing dispatch (a frame without such a write launches nothing)
+  bool prev_depth_dirty = false;
   // scratch of the queue-based schedule of indirect_lit_ambient (hikari_hip.h HK_CTX_WAVEFRONT): ONE allocation, carved into
   // the planes of hkd::WfBuffers on first use and again after hk_resize
   void* wf_mem = nullptr;

@@ -443,6 +443,8 @@ struct AaBuffers {
   void* output;                 // rgba16f
   int out_w, out_h;
 };
+// depth[i] = position[i].w of `pixels` rgba32f texels: the depth plane of a position plane the HOST wrote (the previous frame's)
+void launch_depth_of_position(hipStream_t st, const void* position, float* depth, int pixels);
 void launch_smaa_tu4x(hipStream_t st, const AaBuffers& b, uint32_t frame_number, int y0, int y1);
 void launch_smaa_tu4x_extrapolate(hipStream_t st, void* output, int out_w, int out_h, int render_w, int y0, int y1);
 void launch_taa_jasmine(hipStream_t st, const AaBuffers& b, float blend, const float clear_color[4], int y0, int y1);

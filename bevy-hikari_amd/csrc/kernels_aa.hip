@@ -49,17 +49,31 @@ struct Footprint {
 };
 
 HKD int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-HKD void nearest_coords(int w, int h, f2 uv, int* x, int* y) {
-  *x = clampi((int)floorf(uv.x * (float)w), 0, w - 1);
-  *y = clampi((int)floorf(uv.y * (float)h), 0, h - 1);
+// Two flavours of every sampler.  The plain one serves coordinates a kernel derives from its own pixel index (finite, far inside the
+// int range): convert, then clamp the int.  The REPROJECTED one serves everything that has a velocity in it - a velocity plane may
+// hold +-Inf, NaN or 1e9 (a point next to the previous camera plane) - and clamps IN FLOAT, then converts (DESIGN.md section 2,
+// "Texture coordinates outside the int range"): a float -> int conversion of a value outside the int range, an infinity or a NaN is
+// undefined in C++, differs between targets, and at -O3 has indexed outside the plane.  +huge / +Inf give the last texel, -huge /
+// -Inf the first, NaN texel 0 (fmax_ returns the other operand); every coordinate inside the int range gives what the plain flavour
+// gives.  (The clamps cost k_taa_jasmine 2.6 % when every tap takes them, measured; the taps that cannot need them do not.)
+template <bool REPROJECTED>
+HKD int texel_index(float v, int n) {
+  return REPROJECTED ? (int)fmin_(fmax_(v, 0.0f), (float)(n - 1)) : clampi((int)v, 0, n - 1);
 }
+template <bool REPROJECTED = false>
+HKD void nearest_coords(int w, int h, f2 uv, int* x, int* y) {
+  *x = texel_index<REPROJECTED>(floorf(uv.x * (float)w), w);
+  *y = texel_index<REPROJECTED>(floorf(uv.y * (float)h), h);
+}
+template <bool REPROJECTED = false>
 HKD Footprint footprint(int w, int h, f2 uv) {
   const float px = uv.x * (float)w - 0.5f, py = uv.y * (float)h - 0.5f;
   const float flx = floorf(px), fly = floorf(py);
   Footprint f;
   f.fx = px - flx;
   f.fy = py - fly;
-  const int ix = (int)flx, iy = (int)fly;
+  // (reprojected: to [-1, w] in float first - both texels then clamp as before)
+  const int ix = REPROJECTED ? (int)fmin_(fmax_(flx, -1.0f), (float)w) : (int)flx, iy = REPROJECTED ? (int)fmin_(fmax_(fly, -1.0f), (float)h) : (int)fly;
   f.x0 = clampi(ix, 0, w - 1);
   f.x1 = clampi(ix + 1, 0, w - 1);
   f.y0 = clampi(iy, 0, h - 1);
@@ -68,14 +82,15 @@ HKD Footprint footprint(int w, int h, f2 uv) {
 }
 HKD f4 texel(const Plane16& t, int x, int y) { return unpack_f16x4(t.p[x + t.w * y]); }
 HKD f4 texel(const Plane32& t, int x, int y) { return F4(t.p[x + t.w * y]); }
-template <typename P>
+template <bool REPROJECTED = false, typename P>
 HKD f4 sample_nearest(const P& t, f2 uv) {
   int x, y;
-  nearest_coords(t.w, t.h, uv, &x, &y);
+  nearest_coords<REPROJECTED>(t.w, t.h, uv, &x, &y);
   return texel(t, x, y);
 }
+template <bool REPROJECTED = false>
 HKD f4 sample_linear(const Plane16& t, f2 uv) {
-  const Footprint f = footprint(t.w, t.h, uv);
+  const Footprint f = footprint<REPROJECTED>(t.w, t.h, uv);
   const f4 t00 = texel(t, f.x0, f.y0), t10 = texel(t, f.x1, f.y0), t01 = texel(t, f.x0, f.y1), t11 = texel(t, f.x1, f.y1);
   return mix4(mix4(t00, t10, f.fx), mix4(t01, t11, f.fx), f.fy);
 }
@@ -83,8 +98,9 @@ struct PlaneW {  // the w component of a position texture (clip depth) as its ow
   const float* __restrict__ p;
   int w, h;
 };
+template <bool REPROJECTED = false>
 HKD f4 gather_w(const PlaneW& t, f2 uv) {  // textureGather(3, position-like texture, ..)
-  const Footprint f = footprint(t.w, t.h, uv);
+  const Footprint f = footprint<REPROJECTED>(t.w, t.h, uv);
   return F4(t.p[f.x0 + t.w * f.y1], t.p[f.x1 + t.w * f.y1], t.p[f.x1 + t.w * f.y0], t.p[f.x0 + t.w * f.y0]);
 }
 HKD float sample_nearest_w(const PlaneW& t, f2 uv) {
@@ -95,8 +111,13 @@ HKD float sample_nearest_w(const PlaneW& t, f2 uv) {
 HKD void load_loose(const uint2* p, int w, int h, int x, int y, f4* out) {  // textureLoad: zeros out of bounds
   *out = (x >= 0 && y >= 0 && x < w && y < h) ? unpack_f16x4(p[x + w * y]) : F4(0.0f, 0.0f, 0.0f, 0.0f);
 }
+// What the tail stores: a NaN leaves as THE quiet NaN 0x7e00 ("NaNs the tail stores").  IEEE 754 leaves the sign
+// and the payload of a NaN result open and the targets differ - an invalid operation gives 0x7fc00000 here and 0xffc00000 on x86, a
+// subtraction folded into a negated operand flips the sign of a NaN it passes on - so the bits would follow the compiler.
+HKD float canonical_nan(float v) { return v != v ? u2f(0x7fc00000u) : v; }
+HKD uint2 pack_stored(f4 v) { return pack_f16x4(F4(canonical_nan(v.x), canonical_nan(v.y), canonical_nan(v.z), canonical_nan(v.w))); }
 HKD void store_loose(uint2* p, int w, int h, int x, int y, f4 v) {
-  if (x >= 0 && y >= 0 && x < w && y < h) p[x + w * y] = pack_f16x4(v);
+  if (x >= 0 && y >= 0 && x < w && y < h) p[x + w * y] = pack_stored(v);
 }
 
 HKD f3 rgb(f4 a) { return F3(a.x, a.y, a.z); }
@@ -161,6 +182,11 @@ struct AaTargets {
   int ow, oh;
 };
 
+__global__ __launch_bounds__(256) void k_depth_of_position(const float4* __restrict__ position, float* __restrict__ depth, int pixels) {
+  const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (i < pixels) depth[i] = position[i].w;
+}
+
 __global__ __launch_bounds__(256) void k_taa_jasmine(AaTargets t, float blend, float4 clear_color, int row_begin, int row_end) {
   const Pixel px = pixel_of_thread_rows<64, false>(t.ow, row_begin, row_end);
   if (!px.valid) return;
@@ -181,18 +207,18 @@ __global__ __launch_bounds__(256) void k_taa_jasmine(AaTargets t, float blend, f
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
     const f2 bias = i == 0 ? F2(0.0f, 0.0f) : F2((i & 1) ? 1.5f : -1.5f, i <= 2 ? 1.5f : -1.5f) * texel_size;
-    const f4 previous_depths = gather_w(t.previous_depth, previous_uv + bias);
+    const f4 previous_depths = gather_w<true>(t.previous_depth, previous_uv + bias);
     const f4 depth_ratio = depth_ratio4(current_position_depth.w, previous_depths);
     has_content = has_content || any_gt(previous_depths, 0.0f);
     depth_miss = depth_miss || any_lt(depth_ratio, 0.95f);
-    const f3 pp = xyz(sample_nearest(t.previous_position, previous_uv + bias));
+    const f3 pp = xyz(sample_nearest<true>(t.previous_position, previous_uv + bias));
     position_miss = position_miss || length(xyz(current_position_depth) - pp) > 0.5f;
   }
   if (!has_content) {
-    t.output[x + t.ow * y] = pack_f16x4(F4(clear_color));
+    t.output[x + t.ow * y] = pack_stored(F4(clear_color));
     return;
   }
-  const f4 pv = sample_nearest(t.previous_velocity_uv, previous_uv);
+  const f4 pv = sample_nearest<true>(t.previous_velocity_uv, previous_uv);
   const bool velocity_miss = length2(velocity - F2(pv.x, pv.y)) > 0.00005f;
   // 5-tap Catmull-Rom reprojection, taa.wgsl:127-144
   const f2 sample_position = (uv - velocity) * size;
@@ -208,7 +234,7 @@ __global__ __launch_bounds__(256) void k_taa_jasmine(AaTargets t, float blend, f
   const f2 tp0 = (texel_position_1 - 1.0f) * texel_size;
   const f2 tp3 = (texel_position_1 + 2.0f) * texel_size;
   const f2 tp12 = (texel_position_1 + offset12) * texel_size;
-  auto prev = [&](float u, float v) { return clamp01(rgb(sample_linear(t.previous_render, F2(u, v)))); };
+  auto prev = [&](float u, float v) { return clamp01(rgb(sample_linear<true>(t.previous_render, F2(u, v)))); };
   f3 previous_color = F3(0.0f, 0.0f, 0.0f);
   previous_color = previous_color + prev(tp12.x, tp0.y) * w12.x * w0.y;
   previous_color = previous_color + prev(tp0.x, tp12.y) * w0.x * w12.y;
@@ -236,7 +262,7 @@ __global__ __launch_bounds__(256) void k_taa_jasmine(AaTargets t, float blend, f
     previous_color = YCoCg_to_RGB(previous_color);
   }
   const f3 out = mix(previous_color, current_color, blend);  // taa.wgsl:167
-  t.output[x + t.ow * y] = pack_f16x4(F4(out, original_color.w));
+  t.output[x + t.ow * y] = pack_stored(F4(out, original_color.w));
 }
 
 __global__ __launch_bounds__(256) void k_smaa_tu4x(AaTargets t, uint32_t frame_number, int row_begin, int row_end) {
@@ -256,11 +282,11 @@ __global__ __launch_bounds__(256) void k_smaa_tu4x(AaTargets t, uint32_t frame_n
   const f2 previous_output_uv = F2(((float)pox + 0.5f) / output_size.x, ((float)poy + 0.5f) / output_size.y);
   const f2 velocity = nearest_velocity(t.depth, t.velocity_uv, previous_output_uv, deferred_texel);
   const f2 previous_reprojected_uv = previous_output_uv - velocity;
-  f3 previous_color = rgb(sample_nearest(t.previous_render, previous_reprojected_uv));
+  f3 previous_color = rgb(sample_nearest<true>(t.previous_render, previous_reprojected_uv));
   const bool boundary_miss = fabsf(previous_reprojected_uv.x - 0.5f) > 0.5f || fabsf(previous_reprojected_uv.y - 0.5f) > 0.5f;
-  auto instance_at = [&](f2 p) {
+  auto instance_at = [&](f2 p) {   // (the reprojected flavour for both uses: one of them has the velocity in it)
     int ix, iy;
-    nearest_coords(t.position.w, t.position.h, p, &ix, &iy);
+    nearest_coords<true>(t.position.w, t.position.h, p, &ix, &iy);
     return t.instance_material[ix + t.position.w * iy].x;
   };
   const float current_instance = instance_at(previous_output_uv);
@@ -270,14 +296,14 @@ __global__ __launch_bounds__(256) void k_smaa_tu4x(AaTargets t, uint32_t frame_n
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
     const f2 bias = i == 0 ? F2(0.0f, 0.0f) : F2((i & 1) ? 2.5f : -2.5f, i <= 2 ? 2.5f : -2.5f) * texel_size;
-    const f4 previous_depths = gather_w(t.previous_depth, previous_reprojected_uv + bias);
+    const f4 previous_depths = gather_w<true>(t.previous_depth, previous_reprojected_uv + bias);
     const f4 depth_ratio = depth_ratio4(current_depth, previous_depths);
     const bool any_ratio = any_lt(depth_ratio, 0.95f);
     depth_miss = depth_miss || any_ratio;
     const float previous_instance = instance_at(previous_reprojected_uv + bias);  // the CURRENT instance texture, smaa.wgsl:149
     instance_miss = instance_miss || (any_ratio && fabsf(previous_instance - current_instance) > 1.0f);
   }
-  const f4 pv = sample_nearest(t.previous_velocity_uv, previous_reprojected_uv);
+  const f4 pv = sample_nearest<true>(t.previous_velocity_uv, previous_reprojected_uv);
   const bool velocity_miss = length2(velocity - F2(pv.x, pv.y)) > 0.0001f;
   if (boundary_miss || ((depth_miss || instance_miss) && velocity_miss)) {  // 2x2 YCoCg variance clipping, smaa.wgsl:156-184
     f2 uv_bias = F2(0.0f, 0.0f);
@@ -474,7 +500,7 @@ __global__ __launch_bounds__(256) void k_fsr_easu(FsrEasuArgs a, int row_begin, 
   HK_EASU_TAP(0.0f, 2.0f, zzon, w);   // n
 #undef HK_EASU_TAP
   const f3 pix = min3(max4, max3(min4, aC * (1.0f / aW)));
-  a.output[px.x + a.ow * px.y] = pack_f16x4(F4(pix.x, pix.y, pix.z, 1.0f));  // hdr == 0 (post_process.rs:531)
+  a.output[px.x + a.ow * px.y] = pack_stored(F4(pix.x, pix.y, pix.z, 1.0f));  // hdr == 0 (post_process.rs:531)
 }
 __global__ __launch_bounds__(256) void k_fsr_rcas(const uint2* __restrict__ input, uint2* __restrict__ output, int w, int h, float sharpness,
                                                   int row_begin, int row_end) {
@@ -501,7 +527,7 @@ __global__ __launch_bounds__(256) void k_fsr_rcas(const uint2* __restrict__ inpu
   const float pixR = (lobe * b.x + lobe * d.x + lobe * hh.x + lobe * f.x + e.x) * rcpL;
   const float pixG = (lobe * b.y + lobe * d.y + lobe * hh.y + lobe * f.y + e.y) * rcpL;
   const float pixB = (lobe * b.z + lobe * d.z + lobe * hh.z + lobe * f.z + e.z) * rcpL;
-  output[px.x + w * px.y] = pack_f16x4(F4(pixR, pixG, pixB, 1.0f));
+  output[px.x + w * px.y] = pack_stored(F4(pixR, pixG, pixB, 1.0f));
 }
 
 // ------------------------------------------------------------------ present (OverlayNode, overlay.rs:311-395, overlay.wgsl:28-48)
@@ -584,6 +610,10 @@ static AaTargets make_targets(const AaBuffers& b) {
   return t;
 }
 
+void launch_depth_of_position(hipStream_t st, const void* position, float* depth, int pixels) {
+  if (pixels <= 0) return;
+  hipLaunchKernelGGL(k_depth_of_position, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, (const float4*)position, depth, pixels);
+}
 void launch_smaa_tu4x(hipStream_t st, const AaBuffers& b, uint32_t frame_number, int y0, int y1) {
   if (y1 <= y0) return;
   hipLaunchKernelGGL(k_smaa_tu4x, grid_for_rows(64, b.render_w, y1 - y0), dim3(256), 0, st, make_targets(b), frame_number, y0, y1);

@@ -1092,7 +1092,10 @@ int hk_multi_read_buffer(hk_multi* m, uint32_t buffer, void* dst, size_t bytes);
 
 /* ------------------------------------------------------------------ buffer access */
 int hk_buffer_info(hk_ctx* ctx, uint32_t buffer, uint32_t* width, uint32_t* height, uint32_t* bytes_per_pixel);
-/* synchronous copies (wait for the stream first) */
+/* synchronous copies (wait for the stream first).  Both position planes may be written: the library keeps the depths (.w) of
+ * HK_BUF_POSITION and of HK_BUF_PREVIOUS_POSITION in planes of its own, which the denoiser and the anti-aliasing kernels gather
+ * from, and copies them again from a plane hk_write_buffer wrote before the next dispatch that reads them (hk_pass_run and
+ * hk_frame_stage alike).  A frame that writes neither launches nothing for it. */
 int hk_read_buffer(hk_ctx* ctx, uint32_t buffer, void* dst, size_t bytes);
 int hk_write_buffer(hk_ctx* ctx, uint32_t buffer, const void* src, size_t bytes);
 /* raw device pointer for zero-copy views (a host that composites or exchanges the buffers itself).  *bytes = the size of the
@@ -1101,7 +1104,9 @@ int hk_write_buffer(hk_ctx* ctx, uint32_t buffer, const void* src, size_t bytes)
  * A host that WRITES a G-buffer, albedo, render or variance plane through such a pointer does so before the frame's first stage (with
  * HK_FRAME_EXTERNAL_GBUFFER for the G-buffer): between two hk_frame_stage calls of one frame the library may rely on what the stages
  * before wrote there (the empty-tile plane of the primary rays).  Asking for the pointer of one of those ids makes the frame in
- * progress and the next one take no such shortcut; a pointer kept for longer is the host's to use by this rule. */
+ * progress and the next one take no such shortcut; a pointer kept for longer is the host's to use by this rule.
+ * Asking for HK_BUF_PREVIOUS_POSITION makes the next anti-aliasing dispatch copy that plane's depths again (as after
+ * hk_write_buffer); a host that writes it through a pointer it kept asks again after writing, or uses hk_write_buffer. */
 int hk_device_ptr(hk_ctx* ctx, uint32_t buffer, void** ptr, size_t* bytes);
 /* the HIP stream the context enqueues its frames on.  Without hk_set_stream it is the context's own; the context's FIRST frame may
  * create it again at the device's highest priority (round 6: the frame's dependent chain ahead of the direct-light and a-trous

@@ -193,12 +193,21 @@ struct Tex {
     uint16_t* h16 = (uint16_t*)(p + ((size_t)y * w + x) * 8);
     h16[0] = f32_to_f16(v.x); h16[1] = f32_to_f16(v.y); h16[2] = f32_to_f16(v.z); h16[3] = f32_to_f16(v.w);
   }
+  // the stores of the anti-aliasing / upscale tail: a NaN is stored as the quiet NaN 0x7e00, whatever its sign and payload (IEEE 754
+  // leaves both open for a NaN result, and x86 and gfx950 differ: DESIGN.md section 2, "NaNs the tail stores")
+  void store_f16x4_canonical(int x, int y, v4 v) const {
+    auto c = [](float f) { return f != f ? u2f(0x7fc00000u) : f; };
+    store_f16x4(x, y, V4(c(v.x), c(v.y), c(v.z), c(v.w)));
+  }
   // textureSampleLevel(tex, nearest_sampler, uv, 0): nearest filter, clamp-to-edge
   // (post_process.rs sampler bind group; denoise.wgsl:5-8)
+  // The coordinate is clamped in float and converted afterwards ("Texture coordinates outside the int
+  // range"): converting a value beyond the int range, an infinity or a NaN is undefined.  +huge / +Inf: the last texel,
+  // -huge / -Inf: the first, NaN: texel 0 (fmax_ returns the operand that is a number).
+  static int texel_index(float v, int n) { return (int)fmin_(fmax_(v, 0.0f), (float)(n - 1)); }
   void nearest_coords(v2 uv, int* x, int* y) const {
-    int cx = (int)floorf(uv.x * (float)w), cy = (int)floorf(uv.y * (float)h);
-    *x = std::min(std::max(cx, 0), w - 1);
-    *y = std::min(std::max(cy, 0), h - 1);
+    *x = texel_index(floorf(uv.x * (float)w), w);
+    *y = texel_index(floorf(uv.y * (float)h), h);
   }
   // The 2x2 footprint of the linear sampler (post_process.rs:685-690: mag/min Linear, address mode
   // clamp-to-edge): texel centres at integer + 0.5.  The numeric contract fixes what WGSL leaves to the
@@ -210,7 +219,7 @@ struct Tex {
     Footprint f;
     f.fx = px - flx;
     f.fy = py - fly;
-    int ix = (int)flx, iy = (int)fly;
+    int ix = (int)fmin_(fmax_(flx, -1.0f), (float)w), iy = (int)fmin_(fmax_(fly, -1.0f), (float)h);  // [-1, w] in float, then the int clamp
     f.x0 = std::min(std::max(ix, 0), w - 1);
     f.x1 = std::min(std::max(ix + 1, 0), w - 1);
     f.y0 = std::min(std::max(iy, 0), h - 1);
@@ -1971,7 +1980,7 @@ static void pass_taa_jasmine(Ctx* c, int y0, int y1) {  // taa.wgsl:75-170
         position_miss = position_miss || distance3(xyz(current_position_depth), pp) > 0.5f;
       }
       if (!has_content) {
-        output.store_f16x4(x, y, P4(c->frame.clear_color));
+        output.store_f16x4_canonical(x, y, P4(c->frame.clear_color));
         continue;
       }
       v4 pv = previous_velocity_uv.sample_nearest(previous_uv);
@@ -2018,7 +2027,7 @@ static void pass_taa_jasmine(Ctx* c, int y0, int y1) {  // taa.wgsl:75-170
         previous_color = YCoCg_to_RGB(previous_color);
       }
       v3 out = mix(previous_color, current_color, blend);  // taa.wgsl:167
-      output.store_f16x4(x, y, V4(out, original_color.w));
+      output.store_f16x4_canonical(x, y, V4(out, original_color.w));
     }
 }
 
@@ -2092,8 +2101,8 @@ static void pass_smaa_tu4x(Ctx* c, int y0, int y1) {  // smaa.wgsl:81-188; one t
       blend_factor = clamp_(-cos_(blend_factor * TAU), 0.0f, 1.0f);
       v3 remix_color = rgb(render.sample_linear(previous_output_uv));
       previous_color = mix(previous_color, remix_color, blend_factor);
-      output.store_f16x4(cox, coy, V4(current_color, 1.0f));
-      output.store_f16x4(pox, poy, V4(previous_color, 1.0f));
+      output.store_f16x4_canonical(cox, coy, V4(current_color, 1.0f));
+      output.store_f16x4_canonical(pox, poy, V4(previous_color, 1.0f));
     }
 }
 
@@ -2244,7 +2253,7 @@ static void pass_fsr_easu(Ctx* c, int y0, int y1) {  // FSR_Pass.glsl CurrFilter
       tap(1.0f, 2.0f, zzon.r.z, zzon.g.z, zzon.b.z);   // o
       tap(0.0f, 2.0f, zzon.r.w, zzon.g.w, zzon.b.w);   // n
       v3 pix = min3(max4, max3(min4, aC * (1.0f / aW)));
-      output.store_f16x4(x, y, V4(pix, 1.0f));          // hdr == 0: no c *= c
+      output.store_f16x4_canonical(x, y, V4(pix, 1.0f));          // hdr == 0: no c *= c
     }
 }
 static void pass_fsr_rcas(Ctx* c, int y0, int y1) {  // FSR_Pass.glsl CurrFilter (SAMPLE_RCAS) + ffx_fsr1.h:662-768
@@ -2274,7 +2283,7 @@ static void pass_fsr_rcas(Ctx* c, int y0, int y1) {  // FSR_Pass.glsl CurrFilter
       float pixR = (lobe * b.x + lobe * d.x + lobe * h.x + lobe * f.x + e.x) * rcpL;
       float pixG = (lobe * b.y + lobe * d.y + lobe * h.y + lobe * f.y + e.y) * rcpL;
       float pixB = (lobe * b.z + lobe * d.z + lobe * h.z + lobe * f.z + e.z) * rcpL;
-      output.store_f16x4(x, y, V4(pixR, pixG, pixB, 1.0f));
+      output.store_f16x4_canonical(x, y, V4(pixR, pixG, pixB, 1.0f));
     }
 }
 
@@ -2309,8 +2318,8 @@ static void pass_smaa_tu4x_extrapolate(Ctx* c, int y0, int y1) {  // smaa.wgsl:2
       v3 factor = differential_blend_factor(t_color, b_color, n_color, e_color, s_color, w_color);
       v4 x_color = differential_blend(t_color, s_color, w_color, b_color, factor);
       v4 y_color = differential_blend(n_color, b_color, t_color, e_color, factor);
-      output.store_f16x4(bx, by + 1, x_color);
-      output.store_f16x4(bx + 1, by, y_color);
+      output.store_f16x4_canonical(bx, by + 1, x_color);
+      output.store_f16x4_canonical(bx + 1, by, y_color);
     }
 }
 

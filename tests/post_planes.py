@@ -280,3 +280,413 @@ def install(engine, planes, resize=True):
     engine.frame_begin(planes.frame, camera.view_uniform(), camera.previous_view_uniform(None), hk.lights_uniform())
     for buf, array in planes.buffers.items():
         engine.write(buf, array)          # (hk_write_buffer refuses a size that is not the buffer's)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The anti-aliasing / upscale tail: k_smaa_tu4x, k_smaa_tu4x_extrapolate, k_taa_jasmine, k_fsr_easu, k_fsr_rcas
+# ------------------------------------------------------------------------------------------------------------------------------
+"""Plane sets for the tail (`make_aa_planes`).  The five kernels read the tone-mapped image of this frame and the last one, the
+last TAA output, both position and velocity planes and the instance ids; `upscale_output` is filled as well, for the passes that
+are run alone on a written input (the extrapolate pass, RCAS, and TAA under SMAA Tu4x).  Coordinates below are RENDER pixels of a
+130 x 17 image; a special goes to the texel of each plane that lies under that pixel's centre, blocks scale with the plane.
+
+  flat       exactly constant 3 x 3 patches of render pixels (3 x 3 for TAA, 2 x 2 for SMAA and more) at 0, 1, 0.5, at the two first
+             levels of FLAT_LEVELS and at one coloured constant, with the history equal to the patch (`v_clip / e_clip` is 0 / 0) or
+             coloured above / below it in every YCoCg component (+Inf, -Inf), inside blocks where every reprojection test misses
+             (so the clip runs); one image carries five of the 17 patches, which ones rotates with the setting and the parity.
+             `moment_2 / n - mean * mean` rounds below zero in f32 at the FLAT_LEVELS (found by `negative_residue_levels`, a search
+             over the f16 greys); EASU sees a flat input (`zro`, and `prx_lo_rcp(0)`), RCAS a flat 0 (`0 * (1 / 0)`) and a flat 1
+             (`4 * mn4 - 4 == 0`).
+  hdr        NaN, +Inf, -Inf, 65504, -0.0, negative values and values above 1 in single components of the current and the history
+             colour planes, isolated and as a block of 2 x 2 render pixels (at least 4 x 4 texels of the upscaled planes: every tap of RCAS's cross and
+             of the extrapolate pass's six loads non-finite for a pixel inside) and, under FSR1, of 3 x 3 in the image's corner (EASU's 12 taps); alphas other than 1.
+  reproject  velocities (the fill moves by 0.3 output texels: at 0 every gather of the previous frame sits on a texel centre): 0, one
+             and half an output texel, the values whose `fract(v / (2 texel))` is 0, 0.25 and 0.5 and the same
+             negated, a `previous_uv` of exactly 0 and 1 and one f32 ulp outside, +-3, 1e9, 3e38, +-Inf, NaN;
+             `|velocity - previous_velocity|` at 0.00005 and 0.0001, one ulp either side.
+  depth      previous depths 0, negative, NaN, +Inf and a denormal; current depth 0; a depth ratio of 0.95 and one ulp either side;
+             a position distance of 0.5 and one ulp either side; a block whose 20 gathered previous depths are all <= 0 under a
+             current depth of 0 (the clear colour), with ONE positive texel in a second such block (every bias and gather corner
+             sees it alone from some pixel); corner depths of `nearest_velocity` with two, three and four ties at the maximum, the
+             centre equal to the maximum, NaN among the corners.
+  instance   stripes of instance ids that differ by 0, by 1.0 exactly and by 1 + ulp, the upper half of each with a depth-ratio
+             miss at the same taps and the lower half without, under a velocity miss.
+  random     dense seeded noise with a small COUNT of each special."""
+AA_SETS = ("flat", "hdr", "reproject", "depth", "instance", "random")
+#: name -> (upscale, taa): SMAA Tu4x at ratio 2 (with `window_for`, an odd window: 2 x render > output, store_loose cuts the quad)
+#: and at ratio 1, FSR1 at 1.0 / 1.5 / 2.0 with TAA at the scaled size, TAA on and off, sharpness 0, 0.2 and 2
+AA_SETTINGS = {
+    "smaa2_taa": (hk.Upscale.SmaaTu4x(2.0), hk.Taa.Jasmine),
+    "smaa2": (hk.Upscale.SmaaTu4x(2.0), hk.Taa.NONE),
+    "smaa1_taa": (hk.Upscale.SmaaTu4x(1.0), hk.Taa.Jasmine),
+    "fsr10_taa": (hk.Upscale.Fsr1(1.0, 0.2), hk.Taa.Jasmine),
+    "fsr15_taa": (hk.Upscale.Fsr1(1.5, 2.0), hk.Taa.Jasmine),
+    "fsr20": (hk.Upscale.Fsr1(2.0, 0.0), hk.Taa.NONE),
+}
+FSR_SIZES = (1, 15, 16, 17, 33, 130)       # output widths / heights for the 16 x 16 tiles of the two FSR kernels
+
+
+def _ycocg_y32(c):
+    """y of RGB_to_YCoCg for a grey c, in f32 and in the shaders' order"""
+    c = np.float32(c)
+    return np.float32(np.float32(c / np.float32(4.0)) + np.float32(c / np.float32(2.0))) + np.float32(c / np.float32(4.0))
+
+
+def negative_residue_levels(n, count=4):
+    """f16 greys in (0, 1) for which `moment_2 / n - mean * mean` over n equal samples is NEGATIVE in f32 (sums left to right, as
+    the shaders write them): sqrt of it is NaN, and the clip box has NaN corners on an exactly constant neighbourhood."""
+    found = []
+    for bits in range(0x3000, 0x3C00, 7):          # 0.125 .. 1, every 7th f16
+        y = _ycocg_y32(np.uint16(bits).view(np.float16))
+        m1, m2, sq = np.float32(0), np.float32(0), np.float32(y * y)
+        for _ in range(n):
+            m1, m2 = np.float32(m1 + y), np.float32(m2 + sq)
+        mean = np.float32(m1 / np.float32(n))
+        if np.float32(np.float32(m2 / np.float32(n)) - np.float32(mean * mean)) < 0:
+            found.append(bits)
+            if len(found) == count:
+                break
+    return found
+
+
+#: the greys `negative_residue_levels` finds (f16 bits: 0.1668, 0.1685, 0.1703, 0.172), for the nine samples of TAA; the test module
+#: asserts that the search still gives this list.  For the four samples of SMAA Tu4x there are none, whatever the colour: 4 s and
+#: 4 (s * s) are exact in f32 and so are their quarters, so `moment_2 / 4 - mean * mean` is s * s - s * s = 0 exactly.
+FLAT_LEVELS = {9: [0x3157, 0x3165, 0x3173, 0x3181], 4: []}
+
+
+class AaPlanes:
+    def __init__(self, name, seed, window_size, setting, frame_number):
+        self.name, self.seed, self.window_size, self.setting = name, seed, tuple(window_size), setting
+        self.upscale, self.taa = AA_SETTINGS[setting]
+        self.ratio = float(self.upscale.ratio())
+        self.settings = hk.HikariSettings(indirect_bounces=1, upscale=self.upscale, taa=self.taa, clear_color=CLEAR_COLOR)
+        self.frame = hk.frame_uniform(self.settings, frame_number)
+        for i in range(4):
+            self.frame.clear_color[i] = CLEAR_COLOR[i]
+        w, h = self.window_size
+        self.render_size = render_size_of(window_size, self.ratio)
+        scale2 = np.float32(np.float32(1.0) / np.float32(self.ratio)) * np.float32(2.0)
+        self.smaa = self.upscale.kind == F.UPSCALE_SMAA_TU4X
+        self.upscaled_size = (int(np.ceil(np.float32(w) * scale2)), int(np.ceil(np.float32(h) * scale2)))     # UW x UH of hk_resize
+        self.output_size = self.upscaled_size if self.smaa else self.window_size             # upscale_output
+        self.taa_size = self.upscaled_size if self.smaa else self.render_size               # taa_output, previous_taa_output
+        self.buffers, self.placed = {}, {}
+
+    @property
+    def passes(self):
+        """the dispatches of the tail for these settings, in PostProcessNode::run's order"""
+        p = [F.PASS_SMAA_TU4X, F.PASS_SMAA_TU4X_EXTRAPOLATE] if self.smaa else []
+        p += [F.PASS_TAA_JASMINE] if self.taa == hk.Taa.Jasmine else []
+        return p + ([] if self.smaa else [F.PASS_FSR_EASU, F.PASS_FSR_RCAS])
+
+
+def aa_window_for(shape, setting):
+    """the window for a RENDER shape (the 64 x 4 row kernels) under a setting"""
+    return window_for(shape, AA_SETTINGS[setting][0].ratio())
+
+
+def make_aa_planes(name, seed, window_size, setting, frame_number=2, compact=False):
+    assert name in AA_SETS
+    p = AaPlanes(name, seed, window_size, setting, frame_number)
+    rng = np.random.default_rng([seed, 100 + AA_SETS.index(name)])
+    (dw, dh), (rw, rh), (tw, th), (ow, oh) = p.window_size, p.render_size, p.taa_size, p.output_size
+    lw, lh = (rw, rh) if compact else (130, 17)            # the layout the coordinates below are written for
+
+    class Grid:
+        """one plane size: where the render pixel (x, y) of the layout lies in it, as [row, column]; outside the image -> the spare"""
+        def __init__(self, w, h):
+            self.w, self.h = w, h
+            self.placed = np.zeros((h + 1, w + 1), bool)
+
+        def fit(self, x, y):
+            if compact:
+                x, y = x * rw // 130, y * rh // 17
+            return x, y
+
+        def at(self, x, y):
+            x, y = self.fit(x, y)
+            if not (0 <= x < rw and 0 <= y < rh):
+                return self.h, self.w
+            return min(int((y + 0.5) / rh * self.h), self.h - 1), min(int((x + 0.5) / rw * self.w), self.w - 1)
+
+        def block(self, x, y, size):
+            """`size` render pixels square with its corner at (x, y), in this plane's texels (at least size texels)"""
+            r, c = self.at(x, y)
+            if r == self.h:
+                return slice(self.h, self.h + 1), slice(self.w, self.w + 1)
+            nr, nc = max(size, int(np.ceil(size * self.h / rh))), max(size, int(np.ceil(size * self.w / rw)))
+            return slice(r, min(r + nr, self.h)), slice(c, min(c + nc, self.w))
+
+        def mark(self, where):
+            self.placed[where] = True
+
+    G, R, T, O = Grid(dw, dh), Grid(rw, rh), Grid(tw, th), Grid(ow, oh)
+    spare = lambda a: np.pad(a, [(0, 1), (0, 1)] + [(0, 0)] * (a.ndim - 2))
+
+    # ---- the benign fill.  Every reprojection test holds (velocities differ from texel to texel by less than both thresholds): the
+    # clip runs where a set places a block in which every test misses (`still(miss=True)`: previous depth doubled, previous position
+    # 1 away, previous velocity 0.01 off) and nowhere else - at ratio 2 the clip's own gathers sit on texel centres, where rounding
+    # picks the footprint, and a comparison may leave out 2 %.  The last 10 % of the upper half has no geometry now or before (the
+    # clear colour)
+    gx, gy = np.meshgrid(np.arange(dw), np.arange(dh))
+    missing = np.zeros((dh, dw), bool)
+    background = (gx >= dw - max(1, dw // 10)) & (gy < dh // 2) if dw > 8 else np.zeros((dh, dw), bool)
+    depth = (2.0 + 0.002 * gx + 0.003 * gy).astype(np.float32)
+    position = np.zeros((dh, dw, 4), np.float32)
+    position[..., 0], position[..., 1], position[..., 2] = 0.01 * gx, 0.01 * gy, 0.005 * (gx + gy)
+    position[..., 3] = depth
+    previous_position = position + np.float32(0.002) * rng.random((dh, dw, 4)).astype(np.float32)
+    previous_position[missing, 3] *= np.float32(2.0)
+    previous_position[missing, 0] += np.float32(1.0)
+    position[background, 3] = 0.0
+    previous_position[background, 3] = 0.0
+    velocity = np.zeros((dh, dw, 4), np.float32)
+    velocity[..., :2] = (0.0002 + 0.00002 * (rng.random((dh, dw, 2)) - 0.5)).astype(np.float32)
+    # (half the columns move by about 0.2 G-buffer texels exactly: a velocity of 0 puts every gather of the previous frame on a texel centre,
+    # where rounding picks the footprint - the `reproject` set places it, the fill keeps off it)
+    steady = np.array([0.1871 / dw, 0.2137 / dh], np.float32)      # (in G-buffer texels, no simple fraction - the gathers stay off the texel centres at every ratio - and short of the quarter texel between the first SMAA sample and the border)
+    velocity[(gx // 16) % 2 == 0, :2] = steady
+    previous_velocity = velocity.copy()
+    previous_velocity[..., :2] += (2e-6 * rng.random((dh, dw, 2))).astype(np.float32)
+    previous_velocity[missing, 0] += np.float32(0.01)
+    instance = np.zeros((dh, dw, 2), np.float32)
+    instance[..., 0] = np.where(gx < dw // 3, 1.0, 3.0)
+    instance[..., 1] = 0.5
+
+    def colour(grid, alpha_noise):
+        c = np.ones((grid.h, grid.w, 4), np.float32)
+        c[..., :3] = 0.05 + 0.9 * rng.random((grid.h, grid.w, 3))
+        if alpha_noise:
+            c[..., 3] = 0.25 + 0.75 * rng.random((grid.h, grid.w))
+        return spare(f16_bits(c))
+
+    position, previous_position, velocity, previous_velocity, instance = (spare(a) for a in (position, previous_position, velocity, previous_velocity, instance))
+    tone, prev_tone, prev_taa, upscaled = colour(R, name == "hdr"), colour(R, False), colour(T, False), colour(O, name == "hdr")
+    current, history = [(tone, R), (upscaled, O)], [(prev_tone, R), (prev_taa, T)]
+    one_ulp = lambda v, towards: np.nextafter(np.float32(v), np.float32(towards))
+
+    # One special texel costs a comparison a dozen or more pixels (every kernel here has a footprint), and a comparison may leave out
+    # 2 % of a dispatch: an image carries every sixth of a set's blocks (`turns`) - which, rotates with the setting and the parity, so that
+    # every block meets every kernel under one SMAA Tu4x and one FSR1 setting
+    # (an image under 2000 render pixels: every twelfth - its 2 % are a dozen pixels)
+    turns = 6 if rw * rh >= 2000 else 12
+    variant = (2 * list(AA_SETTINGS).index(setting) + frame_number % 2) % turns
+    mine = lambda k: k % turns == variant
+
+    def still(x, y, size, miss):
+        """a block that moves by `steady` (the reprojected uv lies 0.3 texels from the pixel's own) with every test missing or holding"""
+        b = G.block(x, y, size)
+        velocity[b] = 0.0
+        velocity[b + (slice(0, 2),)] = steady
+        previous_velocity[b] = velocity[b]
+        if miss:
+            previous_velocity[b + (0,)] = steady[0] + np.float32(0.01)
+        previous_position[b] = position[b]
+        if miss:
+            previous_position[b + (3,)] = position[b + (3,)] * np.float32(2.0)
+            previous_position[b + (0,)] = position[b + (0,)] + np.float32(1.0)
+        return b
+
+    if name == "flat":
+        # (level, history): the history equal to the patch (0 / 0 in the clip), or coloured above / below it in every YCoCg component
+        # (+Inf / -Inf).  A comparison may leave out 2 % of a dispatch and at ratio 2 every clipped pixel of SMAA Tu4x sits within
+        # rounding of a gather boundary, so one image carries five of the patches (three under 2000 render pixels): which, rotates with the setting and the parity
+        greys = [0x0000, H_ONE, 0x3800] + FLAT_LEVELS[9][:2]
+        patches = [(bits, hist) for bits in greys for hist in ("equal", "above", "below")] + [((0.75, 0.25, 0.5), "equal"), ((0.75, 0.25, 0.5), "above")]
+        variant = 2 * list(AA_SETTINGS).index(setting) + frame_number % 2
+        chosen = [patches[(variant + 4 * k) % len(patches)] for k in range(4 if turns == 6 else 2)]
+        chosen = chosen[:1] + [patches[(variant * 5 + 1) % len(patches)]] + chosen[1:]          # (the second lies where every test holds: no clip)
+        for k, (level, hist) in enumerate(chosen):
+            x, y = 6 + 24 * k, 2 + 3 * (k % 4)
+            still(x, y, 3, miss=k != 1)
+            rgbv = np.array(level if isinstance(level, tuple) else [float(np.uint16(level).view(np.float16))] * 3, np.float32)
+            past = {"equal": rgbv, "above": rgbv * np.float32([1.5, 2.0, 1.25]) + np.float32([0.125, 0.25, 0.0625]), "below": rgbv * np.float32([0.5, 0.25, 0.75])}[hist]
+            for planes, value in ((current, rgbv), (history, past)):
+                for a, grid in planes:
+                    b = grid.block(x, y, 3)
+                    a[b + (slice(0, 3),)] = f16_bits(value)
+                    grid.mark(b)
+    elif name == "hdr":
+        # (few: one non-finite texel reaches 16 outputs of EASU and a dozen of TAA, and a comparison may leave out 2 % of a dispatch)
+        singles = {"current": [(5, 3, 0, H_NAN), (33, 5, 2, 0xC100), (58, 8, 1, 0x4500), (84, 12, 0, H_MAX), (104, 2, 1, H_NZERO), (12, 14, 2, 0xBC00), (70, 15, 3, 0x3800)],
+                   "history": [(20, 2, 1, H_INF), (50, 10, 0, H_NAN), (95, 13, 2, H_NINF), (110, 6, 1, 0x4000), (40, 6, 0, 0xB800), (33, 5, 2, 0x4500)]}
+        for planes, key in ((current, "current"), (history, "history")):
+            for k, (x, y, comp, bits) in enumerate(singles[key]):
+                if not (mine(k) or (key == "current" and turns == 6 and mine(k + 3))):
+                    continue
+                for a, grid in planes:
+                    where = grid.at(x, y)
+                    a[where + (comp,)] = bits
+                    if key == "current":      # (a history texel: the Catmull-Rom taps that sit on texel centres next to it hang on rounding - not `placed`)
+                        grid.mark(where)
+        # (FSR1: the block sits in the image's corner, 3 x 3 render pixels - with clamp-to-edge all 12 taps of EASU's first output pixels
+        # are non-finite, and the block reaches a quarter of the outputs it would reach in the middle)
+        corner = [(0, 0, 3, H_NAN if frame_number % 2 else H_INF)] if not p.smaa and rw * rh >= 1000 and (mine(0) or mine(3)) else []
+        for planes, blocks in ((current, corner + ([(25, 9, 2, H_NAN if frame_number % 2 else H_INF)] if turns == 6 and (mine(2) or mine(4) or (p.smaa and mine(0))) else [])), (history, [(76, 3, 2, H_NAN)] if mine(5) else [])):
+            for x, y, size, bits in blocks:
+                for a, grid in planes:
+                    b = grid.block(x, y, size)
+                    a[b + (slice(0, 3),)] = bits
+                    if planes is current:      # (history: as the single texels above)
+                        grid.mark(b)
+    elif name == "reproject":
+        tx, ty = np.float32(1.0) / np.float32(tw if p.taa == hk.Taa.Jasmine else ow), np.float32(1.0) / np.float32(th if p.taa == hk.Taa.Jasmine else oh)
+        values = [(0.0, 0.0), (tx, ty), (tx / 2, ty / 2), (-tx, 0.0), (0.0, -ty / 2), (2 * tx, 2 * ty), (tx * 5 / 2, -ty * 5 / 2), (-tx / 2, ty), (3 * tx, -ty),
+                  (3.0, 0.0), (0.0, -3.0), (-3.0, 3.0), (1e9, 0.0), (0.0, -1e9), (3e38, 3e38), (-3e38, 0.0), (np.inf, 0.0), (0.0, -np.inf), (np.inf, np.inf),
+                  (np.nan, 0.0), (0.0, np.nan), (np.nan, np.nan), (-np.inf, np.nan)]
+        for k, v in enumerate(values):
+            if not mine(k) or (rw * rh < 1000 and not np.isfinite(v).all()):      # (under 1000 pixels one NaN velocity alone costs EASU over 2 %)
+                continue
+            x, y = 2 + 8 * (k % 15), 1 + 6 * (k // 15) + (k % 3)
+            b = still(x, y, 2 if turns == 6 or np.isfinite(v).all() else 1, miss=k % 2 == 0)      # (no number: through TAA and EASU one texel reaches two dozen outputs)
+            velocity[b + (slice(0, 2),)] = np.array(v, np.float32)
+            # (none of these is `placed`: a whole or half number of texels - +-3 is one at every width - puts the gathers on texel centres
+            # and the nearest taps on boundaries by construction, 1e9 leaves f32 no fraction, and what no number reaches is open)
+        # a previous_uv of exactly 0 and 1, and one ulp outside: the velocity is the uv of the block's own first pixel (minus 1), nudged
+        for k, (edge, nudge) in enumerate([(0.0, 0), (0.0, 1), (1.0, 0), (1.0, -1)]):
+            if not mine(k + 1):
+                continue
+            x, y = 4 + 30 * k, 14
+            b = still(x, y, 2, miss=False)
+            r, c = G.at(x, y)
+            if r < dh:
+                grid_w, grid_h = (tw, th) if p.taa == hk.Taa.Jasmine else (ow, oh)
+                px, py = int((c + 0.5) / dw * grid_w), int((r + 0.5) / dh * grid_h)
+                u, v = (np.float32(px) + np.float32(0.5)) / np.float32(grid_w), (np.float32(py) + np.float32(0.5)) / np.float32(grid_h)
+                vu, vv = np.float32(u - np.float32(edge)), np.float32(v - np.float32(edge))
+                if nudge:
+                    vu, vv = one_ulp(vu, nudge * np.inf), one_ulp(vv, nudge * np.inf)
+                velocity[b + (slice(0, 2),)] = np.array([vu, vv], np.float32)      # (on the boundary test's threshold by design: not `placed`)
+        for k, d in enumerate([0.00005, 0.0001]):
+            for j, towards in enumerate((None, 0.0, 1.0)):
+                if not mine(3 * k + j):
+                    continue
+                x, y = 70 + 8 * j, 8 + 4 * k
+                b = still(x, y, 2, miss=True)
+                dv = np.float32(d) if towards is None else one_ulp(d, towards)
+                velocity[b] = 0.0                     # (0 - dv is exact; within rounding of the threshold by design: not `placed`)
+                previous_velocity[b] = 0.0
+                previous_velocity[b + (0,)] = dv
+    elif name == "depth":
+        specials = [0.0, -1.0, np.nan, np.inf, 1e-40, -0.0]
+        for k, d in enumerate(specials):
+            for j, plane in enumerate((previous_position, previous_position, position)):
+                if not mine(k + 2 * j):
+                    continue
+                x, y = 3 + 9 * k, 1 + 5 * j
+                b = still(x, y, 4, miss=False) if j else G.at(x, y)
+                if j == 2 and d != 0.0:
+                    continue
+                plane[b + (3,)] = d
+                G.mark(b)
+        ratio = np.float32(0.95)
+        for k, r in enumerate([ratio, one_ulp(ratio, 0.0), one_ulp(ratio, 1.0)]):
+            if not mine(2 * k):
+                continue
+            b = still(60 + 8 * k, 2, 2, miss=False)
+            previous_position[b + (3,)] = 2.0
+            position[b + (3,)] = np.float32(2.0) * r
+            previous_velocity[b + (0,)] = steady[0] + np.float32(0.01)         # (a velocity miss, so that the depth test decides)
+            previous_position[b + (0,)] = position[b + (0,)] + np.float32(1.0)      # (on the threshold by design: not `placed`)
+        for k, dist in enumerate([np.float32(0.5), one_ulp(0.5, 0.0), one_ulp(0.5, 1.0)]):
+            if not mine(2 * k + 1):
+                continue
+            b = still(60 + 8 * k, 8, 2, miss=False)
+            position[b + (slice(0, 3),)] = 0.0
+            previous_position[b + (slice(0, 3),)] = np.array([dist, 0.0, 0.0], np.float32)
+            previous_position[b + (3,)] = position[b + (3,)] * np.float32(2.0)
+            previous_velocity[b + (0,)] = steady[0] + np.float32(0.01)      # (on the threshold by design: not `placed`)
+        for k, lone in enumerate((False, True)):        # 20 gathered previous depths <= 0 under a current depth of 0; then ONE positive texel
+            b = still(86 + 14 * k, 1, 12, miss=False)
+            position[b + (3,)] = 0.0
+            previous_position[b + (3,)] = np.where(rng.random(previous_position[b + (3,)].shape) < 0.5, 0.0, -1.0)
+            if lone and b[0].stop - b[0].start > 2:
+                previous_position[(b[0].start + b[0].stop) // 2, (b[1].start + b[1].stop) // 2, 3] = 1.5
+            G.mark(b)
+        # corner depths of nearest_velocity around a centre of 1.0: (x+ y+, x- y+, x+ y-, x- y-)
+        # (in this order: the two slots of SMAA Tu4x at ratio 2 with TAA - where TAA's input texel is the G-buffer's - get four, three and two ties)
+        patterns = [(3, 3, 3, 3), (3, 3, 3, 1), (1, 1, 1, 1), (0.5, 1, 0.5, 0.5), (np.nan, 3, 1, 1), (np.nan, np.nan, np.nan, np.nan), (3, 3, 1, 1), (3, 1, 1, 3), (3, np.nan, 3, 1)]
+        for k, corners in enumerate(patterns):
+            if not mine(k):
+                continue
+            r, c = G.at(4 + 9 * k, 13)
+            if 1 <= r < dh - 1 and 1 <= c < dw - 1:
+                position[r - 1:r + 2, c - 1:c + 2, 3] = 1.0
+                for (oy, ox), d in zip(((1, 1), (1, -1), (-1, 1), (-1, -1)), corners):
+                    position[r + oy, c + ox, 3] = d
+                nine = np.arange(9).reshape(3, 3)      # nine distinct velocities, so that the offset shows - each an odd fraction of a G-buffer texel, off every centre and boundary
+                velocity[r - 1:r + 2, c - 1:c + 2, 0], velocity[r - 1:r + 2, c - 1:c + 2, 1] = (0.1871 + 0.0731 * nine) / dw, (0.2137 + 0.0611 * nine) / dh
+                previous_velocity[r - 1:r + 2, c - 1:c + 2, :2] = velocity[r - 1:r + 2, c - 1:c + 2, :2]
+                G.mark((slice(r - 1, r + 2), slice(c - 1, c + 2)))
+    elif name == "instance":
+        for k, step in enumerate([np.float32(0.0), np.float32(1.0), one_ulp(2.0, 3.0) - np.float32(1.0)]):
+            for j, miss in enumerate((True, False)):
+                if not mine(2 * k + j):
+                    continue
+                x, y = 4 + 18 * k, 1 + 8 * j
+                b = still(x, y, 4, miss=False)
+                previous_velocity[b + (0,)] = steady[0] + np.float32(0.01)                              # a velocity miss: instance_miss / depth_miss decide
+                if miss:
+                    previous_position[b + (3,)] = position[b + (3,)] * np.float32(2.0)
+                ids = np.where((np.arange(b[1].start, b[1].stop) - b[1].start) % 4 < 2, np.float32(1.0), np.float32(1.0) + step)
+                instance[b + (0,)] = ids[None, :]
+                G.mark(b)
+    position, previous_position, velocity, previous_velocity, instance = (a[:dh, :dw] for a in (position, previous_position, velocity, previous_velocity, instance))
+    tone, prev_tone, prev_taa, upscaled = tone[:rh, :rw], prev_tone[:rh, :rw], prev_taa[:th, :tw], upscaled[:oh, :ow]
+    if name == "random":
+        area = dw * dh
+
+        def some(shape, count):
+            m = np.zeros(int(np.prod(shape)), bool)
+            m[rng.choice(m.size, size=min(count, m.size), replace=False)] = True
+            return m.reshape(shape)
+
+        # (COUNTS, and few: one special texel reaches a dozen outputs of every kernel and a comparison may leave out 2 %.  Every plane
+        # gets `count` specials, each of a kind drawn from the plane's list - over the settings, parities and shapes every kind turns up)
+        count = 0 if area < 600 else max(1, area // 4000)          # (an image 1 wide or 1 high: its 2 % are no texel at all)
+
+        def sprinkle(plane, kinds, index=None):
+            if not compact and area < 8000 and rng.random() > area / 8000:      # (a small image: not every plane gets one; the compact fixtures: every plane)
+                return
+            for _ in range(count):
+                where = some(plane.shape[:2], 1)
+                kind = kinds[int(rng.integers(len(kinds)))]
+                if index is None:
+                    plane[where, int(rng.integers(3))] = kind
+                else:
+                    plane[where, index] = kind
+
+        for a in (tone, prev_tone, prev_taa, upscaled):
+            sprinkle(a, (H_NAN, H_INF, H_NINF, H_MAX, 0, H_NZERO, 0xBC00, 0x4200))
+            a[..., 3][some(a[..., 3].shape, count)] = f16_bits(0.5)
+        for plane in (position, previous_position):
+            sprinkle(plane, (0.0, -1.0, np.nan, np.inf, 1e-40, 50.0), 3)
+            plane[some((dh, dw), 4 * count), 0] += np.float32(0.75)
+        for plane in (velocity, previous_velocity):
+            sprinkle(plane, (0.0, 1.0 / max(tw, 1), 0.5 / max(tw, 1), -3.0, 3.0, 1e9, 3e38, np.inf, -np.inf, np.nan, 0.00005, 0.0001), int(rng.integers(2)))
+        instance[some((dh, dw), 8 * count), 0] += np.float32(1.0)
+        instance[some((dh, dw), 8 * count), 0] += np.float32(2.5)
+    p.buffers = {F.BUF_TONE_MAPPED: tone, F.BUF_PREVIOUS_TONE_MAPPED: prev_tone, F.BUF_PREVIOUS_TAA_OUTPUT: prev_taa, F.BUF_UPSCALE_OUTPUT: upscaled,
+                 F.BUF_POSITION: position, F.BUF_PREVIOUS_POSITION: previous_position, F.BUF_VELOCITY_UV: velocity,
+                 F.BUF_PREVIOUS_VELOCITY_UV: previous_velocity, F.BUF_INSTANCE_MATERIAL: instance}
+    p.buffers = {buf: np.ascontiguousarray(a) for buf, a in p.buffers.items()}
+    p.placed = {"window": G.placed[:dh, :dw], "render": R.placed[:rh, :rw], "taa": T.placed[:th, :tw], "output": O.placed[:oh, :ow]}
+    return p
+
+
+def install_aa(engine, planes, resize=True):
+    """hk_resize (if the size changed), the view options (the sizes of the upscale planes follow the upscale kind), hk_frame_begin,
+    then every plane - the previous frame's after hk_frame_begin too, which is what decides which plane `PREVIOUS_*` names - and
+    zeros in the planes the tail writes."""
+    size = planes.window_size + (planes.ratio,)
+    if resize and getattr(engine, "_post_planes_size", None) != size:
+        engine.resize(*size)
+        engine._post_planes_size = size
+    engine.set_view_options(planes.taa, planes.upscale.kind, planes.upscale.sharpness_)
+    camera = hk.cornell_camera(*planes.window_size)
+    engine.frame_begin(planes.frame, camera.view_uniform(), camera.previous_view_uniform(None), hk.lights_uniform())
+    for buf, array in planes.buffers.items():
+        engine.write(buf, array)
+    for buf in (F.BUF_TAA_OUTPUT, F.BUF_UPSCALE_SHARPENED):
+        engine.write(buf, np.zeros_like(engine.read(buf)))

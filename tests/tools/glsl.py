@@ -73,7 +73,7 @@ class G:
         px, py = uv[0] * w - R.f32(0.5), uv[1] * h - R.f32(0.5)
         fx0, fy0 = np.floor(px), np.floor(py)
         fx, fy = R.f32(np.rint((px - fx0) * R.f32(256.0))) / R.f32(256.0), R.f32(np.rint((py - fy0) * R.f32(256.0))) / R.f32(256.0)
-        ix, iy = int(fx0), int(fy0)
+        ix, iy = T.clamped_index(fx0, -1, tex.w), T.clamped_index(fy0, -1, tex.h)      # clamped in float, then converted
         cl = lambda i, n: min(max(i, 0), n - 1)
         t00, t10 = tex.texel(cl(ix, tex.w), cl(iy, tex.h)), tex.texel(cl(ix + 1, tex.w), cl(iy, tex.h))
         t01, t11 = tex.texel(cl(ix, tex.w), cl(iy + 1, tex.h)), tex.texel(cl(ix + 1, tex.w), cl(iy + 1, tex.h))

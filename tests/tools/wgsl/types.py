@@ -238,6 +238,19 @@ def _wrap(i, n, address):
     return min(max(i, 0), n - 1)
 
 
+def clamped_index(v, lo, hi):
+    """A texel coordinate clamped IN FLOAT to [lo, hi] and converted afterwards ("Texture coordinates outside
+    the int range"): +huge / +Inf -> hi, -huge / -Inf -> lo, NaN -> lo; any coordinate an int holds gives what clamping the int gave."""
+    v = float(v)
+    return int(lo) if v != v else int(min(max(v, float(lo)), float(hi)))
+
+
+def _floor_index(v, n, address):
+    """floor(v) as the int the address mode wraps: clamp-to-edge clamps in float first, to [-1, n] (both texels of a footprint clamp
+    as they did)"""
+    return clamped_index(np.floor(v), -1, n) if address == "clamp" else int(np.floor(v))
+
+
 def texture_sample_level(tex, sampler, uv, level):
     w, h = f32(tex.w), f32(tex.h)
     if not sampler.linear:
@@ -245,13 +258,13 @@ def texture_sample_level(tex, sampler, uv, level):
             x = int(np.floor(R.w_fract(uv[0]) * w)) % tex.w
             y = int(np.floor(R.w_fract(uv[1]) * h)) % tex.h
         else:
-            x = _wrap(int(np.floor(uv[0] * w)), tex.w, sampler.address)
-            y = _wrap(int(np.floor(uv[1] * h)), tex.h, sampler.address_v)
+            x = _wrap(_floor_index(uv[0] * w, tex.w, sampler.address), tex.w, sampler.address)
+            y = _wrap(_floor_index(uv[1] * h, tex.h, sampler.address_v), tex.h, sampler.address_v)
         return tex.texel(x, y)
     px, py = uv[0] * w - f32(0.5), uv[1] * h - f32(0.5)
     fx0, fy0 = f32(np.floor(px)), f32(np.floor(py))
     fx, fy = px - fx0, py - fy0
-    ix, iy = int(fx0), int(fy0)
+    ix, iy = _floor_index(fx0, tex.w, sampler.address), _floor_index(fy0, tex.h, sampler.address_v)
     x0, x1 = _wrap(ix, tex.w, sampler.address), _wrap(ix + 1, tex.w, sampler.address)
     y0, y1 = _wrap(iy, tex.h, sampler.address_v), _wrap(iy + 1, tex.h, sampler.address_v)
     top = R.w_mix(tex.texel(x0, y0), tex.texel(x1, y0), fx)
@@ -262,7 +275,7 @@ def texture_sample_level(tex, sampler, uv, level):
 def texture_gather(component, tex, sampler, uv):
     w, h = f32(tex.w), f32(tex.h)
     px, py = uv[0] * w - f32(0.5), uv[1] * h - f32(0.5)
-    ix, iy = int(np.floor(px)), int(np.floor(py))
+    ix, iy = _floor_index(px, tex.w, "clamp"), _floor_index(py, tex.h, "clamp")
     x0, x1 = _wrap(ix, tex.w, "clamp"), _wrap(ix + 1, tex.w, "clamp")
     y0, y1 = _wrap(iy, tex.h, "clamp"), _wrap(iy + 1, tex.h, "clamp")
     c = int(component)

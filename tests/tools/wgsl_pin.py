@@ -130,6 +130,12 @@ def reference_available():
     return os.path.isdir(SHADERS)
 
 
+def canonical_nans(tex):
+    """the contract's rule for what the anti-aliasing / upscale tail stores ("NaNs the tail stores"): a NaN of any
+    sign and payload is stored as the quiet NaN - numpy on x86 has its own signs, as every target has"""
+    tex.data[np.isnan(tex.data)] = np.float32(np.nan)
+
+
 class Pinner:
     def __init__(self, plugin, scene, noise, log):
         self.p, self.e, self.scene, self.noise, self.log = plugin, plugin.engine, scene, noise, log
@@ -233,6 +239,7 @@ class Pinner:
         m.dispatch(entry, gx, gy)
         rec = {"frame": int(self.frame.number), "pass": F.PASS_NAMES[pass_id], "entry": entry, "defs": [], "seconds": round(time.time() - t0, 1)}
         self.real_pass_run(pass_id)
+        canonical_nans(out)
         self.compare(rec, {F.PASS_NAMES[pass_id] + "_output": (out, out_b, "rgba16f")})
 
     def fsr_pass(self, pass_id):
@@ -264,6 +271,7 @@ class Pinner:
         rec = {"frame": int(self.frame.number), "pass": F.PASS_NAMES[pass_id], "entry": "FSR_Pass.glsl main (%s)" % ("EASU" if easu else "RCAS"), "defs": [],
                "seconds": round(time.time() - t0, 1)}
         self.real_pass_run(pass_id)
+        canonical_nans(out)
         self.compare(rec, {F.PASS_NAMES[pass_id] + "_output": (out, out_b, "rgba16f")})
 
     def tone_mapping_pass(self, denoised):
@@ -439,6 +447,66 @@ def run_planes(name, render_size=(24, 16), ratio=1.0, frame_number=3, seed=7, lo
     return pin.results
 
 
+def run_aa_planes(name, setting, render_size=(24, 16), frame_number=3, seed=7, log=None):
+    """The anti-aliasing / upscale tail on the synthetic planes of tests/post_planes.py (`make_aa_planes`, compact): taa.wgsl and
+    smaa.wgsl through tests/tools/wgsl/, FSR_Pass.glsl through tests/tools/glsl.py, each dispatch on the state the oracle has before
+    it.  Returns the per-dispatch records; what the shaders wrote is in run_aa_planes.recorded."""
+    import post_planes as PP
+
+    p = oracle_plugin()
+    dll = p.engine.api.dll
+    dll.orc_debug_math.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]
+
+    def contract(op, x, y):
+        xi, yi, out = (C.c_float * 1)(float(x)), (C.c_float * 1)(float(y)), (C.c_float * 1)()
+        assert dll.orc_debug_math(None, op, xi, yi, out, 1) == 0
+        return f32(out[0])
+
+    R.bind_contract(contract)
+    scene = hk.load_cornell()
+    p.set_scene(scene)
+    planes = PP.make_aa_planes(name, seed, PP.aa_window_for(render_size, setting), setting, frame_number, compact=True)
+    pin = Pinner(p, scene, None, log or (lambda rec: None))
+    pin.settings, pin.patch = planes.settings, None
+    camera = hk.cornell_camera(*planes.window_size)
+    pin.begin(planes.frame, camera.view_uniform(), camera.previous_view_uniform(None), hk.lights_uniform())
+    PP.install_aa(p.engine, planes)
+    for pass_id in planes.passes:
+        p.engine.pass_run(pass_id)
+    # Texels that rest on the CONTRACT'S rule for a texture coordinate that is no number or lies outside the int range, which the
+    # runtime's samplers take from DESIGN.md section 2 and not from the shader text: the pixels that can fetch a non-finite or huge
+    # velocity (nearest_velocity looks one input texel to either side: one G-buffer texel under SMAA Tu4x, up to two under FSR1), and in
+    # every later plane the pixels within two texels of those (the widest footprint of the tail).  A replay compares outside the mask.
+    velocity = planes.buffers[F.BUF_VELOCITY_UV][..., :2]
+    with np.errstate(invalid="ignore"):
+        reach = _dilate(~(np.abs(velocity) < 2.0 ** 24).all(axis=2), 1 if planes.smaa else 2)
+    for key in list(pin.recorded):
+        w, h = p.engine.buffer_info(int(key.split("buf")[1]))[:2]
+        ys, xs = ((np.arange(h) + 0.5) / h * reach.shape[0]).astype(int), ((np.arange(w) + 0.5) / w * reach.shape[1]).astype(int)
+        pin.recorded["mask_" + key] = _dilate(reach[np.ix_(ys, xs)], 2 * (int(key[1:4]) - 1)).astype(np.uint8)
+    run_aa_planes.recorded = pin.recorded
+    return pin.results
+
+
+def _dilate(mask, n):
+    out = mask.copy()
+    for _ in range(n):
+        pad = np.pad(out, 1)
+        out = pad[:-2, 1:-1] | pad[2:, 1:-1] | pad[1:-1, :-2] | pad[1:-1, 2:] | pad[1:-1, 1:-1] | pad[:-2, :-2] | pad[2:, 2:] | pad[:-2, 2:] | pad[2:, :-2]
+    return out
+
+
+#: (set, setting, render size, frame number): every set and every kernel once, both upscale kinds, both parities
+#: (FSR1 on the sets whose colours are finite: FSR_Pass.glsl gathers through four BILINEAR samples at texel centres, and a weight of
+#: 0 against an Inf or NaN neighbour is NaN there, where the contract takes the texel)
+AA_PLANES_FIXTURES = [("reproject", "smaa2_taa", (24, 16), 3), ("hdr", "smaa1_taa", (24, 16), 2), ("depth", "fsr15_taa", (24, 16), 3), ("flat", "fsr20", (24, 16), 2),
+                      ("instance", "smaa2", (24, 16), 2), ("random", "smaa2_taa", (24, 16), 2), ("depth", "fsr10_taa", (24, 16), 2)]
+
+
+def aa_planes_fixture_path(name, setting, render_size, frame_number):
+    return os.path.join(ROOT, "tests", "golden", f"wgsl_aa_planes_{name}_{setting}_{render_size[0]}x{render_size[1]}_f{frame_number}.npz")
+
+
 PLANES_FIXTURES = [("nonfinite", (24, 16), 1.0, 3), ("thresholds", (24, 16), 1.5, 2), ("black", (24, 16), 1.0, 2), ("nonfinite", (17, 16), 1.5, 3)]
 
 
@@ -447,6 +515,16 @@ def planes_fixture_path(name, render_size, ratio, frame_number):
 
 
 def main():
+    if "--aa-planes" in sys.argv:       # [--write]: the fixtures tests/test_aa_planes*.py replay
+        for case in AA_PLANES_FIXTURES:
+            results = run_aa_planes(*case, log=lambda rec: print(json.dumps(rec), flush=True))
+            bad = [r for r in results if r["mismatch"]]
+            if "--write" in sys.argv:
+                assert not bad
+                np.savez_compressed(aa_planes_fixture_path(*case), **run_aa_planes.recorded)
+                print("wrote", aa_planes_fixture_path(*case), os.path.getsize(aa_planes_fixture_path(*case)), "bytes")
+            print(json.dumps({"aa_planes": case, "dispatches": len(results), "mismatching": len(bad)}))
+        return
     if "--planes" in sys.argv:          # [--write]: the fixtures tests/test_post_chain_planes*.py replay
         for case in PLANES_FIXTURES:
             results = run_planes(*case, log=lambda rec: print(json.dumps(rec), flush=True))

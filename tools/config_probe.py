@@ -22,7 +22,7 @@ def run(name, scene, cam, settings, lights, warm=8, steps=16, antialias=False):
         p.engine.wait()
         p.engine.reset_stats()
         if flags == 0:
-            p.engine.set_timing_mask(0xFFFF)
+            p.engine.set_timing_mask((1 << F.PASS_COUNT) - 1)   # (every pass: the two FSR ones are bits 16 and 17)
         t0 = time.perf_counter()
         for n in range(warm + 1, warm + steps + 1):
             p.render(cam, settings, lights=lights, frame_number=n, antialias=antialias)
@@ -49,11 +49,13 @@ if __name__ == "__main__":
         scene, sun = synthetic_large(0x5EED0004, 60, 80, 160, 2000, 50, 1, 40.0)
         run("4: city-class 3840x2160, 2 bounces, ONE GPU", scene, synthetic_camera(3840, 2160, extent=30.0), hk.HikariSettings(indirect_bounces=2, upscale=U),
             hk.lights_uniform(directional=dict(sun, illuminance=10000.0)))
-    if "aa" in which:   # the reference's full post-process tail on BASELINE config 2: SMAA Tu4x to 3840x2160 + TAA there
+    if "aa" in which:   # the reference's full post-process tail on BASELINE config 2: SMAA Tu4x to 3840x2160 + TAA there; FSR1
         run("2+aa: cornell 1920x1080 traced, 2 bounces, SMAA Tu4x -> 3840x2160 + TAA", hk.load_cornell(), hk.cornell_camera(1920, 1080),
             hk.HikariSettings(indirect_bounces=2, upscale=U), hk.lights_uniform(), warm=16, steps=32, antialias=True)
         run("default settings at a 1920x1080 window: 960x540 traced, SMAA Tu4x -> 1920x1080 + TAA", hk.load_cornell(), hk.cornell_camera(1920, 1080),
             hk.HikariSettings(indirect_bounces=2), hk.lights_uniform(), warm=16, steps=32, antialias=True)
+        run("FSR1 at a 1920x1080 window: 1280x720 traced, TAA there, EASU + RCAS -> 1920x1080", hk.load_cornell(), hk.cornell_camera(1920, 1080),
+            hk.HikariSettings(indirect_bounces=2, upscale=hk.Upscale.Fsr1(1.5, 0.2)), hk.lights_uniform(), warm=16, steps=32, antialias=True)
     if "helmet" in which:   # the reference's textured glTF asset: 94 722 triangles in 6 BLAS, 10 textures
         from bevy_hikari_amd.scenes import flight_helmet_scene
 
