@@ -63,6 +63,7 @@ FORMAT_RGBA16F, FORMAT_RGBA32F, FORMAT_RGBA8_UNORM_SRGB, FORMAT_BGRA8_UNORM_SRGB
 PRESENT_HDR, PRESENT_CLEAR = 1, 2
 RAYS_CLOSEST, RAYS_ANY, RAYS_ATTRIBUTES, RAYS_STACKLESS = 0, 1, 2, 4  # hk_cast_rays flags
 RAY_MISS, RAY_HIT, RAY_INVALID = 0, 1, 2                              # HkRayHit.status
+DEFORM_VERTICES, DEFORM_SKIN = 0, 1                                   # HkMeshDeform.kind
 NO_INSTANCE = 0xFFFFFFFF                                              # HkRay.exclude_instance "nothing"; HkRayHit.instance / primitive of a miss
 
 f32, u32, u64 = C.c_float, C.c_uint32, C.c_uint64
@@ -157,6 +158,10 @@ class HkRayHit(C.Structure):
                 ("normal", f32 * 3), ("status", u32)]
 
 
+class HkMeshDeform(C.Structure):
+    _fields_ = [("mesh", HkMeshIndex), ("kind", u32), ("count", u32), ("data", C.POINTER(f32)), ("normals", C.POINTER(f32))]
+
+
 class HkHaloOp(C.Structure):
     _fields_ = [("buffer", u32), ("peer", u32), ("row_begin", u32), ("row_end", u32), ("row_bytes", u64)]
 
@@ -181,7 +186,7 @@ class HkStats(C.Structure):
 assert C.sizeof(HkVertex) == 32 and C.sizeof(HkPrimitive) == 48 and C.sizeof(HkNode) == 32 and C.sizeof(HkInstance) == 176
 assert C.sizeof(HkMaterial) == 80 and C.sizeof(HkEmissive) == 64 and C.sizeof(HkFrame) == 256 and C.sizeof(HkView) == 416
 assert C.sizeof(HkPreviousView) == 128 and C.sizeof(HkAliasEntry) == 8
-assert C.sizeof(HkRay) == 32 and C.sizeof(HkRayHit) == 48
+assert C.sizeof(HkRay) == 32 and C.sizeof(HkRayHit) == 48 and C.sizeof(HkMeshDeform) == 40
 
 
 class HikariError(RuntimeError):
@@ -233,6 +238,7 @@ _DEBUG = {
     "debug_last_load_times": [_vp, P(C.c_double)],
     "debug_read_emitters": [_vp, P(f32), u32, P(u32), P(f32), u32, P(u32)],
     "debug_read_mesh_geometry": [_vp, P(HkMeshIndex), P(f32), P(f32), u32, P(f32), u32, P(f32), P(u32), P(u32)],
+    "debug_last_deform": [_vp, P(u32)],
     "debug_comm_loopback": [_vp, u32, u32, u32, u32, u32],
     "debug_read_wf_timeline": [_vp, P(C.c_uint64), u32],
     "debug_set_option": [_vp, u32, C.c_int64],
@@ -289,6 +295,7 @@ _PRODUCT_ONLY = {
     "update_mesh_vertices": [_vp, P(HkMeshIndex), u32, P(f32), P(f32)],
     "set_mesh_skin": [_vp, P(HkMeshIndex), u32, P(f32), P(f32), P(C.c_uint16), P(f32)],
     "skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],
+    "deform_meshes": [_vp, P(HkMeshDeform), u32],
     "rebuild_mesh_tree": [_vp, P(HkMeshIndex), u32],
     "present": [_vp, P(HkSettings), u32, P(HkPresentTarget), u32, u32],
     "cast_rays": [_vp, P(HkRay), u32, u32, P(HkRayHit)],
@@ -337,6 +344,7 @@ _PRODUCT_ONLY = {
     "multi_update_mesh_vertices": [_vp, P(HkMeshIndex), u32, P(f32), P(f32)],
     "multi_set_mesh_skin": [_vp, P(HkMeshIndex), u32, P(f32), P(f32), P(C.c_uint16), P(f32)],
     "multi_skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],
+    "multi_deform_meshes": [_vp, P(HkMeshDeform), u32],
     "multi_rebuild_mesh_tree": [_vp, P(HkMeshIndex), u32],
     "multi_set_band_bounds": [_vp, P(u32), u32],
     "multi_upload_textures": [_vp, P(HkImageDesc), u32],

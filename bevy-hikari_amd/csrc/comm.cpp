@@ -836,6 +836,7 @@ int hk_multi_set_mesh_skin(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vert
   HK_EACH(hk_set_mesh_skin(c, mesh, n_vertices, bind_positions, bind_normals, joint_indices, joint_weights));
 }
 int hk_multi_skin_mesh(hk_multi* m, const HkMeshIndex* mesh, const float* joint_matrices, uint32_t n_joints) { HK_EACH(hk_skin_mesh(c, mesh, joint_matrices, n_joints)); }
+int hk_multi_deform_meshes(hk_multi* m, const HkMeshDeform* items, uint32_t n) { HK_EACH(hk_deform_meshes(c, items, n)); }
 int hk_multi_rebuild_mesh_tree(hk_multi* m, const HkMeshIndex* mesh, uint32_t mode) { HK_EACH(hk_rebuild_mesh_tree(c, mesh, mode)); }
 // the same explicit split on every band's context (all of them must agree: the schedules are derived per context)
 int hk_multi_set_band_bounds(hk_multi* m, const uint32_t* bounds, uint32_t n_bounds) { HK_EACH(hk_set_band_bounds(c, bounds, n_bounds)); }

@@ -590,9 +590,11 @@ int ensure_wide(hk_ctx* c, bool with_spill) {
     HK_HIP(hipMalloc((void**)&c->wide_spill, lanes * wide_spill_entries() * sizeof(uint32_t)));
     c->wide_spill_lanes = lanes;
   }
+  uint32_t wide_launches = 0;
   if (c->wide_blas_dirty || c->wide_mesh_check) {
-    // one launch per mesh tree (links are local to a tree): all of them after a mesh-level build, and after a change of the instance
-    // SET the ones no instance used before (a mesh uploaded ahead of its first instance has no records until then)
+    // every mesh tree whose records are missing (links are local to a tree), in ONE launch however many they are: all of them after a
+    // mesh-level build, the ones deformed since the last frame, and after a change of the instance SET the ones no instance used
+    // before (a mesh uploaded ahead of its first instance has no records until then)
     if (c->wide_blas_dirty) c->wide_meshes.clear();
     std::vector<std::pair<uint32_t, uint32_t>> meshes;
     // (node_offset, node_count) -> the mesh's first primitive: a triangle leaf's id is local to its mesh.  Two instances that name the
@@ -609,15 +611,40 @@ int ensure_wide(hk_ctx* c, bool with_spill) {
     for (size_t k = 0; k + 1 < first_primitive.size(); ++k)
       HK_REQUIRE(first_primitive[k].first != first_primitive[k + 1].first, HK_E_INVALID, "two instances share the mesh nodes [%u, +%u) but not the mesh primitives (%u / %u)",
                  first_primitive[k].first.first, first_primitive[k].first.second, first_primitive[k].second, first_primitive[k + 1].second);
+    std::vector<hkd::WideTreeSegment> todo;
+    size_t n_blocks = 0;
     for (const auto& m : meshes) {
       if (std::binary_search(c->wide_meshes.begin(), c->wide_meshes.end(), m)) continue;
       HK_REQUIRE((size_t)m.first + m.second <= blas_slots, HK_E_INVALID, "an instance's mesh nodes lie outside the uploaded mesh nodes");
       const uint32_t prim0 = std::lower_bound(first_primitive.begin(), first_primitive.end(), std::make_pair(m, 0u))->second;
       // (a tree of L leaves has 3 L - 2 nodes: its leaf ids stay below (node_count + 2) / 3)
       HK_REQUIRE((size_t)prim0 + (m.second + 2u) / 3u <= n_prim, HK_E_INVALID, "an instance's mesh primitives lie outside the uploaded primitives");
-      launch_build_wide(c->stream, c->scene.nodes + 2u * ((size_t)c->scene.blas_base + m.first), m.second, c->wide_blas + 8u * (size_t)m.first, c->wide_blas_rank + prim0);
+      if (!m.second) continue;
+      todo.push_back(hkd::WideTreeSegment{m.first, m.second, m.first, prim0});
+      n_blocks += (m.second + 255u) / 256u;
+    }
+    const float4* blas_nodes = c->scene.nodes + 2u * (size_t)c->scene.blas_base;
+    if (todo.size() == 1) {
+      launch_build_wide(c->stream, blas_nodes + 2u * (size_t)todo[0].node_offset, todo[0].count, c->wide_blas + 8u * (size_t)todo[0].wide_offset,
+                        c->wide_blas_rank + todo[0].rank_offset);
+    } else if (!todo.empty()) {  // the tree table and one entry per workgroup, read from pinned staging (mesh_deform.hip stage)
+      const size_t table_bytes = (todo.size() * sizeof(hkd::WideTreeSegment) + 255) & ~(size_t)255;
+      uint8_t* st = nullptr;
+      int k = 0;
+      const int rc = hk::stage(c, table_bytes + n_blocks * sizeof(hkd::SegmentBlock), &st, &k);
+      if (rc) return rc;
+      memcpy(st, todo.data(), todo.size() * sizeof(hkd::WideTreeSegment));
+      hkd::SegmentBlock* blocks = (hkd::SegmentBlock*)(st + table_bytes);
+      size_t at = 0;
+      for (size_t t = 0; t < todo.size(); ++t)
+        for (uint32_t first = 0; first < todo[t].count; first += 256u) blocks[at++] = hkd::SegmentBlock{(uint32_t)t, first};
+      launch_build_wide_trees(c->stream, (const hkd::WideTreeSegment*)st, blocks, (uint32_t)n_blocks, blas_nodes, c->wide_blas, c->wide_blas_rank);
+      HK_HIP(hipGetLastError());
+      HK_HIP(hipEventRecord(c->df_stage[(size_t)k].done, c->stream));
+      c->df_stage[(size_t)k].pending = true;
     }
     HK_HIP(hipGetLastError());
+    wide_launches += todo.empty() ? 0u : 1u;
     std::vector<std::pair<uint32_t, uint32_t>> all;
     std::set_union(c->wide_meshes.begin(), c->wide_meshes.end(), meshes.begin(), meshes.end(), std::back_inserter(all));
     c->wide_meshes.swap(all);
@@ -627,7 +654,9 @@ int ensure_wide(hk_ctx* c, bool with_spill) {
     launch_build_wide(c->stream, c->scene.nodes, (uint32_t)tlas_slots, c->wide_tlas, c->wide_tlas_rank);
     HK_HIP(hipGetLastError());
     c->wide_tlas_dirty = false;
+    wide_launches += tlas_slots ? 1u : 0u;
   }
+  if (wide_launches) c->last_deform[5] = wide_launches;  // (hk_debug_last_deform: the last derivation that launched anything)
   return HK_OK;
 }
 // the records for a fused kernel's walks (the primary rays): scenes in global memory with threaded trees, i.e. the product default

@@ -278,6 +278,10 @@ struct hk_ctx {
   std::vector<struct DeformMesh*> deform;
   struct DeformStage { uint8_t* p = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool pending = false; };
   std::vector<DeformStage> df_stage;
+  hkd::RefitUpdate* df_records = nullptr; // device: the emitter records of one propagation, one per emitting instance of a deformed mesh
+  size_t df_records_cap = 0;
+  uint64_t df_batch = 0;                  // counts hk_deform_meshes calls (a mesh named twice in one batch carries the call's number already)
+  uint32_t last_deform[6] = {0, 0, 0, 0, 0, 0};  // hk_debug_last_deform
   bool deform_pending = false;            // deformed meshes whose new boxes have not reached the instance level yet (flush_deform)
   bool meshes_deformed = false;           // a mesh was deformed on the device since the last hk_upload_meshes: its host copies are stale
   uint64_t instances_generation = 0;      // counts hk_upload_instances (the instance lists of the deformable meshes follow it)

@@ -140,6 +140,40 @@ struct MeshTree {
   float4 *node_lo, *node_hi;                       // per tree node (2n - 1)
   float4 *tri_lo, *tri_hi;                         // per triangle: its box
 };
+// One item of a batched deformation (hk_deform_meshes; kernels_deform.hip k_deform_*, kernels_tree.hip k_deform_boxes / k_deform_emit):
+// everything the kernels need of the item's mesh.  The table lies in the pinned staging block of the call, with the host data of the
+// items behind it, and is read from there (as RefitUpdate records are).
+struct DeformItem {
+  uint32_t kind;                     // HK_DEFORM_VERTICES / HK_DEFORM_SKIN
+  uint32_t n_vertices, n_tris, n_joints;
+  const float *positions, *normals;  // VERTICES: staged, 3 floats per vertex (normals: or NULL = keep)
+  const float4* palette;             // SKIN: the staged joint matrices, copied to joint_mats by k_deform_begin
+  float4* joint_mats;
+  const float4 *bind_pos, *bind_nrm, *weights;
+  const uint2* joints;
+  float4 *pos, *vn;                  // the mesh's position scratch plane; its normals in the normal plane
+  uint32_t* box;                     // the mesh box, 6 order-preserving words
+  float4 *v0, *v1, *v2;              // the mesh's first triangle in the triangle planes
+  MeshTree tree;
+  float4* nodes;                     // the mesh's first node (lo) in ordering 0 of the mesh-level node array
+};
+// A workgroup of a segmented launch: 256 consecutive elements of ONE segment (item, tree), from `first` on.  The host writes one entry
+// per workgroup, so no workgroup - and no wave - spans two segments, whatever their sizes and however many there are.
+struct SegmentBlock {
+  uint32_t segment, first;
+};
+// One instance of a deformed mesh (kernels_scene.hip k_mesh_instances): the mesh's box words, and the emitter record to write if it emits
+struct MeshInstanceEntry {
+  uint32_t instance;
+  uint32_t record;                   // index into the launch's RefitUpdate records, HK_U32_MAX: no emitter
+  const uint32_t* box;
+};
+// One tree of a segmented derivation of wide records (kernels_wavefront.hip k_build_wide_trees): offsets into the launch's arrays
+struct WideTreeSegment {
+  uint32_t node_offset, count;       // its slots in the node array (ordering 0)
+  uint32_t wide_offset;              // its first record (in records of 8 float4)
+  uint32_t rank_offset;              // where its leaf ids start in the rank array
+};
 // One mesh of a forest build (kernels_tree.hip launch_forest_build; hk_load_scene): the trees of many meshes built together
 struct ForestMesh {
   uint32_t tri_begin, n_tris;   // the mesh's positions in the batch: the meshes of a batch tile [0, all its triangles)
@@ -342,6 +376,9 @@ void launch_indirect(hipStream_t st, bool multiple_bounces, const hkd::DScene& s
 // the same dispatch as launch_indirect(multiple_bounces = true), scheduled through ray queues (kernels_wavefront.hip)
 // wide: records of the trees for the trace stages (nullptr members = the threaded walk)
 void launch_build_wide(hipStream_t st, const float4* nodes, uint32_t count, float4* wide, uint32_t* rank);  // one flatten_custom tree (ordering 0) -> its records; rank[leaf id] = the leaf's position
+// ... of many trees in ONE launch: tree k = trees[k] (pinned), its slots from nodes + 2 node_offset, records from wide + 8 wide_offset, ranks from rank + rank_offset
+void launch_build_wide_trees(hipStream_t st, const hkd::WideTreeSegment* trees, const hkd::SegmentBlock* blocks, uint32_t n_blocks, const float4* nodes, float4* wide,
+                             uint32_t* rank);
 // what WideTrees::spill must hold: wide_trace_lanes(compute_units) x wide_spill_entries() u32 (the lanes of the persistent trace launch
 // x the stack entries a lane keeps beyond LDS) - asked of the file that launches the kernel, so that the two cannot disagree
 size_t wide_trace_lanes(int compute_units);
@@ -409,13 +446,21 @@ int launch_forest_build(hipStream_t st, int mode /* 0 LBVH, 1 the reference's bi
                         const float4* v0, const float4* v1, const float4* v2, void* scratch, float4* nodes, uint32_t orderings, size_t ord_stride, uint32_t* launches);
 constexpr uint32_t HK_FOREST_MESH_MAX_TRIANGLES = 32767u;  // (SAH_WIDE_MIN - 1: from there a mesh has the whole chip to itself)
 // mesh deformation: the BLAS refit of one mesh tree into `orderings` orderings of its flat layout (`lo` = its node 0 of ordering 0,
-// interleaved lo / hi pairs, `ord_stride` float4 between orderings); the propagation of a new mesh box (`box`: 6 order-preserving
-// words, kernels_deform.hip) to the instances `ids` (emitters first) of the mesh, their emitters (`records`: device scratch, one per
-// instance) and both trees
+// interleaved lo / hi pairs, `ord_stride` float4 between orderings); the propagation of the new mesh boxes (6 order-preserving words
+// each, kernels_deform.hip) to the instances of ALL the deformed meshes in one launch (`entries`: pinned, one per instance), their
+// emitters (`records`: device scratch, one per emitting instance; the largest such mesh has emitter_triangles triangles) and both
+// trees.  Returns the kernels it launched.
 void launch_mesh_tree_refit(hipStream_t st, const hkd::MeshTree& t, float4* lo, size_t ord_stride, uint32_t orderings);
-void launch_mesh_propagate(hipStream_t st, const hkd::RefitScene& s, const uint32_t* box, const uint32_t* ids, uint32_t n_ids, hkd::RefitUpdate* records,
-                           uint32_t n_emitters, uint32_t emitter_triangles, float4* tlas, uint32_t tlas_count, uint32_t orderings, float4* light_lo, float4* light_hi,
-                           uint32_t light_count);
+uint32_t launch_mesh_propagate(hipStream_t st, const hkd::RefitScene& s, const hkd::MeshInstanceEntry* entries, uint32_t n_entries, hkd::RefitUpdate* records,
+                               uint32_t n_emitters, uint32_t emitter_triangles, float4* tlas, uint32_t tlas_count, uint32_t orderings, float4* light_lo, float4* light_hi,
+                               uint32_t light_count);
+// hk_deform_meshes: `items` and the three workgroup tables (vertices, triangles = leaves, tree nodes x orderings) lie in pinned memory.
+// Five launches whatever n_items is: begin (box words, joint palettes), vertices, triangles (+ arrival counters), boxes bottom-up, emit.
+void launch_deform_batch(hipStream_t st, const hkd::DeformItem* items, uint32_t n_items, const hkd::SegmentBlock* vertex_blocks, uint32_t n_vertex_blocks,
+                         const hkd::SegmentBlock* triangle_blocks, uint32_t n_triangle_blocks, const hkd::SegmentBlock* node_blocks, uint32_t n_node_blocks,
+                         size_t ord_stride, uint32_t orderings);
+void launch_deform_tree_refit(hipStream_t st, const hkd::DeformItem* items, const hkd::SegmentBlock* triangle_blocks, uint32_t n_triangle_blocks,
+                              const hkd::SegmentBlock* node_blocks, uint32_t n_node_blocks, size_t ord_stride, uint32_t orderings);  // (the last two of them: kernels_tree.hip)
 void launch_mesh_stage(hipStream_t st, const float* positions, const float* normals, uint32_t n, float4* pos, float4* vn, uint32_t* box);
 void launch_mesh_skin(hipStream_t st, const float4* bind_pos, const float4* bind_nrm, const uint2* joints, const float4* weights, const float4* joint_mats, uint32_t n,
                       float4* pos, float4* vn, uint32_t* box);

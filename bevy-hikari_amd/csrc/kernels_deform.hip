@@ -1,4 +1,5 @@
-// kernels_deform.hip - new vertex data of one mesh on the device (hk_update_mesh_vertices, hk_skin_mesh; host side mesh_deform.hip):
+// kernels_deform.hip - new vertex data of one mesh, or of many in one call, on the device (hk_update_mesh_vertices, hk_skin_mesh,
+// hk_deform_meshes; host side mesh_deform.hip):
 // the vertices of the mesh land in its normal plane and in a position scratch plane, the mesh box is reduced on the way, then every
 // triangle of the mesh takes its three positions into the triangle planes and its box into the refit's leaf boxes (kernels_tree.hip
 // launch_mesh_tree_refit carries on from there).  Streaming kernels, one thread per vertex / per triangle.
@@ -30,90 +31,75 @@ __device__ __forceinline__ void reduce_box(uint32_t* box, bool valid, float x, f
       atomicMax(&box[3 + k], mx[k]);
     }
 }
-}  // namespace
 
-// hk_update_mesh_vertices: positions / normals (3 floats per vertex, pinned host memory, read once)
-__global__ __launch_bounds__(256) void k_mesh_stage(const float* __restrict__ positions, const float* __restrict__ normals, uint32_t n, float4* __restrict__ pos,
-                                                    float4* __restrict__ vn, uint32_t* __restrict__ box) {
-  const uint32_t v = blockIdx.x * 256u + threadIdx.x;
-  const bool valid = v < n;
-  float x = 0.0f, y = 0.0f, z = 0.0f;
-  if (valid) {
-    x = positions[3u * v];
-    y = positions[3u * v + 1u];
-    z = positions[3u * v + 2u];
-    pos[v] = make_float4(x, y, z, 0.0f);
-    if (normals) vn[v] = make_float4(normals[3u * v], normals[3u * v + 1u], normals[3u * v + 2u], 0.0f);
-  }
-  reduce_box(box, valid, x, y, z);
+// one vertex of hk_update_mesh_vertices: positions / normals (3 floats per vertex, pinned host memory, read once)
+__device__ __forceinline__ void stage_vertex(const float* __restrict__ positions, const float* __restrict__ normals, uint32_t v, float4* __restrict__ pos,
+                                             float4* __restrict__ vn, float& x, float& y, float& z) {
+  x = positions[3u * v];
+  y = positions[3u * v + 1u];
+  z = positions[3u * v + 2u];
+  pos[v] = make_float4(x, y, z, 0.0f);
+  if (normals) vn[v] = make_float4(normals[3u * v], normals[3u * v + 1u], normals[3u * v + 2u], 0.0f);
 }
 
-// Linear-blend skinning, Bevy 0.9 skinning.wgsl (hikari_hip.h hk_skin_mesh; DESIGN "Mesh deformation"): fixed order, no contraction.
+// Linear-blend skinning of one vertex, Bevy 0.9 skinning.wgsl (hikari_hip.h hk_skin_mesh; DESIGN "Mesh deformation"): fixed order, no contraction.
 //   M  = ((w.x J[i.x] + w.y J[i.y]) + w.z J[i.z]) + w.w J[i.w]               element by element
 //   p' = ((M0 x + M1 y) + M2 z) + M3                                           (M0..M3: columns)
 //   n' = ((c0 n.x + c1 n.y) + c2 n.z),  (c0, c1, c2) = (M1 x M2, M2 x M0, M0 x M1) / dot(M2, M0 x M1)   (inverse_transpose_3x3)
 // n' is stored as it comes out (hit_info normalises, as for any uploaded normal).
-__global__ __launch_bounds__(256) void k_mesh_skin(const float4* __restrict__ bind_pos, const float4* __restrict__ bind_nrm, const uint2* __restrict__ joints,
-                                                   const float4* __restrict__ weights, const float4* __restrict__ joint_mats, uint32_t n, float4* __restrict__ pos,
-                                                   float4* __restrict__ vn, uint32_t* __restrict__ box) {
-  const uint32_t v = blockIdx.x * 256u + threadIdx.x;
-  const bool valid = v < n;
-  float px = 0.0f, py = 0.0f, pz = 0.0f;
-  if (valid) {
-    const uint2 jw = joints[v];
-    const uint32_t j[4] = {jw.x & 0xFFFFu, jw.x >> 16, jw.y & 0xFFFFu, jw.y >> 16};
-    const float4 w4 = weights[v];
-    const float w[4] = {w4.x, w4.y, w4.z, w4.w};
-    float m[4][4];  // m[column][row]
-    for (int c = 0; c < 4; ++c) {
-      const float4 a = joint_mats[4u * j[0] + c];
-      m[c][0] = w[0] * a.x;
-      m[c][1] = w[0] * a.y;
-      m[c][2] = w[0] * a.z;
-      m[c][3] = w[0] * a.w;
-    }
-    for (int t = 1; t < 4; ++t)
-      for (int c = 0; c < 4; ++c) {
-        const float4 a = joint_mats[4u * j[t] + c];
-        m[c][0] = m[c][0] + w[t] * a.x;
-        m[c][1] = m[c][1] + w[t] * a.y;
-        m[c][2] = m[c][2] + w[t] * a.z;
-        m[c][3] = m[c][3] + w[t] * a.w;
-      }
-    const float4 p = bind_pos[v];
-    px = ((m[0][0] * p.x + m[1][0] * p.y) + m[2][0] * p.z) + m[3][0];
-    py = ((m[0][1] * p.x + m[1][1] * p.y) + m[2][1] * p.z) + m[3][1];
-    pz = ((m[0][2] * p.x + m[1][2] * p.y) + m[2][2] * p.z) + m[3][2];
-    pos[v] = make_float4(px, py, pz, 0.0f);
-    auto cross = [](const float* a, const float* b, float* o) {
-      o[0] = a[1] * b[2] - a[2] * b[1];
-      o[1] = a[2] * b[0] - a[0] * b[2];
-      o[2] = a[0] * b[1] - a[1] * b[0];
-    };
-    const float* c0 = m[0];
-    const float* c1 = m[1];
-    const float* c2 = m[2];
-    float x[3], y[3], z[3];
-    cross(c1, c2, x);
-    cross(c2, c0, y);
-    cross(c0, c1, z);
-    const float det = (c2[0] * z[0] + c2[1] * z[1]) + c2[2] * z[2];
-    for (int k = 0; k < 3; ++k) {
-      x[k] = x[k] / det;
-      y[k] = y[k] / det;
-      z[k] = z[k] / det;
-    }
-    const float4 q = bind_nrm[v];
-    vn[v] = make_float4((x[0] * q.x + y[0] * q.y) + z[0] * q.z, (x[1] * q.x + y[1] * q.y) + z[1] * q.z, (x[2] * q.x + y[2] * q.y) + z[2] * q.z, 0.0f);
+__device__ __forceinline__ void skin_vertex(const float4* __restrict__ bind_pos, const float4* __restrict__ bind_nrm, const uint2* __restrict__ joints,
+                                            const float4* __restrict__ weights, const float4* __restrict__ joint_mats, uint32_t v, float4* __restrict__ pos,
+                                            float4* __restrict__ vn, float& px, float& py, float& pz) {
+  const uint2 jw = joints[v];
+  const uint32_t j[4] = {jw.x & 0xFFFFu, jw.x >> 16, jw.y & 0xFFFFu, jw.y >> 16};
+  const float4 w4 = weights[v];
+  const float w[4] = {w4.x, w4.y, w4.z, w4.w};
+  float m[4][4];  // m[column][row]
+  for (int c = 0; c < 4; ++c) {
+    const float4 a = joint_mats[4u * j[0] + c];
+    m[c][0] = w[0] * a.x;
+    m[c][1] = w[0] * a.y;
+    m[c][2] = w[0] * a.z;
+    m[c][3] = w[0] * a.w;
   }
-  reduce_box(box, valid, px, py, pz);
+  for (int t = 1; t < 4; ++t)
+    for (int c = 0; c < 4; ++c) {
+      const float4 a = joint_mats[4u * j[t] + c];
+      m[c][0] = m[c][0] + w[t] * a.x;
+      m[c][1] = m[c][1] + w[t] * a.y;
+      m[c][2] = m[c][2] + w[t] * a.z;
+      m[c][3] = m[c][3] + w[t] * a.w;
+    }
+  const float4 p = bind_pos[v];
+  px = ((m[0][0] * p.x + m[1][0] * p.y) + m[2][0] * p.z) + m[3][0];
+  py = ((m[0][1] * p.x + m[1][1] * p.y) + m[2][1] * p.z) + m[3][1];
+  pz = ((m[0][2] * p.x + m[1][2] * p.y) + m[2][2] * p.z) + m[3][2];
+  pos[v] = make_float4(px, py, pz, 0.0f);
+  auto cross = [](const float* a, const float* b, float* o) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+  };
+  const float* c0 = m[0];
+  const float* c1 = m[1];
+  const float* c2 = m[2];
+  float x[3], y[3], z[3];
+  cross(c1, c2, x);
+  cross(c2, c0, y);
+  cross(c0, c1, z);
+  const float det = (c2[0] * z[0] + c2[1] * z[1]) + c2[2] * z[2];
+  for (int k = 0; k < 3; ++k) {
+    x[k] = x[k] / det;
+    y[k] = y[k] / det;
+    z[k] = z[k] / det;
+  }
+  const float4 q = bind_nrm[v];
+  vn[v] = make_float4((x[0] * q.x + y[0] * q.y) + z[0] * q.z, (x[1] * q.x + y[1] * q.y) + z[1] * q.z, (x[2] * q.x + y[2] * q.y) + z[2] * q.z, 0.0f);
 }
 
-// every triangle of the mesh: its three positions (the w words - vertex indices - stay) and its box (light.wgsl:408-412, the leaf box)
-__global__ __launch_bounds__(256) void k_mesh_triangles(const float4* __restrict__ pos, float4* __restrict__ v0, float4* __restrict__ v1, float4* __restrict__ v2,
-                                                        uint32_t n_tris, float4* __restrict__ tri_lo, float4* __restrict__ tri_hi) {
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-  if (t >= n_tris) return;
+// triangle t of the mesh: its three positions (the w words - vertex indices - stay) and its box (light.wgsl:408-412, the leaf box)
+__device__ __forceinline__ void mesh_triangle(const float4* __restrict__ pos, float4* __restrict__ v0, float4* __restrict__ v1, float4* __restrict__ v2, uint32_t t,
+                                              float4* __restrict__ tri_lo, float4* __restrict__ tri_hi) {
   float4 q[3] = {v0[t], v1[t], v2[t]};
   for (int k = 0; k < 3; ++k) {
     const float4 p = pos[f2u(q[k].w)];
@@ -123,6 +109,75 @@ __global__ __launch_bounds__(256) void k_mesh_triangles(const float4* __restrict
   v1[t] = q[1];
   v2[t] = q[2];
   triangle_box(q[0], q[1], q[2], tri_lo[t], tri_hi[t]);
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_mesh_stage(const float* __restrict__ positions, const float* __restrict__ normals, uint32_t n, float4* __restrict__ pos,
+                                                    float4* __restrict__ vn, uint32_t* __restrict__ box) {
+  const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+  const bool valid = v < n;
+  float x = 0.0f, y = 0.0f, z = 0.0f;
+  if (valid) stage_vertex(positions, normals, v, pos, vn, x, y, z);
+  reduce_box(box, valid, x, y, z);
+}
+
+__global__ __launch_bounds__(256) void k_mesh_skin(const float4* __restrict__ bind_pos, const float4* __restrict__ bind_nrm, const uint2* __restrict__ joints,
+                                                   const float4* __restrict__ weights, const float4* __restrict__ joint_mats, uint32_t n, float4* __restrict__ pos,
+                                                   float4* __restrict__ vn, uint32_t* __restrict__ box) {
+  const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+  const bool valid = v < n;
+  float px = 0.0f, py = 0.0f, pz = 0.0f;
+  if (valid) skin_vertex(bind_pos, bind_nrm, joints, weights, joint_mats, v, pos, vn, px, py, pz);
+  reduce_box(box, valid, px, py, pz);
+}
+
+__global__ __launch_bounds__(256) void k_mesh_triangles(const float4* __restrict__ pos, float4* __restrict__ v0, float4* __restrict__ v1, float4* __restrict__ v2,
+                                                        uint32_t n_tris, float4* __restrict__ tri_lo, float4* __restrict__ tri_hi) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= n_tris) return;
+  mesh_triangle(pos, v0, v1, v2, t, tri_lo, tri_hi);
+}
+
+// ------------------------------------------------------------------ many meshes in one call (hk_deform_meshes)
+// The same three steps over ALL items of a batch: the launches do not depend on how many there are.  Every workgroup works on 256
+// consecutive vertices / triangles of ONE item (hk_kernels.hpp SegmentBlock, a table the host writes), so the wave-wide box reduction
+// never mixes two meshes and an item may have any size.  The item records and the tables are read from the call's pinned staging block.
+// One workgroup per item: its box words back to the empty box (min words all ones, max words zero), and - a skin item - its joint
+// matrices into device memory, where the vertex kernel reads each of them once per vertex.
+__global__ __launch_bounds__(256) void k_deform_begin(const DeformItem* __restrict__ items, uint32_t n_items) {
+  if (blockIdx.x >= n_items) return;
+  const DeformItem* it = items + blockIdx.x;
+  uint32_t* box = it->box;
+  if (threadIdx.x < 6u) box[threadIdx.x] = threadIdx.x < 3u ? 0xFFFFFFFFu : 0u;
+  if (it->kind != HK_DEFORM_SKIN) return;
+  const float4* __restrict__ src = it->palette;
+  float4* __restrict__ dst = it->joint_mats;
+  const uint32_t n = 4u * it->n_joints;
+  for (uint32_t i = threadIdx.x; i < n; i += 256u) dst[i] = src[i];
+}
+__global__ __launch_bounds__(256) void k_deform_vertices(const DeformItem* __restrict__ items, const SegmentBlock* __restrict__ blocks) {
+  const SegmentBlock bl = blocks[blockIdx.x];
+  const DeformItem* it = items + bl.segment;
+  const uint32_t v = bl.first + threadIdx.x;
+  const bool valid = v < it->n_vertices;
+  float4* pos = it->pos;
+  float4* vn = it->vn;
+  float x = 0.0f, y = 0.0f, z = 0.0f;
+  if (it->kind == HK_DEFORM_SKIN) {
+    if (valid) skin_vertex(it->bind_pos, it->bind_nrm, it->joints, it->weights, it->joint_mats, v, pos, vn, x, y, z);
+  } else {
+    if (valid) stage_vertex(it->positions, it->normals, v, pos, vn, x, y, z);
+  }
+  reduce_box(it->box, valid, x, y, z);
+}
+// ... and the arrival counters of the item's tree (one per internal node = per triangle but the last) back to zero for the climb
+__global__ __launch_bounds__(256) void k_deform_triangles(const DeformItem* __restrict__ items, const SegmentBlock* __restrict__ blocks) {
+  const SegmentBlock bl = blocks[blockIdx.x];
+  const DeformItem* it = items + bl.segment;
+  const uint32_t t = bl.first + threadIdx.x, n = it->n_tris;
+  if (t >= n) return;
+  if (t + 1u < n) it->tree.arrived[t] = 0u;
+  mesh_triangle(it->pos, it->v0, it->v1, it->v2, t, it->tree.tri_lo, it->tree.tri_hi);
 }
 
 // ... the boxes alone, of triangles nobody has moved yet (hk_rebuild_mesh_tree on a mesh never deformed)
@@ -150,6 +205,15 @@ void launch_mesh_triangles(hipStream_t st, const float4* pos, float4* v0, float4
 }
 void launch_mesh_triangle_boxes(hipStream_t st, const float4* v0, const float4* v1, const float4* v2, uint32_t n_tris, float4* tri_lo, float4* tri_hi) {
   if (n_tris) hipLaunchKernelGGL(k_mesh_triangle_boxes, dim3((n_tris + 255u) / 256u), dim3(256), 0, st, v0, v1, v2, n_tris, tri_lo, tri_hi);
+}
+void launch_deform_batch(hipStream_t st, const DeformItem* items, uint32_t n_items, const SegmentBlock* vertex_blocks, uint32_t n_vertex_blocks,
+                         const SegmentBlock* triangle_blocks, uint32_t n_triangle_blocks, const SegmentBlock* node_blocks, uint32_t n_node_blocks, size_t ord_stride,
+                         uint32_t orderings) {
+  if (!n_items) return;
+  hipLaunchKernelGGL(k_deform_begin, dim3(n_items), dim3(256), 0, st, items, n_items);
+  hipLaunchKernelGGL(k_deform_vertices, dim3(n_vertex_blocks), dim3(256), 0, st, items, vertex_blocks);
+  hipLaunchKernelGGL(k_deform_triangles, dim3(n_triangle_blocks), dim3(256), 0, st, items, triangle_blocks);
+  launch_deform_tree_refit(st, items, triangle_blocks, n_triangle_blocks, node_blocks, n_node_blocks, ord_stride, orderings);
 }
 
 }  // namespace hk

@@ -352,16 +352,18 @@ __global__ __launch_bounds__(256) void k_gather_instance_boxes(RefitScene s, con
   s.inst_hi[entry - HK_LEAF] = make_float4(hi.x, hi.y, hi.z, 0.0f);
 }
 
-// ------------------------------------------------------------------ a deformed mesh's new box, carried to its instances
-// One thread per instance of the mesh: the mesh box (hk_box.hpp box_word, reduced by kernels_deform.hip k_mesh_*) as bevy's Aabb, the world
-// AABB and emitter record with k_refit_instances' arithmetic (instance_world_box, emitter_position_radius: keep both in step) - but the pose, its previous model and its `moved` flag stay as they are
-// (a deformation is no motion: velocity_uv keeps the reference's formula).  Emitters (the first n_emitters ids) also get an update
-// record for k_refit_emitters: their triangle areas and alias table follow the new triangles.
-__global__ __launch_bounds__(64) void k_mesh_instances(RefitScene s, const uint32_t* __restrict__ box, const uint32_t* __restrict__ ids, uint32_t n_ids,
-                                                       RefitUpdate* __restrict__ records, uint32_t n_emitters) {
+// ------------------------------------------------------------------ the deformed meshes' new boxes, carried to their instances
+// One thread per instance of a deformed mesh, ALL such meshes in one launch (`entries`: pinned, hk_kernels.hpp MeshInstanceEntry - the
+// instance, its mesh's box words and the slot of its emitter record): the mesh box (hk_box.hpp box_word, reduced by kernels_deform.hip) as
+// bevy's Aabb, the world AABB and emitter record with k_refit_instances' arithmetic (instance_world_box, emitter_position_radius: keep both
+// in step) - but the pose, its previous model and its `moved` flag stay as they are (a deformation is no motion: velocity_uv keeps the
+// reference's formula).  Emitters also get an update record for k_refit_emitters: their triangle areas and alias table follow the new triangles.
+__global__ __launch_bounds__(64) void k_mesh_instances(RefitScene s, const MeshInstanceEntry* __restrict__ entries, uint32_t n_entries, RefitUpdate* __restrict__ records) {
   const uint32_t u = blockIdx.x * 64u + threadIdx.x;
-  if (u >= n_ids) return;
-  const uint32_t id = ids[u];
+  if (u >= n_entries) return;
+  const MeshInstanceEntry en = entries[u];
+  const uint32_t id = en.instance;
+  const uint32_t* __restrict__ box = en.box;
   const DInstance& d = s.instances[id];
   const float m[16] = {d.m0.x, d.m0.y, d.m0.z, d.m0.w, d.m1.x, d.m1.y, d.m1.z, d.m1.w, d.m2.x, d.m2.y, d.m2.z, d.m2.w, d.m3.x, d.m3.y, d.m3.z, d.m3.w};
   float ac[3], ah[3];
@@ -374,10 +376,7 @@ __global__ __launch_bounds__(64) void k_mesh_instances(RefitScene s, const uint3
   instance_world_box(m, ac, ah, mn, mx);
   s.inst_lo[id] = make_float4(mn[0], mn[1], mn[2], 0.0f);
   s.inst_hi[id] = make_float4(mx[0], mx[1], mx[2], 0.0f);
-  if (u >= n_emitters) return;
-  const uint32_t e = s.emissive_of_instance[id];
-  if (e == HK_U32_MAX) return;
-  s.emissives[e].position_radius = emitter_position_radius(s.materials[4u * d.material + 1u], mn, mx);
+  if (en.record == HK_U32_MAX) return;
   RefitUpdate r;
   r.instance = id;
   r.moved = 1u;
@@ -386,7 +385,10 @@ __global__ __launch_bounds__(64) void k_mesh_instances(RefitScene s, const uint3
     r.aabb_center[k] = ac[k];
     r.aabb_half[k] = ah[k];
   }
-  records[u] = r;
+  const uint32_t e = s.emissive_of_instance[id];
+  if (e == HK_U32_MAX) r.moved = 0u;  // (no emitter after all: k_refit_emitters passes the record by)
+  else s.emissives[e].position_radius = emitter_position_radius(s.materials[4u * d.material + 1u], mn, mx);
+  records[en.record] = r;
 }
 
 // ------------------------------------------------------------------ material and texture edits (hk_update_materials, hk_update_texture)
@@ -481,14 +483,20 @@ void launch_refit(hipStream_t st, const RefitScene& s, const RefitUpdate* update
   launch_refit_trees(st, s, tlas, tlas_count, orderings, light_lo, light_hi, light_count);
 }
 
-void launch_mesh_propagate(hipStream_t st, const RefitScene& s, const uint32_t* box, const uint32_t* ids, uint32_t n_ids, RefitUpdate* records, uint32_t n_emitters,
-                           uint32_t emitter_triangles, float4* tlas, uint32_t tlas_count, uint32_t orderings, float4* light_lo, float4* light_hi, uint32_t light_count) {
-  if (n_ids) hipLaunchKernelGGL(k_mesh_instances, dim3((n_ids + 63u) / 64u), dim3(64), 0, st, s, box, ids, n_ids, records, n_emitters);
-  if (n_emitters) {
+uint32_t launch_mesh_propagate(hipStream_t st, const RefitScene& s, const MeshInstanceEntry* entries, uint32_t n_entries, RefitUpdate* records, uint32_t n_emitters,
+                               uint32_t emitter_triangles, float4* tlas, uint32_t tlas_count, uint32_t orderings, float4* light_lo, float4* light_hi, uint32_t light_count) {
+  uint32_t launches = 0u;
+  if (n_entries) {
+    hipLaunchKernelGGL(k_mesh_instances, dim3((n_entries + 63u) / 64u), dim3(64), 0, st, s, entries, n_entries, records);
+    ++launches;
+  }
+  if (n_emitters) {  // one workgroup (= one wave) per emitter record, with the LDS the largest of their meshes needs
     const uint32_t lds_triangles = std::min(emitter_triangles, HK_EMITTER_LDS_TRIANGLES);
     hipLaunchKernelGGL(k_refit_emitters, dim3(n_emitters), dim3(64), lds_triangles * 5u * 4u, st, s, (const RefitUpdate*)records, n_emitters, lds_triangles);
+    ++launches;
   }
   launch_refit_trees(st, s, tlas, tlas_count, orderings, light_lo, light_hi, light_count);
+  return launches + (tlas_count ? 1u : 0u) + (light_count ? 1u : 0u);
 }
 
 }  // namespace hk

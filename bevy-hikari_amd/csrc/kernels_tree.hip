@@ -205,9 +205,7 @@ __global__ __launch_bounds__(256) void k_lbvh_hierarchy(LbvhBuffers b) {
 }
 // leaf boxes, then every internal node by the second of its children to arrive (min / max are exact: any order gives the same box)
 template <bool LIGHT>
-__global__ __launch_bounds__(256) void k_lbvh_boxes(RefitScene s, LbvhBuffers b) {
-  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-  if (j >= b.n) return;
+__device__ __forceinline__ void lbvh_leaf_climb(const RefitScene& s, const LbvhBuffers& b, uint32_t j) {
   f3 mn, mx;
   lbvh_shape_box<LIGHT>(s, b, b.ids_sorted[j], mn, mx);
   b.node_lo[b.n - 1u + j] = make_float4(mn.x, mn.y, mn.z, 0.0f);
@@ -246,9 +244,15 @@ __global__ __launch_bounds__(256) void k_lbvh_boxes(RefitScene s, LbvhBuffers b)
     if (p == HK_U32_MAX) return;
   }
 }
-// one thread per tree node and ordering (emit_tree_node)
-__global__ __launch_bounds__(256) void k_lbvh_emit(LbvhBuffers b, float4* lo, float4* hi, uint32_t stride, size_t ord_stride /* float4 between orderings */, uint32_t orderings) {
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x, n = b.n, total = 2u * n - 1u;
+template <bool LIGHT>
+__global__ __launch_bounds__(256) void k_lbvh_boxes(RefitScene s, LbvhBuffers b) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= b.n) return;
+  lbvh_leaf_climb<LIGHT>(s, b, j);
+}
+// thread t of (tree nodes x orderings) of a single tree: its node into its ordering (emit_tree_node)
+__device__ __forceinline__ void lbvh_emit_node(const LbvhBuffers& b, uint32_t t, float4* lo, float4* hi, uint32_t stride, size_t ord_stride, uint32_t orderings) {
+  const uint32_t n = b.n, total = 2u * n - 1u;
   if (t >= total * orderings) return;
   const uint32_t o = t / total, v = t - o * total;
   const bool leaf = v >= n - 1u;
@@ -256,6 +260,39 @@ __global__ __launch_bounds__(256) void k_lbvh_emit(LbvhBuffers b, float4* lo, fl
   if (n > 1u && v == 0u) return;  // the root has no navigator
   const uint32_t p = n == 1u ? HK_U32_MAX : leaf ? b.leaf_parent[v - (n - 1u)] : b.parent[v];  // (n == 1: the leaf alone)
   emit_tree_node<false>(b, v, p, o, shape, n, lo + (size_t)o * ord_stride, hi + (size_t)o * ord_stride, stride);
+}
+// one thread per tree node and ordering
+__global__ __launch_bounds__(256) void k_lbvh_emit(LbvhBuffers b, float4* lo, float4* hi, uint32_t stride, size_t ord_stride /* float4 between orderings */, uint32_t orderings) {
+  lbvh_emit_node(b, blockIdx.x * 256u + threadIdx.x, lo, hi, stride, ord_stride, orderings);
+}
+// the buffers of a REFIT of a mesh tree: its fixed topology, leaf boxes = the triangle boxes, ordering 0 kept left before right
+__host__ __device__ inline LbvhBuffers mesh_refit_buffers(const MeshTree& t) {
+  LbvhBuffers b{};
+  b.n = t.n;
+  b.box_lo = t.tri_lo; b.box_hi = t.tri_hi;
+  b.ids_sorted = t.leaf_shape;
+  b.parent = t.parent; b.left = t.left; b.right = t.right; b.first = t.first; b.last = t.last; b.leaf_parent = t.leaf_parent;
+  b.node_lo = t.node_lo; b.node_hi = t.node_hi; b.arrived = t.arrived; b.swap = t.swap;
+  b.keep_order0 = 1u;
+  return b;
+}
+// the refit of the trees of many meshes (hk_deform_meshes): k_lbvh_boxes and k_lbvh_emit, every workgroup on 256 leaves / (node, ordering)
+// pairs of ONE item's tree (hk_kernels.hpp SegmentBlock), each tree into its own node range of every ordering.  The arrival counters
+// were zeroed by kernels_deform.hip k_deform_triangles.
+__global__ __launch_bounds__(256) void k_deform_boxes(const DeformItem* __restrict__ items, const SegmentBlock* __restrict__ blocks) {
+  const SegmentBlock bl = blocks[blockIdx.x];
+  const LbvhBuffers b = mesh_refit_buffers(items[bl.segment].tree);
+  const uint32_t j = bl.first + threadIdx.x;
+  if (j >= b.n) return;
+  const RefitScene none{};
+  lbvh_leaf_climb<false>(none, b, j);
+}
+__global__ __launch_bounds__(256) void k_deform_emit(const DeformItem* __restrict__ items, const SegmentBlock* __restrict__ blocks, size_t ord_stride, uint32_t orderings) {
+  const SegmentBlock bl = blocks[blockIdx.x];
+  const DeformItem* it = items + bl.segment;
+  const LbvhBuffers b = mesh_refit_buffers(it->tree);
+  float4* lo = it->nodes;
+  lbvh_emit_node(b, bl.first + threadIdx.x, lo, lo + 1, 2u, ord_stride, orderings);
 }
 
 
@@ -952,18 +989,19 @@ using namespace hkd;
 // the triangle boxes, every internal node by the second child to arrive, child order per ordering by the rule of hk_bvh_rethread with
 // ordering 0 kept as it is), then every node written at its place in every ordering (k_lbvh_emit)
 void launch_mesh_tree_refit(hipStream_t st, const MeshTree& t, float4* lo, size_t ord_stride, uint32_t orderings) {
-  LbvhBuffers b{};
-  b.n = t.n;
-  b.box_lo = t.tri_lo; b.box_hi = t.tri_hi;
-  b.ids_sorted = t.leaf_shape;
-  b.parent = t.parent; b.left = t.left; b.right = t.right; b.first = t.first; b.last = t.last; b.leaf_parent = t.leaf_parent;
-  b.node_lo = t.node_lo; b.node_hi = t.node_hi; b.arrived = t.arrived; b.swap = t.swap;
-  b.keep_order0 = 1u;
+  const LbvhBuffers b = mesh_refit_buffers(t);
   if (t.n > 1u) (void)hipMemsetAsync(t.arrived, 0, (size_t)(t.n - 1u) * 4, st);
   const RefitScene none{};
   hipLaunchKernelGGL((k_lbvh_boxes<false>), dim3((t.n + 255u) / 256u), dim3(256), 0, st, none, b);
   const uint32_t threads = (2u * t.n - 1u) * orderings;
   hipLaunchKernelGGL(k_lbvh_emit, dim3((threads + 255u) / 256u), dim3(256), 0, st, b, lo, lo + 1, 2u, ord_stride, orderings);
+}
+// ... of every item of a batch, in two launches
+void launch_deform_tree_refit(hipStream_t st, const DeformItem* items, const SegmentBlock* triangle_blocks, uint32_t n_triangle_blocks, const SegmentBlock* node_blocks,
+                              uint32_t n_node_blocks, size_t ord_stride, uint32_t orderings) {
+  if (!n_triangle_blocks || !n_node_blocks) return;
+  hipLaunchKernelGGL(k_deform_boxes, dim3(n_triangle_blocks), dim3(256), 0, st, items, triangle_blocks);
+  hipLaunchKernelGGL(k_deform_emit, dim3(n_node_blocks), dim3(256), 0, st, items, node_blocks, ord_stride, orderings);
 }
 
 // ---- the scratch of a build: ONE description of its layout.  Sizing carves from a null base and returns the end; the builds carve

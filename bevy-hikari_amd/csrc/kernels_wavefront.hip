@@ -448,11 +448,8 @@ __global__ __launch_bounds__(256, HK_WF_TRACE_WAVES) void k_wf_trace(DScene gsc,
 // threaded orderings WAS; since round 5 hk_wide.hpp wide_triangle decides ties by the REFERENCE's rule - the leaf its walk meets first,
 // from the leaves' ranks in ordering 0 - so the closest hit is the reference's, whatever the order of the visits); an any-hit ray's
 // outcome - occluded or not - does not depend on the order at all.
-// one thread per slot of ONE tree (ordering 0; links local to the tree): the record of the inner node at that slot, and - in the
-// last slot - the root's
-__global__ __launch_bounds__(256) void k_build_wide(const float4* __restrict__ nodes, uint32_t count, float4* __restrict__ wide, uint32_t* __restrict__ rank) {
-  const uint32_t x = blockIdx.x * 256u + threadIdx.x;
-  if (x >= count) return;
+// slot x of ONE tree (ordering 0; links local to the tree): the record of the inner node at that slot, and - in the last slot - the root's
+__device__ __forceinline__ void build_wide_slot(const float4* __restrict__ nodes, uint32_t count, float4* __restrict__ wide, uint32_t* __restrict__ rank, uint32_t x) {
   auto entry_of = [&](uint32_t i) { return f2u(nodes[2u * i].w); };
   auto exit_of = [&](uint32_t i) { return f2u(nodes[2u * i + 1u].w); };
   // the rank of a leaf = its position in this (the reference's) flattening: the order in which the reference's walk meets the
@@ -510,6 +507,22 @@ __global__ __launch_bounds__(256) void k_build_wide(const float4* __restrict__ n
   float4* out = wide + 8u * (size_t)x;
 #pragma unroll
   for (int k = 0; k < 8; ++k) out[k] = rec[k];
+}
+// one thread per slot of the tree
+__global__ __launch_bounds__(256) void k_build_wide(const float4* __restrict__ nodes, uint32_t count, float4* __restrict__ wide, uint32_t* __restrict__ rank) {
+  const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+  if (x >= count) return;
+  build_wide_slot(nodes, count, wide, rank, x);
+}
+// ... of MANY trees: every workgroup on 256 slots of one of them (hk_kernels.hpp SegmentBlock; the tables lie in pinned memory).  Links
+// and ranks stay local to a tree: each is derived from its own slots, as if it were alone.
+__global__ __launch_bounds__(256) void k_build_wide_trees(const WideTreeSegment* __restrict__ trees, const SegmentBlock* __restrict__ blocks, const float4* __restrict__ nodes,
+                                                          float4* __restrict__ wide, uint32_t* __restrict__ rank) {
+  const SegmentBlock bl = blocks[blockIdx.x];
+  const WideTreeSegment t = trees[bl.segment];
+  const uint32_t x = bl.first + threadIdx.x;
+  if (x >= t.count) return;
+  build_wide_slot(nodes + 2u * (size_t)t.node_offset, t.count, wide + 8u * (size_t)t.wide_offset, rank + t.rank_offset, x);
 }
 
 #ifndef HK_WIDE_STEPS
@@ -1055,6 +1068,9 @@ size_t wide_trace_lanes(int compute_units) { return (size_t)compute_units * HK_W
 size_t wide_spill_entries() { return HK_WIDE_SPILL; }
 void launch_build_wide(hipStream_t st, const float4* nodes, uint32_t count, float4* wide, uint32_t* rank) {
   if (count) hipLaunchKernelGGL(k_build_wide, dim3((count + 255u) / 256u), dim3(256), 0, st, nodes, count, wide, rank);
+}
+void launch_build_wide_trees(hipStream_t st, const WideTreeSegment* trees, const SegmentBlock* blocks, uint32_t n_blocks, const float4* nodes, float4* wide, uint32_t* rank) {
+  if (n_blocks) hipLaunchKernelGGL(k_build_wide_trees, dim3(n_blocks), dim3(256), 0, st, trees, blocks, nodes, wide, rank);
 }
 
 void launch_indirect_wavefront(hipStream_t st, const DScene& sc, const DFrame& fr, const GBuffer& g, const LightTargets& t, const WfBuffers& w, int y0,

@@ -1,8 +1,10 @@
-// mesh_deform.hip - mesh deformation on the device (hikari_hip.h hk_update_mesh_vertices / hk_set_mesh_skin / hk_skin_mesh; kernels in
+// mesh_deform.hip - mesh deformation on the device (hikari_hip.h hk_update_mesh_vertices / hk_set_mesh_skin / hk_skin_mesh / hk_deform_meshes; kernels in
 // kernels_deform.hip, kernels_tree.hip and kernels_scene.hip; DESIGN "Mesh deformation").  The reference re-prepares a changed mesh on the CPU
 // (mesh.rs:76-166: a BVH build and a re-layout of the whole mesh level); here the new vertices are written into the mesh-level region,
 // the mesh tree is REFIT in every ordering that holds it (same links, every box the union of the triangle boxes below it), and the
 // new mesh box goes up to the instances, emitters and both instance-level trees - all stream-ordered behind the frames enqueued before.
+#include <string>
+
 #include "hk_context.hpp"
 
 using namespace hk;
@@ -16,10 +18,10 @@ struct DeformMesh {
   MeshTree tree{};
   float4* pos = nullptr;                                       // positions of the last update (per vertex; max_vertices)
   uint32_t* box = nullptr;                                     // the mesh box, 6 order-preserving words (kernels_deform.hip)
-  uint32_t* ids = nullptr;                                     // the instances of the mesh, emitters first
-  RefitUpdate* records = nullptr;                              // k_refit_emitters' records, one per instance
-  uint32_t n_ids = 0, n_emitters = 0;
+  std::vector<uint32_t> ids;                                   // the instances of the mesh, emitters first (host: propagate stages them)
+  uint32_t n_emitters = 0;
   uint64_t ids_generation = ~0ull;
+  uint64_t batch = 0;                                          // the last hk_deform_meshes call that named the mesh (hk_ctx::df_batch)
   bool deformed = false;                                       // `box` holds the current mesh box
   bool have_boxes = false;                                     // tree.tri_lo / tri_hi hold the current triangle boxes
   bool pending = false;                                        // ... and its instances have not been given it yet
@@ -43,6 +45,9 @@ void free_deform(hk_ctx* c) {
     if (s.done) (void)hipEventDestroy(s.done);
   }
   c->df_stage.clear();
+  if (c->df_records) (void)hipFree(c->df_records);
+  c->df_records = nullptr;
+  c->df_records_cap = 0;
   c->deform_pending = false;
 }
 }  // namespace hk
@@ -177,22 +182,7 @@ int mesh_instances(hk_ctx* c, DeformMesh* d) {
       if (memcmp(&c->instances[i].mesh, &d->mesh, sizeof(HkMeshIndex)) == 0 && is_emitter[i] == (pass == 0 ? 1 : 0)) ids.push_back(i);
   uint32_t n_emitters = 0;
   for (uint32_t i : ids) n_emitters += is_emitter[i];
-  if (ids.size() > d->n_ids || !d->ids) {  // (grows rarely: the old arrays may still be read by what is enqueued)
-    int rc = sync_all(c);
-    if (rc) return rc;
-    if (d->ids) (void)hipFree(d->ids);
-    d->ids = nullptr;
-    d->records = nullptr;
-    d->n_ids = 0;
-    const size_t cap = std::max<size_t>(ids.size(), 1);
-    HK_HIP(hipMalloc((void**)&d->ids, cap * (4 + sizeof(RefitUpdate)) + 256));
-    d->records = (RefitUpdate*)((uint8_t*)d->ids + ((cap * 4 + 255) & ~(size_t)255));
-  } else {
-    int rc = sync_all(c);
-    if (rc) return rc;
-  }
-  if (!ids.empty()) HK_HIP(hipMemcpy(d->ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
-  d->n_ids = (uint32_t)ids.size();
+  d->ids.swap(ids);
   d->n_emitters = n_emitters;
   d->ids_generation = c->instances_generation;
   return HK_OK;
@@ -256,6 +246,19 @@ int refit_mesh(hk_ctx* c, DeformMesh* d) {
   return HK_OK;
 }
 
+// what every deformation leaves behind on the host side, whatever it wrote: the mirrors are stale, the wide records of the mesh trees
+// `keys` (sorted (node_offset, node_count)) are derived again (context.hip ensure_wide), the instance tree's too
+void mark_deformed(hk_ctx* c, const std::vector<std::pair<uint32_t, uint32_t>>& keys) {
+  c->meshes_deformed = true;
+  c->mirrors_stale = true;
+  update_shared_transform(c);  // (the one-level tree is not walked from here on)
+  c->wide_meshes.erase(std::remove_if(c->wide_meshes.begin(), c->wide_meshes.end(),
+                                      [&](const std::pair<uint32_t, uint32_t>& m) { return std::binary_search(keys.begin(), keys.end(), m); }),
+                       c->wide_meshes.end());
+  c->wide_mesh_check = true;
+  c->wide_tlas_dirty = true;
+}
+
 // one deformation: `fill` enqueues the vertex kernel (positions into d->pos, normals into the normal plane, the mesh box into d->box)
 template <typename Fill>
 int deform(hk_ctx* c, DeformMesh* d, int k, Fill fill) {
@@ -274,32 +277,59 @@ int deform(hk_ctx* c, DeformMesh* d, int k, Fill fill) {
   hk_ctx::DeformStage& st = c->df_stage[(size_t)k];
   HK_HIP(hipEventRecord(st.done, c->stream));
   st.pending = true;
-  c->meshes_deformed = true;
-  c->mirrors_stale = true;
-  update_shared_transform(c);  // (the one-level tree is not walked from here on)
-  // the wide records of this mesh tree are derived again (context.hip ensure_wide), the instance tree's too
-  const std::pair<uint32_t, uint32_t> key(d->mesh.node_offset, d->mesh.node_count);
-  c->wide_meshes.erase(std::remove(c->wide_meshes.begin(), c->wide_meshes.end(), key), c->wide_meshes.end());
-  c->wide_mesh_check = true;
-  c->wide_tlas_dirty = true;
+  mark_deformed(c, {std::make_pair(d->mesh.node_offset, d->mesh.node_count)});
   return HK_OK;
 }
 
-// the new boxes of the meshes selected by `which` to their instances and emitters, then ONE refit of the instance tree and the light tree
+// the new boxes of the meshes selected by `which` to their instances and emitters - ONE launch each over the instances / the emitters of
+// all those meshes, however many - then ONE refit of the instance tree and the light tree
 template <typename Which>
 int propagate(hk_ctx* c, Which which) {
   const hkd::RefitScene r = refit_scene(c);
   uint8_t* base = c->scene_mem + (size_t)c->slot * c->dyn_capacity;
+  size_t n_entries = 0, n_emitters = 0;
+  uint32_t emitter_triangles = 0;
+  int rc;
   for (DeformMesh* d : c->deform) {
     if (!which(d)) continue;
-    int rc = mesh_instances(c, d);
-    if (rc) return rc;
-    launch_mesh_propagate(c->stream, r, d->box, d->ids, d->n_ids, d->records, d->n_emitters, d->n_tris, nullptr, 0u, 1u, nullptr, nullptr, 0u);
-    d->pending = false;
+    if ((rc = mesh_instances(c, d))) return rc;
+    n_entries += d->ids.size();
+    n_emitters += d->n_emitters;
+    if (d->n_emitters) emitter_triangles = std::max(emitter_triangles, d->n_tris);
   }
-  launch_mesh_propagate(c->stream, r, nullptr, nullptr, 0u, nullptr, 0u, 0u, (float4*)(base + c->dyn_off.tlas), (uint32_t)c->instance_nodes.size(), c->threaded ? 8u : 1u,
-                        (float4*)(base + c->dyn_off.light_lo), (float4*)(base + c->dyn_off.light_hi), (uint32_t)c->emissive_nodes.size());
+  MeshInstanceEntry* entries = nullptr;
+  int k = -1;
+  if (n_entries) {
+    if (n_emitters > c->df_records_cap) {  // (grows rarely: what is enqueued may still read the old array)
+      if ((rc = sync_all(c))) return rc;
+      if (c->df_records) (void)hipFree(c->df_records);
+      c->df_records = nullptr;
+      c->df_records_cap = 0;
+      const size_t cap = n_emitters + n_emitters / 4 + 16;
+      HK_HIP(hipMalloc((void**)&c->df_records, cap * sizeof(RefitUpdate)));
+      c->df_records_cap = cap;
+    }
+    uint8_t* st = nullptr;
+    if ((rc = stage(c, n_entries * sizeof(MeshInstanceEntry), &st, &k))) return rc;
+    entries = (MeshInstanceEntry*)st;
+    size_t at = 0;
+    uint32_t record = 0;
+    for (DeformMesh* d : c->deform) {
+      if (!which(d)) continue;
+      for (size_t i = 0; i < d->ids.size(); ++i) entries[at++] = MeshInstanceEntry{d->ids[i], i < d->n_emitters ? record++ : HK_U32_MAX, d->box};
+    }
+  }
+  for (DeformMesh* d : c->deform)
+    if (which(d)) d->pending = false;
+  c->last_deform[4] = launch_mesh_propagate(c->stream, r, entries, (uint32_t)n_entries, c->df_records, (uint32_t)n_emitters, emitter_triangles, (float4*)(base + c->dyn_off.tlas),
+                                            (uint32_t)c->instance_nodes.size(), c->threaded ? 8u : 1u, (float4*)(base + c->dyn_off.light_lo),
+                                            (float4*)(base + c->dyn_off.light_hi), (uint32_t)c->emissive_nodes.size());
   HK_HIP(hipGetLastError());
+  if (k >= 0) {
+    hk_ctx::DeformStage& st = c->df_stage[(size_t)k];
+    HK_HIP(hipEventRecord(st.done, c->stream));
+    st.pending = true;
+  }
   c->deform_pending = false;
   return HK_OK;
 }
@@ -407,6 +437,157 @@ int hk_skin_mesh(hk_ctx* c, const HkMeshIndex* mesh, const float* joint_matrices
   });
 }
 
+// Many meshes in one call (hikari_hip.h): what the single calls above do for each item, as five launches over all of them
+// (kernels_deform.hip launch_deform_batch).  Everything the device reads of the call - the item table, the workgroup tables of the
+// three launch shapes, every item's positions / normals / joint matrices - travels in ONE pinned staging block.
+int hk_deform_meshes(hk_ctx* c, const HkMeshDeform* items, uint32_t n) {
+  HK_REQUIRE(c, HK_E_INVALID, "NULL context");
+  if (n == 0) return HK_OK;
+  HK_REQUIRE(items, HK_E_INVALID, "NULL items");
+  HK_REQUIRE(c->have_meshes && c->have_materials && c->have_instances, HK_E_NOT_READY, "hk_upload_scene must come first");
+  HK_HIP(hipSetDevice(c->device));
+  int rc;
+  if ((rc = finalize_scene(c))) return rc;
+  // ---- the whole batch is validated before anything is enqueued or written
+  c->df_batch += 1;
+  std::vector<DeformMesh*> meshes(n, nullptr);
+  const uint32_t orderings = c->threaded ? 8u : 1u;
+  auto al16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  size_t data_bytes = 0, blocks[3] = {0, 0, 0};
+  uint32_t total_vertices = 0, total_tris = 0;
+  bool grow = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    const HkMeshDeform& it = items[i];
+    HK_REQUIRE(it.kind == HK_DEFORM_VERTICES || it.kind == HK_DEFORM_SKIN, HK_E_INVALID, "item %u: unknown kind %u", i, it.kind);
+    HK_REQUIRE(it.data && it.count, HK_E_INVALID, "item %u: NULL data or a count of zero", i);
+    HK_REQUIRE(it.kind != HK_DEFORM_SKIN || !it.normals, HK_E_INVALID, "item %u: a skin item takes no normals", i);
+    DeformMesh* d = nullptr;
+    if (it.kind == HK_DEFORM_SKIN) {
+      for (DeformMesh* q : c->deform)
+        if (memcmp(&q->mesh, &it.mesh, sizeof(HkMeshIndex)) == 0) d = q;
+      HK_REQUIRE(d && d->skin_vertices, HK_E_INVALID, "item %u: no skin set for this mesh (hk_set_mesh_skin)", i);
+      HK_REQUIRE(d->max_joint < it.count, HK_E_INVALID, "item %u: the skin names joint %u but only %u joint matrices were given", i, d->max_joint, it.count);
+    }
+    if ((rc = find_mesh(c, &it.mesh, &d)) || (rc = mesh_instances(c, d))) {
+      const std::string why = hk_last_error();
+      set_error("item %u: %s", i, why.c_str());
+      return rc;
+    }
+    HK_REQUIRE(it.kind != HK_DEFORM_VERTICES || (it.count >= d->min_vertices && it.count <= d->max_vertices), HK_E_INVALID,
+               "item %u: the mesh has between %u and %u vertices, not %u", i, d->min_vertices, d->max_vertices, it.count);
+    HK_REQUIRE(d->batch != c->df_batch, HK_E_INVALID, "item %u: the mesh record (%u, %u, %u, %u) is named twice in one batch", i, it.mesh.vertex, it.mesh.primitive,
+               it.mesh.node_offset, it.mesh.node_count);
+    d->batch = c->df_batch;
+    meshes[i] = d;
+    const uint32_t nv = it.kind == HK_DEFORM_SKIN ? d->skin_vertices : it.count;
+    total_vertices += nv;
+    total_tris += d->n_tris;
+    blocks[0] += (nv + 255u) / 256u;
+    blocks[1] += (d->n_tris + 255u) / 256u;
+    blocks[2] += ((size_t)(2u * d->n_tris - 1u) * orderings + 255u) / 256u;
+    if (it.kind == HK_DEFORM_SKIN) {
+      data_bytes += (size_t)it.count * 64;
+      grow = grow || it.count > d->joint_cap;
+    } else {
+      data_bytes += al16((size_t)it.count * 12) * (it.normals ? 2 : 1);
+    }
+  }
+  // ---- what has to grow (the first skinning of a mesh, a longer palette): one wait for all of it
+  if (grow) {
+    if ((rc = sync_all(c))) return rc;
+    for (uint32_t i = 0; i < n; ++i) {
+      DeformMesh* d = meshes[i];
+      if (items[i].kind != HK_DEFORM_SKIN || items[i].count <= d->joint_cap) continue;
+      if (d->joint_mats) (void)hipFree(d->joint_mats);
+      d->joint_mats = nullptr;
+      d->joint_cap = 0;
+      HK_HIP(hipMalloc((void**)&d->joint_mats, (size_t)items[i].count * 64));
+      d->joint_cap = items[i].count;
+    }
+  }
+  // ---- the staging block: item table | vertex, triangle and node workgroups | the items' data
+  const size_t table_bytes = (n * sizeof(DeformItem) + 255) & ~(size_t)255;
+  const size_t block_bytes = ((blocks[0] + blocks[1] + blocks[2]) * sizeof(SegmentBlock) + 255) & ~(size_t)255;
+  uint8_t* st = nullptr;
+  int k = 0;
+  if ((rc = stage(c, table_bytes + block_bytes + data_bytes, &st, &k))) return rc;
+  DeformItem* table = (DeformItem*)st;
+  SegmentBlock* bl[3] = {(SegmentBlock*)(st + table_bytes), (SegmentBlock*)(st + table_bytes) + blocks[0], (SegmentBlock*)(st + table_bytes) + blocks[0] + blocks[1]};
+  uint8_t* data = st + table_bytes + block_bytes;
+  const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
+  uint8_t* sbase = c->scene_mem + slots;
+  size_t at[3] = {0, 0, 0};
+  std::vector<std::pair<uint32_t, uint32_t>> keys(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const HkMeshDeform& it = items[i];
+    DeformMesh* d = meshes[i];
+    DeformItem t{};
+    t.kind = it.kind;
+    t.n_tris = d->n_tris;
+    if (it.kind == HK_DEFORM_SKIN) {
+      t.n_vertices = d->skin_vertices;
+      t.n_joints = it.count;
+      memcpy(data, it.data, (size_t)it.count * 64);
+      t.palette = (const float4*)data;
+      data += (size_t)it.count * 64;
+      t.joint_mats = d->joint_mats;
+      t.bind_pos = d->bind_pos; t.bind_nrm = d->bind_nrm; t.weights = d->weights; t.joints = d->joints;
+    } else {
+      const size_t plane = (size_t)it.count * 12;
+      t.n_vertices = it.count;
+      memcpy(data, it.data, plane);
+      t.positions = (const float*)data;
+      data += al16(plane);
+      if (it.normals) {
+        memcpy(data, it.normals, plane);
+        t.normals = (const float*)data;
+        data += al16(plane);
+      }
+    }
+    t.pos = d->pos;
+    t.vn = (float4*)(sbase + c->st_vn) + d->mesh.vertex;
+    t.box = d->box;
+    t.v0 = (float4*)(sbase + c->st_v0) + d->mesh.primitive;
+    t.v1 = (float4*)(sbase + c->st_v1) + d->mesh.primitive;
+    t.v2 = (float4*)(sbase + c->st_v2) + d->mesh.primitive;
+    t.tree = d->tree;
+    t.nodes = (float4*)(sbase + c->st_nodes) + 2 * (size_t)d->mesh.node_offset;
+    table[i] = t;
+    const size_t threads[3] = {t.n_vertices, t.n_tris, (size_t)(2u * t.n_tris - 1u) * orderings};
+    for (int s = 0; s < 3; ++s)
+      for (size_t first = 0; first < threads[s]; first += 256) bl[s][at[s]++] = SegmentBlock{i, (uint32_t)first};
+    keys[i] = std::make_pair(d->mesh.node_offset, d->mesh.node_count);
+  }
+  // ---- enqueue: behind every frame enqueued so far on every stream that reads the scene (stream waits), as a single deformation is
+  if ((rc = join_all(c))) return rc;
+  c->scene_epoch += n;  // (scene memory is written from here on: hk_context.hpp, primary-ray pipelining - a refusal above leaves it alone)
+  launch_deform_batch(c->stream, table, n, bl[0], (uint32_t)blocks[0], bl[1], (uint32_t)blocks[1], bl[2], (uint32_t)blocks[2], 2 * c->node_cap, orderings);
+  HK_HIP(hipGetLastError());
+  hk_ctx::DeformStage& stg = c->df_stage[(size_t)k];
+  HK_HIP(hipEventRecord(stg.done, c->stream));
+  stg.pending = true;
+  for (uint32_t i = 0; i < n; ++i) {
+    DeformMesh* d = meshes[i];
+    d->n_vertices = table[i].n_vertices;
+    d->deformed = d->pending = d->have_boxes = true;
+  }
+  c->deform_pending = true;
+  std::sort(keys.begin(), keys.end());
+  mark_deformed(c, keys);
+  c->last_deform[0] = n;
+  c->last_deform[1] = total_vertices;
+  c->last_deform[2] = total_tris;
+  c->last_deform[3] = 5u;  // begin, vertices, triangles, boxes, emit
+  return HK_OK;
+}
+
+// Test hook (hikari_hip_debug.h)
+int hk_debug_last_deform(hk_ctx* c, uint32_t out[6]) {
+  HK_REQUIRE(c && out, HK_E_INVALID, "NULL argument");
+  for (int k = 0; k < 6; ++k) out[k] = c->last_deform[k];
+  return HK_OK;
+}
+
 // A new tree over the current triangles of one mesh, in place (hikari_hip.h).  The build is the instance level's (kernels_tree.hip
 // launch_tree_build) fed from the mesh's triangle boxes; its topology replaces the one the refit climbs.  The mesh box and the triangle
 // order stay, so nothing at the instance level moves: no propagation, only the staleness a deformation brings.
@@ -455,13 +636,7 @@ int hk_rebuild_mesh_tree(hk_ctx* c, const HkMeshIndex* mesh, uint32_t mode) {
   build.one_workgroup_top = c->mesh_rebuild_one_workgroup;
   build.scratch = c->lbvh_scratch;
   HK_REQUIRE(launch_tree_build(c->stream, build) == 0, HK_E_HIP, "device build of the mesh tree failed: %s", hipGetErrorString(hipGetLastError()));
-  c->meshes_deformed = true;
-  c->mirrors_stale = true;
-  update_shared_transform(c);  // (the one-level tree is not walked from here on)
-  const std::pair<uint32_t, uint32_t> key(d->mesh.node_offset, d->mesh.node_count);
-  c->wide_meshes.erase(std::remove(c->wide_meshes.begin(), c->wide_meshes.end(), key), c->wide_meshes.end());
-  c->wide_mesh_check = true;
-  c->wide_tlas_dirty = true;
+  mark_deformed(c, {std::make_pair(d->mesh.node_offset, d->mesh.node_count)});
   return HK_OK;
 }
 

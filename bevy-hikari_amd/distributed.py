@@ -212,6 +212,10 @@ class BandRenderer:
         self.engine.set_band_bounds(self.bounds)
         self._plans = {}
 
+    def deform_meshes(self, items):
+        """This rank's replica of the scene takes the batch (Engine.deform_meshes): EVERY rank must call it with the same items."""
+        self.engine.deform_meshes(items)
+
     def _follow_resize(self):
         """Engine.resize frees every buffer, bumps engine.generation and - on the C side - drops an explicit band split (it was in
         rows of the old render image): views, plans AND the split of an older generation go (a stale split here would
@@ -523,6 +527,13 @@ class MultiEngine:
     def skin_mesh(self, mesh, joint_matrices):
         j = np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1, 16)
         self.api.call("multi_skin_mesh", self.h, C.byref(mesh), j.ctypes.data_as(C.POINTER(F.f32)), len(j))
+
+    def deform_meshes(self, items):
+        """hk_multi_deform_meshes: Engine.deform_meshes' batch on every band's copy of the scene."""
+        from .plugin import deform_items
+
+        table, keep = deform_items(items)
+        self.api.call("multi_deform_meshes", self.h, table, len(items))
 
     def rebuild_mesh_tree(self, mesh, mode=F.TREE_SAH):
         """hk_multi_rebuild_mesh_tree: the mesh's tree built again on every band's copy of the scene."""

@@ -531,6 +531,30 @@ def image_desc(im):
     return d
 
 
+def deform_items(items):
+    """The HkMeshDeform table of Engine.deform_meshes' `items`, and the arrays it points into (to be kept alive over the call)."""
+    table, keep = (F.HkMeshDeform * max(len(items), 1))(), []
+    fp = lambda a: a.ctypes.data_as(C.POINTER(F.f32))
+    for k, item in enumerate(items):
+        kind, mesh = item[0], item[1]
+        if kind == "skin":
+            if len(item) != 3:
+                raise ValueError('a skin item is ("skin", index, joints)')
+            j = np.ascontiguousarray(item[2], dtype=np.float32).reshape(-1, 16)
+            keep.append(j)
+            table[k] = F.HkMeshDeform(mesh, F.DEFORM_SKIN, len(j), fp(j), None)
+        elif kind == "vertices":
+            pos = np.ascontiguousarray(item[2], dtype=np.float32).reshape(-1, 3)
+            nrm = None if len(item) < 4 or item[3] is None else np.ascontiguousarray(item[3], dtype=np.float32).reshape(-1, 3)
+            if nrm is not None and nrm.shape != pos.shape:
+                raise ValueError("normals must match positions")
+            keep += [pos, nrm]
+            table[k] = F.HkMeshDeform(mesh, F.DEFORM_VERTICES, len(pos), fp(pos), None if nrm is None else fp(nrm))
+        else:
+            raise ValueError(f"unknown deformation kind {kind!r}")
+    return table, keep
+
+
 class Engine:
     """One context of the C ABI (`hk_ctx`).  `api` defaults to the product library."""
 
@@ -656,6 +680,20 @@ class Engine:
         """Per frame: column-major 4x4 joint matrices (n x 16 floats); the device skins and refits (hk_skin_mesh)."""
         j = np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1, 16)
         self.api.call("skin_mesh", self.ctx, C.byref(mesh), j.ctypes.data_as(C.POINTER(F.f32)), len(j))
+
+    def deform_meshes(self, items):
+        """Many meshes deformed in one call (hk_deform_meshes): `items` is a list of ("vertices", index, positions, normals_or_None) and
+        ("skin", index, joints) tuples - what update_mesh_vertices / skin_mesh take, mesh by mesh.  The device work is a fixed number of
+        launches however many items there are; the result is what the single calls in item order would have left."""
+        table, keep = deform_items(items)
+        self.api.call("deform_meshes", self.ctx, table, len(items))
+
+    def last_deform(self):
+        """(items, vertices, triangles, enqueues of the call, launches of the last flush, launches of the last wide-record derivation) -
+        hk_debug_last_deform (test hook)."""
+        out = (F.u32 * 6)()
+        self.api.call("debug_last_deform", self.ctx, out)
+        return tuple(int(v) for v in out)
 
     def rebuild_mesh_tree(self, mesh, mode=F.TREE_SAH):
         """A new tree over the current triangles of one uploaded mesh, built on the device in place (hk_rebuild_mesh_tree): F.TREE_SAH = the
@@ -1201,6 +1239,10 @@ class HikariPlugin:
     def add_meshes(self, builder, mode=F.TREE_SAH):
         """Meshes added to the loaded builder since (glTF assets that arrive frame by frame): appended on the device (Engine.add_meshes)."""
         self.engine.add_meshes(builder, mode)
+
+    def deform_meshes(self, items):
+        """Per frame, every deforming mesh of the scene in one call: Engine.deform_meshes."""
+        self.engine.deform_meshes(items)
 
     def update_instances(self, scene: SceneData):
         """Instances moved (prepare_instances, instance.rs:352-437): rewrite the instance-level buffers only."""

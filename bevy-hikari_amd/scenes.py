@@ -416,3 +416,126 @@ def large_cloth(triangles=1_000_000, size=2.0):
     """One cloth grid of about `triangles` triangles (tools/deform_probe.py: 10^4 - 10^6): positions, normals, uvs, indices."""
     side = max(2, int(round((triangles / 2) ** 0.5)))
     return cloth_grid(side, side, size=size)
+
+
+# ---------------------------------------------------------------------------------------------
+# a crowd of deforming meshes (hk_deform_meshes): many small meshes, each with its own motion
+# ---------------------------------------------------------------------------------------------
+def coil_ribbon(triangles, turns=1.5, radius=0.22, height=0.9, width=0.12):
+    """A ribbon of exactly `triangles` triangles (triangles + 2 vertices) wound round the y axis: positions, outward normals, uvs, indices."""
+    nv = triangles + 2
+    steps = max((nv - 1) // 2, 1)
+    p, n, uv = [], [], []
+    for i in range(nv):
+        t = (i // 2) / steps
+        a = 2.0 * math.pi * turns * t
+        p.append((radius * math.cos(a), height * t + width * (i % 2), radius * math.sin(a)))
+        n.append((math.cos(a), 0.0, math.sin(a)))
+        uv.append((t, float(i % 2)))
+    idx = []
+    for i in range(triangles):
+        idx += [i, i + 1, i + 2] if i % 2 == 0 else [i + 1, i, i + 2]
+    return np.array(p, np.float32), np.array(n, np.float32), np.array(uv, np.float32), np.array(idx, np.uint32)
+
+
+def ribbon_skin(positions, n_joints, height=0.9):
+    """Joint indices (uint16 x 4) and weights (x 4) of a coil_ribbon for a chain of `n_joints` joints along y: every vertex follows the
+    two joints nearest its height, with weights that need not sum to one exactly (the skinning contract uses them as given)."""
+    y = np.clip(positions[:, 1].astype(np.float64) / height, 0.0, 1.0) * (n_joints - 1)
+    lo = np.minimum(np.floor(y).astype(np.int64), max(n_joints - 2, 0))
+    hi = np.minimum(lo + 1, n_joints - 1)
+    f = y - lo
+    ji = np.zeros((len(positions), 4), np.uint16)
+    jw = np.zeros((len(positions), 4), np.float32)
+    ji[:, 0], ji[:, 1] = lo, hi
+    jw[:, 0], jw[:, 1] = 1.0 - f, f * (0.97 + 0.03 * (np.arange(len(positions)) % 3))
+    if n_joints == 1:
+        jw[:, 0], jw[:, 1] = 1.0, 0.0
+    return ji, jw
+
+
+def chain_joints(n_joints, frame, phase=0.0, height=0.9):
+    """`n_joints` column-major joint matrices at `frame`: joint k sways about z and x around its own height and stretches a little."""
+    out = []
+    for k in range(n_joints):
+        t = k / max(n_joints - 1, 1)
+        az = 0.30 * t * math.sin(0.5 * frame + phase + 0.7 * k)
+        ax = 0.20 * t * math.cos(0.4 * frame + 1.3 * phase)
+        cz, sz, cx, sx = math.cos(az), math.sin(az), math.cos(ax), math.sin(ax)
+        rz = np.array([[cz, -sz, 0, 0], [sz, cz, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]], np.float64)
+        rx = np.array([[1, 0, 0, 0], [0, cx, -sx, 0], [0, sx, cx, 0], [0, 0, 0, 1]], np.float64)
+        pivot, back = np.eye(4), np.eye(4)
+        pivot[1, 3], back[1, 3] = height * t, -height * t
+        m = pivot @ rz @ rx @ np.diag([1.0 + 0.05 * math.sin(0.3 * frame + k), 1.0, 1.0 - 0.04 * math.cos(0.2 * frame + phase), 1.0]) @ back
+        m[0, 3] += 0.03 * math.sin(0.6 * frame + phase)
+        out.append(m.T.reshape(-1))
+    return np.stack(out).astype(np.float32)
+
+
+def swaying_ribbon(rest, normals, frame, phase=0.0, height=0.9):
+    """A coil_ribbon's positions and normals at `frame`: bent sideways more the higher up, breathing in and out."""
+    p = rest.astype(np.float64).copy()
+    t = p[:, 1] / height
+    breathe = 1.0 + 0.15 * math.sin(0.7 * frame + phase)
+    p[:, 0] = p[:, 0] * breathe + 0.25 * t * t * math.sin(0.5 * frame + phase)
+    p[:, 2] = p[:, 2] * breathe + 0.15 * t * t * math.cos(0.4 * frame + 2.0 * phase)
+    n = normals.astype(np.float64).copy()
+    n[:, 1] = -0.3 * t * math.sin(0.5 * frame + phase)
+    n /= np.linalg.norm(n, axis=1, keepdims=True)
+    return p.astype(np.float32), n.astype(np.float32)
+
+
+def crowd_scene(base, sizes, joints=(1, 3, 17), n_emissive=2, n_doubled=3, extent=3.2, skinned=None):
+    """A crowd on top of `base` ("yard" / "small", as deforming_scene): one coil_ribbon of sizes[k] triangles per entry, one instance each
+    and a second one of `n_doubled` of them; `n_emissive` of the meshes glow.  Entries for which skinned(k) holds (default: the even ones)
+    are skinned - palettes of `joints` joints in turn - the others are vertex-updated, every third of those without new normals.  Returns (SceneData with .builder, sun, meshes) like
+    deforming_scene: meshes maps "m0", "m1", ... to dict(id, index, rest, normals, kind = "skin" / "vertices", pose = frame -> what the
+    deformation call takes after the mesh: (joints,) or (positions, normals_or_None); skinned ones also joints / weights for
+    set_mesh_skin) in the order the meshes were added."""
+    if base == "yard":
+        scene, sun = synthetic_scene(n_boxes=20, n_spheres=5, n_emitters=2, sphere_rings=12, sphere_segs=16)
+    else:
+        scene, sun = synthetic_scene(n_boxes=2, n_spheres=1, n_emitters=1, sphere_rings=4, sphere_segs=5)
+    b = scene.builder
+    n = len(sizes)
+    plain = b.add_material(standard_material((0.3, 0.6, 0.8, 1.0), (0, 0, 0), 0.6, 0.0, 0.5))
+    glow = b.add_material(standard_material((0.9, 0.9, 0.9, 1.0), (0.6, 1.0, 0.7), 1.0, 0.0, 0.5))
+    emissive = {(j + 1) * n // (n_emissive + 1) for j in range(n_emissive)} if n else set()
+    doubled = {(2 * j + 1) * n // (2 * n_doubled) for j in range(n_doubled)} if n else set()
+    side = max(int(math.ceil(math.sqrt(n))), 1)
+    meshes, vertex_items, skin_items = {}, 0, 0
+    skinned = skinned or (lambda k: k % 2 == 0)
+    for k, triangles in enumerate(sizes):
+        p, nr, uv, idx = coil_ribbon(triangles)
+        m = dict(id=b.add_mesh(p, nr, uv, idx), rest=p, normals=nr)
+        phase = 0.37 * k
+        if skinned(k):
+            nj = joints[skin_items % len(joints)]
+            skin_items += 1
+            ji, jw = ribbon_skin(p, nj)
+            m.update(kind="skin", joints=ji, weights=jw, pose=lambda frame, nj=nj, phase=phase: (chain_joints(nj, frame, phase),))
+        else:
+            keep_normals = vertex_items % 3 == 2
+            vertex_items += 1
+
+            def pose(frame, p=p, nr=nr, phase=phase, keep_normals=keep_normals):
+                q, qn = swaying_ribbon(p, nr, frame, phase)
+                return q, (None if keep_normals else qn)
+
+            m.update(kind="vertices", pose=pose)
+        gx, gz = k % side, k // side
+        x, z = ((gx + 0.5) / side - 0.5) * 2.0 * extent, ((gz + 0.5) / side - 0.5) * 2.0 * extent
+        b.add_instance(m["id"], glow if k in emissive else plain, _trs((x, 0.05, z), (0.0, 0.9 * k, 0.0), (1.0, 1.0, 1.0)))
+        if k in doubled:
+            b.add_instance(m["id"], plain, _trs((x + 0.3, 1.3, z - 0.2), (0.3, 0.5 * k, 0.1), (0.7, 0.8, 0.7)))
+        meshes[f"m{k}"] = m
+    scene = b.finish()
+    scene.builder = b
+    for m in meshes.values():
+        m["index"] = b.mesh_index(m["id"])
+    return scene, sun, meshes
+
+
+def crowd_items(meshes, frame):
+    """Engine.deform_meshes' item list for every mesh of a crowd_scene at `frame`, in the order the meshes were added."""
+    return [(m["kind"], m["index"]) + tuple(m["pose"](frame)) for m in meshes.values()]

@@ -426,6 +426,8 @@ class HikariPlugin {
   // new texels and sampler of one uploaded texture of the same size, in place
   void update_texture(uint32_t index, const HkImageDesc& image) { check(hk_update_texture(ctx_.get(), index, &image), "hk_update_texture"); }
   // a new tree over the current triangles of one deformed mesh, built on the device in place (later deformations refit the new shape)
+  // per frame: every deforming mesh in one call (vertex updates and skinned meshes alike), at a launch count that does not depend on how many
+  void deform_meshes(const std::vector<HkMeshDeform>& items) { check(hk_deform_meshes(ctx_.get(), items.data(), (uint32_t)items.size()), "hk_deform_meshes"); }
   void rebuild_mesh_tree(const HkMeshIndex& mesh, uint32_t mode = HK_TREE_SAH) { check(hk_rebuild_mesh_tree(ctx_.get(), &mesh, mode), "hk_rebuild_mesh_tree"); }
 
   // one frame of the camera's render graph; by_nodes = dispatch by dispatch through the three nodes,
@@ -508,6 +510,7 @@ class HikariMultiGpuPlugin {
     return changed;
   }
   void update_texture(uint32_t index, const HkImageDesc& image) { check(hk_multi_update_texture(m_, index, &image), "hk_multi_update_texture"); }
+  void deform_meshes(const std::vector<HkMeshDeform>& items) { check(hk_multi_deform_meshes(m_, items.data(), (uint32_t)items.size()), "hk_multi_deform_meshes"); }
   void rebuild_mesh_tree(const HkMeshIndex& mesh, uint32_t mode = HK_TREE_SAH) { check(hk_multi_rebuild_mesh_tree(m_, &mesh, mode), "hk_multi_rebuild_mesh_tree"); }
   // rows of last frame's reservoirs fetched across the band borders before reprojection (0 for a static camera)
   void set_history_rows(uint32_t rows) { check(hk_multi_set_history_rows(m_, rows), "hk_multi_set_history_rows"); }

@@ -652,6 +652,28 @@ int hk_set_mesh_skin(hk_ctx* ctx, const HkMeshIndex* mesh, uint32_t n_vertices, 
 /* per frame: n_joints column-major 4x4 joint matrices; the device skins the mesh (positions and normals, mesh-local) and refits as
  * hk_update_mesh_vertices does.  A joint index >= n_joints in the skin is refused (HK_E_INVALID, nothing written). */
 int hk_skin_mesh(hk_ctx* ctx, const HkMeshIndex* mesh, const float* joint_matrices, uint32_t n_joints);
+/* MANY meshes deformed in one call: item k is what hk_update_mesh_vertices (HK_DEFORM_VERTICES) or hk_skin_mesh (HK_DEFORM_SKIN) takes for
+ * one mesh.  After the call the context is in every respect what the n single-mesh calls in item order would have left - device bytes,
+ * what is stale, what is refused afterwards - but the device work is a fixed number of kernel launches, however many items there are
+ * (a crowd of skinned characters costs what one character costs to enqueue), and so is what follows before the next frame: the new
+ * boxes reach the instances and emitters of all deformed meshes in one launch each, the wide records of their trees are derived in
+ * one.  Composes with hk_refit_scene_instances, hk_rebuild_mesh_tree, the single-mesh calls and frames in flight as those calls do.
+ * The whole batch is validated before anything is enqueued or written: the first bad item returns its error with the item's index
+ * in hk_last_error(), the scene untouched.  Per item the checks of the single calls (unknown mesh record, vertex count out of range,
+ * no skin set, a joint index >= count, NULL data, normals on a skin item, unknown kind: HK_E_INVALID); a mesh named twice in one
+ * batch is HK_E_INVALID.  n == 0 returns HK_OK and does nothing.  Once every mesh of the batch has been deformed before and nothing
+ * has to grow, the call neither waits for the device nor allocates: the item table, every item's data and the joint palettes travel
+ * in ONE pinned staging block from the pool. */
+#define HK_DEFORM_VERTICES 0u   /* what hk_update_mesh_vertices takes */
+#define HK_DEFORM_SKIN     1u   /* what hk_skin_mesh takes; hk_set_mesh_skin must have been called for the mesh */
+typedef struct HkMeshDeform {
+  HkMeshIndex  mesh;
+  uint32_t     kind;
+  uint32_t     count;    /* VERTICES: n_vertices.  SKIN: n_joints */
+  const float* data;     /* VERTICES: count x 3 positions.  SKIN: count x 16 joint matrices, column-major */
+  const float* normals;  /* VERTICES: count x 3, or NULL = keep.  SKIN: must be NULL */
+} HkMeshDeform;
+int hk_deform_meshes(hk_ctx* ctx, const HkMeshDeform* items, uint32_t n);
 /* ... and the REBUILD of one mesh's tree on the device, for when refits have degraded it (a skinned character far from its bind pose,
  * a cloth folded onto itself): a new tree over the mesh's current triangle boxes, written in place over the mesh's nodes in the
  * mesh-level region - ordering 0 in the builder's left-before-right order, orderings 1-7 by the rule of hk_bvh_rethread, single-leaf
@@ -1069,6 +1091,7 @@ int hk_multi_update_mesh_vertices(hk_multi* m, const HkMeshIndex* mesh, uint32_t
 int hk_multi_set_mesh_skin(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vertices, const float* bind_positions, const float* bind_normals,
                            const uint16_t* joint_indices, const float* joint_weights);
 int hk_multi_skin_mesh(hk_multi* m, const HkMeshIndex* mesh, const float* joint_matrices, uint32_t n_joints);
+int hk_multi_deform_meshes(hk_multi* m, const HkMeshDeform* items, uint32_t n);
 int hk_multi_rebuild_mesh_tree(hk_multi* m, const HkMeshIndex* mesh, uint32_t mode);
 int hk_multi_set_band_bounds(hk_multi* m, const uint32_t* bounds, uint32_t n_bounds);
 /* hk_migrate_bands for the one-process form: the rows that change owner travel as peer copies, then every band takes the new split */
