@@ -1904,7 +1904,9 @@ int hk_write_buffer(hk_ctx* c, uint32_t buffer, const void* src, size_t bytes) {
   HK_HIP(hipMemcpy(c->buf[buffer], src, bytes, hipMemcpyHostToDevice));
   if (buffer >= HK_BUF_RESERVOIR0 && buffer < HK_BUF_RESERVOIR0 + 10 && c->tile_meta[buffer - HK_BUF_RESERVOIR0]) {  // host-written reservoirs: tiles unknown
     const uint32_t k = buffer - HK_BUF_RESERVOIR0;
-    HK_HIP(hipMemset(c->tile_meta[k], 0, (size_t)c->tiles_x * c->tiles_y * sizeof(TileMeta)));
+    // (on the context's stream, in front of every later dispatch: hipMemset runs on the null stream, asynchronously to the host, and the
+    // context's streams are non-blocking - the next spatial dispatch could read the old tile records and elide the host's record)
+    HK_HIP(hipMemsetAsync(c->tile_meta[k], 0, (size_t)c->tiles_x * c->tiles_y * sizeof(TileMeta), c->stream));
     c->tile_meta_zero[k] = true;
   }
   if (buffer == HK_BUF_POSITION || buffer == HK_BUF_NORMAL || buffer == HK_BUF_INSTANCE_MATERIAL) c->derived_dirty = true;

@@ -277,6 +277,14 @@ HKD float unsnorm8(uint32_t b) { return fmax_(div_norm<127>((float)(int32_t)(int
 HKD float unorm8(uint32_t b) { return div_norm<255>((float)(b & 0xffu)); }
 HKD f4 unpack4x8snorm(uint32_t u) { return {unsnorm8(u & 0xffu), unsnorm8((u >> 8) & 0xffu), unsnorm8((u >> 16) & 0xffu), unsnorm8(u >> 24)}; }
 HKD uint2 pack_f16x4(f4 v) { return make_uint2(pack2x16float(v.x, v.y), pack2x16float(v.z, v.w)); }
+// a NaN as THE quiet NaN (0x7e00 once stored as f16): what the anti-aliasing tail and spatial_reuse store ("NaNs the
+// tail stores" and "Spatial reuse on adversarial planes")
+HKD float canonical_nan(float v) { return v != v ? u2f(0x7fc00000u) : v; }
+HKD uint32_t canonical_nan_f16x2(uint32_t u) {  // the same on two packed halves (what converting canonical_nan(v) stores)
+  if ((u & 0x7fffu) > 0x7c00u) u = (u & 0xffff0000u) | 0x7e00u;
+  if ((u & 0x7fff0000u) > 0x7c000000u) u = (u & 0x0000ffffu) | 0x7e000000u;
+  return u;
+}
 HKD f4 unpack_f16x4(uint2 u) {
   f2 a = unpack2x16float(u.x), b = unpack2x16float(u.y);
   return {a.x, a.y, b.x, b.y};

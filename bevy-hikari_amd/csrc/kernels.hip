@@ -893,10 +893,19 @@ __global__ __launch_bounds__(256, HK_SPATIAL_WGS) void k_spatial_reuse(DScene sc
   const float total_lum = EMISSIVE_LIT ? r.count * luminance(xyz(r.s.radiance)) : r.count * luminance(out_radiance);
   r.w = (total_lum > 0.0f) ? r.w_sum / total_lum : 0.0f;
   r.lifetime += 1.0f;
-  store_packed(t.spatial, index, pack_reservoir(r));
+  // What this pass computed and stores - the four statistics and the colour - leaves as THE quiet NaN 0x7e00 where it is one: the sign
+  // of a NaN result follows the compiler (the statistics of a neighbour with a NaN `w` came out as 0xfe00 here, 0x7e00 on x86).  On the
+  // packed halves, after everything else: the arithmetic in front of the stores is what it was.
+  PackedReservoir pr = pack_reservoir(r);
+  pr.reservoir.x = canonical_nan_f16x2(pr.reservoir.x);
+  pr.reservoir.y = canonical_nan_f16x2(pr.reservoir.y);
+  store_packed(t.spatial, index, pr);
   if (t.m_spatial) tile_unknown(t.m_spatial, tile);
-  if (use_spatial_variance) t.variance[index] = reservoir_variance(r);
-  t.render[index] = pack_f16x4(F4(r.w * out_radiance, 1.0f));
+  if (use_spatial_variance) t.variance[index] = reservoir_variance(r);  // (never a NaN: fmin_ returns the operand that is a number)
+  uint2 color = pack_f16x4(F4(r.w * out_radiance, 1.0f));
+  color.x = canonical_nan_f16x2(color.x);
+  color.y = canonical_nan_f16x2(color.y);
+  t.render[index] = color;
 }
 
 // (demodulation + a-trous kernels live in kernels_denoise.hip)

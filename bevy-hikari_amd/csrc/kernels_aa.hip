@@ -114,7 +114,7 @@ HKD void load_loose(const uint2* p, int w, int h, int x, int y, f4* out) {  // t
 // What the tail stores: a NaN leaves as THE quiet NaN 0x7e00 ("NaNs the tail stores").  IEEE 754 leaves the sign
 // and the payload of a NaN result open and the targets differ - an invalid operation gives 0x7fc00000 here and 0xffc00000 on x86, a
 // subtraction folded into a negated operand flips the sign of a NaN it passes on - so the bits would follow the compiler.
-HKD float canonical_nan(float v) { return v != v ? u2f(0x7fc00000u) : v; }
+// (canonical_nan: hk_device_math.hpp)
 HKD uint2 pack_stored(f4 v) { return pack_f16x4(F4(canonical_nan(v.x), canonical_nan(v.y), canonical_nan(v.z), canonical_nan(v.w))); }
 HKD void store_loose(uint2* p, int w, int h, int x, int y, f4 v) {
   if (x >= 0 && y >= 0 && x < w && y < h) p[x + w * y] = pack_stored(v);

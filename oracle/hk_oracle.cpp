@@ -1712,17 +1712,24 @@ static void pass_spatial_reuse(Ctx* c, bool emissive_lit, int y0, int y1) {
       r.w = (total_lum > 0.0f) ? r.w_sum / total_lum : 0.0f;
       r.lifetime += 1.0f;
 
+      // RENDER_EMISSIVE is never defined for spatial_reuse pipelines (light.rs:433-442)
+      v3 out_color = r.w * out_radiance;
+      // what the pass computed and stores leaves as the quiet NaN where it is one, as in the anti-aliasing tail (IEEE 754 leaves the
+      // sign of a NaN result open and x86 and gfx950 differ: DESIGN.md section 2, "Spatial reuse on adversarial planes")
+      auto canonical = [](float f) { return f != f ? u2f(0x7fc00000u) : f; };
+      r.count = canonical(r.count);
+      r.w = canonical(r.w);
+      r.w_sum = canonical(r.w_sum);
+      r.w2_sum = canonical(r.w2_sum);
       rs.spatial[index] = pack_reservoir(r);
 
       if (use_spatial_variance) {
         float variance = r.w2_sum / r.count - pow2_(r.w_sum / r.count);
         variance = (r.count < 1.0f) ? variance : variance / r.count;
         variance = fmin_(variance, MAX_VARIANCE);
-        variance_texture.store_f32(x, y, variance);
+        variance_texture.store_f32(x, y, variance);  // (never a NaN: fmin_ returns the operand that is a number)
       }
-      // RENDER_EMISSIVE is never defined for spatial_reuse pipelines (light.rs:433-442)
-      v3 out_color = r.w * out_radiance;
-      render_texture.store_f16x4(x, y, V4(out_color, 1.0f));
+      render_texture.store_f16x4_canonical(x, y, V4(out_color, 1.0f));
     }
   }
 }

@@ -690,3 +690,530 @@ def install_aa(engine, planes, resize=True):
         engine.write(buf, array)
     for buf in (F.BUF_TAA_OUTPUT, F.BUF_UPSCALE_SHARPENED):
         engine.write(buf, np.zeros_like(engine.read(buf)))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# spatial_reuse: k_spatial_reuse<emissive or indirect, plain or windowed>
+# ------------------------------------------------------------------------------------------------------------------------------
+"""Plane sets for ONE spatial_reuse dispatch (`make_spatial_planes`): the three G-buffer planes the pass reads (position with the
+depth in .w, instance_material, velocity_uv), the channel's `current` and `previous_spatial` reservoirs as 64-byte records
+(`pack_records` mirrors pack_reservoir, light.wgsl:111-136) and a sentinel fill of everything the pass writes or must leave alone.
+Coordinates below are RENDER pixels of a 70 x 45 image; `compact` scales them into a small one.  Material ids stay inside the table of
+`spatial_scene()`; the frame uniform comes from hk.frame_uniform.
+
+  terraces    the benign fill: depths on the lattice 2 + k / 64 in terraces a few texels wide (every depth ratio within 3 % of 1, every
+              march comparison an exact tie or off by 1 / 384 and more), normals from three directions 15, 40 and 55 degrees apart,
+              samples one unit in front of or behind their surface, counts 1 .. 20, radiance 0.05 .. 3, a background block.
+  depths      the centre depth 0 and F32_EPSILON -/+ one ulp; NaN, +Inf, negative and denormal depths at a centre, at a neighbour and
+              under a march step; depth ratios of 0.9 and 1.1 -/+ one ulp on both sides; a one-texel occluder at each march step of
+              the longest and of the shortest marched tap; an occluder 1e-5 -/+ one ulp above the interpolated depth; taps that land on
+              background texels (depth / 0) and, at ratios above 1, taps at the border whose jittered texel lies outside the plane.
+  records     neighbour counts 0, denormal, F32_EPSILON -/+ ulp, 4, 5, 65504, +Inf, NaN; sums that cross max_spatial_reuse_count
+              exactly, by one, not at all; w / w_sum / w2_sum of 0, 65504, Inf, NaN; radiance +0, -0, NaN, 65504; normals at the
+              0.866 threshold -/+ one snorm step, zero and anti-parallel; samples on the visible position, edge-on and behind; the
+              Jacobian flag with edge-on / averted sample normals, near and far; lifetimes around the limit and at 254; the `random`
+              sums that put some tap's angle nearest to 0, 1/4, 1/2 and 3/4 of a turn.
+  history     previous_uv exactly 0, one ulp under 1, exactly 1, negative, NaN, +-Inf, 1e9; a history record that passes, a zero one.
+  background  all-background wave tiles, tiles with one geometry pixel in a corner lane, a whole workgroup of background next to one of
+              geometry, a NaN-depth pixel as a tile's only non-background lane.
+  random      dense seeded noise with a few percent of each special, on a depth plane in which every texel differs."""
+SPATIAL_SETS = ("terraces", "depths", "records", "history", "background", "random")
+SPATIAL_WIDTHS, SPATIAL_HEIGHTS = (1, 8, 17, 49, 70), (1, 17, 45)
+SPATIAL_COUNTS, SPATIAL_LIFETIMES, SPATIAL_RATIOS = (4, 100, 800), (0.0, 1.0, 7.0), (1.0, 1.5, 2.0)
+T_SLOT, S_SLOT = (0, 2, 6), (4, 4, 8)              # light.rs:518-546, as make_light_targets and wgsl_pin.Pinner.reservoirs
+SENTINEL_U32, SENTINEL_F32, SENTINEL_F16 = 0xC3A5C3A5, np.float32(-12345.5), 0x5BCD
+SPATIAL_NORMALS = np.array([[0.0, 0.0, 1.0], [np.sin(np.radians(15.0)), 0.0, np.cos(np.radians(15.0))], [-np.sin(np.radians(40.0)), 0.0, np.cos(np.radians(40.0))]])
+#: (base colour, metallic, perceptual roughness): roughness either side of the 0.089 clamp, metallic 0 and 1
+SPATIAL_MATERIALS = [((0.8, 0.7, 0.6), 0.0, 0.5), ((0.2, 0.9, 0.3), 1.0, 0.05), ((0.9, 0.1, 0.1), 0.0, 0.089), ((0.3, 0.3, 0.95), 1.0, 0.09),
+                     ((1.0, 1.0, 1.0), 0.0, 1.0), ((0.05, 0.5, 0.7), 0.0, 0.0885)]
+_f32 = np.float32
+
+
+def spatial_scene():
+    """one triangle per material (the pass traces nothing): six materials distinct in colour, metallic and roughness, no textures"""
+    b = hk.SceneBuilder()
+    mesh = b.add_mesh([[0, 0, 0], [1, 0, 0], [0, 1, 0]], [[0, 0, 1]] * 3, [[0, 0], [1, 0], [0, 1]])
+    for k, (colour, metallic, roughness) in enumerate(SPATIAL_MATERIALS):
+        m = b.add_material(hk.standard_material(colour + (1.0,), perceptual_roughness=roughness, metallic=metallic, reflectance=0.3 + 0.1 * k))
+        t = np.eye(4, dtype=np.float32)
+        t[3, 0] = 3.0 * k
+        b.add_instance(mesh, m, t)
+    return b.finish()
+
+
+def _hash(value):
+    """utils.wgsl:15-24"""
+    s = value & 0xFFFFFFFF
+    s ^= 2747636419
+    s = (s * 2654435769) & 0xFFFFFFFF
+    s ^= s >> 16
+    s = (s * 2654435769) & 0xFFFFFFFF
+    s ^= s >> 16
+    s = (s * 2654435769) & 0xFFFFFFFF
+    return s
+
+
+def random_float(value):
+    return _f32(_f32(_hash(value)) / _f32(4294967295.0))
+
+
+class Records:
+    """reservoirs of one buffer on a grid, field by field, in the units of their storage: f16 BITS for count / w / w_sum / w2_sum and
+    the radiance, unorm16 CODES for random, f32 for the positions and the instance, snorm8 BYTES (int8) for the normals, the lifetime
+    as a number 0 .. 254 (byte = lifetime - 127) and the flag byte (127: the sample has a Jacobian)"""
+
+    def __init__(self, h, w):
+        self.count, self.w, self.w_sum, self.w2_sum = (np.zeros((h, w), np.uint16) for _ in range(4))
+        self.radiance, self.random = np.zeros((h, w, 4), np.uint16), np.zeros((h, w, 4), np.uint16)
+        self.visible_position, self.sample_position = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 3), np.float32)
+        self.visible_instance = np.zeros((h, w), np.float32)
+        self.visible_normal, self.sample_normal = np.zeros((h, w, 3), np.int8), np.zeros((h, w, 3), np.int8)
+        self.lifetime, self.jacobian_flag = np.full((h, w), 127, np.int16), np.zeros((h, w), np.int8)
+
+    def crop(self, h, w):
+        out = Records(0, 0)
+        for k, v in vars(self).items():
+            setattr(out, k, np.ascontiguousarray(v[:h, :w]))
+        return out
+
+    def zero(self, where):
+        for k, v in vars(self).items():
+            v[where] = 127 if k == "lifetime" else 0
+
+
+def pack_records(r):
+    """[h, w, 16] u32: PackedReservoir (light.wgsl:35-43) word for word"""
+    h, w = r.count.shape
+    out = np.zeros((h, w, 16), np.uint32)
+    u = lambda lo, hi: lo.astype(np.uint32) | (hi.astype(np.uint32) << 16)
+    out[..., 0], out[..., 1] = u(r.radiance[..., 0], r.radiance[..., 1]), u(r.radiance[..., 2], r.radiance[..., 3])
+    out[..., 2], out[..., 3] = u(r.random[..., 0], r.random[..., 1]), u(r.random[..., 2], r.random[..., 3])
+    out[..., 4:8] = r.visible_position.view(np.uint32)
+    out[..., 8:11] = r.sample_position.view(np.uint32)
+    out[..., 11] = r.visible_instance.view(np.uint32)
+    b = lambda n, last: (n[..., 0].astype(np.uint8).astype(np.uint32) | (n[..., 1].astype(np.uint8).astype(np.uint32) << 8) |
+                         (n[..., 2].astype(np.uint8).astype(np.uint32) << 16) | (last.astype(np.uint8).astype(np.uint32) << 24))
+    out[..., 12] = b(r.visible_normal, (r.lifetime - 127).astype(np.int8))
+    out[..., 13] = b(r.sample_normal, r.jacobian_flag)
+    out[..., 14], out[..., 15] = u(r.count, r.w), u(r.w_sum, r.w2_sum)
+    return out
+
+
+def snorm8(n):
+    return np.floor(0.5 + 127.0 * np.clip(np.asarray(n, dtype=np.float64), -1.0, 1.0)).astype(np.int8)
+
+
+class SpatialPlanes:
+    def __init__(self, name, seed, window_size, ratio, channel, frame_number, max_count, max_lifetime):
+        self.name, self.seed, self.window_size, self.ratio, self.channel = name, seed, tuple(window_size), float(ratio), channel
+        self.settings = hk.HikariSettings(indirect_bounces=1, upscale=hk.Upscale.SmaaTu4x(ratio), max_spatial_reuse_count=max_count,
+                                          max_reservoir_lifetime=max_lifetime, emissive_spatial_reuse=True)
+        self.frame = hk.frame_uniform(self.settings, frame_number)
+        self.render_size = render_size_of(window_size, ratio)
+        cur = frame_number % 2
+        prev = 1 - cur
+        self.slots = {"previous": F.BUF_RESERVOIR0 + cur + T_SLOT[channel], "current": F.BUF_RESERVOIR0 + prev + T_SLOT[channel],
+                      "previous_spatial": F.BUF_RESERVOIR0 + cur + S_SLOT[channel], "spatial": F.BUF_RESERVOIR0 + prev + S_SLOT[channel]}
+        self.pass_id = F.PASS_EMISSIVE_SPATIAL_REUSE if channel == 1 else F.PASS_INDIRECT_SPATIAL_REUSE
+        self.buffers, self.placed = {}, None
+        self.current = self.previous_spatial = None          # Records on the render grid
+
+    @property
+    def outputs(self):
+        """what the pass writes"""
+        return {"spatial": self.slots["spatial"], "variance": F.BUF_VARIANCE0 + self.channel, "render": F.BUF_RENDER0 + self.channel}
+
+    @property
+    def untouched(self):
+        """what it reads or must leave alone"""
+        return {"current": self.slots["current"], "previous_spatial": self.slots["previous_spatial"], "previous": self.slots["previous"],
+                "position": F.BUF_POSITION, "instance_material": F.BUF_INSTANCE_MATERIAL, "velocity_uv": F.BUF_VELOCITY_UV}
+
+
+def spatial_deferred(p, u, v):
+    """jittered_deferred_coords (light.wgsl:1007-1017) of a uv in f32, unclamped: (column, row) of the G-buffer texel"""
+    dw, dh = p.window_size
+    sgn = _f32(-0.25) if p.frame.number % 2 == 0 else _f32(0.25)
+    ratio = _f32(_f32(p.frame.upscale_ratio) - _f32(1.0))
+    ju = _f32(_f32(u) + _f32(_f32(sgn * _f32(_f32(1.0) / _f32(dw))) * ratio))
+    jv = _f32(_f32(v) + _f32(_f32(sgn * _f32(_f32(1.0) / _f32(dh))) * ratio))
+    return int(np.trunc(_f32(ju * _f32(dw)))), int(np.trunc(_f32(jv * _f32(dh))))
+
+
+def spatial_texel(p, x, y):
+    rw, rh = p.render_size
+    return spatial_deferred(p, _f32(_f32(x + 0.5) / _f32(rw)), _f32(_f32(y + 0.5) / _f32(rh)))
+
+
+def spatial_tap(p, x, y, i, random_sum=0.0):
+    """tap i (1 ..) of render pixel (x, y) whose record's random components sum to `random_sum`: (sample pixel, [march texels]) as the
+    shader places them (light.wgsl:1568-1576, 1609-1618), in f32 with numpy's cos and sin - for PLACING specials, no reference"""
+    count, reach = (8, 10.0) if p.channel == 1 else (16, 20.0)
+    rw, rh = p.render_size
+    turn = _f32(_f32(_f32(_f32(i) * _f32(1.618033989)) + _f32(random_sum)) + random_float(p.frame.number))
+    angle = _f32(_f32(6.283185307) * _f32(turn - np.floor(turn)))
+    radius = _f32(np.sqrt(_f32(_f32(i) / _f32(count))) * _f32(reach))
+    ox, oy = _f32(radius * np.cos(angle, dtype=np.float32)), _f32(radius * np.sin(angle, dtype=np.float32))
+    sx, sy = int(np.trunc(_f32(ox + _f32(x)))), int(np.trunc(_f32(oy + _f32(y))))
+    interval = max(_f32(1.0), _f32(radius / _f32(5.0)))
+    n = int(_f32(radius / interval))
+    length = _f32(np.sqrt(_f32(ox * ox + oy * oy)))
+    u, v = _f32(_f32(x + 0.5) / _f32(rw)), _f32(_f32(y + 0.5) / _f32(rh))
+    march = []
+    for j in range(1, n + 1):
+        d = _f32(_f32(j) * interval)
+        march.append(spatial_deferred(p, _f32(u + _f32(_f32(d * _f32(ox / length)) / _f32(rw))), _f32(v + _f32(_f32(d * _f32(oy / length)) / _f32(rh)))))
+    return (sx, sy), march
+
+
+def quarter_turn_randoms(frame_number, count=16):
+    """for each of 0, 1/4, 1/2, 3/4 of a turn: the unorm16 code c whose decoded value c / 65535 (the other three components 0) puts
+    fract(i * golden + random + random_float(frame)) nearest to it for some tap i - a search over the codes (f32, the shader's order)"""
+    codes = np.arange(65536, dtype=np.float32) / _f32(65535.0)
+    found = []
+    for target in (0.0, 0.25, 0.5, 0.75):
+        best = None
+        for i in range(1, count + 1):
+            t = (_f32(_f32(i) * _f32(1.618033989)) + codes).astype(np.float32) + random_float(frame_number)
+            fr = (t - np.floor(t)).astype(np.float32)
+            d = np.abs(fr.astype(np.float64) - target)
+            if target == 0.0:
+                d = np.minimum(d, 1.0 - fr.astype(np.float64))
+            k = int(np.argmin(d))
+            if best is None or d[k] < best[0]:
+                best = (float(d[k]), k, i)
+        found.append((best[1], best[2]))
+    return found
+
+
+def make_spatial_planes(name, seed, render_size, ratio, channel, frame_number=2, max_count=800, max_lifetime=0.0, compact=False):
+    """One spatial_reuse dispatch of `channel` (1 emissive, 2 indirect) at `render_size`, the window being window_for(render_size, ratio)."""
+    assert name in SPATIAL_SETS and channel in (1, 2)
+    p = SpatialPlanes(name, seed, window_for(render_size, ratio), ratio, channel, frame_number, max_count, max_lifetime)
+    assert p.render_size == tuple(render_size)
+    rng = np.random.default_rng([seed, 200 + SPATIAL_SETS.index(name), channel])
+    (dw, dh), (rw, rh) = p.window_size, p.render_size
+    fit = (lambda x, y: (x * rw // 70, y * rh // 45)) if compact else (lambda x, y: (x, y))
+    inside = lambda x, y: 0 <= x < rw and 0 <= y < rh
+    placed = np.zeros((rh + 1, rw + 1), bool)
+
+    def at(x, y, mark=True):
+        """render grid [row, column] of a layout pixel (the spare row / column when it falls outside)"""
+        x, y = fit(x, y)
+        if not inside(x, y):
+            return rh, rw
+        if mark:
+            placed[y, x] = True
+        return y, x
+
+    def under(x, y, fitted=False):
+        """G-buffer [row, column] under a layout pixel"""
+        if not fitted:
+            x, y = fit(x, y)
+        if not inside(x, y):
+            return dh, dw
+        tx, ty = spatial_texel(p, x, y)
+        return (ty, tx) if 0 <= tx < dw and 0 <= ty < dh else (dh, dw)
+
+    # ---- the G-buffer: terraces (or, for `random`, a depth that differs in every texel) facing the camera of cornell_camera
+    gx, gy = np.meshgrid(np.arange(dw + 1), np.arange(dh + 1))
+    terrace = (gx // 5 + gy // 4) % 4
+    depth = (2.0 + terrace / 64.0).astype(np.float32)
+    if name == "random":
+        depth = (2.0 + 0.1 * rng.permutation((dw + 1) * (dh + 1)).reshape(dh + 1, dw + 1) / ((dw + 1) * (dh + 1))).astype(np.float32)
+    position = np.zeros((dh + 1, dw + 1, 4), np.float32)
+    position[..., 0], position[..., 1], position[..., 2] = 0.02 * (gx - dw / 2), 1.0 + 0.02 * (dh / 2 - gy), 4.0 - depth
+    position[..., 3] = depth
+    background = (gx >= dw - max(1, dw // 10)) & (gy < dh // 2) if dw > 8 else np.zeros((dh + 1, dw + 1), bool)
+    instance = np.zeros((dh + 1, dw + 1, 2), np.float32)
+    instance[..., 0] = (gx // 9 + gy // 7) % len(SPATIAL_MATERIALS)
+    instance[..., 1] = instance[..., 0]                               # material id = instance id: inside the table
+    velocity = np.zeros((dh + 1, dw + 1, 4), np.float32)
+    velocity[..., 2:] = rng.random((dh + 1, dw + 1, 2))
+    # (history: every third column block looks one render pixel to the left, the rest at the pixel itself)
+    velocity[..., 0] = np.where((gx // 6) % 3 == 1, _f32(1.0) / _f32(rw), _f32(0.0))
+
+    # ---- the records of `current` and `previous_spatial`, on the render grid
+    ry, rx = np.meshgrid(np.arange(rh + 1), np.arange(rw + 1), indexing="ij")
+    tex_of = np.array([[under(x, y, fitted=True) for x in range(rw)] + [(dh, dw)] for y in range(rh)] + [[(dh, dw)] * (rw + 1)])
+    ty_, tx_ = tex_of[..., 0], tex_of[..., 1]
+
+    def fill():
+        r = Records(rh + 1, rw + 1)
+        shape = (rh + 1, rw + 1)
+        r.count[...] = f16_bits(rng.integers(1, 21, shape))
+        r.w[...] = f16_bits(0.1 + 1.9 * rng.random(shape))
+        r.w_sum[...] = f16_bits(0.5 + 9.5 * rng.random(shape))
+        r.w2_sum[...] = f16_bits(0.5 + 49.5 * rng.random(shape))
+        r.radiance[..., :3] = f16_bits(0.05 + 2.95 * rng.random(shape + (3,)))
+        r.radiance[..., 3] = np.where(rng.random(shape) < 0.85, H_ONE, 0)          # input_radiance.a: lit, or the ambient miss
+        r.random[...] = rng.integers(0, 65536, shape + (4,))
+        r.visible_position[...] = position[ty_, tx_]
+        which = (rx // 11 + ry // 6) % 3
+        normal = SPATIAL_NORMALS[which]
+        r.visible_normal[...] = snorm8(normal)
+        front = rng.random(shape) < 0.8                                             # the sample: one unit in front of the surface, or behind it
+        lateral = 0.3 * (rng.random(shape + (3,)) - 0.5)
+        r.sample_position[...] = (r.visible_position[..., :3] + np.where(front[..., None], 1.0, -1.0) * normal + lateral).astype(np.float32)
+        r.sample_normal[...] = snorm8(-normal + 0.2 * (rng.random(shape + (3,)) - 0.5))
+        r.jacobian_flag[...] = np.where(rng.random(shape) < 0.5, 127, 0)
+        life = rng.integers(0, 11, shape)
+        r.lifetime[...] = life + (life >= 7)                                          # 0 .. 6, 8 .. 11: never AT the limit of 7 (127 * (1 + b / 127) is not 7 in f32)
+        r.visible_instance[...] = instance[ty_, tx_, 0]
+        return r
+
+    cur, hist = fill(), fill()
+    hist.zero(rng.random((rh + 1, rw + 1)) < 0.1)                                     # a tenth of the history is empty
+    one_ulp = lambda v, towards: np.nextafter(_f32(v), _f32(towards))
+    n_taps = 8 if channel == 1 else 16
+
+    def centre(x, y):
+        """a centre pixel whose tap pattern is known: random = 0, a long history refusal left to the fill"""
+        cur.random[at(x, y)] = 0
+        return fit(x, y)
+
+    def neighbour(x, y, i):
+        """the render pixel [row, column] tap i of layout pixel (x, y) lands on and the G-buffer texels of its march, or None"""
+        fx, fy = fit(x, y)
+        (sx, sy), march = spatial_tap(p, fx, fy, i, 0.0)
+        if not (inside(fx, fy) and inside(sx, sy)):
+            return None
+        placed[sy, sx] = True
+        return (sy, sx), under(sx, sy, fitted=True), [(ty, tx) if 0 <= tx < dw and 0 <= ty < dh else (dh, dw) for tx, ty in march]
+
+    def flat_all():
+        """terrace 0 everywhere, one normal, every sample in front: every tap merges unless the set says otherwise (a special is not
+        to depend on which terrace or normal the fill gave its surroundings)"""
+        position[..., 2:] = 2.0
+        cur.visible_position[...] = position[ty_, tx_]
+        cur.visible_normal[...] = snorm8(SPATIAL_NORMALS[0])
+        cur.sample_position[...] = cur.visible_position[..., :3] + _f32([0.05, 0.02, 1.0])
+
+    eps = F32_EPSILON
+    if name == "depths":
+        flat_all()
+        specials = [0.0, np.nextafter(eps, _f32(0)), eps, np.nextafter(eps, _f32(1)), np.nan, np.inf, -1.0, 1e-40]
+        for k, d in enumerate(specials):                       # at a centre
+            position[under(3 + 8 * k, 2)][3] = d
+            at(3 + 8 * k, 2)
+        for k, d in enumerate(specials[4:] + [0.0]):           # at a neighbour (tap 3) and under a march step of tap 12 / 6 only
+            x, y = 8 + 12 * k, 12
+            centre(x, y)
+            n = neighbour(x, y, 3)
+            if n:
+                position[n[1]][3] = d
+            m = neighbour(x, y, n_taps - 4)
+            if m and len(m[2]) > 2:
+                position[m[2][2]][3] = d
+        ratios = [_f32(0.9), one_ulp(0.9, 0), one_ulp(0.9, 1), _f32(1.1), one_ulp(1.1, 0), one_ulp(1.1, 2)]
+        for k, q in enumerate(ratios):                         # depth / sample_depth around 0.9 and 1.1: sample_depth = 2, depth = 2 q (exact)
+            x, y = 6 + 11 * k, 24
+            centre(x, y)
+            position[under(x, y)][3] = _f32(2.0) * q
+            cur.visible_position[at(x, y)][3] = _f32(2.0) * q
+        for k in range(5):                                     # a one-texel occluder at march step k of the longest tap and of the shortest marched tap
+            for row, i in ((34, n_taps), (40, 1)):
+                x, y = 5 + 13 * k, row
+                centre(x, y)
+                n = neighbour(x, y, i)
+                if n and k < len(n[2]):
+                    position[n[2][k]][3] = 2.25
+        for k, lift in enumerate([_f32(0.00001), one_ulp(0.00001, 0), one_ulp(0.00001, 1)]):      # 1e-5 -/+ ulp above the (flat) interpolated depth
+            x, y = 60, 4 + 14 * k
+            centre(x, y)
+            n = neighbour(x, y, n_taps)
+            if n and n[2]:
+                position[n[2][0]][3] = _f32(2.0) + _f32(lift)
+        for x, y in ((66, 3), (64, 10), (1, 1), (68, 43), (0, 44), (69, 0)):     # next to the background block; the image's corners (jittered texels outside)
+            centre(x, y)
+    elif name == "records":
+        flat_all()
+        counts = [0x0000, 0x0001, f16_bits(np.nextafter(np.float16(eps), np.float16(0)).astype(np.float32)), f16_bits(eps),
+                  f16_bits(np.nextafter(np.float16(eps), np.float16(1)).astype(np.float32)), f16_bits(4.0), f16_bits(5.0), H_MAX, H_INF, H_NAN]
+        for k, bits in enumerate(counts):                       # at a neighbour (tap 2), and at the centre itself one row below
+            x, y = 4 + 7 * k, 3
+            centre(x, y)
+            n = neighbour(x, y, 2)
+            if n:
+                cur.count[n[0]] = bits
+            # ... over a zero history record (the uv far outside) and with every tap refused (the normal turned away): the merged count
+            # stays the pixel's own - below 1 for five of them, where the variance is NOT divided by the count
+            cur.count[at(4 + 7 * k, 9)] = bits
+            cur.lifetime[at(4 + 7 * k, 9)] = 0
+            cur.visible_normal[at(4 + 7 * k, 9)] = (0, 0, -127)
+            velocity[under(4 + 7 * k, 9)][:2] = 5.0
+        # merged counts against max_spatial_reuse_count: a centre of count c over a zero history record whose taps all carry count 0 but
+        # one: c + n == max, max + 1, max - 1
+        for k, extra in enumerate((0, 1, -1)):
+            x, y = 8 + 20 * k, 16
+            fx, fy = fit(x, y)
+            centre(x, y)
+            if inside(fx, fy):
+                for i in range(1, n_taps + 1):
+                    n = neighbour(x, y, i)
+                    if n:
+                        cur.count[n[0]] = 0
+                half_max = max_count // 2
+                cur.count[fy, fx] = f16_bits(float(half_max))
+                cur.lifetime[fy, fx] = 0                         # the history is asked for under every limit ...
+                velocity[under(x, y)][:2] = 5.0                 # ... and previous_uv lies far outside: a zero record
+                n = neighbour(x, y, 2)
+                if n:
+                    cur.count[n[0]] = f16_bits(float(max_count - half_max + extra))
+        for k, bits in enumerate([0, H_MAX, H_INF, H_NAN]):     # w / w_sum / w2_sum at a neighbour and at the centre
+            for j, field in enumerate(("w", "w_sum", "w2_sum")):
+                x, y = 3 + 9 * k + 3 * j, 22
+                centre(x, y)
+                getattr(cur, field)[at(x, y)] = bits
+                n = neighbour(x, y, 1)
+                if n:
+                    getattr(cur, field)[n[0]] = bits
+        for k, bits in enumerate([0, H_NZERO, H_NAN, H_MAX]):   # radiance: total_lum > 0 false, NaN, the f16 maximum
+            x, y = 40 + 7 * k, 22
+            centre(x, y)
+            cur.radiance[at(x, y)][:3] = bits
+            hist.zero(at(x, y))
+            n = neighbour(x, y, 1)
+            if n:
+                cur.radiance[n[0]][1] = bits
+        # neighbour normals around dot = 0.866 against a centre normal (0, 0, 1): (sin a, 0, cos a) quantised, the z byte one step either way
+        for k, nz in enumerate((109, 110, 111)):                # 110 / 127 = 0.8661: the bytes (63, 0, nz) normalise to a dot of 0.8679, 0.8678 ..
+            x, y = 5 + 9 * k, 28
+            centre(x, y)
+            n = neighbour(x, y, 2)
+            if n:
+                cur.visible_normal[n[0]] = (64 + k - 1, 0, 110)
+        for k, nrm in enumerate([(0, 0, 0), (0, 0, -127), (127, 0, 0), (60, 0, 112)]):      # zero (normalize(0)), anti-parallel, perpendicular, 28 degrees (a dot of 0.88: between 0.866 and 0.9)
+            x, y = 34 + 7 * k, 28
+            centre(x, y)
+            n = neighbour(x, y, 2)
+            if n:
+                cur.visible_normal[n[0]] = nrm
+            cur.visible_normal[at(34 + 7 * k, 31)] = nrm        # and at a centre
+        # the neighbour's sample against the centre's visible position: on it (a zero-length direction), in the surface plane
+        # (dot exactly 0), just in front, just behind
+        for k, off in enumerate([(0.0, 0.0, 0.0), (0.5, 0.0, 0.0), (0.5, 0.0, 1e-6), (0.5, 0.0, -1e-6)]):
+            x, y = 4 + 10 * k, 34
+            centre(x, y)
+            n = neighbour(x, y, 2)
+            if n and inside(*fit(x, y)):
+                cur.sample_position[n[0]] = cur.visible_position[at(x, y)][:3] + _f32(off)
+            cur.sample_position[at(4 + 10 * k, 37)] = cur.visible_position[at(4 + 10 * k, 37)][:3] + _f32(off)      # the centre's own sample
+        # the Jacobian: flag on / off x sample normal edge-on / averted / facing x near / far sample
+        combos = [(flag, sn, dist) for flag in (127, 0) for sn in ((127, 0, 0), (0, 0, 127), (0, 0, -127)) for dist in (0.01, 30.0)]
+        for k, (flag, sn, dist) in enumerate(combos):
+            x, y = 3 + 5 * k, 41
+            centre(x, y)
+            n = neighbour(x, y, 1)
+            if n:
+                cur.jacobian_flag[n[0]], cur.sample_normal[n[0]] = flag, sn
+                cur.sample_position[n[0]] = cur.visible_position[n[0]][:3] + _f32([0.0, 0.0, dist])
+        limit = int(max_lifetime)
+        for k, life in enumerate([max(limit - 1, 0), limit, limit + 1, 0, 1, 2, 253, 254]):      # at the centre: history taken or refused, the byte saturating on re-pack
+            cur.lifetime[at(50 + 2 * k, 9)] = life
+        for k, (code, _) in enumerate(quarter_turn_randoms(frame_number, n_taps)):                    # the tap angles nearest the quarter turns
+            x, y = 62, 14 + 8 * k
+            cur.random[at(x, y)] = (code, 0, 0, 0)
+    elif name == "history":
+        # previous_uv = jittered uv - velocity: the velocity is the pixel's own jittered uv minus the target, in f32
+        targets = [(0.0, 0), (1.0, -1), (1.0, 0), (-0.25, 0), (np.nan, 0), (np.inf, 0), (-np.inf, 0), (1e9, 0), (0.5, 0), (0.25, 0)]
+        sgn = _f32(-0.25) if frame_number % 2 == 0 else _f32(0.25)
+        jr = _f32(_f32(p.frame.upscale_ratio) - _f32(1.0))
+        for k, (target, nudge) in enumerate(targets):
+            for axis in (0, 1):
+                x, y = 3 + 6 * k, 4 + 12 * axis
+                fx, fy = fit(x, y)
+                if not inside(fx, fy):
+                    continue
+                size, coord, dsize = (rw, fx, dw) if axis == 0 else (rh, fy, dh)
+                ju = _f32(_f32(_f32(coord + 0.5) / _f32(size)) + _f32(_f32(sgn * _f32(_f32(1.0) / _f32(dsize))) * jr))
+                if np.isfinite(target):
+                    vel = _f32(ju - _f32(target))
+                    if nudge:                                    # one ulp under the target, as the shader forms it
+                        while not _f32(ju - vel) < _f32(target):
+                            vel = np.nextafter(vel, _f32(np.inf))
+                        assert _f32(ju - vel) < _f32(target)
+                else:
+                    vel = _f32(-target) if not np.isnan(target) else _f32(np.nan)
+                velocity[under(x, y)][axis] = vel
+                cur.lifetime[at(x, y)] = 0                      # the history is asked for under every lifetime limit
+        hist.zero((slice(0, rh // 3), slice(0, rw // 2)))      # a zero history record under a passing uv; the rest passes
+    elif name == "background":
+        # against the 8 x 8 wave tile and the 16 x 16 workgroup: columns 0..15 all background (one workgroup column), tiles 16..31 x
+        # 0..15 geometry, then all-background tiles with ONE geometry pixel in each corner lane, and a NaN depth as a tile's only
+        # non-background lane
+        bg = np.zeros((rh + 1, rw + 1), bool)
+        bg[:, :min(16, rw)] = True
+        bg[16:32, 32:48] = True                                 # a background workgroup in the middle, geometry around it
+        for tile_x, tile_y, (lx, ly) in ((4, 0, (0, 0)), (5, 0, (7, 0)), (4, 1, (0, 7)), (5, 1, (7, 7)), (6, 4, (3, 3))):
+            bg[8 * tile_y:8 * tile_y + 8, 8 * tile_x:8 * tile_x + 8] = True
+            if 8 * tile_y + ly < rh and 8 * tile_x + lx < rw:
+                bg[8 * tile_y + ly, 8 * tile_x + lx] = False
+                placed[8 * tile_y + ly, 8 * tile_x + lx] = True
+        for y in range(rh):
+            for x in range(rw):
+                if bg[y, x]:
+                    position[under(x, y, fitted=True)][3] = 0.0
+        if rw > 8 * 6 + 3 and rh > 8 * 4 + 3:
+            position[under(8 * 6 + 3, 8 * 4 + 3, fitted=True)][3] = np.nan
+        background[...] = False
+        cur.count[:, :min(8, rw)] = f16_bits(3.0)               # one tile column holds ONE record everywhere (the tile records' uniform case)
+        for field in vars(cur):
+            getattr(cur, field)[:, :min(8, rw)] = getattr(cur, field)[0, 0]
+    position[background, 3] = 0.0
+    if name == "terraces":      # (placed: the render pixels of the background block)
+        for y in range(rh):
+            for x in range(rw):
+                if background[under(x, y, fitted=True)]:
+                    placed[y, x] = True
+    position, instance, velocity = position[:dh, :dw], instance[:dh, :dw], velocity[:dh, :dw]
+    cur, hist, placed = cur.crop(rh, rw), hist.crop(rh, rw), placed[:rh, :rw]
+    if name == "random":
+        def some(shape, rate):
+            return rng.random(shape) < rate
+
+        for d in (0.0, np.nan, np.inf, -1.0, 1e-40, 2.25, 1.8):
+            position[some((dh, dw), 0.01), 3] = d
+        for r in (cur, hist):
+            for bits in (0, 1, H_MAX, H_INF, H_NAN, f16_bits(4.0), f16_bits(5.0), f16_bits(float(max_count))):
+                r.count[some((rh, rw), 0.01)] = bits
+            for field in (r.w, r.w_sum, r.w2_sum):
+                for bits in (0, H_MAX, H_INF, H_NAN):
+                    field[some((rh, rw), 0.005)] = bits
+            for bits in (0, H_NZERO, H_NAN, H_MAX):
+                r.radiance[some((rh, rw, 4), 0.005)] = bits
+            r.visible_normal[some((rh, rw), 0.01)] = 0
+            r.visible_normal[some((rh, rw), 0.01)] = (0, 0, -127)
+            r.lifetime[some((rh, rw), 0.03)] = 254
+            r.lifetime[some((rh, rw), 0.03)] = 7
+            m = some((rh, rw), 0.02)
+            r.sample_position[m] = r.visible_position[m][:, :3]
+        for v in (np.nan, np.inf, -np.inf, 1e9, -3.0, 0.5):
+            velocity[some((dh, dw), 0.005), int(rng.integers(2))] = v
+    p.current, p.previous_spatial, p.placed = cur, hist, placed
+    sentinel_records = np.full((dh, dw, 16), SENTINEL_U32, np.uint32)
+
+    def records_buffer(r):
+        out = sentinel_records.copy()
+        out.reshape(-1, 16)[:rw * rh] = pack_records(r).reshape(-1, 16)
+        return out
+
+    p.buffers = {F.BUF_POSITION: position, F.BUF_INSTANCE_MATERIAL: instance, F.BUF_VELOCITY_UV: velocity,
+                 p.slots["current"]: records_buffer(cur), p.slots["previous_spatial"]: records_buffer(hist),
+                 p.slots["spatial"]: sentinel_records.copy(), p.slots["previous"]: sentinel_records.copy(),
+                 F.BUF_VARIANCE0 + channel: np.full((rh, rw, 1), SENTINEL_F32, np.float32),
+                 F.BUF_RENDER0 + channel: np.full((rh, rw, 4), SENTINEL_F16, np.uint16)}
+    p.buffers = {buf: np.ascontiguousarray(a) for buf, a in p.buffers.items()}
+    return p
+
+
+def install_spatial(engine, planes, resize=True):
+    """hk_resize (if the size changed), hk_frame_begin with the planes' frame uniform, then every plane, record buffer and sentinel."""
+    size = planes.window_size + (planes.ratio,)
+    if resize and getattr(engine, "_post_planes_size", None) != size:
+        engine.resize(*size)
+        engine._post_planes_size = size
+    camera = hk.cornell_camera(*planes.window_size)
+    engine.frame_begin(planes.frame, camera.view_uniform(), camera.previous_view_uniform(None), hk.lights_uniform())
+    for buf, array in planes.buffers.items():
+        engine.write(buf, array)

@@ -9,6 +9,7 @@ corresponding dispatch and compares what the shader writes with what the oracle 
 comes from the oracle (prepass.wgsl is a raster shader; the ray-cast G-buffer is this project's contract).
 
   [HIKARI_REFERENCE_DIR=<bevy-hikari checkout>] python tests/tools/wgsl_pin.py [--size W H] [--frames N] [--write]      (minutes of pure Python)
+  ... --planes | --aa-planes | --spatial-planes [--write]      the synthetic planes of tests/post_planes.py (the fixtures of the plane suites)
 
 --write stores the inputs and the shader-produced outputs of every dispatch under tests/golden/wgsl_pin.npz, which
 tests/test_wgsl_pin.py replays against the oracle without the reference."""
@@ -299,6 +300,14 @@ class Pinner:
                    previous_spatial_reservoir_buffer=cur + S_SLOT[channel], spatial_reservoir_buffer=prev + S_SLOT[channel])
         return {k: F.BUF_RESERVOIR0 + v for k, v in ids.items()}
 
+    def spatial_texel(self, x, y, rw, rh, dw, dh):
+        """jittered_deferred_coords(coords_to_uv) of a render pixel (light.wgsl:1007-1017), in f32"""
+        sgn = f32(-0.25) if self.frame.number % 2 == 0 else f32(0.25)
+        ratio = f32(f32(self.frame.upscale_ratio) - f32(1.0))
+        u = f32(f32(f32(x + 0.5) / f32(rw)) + f32(f32(sgn * f32(f32(1.0) / f32(dw))) * ratio))
+        v = f32(f32(f32(y + 0.5) / f32(rh)) + f32(f32(sgn * f32(f32(1.0) / f32(dh))) * ratio))
+        return int(f32(u * f32(dw))), int(f32(v * f32(dh)))
+
     def light_pass(self, pass_id):
         e = self.e
         entry, defs, channel = LIGHT[pass_id]
@@ -340,6 +349,15 @@ class Pinner:
         # racing with their owners.  The oracle and the library guard instead; the pin runs the guarded grid.
         m.dispatch(entry, gx, gy, limit=None if self.unguarded else ((w, h) if entry == "full_screen_albedo" else (rw, rh)))
         seconds = time.time() - t0
+        if entry == "spatial_reuse":
+            # the contract's rule for what spatial_reuse stores ("Spatial reuse on adversarial planes"): the colour and
+            # the four statistics a geometry pixel computed leave as the quiet NaN where they are one - numpy has its own signs
+            canonical_nans(render)
+            stats = res_bytes["spatial_reservoir_buffer"][:rw * rh * 64].view(np.uint16).reshape(rh, rw, 32)[..., 28:]
+            position = e.read(F.BUF_POSITION)
+            depth = np.array([[position[self.spatial_texel(x, y, rw, rh, w, h)[::-1]][3] for x in range(rw)] for y in range(rh)], np.float32)
+            with np.errstate(invalid="ignore"):
+                stats[((stats & 0x7FFF) > 0x7C00) & ~(depth < f32(1.1920929e-7))[..., None]] = 0x7E00
         self.real_pass_run(pass_id)                 # now the oracle
         bad = {}
         # every writable resource of the bind groups is compared, also the ones this entry point is not expected to touch
@@ -488,6 +506,53 @@ def run_aa_planes(name, setting, render_size=(24, 16), frame_number=3, seed=7, l
     return pin.results
 
 
+def run_spatial_planes(name, channel, ratio=1.0, frame_number=3, max_count=100, max_lifetime=7.0, render_size=(24, 16), seed=7, log=None):
+    """One spatial_reuse dispatch of light.wgsl (with EMISSIVE_LIT for channel 1, without for channel 2) on the synthetic planes of
+    tests/post_planes.py (`make_spatial_planes`, compact), on the state the oracle has before it.  Returns the per-dispatch records;
+    what the shader wrote - `spatial`, `variance`, `render` - is in run_spatial_planes.recorded."""
+    import post_planes as PP
+
+    p = oracle_plugin()
+    dll = p.engine.api.dll
+    dll.orc_debug_math.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]
+
+    def contract(op, x, y):
+        key = (op, float(x), float(y))
+        if key not in _contract_cache:
+            xi, yi, out = (C.c_float * 1)(float(x)), (C.c_float * 1)(float(y)), (C.c_float * 1)()
+            assert dll.orc_debug_math(None, op, xi, yi, out, 1) == 0
+            _contract_cache[key] = f32(out[0])
+        return _contract_cache[key]
+
+    R.bind_contract(contract)
+    scene = PP.spatial_scene()
+    p.set_scene(scene)
+    planes = PP.make_spatial_planes(name, seed, render_size, ratio, channel, frame_number, max_count, max_lifetime, compact=True)
+    pin = Pinner(p, scene, load_noise_planes(), log or (lambda rec: None))
+    pin.settings, pin.patch = planes.settings, None
+    camera = hk.cornell_camera(*planes.window_size)
+    pin.begin(planes.frame, camera.view_uniform(), camera.previous_view_uniform(None), hk.lights_uniform())
+    PP.install_spatial(p.engine, planes)
+    p.engine.pass_run(planes.pass_id)
+    keep = {planes.outputs["spatial"], planes.outputs["variance"], planes.outputs["render"]}
+    run_spatial_planes.recorded = {k: v for k, v in pin.recorded.items() if int(k.split("buf")[1]) in keep}
+    return pin.results
+
+
+def load_noise_planes():
+    from bevy_hikari_amd.plugin import load_noise
+    return load_noise().reshape(16, 64, 64, 4)
+
+
+#: (set, channel, ratio, frame number, max_spatial_reuse_count, max_reservoir_lifetime): one per set; both channels, ratios 1.0 and 1.5, both parities
+SPATIAL_PLANES_FIXTURES = [("terraces", 2, 1.0, 2, 100, 7.0), ("depths", 2, 1.5, 3, 800, 0.0), ("records", 1, 1.0, 3, 4, 7.0), ("history", 1, 1.5, 2, 100, 1.0),
+                           ("background", 2, 1.0, 3, 100, 7.0), ("random", 2, 1.5, 2, 4, 7.0), ("records", 2, 1.5, 2, 100, 7.0)]
+
+
+def spatial_planes_fixture_path(name, channel, ratio, frame_number, max_count, max_lifetime):
+    return os.path.join(ROOT, "tests", "golden", f"wgsl_spatial_planes_{name}_ch{channel}_r{int(ratio * 10)}_f{frame_number}_m{max_count}_l{int(max_lifetime)}.npz")
+
+
 def _dilate(mask, n):
     out = mask.copy()
     for _ in range(n):
@@ -515,6 +580,16 @@ def planes_fixture_path(name, render_size, ratio, frame_number):
 
 
 def main():
+    if "--spatial-planes" in sys.argv:  # [--write]: the fixtures tests/test_spatial_planes*.py replay
+        for case in SPATIAL_PLANES_FIXTURES:
+            results = run_spatial_planes(*case, log=lambda rec: print(json.dumps(rec), flush=True))
+            bad = [r for r in results if r["mismatch"]]
+            if "--write" in sys.argv:
+                assert not bad
+                np.savez_compressed(spatial_planes_fixture_path(*case), **run_spatial_planes.recorded)
+                print("wrote", spatial_planes_fixture_path(*case), os.path.getsize(spatial_planes_fixture_path(*case)), "bytes")
+            print(json.dumps({"spatial_planes": case, "dispatches": len(results), "mismatching": len(bad)}))
+        return
     if "--aa-planes" in sys.argv:       # [--write]: the fixtures tests/test_aa_planes*.py replay
         for case in AA_PLANES_FIXTURES:
             results = run_aa_planes(*case, log=lambda rec: print(json.dumps(rec), flush=True))
