@@ -157,7 +157,9 @@ int free_screen(hk_ctx* c) {
   for (int k = 0; k < 2; ++k) {
     if (c->empty_tiles[k]) (void)hipFree(c->empty_tiles[k]);
     c->empty_tiles[k] = nullptr;
-    c->empty_ok[k] = c->lights_ok[k] = false;
+    if (c->kept_tiles[k]) (void)hipFree(c->kept_tiles[k]);
+    c->kept_tiles[k] = nullptr;
+    c->empty_ok[k] = c->lights_ok[k] = c->kept_ok[k] = c->kept_lights[k] = false;
   }
   c->pixel_identity = false;
   if (c->wf_mem) (void)hipFree(c->wf_mem);
@@ -282,6 +284,7 @@ GBuffer make_gbuffer(const hk_ctx* c) {
   g.albedo_out = nullptr;
   g.empty_out = nullptr;
   g.empty_in = nullptr;
+  g.kept_out = nullptr;
   g.tiles_x = c->tiles_x;
   return g;
 }
@@ -305,7 +308,39 @@ const uint8_t* known_empty_plane(hk_ctx* c, int y0, int y1, bool demodulation = 
   c->empty_plane_launches += 1;
   return c->empty_tiles[p];
 }
-void forget_empty_tiles(hk_ctx* c) { c->empty_ok[0] = c->empty_ok[1] = c->lights_ok[0] = c->lights_ok[1] = false; }
+void forget_empty_tiles(hk_ctx* c) {
+  for (int k = 0; k < 2; ++k) c->empty_ok[k] = c->lights_ok[k] = c->kept_ok[k] = c->kept_lights[k] = false;
+}
+// Background stores (hk_context.hpp kept_tiles): a wave of an empty tile may skip a store only if the launch that last wrote that
+// PHYSICAL plane stored the background's constant to the tile and nothing has written the plane since.  The G-buffer planes and their
+// derived planes, render / variance are mapped by frame parity (hk_frame_begin), so their last writer is the last frame of THIS parity;
+// the byte it left in empty_tiles[parity] is what this frame's primary rays find there.  That byte may be trusted iff empty_ok[parity]
+// still holds when the stage begins (`had_plane`: taken before the stage clears it) - it says that those primary rays ran through
+// hk_frame_stage over the whole image at ratio 1, one band, certified pixel identity, and that no hk_write_buffer / hk_device_ptr,
+// hand-driven hk_pass_run, hk_resize or switch of HK_DEBUG_OPT_KNOWN_RESULTS came since (forget_empty_tiles, free_screen); hk_frame_stage
+// itself forgets both parities on a host-rasterised G-buffer, a ratio other than 1 and a band count other than 1 - and iff every plane
+// has its twin (without a post stream some planes are written by every frame), these rays write their own plane (`write_plane`), and
+// the context neither counts rays nor has a communicator attached.
+// `lights`: that frame's three light passes ran over every row through hk_frame_stage as well (every writer of variance / render - the
+// fused kernels, the queue-based indirect schedule, the spatial passes - stores 0 to a background pixel), so the light kernels of this
+// frame may skip those stores in kept tiles.  Whatever this cannot prove takes the long way.
+#ifndef HK_KEPT_LIGHTS
+#define HK_KEPT_LIGHTS 1   // (A/B: 0 = the primary rays alone skip their stores)
+#endif
+bool kept_grant(hk_ctx* c, bool had_plane, bool write_plane, bool* lights) {
+  const uint32_t p = c->mapped_parity & 1u;
+  const bool twins = c->albedo_twin && c->depth_gradient_twin && c->dn_g_twin && c->normal_twin && c->instance_material_twin && c->render_twin[0] && c->variance_twin[0];
+  // (the ray-counting replays store everything; with a communicator attached exchanges, gathers and hk_debug_comm_loopback write planes)
+  const bool grant = had_plane && write_plane && twins && c->kept_tiles[p] && !(c->flags & HK_CTX_COUNT_RAYS) && !c->comm;
+  *lights = HK_KEPT_LIGHTS && grant && c->lights_ok[p] && c->lights_frame[p] == c->empty_frame[p];
+  return grant;
+}
+// ... and the plane for a fused light launch that was handed this frame's empty-tile plane (known_empty_plane): the kept-tile plane - the
+// same bytes plus HK_TILE_KEPT - where the grant covers the light planes, the empty-tile plane itself otherwise
+const uint8_t* kept_plane_for_lights(hk_ctx* c, const uint8_t* empty_in) {
+  const uint32_t p = c->mapped_parity & 1u;
+  return empty_in && c->kept_ok[p] && c->kept_lights[p] && c->kept_frame[p] == c->frame.number ? c->kept_tiles[p] : empty_in;
+}
 // A band of a sharded frame whose history halo is not empty parks the scatter stores of its temporal dispatches instead of
 // racing them into its local copy of previous_spatial: the neighbours need them (and this band theirs) before spatial_reuse
 bool parks_across_bands(const hk_ctx* c) { return c->band_count > 1 && c->history_now > 0; }
@@ -808,6 +843,7 @@ int run_pass(hk_ctx* c, uint32_t pass, uint32_t arg, int y0, int y1) {
   const bool fused_light = pass == HK_PASS_DIRECT_LIT || pass == HK_PASS_DIRECT_EMISSIVE || (pass == HK_PASS_INDIRECT && !use_wavefront(c)) ||
                            pass == HK_PASS_EMISSIVE_SPATIAL_REUSE || pass == HK_PASS_INDIRECT_SPATIAL_REUSE;
   if (fused_light) g.empty_in = known_empty_plane(c, y0, y1);
+  g.empty_in = kept_plane_for_lights(c, g.empty_in);
   // (the two long dispatches of a frame carry their events ON the dispatch - hipExtLaunchKernelGGL - so that timing them inside a
   // pipelined frame adds no stream operation; every other pass is bracketed by two records)
   ScopedTimer timer(c, pass, pass == HK_PASS_INDIRECT || pass == HK_PASS_INDIRECT_SPATIAL_REUSE || pass == HK_PASS_EMISSIVE_SPATIAL_REUSE);
@@ -1206,6 +1242,8 @@ static int resize_resources(hk_ctx* c, uint32_t width, uint32_t height, float up
     for (int k = 0; k < 2; ++k) {
       HK_HIP(hipMalloc((void**)&c->empty_tiles[k], (size_t)c->tiles_x * c->tiles_y));
       HK_HIP(hipMemset(c->empty_tiles[k], 0, (size_t)c->tiles_x * c->tiles_y));
+      HK_HIP(hipMalloc((void**)&c->kept_tiles[k], (size_t)c->tiles_x * c->tiles_y));
+      HK_HIP(hipMemset(c->kept_tiles[k], 0, (size_t)c->tiles_x * c->tiles_y));
     }
   }
   HK_HIP(hipMalloc((void**)&c->depth_plane, nf * 4));
@@ -1343,6 +1381,7 @@ int hk_set_band(hk_ctx* c, uint32_t band_index, uint32_t band_count) {
     c->band_bounds.clear();
     c->bounds_generation += 1;
   }
+  if (band_count != c->band_count) forget_empty_tiles(c);   // (kept_grant: other rows of the planes are this context's to write now)
   c->band_index = band_index;
   c->band_count = band_count;
   return HK_OK;
@@ -1530,10 +1569,15 @@ int hk_frame_stage(hk_ctx* c, uint32_t stage, const HkSettings* st, uint32_t fla
     if (c->timing_mask) (void)hipEventRecord(c->frame_start, c->stream);
     // the empty-tile plane of this parity: whatever it held is about to be out of date; these primary rays write it again where every
     // launch that could be handed it would qualify (known_empty_plane) and the rays cover the whole image
-    c->empty_ok[parity] = c->lights_ok[parity] = false;
+    // (background stores - kept_grant: a frame whose planes the host rasterised, a ratio other than 1, a band among several ends every grant)
+    if ((flags & HK_FRAME_EXTERNAL_GBUFFER) || c->frame.upscale_ratio != 1.0f || c->band_count != 1) forget_empty_tiles(c);
+    const bool had_plane = c->empty_ok[parity];
     const bool write_plane = c->known_results && c->empty_tiles[parity] && c->pixel_identity && c->frame.upscale_ratio == 1.0f && c->band_count == 1 &&
                              !(flags & HK_FRAME_EXTERNAL_GBUFFER) && !c->derived_dirty && !c->host_wrote && f0 == 0 && f1 == c->H;
     c->host_wrote = false;
+    bool keep_lights = false;
+    const bool keep = kept_grant(c, had_plane, write_plane, &keep_lights);
+    c->empty_ok[parity] = c->lights_ok[parity] = c->kept_ok[parity] = c->kept_lights[parity] = false;
     if (!(flags & HK_FRAME_EXTERNAL_GBUFFER)) {
       if (f1 > f0) {  // the prepass also fills the albedo of every pixel it covers (a superset of the rows albedo needs)
         const DFrame fr = make_dframe(c);
@@ -1543,6 +1587,12 @@ int hk_frame_stage(hk_ctx* c, uint32_t stage, const HkSettings* st, uint32_t fla
           g.empty_out = c->empty_tiles[parity];
           c->empty_ok[parity] = true;
           c->empty_frame[parity] = c->frame.number;
+          if (keep) {  // (the tile's old byte can be trusted: tiles that stay empty keep what they hold)
+            g.kept_out = c->kept_tiles[parity];
+            c->kept_ok[parity] = true;
+            c->kept_lights[parity] = keep_lights;
+            c->kept_frame[parity] = c->frame.number;
+          }
         }
         unsigned long long* counters = (c->flags & HK_CTX_COUNT_RAYS) ? c->d_counters : nullptr;
         const Jitter j = prepass_jitter(c);
@@ -1920,6 +1970,7 @@ int hk_device_ptr(hk_ctx* c, uint32_t buffer, void** ptr, size_t* bytes) {
   *ptr = c->buf[buffer];
   // (a plane the empty-tile shortcuts vouch for, about to be in the host's hands: as hk_write_buffer - hikari_hip.h)
   if (buffer == HK_BUF_POSITION || buffer == HK_BUF_NORMAL || buffer == HK_BUF_DEPTH_GRADIENT || buffer == HK_BUF_INSTANCE_MATERIAL || buffer == HK_BUF_VELOCITY_UV ||
+      buffer == HK_BUF_PREVIOUS_POSITION || buffer == HK_BUF_PREVIOUS_VELOCITY_UV ||   // (the next frame's planes: its primary rays may keep what their empty tiles hold)
       buffer == HK_BUF_ALBEDO || (buffer >= HK_BUF_VARIANCE0 && buffer < HK_BUF_VARIANCE0 + 3) || (buffer >= HK_BUF_RENDER0 && buffer < HK_BUF_RENDER0 + 3)) {
     forget_empty_tiles(c);
     c->host_wrote = true;

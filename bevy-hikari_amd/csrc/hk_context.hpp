@@ -244,6 +244,15 @@ struct hk_ctx {
   uint8_t* empty_tiles[2] = {nullptr, nullptr};
   bool empty_ok[2] = {false, false}, lights_ok[2] = {false, false};
   uint32_t empty_frame[2] = {0, 0}, lights_frame[2] = {0, 0};
+  // Background stores (DESIGN 4 "Empty tiles"): a second byte per tile and parity, written by the same primary rays - the empty-tile byte
+  // plus HK_TILE_KEPT where the tile was empty in the frame that last wrote the parity's physical planes too, whose byte the rays found
+  // in empty_tiles.  Such a wave skips the stores that would rewrite the background's constants.  kept_ok: the plane was written by frame
+  // kept_frame's primary rays (they skipped the G-buffer's stores); kept_lights: that earlier frame's light passes had stored their
+  // constants too, so this frame's may skip variance / render (context.hip kept_grant, kept_plane_for_lights).  Cleared with empty_ok
+  // by everything that clears it.
+  uint8_t* kept_tiles[2] = {nullptr, nullptr};
+  bool kept_ok[2] = {false, false}, kept_lights[2] = {false, false};
+  uint32_t kept_frame[2] = {0, 0};
   bool pixel_identity = false;           // at ratio 1 the kernels' coordinate chains map every pixel to itself (certify_pixel_identity, per hk_resize)
   bool host_wrote = false;               // hk_write_buffer since the last primary rays: the next frame keeps today's path
   bool in_frame_stage = false;           // hk_frame_stage is launching (hk_pass_run's hand-driven passes never get the plane)

@@ -25,6 +25,12 @@ struct GBuffer {
   // null where the context cannot vouch for the plane (context.hip known_empty_plane)
   uint8_t* empty_out;
   const uint8_t* empty_in;
+  // the kept-tile plane of the same parity (DESIGN 4 "Empty tiles"): the empty-tile byte (HK_TILE_EMPTY) plus HK_TILE_KEPT where the tile
+  // was empty in the frame that last wrote these physical planes too - the byte k_prepass finds in empty_out before it overwrites it.
+  // kept_out non-null says that the old byte may be trusted (context.hip kept_grant): the miss branch of a kept tile stores nothing,
+  // every plane holds the background's constants already.  A light kernel whose own planes of this parity are in the same state is
+  // handed this plane as its empty_in (otherwise the empty-tile plane, which never carries the bit) and skips its constant stores
+  uint8_t* kept_out;
   int tiles_x;
 };
 // Uniform-tile store elision.  The reference stores a packed reservoir to up to three buffers for EVERY pixel of EVERY light
@@ -248,11 +254,15 @@ __device__ __forceinline__ int wave_tile(const Pixel& px, int tiles_x) {
 }
 // the empty-tile plane: is the 8x8 tile of this wave (pixel_of_thread; called by its valid lanes only - their tile lies in the image) one
 // whose primary rays all missed this frame?  Wave-uniform, and known to be: the byte is read through the first lane.
-__device__ __forceinline__ bool wave_tile_known_empty(const uint8_t* __restrict__ plane, const Pixel& px, int tiles_x) {
-  if (!plane) return false;
+// The byte itself: 0 = not known to be empty (or no plane), HK_TILE_EMPTY = empty, HK_TILE_EMPTY | HK_TILE_KEPT = empty and kept (GBuffer).
+#define HK_TILE_EMPTY 1
+#define HK_TILE_KEPT 2
+__device__ __forceinline__ int wave_tile_state(const uint8_t* __restrict__ plane, const Pixel& px, int tiles_x) {
+  if (!plane) return 0;
   const int tile = __builtin_amdgcn_readfirstlane(wave_tile(px, tiles_x));
-  return __builtin_amdgcn_readfirstlane((int)plane[tile]) != 0;
+  return __builtin_amdgcn_readfirstlane((int)plane[tile]);
 }
+__device__ __forceinline__ bool wave_tile_known_empty(const uint8_t* __restrict__ plane, const Pixel& px, int tiles_x) { return wave_tile_state(plane, px, tiles_x) != 0; }
 // ... and for the row-shaped waves of the stencil kernels (pixel_of_thread_rows): do this pixel and its neighbours up to `reach` pixels
 // away that lie in the image (reach <= 8: the four corners of the window name every tile it touches) all lie in empty tiles?  Per lane
 // (a wave is one row of 64 pixels there: y and with it the two tile rows are wave-uniform and kept in scalar registers)

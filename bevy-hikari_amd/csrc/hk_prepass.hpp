@@ -54,8 +54,12 @@ __device__ __forceinline__ Ray primary_ray(const DFrame& fr, const PrepassParams
 
 
 // the pixel's G-buffer record (and albedo, when the dispatch also fills it) from the closest hit of its primary ray
-__device__ __forceinline__ void prepass_store(const DScene& sc, const DFrame& fr, const PrepassParams& pp, const GBuffer& g, int x, int y, const Ray& ray, const Hit& hit) {
+// `kept` (wave-uniform, k_prepass): every ray of the tile missed, as in the frame that last wrote these planes - they hold the miss
+// branch's constants already, nothing is stored
+__device__ __forceinline__ void prepass_store(const DScene& sc, const DFrame& fr, const PrepassParams& pp, const GBuffer& g, int x, int y, const Ray& ray, const Hit& hit,
+                                              bool kept) {
   const int idx = x + fr.dw * y;
+  if (kept) return;
   if (hit.instance_index == HK_U32_MAX) {
     g.position[idx] = make_float4(0, 0, 0, 0);
     g.normal[idx] = 0u;

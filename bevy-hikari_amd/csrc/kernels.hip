@@ -103,6 +103,10 @@ __global__ __launch_bounds__(256, (LDS == 4 ? HK_PREPASS_WIDE_WAVES : (LDS == 2 
   uint32_t primary = 0;
   __shared__ uint32_t wide_lds[LDS == 4 ? HK_WIDE_LDS_STACK * 256u : 1u];
   if (px.valid) {
+    // the tile's byte of the frame that last wrote these planes, ahead of the walk (one scalar; g.kept_out: the context vouches for it.
+    // The ray-counting replays keep every store: context.hip kept_grant hands them no plane)
+    const int tile = __builtin_amdgcn_readfirstlane(wave_tile(px, g.tiles_x));
+    const bool was_empty = !COUNT && g.kept_out && __builtin_amdgcn_readfirstlane((int)g.empty_out[tile]) != 0;
     Ray ray = primary_ray(fr, pp, (float)px.x, (float)px.y);
     Hit hit;
 #pragma unroll 1
@@ -120,11 +124,16 @@ __global__ __launch_bounds__(256, (LDS == 4 ? HK_PREPASS_WIDE_WAVES : (LDS == 2 
     rc.tlas = 0;  // counted as a primary ray
     primary = 1;
     rc.hits += hit.instance_index != HK_U32_MAX ? 1u : 0u;
+    bool kept = false;  // (wave-uniform: the tile was empty before and is again - its planes hold the background's constants already)
     if (g.empty_out) {  // the empty-tile plane (hk_kernels.hpp GBuffer): did every primary ray of the wave's tile - its pixels inside the image - miss?
       const bool all_missed = __ballot(hit.instance_index != HK_U32_MAX) == 0ull;   // (ahead of the stores: nothing of it stays live across them)
-      if (wave_leader()) g.empty_out[wave_tile(px, g.tiles_x)] = all_missed ? (uint8_t)1 : (uint8_t)0;
+      kept = was_empty && all_missed;
+      if (wave_leader()) {
+        g.empty_out[tile] = all_missed ? (uint8_t)1 : (uint8_t)0;
+        if (!COUNT && g.kept_out) g.kept_out[tile] = (uint8_t)(all_missed ? (kept ? HK_TILE_EMPTY | HK_TILE_KEPT : HK_TILE_EMPTY) : 0);
+      }
     }
-    prepass_store(sc, fr, pp, g, px.x, px.y, ray, hit);
+    prepass_store(sc, fr, pp, g, px.x, px.y, ray, hit, kept);
   }
   flush_counters<COUNT>(rc, primary, counters);
 }
@@ -179,7 +188,8 @@ __global__ __launch_bounds__(256, (LDS == 0 ? HK_DIRECT_GLOBAL_WAVES : (LDS == 2
     f2 uv = F2(0.0f, 0.0f);
     int dcx = 0, dcy = 0;
     float4 position_depth = make_float4(0, 0, 0, 0);
-    if (!wave_tile_known_empty(g.empty_in, px, g.tiles_x)) {
+    const int tile_state = wave_tile_state(g.empty_in, px, g.tiles_x);
+    if (!tile_state) {
       uv = coords_to_uv(fr, x, y);
       jittered_deferred_coords(fr, uv, &dcx, &dcy);
       if (in_bounds(dcx, dcy, fr.dw, fr.dh)) position_depth = g.position[dcx + fr.dw * dcy];
@@ -194,8 +204,10 @@ __global__ __launch_bounds__(256, (LDS == 0 ? HK_DIRECT_GLOBAL_WAVES : (LDS == 2
       out = pack_reservoir(r);
       write_current = true;
       background = true;
-      t.variance[index] = 0.0f;
-      t.render[index] = make_uint2(0u, 0u);
+      if (!(tile_state & HK_TILE_KEPT)) {  // (a kept tile: both planes hold these constants already - hk_kernels.hpp GBuffer)
+        t.variance[index] = 0.0f;
+        t.render[index] = make_uint2(0u, 0u);
+      }
     } else {
       const f3 normal = xyz(unpack4x8snorm(g.normal[didx]));
       const float2 imf = g.instance_material[didx];
@@ -516,6 +528,8 @@ __global__ __launch_bounds__(256, (LDS == 2 && MULTIPLE_BOUNCES ? HK_INDIRECT_FL
       if (!skip_current) store_packed(t.current, index, pr);
       if (!skip_spatial) store_packed(t.spatial, index, pr);
       if (!skip_previous_spatial) store_previous_spatial(t, index, index, pr);
+      // (a kept tile - hk_kernels.hpp GBuffer - stores these all the same here: with the bit test the headline instantiation spills 8 more
+      // VGPRs, 76 -> 92 B of scratch per lane)
       t.variance[index] = 0.0f;
       t.render[index] = make_uint2(0u, 0u);
     } else {
@@ -763,7 +777,8 @@ __global__ __launch_bounds__(256, HK_SPATIAL_WGS) void k_spatial_reuse(DScene sc
   int dcx = 0, dcy = 0;
   float4 position_depth = make_float4(0, 0, 0, 0);
   // (a tile the primary rays proved empty, as in k_direct_lit; the plain form only - every lane here is a valid pixel of the wave's tile)
-  if (WINDOWED || !wave_tile_known_empty(g.empty_in, px, g.tiles_x)) {
+  const int tile_state = WINDOWED ? 0 : wave_tile_state(g.empty_in, px, g.tiles_x);
+  if (!tile_state) {
     uv = coords_to_uv(fr, x, y);
     jittered_deferred_coords(fr, uv, &dcx, &dcy);
     if (in_bounds(dcx, dcy, fr.dw, fr.dh) && px.valid) position_depth = g.position[dcx + fr.dw * dcy];  // (px.valid: always, in the plain form)
@@ -796,6 +811,7 @@ __global__ __launch_bounds__(256, HK_SPATIAL_WGS) void k_spatial_reuse(DScene sc
   const bool background = depth < HK_F32_EPSILON;
   const bool all_background = __ballot(!background) == 0ull;  // among the wave's valid pixels
   const int tile = wave_tile(px, t.tiles_x);
+  const bool tile_kept = (tile_state & HK_TILE_KEPT) != 0;  // (hk_kernels.hpp GBuffer: the render plane holds the background's zero already)
   unsigned long long input_id = 0ull;
   if (t.m_current && all_background) {
     const TileMeta in = t.m_current[tile];
@@ -803,7 +819,7 @@ __global__ __launch_bounds__(256, HK_SPATIAL_WGS) void k_spatial_reuse(DScene sc
       input_id = in.id;
       const TileMeta have = t.m_spatial[tile];
       if (have.valid > have.poison && have.src == input_id) {
-        t.render[index] = make_uint2(0u, 0u);
+        if (!tile_kept) t.render[index] = make_uint2(0u, 0u);
         return;
       }
     }
@@ -816,7 +832,7 @@ __global__ __launch_bounds__(256, HK_SPATIAL_WGS) void k_spatial_reuse(DScene sc
       if (all_background && input_id != 0ull) tile_mark(t.m_spatial, tile, record_id(pr), input_id, t.serial);
       else tile_unknown(t.m_spatial, tile);
     }
-    t.render[index] = make_uint2(0u, 0u);
+    if (!tile_kept) t.render[index] = make_uint2(0u, 0u);
     return;
   }
   const uint32_t im_y = f32_to_u32(g.instance_material[didx].y);

@@ -1128,6 +1128,10 @@ int hk_write_buffer(hk_ctx* ctx, uint32_t buffer, const void* src, size_t bytes)
  * HK_FRAME_EXTERNAL_GBUFFER for the G-buffer): between two hk_frame_stage calls of one frame the library may rely on what the stages
  * before wrote there (the empty-tile plane of the primary rays).  Asking for the pointer of one of those ids makes the frame in
  * progress and the next one take no such shortcut; a pointer kept for longer is the host's to use by this rule.
+ * The library no longer rewrites what a plane already holds: where a tile had no geometry in the last frame of the same parity and has
+ * none again, the G-buffer, albedo, render and variance planes keep the background's constants that frame stored.  So a host that
+ * writes one of them (the PREVIOUS ids included) through a pointer it kept, outside a HK_FRAME_EXTERNAL_GBUFFER frame, asks for the
+ * pointer again after writing, or uses hk_write_buffer: either makes the following frames store every pixel again.
  * Asking for HK_BUF_PREVIOUS_POSITION makes the next anti-aliasing dispatch copy that plane's depths again (as after
  * hk_write_buffer); a host that writes it through a pointer it kept asks again after writing, or uses hk_write_buffer. */
 int hk_device_ptr(hk_ctx* ctx, uint32_t buffer, void** ptr, size_t* bytes);

@@ -129,7 +129,7 @@ int hk_debug_comm_lanes(hk_ctx* ctx, uint32_t* lanes);
 #define HK_DEBUG_OPT_PREPASS_PIPELINE 10u /* a frame's primary rays on a stream of their own beside the previous frame's spatial pass, where the order allows (context.hip stage TEMPORAL): -1 by the library's rule (default: scenes beyond the LDS copy in frames of up to 3 Mi pixels, on a context whose chain runs at the highest priority), 0 never, 1 whenever the order allows */
 #define HK_DEBUG_OPT_LOAD_DEVICE_LIMIT 12u /* hk_load_scene completes a deferred mesh of more than this many triangles on the host instead of the device (default 0: HK_MESH_REBUILD_MAX_TRIANGLES); tests reach that path without a mesh of four million triangles */
 #define HK_DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP 11u /* 1: hk_rebuild_mesh_tree (HK_TREE_SAH) runs the top levels of its build in one workgroup at any mesh size, as the instance tree's build does (default 0: on the whole chip from 32 768 triangles); the same tree either way - the A/B of tools/deform_probe.py */
-#define HK_DEBUG_OPT_KNOWN_RESULTS 13u /* 0: no launch is handed the empty-tile plane of the frame's primary rays - every wave computes its way to the background constants (default 1; the A/B and tests/test_known_results_gpu.py) */
+#define HK_DEBUG_OPT_KNOWN_RESULTS 13u /* 0: no launch is handed the empty-tile plane of the frame's primary rays - every wave computes its way to the background constants, and stores them whatever the planes hold (default 1; the A/B, tests/test_known_results_gpu.py and tests/test_background_stores_gpu.py) */
 int hk_debug_set_option(hk_ctx* ctx, uint32_t option, int64_t value);
 /* Test hook of the empty-tile plane (one byte per 8x8 tile of the render image, row-major, (w + 7) / 8 x (h + 7) / 8; 1 = every primary
  * ray of the tile missed): waits for the context's work, copies the plane of the current frame parity into out_bytes (n = the number of
