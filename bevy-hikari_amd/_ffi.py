@@ -64,6 +64,7 @@ PRESENT_HDR, PRESENT_CLEAR = 1, 2
 RAYS_CLOSEST, RAYS_ANY, RAYS_ATTRIBUTES, RAYS_STACKLESS = 0, 1, 2, 4  # hk_cast_rays flags
 RAY_MISS, RAY_HIT, RAY_INVALID = 0, 1, 2                              # HkRayHit.status
 DEFORM_VERTICES, DEFORM_SKIN = 0, 1                                   # HkMeshDeform.kind
+DEFORM_RECOMPUTE_NORMALS = 1                                          # HkMeshDeformDevice.flags
 NO_INSTANCE = 0xFFFFFFFF                                              # HkRay.exclude_instance "nothing"; HkRayHit.instance / primitive of a miss
 
 f32, u32, u64 = C.c_float, C.c_uint32, C.c_uint64
@@ -162,6 +163,11 @@ class HkMeshDeform(C.Structure):
     _fields_ = [("mesh", HkMeshIndex), ("kind", u32), ("count", u32), ("data", C.POINTER(f32)), ("normals", C.POINTER(f32))]
 
 
+class HkMeshDeformDevice(C.Structure):
+    _fields_ = [("mesh", HkMeshIndex), ("kind", u32), ("count", u32), ("data", C.c_void_p), ("normals", C.c_void_p),
+                ("data_stride", u32), ("normals_stride", u32), ("flags", u32), ("_pad", u32)]
+
+
 class HkHaloOp(C.Structure):
     _fields_ = [("buffer", u32), ("peer", u32), ("row_begin", u32), ("row_end", u32), ("row_bytes", u64)]
 
@@ -186,7 +192,7 @@ class HkStats(C.Structure):
 assert C.sizeof(HkVertex) == 32 and C.sizeof(HkPrimitive) == 48 and C.sizeof(HkNode) == 32 and C.sizeof(HkInstance) == 176
 assert C.sizeof(HkMaterial) == 80 and C.sizeof(HkEmissive) == 64 and C.sizeof(HkFrame) == 256 and C.sizeof(HkView) == 416
 assert C.sizeof(HkPreviousView) == 128 and C.sizeof(HkAliasEntry) == 8
-assert C.sizeof(HkRay) == 32 and C.sizeof(HkRayHit) == 48 and C.sizeof(HkMeshDeform) == 40
+assert C.sizeof(HkRay) == 32 and C.sizeof(HkRayHit) == 48 and C.sizeof(HkMeshDeform) == 40 and C.sizeof(HkMeshDeformDevice) == 56
 
 
 class HikariError(RuntimeError):
@@ -281,6 +287,7 @@ _PRODUCT_ONLY = {
     "scene_builder_emissive_nodes": [_vp, P(P(HkNode)), P(u32)],
     "scene_builder_alias_table": [_vp, P(P(HkAliasEntry)), P(u32)],
     "scene_builder_set_mesh_vertices": [_vp, u32, P(f32), P(f32)],
+    "scene_builder_recompute_mesh_normals": [_vp, u32],
     "scene_builder_rebuild_mesh_tree": [_vp, u32],
     "scene_builder_mesh_index": [_vp, u32, P(HkMeshIndex)],
     "upload_scene": [_vp, _vp],
@@ -296,6 +303,7 @@ _PRODUCT_ONLY = {
     "set_mesh_skin": [_vp, P(HkMeshIndex), u32, P(f32), P(f32), P(C.c_uint16), P(f32)],
     "skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],
     "deform_meshes": [_vp, P(HkMeshDeform), u32],
+    "deform_meshes_device": [_vp, P(HkMeshDeformDevice), u32, _vp],
     "rebuild_mesh_tree": [_vp, P(HkMeshIndex), u32],
     "present": [_vp, P(HkSettings), u32, P(HkPresentTarget), u32, u32],
     "cast_rays": [_vp, P(HkRay), u32, u32, P(HkRayHit)],

@@ -291,6 +291,7 @@ struct hk_ctx {
   size_t df_records_cap = 0;
   uint64_t df_batch = 0;                  // counts hk_deform_meshes calls (a mesh named twice in one batch carries the call's number already)
   uint32_t last_deform[6] = {0, 0, 0, 0, 0, 0};  // hk_debug_last_deform
+  hipEvent_t df_src_ready = nullptr, df_src_read = nullptr;  // hk_deform_meshes_device: the producer's stream before the batch, the batch's vertex launch before the producer
   bool deform_pending = false;            // deformed meshes whose new boxes have not reached the instance level yet (flush_deform)
   bool meshes_deformed = false;           // a mesh was deformed on the device since the last hk_upload_meshes: its host copies are stale
   uint64_t instances_generation = 0;      // counts hk_upload_instances (the instance lists of the deformable meshes follow it)

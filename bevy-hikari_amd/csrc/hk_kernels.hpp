@@ -162,6 +162,11 @@ struct DeformItem {
   float4 *v0, *v1, *v2;              // the mesh's first triangle in the triangle planes
   MeshTree tree;
   float4* nodes;                     // the mesh's first node (lo) in ordering 0 of the mesh-level node array
+  uint32_t pos_stride, nrm_stride;   // VERTICES: floats from one vertex to the next in positions / normals (3: packed staging; hk_deform_meshes_device: the caller's)
+  // HK_DEFORM_RECOMPUTE_NORMALS (hk_deform_meshes_device; NULL otherwise): the mesh's face-vector plane, one per triangle, and its corner
+  // list - corner_tri[corner_off[v] .. corner_off[v + 1]) are the triangles that name vertex v, ascending, one entry per naming corner
+  float4* face;
+  const uint32_t *corner_off, *corner_tri;
 };
 // A workgroup of a segmented launch: 256 consecutive elements of ONE segment (item, tree), from `first` on.  The host writes one entry
 // per workgroup, so no workgroup - and no wave - spans two segments, whatever their sizes and however many there are.
@@ -466,9 +471,12 @@ uint32_t launch_mesh_propagate(hipStream_t st, const hkd::RefitScene& s, const h
                                uint32_t light_count);
 // hk_deform_meshes: `items` and the three workgroup tables (vertices, triangles = leaves, tree nodes x orderings) lie in pinned memory.
 // Five launches whatever n_items is: begin (box words, joint palettes), vertices, triangles (+ arrival counters), boxes bottom-up, emit.
+// hk_deform_meshes_device: `sources_read` (or NULL) is recorded behind the vertex launch, the last that reads the caller's memory; with
+// n_normal_blocks (the vertex workgroups of the items that recompute their normals) a sixth launch gathers them behind the triangles.
 void launch_deform_batch(hipStream_t st, const hkd::DeformItem* items, uint32_t n_items, const hkd::SegmentBlock* vertex_blocks, uint32_t n_vertex_blocks,
                          const hkd::SegmentBlock* triangle_blocks, uint32_t n_triangle_blocks, const hkd::SegmentBlock* node_blocks, uint32_t n_node_blocks,
-                         size_t ord_stride, uint32_t orderings);
+                         size_t ord_stride, uint32_t orderings, hipEvent_t sources_read = nullptr, const hkd::SegmentBlock* normal_blocks = nullptr,
+                         uint32_t n_normal_blocks = 0);
 void launch_deform_tree_refit(hipStream_t st, const hkd::DeformItem* items, const hkd::SegmentBlock* triangle_blocks, uint32_t n_triangle_blocks,
                               const hkd::SegmentBlock* node_blocks, uint32_t n_node_blocks, size_t ord_stride, uint32_t orderings);  // (the last two of them: kernels_tree.hip)
 void launch_mesh_stage(hipStream_t st, const float* positions, const float* normals, uint32_t n, float4* pos, float4* vn, uint32_t* box);

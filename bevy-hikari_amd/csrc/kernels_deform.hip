@@ -1,5 +1,5 @@
 // kernels_deform.hip - new vertex data of one mesh, or of many in one call, on the device (hk_update_mesh_vertices, hk_skin_mesh,
-// hk_deform_meshes; host side mesh_deform.hip):
+// hk_deform_meshes, hk_deform_meshes_device; host side mesh_deform.hip):
 // the vertices of the mesh land in its normal plane and in a position scratch plane, the mesh box is reduced on the way, then every
 // triangle of the mesh takes its three positions into the triangle planes and its box into the refit's leaf boxes (kernels_tree.hip
 // launch_mesh_tree_refit carries on from there).  Streaming kernels, one thread per vertex / per triangle.
@@ -32,14 +32,19 @@ __device__ __forceinline__ void reduce_box(uint32_t* box, bool valid, float x, f
     }
 }
 
-// one vertex of hk_update_mesh_vertices: positions / normals (3 floats per vertex, pinned host memory, read once)
+// one vertex of hk_update_mesh_vertices: positions / normals (3 floats per vertex, pinned host memory, read once; hk_deform_meshes_device:
+// the caller's device memory, `ps` / `ns` floats from one vertex to the next)
 __device__ __forceinline__ void stage_vertex(const float* __restrict__ positions, const float* __restrict__ normals, uint32_t v, float4* __restrict__ pos,
-                                             float4* __restrict__ vn, float& x, float& y, float& z) {
-  x = positions[3u * v];
-  y = positions[3u * v + 1u];
-  z = positions[3u * v + 2u];
+                                             float4* __restrict__ vn, float& x, float& y, float& z, uint32_t ps = 3u, uint32_t ns = 3u) {
+  const float* p = positions + (size_t)ps * v;
+  x = p[0];
+  y = p[1];
+  z = p[2];
   pos[v] = make_float4(x, y, z, 0.0f);
-  if (normals) vn[v] = make_float4(normals[3u * v], normals[3u * v + 1u], normals[3u * v + 2u], 0.0f);
+  if (normals) {
+    const float* q = normals + (size_t)ns * v;
+    vn[v] = make_float4(q[0], q[1], q[2], 0.0f);
+  }
 }
 
 // Linear-blend skinning of one vertex, Bevy 0.9 skinning.wgsl (hikari_hip.h hk_skin_mesh; DESIGN "Mesh deformation"): fixed order, no contraction.
@@ -98,8 +103,9 @@ __device__ __forceinline__ void skin_vertex(const float4* __restrict__ bind_pos,
 }
 
 // triangle t of the mesh: its three positions (the w words - vertex indices - stay) and its box (light.wgsl:408-412, the leaf box)
+// `face` (or NULL): the triangle's un-normalised face vector e1 x e2, e1 = p1 - p0, e2 = p2 - p0 (hikari_hip.h HK_DEFORM_RECOMPUTE_NORMALS)
 __device__ __forceinline__ void mesh_triangle(const float4* __restrict__ pos, float4* __restrict__ v0, float4* __restrict__ v1, float4* __restrict__ v2, uint32_t t,
-                                              float4* __restrict__ tri_lo, float4* __restrict__ tri_hi) {
+                                              float4* __restrict__ tri_lo, float4* __restrict__ tri_hi, float4* __restrict__ face = nullptr) {
   float4 q[3] = {v0[t], v1[t], v2[t]};
   for (int k = 0; k < 3; ++k) {
     const float4 p = pos[f2u(q[k].w)];
@@ -109,6 +115,11 @@ __device__ __forceinline__ void mesh_triangle(const float4* __restrict__ pos, fl
   v1[t] = q[1];
   v2[t] = q[2];
   triangle_box(q[0], q[1], q[2], tri_lo[t], tri_hi[t]);
+  if (face) {
+    const float ax = q[1].x - q[0].x, ay = q[1].y - q[0].y, az = q[1].z - q[0].z;
+    const float bx = q[2].x - q[0].x, by = q[2].y - q[0].y, bz = q[2].z - q[0].z;
+    face[t] = make_float4(ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx, 0.0f);
+  }
 }
 }  // namespace
 
@@ -166,7 +177,7 @@ __global__ __launch_bounds__(256) void k_deform_vertices(const DeformItem* __res
   if (it->kind == HK_DEFORM_SKIN) {
     if (valid) skin_vertex(it->bind_pos, it->bind_nrm, it->joints, it->weights, it->joint_mats, v, pos, vn, x, y, z);
   } else {
-    if (valid) stage_vertex(it->positions, it->normals, v, pos, vn, x, y, z);
+    if (valid) stage_vertex(it->positions, it->normals, v, pos, vn, x, y, z, it->pos_stride, it->nrm_stride);
   }
   reduce_box(it->box, valid, x, y, z);
 }
@@ -177,7 +188,28 @@ __global__ __launch_bounds__(256) void k_deform_triangles(const DeformItem* __re
   const uint32_t t = bl.first + threadIdx.x, n = it->n_tris;
   if (t >= n) return;
   if (t + 1u < n) it->tree.arrived[t] = 0u;
-  mesh_triangle(it->pos, it->v0, it->v1, it->v2, t, it->tree.tri_lo, it->tree.tri_hi);
+  mesh_triangle(it->pos, it->v0, it->v1, it->v2, t, it->tree.tri_lo, it->tree.tri_hi, it->face);
+}
+// HK_DEFORM_RECOMPUTE_NORMALS: vertex v's normal = ((+0 + f[t_1]) + f[t_2]) + ... over its corner list, in list order - a gather, so the
+// result is the same whatever the scheduling.  An all-zero sum (no triangle names v, or areas that cancel) keeps the normal there is.
+// `blocks` holds the vertex workgroups of the flagged items only.
+__global__ __launch_bounds__(256) void k_deform_normals(const DeformItem* __restrict__ items, const SegmentBlock* __restrict__ blocks) {
+  const SegmentBlock bl = blocks[blockIdx.x];
+  const DeformItem* it = items + bl.segment;
+  const uint32_t v = bl.first + threadIdx.x;
+  if (v >= it->n_vertices) return;
+  const uint32_t* __restrict__ tri = it->corner_tri;
+  const float4* __restrict__ face = it->face;
+  const uint32_t b = it->corner_off[v], e = it->corner_off[v + 1u];
+  float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+  for (uint32_t i = b; i < e; ++i) {
+    const float4 f = face[tri[i]];
+    sx = sx + f.x;
+    sy = sy + f.y;
+    sz = sz + f.z;
+  }
+  if (sx == 0.0f && sy == 0.0f && sz == 0.0f) return;
+  it->vn[v] = make_float4(sx, sy, sz, 0.0f);
 }
 
 // ... the boxes alone, of triangles nobody has moved yet (hk_rebuild_mesh_tree on a mesh never deformed)
@@ -208,11 +240,13 @@ void launch_mesh_triangle_boxes(hipStream_t st, const float4* v0, const float4* 
 }
 void launch_deform_batch(hipStream_t st, const DeformItem* items, uint32_t n_items, const SegmentBlock* vertex_blocks, uint32_t n_vertex_blocks,
                          const SegmentBlock* triangle_blocks, uint32_t n_triangle_blocks, const SegmentBlock* node_blocks, uint32_t n_node_blocks, size_t ord_stride,
-                         uint32_t orderings) {
+                         uint32_t orderings, hipEvent_t sources_read, const SegmentBlock* normal_blocks, uint32_t n_normal_blocks) {
   if (!n_items) return;
   hipLaunchKernelGGL(k_deform_begin, dim3(n_items), dim3(256), 0, st, items, n_items);
   hipLaunchKernelGGL(k_deform_vertices, dim3(n_vertex_blocks), dim3(256), 0, st, items, vertex_blocks);
+  if (sources_read) (void)hipEventRecord(sources_read, st);
   hipLaunchKernelGGL(k_deform_triangles, dim3(n_triangle_blocks), dim3(256), 0, st, items, triangle_blocks);
+  if (n_normal_blocks) hipLaunchKernelGGL(k_deform_normals, dim3(n_normal_blocks), dim3(256), 0, st, items, normal_blocks);
   launch_deform_tree_refit(st, items, triangle_blocks, n_triangle_blocks, node_blocks, n_node_blocks, ord_stride, orderings);
 }
 

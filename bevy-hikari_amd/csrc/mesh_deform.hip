@@ -1,4 +1,4 @@
-// mesh_deform.hip - mesh deformation on the device (hikari_hip.h hk_update_mesh_vertices / hk_set_mesh_skin / hk_skin_mesh / hk_deform_meshes; kernels in
+// mesh_deform.hip - mesh deformation on the device (hikari_hip.h hk_update_mesh_vertices / hk_set_mesh_skin / hk_skin_mesh / hk_deform_meshes / hk_deform_meshes_device; kernels in
 // kernels_deform.hip, kernels_tree.hip and kernels_scene.hip; DESIGN "Mesh deformation").  The reference re-prepares a changed mesh on the CPU
 // (mesh.rs:76-166: a BVH build and a re-layout of the whole mesh level); here the new vertices are written into the mesh-level region,
 // the mesh tree is REFIT in every ordering that holds it (same links, every box the union of the triangle boxes below it), and the
@@ -30,12 +30,17 @@ struct DeformMesh {
   float4 *bind_pos = nullptr, *bind_nrm = nullptr, *weights = nullptr, *joint_mats = nullptr;
   uint2* joints = nullptr;
   uint32_t skin_vertices = 0, max_joint = 0, joint_cap = 0;
+  // HK_DEFORM_RECOMPUTE_NORMALS (hk_deform_meshes_device), made at the mesh's first such item: the face-vector plane (per triangle) and
+  // the corner list (hk_kernels.hpp DeformItem) - the topology never changes, so neither does the list
+  void* nrm_mem = nullptr;
+  float4* face = nullptr;
+  uint32_t *corner_off = nullptr, *corner_tri = nullptr;
 };
 
 namespace hk {
 void free_deform(hk_ctx* c) {
   for (DeformMesh* d : c->deform) {
-    for (void* q : {d->mem, d->skin_mem, (void*)d->joint_mats})
+    for (void* q : {d->mem, d->skin_mem, (void*)d->joint_mats, d->nrm_mem})
       if (q) (void)hipFree(q);
     delete d;
   }
@@ -49,6 +54,10 @@ void free_deform(hk_ctx* c) {
   c->df_records = nullptr;
   c->df_records_cap = 0;
   c->deform_pending = false;
+  for (hipEvent_t* e : {&c->df_src_ready, &c->df_src_read}) {
+    if (*e) (void)hipEventDestroy(*e);
+    *e = nullptr;
+  }
 }
 }  // namespace hk
 
@@ -221,6 +230,56 @@ int hk::stage(hk_ctx* c, size_t bytes, uint8_t** out, int* k_out) {
 }
 
 namespace {
+inline uint32_t stride_of(uint32_t bytes) { return bytes ? bytes : 12u; }
+
+// a source of hk_deform_meshes_device: aligned, memory the context's device can read - its own, or host memory mapped for it - and
+// `extent` bytes from `p` on inside the allocation, so that no launch can fault on what a caller named by mistake
+int check_source(hk_ctx* c, uint32_t item, const char* what, const void* p, size_t align, size_t extent) {
+  HK_REQUIRE(((uintptr_t)p & (align - 1)) == 0, HK_E_INVALID, "item %u: the %s at %p are not aligned to %zu bytes", item, what, p, align);
+  hipPointerAttribute_t a{};
+  const hipError_t e = hipPointerGetAttributes(&a, p);
+  if (e != hipSuccess) (void)hipGetLastError();  // (plain host memory: an error on some runtimes, hipMemoryTypeUnregistered on others)
+  HK_REQUIRE(e == hipSuccess && ((a.type == hipMemoryTypeDevice && a.device == c->device) || a.type == hipMemoryTypeHost), HK_E_INVALID,
+             "item %u: the %s at %p are neither memory of device %d nor host memory the device can access", item, what, p, c->device);
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+    (void)hipGetLastError();
+    return HK_OK;
+  }
+  HK_REQUIRE((const uint8_t*)p + extent <= (const uint8_t*)base + size, HK_E_INVALID, "item %u: the %s reach %zu bytes beyond their allocation", item, what,
+             (size_t)(((const uint8_t*)p + extent) - ((const uint8_t*)base + size)));
+  return HK_OK;
+}
+
+// the corner list and the face plane of a mesh's recomputed normals, from the primitive mirror (indices never change): per vertex the
+// triangles that name it, ascending, one entry per corner - the order k_deform_normals sums in
+int corner_list(hk_ctx* c, DeformMesh* d) {
+  const size_t nv = d->max_vertices, nt = d->n_tris;
+  std::vector<uint32_t> host(nv + 1 + 3 * nt, 0);
+  uint32_t* off = host.data();
+  uint32_t* tri = host.data() + nv + 1;
+  const HkPrimitive* prims = c->primitives.data() + d->mesh.primitive;
+  for (size_t t = 0; t < nt; ++t)
+    for (int k = 0; k < 3; ++k) off[prims[t].vertices[k].index + 1] += 1;
+  for (size_t v = 0; v < nv; ++v) off[v + 1] += off[v];
+  std::vector<uint32_t> at(off, off + nv);
+  for (size_t t = 0; t < nt; ++t)
+    for (int k = 0; k < 3; ++k) tri[at[prims[t].vertices[k].index]++] = (uint32_t)t;
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t bytes = al(nt * 16) + host.size() * 4;
+  HK_REQUIRE(hipMalloc(&d->nrm_mem, bytes) == hipSuccess, HK_E_NOMEM, "device allocation of %zu bytes failed", bytes);
+  d->face = (float4*)d->nrm_mem;
+  d->corner_off = (uint32_t*)((uint8_t*)d->nrm_mem + al(nt * 16));
+  d->corner_tri = d->corner_off + nv + 1;
+  if (hipMemcpy(d->corner_off, host.data(), host.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d->nrm_mem);
+    d->nrm_mem = nullptr;
+    HK_REQUIRE(false, HK_E_HIP, "copying the corner list failed: %s", hipGetErrorString(hipGetLastError()));
+  }
+  return HK_OK;
+}
+
 // common front of the three calls: the scene as laid out, the refit's side arrays, the mesh
 int begin(hk_ctx* c, const HkMeshIndex* m, DeformMesh** d) {
   HK_REQUIRE(c->have_meshes && c->have_materials && c->have_instances, HK_E_NOT_READY, "hk_upload_scene must come first");
@@ -440,10 +499,12 @@ int hk_skin_mesh(hk_ctx* c, const HkMeshIndex* mesh, const float* joint_matrices
 // Many meshes in one call (hikari_hip.h): what the single calls above do for each item, as five launches over all of them
 // (kernels_deform.hip launch_deform_batch).  Everything the device reads of the call - the item table, the workgroup tables of the
 // three launch shapes, every item's positions / normals / joint matrices - travels in ONE pinned staging block.
-int hk_deform_meshes(hk_ctx* c, const HkMeshDeform* items, uint32_t n) {
-  HK_REQUIRE(c, HK_E_INVALID, "NULL context");
-  if (n == 0) return HK_OK;
-  HK_REQUIRE(items, HK_E_INVALID, "NULL items");
+// hk_deform_meshes_device is the same batch with `device` set: the items' data stays where the caller has it (validated first: memory the
+// device can read, aligned, strided), only the tables are staged, `producer` (or NULL) is ordered against the context's stream by two
+// events, and flagged items recompute their normals in a sixth launch.
+}  // extern "C"
+namespace {
+int deform_batch(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, bool device, hipStream_t producer) {
   HK_REQUIRE(c->have_meshes && c->have_materials && c->have_instances, HK_E_NOT_READY, "hk_upload_scene must come first");
   HK_HIP(hipSetDevice(c->device));
   int rc;
@@ -453,14 +514,26 @@ int hk_deform_meshes(hk_ctx* c, const HkMeshDeform* items, uint32_t n) {
   std::vector<DeformMesh*> meshes(n, nullptr);
   const uint32_t orderings = c->threaded ? 8u : 1u;
   auto al16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  size_t data_bytes = 0, blocks[3] = {0, 0, 0};
+  size_t data_bytes = 0, blocks[4] = {0, 0, 0, 0};  // vertex, triangle, node workgroups; the vertex workgroups of the items that recompute normals
   uint32_t total_vertices = 0, total_tris = 0;
   bool grow = false;
   for (uint32_t i = 0; i < n; ++i) {
-    const HkMeshDeform& it = items[i];
+    const HkMeshDeformDevice& it = items[i];
     HK_REQUIRE(it.kind == HK_DEFORM_VERTICES || it.kind == HK_DEFORM_SKIN, HK_E_INVALID, "item %u: unknown kind %u", i, it.kind);
     HK_REQUIRE(it.data && it.count, HK_E_INVALID, "item %u: NULL data or a count of zero", i);
     HK_REQUIRE(it.kind != HK_DEFORM_SKIN || !it.normals, HK_E_INVALID, "item %u: a skin item takes no normals", i);
+    const bool recompute = (it.flags & HK_DEFORM_RECOMPUTE_NORMALS) != 0;
+    if (device) {
+      HK_REQUIRE(!(it.flags & ~HK_DEFORM_RECOMPUTE_NORMALS), HK_E_INVALID, "item %u: unknown flag bits 0x%x", i, it.flags & ~HK_DEFORM_RECOMPUTE_NORMALS);
+      HK_REQUIRE(!recompute || it.kind == HK_DEFORM_VERTICES, HK_E_INVALID, "item %u: a skin item cannot recompute its normals (the skin transforms them)", i);
+      HK_REQUIRE(!recompute || !it.normals, HK_E_INVALID, "item %u: normals given together with HK_DEFORM_RECOMPUTE_NORMALS", i);
+      if (it.kind == HK_DEFORM_SKIN) {
+        HK_REQUIRE(it.data_stride == 0 || it.data_stride == 64, HK_E_INVALID, "item %u: joint matrices are contiguous (a stride of 0 or 64 bytes, not %u)", i, it.data_stride);
+      } else {
+        for (const uint32_t stride : {it.data_stride, it.normals ? it.normals_stride : 0u})
+          HK_REQUIRE(stride == 0 || (stride >= 12 && stride % 4 == 0), HK_E_INVALID, "item %u: a stride of %u bytes (0, or a multiple of 4 from 12 on)", i, stride);
+      }
+    }
     DeformMesh* d = nullptr;
     if (it.kind == HK_DEFORM_SKIN) {
       for (DeformMesh* q : c->deform)
@@ -480,23 +553,36 @@ int hk_deform_meshes(hk_ctx* c, const HkMeshDeform* items, uint32_t n) {
     d->batch = c->df_batch;
     meshes[i] = d;
     const uint32_t nv = it.kind == HK_DEFORM_SKIN ? d->skin_vertices : it.count;
+    if (device) {  // (the counts are known to be the mesh's: the extents below are what the kernels will read)
+      if (it.kind == HK_DEFORM_SKIN) {
+        if ((rc = check_source(c, i, "joint matrices", it.data, 16, (size_t)it.count * 64))) return rc;
+      } else {
+        if ((rc = check_source(c, i, "positions", it.data, 4, (size_t)(nv - 1) * stride_of(it.data_stride) + 12))) return rc;
+        if (it.normals && (rc = check_source(c, i, "normals", it.normals, 4, (size_t)(nv - 1) * stride_of(it.normals_stride) + 12))) return rc;
+      }
+      if (recompute) {
+        blocks[3] += (nv + 255u) / 256u;
+        grow = grow || !d->nrm_mem;
+      }
+    }
     total_vertices += nv;
     total_tris += d->n_tris;
     blocks[0] += (nv + 255u) / 256u;
     blocks[1] += (d->n_tris + 255u) / 256u;
     blocks[2] += ((size_t)(2u * d->n_tris - 1u) * orderings + 255u) / 256u;
     if (it.kind == HK_DEFORM_SKIN) {
-      data_bytes += (size_t)it.count * 64;
+      if (!device) data_bytes += (size_t)it.count * 64;
       grow = grow || it.count > d->joint_cap;
-    } else {
+    } else if (!device) {
       data_bytes += al16((size_t)it.count * 12) * (it.normals ? 2 : 1);
     }
   }
-  // ---- what has to grow (the first skinning of a mesh, a longer palette): one wait for all of it
+  // ---- what has to grow (the first skinning of a mesh, a longer palette, a mesh's first recomputed normals): one wait for all of it
   if (grow) {
     if ((rc = sync_all(c))) return rc;
     for (uint32_t i = 0; i < n; ++i) {
       DeformMesh* d = meshes[i];
+      if (device && (items[i].flags & HK_DEFORM_RECOMPUTE_NORMALS) && !d->nrm_mem && (rc = corner_list(c, d))) return rc;
       if (items[i].kind != HK_DEFORM_SKIN || items[i].count <= d->joint_cap) continue;
       if (d->joint_mats) (void)hipFree(d->joint_mats);
       d->joint_mats = nullptr;
@@ -505,33 +591,54 @@ int hk_deform_meshes(hk_ctx* c, const HkMeshDeform* items, uint32_t n) {
       d->joint_cap = items[i].count;
     }
   }
-  // ---- the staging block: item table | vertex, triangle and node workgroups | the items' data
+  if (producer)
+    for (hipEvent_t* e : {&c->df_src_ready, &c->df_src_read})
+      if (!*e) HK_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  // ---- the staging block: item table | vertex, triangle, node and normal workgroups | the items' data (host sources only)
   const size_t table_bytes = (n * sizeof(DeformItem) + 255) & ~(size_t)255;
-  const size_t block_bytes = ((blocks[0] + blocks[1] + blocks[2]) * sizeof(SegmentBlock) + 255) & ~(size_t)255;
+  const size_t block_bytes = ((blocks[0] + blocks[1] + blocks[2] + blocks[3]) * sizeof(SegmentBlock) + 255) & ~(size_t)255;
   uint8_t* st = nullptr;
   int k = 0;
   if ((rc = stage(c, table_bytes + block_bytes + data_bytes, &st, &k))) return rc;
   DeformItem* table = (DeformItem*)st;
-  SegmentBlock* bl[3] = {(SegmentBlock*)(st + table_bytes), (SegmentBlock*)(st + table_bytes) + blocks[0], (SegmentBlock*)(st + table_bytes) + blocks[0] + blocks[1]};
+  SegmentBlock* bl[4] = {(SegmentBlock*)(st + table_bytes), (SegmentBlock*)(st + table_bytes) + blocks[0], (SegmentBlock*)(st + table_bytes) + blocks[0] + blocks[1],
+                         (SegmentBlock*)(st + table_bytes) + blocks[0] + blocks[1] + blocks[2]};
   uint8_t* data = st + table_bytes + block_bytes;
   const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
   uint8_t* sbase = c->scene_mem + slots;
-  size_t at[3] = {0, 0, 0};
+  size_t at[4] = {0, 0, 0, 0};
   std::vector<std::pair<uint32_t, uint32_t>> keys(n);
   for (uint32_t i = 0; i < n; ++i) {
-    const HkMeshDeform& it = items[i];
+    const HkMeshDeformDevice& it = items[i];
     DeformMesh* d = meshes[i];
     DeformItem t{};
+    t.pos_stride = t.nrm_stride = 3u;
     t.kind = it.kind;
     t.n_tris = d->n_tris;
     if (it.kind == HK_DEFORM_SKIN) {
       t.n_vertices = d->skin_vertices;
       t.n_joints = it.count;
-      memcpy(data, it.data, (size_t)it.count * 64);
-      t.palette = (const float4*)data;
-      data += (size_t)it.count * 64;
+      if (device) {
+        t.palette = (const float4*)it.data;
+      } else {
+        memcpy(data, it.data, (size_t)it.count * 64);
+        t.palette = (const float4*)data;
+        data += (size_t)it.count * 64;
+      }
       t.joint_mats = d->joint_mats;
       t.bind_pos = d->bind_pos; t.bind_nrm = d->bind_nrm; t.weights = d->weights; t.joints = d->joints;
+    } else if (device) {
+      t.n_vertices = it.count;
+      t.positions = (const float*)it.data;
+      t.normals = (const float*)it.normals;
+      t.pos_stride = stride_of(it.data_stride) / 4u;
+      t.nrm_stride = stride_of(it.normals_stride) / 4u;
+      if (it.flags & HK_DEFORM_RECOMPUTE_NORMALS) {
+        t.face = d->face;
+        t.corner_off = d->corner_off;
+        t.corner_tri = d->corner_tri;
+        for (uint32_t first = 0; first < t.n_vertices; first += 256) bl[3][at[3]++] = SegmentBlock{i, first};
+      }
     } else {
       const size_t plane = (size_t)it.count * 12;
       t.n_vertices = it.count;
@@ -560,9 +667,15 @@ int hk_deform_meshes(hk_ctx* c, const HkMeshDeform* items, uint32_t n) {
   }
   // ---- enqueue: behind every frame enqueued so far on every stream that reads the scene (stream waits), as a single deformation is
   if ((rc = join_all(c))) return rc;
+  if (producer) {  // what the producer has enqueued on the sources so far comes first; it may write them again once the vertex launch has read them
+    HK_HIP(hipEventRecord(c->df_src_ready, producer));
+    HK_HIP(hipStreamWaitEvent(c->stream, c->df_src_ready, 0));
+  }
   c->scene_epoch += n;  // (scene memory is written from here on: hk_context.hpp, primary-ray pipelining - a refusal above leaves it alone)
-  launch_deform_batch(c->stream, table, n, bl[0], (uint32_t)blocks[0], bl[1], (uint32_t)blocks[1], bl[2], (uint32_t)blocks[2], 2 * c->node_cap, orderings);
+  launch_deform_batch(c->stream, table, n, bl[0], (uint32_t)blocks[0], bl[1], (uint32_t)blocks[1], bl[2], (uint32_t)blocks[2], 2 * c->node_cap, orderings,
+                      producer ? c->df_src_read : nullptr, bl[3], (uint32_t)blocks[3]);
   HK_HIP(hipGetLastError());
+  if (producer) HK_HIP(hipStreamWaitEvent(producer, c->df_src_read, 0));
   hk_ctx::DeformStage& stg = c->df_stage[(size_t)k];
   HK_HIP(hipEventRecord(stg.done, c->stream));
   stg.pending = true;
@@ -577,8 +690,32 @@ int hk_deform_meshes(hk_ctx* c, const HkMeshDeform* items, uint32_t n) {
   c->last_deform[0] = n;
   c->last_deform[1] = total_vertices;
   c->last_deform[2] = total_tris;
-  c->last_deform[3] = 5u;  // begin, vertices, triangles, boxes, emit
+  c->last_deform[3] = blocks[3] ? 6u : 5u;  // begin, vertices, triangles, (normals,) boxes, emit
   return HK_OK;
+}
+}  // namespace
+
+extern "C" {
+int hk_deform_meshes(hk_ctx* c, const HkMeshDeform* items, uint32_t n) {
+  HK_REQUIRE(c, HK_E_INVALID, "NULL context");
+  if (n == 0) return HK_OK;
+  HK_REQUIRE(items, HK_E_INVALID, "NULL items");
+  std::vector<HkMeshDeformDevice> wide(n);  // (host pointers in the device item's fields, strides and flags zero: deform_batch stages what they name)
+  for (uint32_t i = 0; i < n; ++i) {
+    wide[i].mesh = items[i].mesh;
+    wide[i].kind = items[i].kind;
+    wide[i].count = items[i].count;
+    wide[i].data = items[i].data;
+    wide[i].normals = items[i].normals;
+  }
+  return deform_batch(c, wide.data(), n, false, nullptr);
+}
+
+int hk_deform_meshes_device(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, void* producer_stream) {
+  HK_REQUIRE(c, HK_E_INVALID, "NULL context");
+  if (n == 0) return HK_OK;
+  HK_REQUIRE(items, HK_E_INVALID, "NULL items");
+  return deform_batch(c, items, n, true, (hipStream_t)producer_stream);
 }
 
 // Test hook (hikari_hip_debug.h)

@@ -634,6 +634,38 @@ int hk_scene_builder_set_mesh_vertices(hk_scene_builder* b, uint32_t mesh_id, co
   return HK_OK;
 }
 
+// The host twin of HK_DEFORM_RECOMPUTE_NORMALS (kernels_deform.hip k_deform_triangles' face vectors, k_deform_normals' gather): the same
+// f32 operations in the same order (no contraction: -ffp-contract=off), so the normals equal the device's bit for bit.
+int hk_scene_builder_recompute_mesh_normals(hk_scene_builder* b, uint32_t mesh_id) {
+  HK_REQUIRE(b, HK_E_INVALID, "builder is NULL");
+  HK_REQUIRE(mesh_id < b->meshes.size(), HK_E_INVALID, "unknown mesh id");
+  BuilderMesh& mesh = b->meshes[mesh_id];
+  const size_t nv = mesh.vertices.size();
+  for (const HkPrimitive& p : mesh.primitives)
+    for (int k = 0; k < 3; ++k) HK_REQUIRE(p.vertices[k].index < nv, HK_E_INVALID, "a triangle names vertex %u of %zu", p.vertices[k].index, nv);
+  std::vector<float> sum(3 * nv, 0.0f);  // (+0: the first face vector is added to it, so a sum of -0 stores +0)
+  for (const HkPrimitive& p : mesh.primitives) {  // ascending triangle, then corner: every vertex's sum in the order of the rule
+    const float* p0 = mesh.vertices[p.vertices[0].index].position;
+    const float* p1 = mesh.vertices[p.vertices[1].index].position;
+    const float* p2 = mesh.vertices[p.vertices[2].index].position;
+    const float e1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]}, e2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
+    const float f[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+    for (int k = 0; k < 3; ++k) {
+      float* s = &sum[3 * (size_t)p.vertices[k].index];
+      for (int a = 0; a < 3; ++a) s[a] = s[a] + f[a];
+    }
+  }
+  for (size_t v = 0; v < nv; ++v) {
+    const float* s = &sum[3 * v];
+    if (s[0] == 0.0f && s[1] == 0.0f && s[2] == 0.0f) continue;  // (also a vertex no triangle names: it keeps its normal)
+    memcpy(mesh.vertices[v].normal, s, 12);
+  }
+  b->concat_meshes = std::min<size_t>(b->concat_meshes, mesh_id);
+  b->meshes_dirty = true;
+  b->finished = false;
+  return HK_OK;
+}
+
 // The host twin of the device rebuild (mesh_deform.hip hk_rebuild_mesh_tree, HK_TREE_SAH): the tree hk_scene_builder_add_mesh would
 // build over the mesh's CURRENT triangles - `bvh` 0.7.1 BVH::build over their boxes, formed with add_mesh's arithmetic - and then the
 // canonical navigator boxes of refit_nodes, so that the result is what the device writes and what a later refit leaves alone.

@@ -425,6 +425,11 @@ class SceneBuilder:
         self.api.call("scene_builder_set_mesh_vertices", self.h, mesh_id, pos.ctypes.data_as(C.POINTER(F.f32)),
                       None if nrm is None else nrm.ctypes.data_as(C.POINTER(F.f32)))
 
+    def recompute_mesh_normals(self, mesh_id):
+        """The host mirror of a device deformation with recompute_normals=True (hk_scene_builder_recompute_mesh_normals): the mesh's normals
+        from its current positions, area-weighted, bit for bit what the device stores; after set_mesh_vertices(positions, None)."""
+        self.api.call("scene_builder_recompute_mesh_normals", self.h, mesh_id)
+
     def rebuild_mesh_tree(self, mesh_id):
         """The host mirror of Engine.rebuild_mesh_tree (hk_scene_builder_rebuild_mesh_tree): the mesh's tree built again over its current
         triangles, as add_mesh would build it; finish() + upload next."""
@@ -555,8 +560,64 @@ def deform_items(items):
     return table, keep
 
 
+def _item_arrays(item):
+    return [a for a in item[2:4] if a is not None and not isinstance(a, dict)]
+
+
+def _item_options(item):
+    """the trailing dict of an item: ("vertices", index, positions, None, dict(recompute_normals=True))"""
+    options = item[-1] if isinstance(item[-1], dict) else {}
+    if set(options) - {"recompute_normals"}:
+        raise ValueError(f"unknown item options {sorted(set(options) - {'recompute_normals'})}")
+    return options
+
+
+def _is_device_tensor(a):
+    return type(a).__module__.partition(".")[0] == "torch" and bool(getattr(a, "is_cuda", False))
+
+
+def deform_items_device(items, device):
+    """The HkMeshDeformDevice table of Engine.deform_meshes' `items` when their arrays are torch tensors on cuda:`device`, and the tensors
+    it points into.  float32 tensors whose rows are contiguous are named where they lie - pointer and row stride from the tensor, so a
+    column slice state[:, 0:3] of a wider state tensor costs no copy; anything else is converted on the device first."""
+    import torch
+
+    def rows(t, width):
+        if t.device.index != device:
+            raise ValueError(f"the tensor lies on {t.device}, the context on cuda:{device}")
+        t = t.reshape(-1, width) if t.dim() != 2 else t
+        if t.shape[1] != width:
+            raise ValueError(f"expected rows of {width} floats, not {tuple(t.shape)}")
+        if t.dtype != torch.float32 or (len(t) > 1 and (t.stride(1) != 1 or t.stride(0) < width)) or (len(t) <= 1 and not t.is_contiguous()):
+            t = t.to(torch.float32).contiguous()
+        return t
+
+    table, keep = (F.HkMeshDeformDevice * max(len(items), 1))(), []
+    for k, item in enumerate(items):
+        kind, mesh = item[0], item[1]
+        flags = F.DEFORM_RECOMPUTE_NORMALS if _item_options(item).get("recompute_normals") else 0
+        if kind == "skin":
+            if len(_item_arrays(item)) != 1:
+                raise ValueError('a skin item is ("skin", index, joints)')
+            j = rows(item[2], 16).contiguous()
+            keep.append(j)
+            table[k] = F.HkMeshDeformDevice(mesh, F.DEFORM_SKIN, len(j), j.data_ptr(), None, 0, 0, flags, 0)
+        elif kind == "vertices":
+            pos = rows(item[2], 3)
+            nrm = None if len(item) < 4 or item[3] is None or isinstance(item[3], dict) else rows(item[3], 3)
+            if nrm is not None and nrm.shape != pos.shape:
+                raise ValueError("normals must match positions")
+            keep += [pos, nrm]
+            table[k] = F.HkMeshDeformDevice(mesh, F.DEFORM_VERTICES, len(pos), pos.data_ptr(), None if nrm is None else nrm.data_ptr(),
+                                            4 * pos.stride(0) if len(pos) > 1 else 0, 4 * nrm.stride(0) if nrm is not None and len(nrm) > 1 else 0, flags, 0)
+        else:
+            raise ValueError(f"unknown deformation kind {kind!r}")
+    return table, keep
+
+
 class Engine:
     """One context of the C ABI (`hk_ctx`).  `api` defaults to the product library."""
+    _producer = None  # deform_meshes: a torch stream standing in for torch's legacy default stream (made at the first such call)
 
     def __init__(self, api=None, device=0, flags=0):
         self.api = api or F.api()
@@ -681,12 +742,38 @@ class Engine:
         j = np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1, 16)
         self.api.call("skin_mesh", self.ctx, C.byref(mesh), j.ctypes.data_as(C.POINTER(F.f32)), len(j))
 
-    def deform_meshes(self, items):
+    def deform_meshes(self, items, producer_stream=None):
         """Many meshes deformed in one call (hk_deform_meshes): `items` is a list of ("vertices", index, positions, normals_or_None) and
         ("skin", index, joints) tuples - what update_mesh_vertices / skin_mesh take, mesh by mesh.  The device work is a fixed number of
-        launches however many items there are; the result is what the single calls in item order would have left."""
-        table, keep = deform_items(items)
-        self.api.call("deform_meshes", self.ctx, table, len(items))
+        launches however many items there are; the result is what the single calls in item order would have left.
+        Items whose arrays are torch tensors on the context's device take hk_deform_meshes_device: nothing is copied to the host, the
+        context is ordered behind `producer_stream` (a torch stream; default: torch's current stream) by an event, and that stream behind
+        the context's last read of the tensors, so they may be overwritten in stream order right after the call - there is no host wait.
+        Such a "vertices" item may end in dict(recompute_normals=True) (with normals None): the device recomputes the vertex normals
+        from the new positions (SceneBuilder.recompute_mesh_normals is the host's mirror).  numpy items go through hk_deform_meshes."""
+        on_device = [_is_device_tensor(a) for item in items for a in _item_arrays(item)]
+        if not any(on_device):
+            if any(_item_options(item).get("recompute_normals") for item in items):
+                raise ValueError("recompute_normals needs items whose arrays are torch tensors on the context's device")
+            table, keep = deform_items([tuple(a for a in item if not isinstance(a, dict)) for item in items])
+            self.api.call("deform_meshes", self.ctx, table, len(items))
+            return
+        if not all(on_device):
+            raise ValueError("the items of one batch are either all torch tensors on the context's device or all host arrays")
+        import torch
+
+        table, keep = deform_items_device(items, self.device)
+        current = torch.cuda.current_stream(self.device) if producer_stream is None else producer_stream
+        if current.cuda_stream:
+            self.api.call("deform_meshes_device", self.ctx, table, len(items), current.cuda_stream)
+            return
+        # the legacy default stream has the handle 0, which the C call reads as "the caller has ordered itself": a stream of the engine's
+        # own stands in for it, ordered behind it before the call and in front of it after (events, no host wait)
+        if self._producer is None:
+            self._producer = torch.cuda.Stream(self.device)
+        self._producer.wait_stream(current)
+        self.api.call("deform_meshes_device", self.ctx, table, len(items), self._producer.cuda_stream)
+        current.wait_stream(self._producer)
 
     def last_deform(self):
         """(items, vertices, triangles, enqueues of the call, launches of the last flush, launches of the last wide-record derivation) -
@@ -1240,9 +1327,9 @@ class HikariPlugin:
         """Meshes added to the loaded builder since (glTF assets that arrive frame by frame): appended on the device (Engine.add_meshes)."""
         self.engine.add_meshes(builder, mode)
 
-    def deform_meshes(self, items):
+    def deform_meshes(self, items, producer_stream=None):
         """Per frame, every deforming mesh of the scene in one call: Engine.deform_meshes."""
-        self.engine.deform_meshes(items)
+        self.engine.deform_meshes(items, producer_stream)
 
     def update_instances(self, scene: SceneData):
         """Instances moved (prepare_instances, instance.rs:352-437): rewrite the instance-level buffers only."""

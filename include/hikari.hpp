@@ -428,6 +428,10 @@ class HikariPlugin {
   // a new tree over the current triangles of one deformed mesh, built on the device in place (later deformations refit the new shape)
   // per frame: every deforming mesh in one call (vertex updates and skinned meshes alike), at a launch count that does not depend on how many
   void deform_meshes(const std::vector<HkMeshDeform>& items) { check(hk_deform_meshes(ctx_.get(), items.data(), (uint32_t)items.size()), "hk_deform_meshes"); }
+  // ... with the items' sources in device memory; `producer_stream` (a hipStream_t, or nullptr: the caller has ordered itself) is ordered against the context by events
+  void deform_meshes_device(const std::vector<HkMeshDeformDevice>& items, void* producer_stream = nullptr) {
+    check(hk_deform_meshes_device(ctx_.get(), items.data(), (uint32_t)items.size(), producer_stream), "hk_deform_meshes_device");
+  }
   void rebuild_mesh_tree(const HkMeshIndex& mesh, uint32_t mode = HK_TREE_SAH) { check(hk_rebuild_mesh_tree(ctx_.get(), &mesh, mode), "hk_rebuild_mesh_tree"); }
 
   // one frame of the camera's render graph; by_nodes = dispatch by dispatch through the three nodes,

@@ -512,6 +512,12 @@ int hk_scene_builder_alias_table(const hk_scene_builder* b, const HkAliasEntry**
  * of a finished mesh.  Topology and tree links are kept; every tree box becomes the union of the triangle boxes below it (what the
  * device refit computes), the mesh box is re-derived.  The next finish lays the instance level out again from them. */
 int hk_scene_builder_set_mesh_vertices(hk_scene_builder* b, uint32_t mesh_id, const float* positions, const float* normals);
+/* The host twin of HK_DEFORM_RECOMPUTE_NORMALS (hk_deform_meshes_device): the mesh's vertex normals rewritten from its CURRENT
+ * positions by the same rule in the same f32 arithmetic - area-weighted face vectors summed per vertex in ascending triangle, then
+ * corner order; a vertex whose sum is all zero keeps its normal.  Like hk_scene_builder_set_mesh_vertices it un-finishes the mesh
+ * level; an unknown id returns HK_E_INVALID with the builder unchanged.  set_mesh_vertices(positions, NULL) and then this call bring
+ * the host's mirror back after such a device deformation. */
+int hk_scene_builder_recompute_mesh_normals(hk_scene_builder* b, uint32_t mesh_id);
 /* The host twin of hk_rebuild_mesh_tree (HK_TREE_SAH): the mesh's tree built again over its CURRENT triangles, as
  * hk_scene_builder_add_mesh would build it for these positions (`bvh` 0.7.1 BVH::build), every navigator box then the union of the two
  * boxes below it as hk_scene_builder_set_mesh_vertices forms them.  Primitives, vertices and the mesh box are untouched; the node
@@ -674,6 +680,40 @@ typedef struct HkMeshDeform {
   const float* normals;  /* VERTICES: count x 3, or NULL = keep.  SKIN: must be NULL */
 } HkMeshDeform;
 int hk_deform_meshes(hk_ctx* ctx, const HkMeshDeform* items, uint32_t n);
+/* ... and the same batch with its SOURCES IN DEVICE MEMORY (a cloth solver's positions, a joint palette animated on the GPU): the call
+ * leaves the context in every respect as hk_deform_meshes leaves it when given the same values from host memory - device bytes, what
+ * is stale, what is refused afterwards, how it composes with refits, rebuilds, hk_add_meshes and frames in flight.  Only the item
+ * table travels through pinned staging; positions, normals and palettes are read where they lie, so a stride names a column slice of a
+ * larger state tensor ([n, 8], say) without a copy.  Positions and normals need 4-byte alignment, palettes 16-byte alignment.
+ *   Ordering.  With producer_stream (a hipStream_t) != NULL the context's stream waits for an event recorded on that stream at the
+ * call, before its first launch, and the producer stream then waits for an event recorded behind the last kernel that reads the
+ * sources (the vertex kernel; palettes are copied to the mesh's own memory before it): the caller may overwrite its buffers in stream
+ * order right after the call returns.  No host wait.  With NULL the caller has ordered itself (the rule of hk_cast_rays_device).
+ *   Validation.  Every check of hk_deform_meshes, and HK_E_INVALID for: a source pointer that is neither memory of the context's
+ * device nor host memory the device can access (plain pageable memory is refused: a mistaken pointer cannot fault the device) or whose
+ * extent leaves its allocation, a misaligned pointer, a bad stride, an unknown flag bit, HK_DEFORM_RECOMPUTE_NORMALS on a skin item or
+ * together with normals.  The whole batch is validated before anything is enqueued.
+ *   HK_DEFORM_RECOMPUTE_NORMALS (VERTICES items): after the item's positions have landed its vertex normals are recomputed, all in f32
+ * in the stated order, without contraction.  The face vector of triangle t with corners p0, p1, p2 (the order of HkPrimitive.vertices),
+ * e1 = p1 - p0, e2 = p2 - p0, is f = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x), un-normalised (the sum is
+ * area-weighted).  The normal of vertex v is s = ((+0 + f[t_1]) + f[t_2]) + ... per component over the corners that name v, in
+ * ascending triangle index and then corner index; (s.x, s.y, s.z, 0) is stored un-normalised as every other path stores normals.  If
+ * all three components of s compare equal to zero (a vertex no triangle names included) the vertex keeps its current normal.  The
+ * result does not depend on scheduling (a gather over a per-mesh corner list, built on the mesh's first such call - one wait there).
+ * hk_scene_builder_recompute_mesh_normals is the host twin.  A batch with a flagged item is six launches, five otherwise. */
+#define HK_DEFORM_RECOMPUTE_NORMALS 1u
+typedef struct HkMeshDeformDevice {
+  HkMeshIndex mesh;
+  uint32_t    kind;            /* HK_DEFORM_VERTICES / HK_DEFORM_SKIN */
+  uint32_t    count;           /* VERTICES: n_vertices.  SKIN: n_joints */
+  const void* data;            /* DEVICE memory.  VERTICES: positions, 3 floats per vertex at data + v * data_stride.  SKIN: count x 16 floats, column-major, contiguous */
+  const void* normals;         /* DEVICE memory, 3 floats per vertex at normals + v * normals_stride, or NULL */
+  uint32_t    data_stride;     /* bytes; 0 = packed (12).  VERTICES only: >= 12, a multiple of 4.  SKIN: 0 or 64 */
+  uint32_t    normals_stride;  /* bytes; 0 = packed (12) */
+  uint32_t    flags;           /* HK_DEFORM_RECOMPUTE_NORMALS */
+  uint32_t    _pad;
+} HkMeshDeformDevice;          /* 56 bytes */
+int hk_deform_meshes_device(hk_ctx* ctx, const HkMeshDeformDevice* items, uint32_t n, void* producer_stream);
 /* ... and the REBUILD of one mesh's tree on the device, for when refits have degraded it (a skinned character far from its bind pose,
  * a cloth folded onto itself): a new tree over the mesh's current triangle boxes, written in place over the mesh's nodes in the
  * mesh-level region - ordering 0 in the builder's left-before-right order, orderings 1-7 by the rule of hk_bvh_rethread, single-leaf

@@ -43,9 +43,9 @@ int hk_debug_read_mesh_geometry(hk_ctx* ctx, const HkMeshIndex* mesh, float* pos
 /* Test hook: the emitter records (8 floats each: position xyz, radius, surface area, then instance, alias offset, alias count as u32
  * bits) and the alias table (probability, index bits) as the device holds them; *n_records / *n_alias receive the counts. */
 int hk_debug_read_emitters(hk_ctx* ctx, float* records, uint32_t records_cap, uint32_t* n_records, float* alias, uint32_t alias_cap, uint32_t* n_alias);
-/* Test hook: what the last hk_deform_meshes of this context did and what followed it - out[0] items, out[1] their vertices, out[2] their
- * triangles, out[3] what the call enqueued (kernel launches + asynchronous memsets and copies; stream waits and event records not
- * counted), out[4] the kernel launches of the last propagation of deformed meshes' boxes to the instance level (the flush in front of a
+/* Test hook: what the last hk_deform_meshes / hk_deform_meshes_device of this context did and what followed it - out[0] items, out[1]
+ * their vertices, out[2] their triangles, out[3] what the call enqueued (kernel launches + asynchronous memsets and copies; stream waits
+ * and event records not counted: five, six where an item recomputed its normals), out[4] the kernel launches of the last propagation of deformed meshes' boxes to the instance level (the flush in front of a
  * frame or a read, after single-mesh calls too), out[5] the kernel launches of the last derivation of wide records.  out[0..3] are zero
  * until a batch ran; a refused batch leaves them as they were. */
 int hk_debug_last_deform(hk_ctx* ctx, uint32_t out[6]);
