@@ -160,7 +160,9 @@ int free_screen(hk_ctx* c) {
     if (c->kept_tiles[k]) (void)hipFree(c->kept_tiles[k]);
     c->kept_tiles[k] = nullptr;
     c->empty_ok[k] = c->lights_ok[k] = c->kept_ok[k] = c->kept_lights[k] = false;
+    c->post_kept[k] = c->post_tone_kept[k] = c->post_tone[k].ok = false;
   }
+  c->post_last.ok = false;
   c->pixel_identity = false;
   if (c->wf_mem) (void)hipFree(c->wf_mem);
   c->wf_mem = nullptr;
@@ -285,6 +287,7 @@ GBuffer make_gbuffer(const hk_ctx* c) {
   g.empty_out = nullptr;
   g.empty_in = nullptr;
   g.kept_out = nullptr;
+  g.post_in = nullptr;
   g.tiles_x = c->tiles_x;
   return g;
 }
@@ -308,8 +311,13 @@ const uint8_t* known_empty_plane(hk_ctx* c, int y0, int y1, bool demodulation = 
   c->empty_plane_launches += 1;
   return c->empty_tiles[p];
 }
+void forget_post(hk_ctx* c) {
+  c->post_last.ok = false;
+  for (int k = 0; k < 2; ++k) c->post_kept[k] = c->post_tone_kept[k] = c->post_tone[k].ok = false;
+}
 void forget_empty_tiles(hk_ctx* c) {
   for (int k = 0; k < 2; ++k) c->empty_ok[k] = c->lights_ok[k] = c->kept_ok[k] = c->kept_lights[k] = false;
+  forget_post(c);
 }
 // Background stores (hk_context.hpp kept_tiles): a wave of an empty tile may skip a store only if the launch that last wrote that
 // PHYSICAL plane stored the background's constant to the tile and nothing has written the plane since.  The G-buffer planes and their
@@ -340,6 +348,45 @@ bool kept_grant(hk_ctx* c, bool had_plane, bool write_plane, bool* lights) {
 const uint8_t* kept_plane_for_lights(hk_ctx* c, const uint8_t* empty_in) {
   const uint32_t p = c->mapped_parity & 1u;
   return empty_in && c->kept_ok[p] && c->kept_lights[p] && c->kept_frame[p] == c->frame.number ? c->kept_tiles[p] : empty_in;
+}
+// Post stores.  Demodulation and the a-trous levels write planes that are NOT twinned by frame parity (the private and exposed internal
+// planes, the internal variance, denoise_render): what a tile of them holds is what the LAST post chain left there, so a wave may skip
+// its constant stores iff the tile was empty in the frame of that chain and is empty again (HK_TILE_POST_KEPT, formed by the primary
+// rays from the OTHER parity's empty-tile plane: post_grant), iff that chain stored the constants this one would store, and iff
+// nothing has written the planes since.  post_grant hands the primary rays the other parity's plane only if the kept grant holds (so
+// all of its conditions do: ratio 1, one band, no communicator, no ray counting, no host-rasterised G-buffer ...), the plane is trusted
+// (empty_ok) and was written by the very frame whose post chain ran last (PostRecord::serial; ok = through hk_frame_stage over every
+// row of a single band, every launch with the plane), and the plane's writer is ordered in front of these rays.  The post stage then
+// asks again (post_stage_begin): that chain must still be the last one (PostRecord::id), and must have had this one's launch shape -
+// denoise on (a record exists), the same channel count (it decides which planes a channel uses) and the same clear colour; the fused
+// tone-mapped output is present in every chain of hk_frame_stage.  The writers of these planes are the five launches themselves
+// (hk_frame_stage: replaces the record; hk_pass_run: forgets), hk_write_buffer and a host that holds hk_device_ptr (forget), hk_resize
+// (free_screen) and a communicator's exchanges (no kept grant); the anti-aliasing, upscale and overlay stages only read them.
+// The tone-mapped image IS twinned (hk_frame_begin swaps it with previous_tone_mapped): its store is skipped only where the tile
+// carries HK_TILE_KEPT as well - empty in the last frame of this parity, the kept grant's own bit - and post_tone[parity] says that
+// that frame's chain wrote this clear colour into this physical plane.  Whatever this cannot prove takes the long way.
+#ifndef HK_KEPT_POST
+#define HK_KEPT_POST 1   // (A/B: 0 = the post chain stores everything)
+#endif
+const uint8_t* post_grant(hk_ctx* c, bool keep, bool pre_pipelined) {
+  const uint32_t p = c->mapped_parity & 1u, q = p ^ 1u;
+  const hk_ctx::PostRecord& last = c->post_last;
+  if (!HK_KEPT_POST || !keep || !c->empty_ok[q] || !c->empty_tiles[q] || !last.ok || last.parity != q || last.serial != c->empty_serial[q]) return nullptr;
+  if (pre_pipelined && !c->pre_last_pipelined) return nullptr;   // (that frame's rays ran on the main stream: the pre stream is not behind them)
+  return c->empty_tiles[q];
+}
+// ... and for the post stage that begins: may its launches be handed the kept-tile plane, and may level 3 skip the tone-mapped image?
+void post_stage_begin(hk_ctx* c, const hk_ctx::PostRecord& now, bool full_rows) {
+  const uint32_t p = c->mapped_parity & 1u;
+  auto same_shape = [&](const hk_ctx::PostRecord& r) { return r.ok && r.nch == now.nch && memcmp(r.clear, now.clear, sizeof(now.clear)) == 0; };
+  c->post_use = HK_KEPT_POST && full_rows && c->kept_ok[p] && c->kept_frame[p] == c->frame.number && c->post_kept[p] && same_shape(c->post_last) &&
+                c->post_last.id == c->post_against[p];
+  c->post_tone_use = c->post_use && c->post_tone_kept[p] && same_shape(c->post_tone[p]) && c->post_tone[p].id == c->post_tone_against[p] &&
+                     c->post_tone[p].tone_plane == now.tone_plane;
+  c->post_last.ok = c->post_tone[p].ok = false;   // (this stage writes the planes: whatever it leaves is described when it has run)
+}
+const uint8_t* kept_plane_for_post(hk_ctx* c, const uint8_t* empty_in) {
+  return empty_in && c->post_use ? c->kept_tiles[c->mapped_parity & 1u] : empty_in;
 }
 // A band of a sharded frame whose history halo is not empty parks the scatter stores of its temporal dispatches instead of
 // racing them into its local copy of previous_spatial: the neighbours need them (and this band theirs) before spatial_reuse
@@ -534,7 +581,7 @@ int run_demodulation_fused(hk_ctx* c, uint32_t nch, int y0, int y1) {
     d.output[ch] = (uint2*)dn_internal(c, nch, ch, 0);
     d.internal_variance[ch] = dn_variance(c, nch, ch);
   }
-  d.empty_tiles = known_empty_plane(c, y0, y1, true);
+  d.empty_tiles = kept_plane_for_post(c, known_empty_plane(c, y0, y1, true));
   d.tiles_x = c->tiles_x;
   launch_demodulation(c->stream, (int)nch, fr, d, y0, y1);
   HK_HIP(hipGetLastError());
@@ -558,8 +605,9 @@ int run_denoise_fused(hk_ctx* c, uint32_t nch, int level, int y0, int y1, bool w
     d.tone_mapped = (uint2*)c->buf[HK_BUF_TONE_MAPPED];
     memcpy(d.clear_color, c->frame.clear_color, sizeof(d.clear_color));
   }
-  d.empty_tiles = known_empty_plane(c, y0, y1);
+  d.empty_tiles = kept_plane_for_post(c, known_empty_plane(c, y0, y1));
   d.tiles_x = c->tiles_x;
+  d.tone_kept = d.tone_mapped && c->post_tone_use ? 1 : 0;
   launch_denoise(c->stream, level, (int)nch, 0, fr, d, y0, y1);
   HK_HIP(hipGetLastError());
   return HK_OK;
@@ -1577,7 +1625,8 @@ int hk_frame_stage(hk_ctx* c, uint32_t stage, const HkSettings* st, uint32_t fla
     c->host_wrote = false;
     bool keep_lights = false;
     const bool keep = kept_grant(c, had_plane, write_plane, &keep_lights);
-    c->empty_ok[parity] = c->lights_ok[parity] = c->kept_ok[parity] = c->kept_lights[parity] = false;
+    const uint64_t old_serial = c->empty_serial[parity];   // (of the frame that last wrote this parity's planes: what HK_TILE_KEPT refers to)
+    c->empty_ok[parity] = c->lights_ok[parity] = c->kept_ok[parity] = c->kept_lights[parity] = c->post_kept[parity] = c->post_tone_kept[parity] = false;
     if (!(flags & HK_FRAME_EXTERNAL_GBUFFER)) {
       if (f1 > f0) {  // the prepass also fills the albedo of every pixel it covers (a superset of the rows albedo needs)
         const DFrame fr = make_dframe(c);
@@ -1587,11 +1636,18 @@ int hk_frame_stage(hk_ctx* c, uint32_t stage, const HkSettings* st, uint32_t fla
           g.empty_out = c->empty_tiles[parity];
           c->empty_ok[parity] = true;
           c->empty_frame[parity] = c->frame.number;
+          c->empty_serial[parity] = ++c->stage_serial;
           if (keep) {  // (the tile's old byte can be trusted: tiles that stay empty keep what they hold)
             g.kept_out = c->kept_tiles[parity];
             c->kept_ok[parity] = true;
             c->kept_lights[parity] = keep_lights;
             c->kept_frame[parity] = c->frame.number;
+            if ((g.post_in = post_grant(c, keep, pre_pipelined))) {  // (post stores: the tile's byte of the frame before this one, too)
+              c->post_kept[parity] = true;
+              c->post_against[parity] = c->post_last.id;
+              c->post_tone_kept[parity] = c->post_tone[parity].ok && c->post_tone[parity].serial == old_serial;
+              c->post_tone_against[parity] = c->post_tone[parity].id;
+            }
           }
         }
         unsigned long long* counters = (c->flags & HK_CTX_COUNT_RAYS) ? c->d_counters : nullptr;
@@ -1608,13 +1664,15 @@ int hk_frame_stage(hk_ctx* c, uint32_t stage, const HkSettings* st, uint32_t fla
           HK_HIP(hipEventRecord(c->pre_done, c->pre_stream));
           HK_HIP(hipStreamWaitEvent(c->stream, c->pre_done, 0));
           c->prepasses_pipelined += 1;
-        } else if (c->pre_stream && scene_written) {
+        } else if (c->pre_stream && (scene_written || g.post_in)) {
           // scene memory was written since the last frame - uploads and refits on the main stream behind the previous frame's spatial pass,
           // the wide records derived again just above: whichever later frame pipelines its primary rays (they may start as early as this
-          // frame's own) must find all of it done
+          // frame's own) must find all of it done.  (post_in: these rays READ the other parity's empty-tile plane, which the next
+          // frame's rays write)
           HK_HIP(hipEventRecord(c->pre_scene_mark, c->stream));
           c->pre_scene_marked = true;
         }
+        c->pre_last_pipelined = pre_pipelined;
         albedo_done = true;
       }
     } else if (f1 > f0) {  // host-rasterised G-buffer: only the derived planes are ours to fill
@@ -1681,8 +1739,22 @@ int hk_frame_stage(hk_ctx* c, uint32_t stage, const HkSettings* st, uint32_t fla
     // (hk_frame_render on a band with a communicator has moved to the post stream already: exchange B belongs in front of demodulation)
     bool pipelined = c->post_forked;
     if (!pipelined && (rc = post_begin(c, st, &pipelined))) return rc;
+    // post stores (post_grant): this stage writes the post chain's planes - the record of what they hold is replaced by this stage's own,
+    // and only if all five launches below are handed a plane over every row
+    const uint32_t post_parity = c->mapped_parity & 1u;
+    hk_ctx::PostRecord post_now{};
+    post_now.id = ++c->post_counter;
+    post_now.serial = c->empty_serial[post_parity];
+    post_now.parity = post_parity;
+    post_now.nch = st->indirect_bounces == 0 ? 2u : 3u;
+    memcpy(post_now.clear, c->frame.clear_color, sizeof(post_now.clear));
+    post_now.tone_plane = c->buf[HK_BUF_TONE_MAPPED];
+    const bool post_full = c->band_count == 1 && b0 == 0 && b1 == c->RH;
+    post_stage_begin(c, post_now, post_full && st->denoise);
+    struct PostUse { hk_ctx* c; ~PostUse() { c->post_use = c->post_tone_use = false; } } post_use_{c};
     if (st->denoise) {                               // post_process.rs:1190-1224
       const uint32_t nch = st->indirect_bounces == 0 ? 2u : 3u;  // post_process.rs:949-954
+      const uint64_t handed_before = c->empty_plane_launches;
       // the reference's per-channel loop, with the channels of each step fused into one launch.  Round 6: demodulation too runs on
       // the post stream - the render / variance planes it reads are double-buffered by frame parity, the next frame's light passes
       // write the other set - so a frame's main stream ends with its spatial pass (a band: with exchange A and its spatial pass)
@@ -1691,6 +1763,11 @@ int hk_frame_stage(hk_ctx* c, uint32_t stage, const HkSettings* st, uint32_t fla
       if (!rc) rc = run_denoise_fused(c, nch, 1, clampr(b0 - 3), clampr(b1 + 3));
       if (!rc) rc = run_denoise_fused(c, nch, 2, clampr(b0 - 1), clampr(b1 + 1));
       if (!rc) rc = run_denoise_fused(c, nch, 3, b0, b1, true);  // + tone mapping (post_process.rs:1226-1234) in the same launch
+      if (!rc && post_full && c->empty_plane_launches - handed_before == 5u) {  // (a plane in every launch: each stored the constants, or proved them there)
+        post_now.ok = true;
+        c->post_last = post_now;
+        if (nch == (c->frame.indirect_bounces != 0u ? 3u : 2u)) c->post_tone[post_parity] = post_now;   // (run_denoise_fused: the fused tone-mapped output)
+      }
       if (c->timing_mask) {
         (void)hipEventRecord(c->frame_stop, c->stream);
         c->frame_timed = true;
@@ -1975,6 +2052,8 @@ int hk_device_ptr(hk_ctx* c, uint32_t buffer, void** ptr, size_t* bytes) {
     forget_empty_tiles(c);
     c->host_wrote = true;
   }
+  // (... and a plane the post chain writes: its waves no longer skip their constant stores - post_grant)
+  if ((buffer >= HK_BUF_DENOISE_INTERNAL0 && buffer <= HK_BUF_TONE_MAPPED) || buffer == HK_BUF_PREVIOUS_TONE_MAPPED) forget_post(c);
   // (the previous frame's position plane in the host's hands: its depth plane is copied again in front of the next anti-aliasing
   // dispatch.  The current frame's derived planes follow HK_FRAME_EXTERNAL_GBUFFER - hikari_hip.h)
   if (buffer == HK_BUF_PREVIOUS_POSITION) c->prev_depth_dirty = true;

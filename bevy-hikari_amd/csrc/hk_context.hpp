@@ -253,6 +253,27 @@ struct hk_ctx {
   uint8_t* kept_tiles[2] = {nullptr, nullptr};
   bool kept_ok[2] = {false, false}, kept_lights[2] = {false, false};
   uint32_t kept_frame[2] = {0, 0};
+  // Post stores (DESIGN 4 "Empty tiles"; context.hip post_grant holds the rule).  The planes demodulation and the a-trous levels write are
+  // NOT twinned by frame parity: what they hold is what the last post chain left, whichever frame's it was.  post_last describes that
+  // chain - ok only if it ran through hk_frame_stage over every row with the empty-tile plane in all five launches; every later post
+  // stage replaces it, everything that ends the other grants clears it.  The tone-mapped image IS twinned (hk_frame_begin): post_tone[p]
+  // is the same record for the chain that last wrote parity p's physical plane.  empty_serial[p]: which TEMPORAL stage wrote
+  // empty_tiles[p] (frame numbers may repeat).  post_kept / post_tone_kept: this parity's kept-tile plane carries HK_TILE_POST_KEPT,
+  // formed against the post chain post_against / post_tone_against (PostRecord::id).
+  struct PostRecord {
+    bool ok = false;
+    uint64_t id = 0;          // of the post stage that made it (post_counter)
+    uint64_t serial = 0;      // empty_serial of the frame it belonged to
+    uint32_t parity = 0, nch = 0;
+    float clear[4] = {0, 0, 0, 0};
+    const void* tone_plane = nullptr;   // the physical plane its level 3 wrote the tone-mapped image to
+  };
+  PostRecord post_last{}, post_tone[2]{};
+  uint64_t stage_serial = 0, post_counter = 0, empty_serial[2] = {0, 0};
+  bool post_kept[2] = {false, false}, post_tone_kept[2] = {false, false};
+  uint64_t post_against[2] = {0, 0}, post_tone_against[2] = {0, 0};
+  bool post_use = false, post_tone_use = false;   // for the five launches of the post stage that is running
+  bool pre_last_pipelined = false;       // the last primary rays ran on the pre stream
   bool pixel_identity = false;           // at ratio 1 the kernels' coordinate chains map every pixel to itself (certify_pixel_identity, per hk_resize)
   bool host_wrote = false;               // hk_write_buffer since the last primary rays: the next frame keeps today's path
   bool in_frame_stage = false;           // hk_frame_stage is launching (hk_pass_run's hand-driven passes never get the plane)

@@ -31,6 +31,11 @@ struct GBuffer {
   // every plane holds the background's constants already.  A light kernel whose own planes of this parity are in the same state is
   // handed this plane as its empty_in (otherwise the empty-tile plane, which never carries the bit) and skips its constant stores
   uint8_t* kept_out;
+  // the OTHER parity's empty-tile plane, or null: the planes the post chain writes are not twinned by frame parity (the tone-mapped image
+  // apart), so what they hold in a tile is what the frame before this one left there.  Where the context vouches for that frame's plane
+  // and post chain (context.hip post_grant), the byte written to kept_out carries HK_TILE_POST_KEPT too if every ray of the tile missed
+  // in that frame and in this one; demodulation and the a-trous levels are then handed the kept-tile plane and skip their constant stores
+  const uint8_t* post_in;
   int tiles_x;
 };
 // Uniform-tile store elision.  The reference stores a packed reservoir to up to three buffers for EVERY pixel of EVERY light
@@ -209,7 +214,7 @@ struct DemodTargets {
   const uint2* render[3];               // light render per channel
   uint2* output[3];                     // internal_texture_0 per channel
   float* internal_variance[3];
-  const uint8_t* empty_tiles;           // the frame's empty-tile plane (GBuffer), or null
+  const uint8_t* empty_tiles;           // the frame's empty-tile plane (GBuffer), or null - or its kept-tile plane (context.hip post_grant)
   int tiles_x;
 };
 struct DenoiseTargets {
@@ -224,8 +229,11 @@ struct DenoiseTargets {
   // (f16-rounded) channel outputs and write tone_mapping_output (the frame path); null = separate dispatch
   uint2* tone_mapped;
   float clear_color[4];
-  const uint8_t* empty_tiles;                   // the frame's empty-tile plane (GBuffer), or null
+  const uint8_t* empty_tiles;                   // the frame's empty-tile plane (GBuffer), or null - or its kept-tile plane (context.hip post_grant)
   int tiles_x;
+  // the tone-mapped image IS twinned by frame parity: its store may be skipped only in a tile that carries HK_TILE_KEPT as well as
+  // HK_TILE_POST_KEPT, and only if the last frame of this parity wrote this clear colour there (context.hip post_grant); 0 = always store
+  int tone_kept;
 };
 
 // what an a-trous tap needs of a G-buffer pixel besides its depth: the normal exactly as the filter derives it
@@ -259,9 +267,12 @@ __device__ __forceinline__ int wave_tile(const Pixel& px, int tiles_x) {
 }
 // the empty-tile plane: is the 8x8 tile of this wave (pixel_of_thread; called by its valid lanes only - their tile lies in the image) one
 // whose primary rays all missed this frame?  Wave-uniform, and known to be: the byte is read through the first lane.
-// The byte itself: 0 = not known to be empty (or no plane), HK_TILE_EMPTY = empty, HK_TILE_EMPTY | HK_TILE_KEPT = empty and kept (GBuffer).
+// The byte itself: 0 = not known to be empty (or no plane), HK_TILE_EMPTY = empty; in the kept-tile plane also HK_TILE_KEPT = empty in the
+// last frame of this parity too (the parity's twinned planes hold the background's constants) and HK_TILE_POST_KEPT = empty in the frame
+// before this one too (the post chain's planes, which every frame writes, hold theirs) - GBuffer.  Neither is ever set without HK_TILE_EMPTY.
 #define HK_TILE_EMPTY 1
 #define HK_TILE_KEPT 2
+#define HK_TILE_POST_KEPT 4
 __device__ __forceinline__ int wave_tile_state(const uint8_t* __restrict__ plane, const Pixel& px, int tiles_x) {
   if (!plane) return 0;
   const int tile = __builtin_amdgcn_readfirstlane(wave_tile(px, tiles_x));
@@ -271,13 +282,18 @@ __device__ __forceinline__ bool wave_tile_known_empty(const uint8_t* __restrict_
 // ... and for the row-shaped waves of the stencil kernels (pixel_of_thread_rows): do this pixel and its neighbours up to `reach` pixels
 // away that lie in the image (reach <= 8: the four corners of the window name every tile it touches) all lie in empty tiles?  Per lane
 // (a wave is one row of 64 pixels there: y and with it the two tile rows are wave-uniform and kept in scalar registers)
-__device__ __forceinline__ bool pixel_known_empty(const uint8_t* __restrict__ plane, int tiles_x, int x, int y, int reach, int width, int height) {
+// The byte itself: the AND of the bytes of every tile within reach (every non-zero byte carries HK_TILE_EMPTY: 0 = some tile is not known
+// to be empty; HK_TILE_KEPT / HK_TILE_POST_KEPT survive only where every tile within reach has them)
+__device__ __forceinline__ int pixel_tile_bits(const uint8_t* __restrict__ plane, int tiles_x, int x, int y, int reach, int width, int height) {
   const int yu = __builtin_amdgcn_readfirstlane(y);
   const uint8_t* __restrict__ row0 = plane + (max(yu - reach, 0) >> 3) * tiles_x;
   const uint8_t* __restrict__ row1 = plane + (min(yu + reach, height - 1) >> 3) * tiles_x;
-  if (reach == 0) return row0[(uint32_t)x >> 3] != 0;
+  if (reach == 0) return row0[(uint32_t)x >> 3];
   const uint32_t x0 = (uint32_t)max(x - reach, 0) >> 3, x1 = (uint32_t)min(x + reach, width - 1) >> 3;  // (unsigned: 32-bit offsets from the scalar row address)
-  return (row0[x0] & row0[x1] & row1[x0] & row1[x1]) != 0;
+  return row0[x0] & row0[x1] & row1[x0] & row1[x1];
+}
+__device__ __forceinline__ bool pixel_known_empty(const uint8_t* __restrict__ plane, int tiles_x, int x, int y, int reach, int width, int height) {
+  return pixel_tile_bits(plane, tiles_x, x, y, reach, width, height) != 0;
 }
 __device__ __forceinline__ bool tile_holds(const TileMeta* m, int tile, unsigned long long id) {
   const TileMeta v = m[tile];

@@ -130,7 +130,11 @@ __global__ __launch_bounds__(256, (LDS == 4 ? HK_PREPASS_WIDE_WAVES : (LDS == 2 
       kept = was_empty && all_missed;
       if (wave_leader()) {
         g.empty_out[tile] = all_missed ? (uint8_t)1 : (uint8_t)0;
-        if (!COUNT && g.kept_out) g.kept_out[tile] = (uint8_t)(all_missed ? (kept ? HK_TILE_EMPTY | HK_TILE_KEPT : HK_TILE_EMPTY) : 0);
+        if (!COUNT && g.kept_out) {
+          // (g.post_in: the other parity's plane, the frame before this one - read here, behind the walk, so that nothing more is live across it)
+          const int post_kept = all_missed && g.post_in && g.post_in[tile] != 0 ? HK_TILE_POST_KEPT : 0;
+          g.kept_out[tile] = (uint8_t)(all_missed ? (kept ? HK_TILE_EMPTY | HK_TILE_KEPT : HK_TILE_EMPTY) | post_kept : 0);
+        }
       }
     }
     prepass_store(sc, fr, pp, g, px.x, px.y, ray, hit, kept);

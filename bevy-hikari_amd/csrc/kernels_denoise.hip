@@ -56,7 +56,13 @@ __global__ __launch_bounds__(256) void k_demodulation(DFrame fr, DemodTargets d,
   // handed over only where every texel and tap address below is certified to be the pixel's own or a neighbour's, and where this frame's
   // light passes ran over these rows - context.hip known_empty_plane): the albedo is +0, so the albedo < 0.01 select yields 0 whatever
   // the render plane holds, and every variance tap was written 0.0f by the three light kernels, so each sum + kernel * max(v, 0) stays +0.
-  if (d.empty_tiles && __ballot(!pixel_known_empty(d.empty_tiles, d.tiles_x, x, y, 1, fr.rw, fr.rh)) == 0ull) {
+  // Where the plane is the kept-tile plane (context.hip post_grant) and every tile within reach of every pixel of the wave carries
+  // HK_TILE_POST_KEPT, the frame before this one found the same tiles empty and left these very constants in the two planes, which
+  // nothing has written since: the wave stores nothing.  (One lane without the bit and the whole wave stores; bits < HK_TILE_POST_KEPT:
+  // a byte without the bit is at most HK_TILE_EMPTY | HK_TILE_KEPT.)
+  const int tile_bits = d.empty_tiles ? pixel_tile_bits(d.empty_tiles, d.tiles_x, x, y, 1, fr.rw, fr.rh) : 0;
+  if (__ballot(tile_bits == 0) == 0ull) {
+    if (__ballot(tile_bits < HK_TILE_POST_KEPT) == 0ull) return;
     // (the stores take 32-bit byte offsets from the planes' scalar addresses: 8 x index < 2^32 for every size hk_resize accepts)
     const uint32_t at8 = (uint32_t)index * 8u, at4 = (uint32_t)index * 4u;
 #pragma unroll
@@ -136,10 +142,17 @@ __global__ __launch_bounds__(256, HK_DENOISE_WAVES) void k_denoise(DFrame fr, De
   const int x = px.x, y = px.y, index = x + fr.rw * y;
   // A wave whose pixels all lie in tiles this frame's primary rays proved empty: the centre texel is the pixel's own (certified by the
   // context where it hands the plane over) and holds depth 0 - the background stores below, without the coordinate chains and the loads.
-  if (d.empty_tiles && __ballot(!pixel_known_empty(d.empty_tiles, d.tiles_x, x, y, 0, fr.rw, fr.rh)) == 0ull) {
+  // With the kept-tile plane (context.hip post_grant): a wave whose tiles all carry HK_TILE_POST_KEPT stores nothing to the level's output
+  // planes - the frame before this one left these zeros there; the tone-mapped image, which is twinned by frame parity, is skipped only
+  // where the tiles carry HK_TILE_KEPT as well and the context vouches for the last frame of this parity (d.tone_kept).
+  const int tile_bits = d.empty_tiles ? pixel_tile_bits(d.empty_tiles, d.tiles_x, x, y, 0, fr.rw, fr.rh) : 0;
+  if (__ballot(tile_bits == 0) == 0ull) {
+    if (__ballot(tile_bits < HK_TILE_POST_KEPT) != 0ull) {
 #pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) d.output[ch][index] = make_uint2(0u, 0u);
-    if (LEVEL == 3 && d.tone_mapped) d.tone_mapped[index] = pack_f16x4(F4(d.clear_color[0], d.clear_color[1], d.clear_color[2], d.clear_color[3]));
+      for (int ch = 0; ch < NCH; ++ch) d.output[ch][index] = make_uint2(0u, 0u);
+    }
+    if (LEVEL == 3 && d.tone_mapped && !(d.tone_kept && __ballot(tile_bits != (HK_TILE_EMPTY | HK_TILE_KEPT | HK_TILE_POST_KEPT)) == 0ull))
+      d.tone_mapped[index] = pack_f16x4(F4(d.clear_color[0], d.clear_color[1], d.clear_color[2], d.clear_color[3]));
     return;
   }
   // The stencil's three columns and three rows: the uv of a tap, whether it lies in the image and the G-buffer texel under it are

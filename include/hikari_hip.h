@@ -1172,6 +1172,11 @@ int hk_write_buffer(hk_ctx* ctx, uint32_t buffer, const void* src, size_t bytes)
  * none again, the G-buffer, albedo, render and variance planes keep the background's constants that frame stored.  So a host that
  * writes one of them (the PREVIOUS ids included) through a pointer it kept, outside a HK_FRAME_EXTERNAL_GBUFFER frame, asks for the
  * pointer again after writing, or uses hk_write_buffer: either makes the following frames store every pixel again.
+ * The same holds for the planes the denoiser and tone mapping write - HK_BUF_DENOISE_INTERNAL0..3, HK_BUF_DENOISE_INTERNAL_VARIANCE,
+ * HK_BUF_DENOISE_RENDER0..2, HK_BUF_TONE_MAPPED and HK_BUF_PREVIOUS_TONE_MAPPED: where a tile had no geometry in the frame before and
+ * has none again (the tone-mapped image: in the last frame of the same parity as well) they keep the constants that frame stored.
+ * hk_write_buffer into ANY plane, or asking for the pointer of one of these ids, makes the following frames store every pixel of
+ * them again.
  * Asking for HK_BUF_PREVIOUS_POSITION makes the next anti-aliasing dispatch copy that plane's depths again (as after
  * hk_write_buffer); a host that writes it through a pointer it kept asks again after writing, or uses hk_write_buffer. */
 int hk_device_ptr(hk_ctx* ctx, uint32_t buffer, void** ptr, size_t* bytes);
