@@ -143,6 +143,7 @@ int free_screen(hk_ctx* c) {
     if (c->det_winner[k]) (void)hipFree(c->det_winner[k]);
     c->det_winner[k] = nullptr;
     c->det_lite_clean[k] = false;
+    c->pieces_new_frame[k] = true;
   }
   for (uint32_t b = 0; b < HK_BUF_COUNT; ++b) {
     if (c->buf[b]) (void)hipFree(c->buf[b]);
@@ -497,17 +498,19 @@ LightTargets make_light_targets(const hk_ctx* c, int channel) {
   t.serial = 0;
   t.tiles_x = c->tiles_x;
   t.rw = c->RW;
+  t.slots = c->RW * c->RH;
   return t;
 }
 // Attach the tile records of the dispatch's reservoir targets (uniform-tile store elision), or - when this dispatch cannot
 // maintain them (a band of a sharded frame, a row range that does not start on a tile row) - declare the tiles of the buffers
-// it writes unknown.  `spatial_pass`: spatial_reuse reads `current` and writes `spatial` only.
-int attach_tile_meta(hk_ctx* c, LightTargets& t, int channel, bool spatial_pass, int y0, int y1) {
+// it writes unknown.  `spatial_pass`: spatial_reuse reads `current` and writes `spatial` only.  `may_maintain` false: a temporal piece
+// in the full parked form - its stores to previous_spatial arrive with the resolve pass, which keeps no tile records.
+int attach_tile_meta(hk_ctx* c, LightTargets& t, int channel, bool spatial_pass, int y0, int y1, bool may_maintain = true) {
   if (!c->tile_meta[0]) return HK_OK;
   static const int T[3] = {0, 2, 6}, S[3] = {4, 4, 8};
   const int cur = (int)(c->frame.number % 2u), prev = 1 - cur;
   const int k_current = prev + T[channel], k_spatial = prev + S[channel], k_previous_spatial = cur + S[channel];
-  const bool maintain = c->band_count == 1 && (y0 % 8) == 0 && ((y1 % 8) == 0 || y1 == c->RH);  // whole tiles only
+  const bool maintain = may_maintain && c->band_count == 1 && (y0 % 8) == 0 && ((y1 % 8) == 0 || y1 == c->RH);  // whole tiles only
   const size_t mb = (size_t)c->tiles_x * c->tiles_y * sizeof(TileMeta);
   const int written[3] = {spatial_pass ? -1 : k_current, k_spatial, spatial_pass ? -1 : k_previous_spatial};
   for (int k : written) {
@@ -911,9 +914,22 @@ int run_pass(hk_ctx* c, uint32_t pass, uint32_t arg, int y0, int y1) {
       const bool across = parks_across_bands(c);
       if (across || scatter_lite(c, channel)) { const int rc_ = ensure_parked(c, across ? 7u : 1u << channel); if (rc_) return rc_; }
       LightTargets t = make_light_targets(c, channel);
-      { const int rc_ = attach_tile_meta(c, t, channel, false, y0, y1); if (rc_) return rc_; }
+      // part of the rows in the light form's place (hk_context.hpp pieces_new_frame): the light form decides per piece what only the
+      // whole frame knows - a slot's owner in a piece still to come, a parked store of a piece that has run - so the result depended on
+      // the order of the pieces (tests/test_temporal_planes_gpu.py, the `scatter` planes cut into row ranges, last piece first)
+      // (A single context that parks at all parks in the light form - make_light_targets: det_lite = parked && !across - so this covers every
+      // row range of a single context, HK_CTX_DETERMINISTIC_SCATTER included; a band's full form resolves at stage SPATIAL, not here.)
+      const bool pieces = t.det_winner && t.det_lite && (y0 > 0 || y1 < c->RH);
+      if (pieces) t.det_lite = 0;
+      { const int rc_ = attach_tile_meta(c, t, channel, false, y0, y1, !pieces); if (rc_) return rc_; }
       const size_t px = (size_t)c->RW * c->RH;
-      if (t.det_winner && t.det_lite) {  // the light form: the winner plane is handed back clean by every resolve pass; nothing else to prepare
+      if (pieces) {
+        c->det_lite_clean[channel] = false;
+        HK_HIP(hipMemsetAsync(t.det_winner, 0xFF, px * sizeof(int), c->stream));
+        if (c->pieces_new_frame[channel]) HK_HIP(hipMemsetAsync(t.det_to, 0xFF, px * sizeof(int), c->stream));
+        else HK_HIP(hipMemsetAsync(t.det_to + (size_t)y0 * c->RW, 0xFF, (size_t)(y1 - y0) * c->RW * sizeof(int), c->stream));   // (the same rows again)
+        c->pieces_new_frame[channel] = false;
+      } else if (t.det_winner && t.det_lite) {  // the light form: the winner plane is handed back clean by every resolve pass; nothing else to prepare
         if (!c->det_lite_clean[channel]) {
           // first use, or the channel's last dispatch was not in the light form (a band's full form, the spatial pass switched off): no
           // winners, no notes
@@ -921,8 +937,10 @@ int run_pass(hk_ctx* c, uint32_t pass, uint32_t arg, int y0, int y1) {
           HK_HIP(hipMemsetAsync(t.det_to, 0xFF, px * sizeof(int), c->stream));
           c->det_lite_clean[channel] = true;
         }
+        c->pieces_new_frame[channel] = true;
       } else {
         c->det_lite_clean[channel] = false;
+        c->pieces_new_frame[channel] = true;
         if (t.det_winner) {  // nothing parked, no winner: -1 everywhere (a band: in the rows it dispatches - the others arrive with exchange A)
           HK_HIP(hipMemsetAsync(t.det_winner, 0xFF, px * sizeof(int), c->stream));
           if (across) HK_HIP(hipMemsetAsync(t.det_to + (size_t)y0 * c->RW, 0xFF, (size_t)(y1 - y0) * c->RW * sizeof(int), c->stream));
@@ -956,6 +974,8 @@ int run_pass(hk_ctx* c, uint32_t pass, uint32_t arg, int y0, int y1) {
         launch_direct(c->stream, pass == HK_PASS_DIRECT_EMISSIVE, c->scene, fr, g, t, y0, y1, counters);
       // (a band with a history halo resolves at the start of stage SPATIAL, once the neighbours' parked rows are in)
       if (t.det_winner && t.det_lite) launch_resolve_scatter_lite(c->stream, t, fr, c->depth_plane, pass == HK_PASS_INDIRECT, y0, y1);
+      // (a piece: the pixels of the other rows join the winners with the notes they hold, then every parked store that is its slot's highest lands)
+      else if (pieces) launch_resolve_scatter(c->stream, t, 0, (int)px, y0 * c->RW, y1 * c->RW);
       else if (t.det_winner && !across) launch_resolve_scatter(c->stream, t, 0, (int)px, 0, 0);
       break;
     }
@@ -1353,6 +1373,7 @@ int hk_frame_begin(hk_ctx* c, const HkFrame* f, const HkView* v, const HkPreviou
   c->pview = *pv;
   c->lights = *l;
   c->have_frame = true;
+  for (bool& fresh : c->pieces_new_frame) fresh = true;   // (a new frame: the notes of an earlier frame's row pieces no longer count)
   // double-buffered planes follow frame.number % 2 (hikari_hip.h, HkBuffer): idempotent per frame number.
   // Work already enqueued captured its pointers at launch, so swapping here needs no synchronisation.
   if ((f->number & 1u) != c->mapped_parity) {

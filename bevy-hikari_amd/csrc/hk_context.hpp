@@ -231,6 +231,15 @@ struct hk_ctx {
   // HK_CTX_DETERMINISTIC_SCATTER for all three; HK_CTX_RACING_SCATTER restores the reference's race.  det_lite_clean[k]: channel k's
   // winner plane holds -1 everywhere (the light form hands it back that way; the full form of a band does not).
   bool det_lite_clean[3] = {false, false, false};
+  // A temporal dispatch of PART of the rows (hk_pass_run with a row range, single context) cannot take the light form: whether a slot's
+  // owner stores, and which parked store is the highest, is known only once every piece of the frame has run, in whatever order.  Such a
+  // dispatch parks every store (the full form) and resolves over the WHOLE image after each piece, from the notes all pieces of the frame
+  // have left so far.  pieces_new_frame[k]: channel k's notes are an earlier frame's (hk_frame_begin) or another form's - the first piece clears them.
+  // Cost: every piece memsets the winner plane and runs k_join_winners + k_resolve_scatter over all rw * rh pixels - O(pieces x image), the
+  // price of any order; the frame path never takes it.  Limitation: rows dispatched AGAIN within one frame replace their notes, but a store
+  // that an earlier resolve of the same frame already landed in previous_spatial stays there even if the rows' new note no longer aims at
+  // that slot - the pieces of a frame are meant to tile the image once; hk_frame_begin starts over.
+  bool pieces_new_frame[3] = {true, true, true};
   // uniform-tile store elision (hk_kernels.hpp TileMeta): one record per 8x8 tile per reservoir buffer; tile_meta_zero[k] = the
   // device array of buffer k is known to be all zero ("contents unknown" everywhere)
   TileMeta* tile_meta[10] = {};

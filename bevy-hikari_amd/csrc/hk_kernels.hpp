@@ -78,6 +78,7 @@ struct LightTargets {
   uint32_t serial;  // of this dispatch, > 0, increasing
   int tiles_x;      // 8x8 tiles per row of the render image
   int rw;           // render width (reservoir index = x + rw * y)
+  int slots;        // rw * rh: entries the passes index of every reservoir buffer, and of every parked-store plane (hk_light.hpp previous_slot lets no store land beyond)
 };
 // The queue-based schedule of indirect_lit_ambient (kernels_wavefront.hip): what a path carries from stage to stage, in
 // planes indexed by path slot, plus the ray queues and their counters.  `cap` = the most paths one dispatch can have

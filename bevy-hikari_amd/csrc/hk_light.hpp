@@ -43,7 +43,23 @@ __device__ __forceinline__ DScene stage_scene(const DScene& sc) {
   }
 }
 
-// every store to previous_spatial goes through here: the reference lets them race; the verification mode parks them
+// Where a pixel's rejected history goes: the slot previous_uv addresses, and whether a store there lands.  The reference stores
+// where |uv - 0.5| <= 0.5 (light.wgsl:1092-1095, 1199-1202, 1456-1459) but loads where it is < 0.5 (181-190): a previous_uv.y of exactly
+// 1 - or an x of exactly 1 on the last row - forms a slot one row PAST the buffer and the parked planes (rw * rh entries each).  A WGSL
+// runtime array drops that store; so does every scatter form here: such a slot does not land.  An x of exactly 1 on any other row stays
+// what the reference makes of it - column 0 of the next row, in range.
+// (The slot in unsigned arithmetic: off screen i32() saturates - a uv of 1e9 or Inf - and rw * 2147483647 overflows a signed int.  The
+// range test rides on the y comparison as its bound, a select and no branch of its own: as one more condition in front of the store it
+// made the compiler split everything behind the store by whether the history was refused - k_indirect<true, false, 1> 7 946 -> 8 314
+// VALU instructions, the frame +0.6 %.)
+__device__ __forceinline__ bool previous_slot(const DFrame& fr, const LightTargets& t, f2 previous_uv, int* slot) {
+  *slot = (int)((uint32_t)f32_to_i32(previous_uv.x * (float)fr.rw) + (uint32_t)fr.rw * (uint32_t)f32_to_i32(previous_uv.y * (float)fr.rh));
+  const float reach = (unsigned)*slot < (unsigned)t.slots ? 0.5f : -1.0f;   // (|.| <= -1 never holds)
+  return fabsf(previous_uv.x - 0.5f) <= 0.5f && fabsf(previous_uv.y - 0.5f) <= reach;
+}
+// every store to previous_spatial goes through here: the reference lets them race; the verification mode parks them.  `to` is a slot
+// of the buffer: the pixel's own, or one that previous_slot let through - nothing here, in the parked planes or in the resolve passes
+// behind them (k_join_winners, k_resolve_scatter, k_resolve_scatter_lite) ever sees another.
 __device__ __forceinline__ void store_previous_spatial(const LightTargets& t, int from, int to, const PackedReservoir& v) {
   if (t.det_winner && (!t.det_lite || to != from)) {
     store_packed(t.det_pending, from, v);
@@ -82,10 +98,9 @@ __device__ __forceinline__ void indirect_temporal_tail(const DScene& sc, const D
   const f2 previous_uv = jittered_deferred_uv(fr, uv, 0.25f) - F2(velocity_uv.x, velocity_uv.y);
   Reservoir r = load_reservoir_uv(t.previous, previous_uv, fr.rw, fr.rh);
   if (t.det_lite) t.det_to[index] = -1;  // (every geometry pixel says each frame whether and where it stores: no memset of the plane)
-  if (!check_previous_reservoir(r, s) && fabsf(previous_uv.x - 0.5f) <= 0.5f && fabsf(previous_uv.y - 0.5f) <= 0.5f) {
-    const int previous_index = f32_to_i32(previous_uv.x * (float)fr.rw) + fr.rw * f32_to_i32(previous_uv.y * (float)fr.rh);
-    store_previous_spatial(t, index, previous_index, pack_reservoir(r));
-  }
+  int previous_index;
+  const bool lands = previous_slot(fr, t, previous_uv, &previous_index);
+  if (!check_previous_reservoir(r, s) && lands) store_previous_spatial(t, index, previous_index, pack_reservoir(r));
   const Surface surface = retreive_surface(sc, im_y, F2(velocity_uv.z, velocity_uv.w));
   const f3 view_direction = calculate_view(fr, position);
   f3 sample_radiance = shading(fr, view_direction, s.visible_normal, normalize(xyz(s.sample_position) - xyz(s.visible_position)), surface, s.radiance);

@@ -232,8 +232,8 @@ __global__ __launch_bounds__(256, (LDS == 0 ? HK_DIRECT_GLOBAL_WAVES : (LDS == 2
       const f2 previous_uv = jittered_deferred_uv(fr, uv, 0.25f) - F2(velocity_uv.x, velocity_uv.y);
       Reservoir r = load_reservoir_uv(t.previous, previous_uv, fr.rw, fr.rh);
       if (t.det_lite) t.det_to[index] = -1;  // (every geometry pixel says each frame whether and where it stores: hk_light.hpp store_previous_spatial)
-      const bool prev_on_screen = fabsf(previous_uv.x - 0.5f) <= 0.5f && fabsf(previous_uv.y - 0.5f) <= 0.5f;
-      const int previous_index = f32_to_i32(previous_uv.x * (float)fr.rw) + fr.rw * f32_to_i32(previous_uv.y * (float)fr.rh);
+      int previous_index;
+      const bool prev_on_screen = previous_slot(fr, t, previous_uv, &previous_index);   // (on screen by the closed test AND the slot inside the buffer: hk_light.hpp)
 
       if (!check_previous_reservoir(r, s) && prev_on_screen) store_previous_spatial(t, index, previous_index, pack_reservoir(r));
 

@@ -992,6 +992,11 @@ static float compute_jacobian(const Sample& q, const Sample& r) {  // light.wgsl
   return clamp_(jacobian, 1.0f, 50.0f);
 }
 struct Sizes { int dw, dh, rw, rh; };
+// The store to previous_spatial goes where |uv - 0.5| <= 0.5, the load reads where it is < 0.5 (light.wgsl:181-190 against
+// 1092-1095): a previous_uv.y of exactly 1, or an x of exactly 1 on the last row, forms a slot one row past the buffer.  A WGSL
+// runtime array drops such a store, and so does every scatter form here, before it is queued or parked.  An x of exactly 1 on
+// another row stays in range - column 0 of the next row - and is kept: that is what the reference does.
+static bool scatter_slot_in_range(int slot, const Sizes& sz) { return slot >= 0 && slot < sz.rw * sz.rh; }
 static v2 jittered_deferred_uv(const Scene& sc, const Sizes& sz, v2 uv, float amount) {  // light.wgsl:1007-1011 (0.25), denoise.wgsl:37-41 (0.5)
   v2 texel_size = V2(1.0f / (float)sz.dw, 1.0f / (float)sz.dh);
   float ratio = sc.frame->upscale_ratio - 1.0f;
@@ -1280,9 +1285,11 @@ static void pass_direct_lit(Ctx* c, bool emissive_lit, int y0, int y1) {
       v2 previous_uv = jittered_deferred_uv(sc, sz, uv, 0.25f) - V2(velocity_uv.x, velocity_uv.y);
       Reservoir r = load_reservoir_uv(rs.previous, previous_uv, sz.rw, sz.rh);
       const bool prev_on_screen = fabsf(previous_uv.x - 0.5f) <= 0.5f && fabsf(previous_uv.y - 0.5f) <= 0.5f;
-      const int previous_index = f32_to_i32(previous_uv.x * (float)sz.rw) + rw * f32_to_i32(previous_uv.y * (float)sz.rh);
+      // (formed on screen only: off it i32() saturates - a uv of 1e9 or Inf - and rw * 2147483647 overflows a signed int)
+      const int previous_index = prev_on_screen ? f32_to_i32(previous_uv.x * (float)sz.rw) + rw * f32_to_i32(previous_uv.y * (float)sz.rh) : -1;
+      const bool store_lands = prev_on_screen && scatter_slot_in_range(previous_index, sz);
 
-      if (!check_previous_reservoir(&r, s) && prev_on_screen) {  // light.wgsl:1092-1095
+      if (!check_previous_reservoir(&r, s) && store_lands) {  // light.wgsl:1092-1095
         scatter[y].push_back({index, previous_index, pack_reservoir(r)});
       }
 
@@ -1344,7 +1351,7 @@ static void pass_direct_lit(Ctx* c, bool emissive_lit, int y0, int y1) {
 
         float luminance_ratio = luminance(xyz(validate_radiance)) / fmax_(luminance(xyz(r.s.radiance)), 0.0001f);
         if (luminance_ratio > 1.25f || luminance_ratio < 0.8f) {
-          if (prev_on_screen) scatter[y].push_back({index, previous_index, pack_reservoir(r)});
+          if (store_lands) scatter[y].push_back({index, previous_index, pack_reservoir(r)});
           float w_new = (candidate.p > 0.0f) ? luminance(xyz(s.radiance)) / candidate.p : 0.0f;
           set_reservoir(&r, s, w_new);
         }
@@ -1554,7 +1561,7 @@ static void pass_indirect(Ctx* c, int y0, int y1) {
       r = load_reservoir_uv(rs.previous, previous_uv, sz.rw, sz.rh);
       if (!check_previous_reservoir(&r, s) && fabsf(previous_uv.x - 0.5f) <= 0.5f && fabsf(previous_uv.y - 0.5f) <= 0.5f) {
         int previous_index = f32_to_i32(previous_uv.x * (float)sz.rw) + rw * f32_to_i32(previous_uv.y * (float)sz.rh);
-        scatter[y].push_back({index, previous_index, pack_reservoir(r)});
+        if (scatter_slot_in_range(previous_index, sz)) scatter[y].push_back({index, previous_index, pack_reservoir(r)});
       }
 
       surface = retreive_surface(sc, im_y, V2(velocity_uv.z, velocity_uv.w));

@@ -1217,3 +1217,599 @@ def install_spatial(engine, planes, resize=True):
     engine.frame_begin(planes.frame, camera.view_uniform(), camera.previous_view_uniform(None), hk.lights_uniform())
     for buf, array in planes.buffers.items():
         engine.write(buf, array)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The three temporal light passes - direct_lit (sun, channel 0), direct_emissive (channel 1), indirect_lit_ambient (channel 2) - on a
+# host-written G-buffer and a host-built `previous` reservoir buffer (light.wgsl:917-952, 1040-1240, 1452-1497).
+#
+# Sets (each places its specials deterministically; a small image gets the ones that fall inside it):
+#   benign      every operand clear of every threshold: zero velocity, a history record that matches its pixel, counts 1 .. 20, radiance
+#               0.05 .. 3, samples in the upper hemisphere - six in seven towards the sun, inside its cone.
+#   edge        previous_uv in x, in y and in both, on the first, middle and last row and column: exactly 0, one ulp under 1, exactly 1,
+#               one ulp over 1, negative, NaN, +-Inf, 1e9 - the velocity formed in f32 and the value it yields asserted (a -0 cannot be
+#               formed: the difference of two equal finite operands is +0, so the planes place +0 there).  A uv.y of exactly 1, or a uv.x
+#               of exactly 1 on the last row, forms a slot one row PAST the buffer: the store every scatter form must discard.  A uv.x of
+#               exactly 1 on another row wraps to column 0 of the next row, in range, and is kept.  History records that pass and that
+#               fail by depth, by normal and by instance alone.
+#   thresholds  history depth either side of 1.05 * (1 + 0.5 * random.x) by one ulp, both directions of the ratio, at the pixels whose random.x
+#               (the noise tile's: replayed, not chosen) is lowest, highest and nearest one half; current depth 0, epsilon -/+ ulp, NaN,
+#               Inf, negative, denormal; history normals one snorm8 step either side of a dot of 0.9, zero and anti-parallel; instance ids
+#               equal, off by one, NaN; counts 3, 4 and 4 -/+ one f16 ulp; counts that reach max_temporal_reuse_count exactly, pass it by
+#               one, stay under it; history luminance - a grey f16 radiance under a validation ray that finds the sun - on adjacent f16
+#               levels either side of a ratio of 1.25, of 0.8 and of the 0.0001 floor (`luminance_level`), and far above and below.
+#   records     w / w_sum / w2_sum / radiance of 0, -0, 65504, Inf, NaN; lifetime bytes 0, 126, 127, 254; the history sample ON the visible
+#               position (normalize(0)); samples below the surface.
+#   scatter     a block of pixels whose history all reprojects onto ONE slot; a slot owned by a background pixel, and by a geometry pixel
+#               that stores to itself; targets in another wave tile, another workgroup and far rows; chains a -> b -> c.  Run with the
+#               validate intervals at 1 so that the second store (light.wgsl:1199-1202) happens on both parities.
+#   background  as in the spatial planes: all-background tiles, one geometry pixel in a corner lane, a NaN depth as a tile's only geometry lane.
+#   random      dense seeded noise with a few percent of each special.
+TEMPORAL_SETS = ("benign", "edge", "thresholds", "records", "scatter", "background", "random")
+TEMPORAL_PASSES = (F.PASS_DIRECT_LIT, F.PASS_DIRECT_EMISSIVE, F.PASS_INDIRECT)
+TEMPORAL_SUN = dict(color=(1.0, 0.95, 0.9), illuminance=20000.0, direction_to_light=(0.3, 0.5, 0.8))
+SURFACE_Z, GEOMETRY_Z, TANGENT_MARGIN = 2.0, -50.0, 1.0
+EDGE_UVS = ("zero", "under_one", "one", "over_one", "negative", "nan", "inf", "ninf", "huge", "half")
+
+
+def temporal_scene(kind):
+    """`open`: the six material triangles of spatial_scene, far BELOW every surface point (make_temporal_planes asserts it): a ray that
+    leaves the upper hemisphere of a visible normal hits nothing; no emitter.  `roofed`: the same, plus one large emissive quad above the
+    surface points and one opaque occluder between it and the half x < 0 of them."""
+    assert kind in ("open", "roofed")
+    b = hk.SceneBuilder()
+    mesh = b.add_mesh([[0, 0, 0], [1, 0, 0], [0, 1, 0]], [[0, 0, 1]] * 3, [[0, 0], [1, 0], [0, 1]])
+    for k, (colour, metallic, roughness) in enumerate(SPATIAL_MATERIALS):
+        m = b.add_material(hk.standard_material(colour + (1.0,), perceptual_roughness=roughness, metallic=metallic, reflectance=0.3 + 0.1 * k))
+        t = np.eye(4, dtype=np.float32)
+        t[3, 0], t[3, 2] = 3.0 * k, GEOMETRY_Z
+        b.add_instance(mesh, m, t)
+    if kind == "roofed":
+        quad = b.add_mesh([[-5, -5, 0], [5, -5, 0], [5, 5, 0], [-5, -5, 0], [5, 5, 0], [-5, 5, 0]], [[0, 0, -1]] * 6, [[0, 0], [1, 0], [1, 1], [0, 0], [1, 1], [0, 1]])
+        half = b.add_mesh([[-5, -5, 0], [0, -5, 0], [0, 5, 0], [-5, -5, 0], [0, 5, 0], [-5, 5, 0]], [[0, 0, -1]] * 6, [[0, 0], [1, 0], [1, 1], [0, 0], [1, 1], [0, 1]])
+        lamp = b.add_material(hk.standard_material((1.0, 1.0, 1.0, 1.0), emissive_linear=(4.0, 3.0, 2.0)))
+        slab = b.add_material(hk.standard_material((0.5, 0.5, 0.5, 1.0)))
+        for mesh_id, material, z in ((quad, lamp, 3.5), (half, slab, 3.0)):
+            t = np.eye(4, dtype=np.float32)
+            t[3, 1], t[3, 2] = 1.0, z
+            b.add_instance(mesh_id, material, t)
+    return b.finish()
+
+
+def scene_triangle_vertices(scene):
+    """world positions of every triangle vertex of a SceneData whose instances are pure translations (temporal_scene), float64"""
+    v = np.array([[vt.position[0], vt.position[1], vt.position[2]] for vt in scene.vertices], np.float64)
+    out = []
+    for inst in scene.instances:
+        m = np.array(list(inst.model), np.float64).reshape(4, 4)       # column-major: the translation is m[3, :3]
+        assert np.allclose(m[:3, :3], np.eye(3))
+        out.append(v + m[3, :3])
+    return np.concatenate(out)
+
+
+class TemporalPlanes:
+    def __init__(self, name, seed, window_size, ratio, channel, frame_number, scene, settings):
+        self.name, self.seed, self.window_size, self.ratio, self.channel, self.scene = name, seed, tuple(window_size), float(ratio), channel, scene
+        self.settings = hk.HikariSettings(upscale=hk.Upscale.SmaaTu4x(ratio), **settings)
+        self.frame = hk.frame_uniform(self.settings, frame_number)
+        self.render_size = render_size_of(window_size, ratio)
+        self.lights = hk.lights_uniform(TEMPORAL_SUN, ambient_brightness=0.3)
+        cur = frame_number % 2
+        prev = 1 - cur
+        self.slots = {"previous": F.BUF_RESERVOIR0 + cur + T_SLOT[channel], "current": F.BUF_RESERVOIR0 + prev + T_SLOT[channel],
+                      "previous_spatial": F.BUF_RESERVOIR0 + cur + S_SLOT[channel], "spatial": F.BUF_RESERVOIR0 + prev + S_SLOT[channel]}
+        self.pass_id = TEMPORAL_PASSES[channel]
+        self.buffers, self.placed, self.previous = {}, None, None
+
+    @property
+    def outputs(self):
+        """what the pass writes, wholly or in part (the part it leaves alone keeps its sentinel)"""
+        return {"current": self.slots["current"], "previous_spatial": self.slots["previous_spatial"], "spatial": self.slots["spatial"],
+                "variance": F.BUF_VARIANCE0 + self.channel, "render": F.BUF_RENDER0 + self.channel}
+
+    @property
+    def untouched(self):
+        """what it reads or must leave alone"""
+        return {"previous": self.slots["previous"], "position": F.BUF_POSITION, "normal": F.BUF_NORMAL,
+                "instance_material": F.BUF_INSTANCE_MATERIAL, "velocity_uv": F.BUF_VELOCITY_UV}
+
+
+def temporal_jittered_uv(p, x, y):
+    """jittered_deferred_uv(coords_to_uv(x, y), 0.25) in f32 (light.wgsl:1007-1011): (u, v)"""
+    (dw, dh), (rw, rh) = p.window_size, p.render_size
+    sgn = _f32(-0.25) if p.frame.number % 2 == 0 else _f32(0.25)
+    ratio = _f32(_f32(p.frame.upscale_ratio) - _f32(1.0))
+    u = _f32(_f32(_f32(x + 0.5) / _f32(rw)) + _f32(_f32(sgn * _f32(_f32(1.0) / _f32(dw))) * ratio))
+    v = _f32(_f32(_f32(y + 0.5) / _f32(rh)) + _f32(_f32(sgn * _f32(_f32(1.0) / _f32(dh))) * ratio))
+    return u, v
+
+
+def _i32(v):
+    """WGSL i32(f32) as the library and the oracle take it: truncation, saturating, NaN to 0"""
+    v = float(v)
+    if np.isnan(v):
+        return 0
+    return int(max(-2147483648.0, min(2147483520.0, np.trunc(v))))
+
+
+def temporal_target(p, x, y, velocity):
+    """What render pixel (x, y) makes of its velocity, in f32 as the shader does (light.wgsl:1081-1095): previous_uv, whether the LOAD
+    reads history there (|uv - 0.5| < 0.5), whether the STORE condition holds (<= 0.5), and the slot index the store forms."""
+    rw, rh = p.render_size
+    with np.errstate(all="ignore"):
+        ju, jv = temporal_jittered_uv(p, x, y)
+        u, v = _f32(ju - _f32(velocity[0])), _f32(jv - _f32(velocity[1]))
+        loads = bool(abs(_f32(u - _f32(0.5))) < _f32(0.5) and abs(_f32(v - _f32(0.5))) < _f32(0.5))
+        stores = bool(abs(_f32(u - _f32(0.5))) <= _f32(0.5) and abs(_f32(v - _f32(0.5))) <= _f32(0.5))
+        index = _i32(_f32(u * _f32(rw))) + rw * _i32(_f32(v * _f32(rh))) if stores else None
+    return (u, v), loads, stores, index
+
+
+def velocity_for(j, kind):
+    """the f32 velocity component v for which f32(j - v) is the edge value `kind`, and that value - asserted; (None, None) where no f32
+    velocity yields it from this j"""
+    one = _f32(1.0)
+    want = {"zero": _f32(0.0), "under_one": np.nextafter(one, _f32(0)), "one": one, "over_one": np.nextafter(one, _f32(2)), "negative": _f32(-0.25),
+            "huge": _f32(1e9), "half": _f32(0.5)}.get(kind)
+    with np.errstate(all="ignore"):
+        if want is None:
+            v = {"nan": _f32(np.nan), "inf": _f32(-np.inf), "ninf": _f32(np.inf)}[kind]
+            got = _f32(j - v)
+            assert np.isnan(got) if kind == "nan" else (np.isinf(got) and (got > 0) == (kind == "inf"))
+            return v, got
+        v = _f32(j - want)
+        for _ in range(64):
+            got = _f32(j - v)
+            if got == want:
+                break
+            v = np.nextafter(v, _f32(-np.inf) if got < want else _f32(np.inf))
+        if _f32(j - v) != want:        # (j an odd multiple of half the result's ulp: every difference is a tie, rounds to even, and skips odd targets)
+            return None, None
+        assert want < 0 or not np.signbit(_f32(j - v))
+    return v, _f32(j - v)
+
+
+def temporal_random_x(p, x, y):
+    """s.random.x of render pixel (x, y): the noise tile's texel and fract(. + number * golden) in f32 (light.wgsl:1075-1080)"""
+    n = int(p.frame.number)
+    noise = hk.load_noise().reshape(16, 64, 64, 4)
+    t = _f32(_f32(noise[n % 16, (y + n) % 64, (x + n) % 64, 0]) / _f32(255.0))
+    s = _f32(t + _f32(_f32(n) * _f32(1.618033989)))
+    return _f32(s - np.floor(s))
+
+
+def f32_luminance(rgb):
+    """luminance (utils.wgsl:63-65) in f32, the products summed in order"""
+    r, g, b = (_f32(v) for v in rgb)
+    return _f32(_f32(_f32(r * _f32(0.2126)) + _f32(g * _f32(0.7152))) + _f32(b * _f32(0.0722)))
+
+
+def luminance_ratio_f32(p, grey_bits):
+    """light.wgsl:1196: luminance(sun colour) / max(luminance(history radiance), 0.0001) in f32, the history radiance the f16 grey `grey_bits`"""
+    g = np.uint16(grey_bits).view(np.float16).astype(np.float32)
+    return _f32(f32_luminance(p.lights.directional_color[:3]) / max(f32_luminance((g, g, g)), _f32(0.0001)))
+
+
+def luminance_level(p, target, side):
+    """f16 bits of the grey history radiance that puts the validation's luminance ratio next to `target`: "1.25" / "0.8" - the last level
+    whose ratio is above the threshold (`above`) or the first whose ratio is not (`below`), adjacent f16 values, the finest step the
+    record's storage has; "floor" - the last level whose luminance is under the 0.0001 floor (`below`) or the first that is not.  Asserted."""
+    levels = np.arange(1, 0x7C00, dtype=np.uint16)                                        # positive finite f16, ascending
+    if target == "floor":
+        lum = np.array([f32_luminance((g, g, g)) for g in levels.view(np.float16).astype(np.float32)[:0x0800]])
+        first = int(np.argmax(lum >= _f32(0.0001)))
+        assert lum[first] >= _f32(0.0001) > lum[first - 1]
+        return levels[first - 1] if side == "below" else levels[first]
+    thr = _f32(float(target))
+    lo, hi = 0, len(levels) - 1                                                            # the ratio falls as the level rises
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if luminance_ratio_f32(p, levels[mid]) > thr else (lo, mid)
+    assert luminance_ratio_f32(p, levels[lo]) > thr >= luminance_ratio_f32(p, levels[hi]) and hi == lo + 1
+    return levels[lo] if side == "above" else levels[hi]
+
+
+def make_temporal_planes(name, seed, render_size, ratio, channel, frame_number=2, scene="open", **settings):
+    """One dispatch of temporal pass `channel` (0 sun, 1 emissive, 2 indirect) at `render_size`, the window being window_for(render_size,
+    ratio); `settings` go to HikariSettings (indirect_bounces, validate intervals, max_temporal_reuse_count, temporal_reuse)."""
+    assert name in TEMPORAL_SETS and channel in (0, 1, 2) and scene in ("open", "roofed")
+    settings.setdefault("indirect_bounces", 1)
+    settings.setdefault("emissive_spatial_reuse", True)             # previous_spatial of channels 0 and 1 has a reader: the library resolves their scatter by default
+    if name == "scatter":
+        settings.setdefault("direct_validate_interval", 1)
+        settings.setdefault("emissive_validate_interval", 1)
+    p = TemporalPlanes(name, seed, window_for(render_size, ratio), ratio, channel, frame_number, scene, settings)
+    assert p.render_size == tuple(render_size)
+    rng = np.random.default_rng([seed, 300 + TEMPORAL_SETS.index(name), channel])
+    (dw, dh), (rw, rh) = p.window_size, p.render_size
+    inside = lambda x, y: 0 <= x < rw and 0 <= y < rh
+    placed = np.zeros((rh, rw), bool)
+    p.branches, p.where = {}, {}                                     # what the set placed, by purpose: counts a test asserts to be non-zero, and (thresholds) where
+
+    def note(key, n=1):
+        p.branches[key] = p.branches.get(key, 0) + n
+
+    def texel(x, y):
+        """G-buffer [row, column] under render pixel (x, y), or None where the jittered texel lies outside"""
+        tx, ty = spatial_texel(p, x, y)
+        return (ty, tx) if 0 <= tx < dw and 0 <= ty < dh else None
+
+    # ---- the G-buffer: a wall facing the camera of cornell_camera, every texel's normal in the upper hemisphere of +z
+    gx, gy = np.meshgrid(np.arange(dw), np.arange(dh))
+    depth = np.full((dh, dw), 2.0, np.float32) if name != "random" else (2.0 + 0.05 * rng.random((dh, dw))).astype(np.float32)
+    position = np.zeros((dh, dw, 4), np.float32)
+    position[..., 0], position[..., 1], position[..., 2], position[..., 3] = 0.02 * (gx - dw / 2), 1.0 + 0.02 * (dh / 2 - gy), SURFACE_Z, depth
+    which = (gx // 11 + gy // 6) % 3
+    normal3 = SPATIAL_NORMALS[which]
+    instance = np.zeros((dh, dw, 2), np.float32)
+    instance[..., 0] = (gx // 9 + gy // 7) % len(SPATIAL_MATERIALS)
+    instance[..., 1] = instance[..., 0]
+    velocity = np.zeros((dh, dw, 4), np.float32)
+    velocity[..., 2:] = rng.random((dh, dw, 2))
+
+    # ---- `previous`: per render pixel the record of the SAME surface point (zero velocity: previous_uv stays in the pixel)
+    tex = np.array([[texel(x, y) or (0, 0) for x in range(rw)] for y in range(rh)])
+    has_texel = np.array([[texel(x, y) is not None for x in range(rw)] for y in range(rh)])
+    ty_, tx_ = tex[..., 0], tex[..., 1]
+    hist = Records(rh, rw)
+    shape = (rh, rw)
+    hist.count[...] = f16_bits(rng.integers(1, 21, shape))
+    hist.w[...] = f16_bits(0.1 + 1.9 * rng.random(shape))
+    hist.w_sum[...] = f16_bits(0.5 + 9.5 * rng.random(shape))
+    hist.w2_sum[...] = f16_bits(0.5 + 49.5 * rng.random(shape))
+    hist.radiance[..., :3] = f16_bits(0.05 + 2.95 * rng.random(shape + (3,)))
+    hist.radiance[..., 3] = H_ONE
+    hist.random[...] = rng.integers(0, 65536, shape + (4,))
+    hist.visible_position[...] = position[ty_, tx_]
+    hist.visible_normal[...] = snorm8(normal3[ty_, tx_])
+    hist.visible_instance[...] = instance[ty_, tx_, 0]
+    lateral = 0.3 * (rng.random(shape + (3,)) - 0.5)
+    hist.sample_position[...] = (hist.visible_position[..., :3] + 1.5 * normal3[ty_, tx_] + lateral).astype(np.float32)
+    # six in seven history samples lie TOWARDS THE SUN, well inside its cone (solar_angle 0.046): a validation ray to them finds the sun,
+    # and its radiance is known; the rest lie in the upper hemisphere outside the cone, where the validation ray finds nothing
+    sun = np.asarray(TEMPORAL_SUN["direction_to_light"], np.float64) / np.linalg.norm(TEMPORAL_SUN["direction_to_light"])
+    toward = sun + 0.01 * (rng.random(shape + (3,)) - 0.5)
+    sunward = rng.random(shape) < 6.0 / 7.0
+    hist.sample_position[sunward] = (hist.visible_position[..., :3] + 100.0 * toward / np.linalg.norm(toward, axis=-1, keepdims=True)).astype(np.float32)[sunward]
+    hist.sample_normal[...] = snorm8(-normal3[ty_, tx_])
+    hist.jacobian_flag[...] = np.where(rng.random(shape) < 0.5, 127, 0)
+    hist.lifetime[...] = rng.integers(0, 11, shape)
+
+    def put(x, y):
+        placed[y, x] = True
+        return y, x
+
+    def aim(x, y, tx, ty):
+        """the velocity that makes pixel (x, y) look at the centre of render pixel (tx, ty); asserted through temporal_target"""
+        t = texel(x, y)
+        if t is None:
+            return False
+        ju, jv = temporal_jittered_uv(p, x, y)
+        velocity[t][0], velocity[t][1] = _f32(ju - _f32(_f32(tx + 0.5) / _f32(rw))), _f32(jv - _f32(_f32(ty + 0.5) / _f32(rh)))
+        _, loads, stores, index = temporal_target(p, x, y, velocity[t][:2])
+        assert loads and stores and index == tx + rw * ty, (x, y, tx, ty, index)
+        put(x, y)
+        return True
+
+    def fail(y, x, reason):
+        """make the history record at [y, x] fail check_previous_reservoir for ONE reason against a pixel that matches it otherwise"""
+        if reason == "depth":
+            hist.visible_position[y, x, 3] *= _f32(1.5)
+        elif reason == "normal":
+            hist.visible_normal[y, x] = snorm8(-normal3[ty_[y, x], tx_[y, x]])
+        else:
+            hist.visible_instance[y, x] += 1.0
+        note("fails_" + reason)
+
+    one_ulp = lambda v, towards: np.nextafter(_f32(v), _f32(towards))
+    if name == "edge":
+        cols, rows = sorted({0, rw // 2, rw - 1}), sorted({0, rh // 2, rh - 1})
+        k = 0
+        for y in range(rh):
+            for x in range(rw):
+                t = texel(x, y)
+                if t is None or not (x in cols or y in rows):
+                    if t is not None and (x + 2 * y) % 8 < 3:          # elsewhere: history that passes, or fails for one reason alone
+                        fail(y, x, ("depth", "normal", "instance")[(x + 2 * y) % 8])
+                    continue
+                kind, axes = EDGE_UVS[k % len(EDGE_UVS)], ((0,), (1,), (0, 1))[(k // len(EDGE_UVS)) % 3]
+                k += 7                                                  # (7 is coprime to 30: every value x axes combination comes round)
+                if (x, y) == (rw - 1, rh - 1):
+                    kind, axes = "one", (1,)                            # the slot one row past the buffer, in every shape
+                elif (x, y) == (0, rh - 1) and rw > 1:
+                    kind, axes = "one", (0,)                            # x exactly 1 on the last row: past the buffer as well
+                elif (x, y) == (rw - 1, 0) and rh > 1:
+                    kind, axes = "one", (0,)                            # x exactly 1 on another row: column 0 of the next row, kept
+                j = temporal_jittered_uv(p, x, y)
+                while any(velocity_for(j[a], kind)[0] is None for a in axes):       # (the next value that this pixel's uv can reach)
+                    kind = EDGE_UVS[(EDGE_UVS.index(kind) + 1) % len(EDGE_UVS)]
+                for a in axes:
+                    velocity[t][a], _ = velocity_for(j[a], kind)
+                put(x, y)
+                (_u, _v), loads, stores, index = temporal_target(p, x, y, velocity[t][:2])
+                note("uv_" + kind)
+                if stores and not loads:
+                    note("store_without_load")
+                    note("store_discarded" if index >= rw * rh else "store_wrapped_in_range")
+    elif name == "thresholds":
+        k = 0
+        cases = ([("depth", d, s) for d in (1, -1) for s in (1, -1)] + [("cur_depth", v, 0) for v in (0.0, np.nextafter(F32_EPSILON, _f32(0)), F32_EPSILON,
+                 np.nextafter(F32_EPSILON, _f32(1)), np.nan, np.inf, -1.0, 1e-40)] + [("normal", z, 0) for z in (-2, -1, 0, 1, 2)] + [("normal_zero", 0, 0), ("normal_anti", 0, 0)] +
+                 [("instance", v, 0) for v in (0.0, 1.0, np.nan)] + [("count", b, 0) for b in (f16_bits(3.0), f16_bits(4.0), f16_bits(4.0) - 1, f16_bits(4.0) + 1)] +
+                 [("clamp", e, 0) for e in (-1, 0, 1, -10)] + [("luminance", v, 0) for v in ("1.25 above", "1.25 below", "0.8 above", "0.8 below", "floor above", "floor below", 0.0, 60000.0)])
+        grid = [(x, y) for y in range(0, rh, 2) for x in range((y // 2) % 3, rw, 3) if texel(x, y) is not None]
+        # the depth cases go where random.x - the noise tile's, not the set's to choose - is lowest, highest and nearest one half
+        rx = {q: float(temporal_random_x(p, *q)) for q in grid}
+        ranked = sorted(grid, key=lambda q: rx[q])
+        middle = sorted(grid, key=lambda q: abs(rx[q] - 0.5))
+        depth_cases, chosen = [c for c in cases if c[0] == "depth"], {}
+        for group in (ranked, ranked[::-1], middle):
+            for c in depth_cases:
+                q = next((q for q in group if q not in chosen), None)
+                if q is not None:
+                    chosen[q] = c
+        rest = [c for c in cases if c[0] != "depth"]
+        for x, y in grid:
+            t = texel(x, y)
+            if (x, y) in chosen:
+                what, a, b = chosen[(x, y)]
+            else:
+                what, a, b = rest[k % len(rest)]
+                k += 1
+            put(x, y)
+            note(what)
+            p.where.setdefault(what, []).append((x, y))
+            d_cur = _f32(position[t][3])
+            if what == "depth":                                     # history depth = current * (or /) the threshold, one ulp either side of it
+                thr = _f32(_f32(1.05) * _f32(_f32(1.0) + _f32(_f32(0.5) * temporal_random_x(p, x, y))))
+                d = _f32(d_cur * thr) if a > 0 else _f32(d_cur / thr)
+                ratio = lambda d: (lambda q: _f32(_f32(1.0) / q) if q < 1 else q)(_f32(d / d_cur))
+                # walk to the last depth whose ratio does not exceed the threshold, then (b > 0) one ulp beyond it
+                away = _f32(np.inf) if a > 0 else _f32(0.0)
+                for _ in range(64):
+                    if ratio(d) > thr:
+                        d = np.nextafter(d, _f32(d_cur))
+                    elif not ratio(np.nextafter(d, away)) > thr:
+                        d = np.nextafter(d, away)
+                    else:
+                        break
+                assert not ratio(d) > thr and ratio(np.nextafter(d, away)) > thr
+                hist.visible_position[y, x, 3] = np.nextafter(d, away) if b > 0 else d
+            elif what == "cur_depth":
+                position[t][3] = a
+            elif what == "normal":                                  # the pixel's normal is +z; the history normal (s, 0, c) near a dot of 0.9
+                normal3[t] = SPATIAL_NORMALS[0]
+                hist.visible_normal[y, x] = (55 + a, 0, 114)        # normalised: 114 / hypot(55 + a, 114) = 0.9025 .. 0.8990 over a = -2 .. 2
+            elif what == "normal_zero":
+                hist.visible_normal[y, x] = 0
+            elif what == "normal_anti":
+                hist.visible_normal[y, x] = snorm8(-normal3[t])
+            elif what == "instance":
+                hist.visible_instance[y, x] = hist.visible_instance[y, x] + _f32(a)
+            elif what == "count":
+                hist.count[y, x] = a
+            elif what == "clamp":
+                hist.count[y, x] = f16_bits(float(max(0, p.settings.max_temporal_reuse_count + a)))
+            elif what == "luminance":
+                # validation with a count of 5: nothing is merged, the validation ray goes to the history sample - put inside the sun's
+                # cone, so that on the open scene its radiance is the sun's colour - and the ratio is lum(sun) / max(lum(history), 1e-4).
+                # The history radiance is f16: the grey level whose ratio is the last one above 1.25 (0.8), or the first one not above.
+                hist.count[y, x] = f16_bits(5.0)
+                hist.sample_position[y, x] = (hist.visible_position[y, x, :3] + 100.0 * sun).astype(np.float32)
+                if isinstance(a, str):
+                    target, side = a.split()
+                    hist.radiance[y, x, :3] = luminance_level(p, target, side)
+                else:
+                    hist.radiance[y, x, :3] = f16_bits(a)
+    elif name == "records":
+        k = 0
+        cases = ([(f, b) for f in ("w", "w_sum", "w2_sum", "radiance") for b in (0, H_NZERO, H_MAX, H_INF, H_NAN)] + [("lifetime", v) for v in (0, 126, 127, 254)] +
+                 [("sample_on_surface", 0), ("sample_below", 0)])
+        for y in range(rh):
+            for x in range((y * 2) % 3, rw, 3):
+                what, b = cases[k % len(cases)]
+                k += 1
+                put(x, y)
+                note(what)
+                if what == "radiance":
+                    hist.radiance[y, x, :3] = b
+                elif what == "lifetime":
+                    hist.lifetime[y, x] = b
+                elif what == "sample_on_surface":
+                    hist.sample_position[y, x] = hist.visible_position[y, x, :3]
+                elif what == "sample_below":
+                    hist.sample_position[y, x] = hist.visible_position[y, x, :3] - _f32(1.5) * normal3[ty_[y, x], tx_[y, x]].astype(np.float32)
+                else:
+                    getattr(hist, what)[y, x] = b
+                    if what == "w_sum":
+                        hist.count[y, x] = f16_bits(2.0)
+    elif name == "scatter":
+        normal3[...] = SPATIAL_NORMALS[0]
+        instance[...] = 2.0
+        hist.visible_normal[...] = snorm8(SPATIAL_NORMALS[0])
+        hist.visible_instance[...] = 2.0
+        hist.count[...] = f16_bits(rng.integers(1, 4, shape))          # under 4: the new sample is merged, so every pixel's record differs
+        hist.radiance[..., :3] = f16_bits(40.0 + 10.0 * rng.random(shape + (3,)))      # far from any validate radiance: the second store happens
+
+        def owner_fails(tx, ty):
+            if inside(tx, ty):
+                fail(ty, tx, "depth")
+
+        # many onto one slot, its history refused (first store) - and one onto a slot whose history passes (second store only)
+        for target, block, refused in (((4, 2), [(x, y) for y in range(0, 4) for x in range(0, 8)], True),
+                                       ((12, 9), [(x, y) for y in range(8, 12) for x in range(9, 16)], False)):
+            if not inside(*target):
+                continue
+            if refused:
+                owner_fails(*target)
+            for x, y in block:
+                if inside(x, y) and aim(x, y, *target):
+                    note("contested")
+        # the owner a background pixel / a geometry pixel that stores to itself (zero velocity, refused history)
+        for target, sources in (((20, 3), [(22, 3), (19, 5)]), ((26, 3), [(24, 2), (30, 6)])):
+            if not inside(*target) or texel(*target) is None:
+                continue
+            if target[0] == 20:
+                position[texel(*target)][3] = 0.0
+                note("owner_background")
+            else:
+                owner_fails(*target)
+                note("owner_stores_to_itself")
+            put(*target)
+            for x, y in sources:
+                if inside(x, y):
+                    aim(x, y, *target)
+        # another wave tile, another workgroup, far rows - in both directions (a lower and a higher index than the owner)
+        for (x, y), target in (((33, 1), (44, 1)), ((44, 2), (33, 2)), ((2, 14), (50, 14)), ((66, 15), (3, 15)), ((5, 16), (60, 40)), ((61, 41), (6, 17)), ((3, 0), (3, 44)), ((8, 44), (8, 0))):
+            if inside(x, y) and inside(*target):
+                owner_fails(*target)
+                if aim(x, y, *target):
+                    note("far_target")
+        # chains: a -> b -> c
+        for a, b, c in (((40, 20), (42, 24), (45, 30)), ((30, 35), (28, 30), (25, 22)), ((1, 6), (2, 7), (3, 8))):
+            if inside(*a) and inside(*b) and inside(*c):
+                owner_fails(*b)
+                owner_fails(*c)
+                if aim(*a, *b) and aim(*b, *c):
+                    note("chain")
+    elif name == "background":
+        bg = np.zeros((rh, rw), bool)
+        bg[:, :min(16, rw)] = True
+        bg[16:32, 32:48] = True
+        for tile_x, tile_y, (lx, ly) in ((4, 0, (0, 0)), (5, 0, (7, 0)), (4, 1, (0, 7)), (5, 1, (7, 7)), (6, 4, (3, 3))):
+            bg[8 * tile_y:8 * tile_y + 8, 8 * tile_x:8 * tile_x + 8] = True
+            if 8 * tile_y + ly < rh and 8 * tile_x + lx < rw:
+                bg[8 * tile_y + ly, 8 * tile_x + lx] = False
+                placed[8 * tile_y + ly, 8 * tile_x + lx] = True
+        for y in range(rh):
+            for x in range(rw):
+                if bg[y, x] and texel(x, y) is not None:
+                    position[texel(x, y)][3] = 0.0
+                    note("background")
+        if rw > 8 * 6 + 3 and rh > 8 * 4 + 3 and texel(8 * 6 + 3, 8 * 4 + 3) is not None:
+            position[texel(8 * 6 + 3, 8 * 4 + 3)][3] = np.nan
+            note("nan_depth_lane")
+    elif name == "random":
+        some = lambda s, rate: rng.random(s) < rate
+        for d in (0.0, np.nan, np.inf, -1.0, 1e-40, 2.25, 1.8):
+            position[some((dh, dw), 0.01), 3] = d
+        for bits in (0, 1, H_MAX, H_INF, H_NAN, f16_bits(3.0), f16_bits(4.0), f16_bits(5.0), f16_bits(float(p.settings.max_temporal_reuse_count))):
+            hist.count[some(shape, 0.01)] = bits
+        for field in (hist.w, hist.w_sum, hist.w2_sum):
+            for bits in (0, H_NZERO, H_MAX, H_INF, H_NAN):
+                field[some(shape, 0.005)] = bits
+        for bits in (0, H_NZERO, H_NAN, H_MAX):
+            hist.radiance[some(shape + (4,), 0.005)] = bits
+        hist.visible_normal[some(shape, 0.01)] = 0
+        hist.visible_normal[some(shape, 0.01)] = (0, 0, -127)
+        hist.visible_instance[some(shape, 0.02)] += 1.0
+        hist.visible_position[some(shape, 0.03), 3] *= _f32(1.2)
+        hist.lifetime[some(shape, 0.03)] = 254
+        m = some(shape, 0.02)
+        hist.sample_position[m] = hist.visible_position[m][:, :3]
+        hist.zero(some(shape, 0.05))
+        for v in (np.nan, np.inf, -np.inf, 1e9, -3.0, 0.5):
+            velocity[some((dh, dw), 0.005), int(rng.integers(2))] = v
+        # a few percent look at another pixel's slot; one in a hundred at uv exactly 1 (the slot past the buffer, or the in-range wrap)
+        for y in range(rh):
+            for x in range(rw):
+                t, r = texel(x, y), rng.random()
+                if t is None or r > 0.06:
+                    continue
+                j = temporal_jittered_uv(p, x, y)
+                if r < 0.01:
+                    a = int(rng.integers(2))
+                    velocity[t][a], _ = velocity_for(j[a], "one")
+                else:
+                    velocity[t][0] = _f32(j[0] - _f32(_f32(rng.integers(rw) + 0.5) / _f32(rw)))
+                    velocity[t][1] = _f32(j[1] - _f32(_f32(rng.integers(rh) + 0.5) / _f32(rh)))
+
+    # ---- the scene: out of reach where the set's name says so.  Every triangle vertex lies below the tangent plane of every
+    # placed (or, for `benign`, every) surface point by TANGENT_MARGIN, in float64
+    scene_data = temporal_scene(scene)
+    if scene == "open":
+        verts = scene_triangle_vertices(scene_data)
+        pts, nrm = position[..., :3].reshape(-1, 3).astype(np.float64), normal3.reshape(-1, 3)
+        below = ((verts[None, :, :] - pts[:, None, :]) * nrm[:, None, :]).sum(axis=2)
+        assert below.max() < -TANGENT_MARGIN, below.max()
+    p.scene_data = scene_data
+    p.previous, p.placed = hist, placed
+    sentinel_records = np.full((dh, dw, 16), SENTINEL_U32, np.uint32)
+    previous = sentinel_records.copy()
+    previous.reshape(-1, 16)[:rw * rh] = pack_records(hist).reshape(-1, 16)
+    normal = pack_snorm8x4(np.concatenate([normal3, np.zeros((dh, dw, 1))], axis=2))[..., None]
+    p.buffers = {F.BUF_POSITION: position, F.BUF_NORMAL: normal, F.BUF_INSTANCE_MATERIAL: instance, F.BUF_VELOCITY_UV: velocity,
+                 p.slots["previous"]: previous, p.slots["current"]: sentinel_records.copy(), p.slots["previous_spatial"]: sentinel_records.copy(),
+                 p.slots["spatial"]: sentinel_records.copy(),
+                 F.BUF_VARIANCE0 + channel: np.full((rh, rw, 1), SENTINEL_F32, np.float32),
+                 F.BUF_RENDER0 + channel: np.full((rh, rw, 4), SENTINEL_F16, np.uint16)}
+    p.buffers = {buf: np.ascontiguousarray(a) for buf, a in p.buffers.items()}
+    return p
+
+
+def temporal_store_targets(p):
+    """Per geometry pixel of the planes, in f32 as the shader forms them: the slot index where the store condition holds.  Returns
+    (indices, counts, unloaded): `indices` [rh, rw] int64 with -1 where the condition fails or the pixel is background, `counts` a dict
+    of outside / in_range / to_own_slot / to_other_slot / wrapped_in_range (stores without a load that stay inside) / discarded (>= rw *
+    rh), `unloaded` [rh, rw] bool: the store condition holds and the load's does not - a zero record, always refused, so the pixel DOES store."""
+    (dw, dh), (rw, rh) = p.window_size, p.render_size
+    position, velocity = p.buffers[F.BUF_POSITION], p.buffers[F.BUF_VELOCITY_UV]
+    out, unloaded = np.full((rh, rw), -1, np.int64), np.zeros((rh, rw), bool)
+    counts = dict(background=0, outside=0, in_range=0, to_own_slot=0, to_other_slot=0, wrapped_in_range=0, discarded=0)
+    for y in range(rh):
+        for x in range(rw):
+            tx, ty = spatial_texel(p, x, y)
+            d = position[ty, tx, 3] if 0 <= tx < dw and 0 <= ty < dh else _f32(0.0)
+            if d < F32_EPSILON:
+                counts["background"] += 1
+                continue
+            vel = velocity[ty, tx, :2] if 0 <= tx < dw and 0 <= ty < dh else _f32([0.0, 0.0])
+            _, loads, stores, index = temporal_target(p, x, y, vel)
+            if not stores:
+                counts["outside"] += 1
+                continue
+            out[y, x], unloaded[y, x] = index, not loads
+            if index >= rw * rh or index < 0:
+                counts["discarded"] += 1
+                assert not loads
+                continue
+            counts["in_range"] += 1
+            counts["to_own_slot" if index == x + rw * y else "to_other_slot"] += 1
+            if not loads:
+                counts["wrapped_in_range"] += 1
+    return out, counts, unloaded
+
+
+def install_temporal(engine, planes, resize=True):
+    """hk_resize (if the size changed), hk_frame_begin with the planes' frame uniform and lights, then every plane, record buffer and
+    sentinel.  The engine must hold temporal_scene(planes.scene)."""
+    size = planes.window_size + (planes.ratio,)
+    if resize and getattr(engine, "_post_planes_size", None) != size:
+        engine.resize(*size)
+        engine._post_planes_size = size
+    camera = hk.cornell_camera(*planes.window_size)
+    engine.frame_begin(planes.frame, camera.view_uniform(), camera.previous_view_uniform(None), planes.lights)
+    for buf, array in planes.buffers.items():
+        engine.write(buf, array)
+
+
+def dump_temporal_planes(planes, path):
+    """Everything one dispatch needs, as a flat file a stand-alone program can replay without Python (tests/native/
+    temporal_oracle_main.cpp): a sequence of blobs, each a u64 byte count and the bytes - a header (window width, height, the ratio's
+    f32 bits, the pass id, the number of buffers), the nine scene arrays in SceneData.FIELDS order, the noise tiles, HkFrame, HkView,
+    HkPreviousView, HkLights, then per buffer its id (u32) and its contents."""
+    import ctypes as C
+    import struct
+
+    camera = hk.cornell_camera(*planes.window_size)
+    blobs = [struct.pack("<IIfII", planes.window_size[0], planes.window_size[1], planes.ratio, planes.pass_id, len(planes.buffers))]
+    blobs += [bytes(memoryview(getattr(planes.scene_data, k))) for k in hk.SceneData.FIELDS]
+    blobs += [hk.load_noise().tobytes()]
+    blobs += [bytes(memoryview(s)) if isinstance(s, (C.Structure, C.Array)) else bytes(s)
+              for s in (planes.frame, camera.view_uniform(), camera.previous_view_uniform(None), planes.lights)]
+    for buf, array in planes.buffers.items():
+        blobs += [struct.pack("<I", buf), array.tobytes()]
+    with open(path, "wb") as f:
+        for b in blobs:
+            f.write(struct.pack("<Q", len(b)))
+            f.write(b)

@@ -9,7 +9,7 @@ corresponding dispatch and compares what the shader writes with what the oracle 
 comes from the oracle (prepass.wgsl is a raster shader; the ray-cast G-buffer is this project's contract).
 
   [HIKARI_REFERENCE_DIR=<bevy-hikari checkout>] python tests/tools/wgsl_pin.py [--size W H] [--frames N] [--write]      (minutes of pure Python)
-  ... --planes | --aa-planes | --spatial-planes [--write]      the synthetic planes of tests/post_planes.py (the fixtures of the plane suites)
+  ... --planes | --aa-planes | --spatial-planes | --temporal-planes [--write]      the synthetic planes of tests/post_planes.py (the fixtures of the plane suites)
 
 --write stores the inputs and the shader-produced outputs of every dispatch under tests/golden/wgsl_pin.npz, which
 tests/test_wgsl_pin.py replays against the oracle without the reference."""
@@ -539,6 +539,50 @@ def run_spatial_planes(name, channel, ratio=1.0, frame_number=3, max_count=100, 
     return pin.results
 
 
+def run_temporal_planes(name, channel, ratio=1.0, frame_number=3, scene="open", render_size=(24, 16), seed=7, log=None):
+    """One dispatch of a temporal light pass of light.wgsl - direct_lit with RENDER_EMISSIVE (channel 0) or EMISSIVE_LIT (1),
+    indirect_lit_ambient (2) - on the synthetic planes of tests/post_planes.py (`make_temporal_planes`), on the state the oracle has
+    before it.  The shader's stores to previous_spatial race; the runtime applies them in invocation order, so the highest invocation
+    index wins, and drops a store beyond a runtime array's end (types.py BufferArray.__setitem__).  Returns the per-dispatch records;
+    what the shader wrote - `current`, `previous_spatial`, `spatial`, `variance`, `render` - is in run_temporal_planes.recorded."""
+    import post_planes as PP
+
+    p = oracle_plugin()
+    dll = p.engine.api.dll
+    dll.orc_debug_math.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]
+
+    def contract(op, x, y):
+        key = (op, float(x), float(y))
+        if key not in _contract_cache:
+            xi, yi, out = (C.c_float * 1)(float(x)), (C.c_float * 1)(float(y)), (C.c_float * 1)()
+            assert dll.orc_debug_math(None, op, xi, yi, out, 1) == 0
+            _contract_cache[key] = f32(out[0])
+        return _contract_cache[key]
+
+    R.bind_contract(contract)
+    planes = PP.make_temporal_planes(name, seed, render_size, ratio, channel, frame_number, scene=scene)
+    p.set_scene(planes.scene_data)
+    pin = Pinner(p, planes.scene_data, load_noise_planes(), log or (lambda rec: None))
+    pin.settings, pin.patch = planes.settings, None
+    camera = hk.cornell_camera(*planes.window_size)
+    pin.begin(planes.frame, camera.view_uniform(), camera.previous_view_uniform(None), planes.lights)
+    PP.install_temporal(p.engine, planes)
+    p.engine.pass_run(planes.pass_id)
+    keep = set(planes.outputs.values())
+    run_temporal_planes.recorded = {k: v for k, v in pin.recorded.items() if int(k.split("buf")[1]) in keep}
+    return pin.results
+
+
+#: (set, channel, ratio, frame number, scene): every channel on `edge`, `thresholds` and `scatter`, the roofed scene for each, both parities
+TEMPORAL_PLANES_FIXTURES = [("edge", 0, 1.0, 3, "open"), ("edge", 1, 1.5, 2, "roofed"), ("edge", 2, 1.0, 2, "open"),
+                            ("thresholds", 0, 1.5, 3, "open"), ("thresholds", 1, 1.0, 5, "roofed"), ("thresholds", 2, 1.5, 2, "roofed"),
+                            ("scatter", 0, 1.0, 2, "roofed"), ("scatter", 1, 1.5, 3, "roofed"), ("scatter", 2, 1.0, 3, "open"), ("records", 0, 1.0, 3, "roofed")]
+
+
+def temporal_planes_fixture_path(name, channel, ratio, frame_number, scene):
+    return os.path.join(ROOT, "tests", "golden", f"wgsl_temporal_planes_{name}_ch{channel}_r{int(ratio * 10)}_f{frame_number}_{scene}.npz")
+
+
 def load_noise_planes():
     from bevy_hikari_amd.plugin import load_noise
     return load_noise().reshape(16, 64, 64, 4)
@@ -589,6 +633,16 @@ def main():
                 np.savez_compressed(spatial_planes_fixture_path(*case), **run_spatial_planes.recorded)
                 print("wrote", spatial_planes_fixture_path(*case), os.path.getsize(spatial_planes_fixture_path(*case)), "bytes")
             print(json.dumps({"spatial_planes": case, "dispatches": len(results), "mismatching": len(bad)}))
+        return
+    if "--temporal-planes" in sys.argv:  # [--write]: the fixtures tests/test_temporal_planes*.py replay
+        for case in TEMPORAL_PLANES_FIXTURES:
+            results = run_temporal_planes(*case, log=lambda rec: print(json.dumps(rec), flush=True))
+            bad = [r for r in results if r["mismatch"]]
+            if "--write" in sys.argv:
+                assert not bad
+                np.savez_compressed(temporal_planes_fixture_path(*case), **run_temporal_planes.recorded)
+                print("wrote", temporal_planes_fixture_path(*case), os.path.getsize(temporal_planes_fixture_path(*case)), "bytes")
+            print(json.dumps({"temporal_planes": case, "dispatches": len(results), "mismatching": len(bad)}))
         return
     if "--aa-planes" in sys.argv:       # [--write]: the fixtures tests/test_aa_planes*.py replay
         for case in AA_PLANES_FIXTURES:
