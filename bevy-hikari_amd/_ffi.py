@@ -245,6 +245,7 @@ _DEBUG = {
     "debug_read_emitters": [_vp, P(f32), u32, P(u32), P(f32), u32, P(u32)],
     "debug_read_mesh_geometry": [_vp, P(HkMeshIndex), P(f32), P(f32), u32, P(f32), u32, P(f32), P(u32), P(u32)],
     "debug_last_deform": [_vp, P(u32)],
+    "debug_last_pose": [_vp, P(u32)],
     "debug_comm_loopback": [_vp, u32, u32, u32, u32, u32],
     "debug_read_wf_timeline": [_vp, P(C.c_uint64), u32],
     "debug_set_option": [_vp, u32, C.c_int64],
@@ -304,6 +305,8 @@ _PRODUCT_ONLY = {
     "skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],
     "deform_meshes": [_vp, P(HkMeshDeform), u32],
     "deform_meshes_device": [_vp, P(HkMeshDeformDevice), u32, _vp],
+    "set_instance_transforms_device": [_vp, _vp, P(u32), u32, _vp, u32, _vp, _vp],
+    "read_instance_transforms": [_vp, P(f32), u32],
     "rebuild_mesh_tree": [_vp, P(HkMeshIndex), u32],
     "present": [_vp, P(HkSettings), u32, P(HkPresentTarget), u32, u32],
     "cast_rays": [_vp, P(HkRay), u32, u32, P(HkRayHit)],

@@ -453,6 +453,10 @@ void scene_bounds(const hk_ctx* c, float mn[3], float mx[3]) {
 int derive_history_rows(const hk_ctx* c, uint32_t* rows) {
   *rows = 0;
   if (c->instances.empty()) return HK_OK;
+  if (c->poses_on_device) {  // the host has neither the poses nor the boxes (hk_set_instance_transforms_device): every row may be needed
+    *rows = (uint32_t)c->RH;
+    return HK_OK;
+  }
   std::vector<HkMovedBox> moved;
   const size_t ni = c->instances.size();
   if (c->prev_models.size() == 16 * ni)
@@ -1426,6 +1430,7 @@ int hk_history_rows(hk_ctx* c, uint32_t* rows) {
 int hk_scene_bounds(hk_ctx* c, float mn[3], float mx[3]) {
   HK_REQUIRE(c && mn && mx, HK_E_INVALID, "bad argument");
   HK_REQUIRE(c->have_instances, HK_E_NOT_READY, "no scene uploaded");
+  HK_REQUIRE(!c->poses_on_device, HK_E_NOT_READY, "the instances' poses were last set from device memory (hk_set_instance_transforms_device): the host does not hold their boxes");
   scene_bounds(c, mn, mx);
   return HK_OK;
 }

@@ -324,6 +324,22 @@ struct hk_ctx {
   hipEvent_t df_src_ready = nullptr, df_src_read = nullptr;  // hk_deform_meshes_device: the producer's stream before the batch, the batch's vertex launch before the producer
   bool deform_pending = false;            // deformed meshes whose new boxes have not reached the instance level yet (flush_deform)
   bool meshes_deformed = false;           // a mesh was deformed on the device since the last hk_upload_meshes: its host copies are stale
+  // poses from device memory (hk_set_instance_transforms_device, scene_refit.hip).  poses_on_device: the device's poses were last set
+  // from memory the host never saw - instances[].model / min / max / inverse_transpose_model and prev_models no longer describe the
+  // device (every reader of them asks; hk_upload_instances clears it).  pd_boxes: the mesh box of every instance (Aabb centre, half
+  // extents; 2 float4) as the builder gave it, pd_boxes_host what it holds; pd_all: the record order of a call that names every instance
+  // (instance, instance), emitters first, valid for the instance list pd_all_generation; pd_records: the call's RefitUpdate records.
+  bool poses_on_device = false;
+  float4* pd_boxes = nullptr;
+  std::vector<float> pd_boxes_host;
+  uint2* pd_all = nullptr;
+  hkd::RefitUpdate* pd_records = nullptr;
+  size_t pd_cap = 0;                      // instances the three were allocated for
+  bool pd_all_ready = false;
+  uint64_t pd_all_generation = 0;
+  uint32_t pd_all_emitters = 0, pd_all_emitter_triangles = 0;
+  hipEvent_t pd_src_ready = nullptr, pd_src_read = nullptr;  // the producer's stream before the call's launches, the pose kernel before the producer
+  uint32_t last_pose[2] = {0, 0};         // hk_debug_last_pose: launches of the last call, 1 if it copied mesh boxes to the device
   uint64_t instances_generation = 0;      // counts hk_upload_instances (the instance lists of the deformable meshes follow it)
   uint64_t device_refits = 0, device_tree_builds = 0;
   void* lbvh_scratch = nullptr;           // hk_rebuild_scene_trees

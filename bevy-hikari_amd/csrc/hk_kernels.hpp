@@ -444,6 +444,13 @@ void launch_gather_instance_boxes(hipStream_t st, const hkd::RefitScene& s, cons
 void launch_refit(hipStream_t st, const hkd::RefitScene& s, const hkd::RefitUpdate* updates, uint32_t n_updates, uint32_t n_emitter_updates, uint32_t emitter_triangles,
                   uint32_t* failed, float4* tlas,
                   uint32_t tlas_count, uint32_t orderings, float4* light_lo, float4* light_hi, uint32_t light_count);
+// hk_set_instance_transforms_device: the `moved` flags of all n_instances cleared and *status (or NULL) zeroed, then one RefitUpdate per
+// named[r] = (instance, index of its pose at models + index * stride; DEVICE memory) into records[r] for launch_refit - moved 1 where the
+// pose differs bit for bit from the model the device holds and can be inverted, else 0, with 1 + the instance id of an unusable pose
+// atomicMax-ed into *status.  mesh_boxes: 2 float4 per instance (Aabb centre, half extents).  `sources_read` (or NULL) is recorded
+// behind the launch that reads `models`.  Two launches whatever n_named is (one with none named); returns how many.
+uint32_t launch_pose_records(hipStream_t st, const hkd::RefitScene& s, uint32_t n_instances, const uint2* named, uint32_t n_named, const void* models, uint32_t stride,
+                             const float4* mesh_boxes, hkd::RefitUpdate* records, uint32_t* status, hipEvent_t sources_read);
 // hk_update_materials: the changed records into `materials` (the slot's array, which s.materials names too), then - n_emitters != 0 -
 // position_radius of the listed emitters again from their instances' boxes, and the light tree refit in its shape
 void launch_material_update(hipStream_t st, const hkd::RefitScene& s, float4* materials, const hkd::MaterialUpdate* updates, uint32_t n_updates, const uint32_t* emitters,

@@ -391,6 +391,60 @@ __global__ __launch_bounds__(64) void k_mesh_instances(RefitScene s, const MeshI
   records[en.record] = r;
 }
 
+// ------------------------------------------------------------------ poses from device memory (hk_set_instance_transforms_device)
+// The host cannot diff poses it never sees: which instance moved is decided here, and k_refit_instances / k_refit_emitters then run
+// unchanged over the records written here (launch_refit), as they run over k_mesh_instances' records.
+// Phase 1, one thread per instance of the scene: every `moved` flag still set goes (an instance the call does not name is at rest; a
+// named one gets its flag back from its record), and the call's status word starts at 0.
+__global__ __launch_bounds__(64) void k_pose_begin(RefitScene s, uint32_t n_instances, uint32_t* __restrict__ status) {
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  if (i == 0u && status) *status = 0u;
+  if (i >= n_instances) return;
+  if (s.instances[i].moved != 0u) s.instances[i].moved = 0u;
+}
+// Phase 2, one thread per named instance.  named[r] = (instance, index of its pose in the caller's memory), in record order - the host
+// puts emitters first (k_refit_emitters runs on the first records only).  The 64 bytes at models + k * stride are compared bit for bit
+// with the model the device holds: equal = at rest (a record with moved 0, which every consumer passes by), else the new pose with the
+// mesh box from the plane (2 float4 per instance: Aabb centre, half extents).  A pose that is not finite or has no inverse - checked
+// with the arithmetic k_refit_instances would use - becomes a record at rest too and reports 1 + its instance id to `status`.
+// The pose is read as sixteen floats - the caller owes 4-byte alignment, no more.  The compiler merges them into four 16-byte loads whatever
+// the stride: global loads of gfx950 need no more than the element's alignment, so one form serves aligned and odd sources alike.
+__global__ __launch_bounds__(64) void k_pose_records(RefitScene s, const uint2* __restrict__ named, uint32_t n_named, const uint8_t* __restrict__ models, uint32_t stride,
+                                                     const float4* __restrict__ mesh_boxes, RefitUpdate* __restrict__ records, uint32_t* status) {
+  const uint32_t r = blockIdx.x * 64u + threadIdx.x;
+  if (r >= n_named) return;
+  const uint2 nm = named[r];
+  const uint32_t id = nm.x;
+  const uint8_t* src = models + (size_t)nm.y * stride;
+  const float* f = reinterpret_cast<const float*>(src);
+  float4 c[4];
+  for (int k = 0; k < 4; ++k) c[k] = make_float4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
+  const float m[16] = {c[0].x, c[0].y, c[0].z, c[0].w, c[1].x, c[1].y, c[1].z, c[1].w, c[2].x, c[2].y, c[2].z, c[2].w, c[3].x, c[3].y, c[3].z, c[3].w};
+  const DInstance& d = s.instances[id];
+  const float4 h[4] = {d.m0, d.m1, d.m2, d.m3};
+  uint32_t differs = 0u, finite = 1u;
+  for (int k = 0; k < 4; ++k) {
+    differs |= (f2u(c[k].x) ^ f2u(h[k].x)) | (f2u(c[k].y) ^ f2u(h[k].y)) | (f2u(c[k].z) ^ f2u(h[k].z)) | (f2u(c[k].w) ^ f2u(h[k].w));
+  }
+  for (int k = 0; k < 16; ++k)
+    if ((f2u(m[k]) & 0x7F800000u) == 0x7F800000u) finite = 0u;
+  uint32_t moved = 0u;
+  if (differs != 0u) {
+    float itm[16];
+    if (finite != 0u && inverse_transpose(m, itm)) moved = 1u;
+    else if (status) atomicMax(status, id + 1u);
+  }
+  const float4 bc = mesh_boxes[2u * id], bh = mesh_boxes[2u * id + 1u];
+  float4* out = reinterpret_cast<float4*>(records + r);  // (96 bytes per record in a 16-byte aligned array: six 16-byte stores)
+  out[0] = make_float4(u2f(id), u2f(moved), m[0], m[1]);
+  out[1] = make_float4(m[2], m[3], m[4], m[5]);
+  out[2] = make_float4(m[6], m[7], m[8], m[9]);
+  out[3] = make_float4(m[10], m[11], m[12], m[13]);
+  out[4] = make_float4(m[14], m[15], bc.x, bc.y);
+  out[5] = make_float4(bc.z, bh.x, bh.y, bh.z);
+}
+static_assert(sizeof(RefitUpdate) == 96, "k_pose_records writes a RefitUpdate as six float4");
+
 // ------------------------------------------------------------------ material and texture edits (hk_update_materials, hk_update_texture)
 // One thread per changed material: its four float4 from the pinned record into the slot's material array.
 __global__ __launch_bounds__(64) void k_write_materials(float4* __restrict__ materials, const MaterialUpdate* __restrict__ updates, uint32_t n_updates) {
@@ -481,6 +535,16 @@ void launch_refit(hipStream_t st, const RefitScene& s, const RefitUpdate* update
     }
   }
   launch_refit_trees(st, s, tlas, tlas_count, orderings, light_lo, light_hi, light_count);
+}
+
+uint32_t launch_pose_records(hipStream_t st, const RefitScene& s, uint32_t n_instances, const uint2* named, uint32_t n_named, const void* models, uint32_t stride,
+                             const float4* mesh_boxes, RefitUpdate* records, uint32_t* status, hipEvent_t sources_read) {
+  if (!n_instances) return 0u;
+  hipLaunchKernelGGL(k_pose_begin, dim3((n_instances + 63u) / 64u), dim3(64), 0, st, s, n_instances, status);
+  if (!n_named) return 1u;
+  hipLaunchKernelGGL(k_pose_records, dim3((n_named + 63u) / 64u), dim3(64), 0, st, s, named, n_named, (const uint8_t*)models, stride, mesh_boxes, records, status);
+  if (sources_read) (void)hipEventRecord(sources_read, st);  // (the last launch that reads the caller's memory)
+  return 2u;
 }
 
 uint32_t launch_mesh_propagate(hipStream_t st, const RefitScene& s, const MeshInstanceEntry* entries, uint32_t n_entries, RefitUpdate* records, uint32_t n_emitters,

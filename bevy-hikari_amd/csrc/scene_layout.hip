@@ -478,6 +478,8 @@ void update_shared_transform(hk_ctx* c) {
   c->scene.flat_mode = (c->dyn_off.flat_count && c->scene.shared_xform) ? 1u : 0u;
   // ... nor once a mesh deformed on the device: the tree was built over the host's triangles (hikari_hip.h hk_update_mesh_vertices)
   if (c->meshes_deformed) c->scene.flat_mode = 0u;
+  // ... and poses set from device memory are not in the mirrors this was derived from (hk_set_instance_transforms_device): neither shortcut
+  if (c->poses_on_device) c->scene.shared_xform = c->scene.flat_mode = 0u;
 }
 
 // point c->scene at the arrays of the slot in use
@@ -693,6 +695,7 @@ int hk_upload_instances(hk_ctx* c, const HkInstance* inst, uint32_t ni, const Hk
   c->have_instances = true;
   c->dynamic_dirty = true;
   c->mirrors_stale = false;
+  c->poses_on_device = false;   // (the mirrors are the scene again: hk_set_instance_transforms_device)
   return HK_OK;
 }
 int hk_upload_previous_transforms(hk_ctx* c, const float* models, uint32_t n) {

@@ -6,6 +6,13 @@
 using namespace hk;
 using namespace hkd;
 
+namespace {
+// what the calls that diff or lay out from the host's pose mirrors answer after hk_set_instance_transforms_device (hk_context.hpp poses_on_device)
+const char* const kPosesOnDevice =
+    "the instances' poses were last set from device memory (hk_set_instance_transforms_device): read them back (hk_read_instance_transforms), put them on "
+    "the builder and upload the instances again (hk_upload_scene_instances) first";
+}  // namespace
+
 extern "C" {
 
 // Instances added, removed or re-materialed (the reference re-runs prepare_instances for ANY instance change, instance.rs:352-437):
@@ -18,6 +25,7 @@ int hk_update_scene_instances(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode
   HK_REQUIRE(c && b, HK_E_INVALID, "NULL argument");
   HK_REQUIRE(tree_mode == HK_TREE_SAH || tree_mode == HK_TREE_LBVH, HK_E_INVALID, "unknown tree build mode %u", tree_mode);
   HK_REQUIRE(!c->meshes_deformed, HK_E_NOT_READY, "a mesh was deformed on the device: upload the host's mirror of it (hk_upload_scene) first");
+  HK_REQUIRE(!c->poses_on_device, HK_E_NOT_READY, "%s", kPosesOnDevice);
   HK_NO_PENDING_MESHES(b);  // (before the builder is finished: a refusal changes nothing)
   int rc;
   const bool trace = c->trace_update;
@@ -62,6 +70,16 @@ void free_refit(hk_ctx* c) {
   if (c->lbvh_scratch) (void)hipFree(c->lbvh_scratch);
   c->lbvh_scratch = nullptr;
   c->lbvh_scratch_cap = 0;
+  for (void* q : {(void*)c->pd_boxes, (void*)c->pd_all, (void*)c->pd_records})
+    if (q) (void)hipFree(q);
+  c->pd_boxes = nullptr; c->pd_all = nullptr; c->pd_records = nullptr;
+  c->pd_cap = 0;
+  c->pd_all_ready = false;
+  c->pd_boxes_host.clear();
+  for (hipEvent_t* e : {&c->pd_src_ready, &c->pd_src_read}) {
+    if (*e) (void)hipEventDestroy(*e);
+    *e = nullptr;
+  }
   for (int k = 0; k < 2; ++k) {
     if (c->mt_updates[k]) (void)hipHostFree(c->mt_updates[k]);
     if (c->mt_done[k]) (void)hipEventDestroy(c->mt_done[k]);
@@ -250,6 +268,7 @@ static int refit_impl(hk_ctx* c, hk_scene_builder* b, uint32_t* moved_out, bool 
   HK_REQUIRE(c && b, HK_E_INVALID, "NULL argument");
   c->scene_epoch += 1;   // (scene memory is written: hk_context.hpp, primary-ray pipelining)
   HK_REQUIRE(c->have_meshes && c->have_materials && c->have_instances, HK_E_NOT_READY, "hk_upload_scene must come first");
+  HK_REQUIRE(!c->poses_on_device, HK_E_NOT_READY, "%s", kPosesOnDevice);  // (the diff below would be against poses the device no longer holds)
   HK_HIP(hipSetDevice(c->device));
   int rc;
   if ((rc = finalize_scene(c))) return rc;
@@ -362,7 +381,209 @@ static int refit_impl(hk_ctx* c, hk_scene_builder* b, uint32_t* moved_out, bool 
   if (commit) builder_commit_transforms(b);
   return HK_OK;
 }
-int hk_refit_scene_instances(hk_ctx* c, hk_scene_builder* b, uint32_t* moved_out) { return refit_impl(c, b, moved_out, true); }}  // extern "C"
+int hk_refit_scene_instances(hk_ctx* c, hk_scene_builder* b, uint32_t* moved_out) { return refit_impl(c, b, moved_out, true); }
+
+// ---- instance poses from device memory (hikari_hip.h hk_set_instance_transforms_device; kernels k_pose_begin / k_pose_records) --------
+// What refit_impl does with poses the host never sees: the diff against the device's models, the records and the `moved` rule move into
+// two kernels, k_refit_instances / k_refit_emitters and the tree refits follow unchanged.  The host keeps what it still knows - which
+// instances emit, the builder's mesh boxes (a device plane, copied only when they changed) - and stops trusting its pose mirrors.
+}  // extern "C"
+namespace {
+// memory the context's device can read - its own, or host memory mapped for it - `extent` bytes from `p` on inside its allocation
+// (mesh_deform.hip check_source states the rule for hk_deform_meshes_device)
+int check_pose_memory(hk_ctx* c, const char* what, const void* p, size_t extent) {
+  HK_REQUIRE(((uintptr_t)p & 3u) == 0, HK_E_INVALID, "%s at %p is not aligned to 4 bytes", what, p);
+  hipPointerAttribute_t a{};
+  const hipError_t e = hipPointerGetAttributes(&a, p);
+  if (e != hipSuccess) (void)hipGetLastError();
+  HK_REQUIRE(e == hipSuccess && ((a.type == hipMemoryTypeDevice && a.device == c->device) || a.type == hipMemoryTypeHost), HK_E_INVALID,
+             "%s at %p is neither memory of device %d nor host memory the device can access", what, p, c->device);
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {  // (mapped host memory may have no range to ask for)
+    (void)hipGetLastError();
+    HK_REQUIRE(a.type == hipMemoryTypeHost, HK_E_INVALID, "%s at %p: the extent of its allocation is unknown", what, p);
+    return HK_OK;
+  }
+  HK_REQUIRE((const uint8_t*)p + extent <= (const uint8_t*)base + size, HK_E_INVALID, "%s reaches %zu bytes beyond its allocation", what,
+             (size_t)(((const uint8_t*)p + extent) - ((const uint8_t*)base + size)));
+  return HK_OK;
+}
+}  // namespace
+extern "C" {
+
+int hk_set_instance_transforms_device(hk_ctx* c, hk_scene_builder* b, const uint32_t* ids, uint32_t n, const void* d_models, uint32_t stride_bytes, void* producer_stream,
+                                      uint32_t* d_status) {
+  HK_REQUIRE(c && b && d_models, HK_E_INVALID, "NULL argument");
+  HK_REQUIRE(!(ids && n == 0), HK_E_INVALID, "instance ids given for no instance");
+  HK_REQUIRE(stride_bytes >= 64 && stride_bytes % 4 == 0, HK_E_INVALID, "a stride of %u bytes: a pose is 64 bytes, and strides are multiples of 4", stride_bytes);
+  HK_REQUIRE(c->have_meshes && c->have_materials && c->have_instances, HK_E_NOT_READY, "hk_upload_scene must come first");
+  HK_HIP(hipSetDevice(c->device));
+  const uint32_t ni = (uint32_t)c->instances.size();
+  int rc;
+  // ---- the whole call is validated before anything is enqueued or written
+  HK_REQUIRE(n <= ni, HK_E_INVALID, "%u poses for a scene of %u instances", n, ni);
+  std::vector<uint8_t> is_emitter(ni, 0);
+  for (const HkEmissive& e : c->emissives)
+    if (e.instance < ni) is_emitter[e.instance] = 1;
+  const bool all = !ids && n == ni;  // every instance named, in order: the record order is cached on the device
+  std::vector<uint2> named;          // (instance, index of its pose in the caller's memory), emitters first
+  uint32_t n_emitter_updates = 0, emitter_triangles = 0;
+  if (!all) {
+    std::vector<uint8_t> seen(ni, 0);
+    named.resize(n);
+    for (uint32_t k = 0; k < n; ++k) {
+      const uint32_t id = ids ? ids[k] : k;
+      HK_REQUIRE(id < ni, HK_E_INVALID, "instance id %u (entry %u) of a scene of %u instances", id, k, ni);
+      HK_REQUIRE(!seen[id], HK_E_INVALID, "instance %u is named twice (entry %u)", id, k);
+      seen[id] = 1;
+      if (is_emitter[id]) ++n_emitter_updates;
+    }
+    size_t front = 0, back = n_emitter_updates;
+    for (uint32_t k = 0; k < n; ++k) {
+      const uint32_t id = ids ? ids[k] : k;
+      named[is_emitter[id] ? front++ : back++] = make_uint2(id, k);
+      if (is_emitter[id]) emitter_triangles = std::max(emitter_triangles, (c->instances[id].mesh.node_count + 2u) / 3u);  // a BLAS over n triangles: 3n - 2 nodes
+    }
+  }
+  if (n && (rc = check_pose_memory(c, "the pose array", d_models, (size_t)(n - 1) * stride_bytes + 64))) return rc;
+  if (d_status && (rc = check_pose_memory(c, "the status word", d_status, 4))) return rc;
+  HK_REQUIRE(builder_instance_count(b) == ni, HK_E_INVALID, "the builder has %u instances, the uploaded scene %u: instances were added or removed (use hk_upload_scene_instances)",
+             builder_instance_count(b), ni);
+  bool boxes_changed = !c->pd_boxes || c->pd_boxes_host.size() != 8 * (size_t)ni;
+  for (uint32_t i = 0; i < ni; ++i) {
+    InstanceDecl d;
+    HK_REQUIRE(builder_instance_decl(b, i, &d), HK_E_NOT_READY, "the builder has unfinished mesh changes (hk_scene_builder_finish + hk_upload_scene first)");
+    const HkInstance& in = c->instances[i];
+    HK_REQUIRE(d.material == in.material && memcmp(&d.mesh, &in.mesh, sizeof(HkMeshIndex)) == 0, HK_E_INVALID,
+               "instance %u changed its mesh or material (use hk_upload_scene_instances)", i);
+    if (!boxes_changed) {
+      const float* h = &c->pd_boxes_host[8 * (size_t)i];
+      boxes_changed = memcmp(h, d.aabb_center, 12) != 0 || memcmp(h + 4, d.aabb_half, 12) != 0;
+    }
+  }
+  // ---- the scene as laid out, the refit's side arrays, the planes of this path (waits only where something is missing or grows)
+  if ((rc = finalize_scene(c))) return rc;
+  if ((rc = prepare_refit(c))) return rc;
+  if (ni > c->pd_cap) {
+    if ((rc = sync_all(c))) return rc;
+    for (void* q : {(void*)c->pd_boxes, (void*)c->pd_all, (void*)c->pd_records})
+      if (q) (void)hipFree(q);
+    c->pd_boxes = nullptr; c->pd_all = nullptr; c->pd_records = nullptr;
+    c->pd_cap = 0;
+    c->pd_all_ready = false;
+    const size_t cap = (size_t)ni + ni / 4;
+    HK_HIP(hipMalloc((void**)&c->pd_boxes, cap * 32));
+    HK_HIP(hipMalloc((void**)&c->pd_all, cap * sizeof(uint2)));
+    HK_HIP(hipMalloc((void**)&c->pd_records, cap * sizeof(hkd::RefitUpdate)));
+    c->pd_cap = cap;
+    boxes_changed = true;
+  }
+  c->last_pose[1] = boxes_changed ? 1u : 0u;
+  if (boxes_changed) {  // the builder's mesh boxes (builder_instance_decl, as refit_impl takes them): once per instance list, not per call
+    std::vector<float>& h = c->pd_boxes_host;
+    h.assign(8 * (size_t)ni, 0.0f);
+    for (uint32_t i = 0; i < ni; ++i) {
+      InstanceDecl d;
+      (void)builder_instance_decl(b, i, &d);
+      memcpy(&h[8 * (size_t)i], d.aabb_center, 12);
+      memcpy(&h[8 * (size_t)i + 4], d.aabb_half, 12);
+    }
+    HK_HIP(hipMemcpyAsync(c->pd_boxes, h.data(), h.size() * 4, hipMemcpyHostToDevice, c->stream));  // (behind the last call's kernels, which read the plane)
+    HK_HIP(hipStreamSynchronize(c->stream));
+  }
+  if (all && (!c->pd_all_ready || c->pd_all_generation != c->instances_generation)) {
+    std::vector<uint2> order(ni);
+    size_t front = 0, back = (size_t)std::count(is_emitter.begin(), is_emitter.end(), (uint8_t)1);
+    uint32_t triangles = 0;
+    for (uint32_t i = 0; i < ni; ++i) {
+      order[is_emitter[i] ? front++ : back++] = make_uint2(i, i);
+      if (is_emitter[i]) triangles = std::max(triangles, (c->instances[i].mesh.node_count + 2u) / 3u);
+    }
+    HK_HIP(hipMemcpyAsync(c->pd_all, order.data(), order.size() * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
+    HK_HIP(hipStreamSynchronize(c->stream));  // (`order` is a local; once per instance list)
+    c->pd_all_emitters = (uint32_t)front;
+    c->pd_all_emitter_triangles = triangles;
+    c->pd_all_generation = c->instances_generation;
+    c->pd_all_ready = true;
+  }
+  const uint2* d_named = c->pd_all;
+  int k = -1;
+  if (all) {
+    n_emitter_updates = c->pd_all_emitters;
+    emitter_triangles = c->pd_all_emitter_triangles;
+  } else if (n) {  // the call's own list, read by the kernel from a pinned block of the pool
+    uint8_t* st = nullptr;
+    if ((rc = stage(c, named.size() * sizeof(uint2), &st, &k))) return rc;
+    memcpy(st, named.data(), named.size() * sizeof(uint2));
+    d_named = (const uint2*)st;
+  }
+  hipStream_t producer = n ? (hipStream_t)producer_stream : nullptr;
+  if (producer)
+    for (hipEvent_t* e : {&c->pd_src_ready, &c->pd_src_read})
+      if (!*e) HK_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  // ---- enqueue.  Frames in flight keep reading the slot they were enqueued with (begin_device_update)
+  if ((rc = begin_device_update(c))) return rc;
+  if (producer) {  // what the producer has enqueued on the poses so far comes first; it may write them again once k_pose_records has read them
+    HK_HIP(hipEventRecord(c->pd_src_ready, producer));
+    HK_HIP(hipStreamWaitEvent(c->stream, c->pd_src_ready, 0));
+  }
+  c->scene_epoch += 1;   // (scene memory is written from here on: hk_context.hpp, primary-ray pipelining - a refusal above leaves it alone)
+  const hkd::RefitScene r = refit_scene(c);
+  uint8_t* base = c->scene_mem + (size_t)c->slot * c->dyn_capacity;
+  const uint32_t tlas_count = (uint32_t)c->instance_nodes.size(), light_count = (uint32_t)c->emissive_nodes.size();
+  uint32_t launches = launch_pose_records(c->stream, r, ni, d_named, n, d_models, stride_bytes, c->pd_boxes, c->pd_records, d_status, producer ? c->pd_src_read : nullptr);
+  HK_HIP(hipGetLastError());
+  if (producer) HK_HIP(hipStreamWaitEvent(producer, c->pd_src_read, 0));
+  launch_refit(c->stream, r, c->pd_records, n, n_emitter_updates, emitter_triangles, nullptr, (float4*)(base + c->dyn_off.tlas), tlas_count, c->threaded ? 8u : 1u,
+               (float4*)(base + c->dyn_off.light_lo), (float4*)(base + c->dyn_off.light_hi), light_count);
+  HK_HIP(hipGetLastError());
+  launches += (n ? 1u : 0u) + (n && n_emitter_updates ? 1u : 0u) + (tlas_count ? 1u : 0u) + (light_count ? 1u : 0u);
+  if (k >= 0) {
+    hk_ctx::DeformStage& st = c->df_stage[(size_t)k];
+    HK_HIP(hipEventRecord(st.done, c->stream));
+    st.pending = true;
+  }
+  // a deformed mesh's box is the device's, not the builder's: its instances' boxes, emitters and both trees once more from it
+  if (c->meshes_deformed && (rc = repropagate_deformed(c))) return rc;
+  // the update is enqueued: from here on the host's pose mirrors describe the scene as it was (the builder was not told either)
+  c->poses_on_device = true;
+  update_shared_transform(c);
+  c->d_prev_models = c->rf_prev_models;
+  c->rf_last_moved.clear();  // (the flags are the device's: k_pose_begin clears what an earlier update left)
+  c->mirrors_stale = true;
+  c->wide_tlas_dirty = true;
+  c->device_refits += 1;
+  c->last_pose[0] = launches;
+  return HK_OK;
+}
+
+// The way back: the models the device holds, in the slot the next frame would read.  Waits for the context's streams.
+int hk_read_instance_transforms(hk_ctx* c, float* models, uint32_t n) {
+  HK_REQUIRE(c && models, HK_E_INVALID, "NULL argument");
+  HK_REQUIRE(c->have_meshes && c->have_materials && c->have_instances, HK_E_NOT_READY, "hk_upload_scene must come first");
+  HK_REQUIRE(n == c->instances.size(), HK_E_INVALID, "room for %u poses, the scene has %zu instances", n, c->instances.size());
+  HK_HIP(hipSetDevice(c->device));
+  int rc;
+  if ((rc = finalize_scene(c))) return rc;
+  if ((rc = sync_all(c))) return rc;
+  std::vector<DInstance> records(n);
+  HK_HIP(hipMemcpy(records.data(), c->scene_mem + (size_t)c->slot * c->dyn_capacity + c->dyn_off.instances, (size_t)n * sizeof(DInstance), hipMemcpyDeviceToHost));
+  for (uint32_t i = 0; i < n; ++i) {
+    const float4 col[4] = {records[i].m0, records[i].m1, records[i].m2, records[i].m3};
+    memcpy(models + 16 * (size_t)i, col, 64);
+    memcpy(c->instances[i].model, col, 64);  // (the flag stays: boxes, inverses and previous models are still the device's alone)
+  }
+  return HK_OK;
+}
+// Test hook (hikari_hip_debug.h)
+int hk_debug_last_pose(hk_ctx* c, uint32_t out[2]) {
+  HK_REQUIRE(c && out, HK_E_INVALID, "NULL argument");
+  out[0] = c->last_pose[0];
+  out[1] = c->last_pose[1];
+  return HK_OK;
+}
+}  // extern "C"
 int hk::refit_instances_impl(hk_ctx* c, hk_scene_builder* b, uint32_t* moved, bool commit) { return refit_impl(c, b, moved, commit); }
 
 // ---- material edits on the device (hikari_hip.h hk_update_materials; kernels in kernels_scene.hip) ---------------------------------
@@ -430,6 +651,7 @@ int hk::update_materials_impl(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode
                   (differs[in.material] == 2 && material_emits(mats[in.material]) != material_emits(c->materials[in.material]));
   }
   if (set_changes) {
+    HK_REQUIRE(!c->poses_on_device, HK_E_NOT_READY, "%s", kPosesOnDevice);  // (this case lays the instances out from the builder's poses)
     // (refusals - a mesh deformed on the device - come from the path taken, before it writes anything: the old materials then return)
     std::vector<HkMaterial> old(mats, mats + nm);
     c->materials.swap(old);

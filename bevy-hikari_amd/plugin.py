@@ -618,6 +618,7 @@ def deform_items_device(items, device):
 class Engine:
     """One context of the C ABI (`hk_ctx`).  `api` defaults to the product library."""
     _producer = None  # deform_meshes: a torch stream standing in for torch's legacy default stream (made at the first such call)
+    _n_instances = None  # instances of the scene last uploaded / of the builder last given to set_instance_transforms (read_instance_transforms)
 
     def __init__(self, api=None, device=0, flags=0):
         self.api = api or F.api()
@@ -650,10 +651,12 @@ class Engine:
     def upload_scene(self, scene: SceneData):
         self.upload_textures(getattr(scene, "textures", []))
         scene.upload(self.api, self.ctx)
+        self._n_instances = len(scene.instances)
 
     def upload_instances(self, scene: SceneData):
         """Instance-level update of a scene whose meshes and materials are already uploaded."""
         scene.upload_instances(self.api, self.ctx)
+        self._n_instances = len(scene.instances)
 
     def load_scene(self, builder, mode=F.TREE_SAH, textures=()):
         """hk_load_scene: the upload of a FINISHED builder whose deferred meshes (SceneBuilder.add_mesh(build_tree=False)) get their trees
@@ -760,20 +763,82 @@ class Engine:
             return
         if not all(on_device):
             raise ValueError("the items of one batch are either all torch tensors on the context's device or all host arrays")
+        table, keep = deform_items_device(items, self.device)
+        self._producer_call(producer_stream, lambda handle: self.api.call("deform_meshes_device", self.ctx, table, len(items), handle))
+
+    def _producer_call(self, producer_stream, call):
+        """call(handle of the stream the C call orders itself against): `producer_stream` (a torch stream; None: torch's current stream),
+        or a stream of the engine's own standing in for torch's legacy default stream - whose handle 0 the C call reads as "the caller has
+        ordered itself" - ordered behind it before the call and in front of it after (events, no host wait)."""
         import torch
 
-        table, keep = deform_items_device(items, self.device)
         current = torch.cuda.current_stream(self.device) if producer_stream is None else producer_stream
         if current.cuda_stream:
-            self.api.call("deform_meshes_device", self.ctx, table, len(items), current.cuda_stream)
-            return
-        # the legacy default stream has the handle 0, which the C call reads as "the caller has ordered itself": a stream of the engine's
-        # own stands in for it, ordered behind it before the call and in front of it after (events, no host wait)
+            return call(current.cuda_stream)
         if self._producer is None:
             self._producer = torch.cuda.Stream(self.device)
         self._producer.wait_stream(current)
-        self.api.call("deform_meshes_device", self.ctx, table, len(items), self._producer.cuda_stream)
+        out = call(self._producer.cuda_stream)
         current.wait_stream(self._producer)
+        return out
+
+    def set_instance_transforms(self, builder, models, ids=None, producer_stream=None, status=None):
+        """Instance poses from device memory (hk_set_instance_transforms_device).  `models`: a float32 torch tensor (n, 4, 4) or (n, 16) on
+        the context's device, pose k = 16 floats in column-major order (what SceneBuilder.set_instance_transform takes), rows at any
+        stride - a column slice state[:, :16] of a wider state tensor is read where it lies.  `ids` (a host sequence) names the instance
+        of every row; None: rows 0 .. n - 1 are instances 0 .. n - 1.  Which instance moved is decided on the device; an instance not
+        named is at rest.  `status` (a 1-element int32 / uint32 tensor on the device, optional) receives 1 + the highest instance id
+        whose pose was not finite or singular - such an instance keeps its pose - or 0, in stream order.  The context is ordered behind
+        `producer_stream` (default: torch's current stream) and that stream behind the context's read of `models`, by events: there is
+        no host wait, and the tensor may be overwritten right after the call.  Afterwards refit_instances and
+        update_instances_on_device are refused until read_instance_transforms + SceneBuilder.set_instance_transform +
+        upload_instances bring the poses back to the host."""
+        if not _is_device_tensor(models):
+            raise TypeError("models must be a torch tensor on the context's device (host poses go through SceneBuilder.set_instance_transform and refit_instances)")
+        import torch
+
+        if models.device.index != self.device:
+            raise ValueError(f"the tensor lies on {models.device}, the context on cuda:{self.device}")
+        if models.dim() == 3 and tuple(models.shape[1:]) == (4, 4):
+            if len(models) and (models.stride(2) != 1 or models.stride(1) != 4):
+                models = models.contiguous()
+            models = models.as_strided((len(models), 16), (models.stride(0) if len(models) else 16, 1), models.storage_offset())
+        if models.dim() != 2 or models.shape[1] != 16:
+            raise ValueError(f"expected poses of shape (n, 4, 4) or (n, 16), not {tuple(models.shape)}")
+        if models.dtype != torch.float32 or (len(models) > 1 and (models.stride(1) != 1 or models.stride(0) < 16)) or (len(models) <= 1 and not models.is_contiguous()):
+            models = models.to(torch.float32).contiguous()
+        n = len(models)
+        id_array = None
+        if ids is not None:
+            id_array = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+            if len(id_array) != n:
+                raise ValueError(f"{len(id_array)} ids for {n} poses")
+        if status is not None and (not _is_device_tensor(status) or status.numel() < 1 or status.element_size() != 4):
+            raise TypeError("status must be a 4-byte integer tensor on the context's device")
+        stride = 4 * models.stride(0) if n > 1 else 64
+        self._producer_call(producer_stream, lambda handle: self.api.call(
+            "set_instance_transforms_device", self.ctx, builder.h, None if id_array is None else id_array.ctypes.data_as(C.POINTER(F.u32)), n, models.data_ptr(), stride, handle,
+            None if status is None else status.data_ptr()))
+        p, count = C.POINTER(F.HkInstance)(), F.u32()
+        if self.api.raw("scene_builder_instances")(builder.h, C.byref(p), C.byref(count)) == F.HK_OK:
+            self._n_instances = count.value   # (the call has checked it against the scene's)
+
+    def read_instance_transforms(self, n=None):
+        """The poses the device holds, float32 (n, 16), column-major (hk_read_instance_transforms; waits for the context's streams): the
+        way back after set_instance_transforms.  `n`: the scene's instance count; None: the count of the scene last uploaded through
+        this engine or of the builder last given to set_instance_transforms."""
+        count = self._n_instances if n is None else int(n)
+        if count is None:
+            raise ValueError("the engine has not seen the scene's instance count: pass n")
+        out = np.zeros((max(count, 1), 16), np.float32)
+        self.api.call("read_instance_transforms", self.ctx, out.ctypes.data_as(C.POINTER(F.f32)), count)
+        return out[:count]
+
+    def last_pose(self):
+        """(kernel launches of the last set_instance_transforms, 1 if it copied mesh boxes to the device) - hk_debug_last_pose (test hook)."""
+        out = (F.u32 * 2)()
+        self.api.call("debug_last_pose", self.ctx, out)
+        return tuple(int(v) for v in out)
 
     def last_deform(self):
         """(items, vertices, triangles, enqueues of the call, launches of the last flush, launches of the last wide-record derivation) -
@@ -1330,6 +1395,14 @@ class HikariPlugin:
     def deform_meshes(self, items, producer_stream=None):
         """Per frame, every deforming mesh of the scene in one call: Engine.deform_meshes."""
         self.engine.deform_meshes(items, producer_stream)
+
+    def set_instance_transforms(self, builder, models, ids=None, producer_stream=None, status=None):
+        """Per frame, instance poses that live in device memory: Engine.set_instance_transforms."""
+        self.engine.set_instance_transforms(builder, models, ids, producer_stream, status)
+
+    def read_instance_transforms(self):
+        """The poses the device holds (Engine.read_instance_transforms)."""
+        return self.engine.read_instance_transforms()
 
     def update_instances(self, scene: SceneData):
         """Instances moved (prepare_instances, instance.rs:352-437): rewrite the instance-level buffers only."""

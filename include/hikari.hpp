@@ -433,6 +433,21 @@ class HikariPlugin {
     check(hk_deform_meshes_device(ctx_.get(), items.data(), (uint32_t)items.size(), producer_stream), "hk_deform_meshes_device");
   }
   void rebuild_mesh_tree(const HkMeshIndex& mesh, uint32_t mode = HK_TREE_SAH) { check(hk_rebuild_mesh_tree(ctx_.get(), &mesh, mode), "hk_rebuild_mesh_tree"); }
+  // instance poses from DEVICE memory: pose k (16 floats, column-major) at d_models + k * stride_bytes is instance ids[k]'s (ids empty: instance
+  // k's, n of them); which instance moved is decided on the device.  d_status (device, or nullptr): 1 + the highest instance id whose pose was
+  // unusable, or 0, in stream order.  refit_instances / hk_update_scene_instances are refused until update_instances brings the host's poses back
+  void set_instance_transforms_device(SceneBuilder& b, const std::vector<uint32_t>& ids, uint32_t n, const void* d_models, uint32_t stride_bytes = 64,
+                                      void* producer_stream = nullptr, uint32_t* d_status = nullptr) {
+    check(hk_set_instance_transforms_device(ctx_.get(), b.handle(), ids.empty() ? nullptr : ids.data(), ids.empty() ? n : (uint32_t)ids.size(), d_models, stride_bytes,
+                                            producer_stream, d_status),
+          "hk_set_instance_transforms_device");
+  }
+  // ... and the way back: the models the device holds (waits for the context's streams), 16 floats per instance
+  std::vector<float> read_instance_transforms(uint32_t n_instances) {
+    std::vector<float> models(16 * (size_t)n_instances);
+    check(hk_read_instance_transforms(ctx_.get(), models.data(), n_instances), "hk_read_instance_transforms");
+    return models;
+  }
 
   // one frame of the camera's render graph; by_nodes = dispatch by dispatch through the three nodes,
   // otherwise one hk_frame_render call.  Returns the frame number used.

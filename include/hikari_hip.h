@@ -714,6 +714,44 @@ typedef struct HkMeshDeformDevice {
   uint32_t    _pad;
 } HkMeshDeformDevice;          /* 56 bytes */
 int hk_deform_meshes_device(hk_ctx* ctx, const HkMeshDeformDevice* items, uint32_t n, void* producer_stream);
+/* Instance POSES FROM DEVICE MEMORY (rigid bodies stepped on the GPU, a crowd placed by a kernel): what hk_refit_scene_instances does for
+ * poses the host never sees.  After the call the device scene holds, byte for byte, what hk_refit_scene_instances would have left had the
+ * same values been set on the builder with hk_scene_builder_set_instance_transform: instance records, previous models, world boxes,
+ * emitter records with their alias tables, both trees refit in their shape; the same statistics (scene_device_refits += 1).
+ *   instance_ids (HOST memory) names n distinct instances, pose k at d_models + k * stride_bytes (16 floats, column-major; stride_bytes
+ * >= 64 and a multiple of 4; 4-byte alignment is all a pose needs).  NULL names instances 0 .. n - 1.
+ *   Which instance moved is decided on the device.  A named instance whose 16 floats equal the model the device holds bit for bit is at
+ * rest (`moved` cleared, previous model = model); any other named instance takes the pose and keeps the model it had as its previous
+ * one; an instance the call does not name is at rest, whichever call moved it last (a pass over all instances clears the flags first).
+ *   A pose that is not finite or has no inverse (the builder's own test: the determinant of the double-precision cofactor expansion is
+ * 0) is not taken: the instance keeps its pose and is at rest.  d_status (DEVICE memory, 4 bytes, or NULL) receives 1 + the highest
+ * such instance id of the call, or 0, in stream order - the call cannot return an error for values it has not read.
+ *   `b` is the builder the scene came from: it supplies each instance's mesh box (kept in a device plane and copied only when it changed:
+ * a warm call copies nothing per instance beyond the 8 bytes of a named id) and is validated as hk_refit_scene_instances validates it
+ * (same instance count, meshes, materials; finished mesh level).  Its previous-transform bookkeeping does not advance: it was not told.
+ * Meshes deformed on the device keep their device box, as after hk_refit_scene_instances.
+ *   Ordering: the rule of hk_deform_meshes_device.  With producer_stream != NULL the context's stream waits for an event recorded there
+ * at the call, and the producer then waits for an event behind the kernel that reads d_models (and writes d_status): the caller may
+ * overwrite the poses in stream order right after the call.  NULL: the caller has ordered itself.  A warm call - not the first for an
+ * instance list - never waits on the host; two-slot scenes are updated in the spare slot, one-slot scenes in place behind everything
+ * enqueued.
+ *   Validated as a whole before anything is enqueued; HK_E_INVALID with nothing written for: NULL ctx / b / d_models, ids given with n ==
+ * 0, n or an id beyond the instance count, an id named twice, a bad stride, d_models or d_status misaligned (4 bytes), not memory of the
+ * context's device nor host memory mapped for it, or reaching beyond its allocation; a builder that is not the scene's.  HK_E_NOT_READY
+ * without a scene or for a builder with unfinished mesh changes.
+ *   Afterwards the host's copies of the poses, boxes and previous models no longer describe the device (as its trees and emitter records
+ * do not after any device-side update).  What would diff against or lay out from them is refused with HK_E_NOT_READY:
+ * hk_refit_scene_instances, hk_update_scene_instances, case B of hk_update_materials, hk_scene_bounds; a band of a sharded frame that
+ * derives its history rows takes all of them.  The one-level walk and the shared-transform shortcut are off (hk_traversal_mode reports
+ * it).  Case A of hk_update_materials, hk_rebuild_scene_trees, hk_add_meshes, the deformation calls, hk_rebuild_mesh_tree, hk_cast_rays*
+ * and hk_update_texture work from device state and stay usable.  hk_upload_scene_instances / hk_upload_instances / hk_upload_scene end
+ * the state.  There is no hk_multi_ form, as hk_deform_meshes_device has none: a device pointer lives on one device. */
+int hk_set_instance_transforms_device(hk_ctx* ctx, hk_scene_builder* b, const uint32_t* instance_ids, uint32_t n, const void* d_models,
+                                      uint32_t stride_bytes, void* producer_stream, uint32_t* d_status);
+/* ... and the way back: waits for the context's streams and copies the models the device holds - the slot the next frame would read - to
+ * `models` (n x 16 floats, n = the instance count).  The context's own copies of the models follow; the state above stays until the host
+ * has put the poses on its builder and called hk_upload_scene_instances. */
+int hk_read_instance_transforms(hk_ctx* ctx, float* models, uint32_t n);
 /* ... and the REBUILD of one mesh's tree on the device, for when refits have degraded it (a skinned character far from its bind pose,
  * a cloth folded onto itself): a new tree over the mesh's current triangle boxes, written in place over the mesh's nodes in the
  * mesh-level region - ordering 0 in the builder's left-before-right order, orderings 1-7 by the rule of hk_bvh_rethread, single-leaf

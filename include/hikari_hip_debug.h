@@ -49,6 +49,10 @@ int hk_debug_read_emitters(hk_ctx* ctx, float* records, uint32_t records_cap, ui
  * frame or a read, after single-mesh calls too), out[5] the kernel launches of the last derivation of wide records.  out[0..3] are zero
  * until a batch ran; a refused batch leaves them as they were. */
 int hk_debug_last_deform(hk_ctx* ctx, uint32_t out[6]);
+/* What the last accepted hk_set_instance_transforms_device did: out[0] its kernel launches (the two pose kernels, the refit of the named
+ * instances, of the named emitters, of the two trees; the slot copy of a two-slot scene and event records not counted), out[1] 1 if it
+ * copied the builder's mesh boxes to the device (the first call for an instance list), else 0.  A refused call leaves them as they were. */
+int hk_debug_last_pose(hk_ctx* ctx, uint32_t out[2]);
 
 /* Measurement hook ("measure the empirical HBM ceiling with a device copy/triad kernel in the same run"): streams
  * three private arrays of `bytes_per_array` bytes (use >= 1 GiB: the 256 MB Infinity Cache must not hold them) `reps` times
