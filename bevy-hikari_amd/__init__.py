@@ -24,6 +24,7 @@ from .plugin import (  # noqa: F401
     Taa,
     Upscale,
     cornell_camera,
+    encode_texels,
     frame_uniform,
     graph,
     lights_uniform,

@@ -65,6 +65,8 @@ RAYS_CLOSEST, RAYS_ANY, RAYS_ATTRIBUTES, RAYS_STACKLESS = 0, 1, 2, 4  # hk_cast_
 RAY_MISS, RAY_HIT, RAY_INVALID = 0, 1, 2                              # HkRayHit.status
 DEFORM_VERTICES, DEFORM_SKIN = 0, 1                                   # HkMeshDeform.kind
 DEFORM_RECOMPUTE_NORMALS = 1                                          # HkMeshDeformDevice.flags
+TEXELS_U8, TEXELS_F16, TEXELS_F32 = 0, 1, 2                           # HkTextureSource.format
+TEXTURE_SET_SAMPLER, TEXTURE_LINEAR_SOURCE = 1, 2                     # HkTextureSource.flags
 NO_INSTANCE = 0xFFFFFFFF                                              # HkRay.exclude_instance "nothing"; HkRayHit.instance / primitive of a miss
 
 f32, u32, u64 = C.c_float, C.c_uint32, C.c_uint64
@@ -168,6 +170,12 @@ class HkMeshDeformDevice(C.Structure):
                 ("data_stride", u32), ("normals_stride", u32), ("flags", u32), ("_pad", u32)]
 
 
+class HkTextureSource(C.Structure):
+    _fields_ = [("index", u32), ("format", u32), ("data", C.c_void_p), ("stride_x", u64), ("stride_y", u64), ("stride_c", u64),
+                ("channels", u32), ("x0", u32), ("y0", u32), ("width", u32), ("height", u32), ("flags", u32),
+                ("is_srgb", u32), ("address_u", u32), ("address_v", u32), ("filter_linear", u32)]
+
+
 class HkHaloOp(C.Structure):
     _fields_ = [("buffer", u32), ("peer", u32), ("row_begin", u32), ("row_end", u32), ("row_bytes", u64)]
 
@@ -193,6 +201,7 @@ assert C.sizeof(HkVertex) == 32 and C.sizeof(HkPrimitive) == 48 and C.sizeof(HkN
 assert C.sizeof(HkMaterial) == 80 and C.sizeof(HkEmissive) == 64 and C.sizeof(HkFrame) == 256 and C.sizeof(HkView) == 416
 assert C.sizeof(HkPreviousView) == 128 and C.sizeof(HkAliasEntry) == 8
 assert C.sizeof(HkRay) == 32 and C.sizeof(HkRayHit) == 48 and C.sizeof(HkMeshDeform) == 40 and C.sizeof(HkMeshDeformDevice) == 56
+assert C.sizeof(HkTextureSource) == 80
 
 
 class HikariError(RuntimeError):
@@ -246,6 +255,7 @@ _DEBUG = {
     "debug_read_mesh_geometry": [_vp, P(HkMeshIndex), P(f32), P(f32), u32, P(f32), u32, P(f32), P(u32), P(u32)],
     "debug_last_deform": [_vp, P(u32)],
     "debug_last_pose": [_vp, P(u32)],
+    "debug_last_texture_update": [_vp, P(u32)],
     "debug_comm_loopback": [_vp, u32, u32, u32, u32, u32],
     "debug_read_wf_timeline": [_vp, P(C.c_uint64), u32],
     "debug_set_option": [_vp, u32, C.c_int64],
@@ -300,6 +310,9 @@ _PRODUCT_ONLY = {
     "update_scene_instances": [_vp, _vp, u32],
     "update_materials": [_vp, _vp, u32, P(u32)],
     "update_texture": [_vp, u32, P(HkImageDesc)],
+    "update_textures_device": [_vp, P(HkTextureSource), u32, _vp],
+    "read_texture": [_vp, u32, _vp, C.c_size_t],
+    "encode_texels": [P(HkTextureSource), u32, _vp],
     "update_mesh_vertices": [_vp, P(HkMeshIndex), u32, P(f32), P(f32)],
     "set_mesh_skin": [_vp, P(HkMeshIndex), u32, P(f32), P(f32), P(C.c_uint16), P(f32)],
     "skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],

@@ -1185,6 +1185,9 @@ void hk_destroy(hk_ctx* c) {
   for (void* q : {(void*)c->wide_tlas, (void*)c->wide_blas, (void*)c->wide_spill, (void*)c->wide_tlas_rank, (void*)c->wide_blas_rank})
     if (q) (void)hipFree(q);
   c->d_tex_data.release();
+  if (c->tx_thresholds) (void)hipFree(c->tx_thresholds);
+  for (hipEvent_t e : {c->tx_src_ready, c->tx_src_read})
+    if (e) (void)hipEventDestroy(e);
   c->d_noise.release();
   if (c->d_counters) (void)hipFree(c->d_counters);
   if (c->side_stream) (void)hipStreamDestroy(c->side_stream);

@@ -354,6 +354,13 @@ struct hk_ctx {
   const float4* d_prev_models = nullptr;  // 4 columns per instance, valid where DInstance::moved
   DevArray<uint32_t> d_noise;
   DevArray<uint32_t> d_tex_data;
+  // textures from device memory (hk_update_textures_device, scene_layout.hip): the 256 thresholds of the sRGB encoding (host_logic.cpp
+  // srgb_encode_thresholds; made at the first call), the producer's stream before the launch and the launch before the producer, which
+  // textures' host copies (textures[i].texels) no longer hold what the device does, and what the last accepted call did
+  float* tx_thresholds = nullptr;
+  hipEvent_t tx_src_ready = nullptr, tx_src_read = nullptr;
+  std::vector<uint8_t> tx_host_stale;
+  uint32_t last_texture_update[3] = {0, 0, 0};  // hk_debug_last_texture_update: items, kernel launches, texels
   DScene scene{};
 
   // screen-space resources
@@ -470,6 +477,8 @@ hkd::RefitScene refit_scene(hk_ctx* c);
 // ---- mesh_deform.hip
 void free_deform(hk_ctx* c);
 int stage(hk_ctx* c, size_t bytes, uint8_t** out, int* k);   // a pinned staging buffer from the pool (c->df_stage[*k]: record its `done` event behind the reader)
+// a caller's source in device memory (hk_deform_meshes_device, hk_update_textures_device): aligned, the context's device's or mapped host memory, `extent` bytes inside its allocation
+int check_source(hk_ctx* c, uint32_t item, const char* what, const void* p, size_t align, size_t extent);
 int repropagate_deformed(hk_ctx* c);   // after an instance refit: the deformed meshes' current boxes again (hk_refit_scene_instances)
 int flush_deform(hk_ctx* c);           // the instance level of the meshes deformed since the last flush, once (frames, tree rebuilds, reads)
 }  // namespace hk

@@ -72,6 +72,19 @@ int update_materials_impl(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode, ui
 int upload_instances_and_build_trees(hk_ctx* c, const hk_scene_builder* b, uint32_t tree_mode);  // scene_refit.hip
 int refit_instances_impl(hk_ctx* c, hk_scene_builder* b, uint32_t* moved, bool commit);  // hk_refit_scene_instances
 
+// ---- material textures (host_logic.cpp): the 256-entry sRGB decode table the samplers read (the EOTF in double, rounded once), and the
+// 255 thresholds of its inverse (hikari_hip.h HK_TEXTURE_LINEAR_SOURCE): mid[k] = (float)((lut[k - 1] + lut[k]) / 2) in double for
+// k = 1 .. 255, mid[0] = -1 (below every clamped value; never compared)
+void srgb_decode_table(float lut[256]);
+void srgb_encode_thresholds(float mid[256]);
+// hk_update_textures_device / hk_encode_texels: bytes of an element of `format` (0: unknown); what both calls check of one item without a
+// device (returns HK_OK or sets the error); the bytes from `data` on that the item's rectangle reads, from its strides; whether the
+// rectangles of two items of one texture share a texel
+uint32_t texel_element_bytes(uint32_t format);
+int check_texture_source(const HkTextureSource& it, uint32_t item);
+size_t texture_source_extent(const HkTextureSource& it);
+bool texture_rectangles_overlap(const HkTextureSource& a, const HkTextureSource& b);
+
 // bytes per pixel / full-size flag of an HkBuffer id (0 = invalid id)
 uint32_t buffer_bpp(uint32_t buffer);
 bool buffer_is_full_size(uint32_t buffer);

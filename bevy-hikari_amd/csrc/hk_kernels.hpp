@@ -179,6 +179,24 @@ struct DeformItem {
 struct SegmentBlock {
   uint32_t segment, first;
 };
+// One item of hk_update_textures_device (kernels_scene.hip k_update_textures): a rectangle of one texture and the caller's strided source
+// for it.  The table lies in the pinned staging block of the call; a workgroup (SegmentBlock: segment = item, first = a row of the
+// rectangle) converts `rows` rows from `first` on.
+struct TextureItem {
+  const uint8_t* src;                // DEVICE memory: element (x, y, ch) at src + y * stride_y + x * stride_x + ch * stride_c
+  uint64_t stride_x, stride_y, stride_c;
+  uint32_t dst;                      // the texel of the rectangle's corner (x0, y0), counted from the start of the texel buffer
+  uint32_t pitch;                    // the texture's width
+  uint32_t width, height;            // the rectangle
+  uint32_t format, channels;         // HK_TEXELS_*; 1, 3 or 4
+  uint32_t mode;                     // HK_TEXTURE_ITEM_*
+  uint32_t rows;                     // rows of the rectangle per workgroup
+  uint32_t index;                    // the texture: its descriptor becomes `info`
+  uint32_t pad[3];
+  uint4 info;
+};
+constexpr uint32_t HK_TEXTURE_ITEM_ENCODE = 1u;   // rgb are linear light of an sRGB texture: encoded through the thresholds
+constexpr uint32_t HK_TEXTURE_ITEM_PACKED = 2u;   // four channels side by side, every element aligned to all four: one 4 / 8 / 16 B load
 // One instance of a deformed mesh (kernels_scene.hip k_mesh_instances): the mesh's box words, and the emitter record to write if it emits
 struct MeshInstanceEntry {
   uint32_t instance;
@@ -457,6 +475,12 @@ void launch_material_update(hipStream_t st, const hkd::RefitScene& s, float4* ma
                             uint32_t n_emitters, float4* light_lo, float4* light_hi, uint32_t light_count);
 // hk_update_texture: n texels from pinned memory to their place in the texel buffer, and the texture's descriptor into `info0` / `info1` (or NULL)
 void launch_texture_update(hipStream_t st, uint32_t* dst, const uint32_t* src, size_t n, uint4* info0, uint4* info1, uint4 info);
+// hk_update_textures_device: every item's rectangle converted from the caller's memory into the texel buffer and every item's descriptor
+// into info0[index] / info1[index] (or NULL), in ONE launch of n_blocks workgroups whatever the number of items (`items`, `blocks`: pinned).
+// `thresholds`: 256 floats in device memory (hk_internal.hpp srgb_encode_thresholds).  `sources_read` (or NULL) is recorded behind it.
+// Returns the kernels it launched.
+uint32_t launch_textures_update(hipStream_t st, uint32_t* tex_data, const hkd::TextureItem* items, const hkd::SegmentBlock* blocks, uint32_t n_blocks,
+                                const float* thresholds, uint4* info0, uint4* info1, hipEvent_t sources_read);
 // A new tree over n shapes, built on the device into a flat skip-link BVH (kernels_tree.hip): the scratch one build needs in either
 // mode, and the build
 size_t lbvh_scratch_bytes(uint32_t n);

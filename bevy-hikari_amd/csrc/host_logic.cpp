@@ -203,6 +203,82 @@ bool rethread_flat_bvh(const HkNode* nodes, uint32_t count, uint32_t oct, HkNode
   return out_pos == count;
 }
 
+// ---- material textures: the sRGB decode table and its inverse by thresholds, the checks of a texture source (hk_internal.hpp)
+void srgb_decode_table(float lut[256]) {
+  for (int i = 0; i < 256; ++i) {  // sRGB EOTF in double, rounded once
+    double v = i / 255.0;
+    lut[i] = (float)(v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4));
+  }
+}
+void srgb_encode_thresholds(float mid[256]) {
+  float lut[256];
+  srgb_decode_table(lut);
+  mid[0] = -1.0f;
+  for (int k = 1; k < 256; ++k) mid[k] = (float)(((double)lut[k - 1] + (double)lut[k]) / 2);
+}
+uint32_t texel_element_bytes(uint32_t format) { return format == HK_TEXELS_U8 ? 1u : format == HK_TEXELS_F16 ? 2u : format == HK_TEXELS_F32 ? 4u : 0u; }
+int check_texture_source(const HkTextureSource& it, uint32_t i) {
+  const uint32_t elem = texel_element_bytes(it.format);
+  HK_REQUIRE(elem, HK_E_INVALID, "item %u: unknown format %u", i, it.format);
+  const uint32_t known = HK_TEXTURE_SET_SAMPLER | HK_TEXTURE_LINEAR_SOURCE;
+  HK_REQUIRE(!(it.flags & ~known), HK_E_INVALID, "item %u: unknown flag bits 0x%x", i, it.flags & ~known);
+  HK_REQUIRE(!(it.flags & HK_TEXTURE_LINEAR_SOURCE) || it.format != HK_TEXELS_U8, HK_E_INVALID,
+             "item %u: HK_TEXTURE_LINEAR_SOURCE on 8-bit texels (bytes are taken as they are)", i);
+  HK_REQUIRE(it.channels == 1 || it.channels == 3 || it.channels == 4, HK_E_INVALID, "item %u: %u channels (1, 3 or 4)", i, it.channels);
+  HK_REQUIRE(it.data, HK_E_INVALID, "item %u: NULL data", i);
+  HK_REQUIRE(it.width && it.height, HK_E_INVALID, "item %u: an empty rectangle (%u x %u)", i, it.width, it.height);
+  HK_REQUIRE(it.width <= 16384 && it.height <= 16384, HK_E_INVALID, "item %u: a rectangle of %u x %u (no texture is larger than 16384 x 16384)", i, it.width, it.height);
+  for (const uint64_t s : {it.stride_x, it.stride_y, it.stride_c}) {
+    HK_REQUIRE(s % elem == 0, HK_E_INVALID, "item %u: a stride of %llu bytes is no multiple of the element size %u", i, (unsigned long long)s, elem);
+    HK_REQUIRE(s <= ((uint64_t)1 << 40), HK_E_INVALID, "item %u: a stride of %llu bytes (beyond 2^40)", i, (unsigned long long)s);
+  }
+  HK_REQUIRE(((uintptr_t)it.data & (elem - 1u)) == 0, HK_E_INVALID, "item %u: the texels at %p are not aligned to %u bytes", i, it.data, elem);
+  return HK_OK;
+}
+size_t texture_source_extent(const HkTextureSource& it) {
+  return (size_t)((it.width - 1u) * it.stride_x + (it.height - 1u) * it.stride_y + (it.channels - 1u) * it.stride_c + texel_element_bytes(it.format));
+}
+bool texture_rectangles_overlap(const HkTextureSource& a, const HkTextureSource& b) {
+  return a.index == b.index && a.x0 < b.x0 + b.width && b.x0 < a.x0 + a.width && a.y0 < b.y0 + b.height && b.y0 < a.y0 + a.height;
+}
+
+namespace {
+inline float half_to_float(uint16_t h) {  // exact: every half is an f32
+  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, exp = (h >> 10) & 31u, man = h & 1023u;
+  uint32_t bits;
+  if (exp == 31u) {
+    bits = sign | 0x7F800000u | (man << 13);
+  } else if (exp) {
+    bits = sign | ((exp + 112u) << 23) | (man << 13);
+  } else if (man) {
+    int e = -1;
+    uint32_t m = man;
+    do { m <<= 1; ++e; } while (!(m & 1024u));
+    bits = sign | ((uint32_t)(112 - e) << 23) | ((m & 1023u) << 13);
+  } else {
+    bits = sign;
+  }
+  float f;
+  memcpy(&f, &bits, 4);
+  return f;
+}
+inline float texel_clamp(float x) {
+  if (x != x) return 0.0f;
+  return std::min(std::max(x, 0.0f), 1.0f);
+}
+inline uint32_t texel_unorm(float x) {  // two separately rounded f32 operations (the library is built with -ffp-contract=off)
+  const float p = texel_clamp(x) * 255.0f;
+  return (uint32_t)(p + 0.5f);
+}
+inline uint32_t texel_srgb(float x, const float* mid) {  // the number of k in 1 .. 255 with v > mid[k]: mid ascends
+  const float v = texel_clamp(x);
+  uint32_t k = 0;
+  for (uint32_t step = 128; step; step >>= 1)
+    if (v > mid[k + step]) k += step;
+  return k;
+}
+}  // namespace
+
 }  // namespace hk
 
 using namespace hk;
@@ -211,6 +287,42 @@ extern "C" {
 
 uint32_t hk_abi_version(void) { return HK_ABI_VERSION; }
 const char* hk_last_error(void) { return g_error; }
+
+// the host twin of k_update_textures (kernels_scene.hip): one item's rectangle from host memory, element by element
+int hk_encode_texels(const HkTextureSource* item, uint32_t texture_is_srgb, uint8_t* out) {
+  HK_REQUIRE(item && out, HK_E_INVALID, "NULL argument");
+  const HkTextureSource& it = *item;
+  const int rc = check_texture_source(it, 0);
+  if (rc) return rc;
+  float mid[256];
+  const bool encode = (it.flags & HK_TEXTURE_LINEAR_SOURCE) && texture_is_srgb;
+  if (encode) srgb_encode_thresholds(mid);
+  const uint8_t* base = (const uint8_t*)it.data;
+  for (uint32_t y = 0; y < it.height; ++y)
+    for (uint32_t x = 0; x < it.width; ++x) {
+      uint32_t b[4] = {0, 0, 0, 255};
+      for (uint32_t ch = 0; ch < it.channels; ++ch) {
+        const uint8_t* p = base + y * it.stride_y + x * it.stride_x + ch * it.stride_c;
+        if (it.format == HK_TEXELS_U8) {
+          b[ch] = *p;
+          continue;
+        }
+        float f;
+        if (it.format == HK_TEXELS_F16) {
+          uint16_t h;
+          memcpy(&h, p, 2);
+          f = half_to_float(h);
+        } else {
+          memcpy(&f, p, 4);
+        }
+        b[ch] = encode && ch < 3 ? texel_srgb(f, mid) : texel_unorm(f);  // (channel 3 is alpha: the plain rule)
+      }
+      if (it.channels == 1) b[1] = b[2] = b[0];
+      uint8_t* o = out + ((size_t)y * it.width + x) * 4;
+      for (int k = 0; k < 4; ++k) o[k] = (uint8_t)b[k];
+    }
+  return HK_OK;
+}
 
 int hk_settings_default(HkSettings* s) {  // lib.rs:435-455
   HK_REQUIRE(s, HK_E_INVALID, "settings is NULL");

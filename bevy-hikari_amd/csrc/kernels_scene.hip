@@ -473,6 +473,85 @@ __global__ __launch_bounds__(256) void k_update_texture(uint32_t* __restrict__ d
   }
 }
 
+// ------------------------------------------------------------------ textures from device memory (hk_update_textures_device)
+// The conversion of hikari_hip.h, element by element: host_logic.cpp hk_encode_texels is its twin, operation for operation.
+namespace {
+__device__ __forceinline__ float texel_clamp(float x) { return x != x ? 0.0f : fminf(fmaxf(x, 0.0f), 1.0f); }
+__device__ __forceinline__ uint32_t texel_unorm(float x) { return (uint32_t)__fadd_rn(__fmul_rn(texel_clamp(x), 255.0f), 0.5f); }
+// the number of k in 1 .. 255 with v > mid[k] (mid ascends): eight compare steps, no divergence
+__device__ __forceinline__ uint32_t texel_srgb(float x, const float* mid) {
+  const float v = texel_clamp(x);
+  uint32_t k = 0u;
+#pragma unroll
+  for (uint32_t step = 128u; step; step >>= 1) k += v > mid[k + step] ? step : 0u;
+  return k;
+}
+__device__ __forceinline__ float half_bits(uint32_t h) { return (float)__builtin_bit_cast(_Float16, (unsigned short)h); }  // exact
+__device__ __forceinline__ float texel_float(const uint8_t* p, bool half) { return half ? half_bits(*(const unsigned short*)p) : *(const float*)p; }
+// one texel of an item: its element(s) at (x, y) of the source, converted and packed r | g << 8 | b << 16 | a << 24
+__device__ __forceinline__ uint32_t texel_word(const TextureItem& it, bool encode, bool packed, bool half, const float* mid, uint32_t x, uint32_t y) {
+  const uint8_t* p = it.src + (size_t)y * it.stride_y + (size_t)x * it.stride_x;
+  if (it.format == HK_TEXELS_U8) {
+    if (packed) return *(const uint32_t*)p;
+    const uint32_t r = p[0];
+    uint32_t g = r, b = r, a = 255u;
+    if (it.channels >= 3u) {
+      g = p[it.stride_c];
+      b = p[2u * it.stride_c];
+    }
+    if (it.channels == 4u) a = p[3u * it.stride_c];
+    return r | (g << 8) | (b << 16) | (a << 24);
+  }
+  float f0, f1, f2, f3 = 1.0f;
+  if (packed && half) {
+    const uint2 q = *(const uint2*)p;
+    f0 = half_bits(q.x & 0xFFFFu); f1 = half_bits(q.x >> 16); f2 = half_bits(q.y & 0xFFFFu); f3 = half_bits(q.y >> 16);
+  } else if (packed) {
+    const float4 q = *(const float4*)p;
+    f0 = q.x; f1 = q.y; f2 = q.z; f3 = q.w;
+  } else {
+    f0 = f1 = f2 = texel_float(p, half);
+    if (it.channels >= 3u) {
+      f1 = texel_float(p + it.stride_c, half);
+      f2 = texel_float(p + 2u * it.stride_c, half);
+    }
+    if (it.channels == 4u) f3 = texel_float(p + 3u * it.stride_c, half);
+  }
+  const uint32_t r = encode ? texel_srgb(f0, mid) : texel_unorm(f0);
+  const uint32_t g = encode ? texel_srgb(f1, mid) : texel_unorm(f1);
+  const uint32_t b = encode ? texel_srgb(f2, mid) : texel_unorm(f2);
+  const uint32_t a = it.channels == 4u ? texel_unorm(f3) : 255u;
+  return r | (g << 8) | (b << 16) | (a << 24);
+}
+}  // namespace
+// One workgroup per span of rows of ONE item's rectangle (hk_kernels.hpp TextureItem, SegmentBlock): lanes run along x, so a wave reads
+// whole lines of a CHW plane or contiguous elements of an HWC source, and stores 4 B per lane - contiguous along the row (a texture's
+// place in the texel buffer is 4-B aligned and no more, and x0 is arbitrary).  Format, channels and mode are uniform per workgroup.
+// (16-B stores of four texels per lane, with single-texel heads and tails per row, were built and measured equal within the noise at
+// 1024^2 and 4096^2: profiles/texture_store16_ab.json, profiles/texture_store16_experiment.patch.  The simpler form stayed.)
+__global__ __launch_bounds__(256) void k_update_textures(uint32_t* __restrict__ tex_data, const TextureItem* __restrict__ items, const SegmentBlock* __restrict__ blocks,
+                                                         const float* __restrict__ thresholds, uint4* info0, uint4* info1) {
+  __shared__ float mid[256];
+  const SegmentBlock bl = blocks[blockIdx.x];
+  const TextureItem& it = items[bl.segment];  // (uniform: read field by field, nothing of it lives in private memory)
+  const bool encode = (it.mode & HK_TEXTURE_ITEM_ENCODE) != 0u, packed = (it.mode & HK_TEXTURE_ITEM_PACKED) != 0u;
+  if (encode) {
+    mid[threadIdx.x] = thresholds[threadIdx.x];
+    __syncthreads();
+  }
+  if (bl.first == 0u && threadIdx.x == 0u) {  // the item's first workgroup: the descriptor, as k_update_texture writes it
+    if (info0) info0[it.index] = it.info;
+    if (info1) info1[it.index] = it.info;
+  }
+  const uint32_t rows = min(it.rows, it.height - bl.first);
+  const bool half = it.format == HK_TEXELS_F16;
+  const uint32_t count = rows * it.width;
+  for (uint32_t t = threadIdx.x; t < count; t += 256u) {
+    const uint32_t ry = t / it.width, x = t - ry * it.width, y = bl.first + ry;
+    tex_data[(size_t)it.dst + (size_t)y * it.pitch + x] = texel_word(it, encode, packed, half, mid, x, y);
+  }
+}
+
 }  // namespace hkd
 
 namespace hk {
@@ -498,6 +577,13 @@ void launch_material_update(hipStream_t st, const RefitScene& s, float4* materia
 void launch_texture_update(hipStream_t st, uint32_t* dst, const uint32_t* src, size_t n, uint4* info0, uint4* info1, uint4 info) {
   const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 4096));
   hipLaunchKernelGGL(k_update_texture, dim3(blocks), dim3(256), 0, st, dst, src, n, info0, info1, info);
+}
+uint32_t launch_textures_update(hipStream_t st, uint32_t* tex_data, const TextureItem* items, const SegmentBlock* blocks, uint32_t n_blocks, const float* thresholds,
+                                uint4* info0, uint4* info1, hipEvent_t sources_read) {
+  if (!n_blocks) return 0u;
+  hipLaunchKernelGGL(k_update_textures, dim3(n_blocks), dim3(256), 0, st, tex_data, items, blocks, thresholds, info0, info1);
+  if (sources_read) (void)hipEventRecord(sources_read, st);
+  return 1u;
 }
 
 void launch_copy_region(hipStream_t st, void* dst, const void* src, size_t bytes) {

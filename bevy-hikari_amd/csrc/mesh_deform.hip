@@ -229,12 +229,9 @@ int hk::stage(hk_ctx* c, size_t bytes, uint8_t** out, int* k_out) {
   return HK_OK;
 }
 
-namespace {
-inline uint32_t stride_of(uint32_t bytes) { return bytes ? bytes : 12u; }
-
-// a source of hk_deform_meshes_device: aligned, memory the context's device can read - its own, or host memory mapped for it - and
-// `extent` bytes from `p` on inside the allocation, so that no launch can fault on what a caller named by mistake
-int check_source(hk_ctx* c, uint32_t item, const char* what, const void* p, size_t align, size_t extent) {
+// a source of hk_deform_meshes_device / hk_update_textures_device: aligned, memory the context's device can read - its own, or host memory
+// mapped for it - and `extent` bytes from `p` on inside the allocation, so that no launch can fault on what a caller named by mistake
+int hk::check_source(hk_ctx* c, uint32_t item, const char* what, const void* p, size_t align, size_t extent) {
   HK_REQUIRE(((uintptr_t)p & (align - 1)) == 0, HK_E_INVALID, "item %u: the %s at %p are not aligned to %zu bytes", item, what, p, align);
   hipPointerAttribute_t a{};
   const hipError_t e = hipPointerGetAttributes(&a, p);
@@ -251,6 +248,9 @@ int check_source(hk_ctx* c, uint32_t item, const char* what, const void* p, size
              (size_t)(((const uint8_t*)p + extent) - ((const uint8_t*)base + size)));
   return HK_OK;
 }
+
+namespace {
+inline uint32_t stride_of(uint32_t bytes) { return bytes ? bytes : 12u; }
 
 // the corner list and the face plane of a mesh's recomputed normals, from the primitive mirror (indices never change): per vertex the
 // triangles that name it, ascending, one entry per corner - the order k_deform_normals sums in

@@ -414,10 +414,7 @@ int build_dynamic_region(hk_ctx* c, Blob& blob, DynOffsets& o, size_t static_byt
     texel_offset += t.texels.size();
   }
   std::vector<float> srgb_lut(256);
-  for (int i = 0; i < 256; ++i) {  // sRGB EOTF in double, rounded once
-    double v = i / 255.0;
-    srgb_lut[i] = (float)(v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4));
-  }
+  srgb_decode_table(srgb_lut.data());  // (host_logic.cpp: the table hk_encode_texels inverts)
   o.tex_info = blob.add(tex_info);
   o.srgb_lut = blob.add(srgb_lut);
   blob.bytes.resize((blob.bytes.size() + 31) & ~(size_t)31, 0);
@@ -778,6 +775,7 @@ int hk_upload_textures(hk_ctx* c, const HkImageDesc* images, uint32_t n) {
     memcpy(tex[i].texels.data(), d.rgba8, tex[i].texels.size() * 4);
   }
   c->textures.swap(tex);
+  c->tx_host_stale.clear();   // (every host copy is the scene again: hk_update_textures_device)
   c->textures_dirty = true;
   c->dynamic_dirty = true;
   return HK_OK;
@@ -824,6 +822,141 @@ int hk_update_texture(hk_ctx* c, uint32_t index, const HkImageDesc* image) {
   }
   memcpy(t.texels.data(), image->rgba8, n * 4);
   t.flags = flags;
+  if (index < c->tx_host_stale.size()) c->tx_host_stale[index] = 0;  // (the copy holds what the device does again)
+  return HK_OK;
+}
+// Rectangles of many textures from the caller's DEVICE memory, converted in one launch (hikari_hip.h; kernels_scene.hip
+// k_update_textures).  Ordered as hk_update_texture orders its write; only the item table and the workgroup table are staged.
+int hk_update_textures_device(hk_ctx* c, const HkTextureSource* items, uint32_t n, void* producer_stream) {
+  HK_REQUIRE(c && (items || !n), HK_E_INVALID, "NULL argument");
+  HK_REQUIRE(!c->textures.empty(), HK_E_NOT_READY, "hk_upload_textures must come first");
+  if (!n) return HK_OK;
+  HK_HIP(hipSetDevice(c->device));
+  int rc;
+  // ---- the whole batch is validated before anything is enqueued or written
+  const uint32_t n_tex = (uint32_t)c->textures.size();
+  std::vector<uint32_t> new_flags(n_tex);
+  for (uint32_t i = 0; i < n_tex; ++i) new_flags[i] = c->textures[i].flags;
+  size_t n_blocks = 0;
+  uint64_t texels = 0;
+  bool any_encode = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    const HkTextureSource& it = items[i];
+    if ((rc = check_texture_source(it, i))) return rc;
+    HK_REQUIRE(it.index < n_tex, HK_E_INVALID, "item %u: texture %u of %u", i, it.index, n_tex);
+    const hk_ctx::HostTexture& t = c->textures[it.index];
+    HK_REQUIRE((uint64_t)it.x0 + it.width <= t.w && (uint64_t)it.y0 + it.height <= t.h, HK_E_INVALID,
+               "item %u: the rectangle (%u, %u) + %u x %u leaves texture %u of %u x %u", i, it.x0, it.y0, it.width, it.height, it.index, t.w, t.h);
+    if (it.flags & HK_TEXTURE_SET_SAMPLER) {
+      HK_REQUIRE(it.address_u <= HK_ADDRESS_MIRROR_REPEAT && it.address_v <= HK_ADDRESS_MIRROR_REPEAT, HK_E_INVALID, "item %u: bad address mode", i);
+      new_flags[it.index] = (it.is_srgb ? 1u : 0u) | (it.filter_linear ? 2u : 0u) | (it.address_u << 4) | (it.address_v << 6);  // (of several items of a texture the last one)
+    }
+    for (uint32_t k = 0; k < i; ++k)
+      HK_REQUIRE(!texture_rectangles_overlap(items[k], it), HK_E_INVALID, "items %u and %u overlap in texture %u: one launch cannot order them", k, i, it.index);
+    if ((rc = check_source(c, i, "texels", it.data, texel_element_bytes(it.format), texture_source_extent(it)))) return rc;
+    const uint32_t rows = std::max(1u, 2048u / it.width);
+    n_blocks += (it.height + rows - 1u) / rows;
+    texels += (uint64_t)it.width * it.height;
+    any_encode = any_encode || (it.flags & HK_TEXTURE_LINEAR_SOURCE);
+  }
+  // ---- a pending hk_upload_textures is laid out first, as the next frame would; then the texel buffer is the device's
+  if (c->textures_dirty && (rc = finalize_scene(c))) return rc;
+  std::vector<size_t> offset(n_tex + 1, 0);
+  for (uint32_t i = 0; i < n_tex; ++i) offset[i + 1] = offset[i] + c->textures[i].texels.size();
+  HK_REQUIRE(c->d_tex_data.p && c->d_tex_data.n >= offset[n_tex], HK_E_NOT_READY, "the texel buffer is not on the device");
+  const bool info_live = !c->dynamic_dirty && !c->mesh_dirty && c->scene_mem;  // (else the pending relayout writes the descriptors from the flags below)
+  if (any_encode && !c->tx_thresholds) {  // once per context
+    float mid[256];
+    srgb_encode_thresholds(mid);
+    HK_HIP(hipMalloc((void**)&c->tx_thresholds, sizeof(mid)));
+    if (hipMemcpy(c->tx_thresholds, mid, sizeof(mid), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(c->tx_thresholds);
+      c->tx_thresholds = nullptr;
+      HK_REQUIRE(false, HK_E_HIP, "copying the sRGB thresholds failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+  }
+  hipStream_t producer = (hipStream_t)producer_stream;
+  if (producer)
+    for (hipEvent_t* e : {&c->tx_src_ready, &c->tx_src_read})
+      if (!*e) HK_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  // ---- the staging block: item table | workgroup table
+  const size_t table_bytes = (n * sizeof(TextureItem) + 255) & ~(size_t)255;
+  uint8_t* st = nullptr;
+  int k = 0;
+  if ((rc = stage(c, table_bytes + n_blocks * sizeof(SegmentBlock), &st, &k))) return rc;
+  TextureItem* table = (TextureItem*)st;
+  SegmentBlock* blocks = (SegmentBlock*)(st + table_bytes);
+  size_t at = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const HkTextureSource& it = items[i];
+    const hk_ctx::HostTexture& t = c->textures[it.index];
+    const uint32_t elem = texel_element_bytes(it.format);
+    TextureItem d{};
+    d.src = (const uint8_t*)it.data;
+    d.stride_x = it.stride_x; d.stride_y = it.stride_y; d.stride_c = it.stride_c;
+    d.dst = (uint32_t)(offset[it.index] + (size_t)it.y0 * t.w + it.x0);
+    d.pitch = t.w;
+    d.width = it.width; d.height = it.height;
+    d.format = it.format; d.channels = it.channels;
+    const size_t vec = 4u * elem;
+    if ((it.flags & HK_TEXTURE_LINEAR_SOURCE) && (new_flags[it.index] & 1u)) d.mode |= HK_TEXTURE_ITEM_ENCODE;
+    if (it.channels == 4u && it.stride_c == elem && (uintptr_t)it.data % vec == 0 && it.stride_x % vec == 0 && it.stride_y % vec == 0) d.mode |= HK_TEXTURE_ITEM_PACKED;
+    d.rows = std::max(1u, 2048u / it.width);
+    d.index = it.index;
+    d.info = make_uint4((uint32_t)offset[it.index], t.w, t.h, new_flags[it.index]);
+    table[i] = d;
+    for (uint32_t first = 0; first < it.height; first += d.rows) blocks[at++] = SegmentBlock{i, first};
+  }
+  // ---- enqueue: behind every frame enqueued so far on every stream that reads texels (stream waits, no host wait)
+  if ((rc = join_all(c))) return rc;
+  if (producer) {  // what the producer has enqueued on the sources so far comes first; it may write them again once the launch has read them
+    HK_HIP(hipEventRecord(c->tx_src_ready, producer));
+    HK_HIP(hipStreamWaitEvent(c->stream, c->tx_src_ready, 0));
+  }
+  c->scene_epoch += 1;   // (scene memory is written from here on: hk_context.hpp, primary-ray pipelining - a refusal above leaves it alone)
+  uint4 *info0 = nullptr, *info1 = nullptr;
+  if (info_live) {
+    info0 = (uint4*)(c->scene_mem + c->dyn_off.tex_info);
+    if (c->two_slots) info1 = (uint4*)(c->scene_mem + c->dyn_capacity + c->dyn_off.tex_info);
+  }
+  const uint32_t launches = launch_textures_update(c->stream, c->d_tex_data.p, table, blocks, (uint32_t)n_blocks, c->tx_thresholds, info0, info1,
+                                                   producer ? c->tx_src_read : nullptr);
+  HK_HIP(hipGetLastError());
+  if (producer) HK_HIP(hipStreamWaitEvent(producer, c->tx_src_read, 0));
+  hk_ctx::DeformStage& stg = c->df_stage[(size_t)k];
+  HK_HIP(hipEventRecord(stg.done, c->stream));
+  stg.pending = true;
+  c->tx_host_stale.resize(n_tex, 0);
+  for (uint32_t i = 0; i < n; ++i) c->tx_host_stale[items[i].index] = 1;
+  for (uint32_t i = 0; i < n_tex; ++i) c->textures[i].flags = new_flags[i];
+  c->last_texture_update[0] = n;
+  c->last_texture_update[1] = launches;
+  c->last_texture_update[2] = (uint32_t)std::min<uint64_t>(texels, 0xFFFFFFFFull);
+  return HK_OK;
+}
+// ... and the way back: the device's texels of one texture, behind a wait for the context's streams; the host copy follows
+int hk_read_texture(hk_ctx* c, uint32_t index, uint8_t* rgba8, size_t bytes) {
+  HK_REQUIRE(c && rgba8, HK_E_INVALID, "NULL argument");
+  HK_REQUIRE(!c->textures.empty(), HK_E_NOT_READY, "hk_upload_textures must come first");
+  HK_REQUIRE(index < c->textures.size(), HK_E_INVALID, "texture %u of %zu", index, c->textures.size());
+  hk_ctx::HostTexture& t = c->textures[index];
+  HK_REQUIRE(bytes == t.texels.size() * 4, HK_E_INVALID, "texture %u holds %zu bytes (%u x %u x 4), not %zu", index, t.texels.size() * 4, t.w, t.h, bytes);
+  if (!c->textures_dirty) {  // (a pending hk_upload_textures: the copy IS what the device is about to hold)
+    size_t texel_offset = 0;
+    for (uint32_t i = 0; i < index; ++i) texel_offset += c->textures[i].texels.size();
+    HK_REQUIRE(c->d_tex_data.p && c->d_tex_data.n >= texel_offset + t.texels.size(), HK_E_NOT_READY, "the texel buffer is not on the device");
+    HK_HIP(hipSetDevice(c->device));
+    int rc;
+    if ((rc = sync_all(c))) return rc;
+    HK_HIP(hipMemcpy(t.texels.data(), c->d_tex_data.p + texel_offset, bytes, hipMemcpyDeviceToHost));
+    if (index < c->tx_host_stale.size()) c->tx_host_stale[index] = 0;
+  }
+  memcpy(rgba8, t.texels.data(), bytes);
+  return HK_OK;
+}
+int hk_debug_last_texture_update(hk_ctx* c, uint32_t out[3]) {
+  HK_REQUIRE(c && out, HK_E_INVALID, "NULL argument");
+  for (int k = 0; k < 3; ++k) out[k] = c->last_texture_update[k];
   return HK_OK;
 }
 int hk_upload_noise(hk_ctx* c, const uint8_t* rgba, size_t bytes) {

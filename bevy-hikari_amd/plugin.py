@@ -536,6 +536,57 @@ def image_desc(im):
     return d
 
 
+def _texture_record(desc):
+    """What Engine keeps of an uploaded texture: its size (read_texture) and its sampler (update_textures fills in what an item leaves out)."""
+    return dict(width=desc.width, height=desc.height, srgb=bool(desc.is_srgb), address_u=desc.address_u, address_v=desc.address_v, filter=bool(desc.filter_linear))
+
+
+_TEXEL_FORMATS = {"uint8": F.TEXELS_U8, "float16": F.TEXELS_F16, "float32": F.TEXELS_F32}
+
+
+def texture_source(index, array, layout="hwc", origin=(0, 0), linear=False, sampler=None):
+    """One HkTextureSource over `array` - a torch tensor or a numpy array of uint8 / float16 / float32, [h][w][c] (layout "hwc"),
+    [c][h][w] ("chw") or [h][w] (grey), c = 1, 3 or 4 - read where it lies: pointer, strides and channel count come from the array, so a
+    slice or an expanded (stride 0) array costs no copy.  sampler: None (the descriptor stays) or dict(srgb, address_u, address_v,
+    filter), all four given."""
+    is_torch = type(array).__module__.partition(".")[0] == "torch"
+    fmt = _TEXEL_FORMATS.get(str(array.dtype).replace("torch.", ""))
+    if fmt is None:
+        raise TypeError(f"texels of dtype {array.dtype}: uint8, float16 or float32")
+    elem = array.element_size() if is_torch else array.itemsize
+    shape = tuple(array.shape)
+    strides = tuple(s * elem for s in array.stride()) if is_torch else tuple(array.strides)
+    if any(s < 0 for s in strides):
+        raise ValueError("negative strides (a flipped array) are not supported: flip a copy")
+    if len(shape) == 2:
+        (h, w), (sy, sx), c, sc = shape, strides, 1, 0
+    elif len(shape) == 3 and layout == "hwc":
+        (h, w, c), (sy, sx, sc) = shape, strides
+    elif len(shape) == 3 and layout == "chw":
+        (c, h, w), (sc, sy, sx) = shape, strides
+    else:
+        raise ValueError(f"texels of shape {shape} in layout {layout!r}: [h][w][c] (\"hwc\"), [c][h][w] (\"chw\") or [h][w]")
+    s = F.HkTextureSource()
+    s.index, s.format, s.channels = index, fmt, c
+    s.data = array.data_ptr() if is_torch else array.ctypes.data
+    s.stride_x, s.stride_y, s.stride_c = sx, sy, sc
+    (s.x0, s.y0), s.width, s.height = origin, w, h
+    s.flags = (F.TEXTURE_LINEAR_SOURCE if linear else 0) | (F.TEXTURE_SET_SAMPLER if sampler is not None else 0)
+    if sampler is not None:
+        s.is_srgb, s.filter_linear = int(bool(sampler["srgb"])), int(bool(sampler["filter"]))
+        s.address_u, s.address_v = sampler["address_u"], sampler["address_v"]
+    return s
+
+
+def encode_texels(array, layout="hwc", linear=False, texture_srgb=True):
+    """hk_encode_texels: the bytes Engine.update_textures leaves for the same values, uint8[h][w][4] - `array` is a numpy array as in
+    texture_source; texture_srgb is the texture's sRGB bit after the call.  Needs no GPU."""
+    src = texture_source(0, array, layout, linear=linear)
+    out = np.zeros((src.height, src.width, 4), np.uint8)
+    F.api().call("encode_texels", C.byref(src), int(bool(texture_srgb)), out.ctypes.data)
+    return out
+
+
 def deform_items(items):
     """The HkMeshDeform table of Engine.deform_meshes' `items`, and the arrays it points into (to be kept alive over the call)."""
     table, keep = (F.HkMeshDeform * max(len(items), 1))(), []
@@ -619,6 +670,7 @@ class Engine:
     """One context of the C ABI (`hk_ctx`).  `api` defaults to the product library."""
     _producer = None  # deform_meshes: a torch stream standing in for torch's legacy default stream (made at the first such call)
     _n_instances = None  # instances of the scene last uploaded / of the builder last given to set_instance_transforms (read_instance_transforms)
+    _textures = None     # per uploaded texture its size and sampler (_texture_record): read_texture, update_textures
 
     def __init__(self, api=None, device=0, flags=0):
         self.api = api or F.api()
@@ -894,11 +946,62 @@ class Engine:
         one = [image_desc(im) for im in images]   # (each keeps its pixel array alive until the call has copied it)
         descs = (F.HkImageDesc * max(len(images), 1))(*one)
         self.api.call("upload_textures", self.ctx, descs, len(images))
+        self._textures = [_texture_record(d) for d in one]
 
     def update_texture(self, index, image):
         """New texels and sampler of ONE uploaded texture of the same size (hk_update_texture), in place and without a host wait; `image`
         as in upload_textures."""
-        self.api.call("update_texture", self.ctx, index, C.byref(image_desc(image)))
+        desc = image_desc(image)
+        self.api.call("update_texture", self.ctx, index, C.byref(desc))
+        if self._textures is not None and index < len(self._textures):
+            self._textures[index] = _texture_record(desc)
+
+    def update_textures(self, items, producer_stream=None):
+        """Texture edits from device memory, many per call (hk_update_textures_device): one kernel launch however many items there are,
+        nothing is copied to the host and there is no host wait.  Each item is a dict: `index` (an uploaded texture); `tensor`, a torch
+        uint8 / float16 / float32 tensor on the context's device, [h][w][c] with layout="hwc" (the default), [c][h][w] with "chw" or
+        [h][w] (grey), c = 1, 3 or 4, read where it lies (a slice or an expanded tensor costs no copy); optional origin=(x0, y0) of the
+        rectangle it fills (default: the corner; the tensor's size is the rectangle's); optional linear=True: a float tensor holds LINEAR
+        light and the rgb of an sRGB texture are encoded (HK_TEXTURE_LINEAR_SOURCE); optional srgb, address_u, address_v, filter: a new
+        sampler - those not given stay what the texture has.  uint8 is taken as it is, floats are the encoded value in [0, 1].
+        The context is ordered behind `producer_stream` (a torch stream; default: torch's current stream) and that stream behind the
+        context's read of the tensors, by events: they may be overwritten right after the call.  encode_texels is the host's twin."""
+        if self._textures is None:
+            raise ValueError("the engine has not uploaded textures (upload_textures)")
+        table, keep = (F.HkTextureSource * max(len(items), 1))(), []
+        samplers = [dict(t) for t in self._textures]
+        for k, item in enumerate(items):
+            tensor, index = item["tensor"], int(item["index"])
+            if not _is_device_tensor(tensor):
+                raise TypeError("tensor must be a torch tensor on the context's device (host texels go through update_texture)")
+            if tensor.device.index != self.device:
+                raise ValueError(f"the tensor lies on {tensor.device}, the context on cuda:{self.device}")
+            if not 0 <= index < len(samplers):
+                raise ValueError(f"texture {index} of {len(samplers)}")
+            sampler = None
+            if any(key in item for key in ("srgb", "address_u", "address_v", "filter")):
+                sampler = samplers[index]
+                sampler.update({key: item[key] for key in ("srgb", "address_u", "address_v", "filter") if key in item})
+            table[k] = texture_source(index, tensor, item.get("layout", "hwc"), item.get("origin", (0, 0)), bool(item.get("linear", False)), sampler)
+            keep.append(tensor)   # (alive until the call has returned: the producer stream is ordered behind the read by then)
+        self._producer_call(producer_stream, lambda handle: self.api.call("update_textures_device", self.ctx, table, len(items), handle))
+        for record, new in zip(self._textures, samplers):
+            record.update(new)
+
+    def read_texture(self, index):
+        """The texels the device holds of one texture, uint8[h][w][4] (hk_read_texture; waits for the context's streams): the way back
+        after update_textures."""
+        if self._textures is None or not 0 <= index < len(self._textures):
+            raise ValueError(f"texture {index}: the engine has uploaded {0 if self._textures is None else len(self._textures)}")
+        out = np.zeros((self._textures[index]["height"], self._textures[index]["width"], 4), np.uint8)
+        self.api.call("read_texture", self.ctx, index, out.ctypes.data, out.size)
+        return out
+
+    def last_texture_update(self):
+        """(items, kernel launches, texels written) of the last update_textures - hk_debug_last_texture_update (test hook)."""
+        out = (F.u32 * 3)()
+        self.api.call("debug_last_texture_update", self.ctx, out)
+        return tuple(int(v) for v in out)
 
     def upload_noise(self, noise=None):
         noise = load_noise() if noise is None else np.ascontiguousarray(noise, dtype=np.uint8)
@@ -1403,6 +1506,14 @@ class HikariPlugin:
     def read_instance_transforms(self):
         """The poses the device holds (Engine.read_instance_transforms)."""
         return self.engine.read_instance_transforms()
+
+    def update_textures(self, items, producer_stream=None):
+        """Per frame, textures whose texels live in device memory, many per call: Engine.update_textures."""
+        self.engine.update_textures(items, producer_stream)
+
+    def read_texture(self, index):
+        """The texels the device holds of one texture (Engine.read_texture)."""
+        return self.engine.read_texture(index)
 
     def update_instances(self, scene: SceneData):
         """Instances moved (prepare_instances, instance.rs:352-437): rewrite the instance-level buffers only."""

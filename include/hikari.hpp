@@ -425,6 +425,17 @@ class HikariPlugin {
   }
   // new texels and sampler of one uploaded texture of the same size, in place
   void update_texture(uint32_t index, const HkImageDesc& image) { check(hk_update_texture(ctx_.get(), index, &image), "hk_update_texture"); }
+  // rectangles of many textures from DEVICE memory (strided, 8-bit or float), converted in one launch; `producer_stream` (a hipStream_t, or
+  // nullptr: the caller has ordered itself) is ordered against the context by events.  hk_encode_texels is the conversion's host twin
+  void update_textures_device(const std::vector<HkTextureSource>& items, void* producer_stream = nullptr) {
+    check(hk_update_textures_device(ctx_.get(), items.data(), (uint32_t)items.size(), producer_stream), "hk_update_textures_device");
+  }
+  // ... and the way back: the texels the device holds of one texture of width x height (waits for the context's streams), rgba8
+  std::vector<uint8_t> read_texture(uint32_t index, uint32_t width, uint32_t height) {
+    std::vector<uint8_t> rgba((size_t)width * height * 4);
+    check(hk_read_texture(ctx_.get(), index, rgba.data(), rgba.size()), "hk_read_texture");
+    return rgba;
+  }
   // a new tree over the current triangles of one deformed mesh, built on the device in place (later deformations refit the new shape)
   // per frame: every deforming mesh in one call (vertex updates and skinned meshes alike), at a launch count that does not depend on how many
   void deform_meshes(const std::vector<HkMeshDeform>& items) { check(hk_deform_meshes(ctx_.get(), items.data(), (uint32_t)items.size()), "hk_deform_meshes"); }

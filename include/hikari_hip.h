@@ -822,6 +822,67 @@ int hk_upload_textures(hk_ctx* ctx, const HkImageDesc* images, uint32_t n_images
  * was changed on the device before (refits, tree rebuilds, deformations).  HK_E_INVALID with nothing written for NULL, index >= the
  * uploaded count, a size that differs or an address mode out of range; HK_E_NOT_READY when no textures have been uploaded. */
 int hk_update_texture(hk_ctx* ctx, uint32_t index, const HkImageDesc* image);
+/* Texture edits whose SOURCES LIE IN DEVICE MEMORY (a video frame decoded on the GPU, a procedural or learned texture in a tensor, a
+ * lightmap a kernel wrote), MANY per call: whole textures or sub-rectangles, 8-bit or floating point, strided.  After the call the
+ * texel buffer and the texture descriptors - in both slots of a two-slot scene - hold, byte for byte, what hk_update_texture would have
+ * left, given per texture the current texels with the rectangles replaced by hk_encode_texels of the same values.  One kernel launch
+ * whatever n is; only the item table travels through the pinned staging pool, the sources are read where they lie.
+ *   Sources.  Element (x, y, ch) of an item lies at data + y * stride_y + x * stride_x + ch * stride_c (bytes; multiples of the element
+ * size; 0 = a broadcast): a torch tensor in HWC or CHW order, a slice of one or an expanded one, without a copy.  channels 1 = grey
+ * (rgb take the value, alpha 255), 3 = rgb (alpha 255), 4 = rgba.  Row 0 is v = 0, as in HkImageDesc.
+ *   Conversion, per element, in f32, without contraction.
+ *     HK_TEXELS_U8   the byte is taken as it is (it is already in the texture's encoding).
+ *     HK_TEXELS_F16  the half is widened exactly to f32, then as F32.
+ *     HK_TEXELS_F32  without HK_TEXTURE_LINEAR_SOURCE the float IS the encoded value: NaN -> 0, v = min(max(x, 0), 1),
+ *                    byte = (uint32_t)(v * 255.0f + 0.5f), the product and the sum two separately rounded f32 operations.
+ *     HK_TEXTURE_LINEAR_SOURCE (float sources only; on a U8 item HK_E_INVALID): the rgb channels of a texture whose sRGB bit is set
+ *                    after this call are LINEAR light and are encoded: v clamped as above, byte = the number of k in 1 .. 255 with
+ *                    v > mid[k], mid[k] = (float)(((double)lut[k - 1] + (double)lut[k]) / 2), lut the 256-entry sRGB decode table the
+ *                    samplers read (the sRGB EOTF in double, rounded once).  Comparisons only: encode(lut[b]) == b for every b.  Alpha,
+ *                    and every channel of a texture that is not sRGB, take the plain rule.
+ *   Sampler.  With HK_TEXTURE_SET_SAMPLER the item's is_srgb / address_u / address_v / filter_linear replace the texture's; otherwise the
+ * descriptor stays as it is and those fields are not read.
+ *   Ordering.  The rule of hk_update_texture and hk_deform_meshes_device: the texel buffer has one copy, so the write goes behind every
+ * frame enqueued on every stream that reads texels - no host wait.  With producer_stream (a hipStream_t) != NULL the context's stream
+ * first waits for an event recorded there at the call, and the producer then waits for an event recorded behind the kernel that reads
+ * the sources: the caller may overwrite them in stream order right after the call.  NULL: the caller has ordered itself.  If an
+ * hk_upload_textures is still pending, the call lays the scene out first, as the next frame would (HK_E_NOT_READY without a complete
+ * scene).
+ *   Validation.  The whole batch before anything is enqueued; a refused call writes nothing.  HK_E_INVALID for: NULL ctx, or NULL items
+ * with n > 0; an index >= the uploaded count; an unknown format, flag bit or channel count; a rectangle that is empty or leaves the
+ * texture; a stride that is no multiple of the element size; an address mode out of range under HK_TEXTURE_SET_SAMPLER; two items of one
+ * call whose rectangles in the same texture overlap (one launch cannot order them); a source that is misaligned for its element size,
+ * neither memory of the context's device nor host memory mapped for it (pageable memory is refused: a mistaken pointer cannot fault the
+ * device), or whose extent - computed from the strides - leaves its allocation.  HK_E_NOT_READY when no textures have been uploaded.
+ * n == 0: HK_OK, nothing enqueued.
+ *   State.  Afterwards the context's host copy of the touched textures is stale (a mark per texture).  Nothing reads that copy until
+ * hk_upload_textures replaces all of it, and an hk_update_texture of a texture refreshes its copy: NO CALL IS NEWLY REFUSED after this one.
+ * There is no hk_multi_ form, as hk_deform_meshes_device and hk_set_instance_transforms_device have none: a device pointer lives on one device. */
+#define HK_TEXELS_U8  0u   /* unsigned bytes, already in the texture's encoding */
+#define HK_TEXELS_F16 1u   /* IEEE half, widened exactly to f32, then as F32 */
+#define HK_TEXELS_F32 2u
+#define HK_TEXTURE_SET_SAMPLER   1u  /* take is_srgb / address_u / address_v / filter_linear from the item; otherwise the descriptor stays */
+#define HK_TEXTURE_LINEAR_SOURCE 2u  /* float sources only: rgb of an sRGB texture is LINEAR light and is encoded (rule above) */
+typedef struct HkTextureSource {
+  uint32_t    index;           /* an uploaded texture */
+  uint32_t    format;          /* HK_TEXELS_* */
+  const void* data;            /* DEVICE memory (or host memory mapped for the device); hk_encode_texels: HOST memory */
+  uint64_t    stride_x, stride_y, stride_c;  /* bytes; multiples of the element size; 0 allowed (a broadcast) */
+  uint32_t    channels;        /* 1 (grey -> rgb, alpha 255), 3 (alpha 255) or 4 */
+  uint32_t    x0, y0, width, height;  /* the rectangle of the texture that is written; inside the texture, width, height >= 1 */
+  uint32_t    flags;           /* HK_TEXTURE_SET_SAMPLER | HK_TEXTURE_LINEAR_SOURCE */
+  uint32_t    is_srgb, address_u, address_v, filter_linear;  /* read with HK_TEXTURE_SET_SAMPLER */
+} HkTextureSource;             /* 80 bytes, no implicit padding: 8-byte members at 8, 16, 24, 32, then ten 4-byte members */
+int hk_update_textures_device(hk_ctx* ctx, const HkTextureSource* items, uint32_t n, void* producer_stream);
+/* ... and the way back: waits for the context's streams, then copies the texels the device holds of texture `index` to `rgba8` (bytes
+ * must be width * height * 4, else HK_E_INVALID; HK_E_NOT_READY when no textures have been uploaded).  Refreshes the context's host copy
+ * of the texture and clears its mark. */
+int hk_read_texture(hk_ctx* ctx, uint32_t index, uint8_t* rgba8, size_t bytes);
+/* The host twin of the kernel's conversion, no GPU needed: one item's rectangle, read from HOST memory laid out the same way, to
+ * width * height * 4 bytes (row-major, rgba).  texture_is_srgb: the texture's sRGB bit AFTER the call the item would be part of.  index,
+ * x0, y0 and the sampler fields are not read.  HK_E_INVALID for NULL, an unknown format, flag bit or channel count, an empty
+ * rectangle, a stride that is no multiple of the element size, a misaligned pointer, HK_TEXTURE_LINEAR_SOURCE on a U8 item. */
+int hk_encode_texels(const HkTextureSource* item, uint32_t texture_is_srgb, uint8_t* rgba8_out);
 /* InstanceRenderAssets::set + write_buffer, instance.rs:82-108 */
 int hk_upload_instances(hk_ctx* ctx, const HkInstance* instances, uint32_t n_instances, const HkNode* instance_nodes,
                         uint32_t n_instance_nodes, const HkEmissive* emissives, uint32_t n_emissives,

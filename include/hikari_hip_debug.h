@@ -53,6 +53,10 @@ int hk_debug_last_deform(hk_ctx* ctx, uint32_t out[6]);
  * instances, of the named emitters, of the two trees; the slot copy of a two-slot scene and event records not counted), out[1] 1 if it
  * copied the builder's mesh boxes to the device (the first call for an instance list), else 0.  A refused call leaves them as they were. */
 int hk_debug_last_pose(hk_ctx* ctx, uint32_t out[2]);
+/* What the last accepted hk_update_textures_device did: out[0] its items, out[1] its kernel launches (event records not counted; a scene
+ * laid out first because an hk_upload_textures was pending is not part of it), out[2] the texels it wrote, saturated at 2^32 - 1.  A
+ * refused call, or one with n == 0, leaves them as they were. */
+int hk_debug_last_texture_update(hk_ctx* ctx, uint32_t out[3]);
 
 /* Measurement hook ("measure the empirical HBM ceiling with a device copy/triad kernel in the same run"): streams
  * three private arrays of `bytes_per_array` bytes (use >= 1 GiB: the 256 MB Infinity Cache must not hold them) `reps` times
