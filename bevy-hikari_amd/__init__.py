@@ -32,6 +32,7 @@ from .plugin import (  # noqa: F401
     load_noise,
     look_at_transform,
     make_rays,
+    morph_vertices,
     standard_material,
 )
 

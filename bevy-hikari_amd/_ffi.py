@@ -63,7 +63,8 @@ FORMAT_RGBA16F, FORMAT_RGBA32F, FORMAT_RGBA8_UNORM_SRGB, FORMAT_BGRA8_UNORM_SRGB
 PRESENT_HDR, PRESENT_CLEAR = 1, 2
 RAYS_CLOSEST, RAYS_ANY, RAYS_ATTRIBUTES, RAYS_STACKLESS = 0, 1, 2, 4  # hk_cast_rays flags
 RAY_MISS, RAY_HIT, RAY_INVALID = 0, 1, 2                              # HkRayHit.status
-DEFORM_VERTICES, DEFORM_SKIN = 0, 1                                   # HkMeshDeform.kind
+DEFORM_VERTICES, DEFORM_SKIN, DEFORM_MORPH, DEFORM_MORPH_SKIN = 0, 1, 2, 3   # HkMeshDeform.kind
+MORPH_MAX_TARGETS = 4096                                              # hk_set_mesh_morph_targets
 DEFORM_RECOMPUTE_NORMALS = 1                                          # HkMeshDeformDevice.flags
 TEXELS_U8, TEXELS_F16, TEXELS_F32 = 0, 1, 2                           # HkTextureSource.format
 TEXTURE_SET_SAMPLER, TEXTURE_LINEAR_SOURCE = 1, 2                     # HkTextureSource.flags
@@ -316,6 +317,8 @@ _PRODUCT_ONLY = {
     "update_mesh_vertices": [_vp, P(HkMeshIndex), u32, P(f32), P(f32)],
     "set_mesh_skin": [_vp, P(HkMeshIndex), u32, P(f32), P(f32), P(C.c_uint16), P(f32)],
     "skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],
+    "set_mesh_morph_targets": [_vp, P(HkMeshIndex), u32, u32, P(f32), P(f32), P(f32), P(f32)],
+    "morph_vertices": [u32, u32, P(f32), P(f32), P(f32), P(f32), P(f32), P(f32), P(f32)],
     "deform_meshes": [_vp, P(HkMeshDeform), u32],
     "deform_meshes_device": [_vp, P(HkMeshDeformDevice), u32, _vp],
     "set_instance_transforms_device": [_vp, _vp, P(u32), u32, _vp, u32, _vp, _vp],
@@ -368,6 +371,7 @@ _PRODUCT_ONLY = {
     "multi_update_mesh_vertices": [_vp, P(HkMeshIndex), u32, P(f32), P(f32)],
     "multi_set_mesh_skin": [_vp, P(HkMeshIndex), u32, P(f32), P(f32), P(C.c_uint16), P(f32)],
     "multi_skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],
+    "multi_set_mesh_morph_targets": [_vp, P(HkMeshIndex), u32, u32, P(f32), P(f32), P(f32), P(f32)],
     "multi_deform_meshes": [_vp, P(HkMeshDeform), u32],
     "multi_rebuild_mesh_tree": [_vp, P(HkMeshIndex), u32],
     "multi_set_band_bounds": [_vp, P(u32), u32],

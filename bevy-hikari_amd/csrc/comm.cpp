@@ -836,6 +836,10 @@ int hk_multi_set_mesh_skin(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vert
   HK_EACH(hk_set_mesh_skin(c, mesh, n_vertices, bind_positions, bind_normals, joint_indices, joint_weights));
 }
 int hk_multi_skin_mesh(hk_multi* m, const HkMeshIndex* mesh, const float* joint_matrices, uint32_t n_joints) { HK_EACH(hk_skin_mesh(c, mesh, joint_matrices, n_joints)); }
+int hk_multi_set_mesh_morph_targets(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vertices, uint32_t n_targets, const float* base_positions, const float* base_normals,
+                                    const float* position_deltas, const float* normal_deltas) {
+  HK_EACH(hk_set_mesh_morph_targets(c, mesh, n_vertices, n_targets, base_positions, base_normals, position_deltas, normal_deltas));
+}
 int hk_multi_deform_meshes(hk_multi* m, const HkMeshDeform* items, uint32_t n) { HK_EACH(hk_deform_meshes(c, items, n)); }
 int hk_multi_rebuild_mesh_tree(hk_multi* m, const HkMeshIndex* mesh, uint32_t mode) { HK_EACH(hk_rebuild_mesh_tree(c, mesh, mode)); }
 // the same explicit split on every band's context (all of them must agree: the schedules are derived per context)

@@ -156,10 +156,10 @@ struct MeshTree {
 // everything the kernels need of the item's mesh.  The table lies in the pinned staging block of the call, with the host data of the
 // items behind it, and is read from there (as RefitUpdate records are).
 struct DeformItem {
-  uint32_t kind;                     // HK_DEFORM_VERTICES / HK_DEFORM_SKIN
+  uint32_t kind;                     // HK_DEFORM_VERTICES / HK_DEFORM_SKIN / HK_DEFORM_MORPH / HK_DEFORM_MORPH_SKIN
   uint32_t n_vertices, n_tris, n_joints;
   const float *positions, *normals;  // VERTICES: staged, 3 floats per vertex (normals: or NULL = keep)
-  const float4* palette;             // SKIN: the staged joint matrices, copied to joint_mats by k_deform_begin
+  const float4* palette;             // SKIN, MORPH_SKIN: the staged joint matrices, copied to joint_mats by k_deform_begin
   float4* joint_mats;
   const float4 *bind_pos, *bind_nrm, *weights;
   const uint2* joints;
@@ -173,6 +173,15 @@ struct DeformItem {
   // list - corner_tri[corner_off[v] .. corner_off[v + 1]) are the triangles that name vertex v, ascending, one entry per naming corner
   float4* face;
   const uint32_t *corner_off, *corner_tri;
+  // HK_DEFORM_MORPH / HK_DEFORM_MORPH_SKIN (hikari_hip.h hk_set_mesh_morph_targets): the mesh's morph set - packed planes of 3 floats per
+  // vertex, the deltas target-major (delta k of vertex v at [(k * n_vertices + v) * 3]; morph_dn NULL: the normals do not morph) - the
+  // item's weights as given (staged, or the caller's device memory), and what k_deform_begin makes of them in the mesh's own memory: a
+  // copy of the n_targets weights and the ascending list of the active targets, its length in morph_active[n_targets]
+  const float *morph_base_p, *morph_base_n, *morph_dp, *morph_dn;
+  const float* morph_src;
+  float* morph_w;
+  uint32_t* morph_active;
+  uint32_t n_targets, pad_;
 };
 // A workgroup of a segmented launch: 256 consecutive elements of ONE segment (item, tree), from `first` on.  The host writes one entry
 // per workgroup, so no workgroup - and no wave - spans two segments, whatever their sizes and however many there are.

@@ -324,6 +324,27 @@ int hk_encode_texels(const HkTextureSource* item, uint32_t texture_is_srgb, uint
   return HK_OK;
 }
 
+// the host twin of the morph branch of k_deform_vertices (kernels_deform.hip morph_vertex): base, then one active target after the
+// other in ascending index - per component the same products and sums in the same order (this file is built with -ffp-contract=off)
+int hk_morph_vertices(uint32_t n_vertices, uint32_t n_targets, const float* base_positions, const float* base_normals, const float* position_deltas,
+                      const float* normal_deltas, const float* weights, float* positions_out, float* normals_out) {
+  HK_REQUIRE(base_positions && base_normals && position_deltas && weights && positions_out && normals_out && n_vertices, HK_E_INVALID, "NULL argument or no vertices");
+  HK_REQUIRE(n_targets >= 1 && n_targets <= HK_MORPH_MAX_TARGETS, HK_E_INVALID, "a morph set has between 1 and %u targets, not %u", HK_MORPH_MAX_TARGETS, n_targets);
+  const size_t plane = 3 * (size_t)n_vertices;
+  memmove(positions_out, base_positions, plane * 4);
+  memmove(normals_out, base_normals, plane * 4);
+  for (uint32_t k = 0; k < n_targets; ++k) {
+    const float w = weights[k];
+    if (w == 0.0f) continue;  // (+0 and -0: skipped, nothing added; a NaN weight is active)
+    const float* dp = position_deltas + plane * k;
+    for (size_t i = 0; i < plane; ++i) positions_out[i] = positions_out[i] + w * dp[i];
+    if (!normal_deltas) continue;
+    const float* dn = normal_deltas + plane * k;
+    for (size_t i = 0; i < plane; ++i) normals_out[i] = normals_out[i] + w * dn[i];
+  }
+  return HK_OK;
+}
+
 int hk_settings_default(HkSettings* s) {  // lib.rs:435-455
   HK_REQUIRE(s, HK_E_INVALID, "settings is NULL");
   memset(s, 0, sizeof(*s));

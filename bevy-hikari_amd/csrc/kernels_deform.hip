@@ -25,10 +25,13 @@ __device__ __forceinline__ void reduce_box(uint32_t* box, bool valid, float x, f
       mn[k] = min(mn[k], (uint32_t)__shfl_xor((int)mn[k], off));
       mx[k] = max(mx[k], (uint32_t)__shfl_xor((int)mx[k], off));
     }
+  // (an atomic that would change nothing is not issued: the six words only ever shrink / grow during a launch, so whatever value of
+  // this launch the load sees, a wave that does not beat it cannot beat the current one.  Without the test every wave of a large mesh
+  // queues on the same six addresses, and the launch takes the time of those atomics, not of its memory traffic.)
   if ((threadIdx.x & 63u) == 0u && mx[0] != 0u)
     for (int k = 0; k < 3; ++k) {
-      atomicMin(&box[k], mn[k]);
-      atomicMax(&box[3 + k], mx[k]);
+      if (mn[k] < __hip_atomic_load(&box[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&box[k], mn[k]);
+      if (mx[k] > __hip_atomic_load(&box[3 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&box[3 + k], mx[k]);
     }
 }
 
@@ -52,9 +55,10 @@ __device__ __forceinline__ void stage_vertex(const float* __restrict__ positions
 //   p' = ((M0 x + M1 y) + M2 z) + M3                                           (M0..M3: columns)
 //   n' = ((c0 n.x + c1 n.y) + c2 n.z),  (c0, c1, c2) = (M1 x M2, M2 x M0, M0 x M1) / dot(M2, M0 x M1)   (inverse_transpose_3x3)
 // n' is stored as it comes out (hit_info normalises, as for any uploaded normal).
-__device__ __forceinline__ void skin_vertex(const float4* __restrict__ bind_pos, const float4* __restrict__ bind_nrm, const uint2* __restrict__ joints,
-                                            const float4* __restrict__ weights, const float4* __restrict__ joint_mats, uint32_t v, float4* __restrict__ pos,
-                                            float4* __restrict__ vn, float& px, float& py, float& pz) {
+// `p` / `q`: the vertex's bind position and normal (HK_DEFORM_SKIN: of the skin's bind planes; HK_DEFORM_MORPH_SKIN: morphed, in registers)
+__device__ __forceinline__ void skin_vertex(const float4 p, const float4 q, const uint2* __restrict__ joints, const float4* __restrict__ weights,
+                                            const float4* __restrict__ joint_mats, uint32_t v, float4* __restrict__ pos, float4* __restrict__ vn, float& px,
+                                            float& py, float& pz) {
   const uint2 jw = joints[v];
   const uint32_t j[4] = {jw.x & 0xFFFFu, jw.x >> 16, jw.y & 0xFFFFu, jw.y >> 16};
   const float4 w4 = weights[v];
@@ -75,7 +79,6 @@ __device__ __forceinline__ void skin_vertex(const float4* __restrict__ bind_pos,
       m[c][2] = m[c][2] + w[t] * a.z;
       m[c][3] = m[c][3] + w[t] * a.w;
     }
-  const float4 p = bind_pos[v];
   px = ((m[0][0] * p.x + m[1][0] * p.y) + m[2][0] * p.z) + m[3][0];
   py = ((m[0][1] * p.x + m[1][1] * p.y) + m[2][1] * p.z) + m[3][1];
   pz = ((m[0][2] * p.x + m[1][2] * p.y) + m[2][2] * p.z) + m[3][2];
@@ -98,8 +101,64 @@ __device__ __forceinline__ void skin_vertex(const float4* __restrict__ bind_pos,
     y[k] = y[k] / det;
     z[k] = z[k] / det;
   }
-  const float4 q = bind_nrm[v];
   vn[v] = make_float4((x[0] * q.x + y[0] * q.y) + z[0] * q.z, (x[1] * q.x + y[1] * q.y) + z[1] * q.z, (x[2] * q.x + y[2] * q.y) + z[2] * q.z, 0.0f);
+}
+
+// Morph targets of one vertex (hikari_hip.h hk_set_mesh_morph_targets; DESIGN "Mesh deformation"): fixed order, no contraction.
+//   p = ((base + w[a1] dp[a1]) + w[a2] dp[a2]) + ...   per component over the ACTIVE targets a1 < a2 < ... (k_deform_begin's list),
+// normals alike with dn (NORMALS) or the base normals as they are.  The list, its length and the weights are the same for every vertex
+// of the item: scalar loads.  The deltas are packed planes of 3 floats per vertex, one per target: the 64 vertices of a wave read 768
+// consecutive bytes of a plane.  Four targets' loads are issued before the first is used; the additions stay in list order.
+// (The pointers of an item come out of the staged table, so the compiler knows nothing of where they point: the casts below tell it
+// that the list and the weights are constant memory - written by the launch before - and the planes global memory, which makes the
+// former scalar loads and the latter global loads.)
+template <typename T>
+using uniform_ptr = const T __attribute__((address_space(4)))*;
+template <typename T>
+using global_ptr = const T __attribute__((address_space(1)))*;
+template <bool NORMALS>
+__device__ __forceinline__ void morph_vertex(const DeformItem* __restrict__ it, uint32_t v, float p[3], float q[3]) {
+  const auto bp = (global_ptr<float>)(uintptr_t)(it->morph_base_p + 3 * (size_t)v);
+  const auto bn = (global_ptr<float>)(uintptr_t)(it->morph_base_n + 3 * (size_t)v);
+  for (int c = 0; c < 3; ++c) {
+    p[c] = bp[c];
+    q[c] = bn[c];
+  }
+  const auto active = (uniform_ptr<uint32_t>)(uintptr_t)it->morph_active;
+  const auto w = (uniform_ptr<float>)(uintptr_t)it->morph_w;
+  const size_t plane = 3 * (size_t)it->n_vertices;
+  const auto dp = (global_ptr<float>)(uintptr_t)it->morph_dp + 3 * (size_t)v;
+  const auto dn = (global_ptr<float>)(uintptr_t)it->morph_dn + (NORMALS ? 3 * (size_t)v : 0);
+  const uint32_t n = active[it->n_targets];
+  uint32_t i = 0;
+  for (; i + 4u <= n; i += 4u) {
+    float wk[4], d[4][3], e[4][3];
+    for (int t = 0; t < 4; ++t) {
+      const uint32_t k = active[i + t];
+      wk[t] = w[k];
+      const auto a = dp + plane * k;
+      for (int c = 0; c < 3; ++c) d[t][c] = a[c];
+      if (NORMALS) {
+        const auto b = dn + plane * k;
+        for (int c = 0; c < 3; ++c) e[t][c] = b[c];
+      }
+    }
+    for (int t = 0; t < 4; ++t)
+      for (int c = 0; c < 3; ++c) {
+        p[c] = p[c] + wk[t] * d[t][c];
+        if (NORMALS) q[c] = q[c] + wk[t] * e[t][c];
+      }
+  }
+  for (; i < n; ++i) {
+    const uint32_t k = active[i];
+    const float wk = w[k];
+    const auto a = dp + plane * k;
+    for (int c = 0; c < 3; ++c) p[c] = p[c] + wk * a[c];
+    if (NORMALS) {
+      const auto b = dn + plane * k;
+      for (int c = 0; c < 3; ++c) q[c] = q[c] + wk * b[c];
+    }
+  }
 }
 
 // triangle t of the mesh: its three positions (the w words - vertex indices - stay) and its box (light.wgsl:408-412, the leaf box)
@@ -138,7 +197,7 @@ __global__ __launch_bounds__(256) void k_mesh_skin(const float4* __restrict__ bi
   const uint32_t v = blockIdx.x * 256u + threadIdx.x;
   const bool valid = v < n;
   float px = 0.0f, py = 0.0f, pz = 0.0f;
-  if (valid) skin_vertex(bind_pos, bind_nrm, joints, weights, joint_mats, v, pos, vn, px, py, pz);
+  if (valid) skin_vertex(bind_pos[v], bind_nrm[v], joints, weights, joint_mats, v, pos, vn, px, py, pz);
   reduce_box(box, valid, px, py, pz);
 }
 
@@ -154,19 +213,53 @@ __global__ __launch_bounds__(256) void k_mesh_triangles(const float4* __restrict
 // consecutive vertices / triangles of ONE item (hk_kernels.hpp SegmentBlock, a table the host writes), so the wave-wide box reduction
 // never mixes two meshes and an item may have any size.  The item records and the tables are read from the call's pinned staging block.
 // One workgroup per item: its box words back to the empty box (min words all ones, max words zero), and - a skin item - its joint
-// matrices into device memory, where the vertex kernel reads each of them once per vertex.
+// matrices into device memory, where the vertex kernel reads each of them once per vertex; a morph item's weights likewise, with the
+// list of the active targets the vertex kernel loops over.
 __global__ __launch_bounds__(256) void k_deform_begin(const DeformItem* __restrict__ items, uint32_t n_items) {
   if (blockIdx.x >= n_items) return;
   const DeformItem* it = items + blockIdx.x;
   uint32_t* box = it->box;
   if (threadIdx.x < 6u) box[threadIdx.x] = threadIdx.x < 3u ? 0xFFFFFFFFu : 0u;
-  if (it->kind != HK_DEFORM_SKIN) return;
-  const float4* __restrict__ src = it->palette;
-  float4* __restrict__ dst = it->joint_mats;
-  const uint32_t n = 4u * it->n_joints;
-  for (uint32_t i = threadIdx.x; i < n; i += 256u) dst[i] = src[i];
+  const uint32_t kind = it->kind;
+  if (kind == HK_DEFORM_SKIN || kind == HK_DEFORM_MORPH_SKIN) {
+    const float4* __restrict__ src = it->palette;
+    float4* __restrict__ dst = it->joint_mats;
+    const uint32_t n = 4u * it->n_joints;
+    for (uint32_t i = threadIdx.x; i < n; i += 256u) dst[i] = src[i];
+  }
+  if (kind != HK_DEFORM_MORPH && kind != HK_DEFORM_MORPH_SKIN) return;
+  // a morph item: its weights into the mesh's own copy, and the ascending list of the targets whose weight does not compare equal to
+  // zero (NaN: active).  256 targets per round: a ballot per wave, the lanes below in the ballot, the waves below through LDS - the
+  // place of a target in the list depends on the weights alone.
+  __shared__ uint32_t wave_count[4];
+  const float* __restrict__ src = it->morph_src;
+  float* __restrict__ dst = it->morph_w;
+  uint32_t* __restrict__ active = it->morph_active;
+  const uint32_t n = it->n_targets, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t total = 0;
+  for (uint32_t first = 0; first < n; first += 256u) {
+    const uint32_t k = first + threadIdx.x;
+    bool on = false;
+    if (k < n) {
+      const float w = src[k];
+      dst[k] = w;
+      on = w != 0.0f;
+    }
+    const unsigned long long mask = __ballot(on);
+    if (lane == 0u) wave_count[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    uint32_t at = total + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+    for (uint32_t q = 0; q < 4u; ++q) {
+      if (q < wave) at += wave_count[q];
+      total += wave_count[q];
+    }
+    if (on) active[at] = k;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0u) active[n] = total;
 }
-__global__ __launch_bounds__(256) void k_deform_vertices(const DeformItem* __restrict__ items, const SegmentBlock* __restrict__ blocks) {
+// (five workgroups per CU, as before the morph branch: without the bound the skin's matrix loads are hoisted over the morph loop and cost a wave)
+__global__ __launch_bounds__(256, 5) void k_deform_vertices(const DeformItem* __restrict__ items, const SegmentBlock* __restrict__ blocks) {
   const SegmentBlock bl = blocks[blockIdx.x];
   const DeformItem* it = items + bl.segment;
   const uint32_t v = bl.first + threadIdx.x;
@@ -174,10 +267,31 @@ __global__ __launch_bounds__(256) void k_deform_vertices(const DeformItem* __res
   float4* pos = it->pos;
   float4* vn = it->vn;
   float x = 0.0f, y = 0.0f, z = 0.0f;
-  if (it->kind == HK_DEFORM_SKIN) {
-    if (valid) skin_vertex(it->bind_pos, it->bind_nrm, it->joints, it->weights, it->joint_mats, v, pos, vn, x, y, z);
-  } else {
+  const uint32_t kind = it->kind;
+  if (kind == HK_DEFORM_VERTICES) {
     if (valid) stage_vertex(it->positions, it->normals, v, pos, vn, x, y, z, it->pos_stride, it->nrm_stride);
+  } else if (valid) {
+    // the bind pose of the skin, or the morphed vertex: stored as it is (MORPH) or skinned in its place (MORPH_SKIN)
+    float4 p, q;
+    if (kind == HK_DEFORM_SKIN) {
+      p = it->bind_pos[v];
+      q = it->bind_nrm[v];
+    } else {
+      float a[3], b[3];
+      if (it->morph_dn) morph_vertex<true>(it, v, a, b);
+      else morph_vertex<false>(it, v, a, b);
+      p = make_float4(a[0], a[1], a[2], 0.0f);
+      q = make_float4(b[0], b[1], b[2], 0.0f);
+    }
+    if (kind == HK_DEFORM_MORPH) {
+      x = p.x;
+      y = p.y;
+      z = p.z;
+      pos[v] = p;
+      vn[v] = q;
+    } else {
+      skin_vertex(p, q, it->joints, it->weights, it->joint_mats, v, pos, vn, x, y, z);
+    }
   }
   reduce_box(it->box, valid, x, y, z);
 }

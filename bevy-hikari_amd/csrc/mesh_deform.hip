@@ -1,4 +1,4 @@
-// mesh_deform.hip - mesh deformation on the device (hikari_hip.h hk_update_mesh_vertices / hk_set_mesh_skin / hk_skin_mesh / hk_deform_meshes / hk_deform_meshes_device; kernels in
+// mesh_deform.hip - mesh deformation on the device (hikari_hip.h hk_update_mesh_vertices / hk_set_mesh_skin / hk_skin_mesh / hk_set_mesh_morph_targets / hk_deform_meshes / hk_deform_meshes_device; kernels in
 // kernels_deform.hip, kernels_tree.hip and kernels_scene.hip; DESIGN "Mesh deformation").  The reference re-prepares a changed mesh on the CPU
 // (mesh.rs:76-166: a BVH build and a re-layout of the whole mesh level); here the new vertices are written into the mesh-level region,
 // the mesh tree is REFIT in every ordering that holds it (same links, every box the union of the triangle boxes below it), and the
@@ -35,12 +35,19 @@ struct DeformMesh {
   void* nrm_mem = nullptr;
   float4* face = nullptr;
   uint32_t *corner_off = nullptr, *corner_tri = nullptr;
+  // morph targets (hk_set_mesh_morph_targets), one allocation: base planes and delta planes (3 floats per vertex, the deltas target-major
+  // as the caller gave them; morph_dn NULL: none), the weights of the last morph item and the list of its active targets with the
+  // list's length behind it (kernels_deform.hip k_deform_begin writes both)
+  void* morph_mem = nullptr;
+  float *morph_base_p = nullptr, *morph_base_n = nullptr, *morph_dp = nullptr, *morph_dn = nullptr, *morph_w = nullptr;
+  uint32_t* morph_active = nullptr;
+  uint32_t morph_vertices = 0, morph_targets = 0;
 };
 
 namespace hk {
 void free_deform(hk_ctx* c) {
   for (DeformMesh* d : c->deform) {
-    for (void* q : {d->mem, d->skin_mem, (void*)d->joint_mats, d->nrm_mem})
+    for (void* q : {d->mem, d->skin_mem, (void*)d->joint_mats, d->nrm_mem, d->morph_mem})
       if (q) (void)hipFree(q);
     delete d;
   }
@@ -467,6 +474,44 @@ int hk_set_mesh_skin(hk_ctx* c, const HkMeshIndex* mesh, uint32_t n_vertices, co
   return HK_OK;
 }
 
+int hk_set_mesh_morph_targets(hk_ctx* c, const HkMeshIndex* mesh, uint32_t n_vertices, uint32_t n_targets, const float* base_positions, const float* base_normals,
+                              const float* position_deltas, const float* normal_deltas) {
+  HK_REQUIRE(c && mesh && base_positions && base_normals && position_deltas && n_vertices, HK_E_INVALID, "NULL argument or no vertices");
+  HK_REQUIRE(n_targets >= 1 && n_targets <= HK_MORPH_MAX_TARGETS, HK_E_INVALID, "a morph set has between 1 and %u targets, not %u", HK_MORPH_MAX_TARGETS, n_targets);
+  DeformMesh* d = nullptr;
+  int rc;
+  if ((rc = begin(c, mesh, &d))) return rc;
+  HK_REQUIRE(n_vertices >= d->min_vertices && n_vertices <= d->max_vertices, HK_E_INVALID, "the mesh has between %u and %u vertices, not %u", d->min_vertices,
+             d->max_vertices, n_vertices);
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t plane = (size_t)n_vertices * 12, deltas = plane * n_targets;
+  const size_t bytes = 2 * al(plane) + (normal_deltas ? 2 : 1) * al(deltas) + al((size_t)n_targets * 4) + al(((size_t)n_targets + 1) * 4);
+  if ((rc = sync_all(c))) return rc;  // (a set given again: the kernels enqueued so far may still read the old one)
+  if (d->morph_mem) (void)hipFree(d->morph_mem);
+  d->morph_mem = nullptr;
+  d->morph_vertices = d->morph_targets = 0;
+  if (hipMalloc(&d->morph_mem, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    d->morph_mem = nullptr;
+    HK_REQUIRE(false, HK_E_NOMEM, "device allocation of %zu bytes failed", bytes);
+  }
+  uint8_t* p = (uint8_t*)d->morph_mem;
+  auto take = [&](size_t b) { uint8_t* q = p; p += al(b); return q; };
+  d->morph_base_p = (float*)take(plane);
+  d->morph_base_n = (float*)take(plane);
+  d->morph_dp = (float*)take(deltas);
+  d->morph_dn = normal_deltas ? (float*)take(deltas) : nullptr;
+  d->morph_w = (float*)take((size_t)n_targets * 4);
+  d->morph_active = (uint32_t*)take(((size_t)n_targets + 1) * 4);
+  HK_HIP(hipMemcpy(d->morph_base_p, base_positions, plane, hipMemcpyHostToDevice));
+  HK_HIP(hipMemcpy(d->morph_base_n, base_normals, plane, hipMemcpyHostToDevice));
+  HK_HIP(hipMemcpy(d->morph_dp, position_deltas, deltas, hipMemcpyHostToDevice));
+  if (normal_deltas) HK_HIP(hipMemcpy(d->morph_dn, normal_deltas, deltas, hipMemcpyHostToDevice));
+  d->morph_vertices = n_vertices;
+  d->morph_targets = n_targets;
+  return HK_OK;
+}
+
 int hk_skin_mesh(hk_ctx* c, const HkMeshIndex* mesh, const float* joint_matrices, uint32_t n_joints) {
   if (c) c->scene_epoch += 1;   // (scene memory is written: hk_context.hpp, primary-ray pipelining)
   HK_REQUIRE(c && mesh && joint_matrices && n_joints, HK_E_INVALID, "NULL argument or no joints");
@@ -498,7 +543,7 @@ int hk_skin_mesh(hk_ctx* c, const HkMeshIndex* mesh, const float* joint_matrices
 
 // Many meshes in one call (hikari_hip.h): what the single calls above do for each item, as five launches over all of them
 // (kernels_deform.hip launch_deform_batch).  Everything the device reads of the call - the item table, the workgroup tables of the
-// three launch shapes, every item's positions / normals / joint matrices - travels in ONE pinned staging block.
+// three launch shapes, every item's positions / normals / joint matrices / morph weights - travels in ONE pinned staging block.
 // hk_deform_meshes_device is the same batch with `device` set: the items' data stays where the caller has it (validated first: memory the
 // device can read, aligned, strided), only the tables are staged, `producer` (or NULL) is ordered against the context's stream by two
 // events, and flagged items recompute their normals in a sixth launch.
@@ -519,27 +564,40 @@ int deform_batch(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, bool de
   bool grow = false;
   for (uint32_t i = 0; i < n; ++i) {
     const HkMeshDeformDevice& it = items[i];
-    HK_REQUIRE(it.kind == HK_DEFORM_VERTICES || it.kind == HK_DEFORM_SKIN, HK_E_INVALID, "item %u: unknown kind %u", i, it.kind);
+    HK_REQUIRE(it.kind <= HK_DEFORM_MORPH_SKIN, HK_E_INVALID, "item %u: unknown kind %u", i, it.kind);
+    const bool skins = it.kind == HK_DEFORM_SKIN || it.kind == HK_DEFORM_MORPH_SKIN, morphs = it.kind == HK_DEFORM_MORPH || it.kind == HK_DEFORM_MORPH_SKIN;
     HK_REQUIRE(it.data && it.count, HK_E_INVALID, "item %u: NULL data or a count of zero", i);
     HK_REQUIRE(it.kind != HK_DEFORM_SKIN || !it.normals, HK_E_INVALID, "item %u: a skin item takes no normals", i);
+    HK_REQUIRE(it.kind != HK_DEFORM_MORPH || !it.normals, HK_E_INVALID, "item %u: a morph item takes no normals (its data are the weights)", i);
+    HK_REQUIRE(it.kind != HK_DEFORM_MORPH_SKIN || it.normals, HK_E_INVALID, "item %u: a morph + skin item names its weights in `normals`: NULL", i);
     const bool recompute = (it.flags & HK_DEFORM_RECOMPUTE_NORMALS) != 0;
     if (device) {
       HK_REQUIRE(!(it.flags & ~HK_DEFORM_RECOMPUTE_NORMALS), HK_E_INVALID, "item %u: unknown flag bits 0x%x", i, it.flags & ~HK_DEFORM_RECOMPUTE_NORMALS);
+      HK_REQUIRE(!recompute || !morphs, HK_E_INVALID, "item %u: a morph item cannot recompute its normals (HK_DEFORM_RECOMPUTE_NORMALS is for vertex items)", i);
       HK_REQUIRE(!recompute || it.kind == HK_DEFORM_VERTICES, HK_E_INVALID, "item %u: a skin item cannot recompute its normals (the skin transforms them)", i);
       HK_REQUIRE(!recompute || !it.normals, HK_E_INVALID, "item %u: normals given together with HK_DEFORM_RECOMPUTE_NORMALS", i);
-      if (it.kind == HK_DEFORM_SKIN) {
+      if (skins) {
         HK_REQUIRE(it.data_stride == 0 || it.data_stride == 64, HK_E_INVALID, "item %u: joint matrices are contiguous (a stride of 0 or 64 bytes, not %u)", i, it.data_stride);
+        HK_REQUIRE(!morphs || it.normals_stride == 0 || it.normals_stride == 4, HK_E_INVALID, "item %u: morph weights are contiguous (a stride of 0 or 4 bytes, not %u)", i,
+                   it.normals_stride);
+      } else if (morphs) {
+        HK_REQUIRE(it.data_stride == 0 || it.data_stride == 4, HK_E_INVALID, "item %u: morph weights are contiguous (a stride of 0 or 4 bytes, not %u)", i, it.data_stride);
       } else {
         for (const uint32_t stride : {it.data_stride, it.normals ? it.normals_stride : 0u})
           HK_REQUIRE(stride == 0 || (stride >= 12 && stride % 4 == 0), HK_E_INVALID, "item %u: a stride of %u bytes (0, or a multiple of 4 from 12 on)", i, stride);
       }
     }
     DeformMesh* d = nullptr;
-    if (it.kind == HK_DEFORM_SKIN) {
+    if (skins || morphs) {
       for (DeformMesh* q : c->deform)
         if (memcmp(&q->mesh, &it.mesh, sizeof(HkMeshIndex)) == 0) d = q;
-      HK_REQUIRE(d && d->skin_vertices, HK_E_INVALID, "item %u: no skin set for this mesh (hk_set_mesh_skin)", i);
-      HK_REQUIRE(d->max_joint < it.count, HK_E_INVALID, "item %u: the skin names joint %u but only %u joint matrices were given", i, d->max_joint, it.count);
+      HK_REQUIRE(!morphs || (d && d->morph_vertices), HK_E_INVALID, "item %u: no morph set for this mesh (hk_set_mesh_morph_targets)", i);
+      HK_REQUIRE(it.kind != HK_DEFORM_MORPH || it.count == d->morph_targets, HK_E_INVALID, "item %u: the morph set has %u targets but %u weights were given", i,
+                 d->morph_targets, it.count);
+      HK_REQUIRE(!skins || (d && d->skin_vertices), HK_E_INVALID, "item %u: no skin set for this mesh (hk_set_mesh_skin)", i);
+      HK_REQUIRE(!(skins && morphs) || d->skin_vertices == d->morph_vertices, HK_E_INVALID, "item %u: the skin has %u vertices, the morph set %u", i, d->skin_vertices,
+                 d->morph_vertices);
+      HK_REQUIRE(!skins || d->max_joint < it.count, HK_E_INVALID, "item %u: the skin names joint %u but only %u joint matrices were given", i, d->max_joint, it.count);
     }
     if ((rc = find_mesh(c, &it.mesh, &d)) || (rc = mesh_instances(c, d))) {
       const std::string why = hk_last_error();
@@ -552,10 +610,13 @@ int deform_batch(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, bool de
                it.mesh.node_offset, it.mesh.node_count);
     d->batch = c->df_batch;
     meshes[i] = d;
-    const uint32_t nv = it.kind == HK_DEFORM_SKIN ? d->skin_vertices : it.count;
+    const uint32_t nv = morphs ? d->morph_vertices : skins ? d->skin_vertices : it.count;
     if (device) {  // (the counts are known to be the mesh's: the extents below are what the kernels will read)
-      if (it.kind == HK_DEFORM_SKIN) {
+      if (skins) {
         if ((rc = check_source(c, i, "joint matrices", it.data, 16, (size_t)it.count * 64))) return rc;
+        if (morphs && (rc = check_source(c, i, "morph weights", it.normals, 4, (size_t)d->morph_targets * 4))) return rc;
+      } else if (morphs) {
+        if ((rc = check_source(c, i, "morph weights", it.data, 4, (size_t)d->morph_targets * 4))) return rc;
       } else {
         if ((rc = check_source(c, i, "positions", it.data, 4, (size_t)(nv - 1) * stride_of(it.data_stride) + 12))) return rc;
         if (it.normals && (rc = check_source(c, i, "normals", it.normals, 4, (size_t)(nv - 1) * stride_of(it.normals_stride) + 12))) return rc;
@@ -570,9 +631,11 @@ int deform_batch(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, bool de
     blocks[0] += (nv + 255u) / 256u;
     blocks[1] += (d->n_tris + 255u) / 256u;
     blocks[2] += ((size_t)(2u * d->n_tris - 1u) * orderings + 255u) / 256u;
-    if (it.kind == HK_DEFORM_SKIN) {
+    if (morphs && !device) data_bytes += al16((size_t)d->morph_targets * 4);
+    if (skins) {
       if (!device) data_bytes += (size_t)it.count * 64;
       grow = grow || it.count > d->joint_cap;
+    } else if (morphs) {
     } else if (!device) {
       data_bytes += al16((size_t)it.count * 12) * (it.normals ? 2 : 1);
     }
@@ -583,7 +646,7 @@ int deform_batch(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, bool de
     for (uint32_t i = 0; i < n; ++i) {
       DeformMesh* d = meshes[i];
       if (device && (items[i].flags & HK_DEFORM_RECOMPUTE_NORMALS) && !d->nrm_mem && (rc = corner_list(c, d))) return rc;
-      if (items[i].kind != HK_DEFORM_SKIN || items[i].count <= d->joint_cap) continue;
+      if ((items[i].kind != HK_DEFORM_SKIN && items[i].kind != HK_DEFORM_MORPH_SKIN) || items[i].count <= d->joint_cap) continue;
       if (d->joint_mats) (void)hipFree(d->joint_mats);
       d->joint_mats = nullptr;
       d->joint_cap = 0;
@@ -615,7 +678,22 @@ int deform_batch(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, bool de
     t.pos_stride = t.nrm_stride = 3u;
     t.kind = it.kind;
     t.n_tris = d->n_tris;
-    if (it.kind == HK_DEFORM_SKIN) {
+    const bool skins = it.kind == HK_DEFORM_SKIN || it.kind == HK_DEFORM_MORPH_SKIN, morphs = it.kind == HK_DEFORM_MORPH || it.kind == HK_DEFORM_MORPH_SKIN;
+    if (morphs) {  // (the weights: `data` of a morph item, `normals` of a morph + skin item)
+      const void* weights = skins ? it.normals : it.data;
+      t.n_vertices = d->morph_vertices;
+      t.n_targets = d->morph_targets;
+      if (device) {
+        t.morph_src = (const float*)weights;
+      } else {
+        memcpy(data, weights, (size_t)d->morph_targets * 4);
+        t.morph_src = (const float*)data;
+        data += al16((size_t)d->morph_targets * 4);
+      }
+      t.morph_base_p = d->morph_base_p; t.morph_base_n = d->morph_base_n; t.morph_dp = d->morph_dp; t.morph_dn = d->morph_dn;
+      t.morph_w = d->morph_w; t.morph_active = d->morph_active;
+    }
+    if (skins) {
       t.n_vertices = d->skin_vertices;
       t.n_joints = it.count;
       if (device) {
@@ -627,6 +705,7 @@ int deform_batch(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, bool de
       }
       t.joint_mats = d->joint_mats;
       t.bind_pos = d->bind_pos; t.bind_nrm = d->bind_nrm; t.weights = d->weights; t.joints = d->joints;
+    } else if (morphs) {
     } else if (device) {
       t.n_vertices = it.count;
       t.positions = (const float*)it.data;

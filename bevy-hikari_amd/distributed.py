@@ -524,6 +524,13 @@ class MultiEngine:
         fp = lambda a: a.ctypes.data_as(C.POINTER(F.f32))
         self.api.call("multi_set_mesh_skin", self.h, C.byref(mesh), len(pos), fp(pos), fp(nrm), idx.ctypes.data_as(C.POINTER(C.c_uint16)), fp(w))
 
+    def set_mesh_morph_targets(self, mesh, base_positions, base_normals, position_deltas, normal_deltas=None):
+        """hk_multi_set_mesh_morph_targets: Engine.set_mesh_morph_targets on every band's copy of the scene."""
+        from .plugin import _fp, _morph_arrays
+
+        arrays = _morph_arrays(base_positions, base_normals, position_deltas, normal_deltas)
+        self.api.call("multi_set_mesh_morph_targets", self.h, C.byref(mesh), *arrays[0], *[_fp(a) for a in arrays[1:]])
+
     def skin_mesh(self, mesh, joint_matrices):
         j = np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1, 16)
         self.api.call("multi_skin_mesh", self.h, C.byref(mesh), j.ctypes.data_as(C.POINTER(F.f32)), len(j))

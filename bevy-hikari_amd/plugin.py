@@ -587,6 +587,34 @@ def encode_texels(array, layout="hwc", linear=False, texture_srgb=True):
     return out
 
 
+def _fp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(F.f32))
+
+
+def _morph_arrays(base_positions, base_normals, position_deltas, normal_deltas):
+    """((n_vertices, n_targets), base positions, base normals, position deltas, normal deltas or None) of a morph set as contiguous float32"""
+    bp = np.ascontiguousarray(base_positions, dtype=np.float32).reshape(-1, 3)
+    bn = np.ascontiguousarray(base_normals, dtype=np.float32).reshape(-1, 3)
+    dp = np.ascontiguousarray(position_deltas, dtype=np.float32)
+    dp = dp.reshape(-1, len(bp), 3) if len(bp) else dp.reshape(0, 0, 3)
+    dn = None if normal_deltas is None else np.ascontiguousarray(normal_deltas, dtype=np.float32).reshape(-1, len(bp), 3)
+    if bn.shape != bp.shape or (dn is not None and dn.shape != dp.shape):
+        raise ValueError("base normals must match base positions, normal deltas the position deltas")
+    return (len(bp), len(dp)), bp, bn, dp, dn
+
+
+def morph_vertices(base_positions, base_normals, position_deltas, normal_deltas, weights):
+    """hk_morph_vertices: (positions, normals) a ("morph", index, weights) item leaves on the device for a set of these arrays
+    (Engine.set_mesh_morph_targets) - base plus the targets whose weight is not zero, in ascending index.  Needs no GPU."""
+    (nv, nt), bp, bn, dp, dn = _morph_arrays(base_positions, base_normals, position_deltas, normal_deltas)
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    if len(w) != nt:
+        raise ValueError(f"{nt} targets but {len(w)} weights")
+    pos, nrm = np.empty_like(bp), np.empty_like(bn)
+    F.api().call("morph_vertices", nv, nt, _fp(bp), _fp(bn), _fp(dp), _fp(dn), _fp(w), _fp(pos), _fp(nrm))
+    return pos, nrm
+
+
 def deform_items(items):
     """The HkMeshDeform table of Engine.deform_meshes' `items`, and the arrays it points into (to be kept alive over the call)."""
     table, keep = (F.HkMeshDeform * max(len(items), 1))(), []
@@ -599,6 +627,19 @@ def deform_items(items):
             j = np.ascontiguousarray(item[2], dtype=np.float32).reshape(-1, 16)
             keep.append(j)
             table[k] = F.HkMeshDeform(mesh, F.DEFORM_SKIN, len(j), fp(j), None)
+        elif kind == "morph":
+            if len(item) != 3:
+                raise ValueError('a morph item is ("morph", index, weights)')
+            w = np.ascontiguousarray(item[2], dtype=np.float32).reshape(-1)
+            keep.append(w)
+            table[k] = F.HkMeshDeform(mesh, F.DEFORM_MORPH, len(w), fp(w), None)
+        elif kind == "morph_skin":
+            if len(item) != 4:
+                raise ValueError('a morph + skin item is ("morph_skin", index, joints, weights)')
+            j = np.ascontiguousarray(item[2], dtype=np.float32).reshape(-1, 16)
+            w = np.ascontiguousarray(item[3], dtype=np.float32).reshape(-1)
+            keep += [j, w]
+            table[k] = F.HkMeshDeform(mesh, F.DEFORM_MORPH_SKIN, len(j), fp(j), fp(w))
         elif kind == "vertices":
             pos = np.ascontiguousarray(item[2], dtype=np.float32).reshape(-1, 3)
             nrm = None if len(item) < 4 or item[3] is None else np.ascontiguousarray(item[3], dtype=np.float32).reshape(-1, 3)
@@ -643,6 +684,13 @@ def deform_items_device(items, device):
             t = t.to(torch.float32).contiguous()
         return t
 
+    def weights(t):
+        """morph weights: a contiguous float32 vector - a slice of a larger tensor is named where it lies"""
+        if t.device.index != device:
+            raise ValueError(f"the tensor lies on {t.device}, the context on cuda:{device}")
+        t = t.reshape(-1)
+        return t if t.dtype == torch.float32 and t.is_contiguous() else t.to(torch.float32).contiguous()
+
     table, keep = (F.HkMeshDeformDevice * max(len(items), 1))(), []
     for k, item in enumerate(items):
         kind, mesh = item[0], item[1]
@@ -653,6 +701,17 @@ def deform_items_device(items, device):
             j = rows(item[2], 16).contiguous()
             keep.append(j)
             table[k] = F.HkMeshDeformDevice(mesh, F.DEFORM_SKIN, len(j), j.data_ptr(), None, 0, 0, flags, 0)
+        elif kind in ("morph", "morph_skin"):
+            if len(_item_arrays(item)) != (1 if kind == "morph" else 2):
+                raise ValueError('a morph item is ("morph", index, weights), a morph + skin item ("morph_skin", index, joints, weights)')
+            w = weights(item[2] if kind == "morph" else item[3])
+            if kind == "morph":
+                keep.append(w)
+                table[k] = F.HkMeshDeformDevice(mesh, F.DEFORM_MORPH, len(w), w.data_ptr(), None, 0, 0, flags, 0)
+            else:
+                j = rows(item[2], 16).contiguous()
+                keep += [j, w]
+                table[k] = F.HkMeshDeformDevice(mesh, F.DEFORM_MORPH_SKIN, len(j), j.data_ptr(), w.data_ptr(), 0, 0, flags, 0)
         elif kind == "vertices":
             pos = rows(item[2], 3)
             nrm = None if len(item) < 4 or item[3] is None or isinstance(item[3], dict) else rows(item[3], 3)
@@ -792,6 +851,13 @@ class Engine:
         fp = lambda a: a.ctypes.data_as(C.POINTER(F.f32))
         self.api.call("set_mesh_skin", self.ctx, C.byref(mesh), len(pos), fp(pos), fp(nrm), idx.ctypes.data_as(C.POINTER(C.c_uint16)), fp(w))
 
+    def set_mesh_morph_targets(self, mesh, base_positions, base_normals, position_deltas, normal_deltas=None):
+        """Morph targets (blend shapes) of one uploaded mesh, set once (hk_set_mesh_morph_targets): base positions and normals [v][3],
+        position deltas [target][v][3] and normal deltas alike (None: the normals do not morph).  Per frame a ("morph", index, weights)
+        or ("morph_skin", index, joints, weights) item of deform_meshes carries the weights alone."""
+        arrays = _morph_arrays(base_positions, base_normals, position_deltas, normal_deltas)
+        self.api.call("set_mesh_morph_targets", self.ctx, C.byref(mesh), *arrays[0], *[_fp(a) for a in arrays[1:]])
+
     def skin_mesh(self, mesh, joint_matrices):
         """Per frame: column-major 4x4 joint matrices (n x 16 floats); the device skins and refits (hk_skin_mesh)."""
         j = np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1, 16)
@@ -799,7 +865,8 @@ class Engine:
 
     def deform_meshes(self, items, producer_stream=None):
         """Many meshes deformed in one call (hk_deform_meshes): `items` is a list of ("vertices", index, positions, normals_or_None) and
-        ("skin", index, joints) tuples - what update_mesh_vertices / skin_mesh take, mesh by mesh.  The device work is a fixed number of
+        ("skin", index, joints) tuples - what update_mesh_vertices / skin_mesh take, mesh by mesh - and of ("morph", index, weights) and
+        ("morph_skin", index, joints, weights) tuples for meshes with a morph set (set_mesh_morph_targets).  The device work is a fixed number of
         launches however many items there are; the result is what the single calls in item order would have left.
         Items whose arrays are torch tensors on the context's device take hk_deform_meshes_device: nothing is copied to the host, the
         context is ordered behind `producer_stream` (a torch stream; default: torch's current stream) by an event, and that stream behind

@@ -385,6 +385,68 @@ def skin_reference(bind_p, bind_n, ji, jw, joints):
     return pos.astype(np.float32), nrm.astype(np.float32)
 
 
+def morph_reference(base_p, base_n, dp, dn, weights):
+    """numpy float32 restatement of the morph contract (hikari_hip.h hk_set_mesh_morph_targets), operation for operation: base, then the
+    targets whose weight does not compare equal to zero in ascending index, each product rounded, then each sum.  dp / dn: [target][v][3]
+    (dn None: the base normals as they are).  Returns (positions, normals)."""
+    w = np.asarray(weights, np.float32).reshape(-1)
+    pos, nrm = np.array(base_p, np.float32).reshape(-1, 3), np.array(base_n, np.float32).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        for k in range(len(w)):
+            if w[k] == 0:   # (+0 and -0; a NaN weight is active)
+                continue
+            pos = pos + w[k] * np.asarray(dp[k], np.float32).reshape(-1, 3)
+            if dn is not None:
+                nrm = nrm + w[k] * np.asarray(dn[k], np.float32).reshape(-1, 3)
+    return pos.astype(np.float32), nrm.astype(np.float32)
+
+
+def morph_targets(positions, normals, n_targets, seed=0, normal_deltas=True):
+    """`n_targets` dense morph targets for a coil_ribbon / cloth_grid mesh, in turn a bulge along the normals, a twist about the y axis and
+    per-vertex noise, each with its own scale and phase: (position deltas, normal deltas or None), [target][v][3] float32."""
+    rng = np.random.default_rng(seed)
+    p, n = positions.astype(np.float64), normals.astype(np.float64)
+    span = max(float(np.ptp(p[:, 1])), float(np.ptp(p[:, 0])), 1e-3)
+    t = (p[:, 1] - p[:, 1].min()) / span if np.ptp(p[:, 1]) > 0 else (p[:, 0] - p[:, 0].min()) / span
+    dp, dn = np.zeros((n_targets,) + p.shape), np.zeros((n_targets,) + p.shape)
+    for k in range(n_targets):
+        scale, phase = 0.04 + 0.02 * (k % 5), 0.61 * k
+        if k % 3 == 0:    # bulge
+            lobe = np.sin(math.pi * t * (1 + k % 4) + phase)
+            dp[k] = scale * lobe[:, None] * n
+            dn[k] = 0.3 * np.cos(math.pi * t * (1 + k % 4) + phase)[:, None] * np.array([0.0, 1.0, 0.0])
+        elif k % 3 == 1:  # twist about y, growing with height
+            ang = scale * 4.0 * t * math.cos(phase)
+            c, s = np.cos(ang), np.sin(ang)
+            for src, out in ((p, dp), (n, dn)):
+                out[k, :, 0] = c * src[:, 0] - s * src[:, 2] - src[:, 0]
+                out[k, :, 2] = s * src[:, 0] + c * src[:, 2] - src[:, 2]
+        else:             # noise
+            dp[k] = scale * 0.5 * rng.standard_normal(p.shape)
+            dn[k] = 0.1 * rng.standard_normal(p.shape)
+    return dp.astype(np.float32), (dn.astype(np.float32) if normal_deltas else None)
+
+
+def morph_weights(n_targets, frame, phase=0.0, mode="wave"):
+    """Animated weights of `n_targets` targets at `frame`, float32.  "wave": every target swings between about -0.3 and 1.2 (weights are
+    used as given), and the targets k with (k + frame) % 4 == 0 are EXACTLY zero; "none": all zero; "one": target frame % n alone; "all":
+    none zero; "alternate": every other one zero."""
+    k = np.arange(n_targets)
+    w = (0.45 + 0.75 * np.sin(0.8 * frame + phase + 0.9 * k)) / np.sqrt(1.0 + n_targets / 4.0)
+    w = np.where(w == 0, 0.125, w)
+    if mode == "wave":
+        w[(k + frame) % 4 == 0] = 0.0
+    elif mode == "none":
+        w[:] = 0.0
+    elif mode == "one":
+        w[k != frame % n_targets] = 0.0
+    elif mode == "alternate":
+        w[k % 2 == 1] = 0.0
+    elif mode != "all":
+        raise ValueError(f"unknown mode {mode!r}")
+    return w.astype(np.float32)
+
+
 def deforming_scene(base="yard", cloth=(12, 12)):
     """A scene with three deforming meshes on top of `base` ("yard": synthetic_scene beyond the LDS copy, "small": one that fits it):
     a waving cloth, a bending cylinder (skinned) and a pulsing emissive sphere.  Returns (SceneData with .builder, sun, meshes) where

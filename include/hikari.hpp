@@ -250,6 +250,13 @@ inline HkMaterial standard_material(const float base_color[4], const float emiss
   return m;
 }
 
+// hk_morph_vertices: base + the active morph targets in ascending index, the arithmetic of a HK_DEFORM_MORPH item on the host (no GPU);
+// positions_out / normals_out: n_vertices x 3 floats each
+inline void morph_vertices(uint32_t n_vertices, uint32_t n_targets, const float* base_positions, const float* base_normals, const float* position_deltas,
+                           const float* normal_deltas, const float* weights, float* positions_out, float* normals_out) {
+  check(hk_morph_vertices(n_vertices, n_targets, base_positions, base_normals, position_deltas, normal_deltas, weights, positions_out, normals_out), "hk_morph_vertices");
+}
+
 // ------------------------------------------------------------------ RAII over the C handles
 class SceneBuilder {  // the Prepare-stage host work: mesh -> BLAS, TLAS, emissives, alias tables
  public:
@@ -436,6 +443,12 @@ class HikariPlugin {
     check(hk_read_texture(ctx_.get(), index, rgba.data(), rgba.size()), "hk_read_texture");
     return rgba;
   }
+  // morph targets of one mesh, set once (dense, target-major: delta k of vertex v at [(k * n_vertices + v) * 3]; normal_deltas may be nullptr);
+  // per frame a HK_DEFORM_MORPH / HK_DEFORM_MORPH_SKIN item of deform_meshes carries the weights alone.  hk_morph_vertices is the host twin
+  void set_mesh_morph_targets(const HkMeshIndex& mesh, uint32_t n_vertices, uint32_t n_targets, const float* base_positions, const float* base_normals,
+                              const float* position_deltas, const float* normal_deltas = nullptr) {
+    check(hk_set_mesh_morph_targets(ctx_.get(), &mesh, n_vertices, n_targets, base_positions, base_normals, position_deltas, normal_deltas), "hk_set_mesh_morph_targets");
+  }
   // a new tree over the current triangles of one deformed mesh, built on the device in place (later deformations refit the new shape)
   // per frame: every deforming mesh in one call (vertex updates and skinned meshes alike), at a launch count that does not depend on how many
   void deform_meshes(const std::vector<HkMeshDeform>& items) { check(hk_deform_meshes(ctx_.get(), items.data(), (uint32_t)items.size()), "hk_deform_meshes"); }
@@ -540,6 +553,11 @@ class HikariMultiGpuPlugin {
     return changed;
   }
   void update_texture(uint32_t index, const HkImageDesc& image) { check(hk_multi_update_texture(m_, index, &image), "hk_multi_update_texture"); }
+  void set_mesh_morph_targets(const HkMeshIndex& mesh, uint32_t n_vertices, uint32_t n_targets, const float* base_positions, const float* base_normals,
+                              const float* position_deltas, const float* normal_deltas = nullptr) {
+    check(hk_multi_set_mesh_morph_targets(m_, &mesh, n_vertices, n_targets, base_positions, base_normals, position_deltas, normal_deltas),
+          "hk_multi_set_mesh_morph_targets");
+  }
   void deform_meshes(const std::vector<HkMeshDeform>& items) { check(hk_multi_deform_meshes(m_, items.data(), (uint32_t)items.size()), "hk_multi_deform_meshes"); }
   void rebuild_mesh_tree(const HkMeshIndex& mesh, uint32_t mode = HK_TREE_SAH) { check(hk_multi_rebuild_mesh_tree(m_, &mesh, mode), "hk_multi_rebuild_mesh_tree"); }
   // rows of last frame's reservoirs fetched across the band borders before reprojection (0 for a static camera)

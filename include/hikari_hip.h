@@ -675,9 +675,9 @@ int hk_skin_mesh(hk_ctx* ctx, const HkMeshIndex* mesh, const float* joint_matric
 typedef struct HkMeshDeform {
   HkMeshIndex  mesh;
   uint32_t     kind;
-  uint32_t     count;    /* VERTICES: n_vertices.  SKIN: n_joints */
-  const float* data;     /* VERTICES: count x 3 positions.  SKIN: count x 16 joint matrices, column-major */
-  const float* normals;  /* VERTICES: count x 3, or NULL = keep.  SKIN: must be NULL */
+  uint32_t     count;    /* VERTICES: n_vertices.  SKIN, MORPH_SKIN: n_joints.  MORPH: n_targets */
+  const float* data;     /* VERTICES: count x 3 positions.  SKIN, MORPH_SKIN: count x 16 joint matrices, column-major.  MORPH: count weights */
+  const float* normals;  /* VERTICES: count x 3, or NULL = keep.  SKIN, MORPH: must be NULL.  MORPH_SKIN: the set's n_targets weights */
 } HkMeshDeform;
 int hk_deform_meshes(hk_ctx* ctx, const HkMeshDeform* items, uint32_t n);
 /* ... and the same batch with its SOURCES IN DEVICE MEMORY (a cloth solver's positions, a joint palette animated on the GPU): the call
@@ -704,16 +704,55 @@ int hk_deform_meshes(hk_ctx* ctx, const HkMeshDeform* items, uint32_t n);
 #define HK_DEFORM_RECOMPUTE_NORMALS 1u
 typedef struct HkMeshDeformDevice {
   HkMeshIndex mesh;
-  uint32_t    kind;            /* HK_DEFORM_VERTICES / HK_DEFORM_SKIN */
-  uint32_t    count;           /* VERTICES: n_vertices.  SKIN: n_joints */
-  const void* data;            /* DEVICE memory.  VERTICES: positions, 3 floats per vertex at data + v * data_stride.  SKIN: count x 16 floats, column-major, contiguous */
-  const void* normals;         /* DEVICE memory, 3 floats per vertex at normals + v * normals_stride, or NULL */
-  uint32_t    data_stride;     /* bytes; 0 = packed (12).  VERTICES only: >= 12, a multiple of 4.  SKIN: 0 or 64 */
-  uint32_t    normals_stride;  /* bytes; 0 = packed (12) */
+  uint32_t    kind;            /* HK_DEFORM_VERTICES / HK_DEFORM_SKIN / HK_DEFORM_MORPH / HK_DEFORM_MORPH_SKIN */
+  uint32_t    count;           /* VERTICES: n_vertices.  SKIN, MORPH_SKIN: n_joints.  MORPH: n_targets */
+  const void* data;            /* DEVICE memory.  VERTICES: positions, 3 floats per vertex at data + v * data_stride.  SKIN, MORPH_SKIN: count x 16 floats, column-major, contiguous.  MORPH: count weights, contiguous */
+  const void* normals;         /* DEVICE memory, 3 floats per vertex at normals + v * normals_stride, or NULL.  MORPH_SKIN: the set's n_targets weights, contiguous */
+  uint32_t    data_stride;     /* bytes; 0 = packed (12).  VERTICES only: >= 12, a multiple of 4.  SKIN, MORPH_SKIN: 0 or 64.  MORPH: 0 or 4 */
+  uint32_t    normals_stride;  /* bytes; 0 = packed (12).  MORPH_SKIN: 0 or 4 */
   uint32_t    flags;           /* HK_DEFORM_RECOMPUTE_NORMALS */
   uint32_t    _pad;
 } HkMeshDeformDevice;          /* 56 bytes */
 int hk_deform_meshes_device(hk_ctx* ctx, const HkMeshDeformDevice* items, uint32_t n, void* producer_stream);
+/* MORPH TARGETS (blend shapes, glTF 2.0 section 3.7.2.2) blended on the device, as items of the two batch calls above.  A morph set is
+ * given once per mesh, like a skin: base positions and normals (n_vertices x 3 floats each) and n_targets dense targets, target-major -
+ * delta k of vertex v at [(k * n_vertices + v) * 3] of position_deltas and of normal_deltas (or NULL: the normals do not morph).  Per
+ * frame an item carries only the n_targets weights; the deltas never cross the bus again.
+ *   HK_DEFORM_MORPH       count = the set's n_targets, data = count weights (floats), normals must be NULL
+ *   HK_DEFORM_MORPH_SKIN  count = n_joints, data = the palette as for HK_DEFORM_SKIN; `normals` names the set's n_targets weights.  The
+ *                         morphed position and normal of a vertex take the place of the skin's bind position and normal in the skinning
+ *                         arithmetic of hk_skin_mesh (in registers: nothing is written in between); palette, joint indices and joint
+ *                         weights are those of hk_set_mesh_skin, whose bind planes are not read.  Needs a morph set and a skin of the
+ *                         same vertex count.
+ *   The numeric contract.  All in f32, no contraction: each product is rounded, then each sum.  Per component
+ *     p = ((base + w[a1] * dp[a1]) + w[a2] * dp[a2]) + ...
+ * over the ACTIVE targets a1 < a2 < ... in ascending target index.  A target is active iff its weight does not compare equal to zero:
+ * +0 and -0 are skipped, a NaN weight is active.  A skipped target contributes nothing - no signed zero, no NaN from an infinite delta.
+ * Normals follow the same rule with the normal deltas; without normal deltas every call writes the base normals.  Normals are stored
+ * un-normalised, as on every other path.  Weights are used as given, neither clamped nor normalised.  hk_morph_vertices is the host
+ * twin of this arithmetic (no context, no GPU).
+ *   After a MORPH item the context is in every respect what a HK_DEFORM_VERTICES item carrying hk_morph_vertices' positions and normals
+ * would have left; after a MORPH_SKIN item what hk_set_mesh_skin(the morphed bind pose) followed by a HK_DEFORM_SKIN item would have
+ * left - device bytes, what is stale, what is refused afterwards, how it composes with refits, rebuilds and frames in flight.  A batch
+ * with morph items stays at five launches and one pinned staging block, and does not wait for the device once nothing has to grow.
+ *   State.  A set replaces an earlier one behind a wait for the device, as a skin does; hk_upload_meshes / hk_upload_scene drop morph
+ * sets as they drop skins; hk_add_meshes, refits and rebuilds leave them alone.  n_vertices must be the mesh's vertex count.
+ *   Validation (the whole batch before anything is enqueued, item index in hk_last_error(); HK_E_INVALID): no morph set for the mesh;
+ * MORPH with count != the set's target count or with normals != NULL; MORPH_SKIN with normals == NULL, without a skin or with a skin
+ * of another vertex count, or a joint index >= count; HK_DEFORM_RECOMPUTE_NORMALS on either kind.  hk_deform_meshes_device: weights
+ * are a source like any other (4-byte alignment, n_targets x 4 bytes inside their allocation), data_stride of a MORPH item and
+ * normals_stride of a MORPH_SKIN item must be 0 or 4.  The set call: n_targets == 0 or > HK_MORPH_MAX_TARGETS, a NULL pointer (but
+ * normal_deltas) or a vertex count that is not the mesh's is HK_E_INVALID, a failed allocation HK_E_NOMEM. */
+#define HK_DEFORM_MORPH      2u
+#define HK_DEFORM_MORPH_SKIN 3u
+#define HK_MORPH_MAX_TARGETS 4096u
+int hk_set_mesh_morph_targets(hk_ctx* ctx, const HkMeshIndex* mesh, uint32_t n_vertices, uint32_t n_targets, const float* base_positions,
+                              const float* base_normals, const float* position_deltas, const float* normal_deltas);
+/* the vertex arithmetic above on the host: positions_out and normals_out (n_vertices x 3 floats each) from the arrays of a set and
+ * n_targets weights.  HK_E_INVALID for a NULL pointer (but normal_deltas), n_vertices == 0, n_targets == 0 or > HK_MORPH_MAX_TARGETS. */
+int hk_morph_vertices(uint32_t n_vertices, uint32_t n_targets, const float* base_positions, const float* base_normals,
+                      const float* position_deltas, const float* normal_deltas, const float* weights, float* positions_out,
+                      float* normals_out);
 /* Instance POSES FROM DEVICE MEMORY (rigid bodies stepped on the GPU, a crowd placed by a kernel): what hk_refit_scene_instances does for
  * poses the host never sees.  After the call the device scene holds, byte for byte, what hk_refit_scene_instances would have left had the
  * same values been set on the builder with hk_scene_builder_set_instance_transform: instance records, previous models, world boxes,
@@ -1225,11 +1264,13 @@ int hk_multi_add_meshes(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode);
 int hk_multi_upload_scene_instances(hk_multi* m, const hk_scene_builder* b);
 int hk_multi_refit_scene_instances(hk_multi* m, hk_scene_builder* b, uint32_t* moved); /* hk_refit_scene_instances on every band's replica */
 int hk_multi_rebuild_scene_trees(hk_multi* m, uint32_t mode);
-/* hk_update_mesh_vertices / hk_set_mesh_skin / hk_skin_mesh on every band's replica */
+/* hk_update_mesh_vertices / hk_set_mesh_skin / hk_skin_mesh / hk_set_mesh_morph_targets / hk_deform_meshes on every band's replica */
 int hk_multi_update_mesh_vertices(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vertices, const float* positions, const float* normals);
 int hk_multi_set_mesh_skin(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vertices, const float* bind_positions, const float* bind_normals,
                            const uint16_t* joint_indices, const float* joint_weights);
 int hk_multi_skin_mesh(hk_multi* m, const HkMeshIndex* mesh, const float* joint_matrices, uint32_t n_joints);
+int hk_multi_set_mesh_morph_targets(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vertices, uint32_t n_targets, const float* base_positions,
+                                    const float* base_normals, const float* position_deltas, const float* normal_deltas);
 int hk_multi_deform_meshes(hk_multi* m, const HkMeshDeform* items, uint32_t n);
 int hk_multi_rebuild_mesh_tree(hk_multi* m, const HkMeshIndex* mesh, uint32_t mode);
 int hk_multi_set_band_bounds(hk_multi* m, const uint32_t* bounds, uint32_t n_bounds);
