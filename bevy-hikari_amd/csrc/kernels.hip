@@ -670,8 +670,20 @@ struct SpatialPixel {
 //    only notes the taps that reach their record (its index in LDS, 16 x 256 words per workgroup), the second walks each lane's list:
 //    a wave runs it as often as its BUSIEST lane has survivors.  Same taps, same order of merges: the same bits.
 // Measured (profiles/r05_spatial_reuse_ab.txt): 15 % fewer VALU wave-instructions at lane utilisation 0.84 instead of 0.71 - worth
-// -7 % / -18 % on the two spatial passes of a 4K Cornell frame (config 5: the frame 4.44 -> 4.25 ms), and NOTHING at 1080p, where the
-// launch is three rounds of workgroups and ends in a tail as long as a wave lives: there the plain form stays.
+// -7 % / -18 % on the two spatial passes of a 4K Cornell frame (config 5: the frame 4.44 -> 4.25 ms), and nothing at 1080p in the frame
+// of that round, which still waited for its side and post streams at the end of every frame.
+// Measured again on the frame without those waits (profiles/spatial_listed_ab.json; 1080p indirect channel, SQ counters): 155.7 M ->
+// 139.4 M VALU wave-instructions, lane utilisation 0.707 -> 0.846, half the vector memory reads, the launch alone 306 -> 280 us, in the
+// frame 364 -> 336 us.  What the FRAME gets of that depends on what runs beside the pass.  Cornell 1080p with both spatial passes and no
+// denoiser (config 5 at 1080p): 1.166 -> 1.133 ms, -2.8 %, every round of three apart in two sessions (the emissive channel alone:
+// -1.4 %).  The headline (indirect channel only, the denoiser on its own stream): -0.8 %, -0.2 %, +0.2 % in three sessions - nothing
+// that stands out of the run-to-run spread; 1440p and config 3 the same.  Hence the rule: from 1080p (8 160 tiles) up, where it wins or
+// costs nothing; at 720p it moved nothing, and the plain form stays below 1080p.
+// A third form - the lists alone, as 16-bit offsets from the pixel (8 KB), no window, no barrier - issued fewer instructions still
+// (133.8 M, 0.838; alone 286 us), WAITED more (SQ_WAIT_ANY +15 %: the same gathers with less arithmetic between them) and gained less
+// than this one in the same session (the headline 0.8346 against 0.8306 ms): the window's LDS reads in place of ~85 gathered depths per pixel are worth more than its
+// barrier costs.  It is kept as profiles/spatial_listed_experiment.patch.  (16-bit lists in THIS form, 31 -> 22.6 KB so that two of
+// k_direct_lit's workgroups fit beside four of these instead of one: 2 spilled VGPRs and no gain at 1080p or 4K - not kept.)
 constexpr int HK_SPATIAL_TILE_W = 60, HK_SPATIAL_TILE_REACH = 22;
 template <bool WINDOWED>
 struct DepthWindow {
@@ -1124,10 +1136,13 @@ void launch_resolve_scatter_lite(hipStream_t st, const LightTargets& t, const DF
   const int p0 = y0 * fr.rw, p1 = y1 * fr.rw;
   hipLaunchKernelGGL(k_resolve_scatter_lite, dim3((unsigned)((p1 - p0 + 255) / 256)), dim3(256), 0, st, t, fr, depth_plane, indirect ? 1 : 0, p0, p1);
 }
-// windowed: 0 never, 1 always, -1 by the size of the launch - the windowed form pays where the launch is many rounds of workgroups
-// (HK_SPATIAL_WINDOWED_MIN_TILES: sixteen rounds of 4 workgroups on 256 CUs); a 1080p frame (8 160 tiles) keeps the plain one
+// windowed: 0 never, 1 always, -1 by the size of the launch - the windowed form pays where the launch is many rounds of workgroups.
+// HK_SPATIAL_WINDOWED_MIN_TILES is the smallest launch at which it was MEASURED to win: a 1080p frame (8 160 tiles: eight rounds of
+// 4 workgroups on 256 CUs) - where both spatial passes run; the headline, which runs one, neither gains nor loses by it (the comment
+// above DepthWindow).  At 720p (3 600 tiles) it moved nothing, and no size between the two was measured: below 1080p the plain form
+// stays.  (A macro: a build with another value is the A/B from one source tree.)
 #ifndef HK_SPATIAL_WINDOWED_MIN_TILES
-#define HK_SPATIAL_WINDOWED_MIN_TILES 16384u
+#define HK_SPATIAL_WINDOWED_MIN_TILES 8160u
 #endif
 bool launch_spatial(hipStream_t st, bool emissive_lit, const DScene& sc, const DFrame& fr, const GBuffer& g, const LightTargets& t, int y0, int y1, int windowed,
                     hipEvent_t start, hipEvent_t stop) {
