@@ -93,6 +93,10 @@ class HkMeshIndex(C.Structure):
     _fields_ = [("vertex", u32), ("primitive", u32), ("node_offset", u32), ("node_count", u32)]
 
 
+class HkMeshExtent(C.Structure):
+    _fields_ = [("vertex", u32), ("n_vertices", u32), ("primitive", u32), ("n_primitives", u32), ("node_offset", u32), ("node_count", u32)]
+
+
 class HkInstance(C.Structure):
     _fields_ = [("min", f32 * 3), ("material", u32), ("max", f32 * 3), ("node_index", u32), ("model", f32 * 16),
                 ("inverse_transpose_model", f32 * 16), ("mesh", HkMeshIndex)]
@@ -251,6 +255,8 @@ _DEBUG = {
     "debug_last_load": [_vp, P(u32)],
     "debug_last_add": [_vp, P(u32)],
     "debug_last_add_times": [_vp, P(C.c_double)],
+    "debug_last_remove": [_vp, P(C.c_uint64)],
+    "debug_last_remove_ms": [_vp, P(f32)],
     "debug_last_load_times": [_vp, P(C.c_double)],
     "debug_read_emitters": [_vp, P(f32), u32, P(u32), P(f32), u32, P(u32)],
     "debug_read_mesh_geometry": [_vp, P(HkMeshIndex), P(f32), P(f32), u32, P(f32), u32, P(f32), P(u32), P(u32)],
@@ -302,10 +308,14 @@ _PRODUCT_ONLY = {
     "scene_builder_recompute_mesh_normals": [_vp, u32],
     "scene_builder_rebuild_mesh_tree": [_vp, u32],
     "scene_builder_mesh_index": [_vp, u32, P(HkMeshIndex)],
+    "scene_builder_mesh_extent": [_vp, u32, P(HkMeshExtent)],
+    "scene_builder_remove_mesh": [_vp, u32, P(HkMeshExtent)],
+    "rebase_mesh_index": [P(HkMeshExtent), u32, P(HkMeshIndex), P(HkMeshIndex)],
     "upload_scene": [_vp, _vp],
     "upload_scene_instances": [_vp, _vp],
     "load_scene": [_vp, _vp, u32],
     "add_meshes": [_vp, _vp, u32],
+    "remove_meshes": [_vp, P(HkMeshExtent), u32],
     "refit_scene_instances": [_vp, _vp, P(u32)],
     "rebuild_scene_trees": [_vp, u32],
     "update_scene_instances": [_vp, _vp, u32],
@@ -365,6 +375,7 @@ _PRODUCT_ONLY = {
     "multi_upload_scene_instances": [_vp, _vp],
     "multi_load_scene": [_vp, _vp, u32],
     "multi_add_meshes": [_vp, _vp, u32],
+    "multi_remove_meshes": [_vp, P(HkMeshExtent), u32],
     "multi_refit_scene_instances": [_vp, _vp, P(u32)],
     "multi_rebuild_scene_trees": [_vp, u32],
     "multi_update_scene_instances": [_vp, _vp, u32],

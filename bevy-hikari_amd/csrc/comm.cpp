@@ -826,6 +826,8 @@ int hk_multi_add_meshes(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode) {
   for (size_t i = 0; i < m->ctx.size() && !rc; ++i) rc = hk_add_meshes(m->ctx[i], b, tree_mode);
   return rc;
 }
+// hk_remove_meshes for every band (every context validates before it writes; the bands hold one scene, so they agree)
+int hk_multi_remove_meshes(hk_multi* m, const HkMeshExtent* removed, uint32_t n) { HK_EACH(hk_remove_meshes(c, removed, n)); }
 int hk_multi_upload_scene_instances(hk_multi* m, const hk_scene_builder* b) { HK_EACH(hk_upload_scene_instances(c, b)); }
 int hk_multi_rebuild_scene_trees(hk_multi* m, uint32_t mode) { HK_EACH(hk_rebuild_scene_trees(c, mode)); }
 int hk_multi_update_mesh_vertices(hk_multi* m, const HkMeshIndex* mesh, uint32_t n_vertices, const float* positions, const float* normals) {

@@ -1174,6 +1174,8 @@ void hk_destroy(hk_ctx* c) {
   free_screen(c);
   if (c->scene_mem) (void)hipFree(c->scene_mem);
   poll_retired(c, true);
+  for (hipEvent_t e : c->rm_ev)
+    if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < 2; ++k) {
     if (c->staging[k]) (void)hipHostFree(c->staging[k]);
     if (c->staging_done[k]) (void)hipEventDestroy(c->staging_done[k]);

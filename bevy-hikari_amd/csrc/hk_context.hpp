@@ -3,7 +3,8 @@
 //   context.hip       lifetime, screen-space resources, the frame graph (hk_frame_*, hk_pass_run), bands, buffers, statistics
 //   scene_layout.hip  uploads and the layout conversion: reference-layout scene arrays -> the device's scene blob (finalize_scene)
 //   scene_refit.hip   instance motion and instance-set changes on the device (hk_refit_scene_instances, hk_rebuild_scene_trees, ...)
-//   scene_load.hip    mesh trees built on the device at scene load (hk_load_scene); scene_append.hip: meshes appended later (hk_add_meshes)
+//   scene_load.hip    mesh trees built on the device at scene load (hk_load_scene); scene_append.hip: meshes appended later (hk_add_meshes);
+//                     scene_remove.hip: meshes removed, the mesh level compacted (hk_remove_meshes)
 //   probes.hip        measurement hooks (hk_measure_*, hk_debug_math)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -221,6 +222,9 @@ struct hk_ctx {
   std::vector<Retired> retired;
   uint32_t last_add[5] = {0, 0, 0, 0, 0};   // hk_debug_last_add
   double last_add_ms[4] = {0, 0, 0, 0};     // hk_debug_last_add_times
+  uint64_t last_remove[6] = {0, 0, 0, 0, 0, 0};   // hk_debug_last_remove (scene_remove.hip)
+  hipEvent_t rm_ev[2] = {nullptr, nullptr};       // around the compaction launch of the last hk_remove_meshes (hk_debug_last_remove_ms)
+  bool rm_timed = false;
   uint64_t static_rebuilds = 0, dynamic_rebuilds = 0;
   // Parked previous_spatial stores (HK_CTX_DETERMINISTIC_SCATTER; every band of a sharded frame with a history halo: SURVEY 8e
   // step 6), one set per light channel.  `to` and the records are the HK_BUF_PARKED_* planes (c->buf: bands exchange their rows),
@@ -469,6 +473,11 @@ int build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMesh>&
 void retire(hk_ctx* c, void* p, hipEvent_t done);   // free `p` once `done` has passed (takes the event over)
 void poll_retired(hk_ctx* c, bool wait);            // ... checked here, only behind a wait for the context's streams (hipFree may wait by itself); wait: free everything
 int take_appended_materials(hk_ctx* c, const hk_scene_builder* b);  // hk_update_scene_instances: materials the builder holds beyond the context's (the caller takes them back if the upload is refused)
+// ---- mesh_deform.hip, for hk_remove_meshes (scene_remove.hip): the records of the deformable meshes; then, `runs` being the surviving
+// intervals per list (nodes, primitives, vertices), every record rebased and the meshes that lie in no run dropped - their device
+// allocations go to `freed` for the caller to retire
+void deform_mesh_records(const hk_ctx* c, std::vector<HkMeshIndex>& out);
+void rebase_deform_meshes(hk_ctx* c, const std::vector<hk::CompactRun> runs[3], std::vector<void*>& freed);
 // ---- scene_refit.hip
 void free_refit(hk_ctx* c);
 int begin_device_update(hk_ctx* c);

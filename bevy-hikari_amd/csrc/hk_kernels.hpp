@@ -462,6 +462,36 @@ struct CopySegments {
   }
 };
 void launch_copy_segments(hipStream_t st, const CopySegments& segments);
+// hk_remove_meshes (scene_remove.hip): the surviving runs of many planes moved to a new allocation in ONE launch.  Three run lists - the
+// surviving intervals in node, primitive and vertex units, `dst` their prefix sum - and up to HK_COMPACT_PLANES planes, each with its old
+// base, its new base, the list it follows and its element size 1 << shift (4, 8, 16, 32 or 128 B); the tables lie in device memory.  A
+// work item is HK_COMPACT_PIECE bytes of a plane's DESTINATION: the load is the same for one run of a gigabyte and for three thousand
+// runs of a kilobyte.  Bases are 16-B aligned; a run's source is not, in the 4-B and 8-B planes.
+#define HK_COMPACT_PLANES 16u
+#define HK_COMPACT_PIECE 16384u
+struct CompactRun { uint32_t src, dst, count, pad; };
+struct CompactPlane { const uint8_t* src; uint8_t* dst; uint32_t list, shift; uint64_t first_piece; };
+struct CompactArgs {
+  const CompactPlane* planes;
+  const CompactRun* runs[3];
+  uint32_t n_planes, n_runs[3], total[3];   // total: the surviving elements of a list
+  uint64_t n_pieces;
+};
+// where element `x` of a list lies once only the runs are left: x minus the removed elements in front of it (host and device)
+__host__ __device__ inline uint32_t compact_rebase(const CompactRun* runs, uint32_t n, uint32_t x) {
+  uint32_t lo = 0, hi = n;   // the first run that begins behind x
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (runs[mid].src <= x) lo = mid + 1; else hi = mid;
+  }
+  if (!lo) return 0u;
+  const CompactRun r = runs[lo - 1];
+  return r.dst + (x - r.src < r.count ? x - r.src : r.count);
+}
+void launch_compact_planes(hipStream_t st, const CompactArgs& a, int compute_units);
+// ... and beside it: the instance-level slot `src` (n16 pieces of 16 B) copied to both slots of the new allocation, the vertex, primitive
+// and node_offset words of the n_instances DInstance records that begin at piece `first16` rebased by the same runs
+void launch_compact_instances(hipStream_t st, uint4* dst0, uint4* dst1, const uint4* src, size_t n16, size_t first16, uint32_t n_instances, const CompactArgs& a);
 // hk_add_meshes: n_prims HkPrimitive (48 B) and n_verts HkVertex (32 B) records in pinned memory into the triangle planes and the vertex
 // planes, from element 0 of the plane pointers given
 void launch_append_geometry(hipStream_t st, const uint4* prims, uint32_t n_prims, const uint4* verts, uint32_t n_verts, float4* v0, float4* v1, float4* v2, float4* vn,

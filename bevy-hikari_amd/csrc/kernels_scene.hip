@@ -322,6 +322,73 @@ __global__ __launch_bounds__(256) void k_copy_segments(hk::CopySegments t) {
   const uint32_t tail = (uint32_t)(s.bytes % 16u) / 4u;
   if (blockIdx.x == 0u && threadIdx.x < tail) ((uint32_t*)(s.dst + n))[threadIdx.x] = ((const uint32_t*)(s.src + n))[threadIdx.x];
 }
+// hk_remove_meshes: the surviving runs of every plane of the mesh level into a new allocation (hk_kernels.hpp CompactArgs).  A workgroup
+// takes pieces of HK_COMPACT_PIECE destination bytes, grid-strided; plane and run range of a piece are the same for all its lanes, a
+// lane then looks for its run inside that range only - one run however long costs no search, many short ones a short one.  A lane
+// moves 16 B where its 16 destination bytes lie in one run and the source is 16-B aligned too (always in the planes of 16 B elements
+// and more); in the uv and rank planes, where a removed mesh shifts what follows by 8 or 4 B, and across run boundaries, it moves
+// element by element.
+__device__ __forceinline__ uint32_t compact_run_of(const hk::CompactRun* __restrict__ runs, uint32_t lo, uint32_t hi, uint32_t elem) {
+  while (lo < hi) {  // the last run of [lo, hi] that begins at or in front of elem (runs[lo].dst <= elem)
+    const uint32_t mid = lo + (hi - lo + 1u) / 2u;
+    if (runs[mid].dst <= elem) lo = mid; else hi = mid - 1u;
+  }
+  return lo;
+}
+__global__ __launch_bounds__(256) void k_compact_planes(hk::CompactArgs a) {
+  for (uint64_t piece = blockIdx.x; piece < a.n_pieces; piece += gridDim.x) {
+    uint32_t p = 0u;
+    for (uint32_t k = 1u; k < a.n_planes; ++k)
+      if (a.planes[k].first_piece <= piece) p = k;
+    const hk::CompactPlane pl = a.planes[p];
+    const hk::CompactRun* __restrict__ runs = a.runs[pl.list];
+    const uint32_t n_runs = a.n_runs[pl.list], total = a.total[pl.list], shift = pl.shift;
+    const uint64_t bytes = (uint64_t)total << shift;
+    const uint64_t b0 = (piece - pl.first_piece) * HK_COMPACT_PIECE;
+    const uint64_t b1 = b0 + HK_COMPACT_PIECE < bytes ? b0 + HK_COMPACT_PIECE : bytes;
+    if (b0 >= b1 || !n_runs) continue;
+    const uint32_t r_lo = compact_run_of(runs, 0u, n_runs - 1u, (uint32_t)(b0 >> shift));
+    const uint32_t r_hi = compact_run_of(runs, r_lo, n_runs - 1u, (uint32_t)((b1 - 1u) >> shift));
+    for (uint64_t d = b0 + 16u * threadIdx.x; d < b1; d += 16u * 256u) {
+      const uint32_t elem = (uint32_t)(d >> shift);
+      uint32_t r = compact_run_of(runs, r_lo, r_hi, elem);
+      hk::CompactRun run = runs[r];
+      if (shift >= 4u) {  // the 16 B are part of one element
+        const uint64_t s = ((uint64_t)(run.src + (elem - run.dst)) << shift) + (d & ((1ull << shift) - 1u));
+        *(uint4*)(pl.dst + d) = *(const uint4*)(pl.src + s);
+        continue;
+      }
+      const uint32_t per = 16u >> shift, left = total - elem, cnt = left < per ? left : per;
+      const uint64_t s = (uint64_t)(run.src + (elem - run.dst)) << shift;
+      if (cnt == per && elem + cnt <= run.dst + run.count && (((uintptr_t)(pl.src + s)) & 15u) == 0u) {
+        *(uint4*)(pl.dst + d) = *(const uint4*)(pl.src + s);
+        continue;
+      }
+      for (uint32_t j = 0u; j < cnt; ++j) {
+        const uint32_t e = elem + j;
+        while (e >= run.dst + run.count && r + 1u < n_runs) run = runs[++r];
+        const uint64_t from = (uint64_t)(run.src + (e - run.dst)) << shift, to = (uint64_t)e << shift;
+        if (shift == 3u) *(uint2*)(pl.dst + to) = *(const uint2*)(pl.src + from);
+        else *(uint32_t*)(pl.dst + to) = *(const uint32_t*)(pl.src + from);
+      }
+    }
+  }
+}
+// ... and the instance-level slot in use into both slots of the new allocation, the three mesh offsets of every DInstance rebased
+__global__ __launch_bounds__(256) void k_compact_instances(uint4* __restrict__ dst0, uint4* __restrict__ dst1, const uint4* __restrict__ src, size_t n16, size_t first16,
+                                                           uint32_t n_instances, hk::CompactArgs a) {
+  static_assert(sizeof(DInstance) == 13 * 16 && offsetof(DInstance, material) == 11 * 16, "the piece that holds material, vertex, primitive, node_offset");
+  for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256u) {
+    uint4 v = src[i];
+    if (i >= first16 && i - first16 < (size_t)13u * n_instances && (i - first16) % 13u == 11u) {
+      v.y = hk::compact_rebase(a.runs[2], a.n_runs[2], v.y);
+      v.z = hk::compact_rebase(a.runs[1], a.n_runs[1], v.z);
+      v.w = hk::compact_rebase(a.runs[0], a.n_runs[0], v.w);
+    }
+    dst0[i] = v;
+    dst1[i] = v;
+  }
+}
 // hk_add_meshes: reference-layout records (hikari_hip.h HkPrimitive: three 16-B corners; HkVertex: position + u, normal + v) into the
 // planes, with the arithmetic of the host layout (scene_layout.hip build_static_region) - pure moves, the normal plane's w is 0
 __global__ __launch_bounds__(256) void k_append_geometry(const uint4* __restrict__ prims, uint32_t n_prims, const uint4* __restrict__ verts, uint32_t n_verts,
@@ -597,6 +664,16 @@ void launch_copy_segments(hipStream_t st, const CopySegments& segments) {
   for (uint32_t k = 0; k < segments.count; ++k) longest = std::max(longest, segments.seg[k].bytes / 16);
   const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((longest + 255) / 256, 2048));
   hipLaunchKernelGGL(k_copy_segments, dim3(blocks, segments.count), dim3(256), 0, st, segments);
+}
+void launch_compact_planes(hipStream_t st, const CompactArgs& a, int compute_units) {
+  if (!a.n_pieces) return;
+  // (a capped grid, the rest strided: a few workgroups per compute unit keep the memory system busy, more only add launch overhead)
+  const uint64_t cap = (uint64_t)std::max(compute_units, 64) * 8u;
+  hipLaunchKernelGGL(k_compact_planes, dim3((unsigned)std::min<uint64_t>(a.n_pieces, cap)), dim3(256), 0, st, a);
+}
+void launch_compact_instances(hipStream_t st, uint4* dst0, uint4* dst1, const uint4* src, size_t n16, size_t first16, uint32_t n_instances, const CompactArgs& a) {
+  if (!n16) return;
+  hipLaunchKernelGGL(k_compact_instances, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 2048)), dim3(256), 0, st, dst0, dst1, src, n16, first16, n_instances, a);
 }
 void launch_append_geometry(hipStream_t st, const uint4* prims, uint32_t n_prims, const uint4* verts, uint32_t n_verts, float4* v0, float4* v1, float4* v2, float4* vn,
                             float2* vuv) {

@@ -66,6 +66,30 @@ void free_deform(hk_ctx* c) {
     *e = nullptr;
   }
 }
+// hk_remove_meshes (scene_remove.hip): what the deformable meshes name, and their records once only `runs` are left.  A mesh whose nodes
+// lie in no run left with them: its allocations are the caller's to retire (frames in flight may still refit or skin it).  The tree
+// topology, refit planes, skin and morph set of a survivor are its own allocations with links local to the mesh: nothing in them moves.
+void deform_mesh_records(const hk_ctx* c, std::vector<HkMeshIndex>& out) {
+  for (const DeformMesh* d : c->deform) out.push_back(d->mesh);
+}
+void rebase_deform_meshes(hk_ctx* c, const std::vector<CompactRun> runs[3], std::vector<void*>& freed) {
+  size_t kept = 0;
+  for (DeformMesh* d : c->deform) {
+    bool survives = false;
+    for (const CompactRun& r : runs[0]) survives = survives || (d->mesh.node_offset >= r.src && d->mesh.node_offset - r.src < r.count);
+    if (!survives) {
+      for (void* q : {d->mem, d->skin_mem, (void*)d->joint_mats, d->nrm_mem, d->morph_mem})
+        if (q) freed.push_back(q);
+      delete d;
+      continue;
+    }
+    d->mesh.node_offset = compact_rebase(runs[0].data(), (uint32_t)runs[0].size(), d->mesh.node_offset);
+    d->mesh.primitive = compact_rebase(runs[1].data(), (uint32_t)runs[1].size(), d->mesh.primitive);
+    d->mesh.vertex = compact_rebase(runs[2].data(), (uint32_t)runs[2].size(), d->mesh.vertex);
+    c->deform[kept++] = d;
+  }
+  c->deform.resize(kept);
+}
 }  // namespace hk
 
 namespace {

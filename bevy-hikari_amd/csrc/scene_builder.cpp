@@ -272,6 +272,7 @@ struct hk_scene_builder {
   std::vector<HkPrimitive> primitives;
   std::vector<HkNode> asset_nodes;
   std::vector<HkMeshIndex> mesh_index;
+  std::vector<HkMeshExtent> last_extent;   // per mesh the last finish saw, its ranges in THAT finish's arrays (hk_scene_builder_remove_mesh erases with the mesh)
   std::vector<HkInstance> instances;
   std::vector<HkNode> instance_nodes;
   std::vector<HkEmissive> emissives;
@@ -731,6 +732,53 @@ int hk_scene_builder_remove_instance(hk_scene_builder* b, uint32_t instance_id) 
   return HK_OK;
 }
 
+int hk_scene_builder_mesh_extent(const hk_scene_builder* b, uint32_t mesh_id, HkMeshExtent* out) {
+  HK_REQUIRE(b && out, HK_E_INVALID, "NULL argument");
+  HK_REQUIRE(mesh_id < b->meshes.size(), HK_E_INVALID, "unknown mesh id");
+  *out = mesh_id < b->last_extent.size() ? b->last_extent[mesh_id] : HkMeshExtent{0u, 0u, 0u, 0u, 0u, 0u};  // (no finish has seen it: it lies in no array)
+  return HK_OK;
+}
+
+int hk_scene_builder_remove_mesh(hk_scene_builder* b, uint32_t mesh_id, HkMeshExtent* removed) {
+  HK_REQUIRE(b, HK_E_INVALID, "builder is NULL");
+  HK_REQUIRE(mesh_id < b->meshes.size(), HK_E_INVALID, "unknown mesh id");
+  for (size_t i = 0; i < b->instance_decl.size(); ++i)
+    HK_REQUIRE(b->instance_decl[i].mesh != mesh_id, HK_E_INVALID, "instance %zu still names mesh %u: remove its instances first (hk_scene_builder_remove_instance)", i, mesh_id);
+  // ---- nothing is refused from here on
+  if (removed) (void)hk_scene_builder_mesh_extent(b, mesh_id, removed);
+  if (mesh_id < b->last_extent.size()) b->last_extent.erase(b->last_extent.begin() + mesh_id);
+  // the concatenated arrays end where the removed mesh began: the next finish appends the meshes behind it again, what lies in front
+  // keeps its bytes
+  if (mesh_id < b->mesh_index.size()) {
+    const HkMeshIndex cut = b->mesh_index[mesh_id];
+    b->vertices.resize(cut.vertex); b->primitives.resize(cut.primitive); b->asset_nodes.resize(cut.node_offset);
+    b->mesh_index.resize(mesh_id);
+  }
+  b->meshes.erase(b->meshes.begin() + mesh_id);
+  for (hk::BuilderInstance& d : b->instance_decl)
+    if (d.mesh > mesh_id) d.mesh -= 1;
+  b->concat_meshes = std::min<size_t>(b->concat_meshes, mesh_id);
+  b->meshes_dirty = true;
+  b->finished = false;
+  return HK_OK;
+}
+
+int hk_rebase_mesh_index(const HkMeshExtent* removed, uint32_t n, const HkMeshIndex* index, HkMeshIndex* out) {
+  HK_REQUIRE((removed || !n) && index && out, HK_E_INVALID, "NULL argument");
+  // per range the number of removed elements in front of the value: an extent that begins in front of it counts up to the value
+  auto gone = [](uint32_t at, uint32_t begin, uint32_t count) { return begin < at ? std::min(count, at - begin) : 0u; };
+  HkMeshIndex r = *index;
+  for (uint32_t k = 0; k < n; ++k) {
+    const HkMeshExtent& e = removed[k];
+    if (!e.node_count) continue;  // (a mesh no finish had seen: it lay in no array)
+    r.vertex -= gone(index->vertex, e.vertex, e.n_vertices);
+    r.primitive -= gone(index->primitive, e.primitive, e.n_primitives);
+    r.node_offset -= gone(index->node_offset, e.node_offset, e.node_count);
+  }
+  *out = r;
+  return HK_OK;
+}
+
 int hk_scene_builder_set_instance_material(hk_scene_builder* b, uint32_t instance_id, uint32_t material_id) {
   HK_REQUIRE(b, HK_E_INVALID, "builder is NULL");
   HK_REQUIRE(instance_id < b->instance_decl.size() && material_id < b->materials.size(), HK_E_INVALID, "unknown instance or material id");
@@ -772,6 +820,11 @@ static int finish_impl(hk_scene_builder* b, bool build_trees) {
     }
     b->concat_meshes = b->meshes.size();
     b->meshes_dirty = false;
+    b->last_extent.resize(b->meshes.size());
+    for (size_t id = 0; id < b->meshes.size(); ++id) {
+      const HkMeshIndex& mi = b->mesh_index[id];
+      b->last_extent[id] = HkMeshExtent{mi.vertex, (uint32_t)b->meshes[id].vertices.size(), mi.primitive, (uint32_t)b->meshes[id].primitives.size(), mi.node_offset, mi.node_count};
+    }
   }
   b->instances.clear(); b->instance_nodes.clear(); b->emissives.clear(); b->emissive_nodes.clear(); b->alias_table.clear();
   builder_commit_transforms(b);  // PreviousMeshUniform: what the transforms were at the last finish (new instances: their own)

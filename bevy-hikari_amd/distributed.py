@@ -496,6 +496,12 @@ class MultiEngine:
         built once, on band 0's device, and written back into `builder`."""
         self.api.call("multi_add_meshes", self.h, builder.h, mode)
 
+    def remove_meshes(self, extents):
+        """hk_multi_remove_meshes: the meshes whose extents SceneBuilder.remove_mesh returned leave every band's device scene."""
+        extents = list(extents)
+        arr = (F.HkMeshExtent * max(1, len(extents)))(*extents)
+        self.api.call("multi_remove_meshes", self.h, arr, len(extents))
+
     def upload_noise(self, noise=None):
         for e in self.contexts:
             e.upload_noise(noise)

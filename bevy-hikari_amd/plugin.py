@@ -441,6 +441,20 @@ class SceneBuilder:
         self.api.call("scene_builder_mesh_index", self.h, mesh_id, C.byref(out))
         return out
 
+    def mesh_extent(self, mesh_id):
+        """The HkMeshExtent of a mesh: its three ranges in the arrays of the LAST finish (node_count 0: no finish has seen it)."""
+        out = F.HkMeshExtent()
+        self.api.call("scene_builder_mesh_extent", self.h, mesh_id, C.byref(out))
+        return out
+
+    def remove_mesh(self, mesh_id):
+        """Take a mesh no instance names out of the builder (ids of later meshes shift down by one, the instance declarations follow).
+        Returns its HkMeshExtent in the coordinates of the last finish - what Engine.remove_meshes takes, for every removal until the
+        next finish() in one call."""
+        out = F.HkMeshExtent()
+        self.api.call("scene_builder_remove_mesh", self.h, mesh_id, C.byref(out))
+        return out
+
     def finish(self, build_trees=True):
         """hk_scene_builder_finish; build_trees=False: hk_scene_builder_finish_instances (stand-in trees, for a device-side build)."""
         self.api.call("scene_builder_finish" if build_trees else "scene_builder_finish_instances", self.h)
@@ -797,6 +811,28 @@ class Engine:
         out = (F.u32 * 5)()
         self.api.call("debug_last_add", self.ctx, out)
         return tuple(int(v) for v in out)
+
+    def remove_meshes(self, extents):
+        """hk_remove_meshes: the meshes whose extents SceneBuilder.remove_mesh returned since the builder's last finish leave the device
+        scene - the mesh level is compacted into a new, smaller allocation in one launch, behind the frames in flight, and the instance
+        records are rebased.  Their instances must be gone already (update_instances_on_device).  Survivors are named by their new
+        records afterwards (SceneBuilder.mesh_index after the finish, or rebase_mesh_index)."""
+        extents = list(extents)
+        arr = (F.HkMeshExtent * max(1, len(extents)))(*extents)
+        self.api.call("remove_meshes", self.ctx, arr, len(extents))
+
+    def last_remove(self):
+        """(meshes removed, their triangles, kernel launches, runs per plane, path: 0 device compaction / 1 full layout, bytes moved) of
+        the last remove_meshes (test hook)."""
+        out = (C.c_uint64 * 6)()
+        self.api.call("debug_last_remove", self.ctx, out)
+        return tuple(int(v) for v in out)
+
+    def last_remove_ms(self):
+        """ms of the compaction launch of the last remove_meshes between two HIP events (measurement hook; waits for it)."""
+        out = F.f32()
+        self.api.call("debug_last_remove_ms", self.ctx, C.byref(out))
+        return float(out.value)
 
     def last_add_times(self):
         """ms of the last add_meshes: (allocations of a relocation, its copy launch and switch, growth of the mirrors, staging + build +
@@ -1561,6 +1597,10 @@ class HikariPlugin:
     def add_meshes(self, builder, mode=F.TREE_SAH):
         """Meshes added to the loaded builder since (glTF assets that arrive frame by frame): appended on the device (Engine.add_meshes)."""
         self.engine.add_meshes(builder, mode)
+
+    def remove_meshes(self, extents):
+        """Meshes that left the builder (SceneBuilder.remove_mesh): the device scene is compacted (Engine.remove_meshes)."""
+        self.engine.remove_meshes(extents)
 
     def deform_meshes(self, items, producer_stream=None):
         """Per frame, every deforming mesh of the scene in one call: Engine.deform_meshes."""

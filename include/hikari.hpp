@@ -306,6 +306,13 @@ class SceneBuilder {  // the Prepare-stage host work: mesh -> BLAS, TLAS, emissi
   // new values for an existing material (`materials.get_mut(handle)`): the next finish() redoes the instance-level work only;
   // HikariPlugin::update_materials is the device path of the same edit
   void set_material(uint32_t material, const HkMaterial& m) { check(hk_scene_builder_set_material(h_, material, &m), "hk_scene_builder_set_material"); }
+  // a mesh no instance names leaves the builder (ids of later meshes shift down by one); the extent, in the coordinates of the last
+  // finish, is what remove_meshes of a context takes - every removal until the next finish() in one call
+  HkMeshExtent remove_mesh(uint32_t mesh) {
+    HkMeshExtent e{};
+    check(hk_scene_builder_remove_mesh(h_, mesh, &e), "hk_scene_builder_remove_mesh");
+    return e;
+  }
   void finish() { check(hk_scene_builder_finish(h_), "hk_scene_builder_finish"); }
   const hk_scene_builder* handle() const { return h_; }
   hk_scene_builder* handle() { return h_; }
@@ -321,6 +328,8 @@ class Context {
   void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_load_scene(c_, b.handle(), tree_mode), "hk_load_scene"); }
   // meshes added to the loaded, finished builder since: appended to the device scene without laying it out again (hk_add_meshes)
   void add_meshes(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_add_meshes(c_, b.handle(), tree_mode), "hk_add_meshes"); }
+  // meshes that left the builder (SceneBuilder::remove_mesh): the device scene's mesh level compacted behind the frames in flight (hk_remove_meshes)
+  void remove_meshes(const std::vector<HkMeshExtent>& removed) { check(hk_remove_meshes(c_, removed.data(), (uint32_t)removed.size()), "hk_remove_meshes"); }
   ~Context() { hk_destroy(c_); }
   Context(const Context&) = delete;
   Context& operator=(const Context&) = delete;
@@ -413,6 +422,7 @@ class HikariPlugin {
   Context& context() { return ctx_; }
   void set_scene(const SceneBuilder& b) { check(hk_upload_scene(ctx_.get(), b.handle()), "hk_upload_scene"); }
   void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { ctx_.load_scene(b, tree_mode); }  // ... with deferred meshes: trees built on the device
+  void remove_meshes(const std::vector<HkMeshExtent>& removed) { ctx_.remove_meshes(removed); }  // meshes that leave: compacted on the device
   void add_meshes(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { ctx_.add_meshes(b, tree_mode); }  // meshes that arrive later: appended on the device
   // after SceneBuilder::set_instance_transform + finish: rewrite the instance-level device arrays only
   void update_instances(const SceneBuilder& b) { check(hk_upload_scene_instances(ctx_.get(), b.handle()), "hk_upload_scene_instances"); }
@@ -540,6 +550,7 @@ class HikariMultiGpuPlugin {
   void set_scene(const SceneBuilder& b) { check(hk_multi_upload_scene(m_, b.handle()), "hk_multi_upload_scene"); }
   void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_multi_load_scene(m_, b.handle(), tree_mode), "hk_multi_load_scene"); }
   void add_meshes(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_multi_add_meshes(m_, b.handle(), tree_mode), "hk_multi_add_meshes"); }
+  void remove_meshes(const std::vector<HkMeshExtent>& removed) { check(hk_multi_remove_meshes(m_, removed.data(), (uint32_t)removed.size()), "hk_multi_remove_meshes"); }
   void update_instances(const SceneBuilder& b) { check(hk_multi_upload_scene_instances(m_, b.handle()), "hk_multi_upload_scene_instances"); }
   uint32_t refit_instances(SceneBuilder& b) {
     uint32_t moved = 0;

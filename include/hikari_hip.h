@@ -91,6 +91,13 @@ typedef struct HkMeshIndex {
   uint32_t node_offset;
   uint32_t node_count;
 } HkMeshIndex;
+/* A mesh's three ranges in the concatenated arrays of the builder's LAST finish (hk_scene_builder_remove_mesh, hk_remove_meshes), 24 B.
+ * n_primitives is the triangle count, node_count = 3 n_primitives - 2; node_count 0: a mesh no finish has seen (it lies in no array). */
+typedef struct HkMeshExtent {
+  uint32_t vertex, n_vertices;
+  uint32_t primitive, n_primitives;
+  uint32_t node_offset, node_count;
+} HkMeshExtent;
 
 /* mesh_material_types.wgsl:25-33, mod.rs:147-156 (GpuInstance), 176 B. Matrices column-major. */
 typedef struct HkInstance {
@@ -536,6 +543,19 @@ int hk_scene_builder_pending_mesh_trees(const hk_scene_builder* b, uint32_t* cou
 int hk_scene_builder_build_pending_mesh_trees(hk_scene_builder* b);
 /* the HkMeshIndex of a mesh after a finish (what its instances carry, and what the hk_*_mesh_* calls take) */
 int hk_scene_builder_mesh_index(const hk_scene_builder* b, uint32_t mesh_id, HkMeshIndex* out);
+/* Meshes that leave (the twin of hk_scene_builder_remove_instance).  hk_scene_builder_mesh_extent: the mesh's ranges in the arrays of the
+ * last finish - also the layout of a context that has taken all of the builder's meshes; node_count 0 for a mesh no finish has seen.
+ * hk_scene_builder_remove_mesh: the ids of the meshes added after the removed one shift down by one, the mesh ids of the instance
+ * declarations with them; a deferred mesh takes its mark along.  The mesh level is un-finished: the next finish concatenates again from
+ * the removed mesh on, what lies in front of it keeps its bytes, and the builder then holds, getter for getter, what a builder that never
+ * had the mesh holds.  `removed` (or NULL) receives the extent in the coordinates of the last finish - they stay in those coordinates
+ * for every removal until the next finish, which is what hk_remove_meshes takes in one call.  HK_E_INVALID with the builder unchanged
+ * (still finished if it was) for NULL, an unknown id, and a mesh an instance declaration still names. */
+int hk_scene_builder_mesh_extent(const hk_scene_builder* b, uint32_t mesh_id, HkMeshExtent* out);
+int hk_scene_builder_remove_mesh(hk_scene_builder* b, uint32_t mesh_id, HkMeshExtent* removed);
+/* Pure host logic, no context: the record `index` as it reads once removed[0..n) are gone - each of vertex, primitive and node_offset
+ * minus the number of removed elements in front of it (an extent that surrounds the value counts up to the value); node_count is kept. */
+int hk_rebase_mesh_index(const HkMeshExtent* removed, uint32_t n, const HkMeshIndex* index, HkMeshIndex* out);
 
 /* The layout conversion behind HK_CTX_EXACT_TRAVERSAL's opposite (see there): `nodes[0..count)` is ONE flat BVH in the `bvh`
  * 0.7.1 flatten_custom layout the reference produces (mod.rs:185-201,458-459; entry / exit indices local to the array);
@@ -853,6 +873,30 @@ int hk_load_scene(hk_ctx* ctx, hk_scene_builder* b, uint32_t tree_mode);
  * pointers are switched leaves the scene the context had; one after it leaves the context WITHOUT a scene, never with stand-in trees.
  * HkStats: scene_mesh_builds does not move, scene_device_tree_builds counts the meshes built. */
 int hk_add_meshes(hk_ctx* ctx, hk_scene_builder* b, uint32_t tree_mode);
+/* Meshes removed from the loaded scene: the mesh-level region compacted on the device (scene_remove.hip; DESIGN 3 "Meshes that leave").
+ * removed[0..n) are the extents hk_scene_builder_remove_mesh returned since the builder's last finish - all in the context's CURRENT
+ * layout, so one call per builder finish, in order; entries with node_count 0 are skipped, and with nothing left to do the call returns
+ * HK_OK with nothing enqueued.  The host removes the instances of those meshes first (hk_update_scene_instances).  Calls after the
+ * removal name the survivors by their new records (hk_scene_builder_mesh_index after the finish, or hk_rebase_mesh_index).
+ * A scene with two slots of the instance-level region whose ordering count stays what it is: the scene moves, behind every stream and
+ * without a host wait, to a NEW allocation whose capacities follow the survivors (1.5 times what is needed) - ONE compaction launch
+ * however many meshes go moves the surviving runs of every node plane, the triangle and vertex planes and the wide records and ranks,
+ * a small launch beside it copies the instance-level slot and rebases the three mesh offsets of every instance record, and one in front
+ * of both copies the plan (planes and run lists) from pinned to device memory.  Frames in
+ * flight go on reading the old allocation, which is freed behind an event; skins, morph sets, deformed vertices, rebuilt trees and wide
+ * records of the survivors stay as they are, those of the removed meshes are freed behind the same event.  Accepted in every state
+ * hk_add_meshes is accepted in (mirrors stale or fresh); a pending propagate of deformed boxes goes first.
+ * A scene walked from the LDS copy (one slot), or a removal that changes the ordering count: the mirrors are compacted and the scene is
+ * laid out again on the host; HK_E_NOT_READY with NOTHING changed when the mirrors are stale or a mesh was deformed, as any re-layout.
+ * Afterwards the context holds, byte for byte, what hk_upload_scene of a twin builder that never had the meshes leaves (given the same
+ * device-side edits).  Everything is validated before anything is written or enqueued; the failing entry's index is in hk_last_error().
+ * HK_E_INVALID: NULL with n > 0; an extent beyond the mirrors; n_primitives 0 or node_count != 3 n_primitives - 2; two extents that
+ * overlap in a range or are ordered differently in the three ranges; an uploaded instance whose mesh lies inside an extent; an extent
+ * that cuts a mesh the context knows (an instance's record, a deformable mesh, a mesh with wide records) partly; extents that would leave
+ * the scene without a mesh (a scene holds at least one: load another scene instead).  HK_E_NOT_READY: no
+ * scene.  A HIP failure before the scene pointers are switched leaves the scene intact, one after it leaves the context WITHOUT a scene.
+ * HkStats: scene_mesh_builds does not move on the device path. */
+int hk_remove_meshes(hk_ctx* ctx, const HkMeshExtent* removed, uint32_t n);
 int hk_upload_textures(hk_ctx* ctx, const HkImageDesc* images, uint32_t n_images);
 /* New texels and sampler fields for ONE uploaded texture of the same width and height (an animated texture; hk_upload_textures replaces
  * the whole array behind a host wait).  The texels go through the pinned staging pool of the deformations and land in place in the
@@ -1261,6 +1305,8 @@ int hk_multi_load_scene(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode);
 /* hk_add_meshes for every band: deferred trees are built once (on band 0's device) and written back, the other bands take the finished
  * builder's new ranges */
 int hk_multi_add_meshes(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode);
+/* hk_remove_meshes on every band's context (each validates before it writes; the bands hold the same scene, so they agree) */
+int hk_multi_remove_meshes(hk_multi* m, const HkMeshExtent* removed, uint32_t n);
 int hk_multi_upload_scene_instances(hk_multi* m, const hk_scene_builder* b);
 int hk_multi_refit_scene_instances(hk_multi* m, hk_scene_builder* b, uint32_t* moved); /* hk_refit_scene_instances on every band's replica */
 int hk_multi_rebuild_scene_trees(hk_multi* m, uint32_t mode);

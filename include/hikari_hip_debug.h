@@ -30,6 +30,14 @@ int hk_debug_last_add(hk_ctx* ctx, uint32_t out[5]);
  * relocation (the larger scene, wide records, events), out[1] its copy launch and the switch of the scene pointers, out[2] the growth of
  * the context's mirrors, out[3] staging, host layout, the device build with its wait and the read-back.  Zero where a step did not run. */
 int hk_debug_last_add_times(hk_ctx* ctx, double out[4]);
+/* Test hook: what the last hk_remove_meshes of this context did - out[0] meshes removed, out[1] their triangles, out[2] what the call enqueued,
+ * counted where it is enqueued: kernel launches (the propagate of deformed boxes that goes first included) and the fill of the new rank
+ * plane (it does not follow the number of meshes), out[3] the runs per plane (the surviving intervals), out[4] the path (0 the device
+ * compaction, 1 the full layout on the host), out[5] the bytes the compaction launch moved.  All zero after a call with nothing to do. */
+int hk_debug_last_remove(hk_ctx* ctx, uint64_t out[6]);
+/* Measurement hook (tools/remove_mesh_probe.py): ms between two HIP events around the compaction launch of the last hk_remove_meshes
+ * (waits for the launch; 0 for a call that took the full layout or had nothing to do) */
+int hk_debug_last_remove_ms(hk_ctx* ctx, float* ms);
 /* Measurement hook (tools/load_probe.py): where the host time of the last hk_load_scene went, in ms - out[0] host completion of meshes
  * beyond the device limit, out[1] the copy into the context's mirrors, out[2] layout of both regions and their upload, out[3] the device
  * build from its first launch to the end of the stream, out[4] the read-back, its unfolding and the write-back into the builder. */

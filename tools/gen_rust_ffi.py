@@ -20,6 +20,9 @@ OUT = os.path.join(ROOT, "rust", "hikari-hip-sys", "src", "lib.rs")
 
 SCALARS = {"uint8_t": ("u8", 1), "uint16_t": ("u16", 2), "uint32_t": ("u32", 4), "uint64_t": ("u64", 8), "int32_t": ("i32", 4), "int": ("i32", 4),
            "float": ("f32", 4), "double": ("f64", 8), "size_t": ("usize", 8), "char": ("c_char", 1)}
+RUST_KEYWORDS = frozenset("as async await break const continue crate dyn else enum extern false fn for if impl in let loop match mod move mut pub ref return self Self "
+                          "static struct super trait true type unsafe use where while abstract become box do final macro override priv try typeof unsized virtual "
+                          "yield".split())
 OPAQUE = {"hk_ctx": "HkCtx", "hk_scene_builder": "HkSceneBuilder", "hk_multi": "HkMulti"}
 
 
@@ -198,6 +201,7 @@ def emit(api):
         w("#[derive(Clone, Copy, Debug)]")
         w(f"pub struct {name} {{")
         for fname, ctype, dims in fields:
+            assert fname not in RUST_KEYWORDS, f"{name}: the field name `{fname}` is a Rust keyword"
             w(f"    pub {fname}: {rust_type(ctype, dims=dims)},")
         w("}")
         w(f"const _: () = assert!(core::mem::size_of::<{name}>() == {lay[name][0]});")
@@ -208,6 +212,8 @@ def emit(api):
     for fname, ret, params in api["functions"]:
         ps = []
         for pname, ctype, is_const, ptr, is_array in params:
+            # (parameter names are not ABI: a name that is a Rust keyword is renamed in the header, not escaped here)
+            assert pname not in RUST_KEYWORDS, f"{fname}: the parameter name `{pname}` is a Rust keyword - rename it in the header"
             ps.append(f"{pname}: {rust_type(ctype, is_const, ptr + (1 if is_array else 0))}")
         if ret == "void":
             r = ""
