@@ -155,10 +155,17 @@ int layout_host_trees(const hk_ctx* c, const std::vector<LoadMesh>& meshes, uint
   return HK_OK;
 }
 
+// hk_debug_last_add / hk_debug_last_add_times start from zero once a call can no longer be refused
+void clear_add_report(hk_ctx* c) {
+  for (uint32_t& v : c->last_add) v = 0u;
+  for (double& v : c->last_add_ms) v = 0.0;
+}
+
 // what hk_load_scene does for the whole builder: scenes walked from the LDS copy, and additions that change the ordering count
 int full_layout(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode, uint32_t host_built) {
   HK_REQUIRE(!c->mirrors_stale && !c->meshes_deformed, HK_E_NOT_READY,
              "the scene was last changed on the device and this addition lays it out again on the host: upload the host's mirror first (hk_upload_scene)");
+  clear_add_report(c);
   int rc = hk_load_scene(c, b, tree_mode);
   if (!rc) rc = finalize_scene(c);
   if (rc) return rc;
@@ -223,9 +230,11 @@ int hk_add_meshes(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode) {
                  in.mesh.node_count);
     }
   }
-  for (uint32_t& v : c->last_add) v = 0u;
-  for (double& v : c->last_add_ms) v = 0.0;
-  if (first_new == n_meshes) return HK_OK;  // nothing new: nothing is enqueued
+  // (the report of the last add is cleared behind the last refusal - HK_E_NOT_READY, nothing written - as hk_remove_meshes clears its own)
+  if (first_new == n_meshes) {  // nothing new: nothing is enqueued
+    clear_add_report(c);
+    return HK_OK;
+  }
   HK_HIP(hipSetDevice(c->device));
   uint32_t n_host_built = 0;
   for (uint32_t id = first_new; id < n_meshes; ++id) n_host_built += builder_pending_mesh(b, id, nullptr) ? 0u : 1u;
@@ -233,6 +242,7 @@ int hk_add_meshes(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode) {
   if ((rc = finalize_scene(c))) return rc;
   const Sizes now{nn, np, nv};
   if (!c->two_slots || wants_threaded(c, now.nodes, now.prims, now.verts) != c->threaded) return full_layout(c, b, tree_mode, n_host_built);
+  clear_add_report(c);
 
   // ---- the device append.  Deferred meshes beyond the device limit are completed by the host's builder first
   std::vector<LoadMesh> device, host;

@@ -162,8 +162,11 @@ int hk_remove_meshes(hk_ctx* c, const HkMeshExtent* removed, uint32_t n) {
   uint64_t tris_removed = 0;
   for (const Entry& x : ext) tris_removed += x.e.n_primitives;
   // ---- every check of the arguments has passed (a refusal above leaves the report of the last removal as it was)
-  for (uint64_t& v : c->last_remove) v = 0;
-  c->rm_timed = false;
+  // (... and so does the refusal of the full layout below: the report is cleared behind the last refusal)
+  auto clear_report = [&] {
+    for (uint64_t& v : c->last_remove) v = 0;
+    c->rm_timed = false;
+  };
 
   HK_HIP(hipSetDevice(c->device));
   int rc;
@@ -174,6 +177,7 @@ int hk_remove_meshes(hk_ctx* c, const HkMeshExtent* removed, uint32_t n) {
     // ---- the full layout: scenes walked from the LDS copy, removals that change the ordering count (and a scene not laid out yet)
     HK_REQUIRE(!c->mirrors_stale && !c->meshes_deformed, HK_E_NOT_READY,
                "the scene was last changed on the device and this removal lays it out again on the host: upload the host's mirror first (hk_upload_scene)");
+    clear_report();
     if ((rc = sync_all(c))) return rc;  // (the deformable meshes that go are freed at once; the layout below waits anyway)
     compact_host_state(c, gone, runs, freed);
     for (void* q : freed) (void)hipFree(q);
@@ -186,6 +190,7 @@ int hk_remove_meshes(hk_ctx* c, const HkMeshExtent* removed, uint32_t n) {
   }
 
   // ---- the device compaction
+  clear_report();
   uint64_t enqueued = 0;  // kernel launches and fills, counted where they are enqueued (hk_debug_last_remove)
   const bool propagate = c->deform_pending;
   if ((rc = flush_deform(c))) return rc;  // (a pending propagate of deformed boxes names the old records: it goes first, in stream order)

@@ -453,6 +453,7 @@ class SceneBuilder:
         next finish() in one call."""
         out = F.HkMeshExtent()
         self.api.call("scene_builder_remove_mesh", self.h, mesh_id, C.byref(out))
+        del self.mesh_vertices[mesh_id]   # (the ids behind it shift down: set_mesh_vertices checks its arrays against this list)
         return out
 
     def finish(self, build_trees=True):
@@ -1647,6 +1648,18 @@ class HikariPlugin:
             self.engine.frame_render(frame, view, pview, lights, settings.to_c(), F.FRAME_ANTIALIAS if antialias else 0)
         self._previous_camera = camera
         return n
+
+    def reset_history(self):
+        """The next frame starts from an empty temporal history, as a new camera's first frame does: every screen buffer is reallocated and
+        zeroed (a resize away and back, behind a wait for the frames in flight; prepare_light_textures, light.rs:342-363) and the previous
+        camera is forgotten.  The scene stays."""
+        self._previous_camera = None
+        if self._size is None:   # (no frame yet: the first one allocates)
+            return
+        w, h, ratio = self._size
+        self.engine.wait()
+        self.engine.resize(w + 8, h + 8, ratio)
+        self.engine.resize(w, h, ratio)
 
     def present(self, settings: HikariSettings, *, antialias, **kwargs):
         """OverlayNode::run: the frame last rendered into a view target in device memory (Engine.present)."""
