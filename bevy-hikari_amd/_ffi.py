@@ -50,6 +50,7 @@ DEBUG_OPT_SPATIAL_WINDOW, DEBUG_OPT_FRAME_PIPELINE, DEBUG_OPT_WF_TIMELINE, DEBUG
 DEBUG_OPT_MAIN_PRIORITY, DEBUG_OPT_PREPASS_PIPELINE, DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP = 9, 10, 11  # (6, 7 and 8 are retired)
 DEBUG_OPT_LOAD_DEVICE_LIMIT = 12
 DEBUG_OPT_KNOWN_RESULTS = 13
+DEBUG_OPT_SPATIAL_KNOWN = 14
 TIMING_TRACE_STAGES = 18  # hk_set_timing_mask bit / HkStats slot: every trace launch of the queue-based indirect pass
 TRAVERSAL_WIDE = 0x100
 FRAME_EXTERNAL_GBUFFER, FRAME_ANTIALIAS, FRAME_BALANCE_BANDS, FRAME_GATHER, FRAME_TIME_BAND = 1, 2, 4, 8, 16
@@ -269,6 +270,7 @@ _DEBUG = {
     "debug_comm_lanes": [_vp, P(u32)],
     "debug_multi_serial": [C.c_int],
     "debug_spatial_windowed_launches": [_vp, P(C.c_uint64)],
+    "debug_spatial_known_launches": [_vp, P(C.c_uint64)],
     "debug_empty_tiles": [_vp, P(C.c_uint8), C.c_size_t, P(C.c_uint64)],
     "debug_main_stream_priority": [_vp, P(u32)],
     "measure_hbm": [_vp, C.c_size_t, u32, P(C.c_double), P(C.c_double)],

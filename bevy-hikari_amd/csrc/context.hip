@@ -534,6 +534,27 @@ int attach_tile_meta(hk_ctx* c, LightTargets& t, int channel, bool spatial_pass,
   return HK_OK;
 }
 
+// The table of the background's known records for a spatial launch (hk_kernels.hpp SpatialKnown), or nullptr with the switch off.  Made
+// once per context, before its first spatial launch: filled on the context's stream, and waited for there - later launches may run on
+// another of the context's streams, which nothing orders behind this one.
+int spatial_known_table(hk_ctx* c, const hkd::SpatialKnown** out) {
+  *out = nullptr;
+  if (!c->spatial_known_on) return HK_OK;
+  if (!c->spatial_known) {
+    hkd::SpatialKnown* table = nullptr;
+    HK_HIP(hipMalloc((void**)&table, sizeof(hkd::SpatialKnown)));
+    launch_spatial_known_fill(c->stream, table);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+      (void)hipFree(table);
+      HK_REQUIRE(false, HK_E_HIP, "the table of known records was not filled: %s", hipGetErrorString(e));
+    }
+    c->spatial_known = table;
+  }
+  *out = c->spatial_known;
+  return HK_OK;
+}
+
 int ready(hk_ctx* c) {
   HK_REQUIRE(c, HK_E_INVALID, "ctx is NULL");
   HK_REQUIRE(c->W > 0, HK_E_NOT_READY, "hk_resize has not been called");
@@ -988,8 +1009,11 @@ int run_pass(hk_ctx* c, uint32_t pass, uint32_t arg, int y0, int y1) {
       const int channel = pass == HK_PASS_EMISSIVE_SPATIAL_REUSE ? 1 : 2;
       LightTargets t = make_light_targets(c, channel);
       { const int rc_ = attach_tile_meta(c, t, channel, true, y0, y1); if (rc_) return rc_; }
-      if (launch_spatial(c->stream, channel == 1, c->scene, fr, g, t, y0, y1, c->spatial_window, timer.on ? timer.t.start : nullptr, timer.on ? timer.t.stop : nullptr))
+      const hkd::SpatialKnown* known = nullptr;
+      { const int rc_ = spatial_known_table(c, &known); if (rc_) return rc_; }
+      if (launch_spatial(c->stream, channel == 1, c->scene, fr, g, t, y0, y1, c->spatial_window, known, timer.on ? timer.t.start : nullptr, timer.on ? timer.t.stop : nullptr))
         c->spatial_windowed_launches += 1;
+      if (known && y1 > y0) c->spatial_known_launches += 1;
       break;
     }
     case HK_PASS_DEMODULATION: {
@@ -1192,6 +1216,7 @@ void hk_destroy(hk_ctx* c) {
     if (e) (void)hipEventDestroy(e);
   c->d_noise.release();
   if (c->d_counters) (void)hipFree(c->d_counters);
+  if (c->spatial_known) (void)hipFree(c->spatial_known);
   if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
   if (c->post_stream) (void)hipStreamDestroy(c->post_stream);
   if (c->post_fork) (void)hipEventDestroy(c->post_fork);
@@ -1238,6 +1263,7 @@ int hk_debug_set_option(hk_ctx* c, uint32_t option, int64_t value) {
     case HK_DEBUG_OPT_LOAD_DEVICE_LIMIT: c->load_device_limit = value <= 0 ? HK_MESH_REBUILD_MAX_TRIANGLES : (uint32_t)std::min<int64_t>(value, HK_MESH_REBUILD_MAX_TRIANGLES); break;
     case HK_DEBUG_OPT_PREPASS_PIPELINE: c->prepass_pipeline = value < 0 ? -1 : (value ? 1 : 0); break;
     case HK_DEBUG_OPT_KNOWN_RESULTS: c->known_results = value != 0; forget_empty_tiles(c); break;
+    case HK_DEBUG_OPT_SPATIAL_KNOWN: c->spatial_known_on = value != 0; break;
     case HK_DEBUG_OPT_MAIN_PRIORITY: c->main_priority = value < 0 ? -1 : (value ? 1 : 0); return pick_main_stream(c, true);
     default: HK_REQUIRE(false, HK_E_INVALID, "unknown option %u", option);
   }
@@ -1263,6 +1289,12 @@ int hk_debug_empty_tiles(hk_ctx* c, uint8_t* out_bytes, size_t n, uint64_t* laun
 int hk_debug_spatial_windowed_launches(hk_ctx* c, uint64_t* out) {
   HK_REQUIRE(c && out, HK_E_INVALID, "bad argument");
   *out = c->spatial_windowed_launches;
+  return HK_OK;
+}
+
+int hk_debug_spatial_known_launches(hk_ctx* c, uint64_t* out) {
+  HK_REQUIRE(c && out, HK_E_INVALID, "bad argument");
+  *out = c->spatial_known_launches;
   return HK_OK;
 }
 

@@ -168,6 +168,11 @@ struct hk_ctx {
   // test / measurement switches (hikari_hip_debug.h hk_debug_set_option; the library reads no environment variable)
   int spatial_window = -1;               // which form of k_spatial_reuse a launch takes: -1 by its size, 0 plain, 1 windowed (kernels.hip launch_spatial)
   uint64_t spatial_windowed_launches = 0;
+  // the background's known records for the spatial passes (hk_kernels.hpp SpatialKnown): made before the context's first spatial launch
+  // (context.hip spatial_known_table), handed to every spatial launch while the switch is on
+  bool spatial_known_on = true;          // HK_DEBUG_OPT_SPATIAL_KNOWN
+  hkd::SpatialKnown* spatial_known = nullptr;
+  uint64_t spatial_known_launches = 0;   // spatial launches that were handed the table
   bool frame_pipeline = true;            // the a-trous levels of frame n beside frame n + 1's light passes (post_stream)
   bool wf_timeline = false;              // the instrumented twin of the trace kernels (tools/wf_timeline.py)
   bool flat_walk = true;                 // the one-level tree for scenes under one transform (scene_layout.hip)

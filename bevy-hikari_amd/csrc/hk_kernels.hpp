@@ -80,6 +80,19 @@ struct LightTargets {
   int rw;           // render width (reservoir index = x + rw * y)
   int slots;        // rw * rh: entries the passes index of every reservoir buffer, and of every parked-store plane (hk_light.hpp previous_slot lets no store land beyond)
 };
+// The background's known records (kernels.hip k_spatial_known_fill / k_spatial_reuse; DESIGN 4 "Empty tiles").  spatial_reuse's
+// background branch stores pack(unpack(its input)); of the two records the temporal passes store to a background pixel - entry 0:
+// pack(zero_reservoir()), k_indirect's; entry 1: the pack of set_reservoir(zero, zero_sample, 0), k_direct_lit's - that re-pack is a
+// constant, computed once per context by a one-wave kernel with the very functions the long way uses.  A wave whose input tile record
+// names one of the two input ids stores `output` and marks its tile with `output_id`: no load, no unpack, no pack, no hash.
+// Read-only to every kernel but the one that fills it.
+struct SpatialKnownEntry {
+  PackedReservoir output;
+  unsigned long long input_id, output_id;
+};
+struct SpatialKnown {
+  SpatialKnownEntry e[2];
+};
 // The queue-based schedule of indirect_lit_ambient (kernels_wavefront.hip): what a path carries from stage to stage, in
 // planes indexed by path slot, plus the ray queues and their counters.  `cap` = the most paths one dispatch can have
 // (the pixels of the render image).
@@ -573,9 +586,12 @@ void launch_mesh_triangles(hipStream_t st, const float4* pos, float4* v0, float4
 // the triangle boxes alone, from the triangle planes as they are (a mesh rebuilt before its first deformation)
 void launch_mesh_triangle_boxes(hipStream_t st, const float4* v0, const float4* v1, const float4* v2, uint32_t n_tris, float4* tri_lo, float4* tri_hi);
 // windowed: 0 the plain form, 1 the windowed form (depth window + tap lists in LDS: kernels.hip), -1 by the size of the launch; returns
-// whether the windowed form was launched
+// whether the windowed form was launched.  known: the table of the background's known records (launch_spatial_known_fill), or nullptr -
+// the launch then takes the long way for every background tile, and its windowed form is handed no empty-tile / kept-tile plane
+// (HK_DEBUG_OPT_SPATIAL_KNOWN 0: the A/B arm)
 bool launch_spatial(hipStream_t st, bool emissive_lit, const hkd::DScene& sc, const hkd::DFrame& fr, const hkd::GBuffer& g, const hkd::LightTargets& t,
-                    int y0, int y1, int windowed, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);  // (events attached to the dispatch: HkStats timing)
+                    int y0, int y1, int windowed, const hkd::SpatialKnown* known, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);  // (events attached to the dispatch: HkStats timing)
+void launch_spatial_known_fill(hipStream_t st, hkd::SpatialKnown* table);  // one wave; the table is complete once `st` has run it
 void launch_derive_planes(hipStream_t st, const hkd::GBuffer& g, float* depth_plane, void* dn_g, int width, int y0, int y1);
 void launch_count_geometry_rows(hipStream_t st, const float* depth, int width, int height, uint32_t* out);
 void launch_demodulation(hipStream_t st, int nch, const hkd::DFrame& fr, const hkd::DemodTargets& d, int y0, int y1);

@@ -779,11 +779,30 @@ HKD uint32_t spatial_tap_merge(const ShadingSite& site, const Sample& s, Reservo
   }
   return 0u;
 }
+// The table of the background's known records (hk_kernels.hpp SpatialKnown), in two launches of one wave so that the re-pack is computed
+// on what a LOAD returned, as in k_spatial_reuse's long way, and not folded by the compiler: phase 0 parks the two input records in the
+// entries' `output`, phase 1 loads them back and writes the input id, the re-pack and its id.  Lane k owns entry k; plain vector stores.
+__global__ __launch_bounds__(64) void k_spatial_known_fill(SpatialKnown* table, int phase) {
+  const int k = (int)threadIdx.x;
+  if (k >= 2) return;
+  if (phase == 0) {
+    Reservoir r = zero_reservoir();                     // entry 0: what k_indirect stores to a background pixel
+    if (k == 1) set_reservoir(r, zero_sample(), 0.0f);  // entry 1: what k_direct_lit stores
+    store_packed(&table->e[k].output, 0, pack_reservoir(r));
+    return;
+  }
+  const PackedReservoir in = load_packed(&table->e[k].output, 0);
+  const PackedReservoir out = pack_reservoir(unpack_reservoir(in));
+  store_packed(&table->e[k].output, 0, out);
+  table->e[k].input_id = record_id(in);
+  table->e[k].output_id = record_id(out);
+}
 #ifndef HK_SPATIAL_WGS
 #define HK_SPATIAL_WGS 4  // workgroups per CU = waves per SIMD: 128 VGPRs (5 -> 102 VGPRs spills: measured slower)
 #endif
 template <bool EMISSIVE_LIT, bool WINDOWED>
-__global__ __launch_bounds__(256, HK_SPATIAL_WGS) void k_spatial_reuse(DScene sc, DFrame fr, GBuffer g, LightTargets t, SpatialTaps taps, int row_begin, int row_end) {
+__global__ __launch_bounds__(256, HK_SPATIAL_WGS) void k_spatial_reuse(DScene sc, DFrame fr, GBuffer g, LightTargets t, SpatialTaps taps, const SpatialKnown* __restrict__ known,
+                                                                       int row_begin, int row_end) {
   const Pixel px = pixel_of_thread<false>(fr.rw, row_begin, row_end);
   if (!WINDOWED && !px.valid) return;  // (the windowed form has a workgroup barrier ahead: its invalid lanes leave after it)
   constexpr uint32_t SPATIAL_REUSE_COUNT = EMISSIVE_LIT ? 8u : 16u;
@@ -792,8 +811,11 @@ __global__ __launch_bounds__(256, HK_SPATIAL_WGS) void k_spatial_reuse(DScene sc
   f2 uv = F2(0.0f, 0.0f);
   int dcx = 0, dcy = 0;
   float4 position_depth = make_float4(0, 0, 0, 0);
-  // (a tile the primary rays proved empty, as in k_direct_lit; the plain form only - every lane here is a valid pixel of the wave's tile)
-  const int tile_state = WINDOWED ? 0 : wave_tile_state(g.empty_in, px, g.tiles_x);
+  // (a tile the primary rays proved empty, as in k_direct_lit.  In the plain form every lane here is a valid pixel of the wave's tile.  In
+  // the windowed form the lanes beyond the image edge are still here: the tile is the same arithmetic in every lane, valid or not
+  // (wave_tile), but a wave with NO valid lane owns no tile - its tile index lies beyond the plane's row - and reads no byte)
+  int tile_state = 0;
+  if (!WINDOWED || __ballot(px.valid) != 0ull) tile_state = wave_tile_state(g.empty_in, px, g.tiles_x);
   if (!tile_state) {
     uv = coords_to_uv(fr, x, y);
     jittered_deferred_coords(fr, uv, &dcx, &dcy);
@@ -837,6 +859,20 @@ __global__ __launch_bounds__(256, HK_SPATIAL_WGS) void k_spatial_reuse(DScene sc
       if (have.valid > have.poison && have.src == input_id) {
         if (!tile_kept) t.render[index] = make_uint2(0u, 0u);
         return;
+      }
+      // the short way: the tile record names one of the background's two known records (hk_kernels.hpp SpatialKnown), whose re-pack and
+      // its id are in the table - nothing to load from `current`, to unpack, to pack or to hash.  (The id is the same in every lane: all
+      // of them read one tile record.)  Any other id takes the long way below.
+      if (known && input_id != 0ull) {
+        const unsigned long long uid = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(input_id >> 32)) << 32) |
+                                       (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)input_id);
+        const int k = uid == known->e[0].input_id ? 0 : (uid == known->e[1].input_id ? 1 : -1);
+        if (k >= 0) {
+          store_packed(t.spatial, index, load_packed(&known->e[k].output, 0));
+          tile_mark(t.m_spatial, tile, known->e[k].output_id, uid, t.serial);
+          if (!tile_kept) t.render[index] = make_uint2(0u, 0u);
+          return;
+        }
       }
     }
   }
@@ -1144,8 +1180,11 @@ void launch_resolve_scatter_lite(hipStream_t st, const LightTargets& t, const DF
 #ifndef HK_SPATIAL_WINDOWED_MIN_TILES
 #define HK_SPATIAL_WINDOWED_MIN_TILES 8160u
 #endif
-bool launch_spatial(hipStream_t st, bool emissive_lit, const DScene& sc, const DFrame& fr, const GBuffer& g, const LightTargets& t, int y0, int y1, int windowed,
-                    hipEvent_t start, hipEvent_t stop) {
+void launch_spatial_known_fill(hipStream_t st, SpatialKnown* table) {
+  for (int phase = 0; phase < 2; ++phase) hipLaunchKernelGGL(k_spatial_known_fill, dim3(1), dim3(64), 0, st, table, phase);
+}
+bool launch_spatial(hipStream_t st, bool emissive_lit, const DScene& sc, const DFrame& fr, const GBuffer& g_in, const LightTargets& t, int y0, int y1, int windowed,
+                    const SpatialKnown* known, hipEvent_t start, hipEvent_t stop) {
   if (y1 <= y0) return false;
   dim3 grid = grid_for(fr.rw, y1 - y0);
   SpatialTaps taps{};
@@ -1160,10 +1199,13 @@ bool launch_spatial(hipStream_t st, bool emissive_lit, const DScene& sc, const D
     for (uint32_t j = 1; j <= taps.tap_count[i - 1] && j <= 6u; ++j) taps.march_frac[i - 1][j - 1] = (float)j / (float)(taps.tap_count[i - 1] + 1u);
   }
   const bool window = windowed > 0 || (windowed < 0 && grid.x >= HK_SPATIAL_WINDOWED_MIN_TILES);
-  if (emissive_lit && window) hipExtLaunchKernelGGL((k_spatial_reuse<true, true>), grid, dim3(256), 0, st, start, stop, 0, sc, fr, g, t, taps, y0, y1);
-  else if (emissive_lit) hipExtLaunchKernelGGL((k_spatial_reuse<true, false>), grid, dim3(256), 0, st, start, stop, 0, sc, fr, g, t, taps, y0, y1);
-  else if (window) hipExtLaunchKernelGGL((k_spatial_reuse<false, true>), grid, dim3(256), 0, st, start, stop, 0, sc, fr, g, t, taps, y0, y1);
-  else hipExtLaunchKernelGGL((k_spatial_reuse<false, false>), grid, dim3(256), 0, st, start, stop, 0, sc, fr, g, t, taps, y0, y1);
+  // (without the table - the A/B arm - the windowed form gets no plane either: what it did before it could take one)
+  GBuffer g = g_in;
+  if (window && !known) g.empty_in = nullptr;
+  if (emissive_lit && window) hipExtLaunchKernelGGL((k_spatial_reuse<true, true>), grid, dim3(256), 0, st, start, stop, 0, sc, fr, g, t, taps, known, y0, y1);
+  else if (emissive_lit) hipExtLaunchKernelGGL((k_spatial_reuse<true, false>), grid, dim3(256), 0, st, start, stop, 0, sc, fr, g, t, taps, known, y0, y1);
+  else if (window) hipExtLaunchKernelGGL((k_spatial_reuse<false, true>), grid, dim3(256), 0, st, start, stop, 0, sc, fr, g, t, taps, known, y0, y1);
+  else hipExtLaunchKernelGGL((k_spatial_reuse<false, false>), grid, dim3(256), 0, st, start, stop, 0, sc, fr, g, t, taps, known, y0, y1);
   return window;
 }
 void launch_tone_mapping(hipStream_t st, const DFrame& fr, const void* direct, const void* emissive, const void* indirect, void* out, int y0, int y1) {

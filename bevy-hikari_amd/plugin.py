@@ -1452,6 +1452,12 @@ class Engine:
         self.api.call("debug_spatial_windowed_launches", self.ctx, C.byref(n))
         return int(n.value)
 
+    def spatial_known_launches(self):
+        """spatial_reuse launches that were handed the table of the background's known records (hikari_hip_debug.h; F.DEBUG_OPT_SPATIAL_KNOWN)."""
+        n = C.c_uint64()
+        self.api.call("debug_spatial_known_launches", self.ctx, C.byref(n))
+        return int(n.value)
+
     def measure_hbm(self, bytes_per_array=1 << 30, reps=8):
         """Empirical HBM ceiling: (copy GB/s, triad GB/s) of grid-stride float4 streams over arrays too big for the Infinity Cache."""
         cp, tr = C.c_double(), C.c_double()

@@ -121,6 +121,10 @@ int hk_debug_comm_loopback(hk_ctx* ctx, uint32_t src_buffer, uint32_t dst_buffer
  * and the lists of surviving taps in LDS: kernels.hip) since hk_create.  Which form a launch takes: by its size, or what
  * hk_debug_set_option(HK_DEBUG_OPT_SPATIAL_WINDOW) says. */
 int hk_debug_spatial_windowed_launches(hk_ctx* ctx, uint64_t* out);
+/* ... and how many spatial_reuse launches were handed the table of the background's known records (kernels.hip k_spatial_known_fill: the
+ * re-pack of the two records the temporal passes store to a background pixel, computed once per context) since hk_create: every one
+ * while HK_DEBUG_OPT_SPATIAL_KNOWN is on, none while it is off. */
+int hk_debug_spatial_known_launches(hk_ctx* ctx, uint64_t* out);
 
 /* Test hook (round 6): the priority the context's own main stream was created at - 0 the default, 1 the device's highest, and whether the
  * rule has decided yet (bit 1: it decides at the context's first frame; hk_debug_set_option(HK_DEBUG_OPT_MAIN_PRIORITY) decides at once);
@@ -146,6 +150,7 @@ int hk_debug_comm_lanes(hk_ctx* ctx, uint32_t* lanes);
 #define HK_DEBUG_OPT_LOAD_DEVICE_LIMIT 12u /* hk_load_scene completes a deferred mesh of more than this many triangles on the host instead of the device (default 0: HK_MESH_REBUILD_MAX_TRIANGLES); tests reach that path without a mesh of four million triangles */
 #define HK_DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP 11u /* 1: hk_rebuild_mesh_tree (HK_TREE_SAH) runs the top levels of its build in one workgroup at any mesh size, as the instance tree's build does (default 0: on the whole chip from 32 768 triangles); the same tree either way - the A/B of tools/deform_probe.py */
 #define HK_DEBUG_OPT_KNOWN_RESULTS 13u /* 0: no launch is handed the empty-tile plane of the frame's primary rays - every wave computes its way to the background constants, and stores them whatever the planes hold (default 1; the A/B, tests/test_known_results_gpu.py and tests/test_background_stores_gpu.py) */
+#define HK_DEBUG_OPT_SPATIAL_KNOWN 14u /* 0: no spatial_reuse launch is handed the table of the background's known records - every background wave loads, unpacks and re-packs its input - and the windowed form of the kernel is handed no empty-tile / kept-tile plane (default 1; the A/B and tests/test_spatial_background_gpu.py) */
 int hk_debug_set_option(hk_ctx* ctx, uint32_t option, int64_t value);
 /* Test hook of the empty-tile plane (one byte per 8x8 tile of the render image, row-major, (w + 7) / 8 x (h + 7) / 8; 1 = every primary
  * ray of the tile missed): waits for the context's work, copies the plane of the current frame parity into out_bytes (n = the number of
