@@ -42,6 +42,7 @@ STAGE_TEMPORAL, STAGE_SPATIAL, STAGE_POST_PROCESS, STAGE_ANTIALIAS, STAGE_UPSCAL
 DEFAULT_CTX_FLAGS = int(os.environ.get("HIKARI_HIP_DEFAULT_CTX_FLAGS", "0"))
 CTX_COUNT_RAYS, CTX_TIME_PASSES, CTX_PLAIN_DIVISION, CTX_SINGLE_STREAM, CTX_DETERMINISTIC_SCATTER, CTX_EXACT_TRAVERSAL = 1, 2, 4, 8, 16, 32
 TREE_SAH, TREE_LBVH = 0, 1  # hk_rebuild_scene_trees
+INSTANCE_NEW = 0xFFFFFFFF  # hk_change_scene_instances: an origin that names no instance of the scene the context holds
 CTX_WAVEFRONT, CTX_FUSED_INDIRECT = 64, 128  # schedule of indirect_lit_ambient with >= 2 bounces (hikari_hip.h)
 CTX_NO_WIDE_WALK = 256  # closest-hit walks of scenes beyond LDS keep the threaded skip-link walk (A/B switch)
 CTX_COUNT_WALKS = 512   # the trace stages run the counting twin of their kernel (same schedule, same walks): hk_debug_read_wf_timeline
@@ -263,6 +264,7 @@ _DEBUG = {
     "debug_read_mesh_geometry": [_vp, P(HkMeshIndex), P(f32), P(f32), u32, P(f32), u32, P(f32), P(u32), P(u32)],
     "debug_last_deform": [_vp, P(u32)],
     "debug_last_pose": [_vp, P(u32)],
+    "debug_last_instance_change": [_vp, P(u32)],
     "debug_last_texture_update": [_vp, P(u32)],
     "debug_comm_loopback": [_vp, u32, u32, u32, u32, u32],
     "debug_read_wf_timeline": [_vp, P(C.c_uint64), u32],
@@ -321,6 +323,7 @@ _PRODUCT_ONLY = {
     "refit_scene_instances": [_vp, _vp, P(u32)],
     "rebuild_scene_trees": [_vp, u32],
     "update_scene_instances": [_vp, _vp, u32],
+    "change_scene_instances": [_vp, _vp, P(u32), u32, u32],
     "update_materials": [_vp, _vp, u32, P(u32)],
     "update_texture": [_vp, u32, P(HkImageDesc)],
     "update_textures_device": [_vp, P(HkTextureSource), u32, _vp],
@@ -381,6 +384,7 @@ _PRODUCT_ONLY = {
     "multi_refit_scene_instances": [_vp, _vp, P(u32)],
     "multi_rebuild_scene_trees": [_vp, u32],
     "multi_update_scene_instances": [_vp, _vp, u32],
+    "multi_change_scene_instances": [_vp, _vp, P(u32), u32, u32],
     "multi_update_mesh_vertices": [_vp, P(HkMeshIndex), u32, P(f32), P(f32)],
     "multi_set_mesh_skin": [_vp, P(HkMeshIndex), u32, P(f32), P(f32), P(C.c_uint16), P(f32)],
     "multi_skin_mesh": [_vp, P(HkMeshIndex), P(f32), u32],

@@ -881,6 +881,15 @@ int hk_multi_update_scene_instances(hk_multi* m, hk_scene_builder* b, uint32_t t
   }
   return HK_OK;
 }
+// ... and the change from device state: band 0 finishes the builder, every band's replica lays the new level out and derives its values
+int hk_multi_change_scene_instances(hk_multi* m, hk_scene_builder* b, const uint32_t* origins, uint32_t n, uint32_t tree_mode) {
+  HK_REQUIRE(m && b && origins, HK_E_INVALID, "NULL argument");
+  for (size_t i = 0; i < m->ctx.size(); ++i) {
+    const int rc = hk::change_instances_impl(m->ctx[i], b, origins, n, tree_mode, i == 0);
+    if (rc) return rc;
+  }
+  return HK_OK;
+}
 int hk_multi_upload_textures(hk_multi* m, const HkImageDesc* images, uint32_t n) { HK_EACH(hk_upload_textures(c, images, n)); }
 int hk_multi_update_texture(hk_multi* m, uint32_t index, const HkImageDesc* image) { HK_EACH(hk_update_texture(c, index, image)); }
 int hk_multi_upload_noise(hk_multi* m, const uint8_t* rgba, size_t bytes) { HK_EACH(hk_upload_noise(c, rgba, bytes)); }

@@ -5,6 +5,7 @@
 //   scene_refit.hip   instance motion and instance-set changes on the device (hk_refit_scene_instances, hk_rebuild_scene_trees, ...)
 //   scene_load.hip    mesh trees built on the device at scene load (hk_load_scene); scene_append.hip: meshes appended later (hk_add_meshes);
 //                     scene_remove.hip: meshes removed, the mesh level compacted (hk_remove_meshes)
+//   scene_instances.hip  the instance set changed from device state: after deformations and device poses (hk_change_scene_instances)
 //   probes.hip        measurement hooks (hk_measure_*, hk_debug_math)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -348,6 +349,7 @@ struct hk_ctx {
   uint64_t pd_all_generation = 0;
   uint32_t pd_all_emitters = 0, pd_all_emitter_triangles = 0;
   hipEvent_t pd_src_ready = nullptr, pd_src_read = nullptr;  // the producer's stream before the call's launches, the pose kernel before the producer
+  uint32_t last_instance_change[4] = {0, 0, 0, 0};  // hk_debug_last_instance_change (scene_instances.hip)
   uint32_t last_pose[2] = {0, 0};         // hk_debug_last_pose: launches of the last call, 1 if it copied mesh boxes to the device
   uint64_t instances_generation = 0;      // counts hk_upload_instances (the instance lists of the deformable meshes follow it)
   uint64_t device_refits = 0, device_tree_builds = 0;
@@ -457,6 +459,10 @@ int join_all(hk_ctx* c);
 int sync_all(hk_ctx* c);
 // bring the device scene up to date with the host-side arrays (no-op when nothing is dirty)
 int finalize_scene(hk_ctx* c);
+// the instance-level region laid out from the mirrors into `blob` (finalize_scene; hk_change_scene_instances, which lets the device
+// overwrite what the mirrors hold stale), and c->dyn_blob through pinned staging into the slot in use of a two-slot scene
+int build_dynamic_region(hk_ctx* c, Blob& blob, DynOffsets& o, size_t static_bytes);
+int upload_slot_staged(hk_ctx* c);
 void update_shared_transform(hk_ctx* c);
 void point_scene_at_slot(hk_ctx* c);
 size_t fold_leaf_navigators(std::vector<float4>& lo, std::vector<float4>& hi, size_t begin, size_t count);
@@ -477,16 +483,22 @@ int build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMesh>&
 // ---- scene_append.hip
 void retire(hk_ctx* c, void* p, hipEvent_t done);   // free `p` once `done` has passed (takes the event over)
 void poll_retired(hk_ctx* c, bool wait);            // ... checked here, only behind a wait for the context's streams (hipFree may wait by itself); wait: free everything
+int grow_instance_slots(hk_ctx* c, size_t dyn_capacity);   // a two-slot scene moved, device to device in one launch, to an allocation whose instance-level slots hold `dyn_capacity` bytes each (hk_change_scene_instances)
 int take_appended_materials(hk_ctx* c, const hk_scene_builder* b);  // hk_update_scene_instances: materials the builder holds beyond the context's (the caller takes them back if the upload is refused)
 // ---- mesh_deform.hip, for hk_remove_meshes (scene_remove.hip): the records of the deformable meshes; then, `runs` being the surviving
 // intervals per list (nodes, primitives, vertices), every record rebased and the meshes that lie in no run dropped - their device
 // allocations go to `freed` for the caller to retire
 void deform_mesh_records(const hk_ctx* c, std::vector<HkMeshIndex>& out);
 void rebase_deform_meshes(hk_ctx* c, const std::vector<hk::CompactRun> runs[3], std::vector<void*>& freed);
+const uint32_t* deformed_mesh_box(const hk_ctx* c, const HkMeshIndex& m);   // the box words of a mesh deformed on the device, or NULL
+void deform_flushed(hk_ctx* c);                                              // every deformed mesh's box has reached the instance level by another way
 // ---- scene_refit.hip
 void free_refit(hk_ctx* c);
 int begin_device_update(hk_ctx* c);
 int prepare_refit(hk_ctx* c);
+int reserve_refit(hk_ctx* c, size_t n_instances, size_t n_alias);   // the refit's side arrays for that many instances / alias entries (waits only where they grow)
+int reserve_tree_scratch(hk_ctx* c, uint32_t n_instances, uint32_t n_emitters);
+int build_trees_in_slot(hk_ctx* c, uint32_t mode);                 // both trees built over rf_inst_lo / rf_inst_hi and the emitters, in the slot in use (hk_rebuild_scene_trees' launches)
 hkd::RefitScene refit_scene(hk_ctx* c);
 // ---- mesh_deform.hip
 void free_deform(hk_ctx* c);

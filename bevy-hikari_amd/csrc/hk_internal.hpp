@@ -71,6 +71,8 @@ int update_materials_impl(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode, ui
 
 int upload_instances_and_build_trees(hk_ctx* c, const hk_scene_builder* b, uint32_t tree_mode);  // scene_refit.hip
 int refit_instances_impl(hk_ctx* c, hk_scene_builder* b, uint32_t* moved, bool commit);  // hk_refit_scene_instances
+// hk_change_scene_instances on one context (scene_instances.hip); `finish`: the builder is finished here (once per change, by the first context that sees it)
+int change_instances_impl(hk_ctx* c, hk_scene_builder* b, const uint32_t* origins, uint32_t n, uint32_t tree_mode, bool finish);
 
 // ---- material textures (host_logic.cpp): the 256-entry sRGB decode table the samplers read (the EOTF in double, rounded once), and the
 // 255 thresholds of its inverse (hikari_hip.h HK_TEXTURE_LINEAR_SOURCE): mid[k] = (float)((lut[k - 1] + lut[k]) / 2) in double for

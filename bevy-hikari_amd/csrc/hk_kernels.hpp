@@ -225,6 +225,16 @@ struct MeshInstanceEntry {
   uint32_t record;                   // index into the launch's RefitUpdate records, HK_U32_MAX: no emitter
   const uint32_t* box;
 };
+// hk_change_scene_instances (kernels_scene.hip k_carry_instances / k_derive_instances): one record per instance of the NEW instance
+// level, in pinned memory
+struct InstanceDerive {
+  uint32_t origin;                   // the id the instance had in the old level, HK_U32_MAX: it is new
+  uint32_t emitter;                  // its emitter in the new level (and its RefitUpdate record), HK_U32_MAX: none
+  const uint32_t* box;               // the box words of its mesh where the mesh was deformed on the device, else NULL: the builder's box
+  float aabb_center[3], aabb_half[3];
+  uint32_t pad[2];
+};
+static_assert(sizeof(InstanceDerive) == 48, "three 16-B loads per record");
 // One tree of a segmented derivation of wide records (kernels_wavefront.hip k_build_wide_trees): offsets into the launch's arrays
 struct WideTreeSegment {
   uint32_t node_offset, count;       // its slots in the node array (ordering 0)
@@ -569,6 +579,14 @@ void launch_mesh_tree_refit(hipStream_t st, const hkd::MeshTree& t, float4* lo, 
 uint32_t launch_mesh_propagate(hipStream_t st, const hkd::RefitScene& s, const hkd::MeshInstanceEntry* entries, uint32_t n_entries, hkd::RefitUpdate* records,
                                uint32_t n_emitters, uint32_t emitter_triangles, float4* tlas, uint32_t tlas_count, uint32_t orderings, float4* light_lo, float4* light_hi,
                                uint32_t light_count);
+// hk_change_scene_instances: the device's values over a freshly laid-out instance level `s` - the poses of the survivors from
+// `old_instances` (or NULL: the host's poses stand), every instance's world box and emitter slot (into `emissive_of_instance`, the
+// array s names), every emitter's record, surface area and alias slice (`records`: device scratch, one per emitter), then a refit of the
+// trees given a node count (the single-leaf trees nothing builds).  `entries`: pinned, one per instance.  The launches do not follow
+// the number of instances; returns how many.
+uint32_t launch_instance_change(hipStream_t st, const hkd::RefitScene& s, uint32_t* emissive_of_instance, const hkd::DInstance* old_instances,
+                                const hkd::InstanceDerive* entries, uint32_t n_instances, hkd::RefitUpdate* records, uint32_t n_emitters, uint32_t emitter_triangles,
+                                float4* tlas, uint32_t tlas_count, uint32_t orderings, float4* light_lo, float4* light_hi, uint32_t light_count);
 // hk_deform_meshes: `items` and the three workgroup tables (vertices, triangles = leaves, tree nodes x orderings) lie in pinned memory.
 // Five launches whatever n_items is: begin (box words, joint palettes), vertices, triangles (+ arrival counters), boxes bottom-up, emit.
 // hk_deform_meshes_device: `sources_read` (or NULL) is recorded behind the vertex launch, the last that reads the caller's memory; with

@@ -81,6 +81,14 @@ __device__ __forceinline__ void instance_world_box(const float* m, const float* 
     mx[k] = mx[k] + center[k];
   }
 }
+// a deformed mesh's box (6 order-preserving words, kernels_deform.hip) as bevy's Aabb: Aabb::from_min_max (scene_builder.cpp hk_scene_builder_add_mesh)
+__device__ __forceinline__ void mesh_box_of_words(const uint32_t* __restrict__ box, float* aabb_center, float* aabb_half) {
+  for (int k = 0; k < 3; ++k) {
+    const float mn = box_unword(box[k]), mx = box_unword(box[3 + k]);
+    aabb_center[k] = 0.5f * (mx + mn);
+    aabb_half[k] = 0.5f * (mx - mn);
+  }
+}
 // the emitter record's position and radius from the instance's world AABB and its material's emissive colour (instance.rs:380-420)
 __device__ __forceinline__ float4 emitter_position_radius(const float4 col, const float* mn, const float* mx) {
   const float intensity = 255.0f * col.w * sqrtf(col.x * col.x + col.y * col.y + col.z * col.z);
@@ -434,11 +442,7 @@ __global__ __launch_bounds__(64) void k_mesh_instances(RefitScene s, const MeshI
   const DInstance& d = s.instances[id];
   const float m[16] = {d.m0.x, d.m0.y, d.m0.z, d.m0.w, d.m1.x, d.m1.y, d.m1.z, d.m1.w, d.m2.x, d.m2.y, d.m2.z, d.m2.w, d.m3.x, d.m3.y, d.m3.z, d.m3.w};
   float ac[3], ah[3];
-  for (int k = 0; k < 3; ++k) {  // bevy Aabb::from_min_max (scene_builder.cpp hk_scene_builder_add_mesh)
-    const float mn = box_unword(box[k]), mx = box_unword(box[3 + k]);
-    ac[k] = 0.5f * (mx + mn);
-    ah[k] = 0.5f * (mx - mn);
-  }
+  mesh_box_of_words(box, ac, ah);
   float mn[3], mx[3];
   instance_world_box(m, ac, ah, mn, mx);
   s.inst_lo[id] = make_float4(mn[0], mn[1], mn[2], 0.0f);
@@ -456,6 +460,60 @@ __global__ __launch_bounds__(64) void k_mesh_instances(RefitScene s, const MeshI
   if (e == HK_U32_MAX) r.moved = 0u;  // (no emitter after all: k_refit_emitters passes the record by)
   else s.emissives[e].position_radius = emitter_position_radius(s.materials[4u * d.material + 1u], mn, mx);
   records[en.record] = r;
+}
+
+// ------------------------------------------------------------------ the instance set changed (hk_change_scene_instances, scene_instances.hip)
+// The host has laid the new instance level out in the slot `s` names: counts, offsets, mesh and material words, the emitter list and the
+// alias slices are right; poses, boxes and everything derived from them are the host mirrors', which may be stale.  Two kernels put the
+// device's own values over them, whatever the number of instances or edits.
+// Step 1, poses set from device memory only: a survivor keeps the pose the device holds.  One thread per 16 B: the inverse model, the
+// model and the normal matrix - the first 11 float4 of a DInstance - from the record its origin had in the old slot.  The survivor is at
+// rest (the host laid `moved` out as 0, so nobody reads a previous model); a new instance keeps the builder's pose.
+constexpr uint32_t HK_POSE_PIECES = 11u;
+static_assert(offsetof(DInstance, material) == HK_POSE_PIECES * 16u, "the pose of a DInstance is its first 11 float4");
+__global__ __launch_bounds__(256) void k_carry_instances(DInstance* __restrict__ now, const DInstance* __restrict__ old, const InstanceDerive* __restrict__ entries,
+                                                         uint32_t n_instances) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= n_instances * HK_POSE_PIECES) return;
+  const uint32_t id = t / HK_POSE_PIECES, piece = t - id * HK_POSE_PIECES;
+  const uint32_t origin = entries[id].origin;
+  if (origin == HK_U32_MAX) return;
+  reinterpret_cast<float4*>(now + id)[piece] = reinterpret_cast<const float4*>(old + origin)[piece];
+}
+// Step 2, one thread per instance of the new level: its emitter slot into the refit's side array, its world AABB from the pose the slot
+// now holds and the mesh's CURRENT box - the device's for a deformed mesh, the builder's otherwise - and for an emitter position and
+// radius plus the record k_refit_emitters derives surface area and alias slice from (record e = emitter e).  The arithmetic is
+// k_mesh_instances': instance_world_box, emitter_position_radius.
+__global__ __launch_bounds__(64) void k_derive_instances(RefitScene s, uint32_t* __restrict__ emissive_of_instance, const InstanceDerive* __restrict__ entries,
+                                                         uint32_t n_instances, RefitUpdate* __restrict__ records) {
+  const uint32_t id = blockIdx.x * 64u + threadIdx.x;
+  if (id >= n_instances) return;
+  const InstanceDerive en = entries[id];
+  const DInstance& d = s.instances[id];
+  const float m[16] = {d.m0.x, d.m0.y, d.m0.z, d.m0.w, d.m1.x, d.m1.y, d.m1.z, d.m1.w, d.m2.x, d.m2.y, d.m2.z, d.m2.w, d.m3.x, d.m3.y, d.m3.z, d.m3.w};
+  float ac[3], ah[3];
+  if (en.box) mesh_box_of_words(en.box, ac, ah);
+  else
+    for (int k = 0; k < 3; ++k) {
+      ac[k] = en.aabb_center[k];
+      ah[k] = en.aabb_half[k];
+    }
+  float mn[3], mx[3];
+  instance_world_box(m, ac, ah, mn, mx);
+  s.inst_lo[id] = make_float4(mn[0], mn[1], mn[2], 0.0f);
+  s.inst_hi[id] = make_float4(mx[0], mx[1], mx[2], 0.0f);
+  emissive_of_instance[id] = en.emitter;
+  if (en.emitter == HK_U32_MAX) return;
+  RefitUpdate r;
+  r.instance = id;
+  r.moved = 1u;
+  for (int k = 0; k < 16; ++k) r.model[k] = m[k];
+  for (int k = 0; k < 3; ++k) {
+    r.aabb_center[k] = ac[k];
+    r.aabb_half[k] = ah[k];
+  }
+  s.emissives[en.emitter].position_radius = emitter_position_radius(s.materials[4u * d.material + 1u], mn, mx);
+  records[en.emitter] = r;
 }
 
 // ------------------------------------------------------------------ poses from device memory (hk_set_instance_transforms_device)
@@ -708,6 +766,25 @@ uint32_t launch_pose_records(hipStream_t st, const RefitScene& s, uint32_t n_ins
   hipLaunchKernelGGL(k_pose_records, dim3((n_named + 63u) / 64u), dim3(64), 0, st, s, named, n_named, (const uint8_t*)models, stride, mesh_boxes, records, status);
   if (sources_read) (void)hipEventRecord(sources_read, st);  // (the last launch that reads the caller's memory)
   return 2u;
+}
+
+uint32_t launch_instance_change(hipStream_t st, const RefitScene& s, uint32_t* emissive_of_instance, const DInstance* old_instances, const InstanceDerive* entries,
+                                uint32_t n_instances, RefitUpdate* records, uint32_t n_emitters, uint32_t emitter_triangles, float4* tlas, uint32_t tlas_count, uint32_t orderings,
+                                float4* light_lo, float4* light_hi, uint32_t light_count) {
+  if (!n_instances) return 0u;
+  uint32_t launches = 1u;
+  if (old_instances) {
+    hipLaunchKernelGGL(k_carry_instances, dim3((n_instances * HK_POSE_PIECES + 255u) / 256u), dim3(256), 0, st, s.instances, old_instances, entries, n_instances);
+    ++launches;
+  }
+  hipLaunchKernelGGL(k_derive_instances, dim3((n_instances + 63u) / 64u), dim3(64), 0, st, s, emissive_of_instance, entries, n_instances, records);
+  if (n_emitters) {  // one workgroup (= one wave) per emitter record, with the LDS the largest of their meshes needs
+    const uint32_t lds_triangles = std::min(emitter_triangles, HK_EMITTER_LDS_TRIANGLES);
+    hipLaunchKernelGGL(k_refit_emitters, dim3(n_emitters), dim3(64), lds_triangles * 5u * 4u, st, s, (const RefitUpdate*)records, n_emitters, lds_triangles);
+    ++launches;
+  }
+  launch_refit_trees(st, s, tlas, tlas_count, orderings, light_lo, light_hi, light_count);
+  return launches + (tlas_count ? 1u : 0u) + (light_count ? 1u : 0u);
 }
 
 uint32_t launch_mesh_propagate(hipStream_t st, const RefitScene& s, const MeshInstanceEntry* entries, uint32_t n_entries, RefitUpdate* records, uint32_t n_emitters,

@@ -72,6 +72,17 @@ void free_deform(hk_ctx* c) {
 void deform_mesh_records(const hk_ctx* c, std::vector<HkMeshIndex>& out) {
   for (const DeformMesh* d : c->deform) out.push_back(d->mesh);
 }
+// hk_change_scene_instances (scene_instances.hip): the box words of a mesh deformed on the device (NULL: the builder's box is current),
+// and - that call having carried every deformed mesh's box to the new instance level - nothing left to flush
+const uint32_t* deformed_mesh_box(const hk_ctx* c, const HkMeshIndex& m) {
+  for (const DeformMesh* d : c->deform)
+    if (d->deformed && memcmp(&d->mesh, &m, sizeof(HkMeshIndex)) == 0) return d->box;
+  return nullptr;
+}
+void deform_flushed(hk_ctx* c) {
+  for (DeformMesh* d : c->deform) d->pending = false;
+  c->deform_pending = false;
+}
 void rebase_deform_meshes(hk_ctx* c, const std::vector<CompactRun> runs[3], std::vector<void*>& freed) {
   size_t kept = 0;
   for (DeformMesh* d : c->deform) {

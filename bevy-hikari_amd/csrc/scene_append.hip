@@ -48,10 +48,11 @@ double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::
 
 // The scene moved to an allocation with these capacities: both instance-level slots, every ordering's node plane, the triangle and vertex
 // planes and - where they exist - the wide records and ranks of the mesh trees, in one launch behind everything enqueued.  Nothing of the
-// context changes unless every allocation succeeded.
-int relocate(hk_ctx* c, const Sizes& cap) {
+// context changes unless every allocation succeeded.  `dyn_capacity`: the bytes of an instance-level slot in the new allocation, at least
+// today's (hk_change_scene_instances grows them; an append keeps them) - the bytes of the slot in use go to the front of its new slot.
+int relocate(hk_ctx* c, const Sizes& cap, size_t dyn_capacity) {
   const uint32_t orderings = c->threaded ? 8u : 1u;
-  const size_t slots = 2 * c->dyn_capacity;
+  const size_t old_slots = 2 * c->dyn_capacity, slots = 2 * dyn_capacity;
   size_t off[6];
   const size_t bytes = mesh_region_layout(cap.nodes, cap.prims, cap.verts, orderings, off);
   const size_t old_off[6] = {c->st_nodes, c->st_v0, c->st_v1, c->st_v2, c->st_vn, c->st_vuv};
@@ -79,9 +80,10 @@ int relocate(hk_ctx* c, const Sizes& cap) {
   c->last_add_ms[0] = now_ms() - t0;
   const double t1 = now_ms();
   CopySegments s;
-  const uint8_t *from = c->scene_mem + slots, *const old_mem = c->scene_mem;
+  const uint8_t *from = c->scene_mem + old_slots, *const old_mem = c->scene_mem;
   uint8_t* to = mem + slots;
-  s.add(mem, old_mem, slots);
+  if (dyn_capacity == c->dyn_capacity) s.add(mem, old_mem, slots);
+  else s.add(mem + (size_t)c->slot * dyn_capacity, old_mem + (size_t)c->slot * c->dyn_capacity, c->dyn_capacity);  // (the spare slot is about to be written)
   for (uint32_t o = 0; o < orderings; ++o) s.add(to + off[0] + (size_t)o * cap.nodes * 32, from + old_off[0] + (size_t)o * c->node_cap * 32, n_nodes * 32);
   for (int k = 1; k <= 3; ++k) s.add(to + off[k], from + old_off[k], n_prims * 16);
   s.add(to + off[4], from + old_off[4], n_verts * 16);
@@ -105,6 +107,7 @@ int relocate(hk_ctx* c, const Sizes& cap) {
   if (rank) { retire(c, c->wide_blas_rank, done[2]); c->wide_blas_rank = rank; c->wide_rank_primitives = cap.prims; }
   else (void)hipEventDestroy(done[2]);
   c->scene_mem = mem;
+  c->dyn_capacity = dyn_capacity;
   c->node_cap = cap.nodes; c->prim_cap = cap.prims; c->vert_cap = cap.verts;
   c->st_nodes = off[0]; c->st_v0 = off[1]; c->st_v1 = off[2]; c->st_v2 = off[3]; c->st_vn = off[4]; c->st_vuv = off[5];
   c->static_bytes = bytes;
@@ -154,6 +157,18 @@ int layout_host_trees(const hk_ctx* c, const std::vector<LoadMesh>& meshes, uint
   }
   return HK_OK;
 }
+
+}  // namespace
+// hk_change_scene_instances: the same move for larger instance-level slots, the mesh level keeping its capacities (the report of the last
+// hk_add_meshes stays that call's)
+int hk::grow_instance_slots(hk_ctx* c, size_t dyn_capacity) {
+  double ms[4];
+  std::copy(c->last_add_ms, c->last_add_ms + 4, ms);
+  const int rc = relocate(c, Sizes{c->node_cap, c->prim_cap, c->vert_cap}, dyn_capacity);
+  std::copy(ms, ms + 4, c->last_add_ms);
+  return rc;
+}
+namespace {
 
 // hk_debug_last_add / hk_debug_last_add_times start from zero once a call can no longer be refused
 void clear_add_report(hk_ctx* c) {
@@ -264,7 +279,7 @@ int hk_add_meshes(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode) {
   uint32_t relocated = 0;
   if (now.nodes > c->node_cap || now.prims > c->prim_cap || now.verts > c->vert_cap) {
     auto room = [](size_t need, size_t unit) { return ((3 * need + 1) / 2 + unit - 1) / unit * unit; };
-    if ((rc = relocate(c, Sizes{room(now.nodes, 1), room(now.prims, 4), room(now.verts, 4)}))) return rc;  // (nothing was written: the scene is the one it had)
+    if ((rc = relocate(c, Sizes{room(now.nodes, 1), room(now.prims, 4), room(now.verts, 4)}, c->dyn_capacity))) return rc;  // (nothing was written: the scene is the one it had)
     relocated = 1;
   }
   c->scene_epoch += 1;  // (scene memory is written from here on: hk_context.hpp, primary-ray pipelining)

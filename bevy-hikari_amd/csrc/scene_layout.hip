@@ -527,6 +527,40 @@ size_t mesh_region_layout(size_t node_cap, size_t prim_cap, size_t vert_cap, uin
   return (at + 15) & ~(size_t)15;
 }
 
+// The instance-level region as last laid out (c->dyn_blob) into the slot in use - the one frames in flight do NOT read - of a two-slot
+// scene, through pinned staging in stream order: neither the host nor the GPU waits (finalize_scene, hk_change_scene_instances)
+int upload_slot_staged(hk_ctx* c) {
+  uint8_t* const slot_mem = c->scene_mem + (size_t)c->slot * c->dyn_capacity;
+  // (the slot written now was read by the frame before last: its direct-light dispatches may still sit on the side stream - round 6,
+  // hk_context.hpp side_done - so the copy goes behind them)
+  int rc;
+  if ((rc = join_side(c))) return rc;
+  const int k = c->slot;
+  if (c->staging_pending[k]) {  // the copy that last read this staging buffer (two updates ago)
+    HK_HIP(hipEventSynchronize(c->staging_done[k]));
+    c->staging_pending[k] = false;
+  }
+  if (c->staging_bytes[k] < c->dyn_capacity) {
+    if (c->staging[k]) (void)hipHostFree(c->staging[k]);
+    c->staging[k] = nullptr;
+    c->staging_bytes[k] = 0;
+    HK_HIP(hipHostMalloc((void**)&c->staging[k], c->dyn_capacity, hipHostMallocDefault));
+    c->staging_bytes[k] = c->dyn_capacity;
+  }
+  if (!c->staging_done[k]) HK_HIP(hipEventCreateWithFlags(&c->staging_done[k], hipEventDisableTiming));
+  memcpy(c->staging[k], c->dyn_blob.bytes.data(), c->dyn_blob.bytes.size());
+  memset(c->staging[k] + c->dyn_blob.bytes.size(), 0, c->dyn_capacity - c->dyn_blob.bytes.size());
+  // a copy KERNEL reading the pinned buffer over PCIe: the update stays on the compute queue of the stream, between
+  // the kernels of two frames, instead of a hand-off to an SDMA engine and back
+  hipLaunchKernelGGL(k_copy_u4, dim3((unsigned)((c->dyn_capacity / 16 + 255) / 256)), dim3(256), 0, c->stream, (uint4*)slot_mem,
+                     (const uint4*)c->staging[k], c->dyn_capacity / 16);
+  HK_HIP(hipGetLastError());
+  HK_HIP(hipEventRecord(c->staging_done[k], c->stream));
+  c->staging_pending[k] = true;
+  c->async_instance_uploads += 1;
+  return HK_OK;
+}
+
 int finalize_scene(hk_ctx* c) {
   if (!c->mesh_dirty && !c->dynamic_dirty && !c->textures_dirty) return HK_OK;
   c->scene_epoch += 1;   // (scene memory is about to be written on the main stream: hk_context.hpp, primary-ray pipelining)
@@ -607,32 +641,7 @@ int finalize_scene(hk_ctx* c) {
   }
   uint8_t* const slot_mem = c->scene_mem + (size_t)c->slot * c->dyn_capacity;
   if (in_place && c->two_slots) {
-    // (the slot written now was read by the frame before last: its direct-light dispatches may still sit on the side stream - round 6,
-    // hk_context.hpp side_done - so the copy goes behind them)
-    if ((rc = join_side(c))) return rc;
-    const int k = c->slot;
-    if (c->staging_pending[k]) {  // the copy that last read this staging buffer (two updates ago)
-      HK_HIP(hipEventSynchronize(c->staging_done[k]));
-      c->staging_pending[k] = false;
-    }
-    if (c->staging_bytes[k] < c->dyn_capacity) {
-      if (c->staging[k]) (void)hipHostFree(c->staging[k]);
-      c->staging[k] = nullptr;
-      c->staging_bytes[k] = 0;
-      HK_HIP(hipHostMalloc((void**)&c->staging[k], c->dyn_capacity, hipHostMallocDefault));
-      c->staging_bytes[k] = c->dyn_capacity;
-    }
-    if (!c->staging_done[k]) HK_HIP(hipEventCreateWithFlags(&c->staging_done[k], hipEventDisableTiming));
-    memcpy(c->staging[k], dyn.bytes.data(), dyn.bytes.size());
-    memset(c->staging[k] + dyn.bytes.size(), 0, c->dyn_capacity - dyn.bytes.size());
-    // a copy KERNEL reading the pinned buffer over PCIe: the update stays on the compute queue of the stream, between
-    // the kernels of two frames, instead of a hand-off to an SDMA engine and back
-    hipLaunchKernelGGL(k_copy_u4, dim3((unsigned)((c->dyn_capacity / 16 + 255) / 256)), dim3(256), 0, c->stream, (uint4*)slot_mem,
-                       (const uint4*)c->staging[k], c->dyn_capacity / 16);
-    HK_HIP(hipGetLastError());
-    HK_HIP(hipEventRecord(c->staging_done[k], c->stream));
-    c->staging_pending[k] = true;
-    c->async_instance_uploads += 1;
+    if ((rc = upload_slot_staged(c))) return rc;
   } else {
     HK_HIP(hipMemcpy(slot_mem, dyn.bytes.data(), dyn.bytes.size(), hipMemcpyHostToDevice));
     if (dyn.bytes.size() < c->dyn_capacity) HK_HIP(hipMemset(slot_mem + dyn.bytes.size(), 0, c->dyn_capacity - dyn.bytes.size()));

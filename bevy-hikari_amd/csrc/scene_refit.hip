@@ -114,11 +114,8 @@ hkd::RefitScene refit_scene(hk_ctx* c) {
   r.tri_v2 = c->scene.tri_v2;
   return r;
 }
-// side arrays of the refit, (re)filled from the scene as the host last laid it out: world AABB per instance from the TLAS
-// leaves, emitter of an instance, previous models
-int prepare_refit(hk_ctx* c) {
-  if (c->rf_ready) return HK_OK;
-  const size_t ni = c->instances.size(), na = c->alias_table.size();
+// room in the refit's side arrays for `ni` instances and `na` alias entries (waits only where they grow)
+int reserve_refit(hk_ctx* c, size_t ni, size_t na) {
   if (ni > c->rf_instances || na > c->rf_alias) {
     int rc = sync_all(c);
     if (rc) return rc;
@@ -137,6 +134,15 @@ int prepare_refit(hk_ctx* c) {
     c->rf_instances = cap_i;
     c->rf_alias = cap_a;
   }
+  return HK_OK;
+}
+// side arrays of the refit, (re)filled from the scene as the host last laid it out: world AABB per instance from the TLAS
+// leaves, emitter of an instance, previous models
+int prepare_refit(hk_ctx* c) {
+  if (c->rf_ready) return HK_OK;
+  const size_t ni = c->instances.size(), na = c->alias_table.size();
+  const int rc_reserve = reserve_refit(c, ni, na);
+  if (rc_reserve) return rc_reserve;
   std::vector<uint32_t> eoi(ni, 0xFFFFFFFFu);
   for (size_t e = 0; e < c->emissives.size(); ++e) eoi[c->emissives[e].instance] = (uint32_t)e;
   HK_HIP(hipMemcpyAsync(c->rf_emissive_of_instance, eoi.data(), ni * 4, hipMemcpyHostToDevice, c->stream));
@@ -189,6 +195,14 @@ int hk_rebuild_scene_trees(hk_ctx* c, uint32_t mode) {
   HK_REQUIRE(c->instance_nodes.size() == 3 * (size_t)ni - 2 && (ne == 0 || c->emissive_nodes.size() == 3 * (size_t)ne - 2), HK_E_UNSUPPORTED,
              "the uploaded trees are not in the flatten_custom layout of a binary tree (3n - 2 nodes): nothing to rebuild in place");
   if ((rc = prepare_refit(c))) return rc;
+  if ((rc = reserve_tree_scratch(c, ni, ne))) return rc;
+  if ((rc = begin_device_update(c))) return rc;
+  return build_trees_in_slot(c, mode);
+}
+}  // extern "C"
+// the scratch of the two tree builds (waits only where it grows)
+int hk::reserve_tree_scratch(hk_ctx* c, uint32_t ni, uint32_t ne) {
+  int rc;
   const size_t need = std::max(lbvh_scratch_bytes(ni), lbvh_scratch_bytes(std::max(ne, 1u)));
   if (need > c->lbvh_scratch_cap) {
     if ((rc = sync_all(c))) return rc;
@@ -198,7 +212,10 @@ int hk_rebuild_scene_trees(hk_ctx* c, uint32_t mode) {
     HK_HIP(hipMalloc(&c->lbvh_scratch, need + need / 4));
     c->lbvh_scratch_cap = need + need / 4;
   }
-  if ((rc = begin_device_update(c))) return rc;
+  return HK_OK;
+}
+int hk::build_trees_in_slot(hk_ctx* c, uint32_t mode) {
+  const uint32_t ni = (uint32_t)c->instances.size(), ne = (uint32_t)c->emissives.size();
   const hkd::RefitScene r = refit_scene(c);
   uint8_t* base = c->scene_mem + (size_t)c->slot * c->dyn_capacity;
   float4* tlas = (float4*)(base + c->dyn_off.tlas);
@@ -224,6 +241,7 @@ int hk_rebuild_scene_trees(hk_ctx* c, uint32_t mode) {
   c->device_tree_builds += 1;
   return HK_OK;
 }
+extern "C" {
 // Test hook: the instance tree (ordering 0) and the light tree as the device holds them, converted back to the reference layout
 // (navigators that took over their single leaf's role - fold_leaf_navigators - point at the leaf again)
 int hk_debug_read_trees(hk_ctx* c, HkNode* tlas, uint32_t tlas_cap, HkNode* light, uint32_t light_cap) {

@@ -489,6 +489,8 @@ class MultiEngine:
         for e in self.contexts:
             e.upload_textures(list(textures))
         self.api.call("multi_load_scene", self.h, builder.h, mode)
+        if hasattr(builder, "take_origins"):
+            builder.take_origins()
         return builder.scene()
 
     def add_meshes(self, builder, mode=F.TREE_SAH):
@@ -558,6 +560,15 @@ class MultiEngine:
 
     def update_instances_on_device(self, builder, mode=F.TREE_SAH):
         self.api.call("multi_update_scene_instances", self.h, builder.h, mode)
+        if hasattr(builder, "take_origins"):
+            builder.take_origins()
+
+    def change_instances(self, builder, mode=F.TREE_SAH):
+        """hk_multi_change_scene_instances: Engine.change_instances on every band's copy of the scene (the builder is finished once)."""
+        origins = np.array(builder.origins, dtype=np.uint32)
+        self.api.call("multi_change_scene_instances", self.h, builder.h, origins.ctypes.data_as(C.POINTER(F.u32)), len(origins), mode)
+        if hasattr(builder, "take_origins"):
+            builder.take_origins()
 
     def update_materials(self, builder, mode=F.TREE_SAH):
         """hk_multi_update_materials: the material values set on `builder` go to every band's device copy of the scene."""

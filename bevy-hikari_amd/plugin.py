@@ -353,6 +353,17 @@ class SceneBuilder:
         self.h = C.c_void_p()
         self.api.call("scene_builder_create", C.byref(self.h))
         self.mesh_vertices = []  # vertex count per mesh id (set_mesh_vertices checks its arrays against it)
+        # per instance the id it had when a context last took the instance set, or F.INSTANCE_NEW (Engine.change_instances: the builder
+        # shifts ids on removal, so the map is kept here)
+        self.origins = []
+
+    def take_origins(self):
+        """The origin list of hk_change_scene_instances, consumed: afterwards every instance is its own origin.  Every Engine call that
+        hands the builder's instance set to a context consumes it (upload_scene / upload_instances of a SceneData that carries its builder,
+        load_scene, update_instances_on_device, change_instances); a host that uploads through raw arrays calls this itself."""
+        out = np.array(self.origins, dtype=np.uint32)
+        self.origins = list(range(len(self.origins)))
+        return out
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -396,6 +407,7 @@ class SceneBuilder:
         t = np.ascontiguousarray(transform, dtype=np.float32).reshape(-1)
         out = F.u32()
         self.api.call("scene_builder_add_instance", self.h, mesh_id, material_id, t.ctypes.data_as(C.POINTER(F.f32)), C.byref(out))
+        self.origins.append(F.INSTANCE_NEW)
         return out.value
 
     def set_instance_transform(self, instance_id, transform):
@@ -406,6 +418,7 @@ class SceneBuilder:
     def remove_instance(self, instance_id):
         """Take an instance out of the scene (ids of later instances shift down by one)."""
         self.api.call("scene_builder_remove_instance", self.h, instance_id)
+        del self.origins[instance_id]
 
     def set_instance_material(self, instance_id, material_id):
         self.api.call("scene_builder_set_instance_material", self.h, instance_id, material_id)
@@ -778,11 +791,20 @@ class Engine:
         self.upload_textures(getattr(scene, "textures", []))
         scene.upload(self.api, self.ctx)
         self._n_instances = len(scene.instances)
+        self._consumed(scene)
 
     def upload_instances(self, scene: SceneData):
         """Instance-level update of a scene whose meshes and materials are already uploaded."""
         scene.upload_instances(self.api, self.ctx)
         self._n_instances = len(scene.instances)
+        self._consumed(scene)
+
+    @staticmethod
+    def _consumed(scene):
+        """the context holds the instance set of the scene's builder (where the SceneData carries one): its origin list starts over"""
+        builder = getattr(scene, "builder", None)
+        if builder is not None and hasattr(builder, "take_origins"):
+            builder.take_origins()
 
     def load_scene(self, builder, mode=F.TREE_SAH, textures=()):
         """hk_load_scene: the upload of a FINISHED builder whose deferred meshes (SceneBuilder.add_mesh(build_tree=False)) get their trees
@@ -790,6 +812,8 @@ class Engine:
         the builder.  Returns the refreshed SceneData."""
         self.upload_textures(list(textures))
         self.api.call("load_scene", self.ctx, builder.h, mode)
+        if hasattr(builder, "take_origins"):
+            builder.take_origins()
         return builder.scene()
 
     def last_load(self):
@@ -853,6 +877,26 @@ class Engine:
         """Instances added / removed / re-materialed on `builder`: hk_update_scene_instances (host lays out the records, the device
         builds both trees)."""
         self.api.call("update_scene_instances", self.ctx, builder.h, mode)
+        if hasattr(builder, "take_origins"):
+            builder.take_origins()
+
+    def change_instances(self, builder, mode=F.TREE_SAH):
+        """Instances added / removed / re-materialed on `builder` in ANY state of the scene - after mesh deformations and device poses too,
+        where update_instances_on_device is refused: hk_change_scene_instances (the host lays the level out, the device writes its own
+        values over what the host's mirrors hold stale - survivors' poses, boxes, emitter records, alias tables - and builds both trees).
+        The builder's origin list (SceneBuilder.origins) travels with the call and is reset to the identity once the call is accepted."""
+        origins = np.array(builder.origins, dtype=np.uint32)
+        self.api.call("change_scene_instances", self.ctx, builder.h, origins.ctypes.data_as(C.POINTER(F.u32)), len(origins), mode)
+        if hasattr(builder, "take_origins"):
+            builder.take_origins()
+        self._n_instances = len(origins)
+
+    def last_instance_change(self):
+        """(kernel launches of the device path, instances carried over, new instances, bit 0: the scene moved to larger slots | bit 1: the
+        call took update_instances_on_device's path) of the last change_instances - hk_debug_last_instance_change (test hook)."""
+        out = (F.u32 * 4)()
+        self.api.call("debug_last_instance_change", self.ctx, out)
+        return tuple(int(v) for v in out)
 
     def update_materials(self, builder, mode=F.TREE_SAH):
         """Material edits on the device (hk_update_materials): the values set on `builder` (SceneBuilder.set_material) since the materials
@@ -1608,6 +1652,10 @@ class HikariPlugin:
     def remove_meshes(self, extents):
         """Meshes that left the builder (SceneBuilder.remove_mesh): the device scene is compacted (Engine.remove_meshes)."""
         self.engine.remove_meshes(extents)
+
+    def change_instances(self, builder, mode=F.TREE_SAH):
+        """Instances spawned, despawned or re-materialed on the builder, in any state of the scene: Engine.change_instances."""
+        self.engine.change_instances(builder, mode)
 
     def deform_meshes(self, items, producer_stream=None):
         """Per frame, every deforming mesh of the scene in one call: Engine.deform_meshes."""

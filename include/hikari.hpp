@@ -296,7 +296,24 @@ class SceneBuilder {  // the Prepare-stage host work: mesh -> BLAS, TLAS, emissi
   uint32_t add_instance(uint32_t mesh, uint32_t material, const float transform[16]) {
     uint32_t id = 0;
     check(hk_scene_builder_add_instance(h_, mesh, material, transform, &id), "hk_scene_builder_add_instance");
+    origins_.push_back(HK_INSTANCE_NEW);
     return id;
+  }
+  // an instance leaves the scene (ids of later instances shift down by one); another material for one
+  void remove_instance(uint32_t instance) {
+    check(hk_scene_builder_remove_instance(h_, instance), "hk_scene_builder_remove_instance");
+    origins_.erase(origins_.begin() + instance);
+  }
+  void set_instance_material(uint32_t instance, uint32_t material) {
+    check(hk_scene_builder_set_instance_material(h_, instance, material), "hk_scene_builder_set_instance_material");
+  }
+  // per instance the id it had when a context last took the instance set, or HK_INSTANCE_NEW: what change_instances hands to
+  // hk_change_scene_instances (the builder shifts ids on removal, so the map is kept here); consumed = reset to the identity
+  const std::vector<uint32_t>& origins() const { return origins_; }
+  // (every call of this header that hands the builder's instance set to a context consumes the list: set_scene, load_scene,
+  // update_instances, change_instances)
+  void consume_origins() const {
+    for (size_t i = 0; i < origins_.size(); ++i) origins_[i] = (uint32_t)i;
   }
   // move an instance (GlobalTransform change -> InstanceEvent::Modified, instance.rs:137-176); the next
   // finish() redoes the instance-level work only and records the old transform as the previous one
@@ -319,13 +336,17 @@ class SceneBuilder {  // the Prepare-stage host work: mesh -> BLAS, TLAS, emissi
 
  private:
   hk_scene_builder* h_ = nullptr;
+  mutable std::vector<uint32_t> origins_;
 };
 
 class Context {
  public:
   explicit Context(int device = 0, uint32_t flags = 0) { check(hk_create(device, flags, &c_), "hk_create"); }
   // the upload of a finished builder whose deferred meshes get their trees built on the device and written back (hk_load_scene)
-  void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_load_scene(c_, b.handle(), tree_mode), "hk_load_scene"); }
+  void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) {
+    check(hk_load_scene(c_, b.handle(), tree_mode), "hk_load_scene");
+    b.consume_origins();
+  }
   // meshes added to the loaded, finished builder since: appended to the device scene without laying it out again (hk_add_meshes)
   void add_meshes(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_add_meshes(c_, b.handle(), tree_mode), "hk_add_meshes"); }
   // meshes that left the builder (SceneBuilder::remove_mesh): the device scene's mesh level compacted behind the frames in flight (hk_remove_meshes)
@@ -420,12 +441,18 @@ class HikariPlugin {
     check(hk_upload_noise(ctx_.get(), noise_rgba8_16x64x64.data(), noise_rgba8_16x64x64.size()), "hk_upload_noise");
   }
   Context& context() { return ctx_; }
-  void set_scene(const SceneBuilder& b) { check(hk_upload_scene(ctx_.get(), b.handle()), "hk_upload_scene"); }
+  void set_scene(const SceneBuilder& b) {
+    check(hk_upload_scene(ctx_.get(), b.handle()), "hk_upload_scene");
+    b.consume_origins();
+  }
   void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { ctx_.load_scene(b, tree_mode); }  // ... with deferred meshes: trees built on the device
   void remove_meshes(const std::vector<HkMeshExtent>& removed) { ctx_.remove_meshes(removed); }  // meshes that leave: compacted on the device
   void add_meshes(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { ctx_.add_meshes(b, tree_mode); }  // meshes that arrive later: appended on the device
   // after SceneBuilder::set_instance_transform + finish: rewrite the instance-level device arrays only
-  void update_instances(const SceneBuilder& b) { check(hk_upload_scene_instances(ctx_.get(), b.handle()), "hk_upload_scene_instances"); }
+  void update_instances(const SceneBuilder& b) {
+    check(hk_upload_scene_instances(ctx_.get(), b.handle()), "hk_upload_scene_instances");
+    b.consume_origins();
+  }
   // instance motion on the device: the poses set on `b` since the last upload / refit; returns how many moved
   uint32_t refit_instances(SceneBuilder& b) {
     uint32_t moved = 0;
@@ -433,6 +460,12 @@ class HikariPlugin {
     return moved;
   }
   void rebuild_trees(uint32_t mode = HK_TREE_SAH) { check(hk_rebuild_scene_trees(ctx_.get(), mode), "hk_rebuild_scene_trees"); }
+  // instances spawned, despawned or re-materialed on `b`, in ANY state of the scene - after deform_meshes and set_instance_transforms_device
+  // too: the host lays the level out, the device writes its own poses, boxes and emitter records over the stale ones and builds both trees
+  void change_instances(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) {
+    check(hk_change_scene_instances(ctx_.get(), b.handle(), b.origins().data(), (uint32_t)b.origins().size(), tree_mode), "hk_change_scene_instances");
+    b.consume_origins();
+  }
   // material edits on the device: the values set on `b` (SceneBuilder::set_material) since the last upload / update; before
   // refit_instances in a frame that also moves instances.  Returns how many records changed
   uint32_t update_materials(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) {
@@ -547,17 +580,30 @@ class HikariMultiGpuPlugin {
   ~HikariMultiGpuPlugin() { hk_multi_destroy(m_); }
   HikariMultiGpuPlugin(const HikariMultiGpuPlugin&) = delete;
   HikariMultiGpuPlugin& operator=(const HikariMultiGpuPlugin&) = delete;
-  void set_scene(const SceneBuilder& b) { check(hk_multi_upload_scene(m_, b.handle()), "hk_multi_upload_scene"); }
-  void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_multi_load_scene(m_, b.handle(), tree_mode), "hk_multi_load_scene"); }
+  void set_scene(const SceneBuilder& b) {
+    check(hk_multi_upload_scene(m_, b.handle()), "hk_multi_upload_scene");
+    b.consume_origins();
+  }
+  void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) {
+    check(hk_multi_load_scene(m_, b.handle(), tree_mode), "hk_multi_load_scene");
+    b.consume_origins();
+  }
   void add_meshes(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_multi_add_meshes(m_, b.handle(), tree_mode), "hk_multi_add_meshes"); }
   void remove_meshes(const std::vector<HkMeshExtent>& removed) { check(hk_multi_remove_meshes(m_, removed.data(), (uint32_t)removed.size()), "hk_multi_remove_meshes"); }
-  void update_instances(const SceneBuilder& b) { check(hk_multi_upload_scene_instances(m_, b.handle()), "hk_multi_upload_scene_instances"); }
+  void update_instances(const SceneBuilder& b) {
+    check(hk_multi_upload_scene_instances(m_, b.handle()), "hk_multi_upload_scene_instances");
+    b.consume_origins();
+  }
   uint32_t refit_instances(SceneBuilder& b) {
     uint32_t moved = 0;
     check(hk_multi_refit_scene_instances(m_, b.handle(), &moved), "hk_multi_refit_scene_instances");
     return moved;
   }
   void rebuild_trees(uint32_t mode = HK_TREE_SAH) { check(hk_multi_rebuild_scene_trees(m_, mode), "hk_multi_rebuild_scene_trees"); }
+  void change_instances(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) {  // HikariPlugin::change_instances on every band's copy of the scene
+    check(hk_multi_change_scene_instances(m_, b.handle(), b.origins().data(), (uint32_t)b.origins().size(), tree_mode), "hk_multi_change_scene_instances");
+    b.consume_origins();
+  }
   uint32_t update_materials(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) {
     uint32_t changed = 0;
     check(hk_multi_update_materials(m_, b.handle(), tree_mode, &changed), "hk_multi_update_materials");

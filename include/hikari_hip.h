@@ -620,9 +620,41 @@ int hk_refit_scene_instances(hk_ctx* ctx, hk_scene_builder* b, uint32_t* moved);
  * hk_upload_scene_instances gives (the reference's path), minus the two host-side SAH builds that dominate it.
  * Materials APPENDED on the builder since the context took its materials travel with the call (a spawned object is a mesh - hk_add_meshes -
  * a material and an instance); a texture id at or above the uploaded texture count is refused (HK_E_INVALID), as hk_update_materials
- * refuses it.  Changed values of existing materials keep going through hk_update_materials. */
+ * refuses it.  Changed values of existing materials keep going through hk_update_materials.
+ * Refused with HK_E_NOT_READY once a mesh was deformed on the device or the poses came from device memory: the mirrors it lays out from
+ * are stale then.  hk_change_scene_instances (below) is the way on in those states. */
 int hk_update_scene_instances(hk_ctx* ctx, hk_scene_builder* b, uint32_t tree_mode);
 int hk_rebuild_scene_trees(hk_ctx* ctx, uint32_t mode);
+/* The instance set changed, in EVERY state of the scene: after mesh deformations (hk_update_mesh_vertices, hk_skin_mesh, hk_deform_meshes*)
+ * and after poses set from device memory (hk_set_instance_transforms_device) too, where hk_update_scene_instances is refused because the
+ * host's copies of boxes, triangle areas and poses are stale.  The LAYOUT of the instance level never is - counts, offsets, which instance
+ * emits, the length of every alias slice follow from topology and materials - so the host lays the new level out as ever into the spare
+ * slot and the device writes its own values over the stale ones, in stream order, with no host wait on a warm call:
+ *   `b` is the scene's builder after any number of hk_scene_builder_add_instance / _remove_instance / _set_instance_material calls (mesh
+ * additions and removals have gone through hk_add_meshes / hk_remove_meshes first); n is its instance count; origins[k] is the id
+ * instance k had in the scene the context holds, or HK_INSTANCE_NEW - the builder shifts ids on removal, so the caller states the map.
+ * Materials appended on the builder travel with the call, as in hk_update_scene_instances.
+ *   - layout, mesh and material words: the host's (hk_scene_builder_finish_instances).  A survivor is an instance of its origin's mesh.
+ *   - a new instance takes the builder's pose and enters at rest.
+ *   - a survivor, poses on the device: keeps the model and inverses the device holds (the builder's transform for it is ignored, as
+ *     hk_set_instance_transforms_device ignores it for unnamed instances) and is at rest.  Poses not on the device: the builder's pose,
+ *     at motion if it differs from the previous one, and the builder's previous-transform bookkeeping advances - hk_update_scene_instances.
+ *   - world boxes: the mesh's current box - the device's for a deformed mesh, the builder's otherwise - through the instance's model.
+ *   - emitter records, surface areas and alias slices: from those boxes and the triangles the device holds.
+ *   - both trees: built on the device in `tree_mode`, as hk_rebuild_scene_trees builds them; a tree of one leaf is the host's.
+ * With HK_TREE_SAH the instance level ends what a fresh hk_upload_scene of the same meshes (current vertices and tree shapes), poses,
+ * instance set and materials leaves.  Where hk_update_scene_instances is accepted the call takes that call's path and leaves its bytes.
+ * When the spare slot has no room the scene moves once, device to device in one launch, to slots half again the need; frames in flight
+ * keep the allocation they were enqueued with (freed once they are past it).  Deformations, device poses, refits and material edits
+ * issued afterwards land on the new ids.  Whether meshes are deformed and whether the poses are the device's stays as it was.
+ * Refused with nothing written: HK_E_INVALID for NULL arguments, an unknown tree_mode, n other than the builder's instance count, an
+ * origin out of range or named twice, a survivor of another mesh than its origin's, a singular or non-finite pose of a new instance (of
+ * any instance while the poses are the host's), a texture id at or above the uploaded count; HK_E_NOT_READY without a scene, for a
+ * builder with unfinished mesh changes or deferred meshes, for a scene walked from its LDS copy (one slot) whose mirrors are stale or
+ * whose meshes are deformed (the rule of hk_add_meshes / hk_remove_meshes), and - in the stale states - for an instance of a mesh that no
+ * instance had used when the mesh level was last laid out on the host (its tree has no leaf boxes; meshes from hk_add_meshes have them). */
+#define HK_INSTANCE_NEW 0xFFFFFFFFu
+int hk_change_scene_instances(hk_ctx* ctx, hk_scene_builder* b, const uint32_t* origins, uint32_t n, uint32_t tree_mode);
 /* Material edits on the DEVICE.  The builder's materials (hk_scene_builder_set_material; the builder need not be finished) are diffed
  * against the materials the context holds, as hk_refit_scene_instances diffs poses; *changed (optional) = the records that differ.
  * With none the call returns HK_OK and enqueues nothing.  Otherwise one of two cases, decided inside the call by the builder's own rule
@@ -804,7 +836,8 @@ int hk_morph_vertices(uint32_t n_vertices, uint32_t n_targets, const float* base
  * derives its history rows takes all of them.  The one-level walk and the shared-transform shortcut are off (hk_traversal_mode reports
  * it).  Case A of hk_update_materials, hk_rebuild_scene_trees, hk_add_meshes, the deformation calls, hk_rebuild_mesh_tree, hk_cast_rays*
  * and hk_update_texture work from device state and stay usable.  hk_upload_scene_instances / hk_upload_instances / hk_upload_scene end
- * the state.  There is no hk_multi_ form, as hk_deform_meshes_device has none: a device pointer lives on one device. */
+ * the state.  Instances are added, removed and re-materialed in it through hk_change_scene_instances, which keeps the device's poses.
+ * There is no hk_multi_ form, as hk_deform_meshes_device has none: a device pointer lives on one device. */
 int hk_set_instance_transforms_device(hk_ctx* ctx, hk_scene_builder* b, const uint32_t* instance_ids, uint32_t n, const void* d_models,
                                       uint32_t stride_bytes, void* producer_stream, uint32_t* d_status);
 /* ... and the way back: waits for the context's streams and copies the models the device holds - the slot the next frame would read - to
@@ -1325,6 +1358,7 @@ int hk_multi_migrate_bands(hk_multi* m, const uint32_t* new_bounds, uint32_t n_b
 /* the root band's context collects every other band's rows of `buffer` on its own device (peer copies ordered by events, no host wait) */
 int hk_multi_gather(hk_multi* m, uint32_t buffer, uint32_t root);  /* hk_set_band_bounds on every band's context */
 int hk_multi_update_scene_instances(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode);  /* hk_update_scene_instances on every band's replica */
+int hk_multi_change_scene_instances(hk_multi* m, hk_scene_builder* b, const uint32_t* origins, uint32_t n, uint32_t tree_mode);  /* hk_change_scene_instances on every band's replica (the builder is finished once) */
 int hk_multi_upload_textures(hk_multi* m, const HkImageDesc* images, uint32_t n_images);
 /* hk_update_materials / hk_update_texture on every band's replica (an emitter switched on or off finishes the builder once) */
 int hk_multi_update_materials(hk_multi* m, hk_scene_builder* b, uint32_t tree_mode, uint32_t* changed);

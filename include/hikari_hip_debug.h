@@ -61,6 +61,13 @@ int hk_debug_last_deform(hk_ctx* ctx, uint32_t out[6]);
  * instances, of the named emitters, of the two trees; the slot copy of a two-slot scene and event records not counted), out[1] 1 if it
  * copied the builder's mesh boxes to the device (the first call for an instance list), else 0.  A refused call leaves them as they were. */
 int hk_debug_last_pose(hk_ctx* ctx, uint32_t out[2]);
+/* What the last accepted hk_change_scene_instances did: out[0] the kernel launches of its device path - the move of a scene whose spare
+ * slot had no room, the staged copy of the laid-out level, the carry of the survivors' poses (only where the poses are the device's),
+ * the derive pass, the emitters' pass, the refit of a single-leaf tree, the copy of the previous models of instances at motion - which do
+ * not follow the number of instances or edits; the two tree builds (hk_rebuild_scene_trees' launches) and event records are not
+ * counted.  out[1] the instances carried over, out[2] the new ones, out[3] bit 0: the scene moved to larger slots, bit 1: the mirrors
+ * were current and the call took hk_update_scene_instances' path (out[0] is 0 then).  A refused call leaves them as they were. */
+int hk_debug_last_instance_change(hk_ctx* ctx, uint32_t out[4]);
 /* What the last accepted hk_update_textures_device did: out[0] its items, out[1] its kernel launches (event records not counted; a scene
  * laid out first because an hk_upload_textures was pending is not part of it), out[2] the texels it wrote, saturated at 2^32 - 1.  A
  * refused call, or one with n == 0, leaves them as they were. */

@@ -433,3 +433,11 @@ pub fn cast_rays(context: &HipContext, rays: &[hk::HkRay], flags: u32) -> Result
     unsafe { hits.set_len(rays.len()) };
     Ok(hits)
 }
+
+/// Instances spawned, despawned or given another material on a host that keeps its scene in an `hk_scene_builder`
+/// (`hk_change_scene_instances`): works in every state of the scene, after mesh deformations and poses set from device memory too,
+/// where `hk_update_scene_instances` is refused.  `origins[k]` is the id instance `k` of the builder had in the scene the context
+/// holds, or `hk::HK_INSTANCE_NEW`; `tree_mode` = `hk::HK_TREE_SAH` for the reference's trees.
+pub fn change_instances(context: &HipContext, builder: *mut hk::HkSceneBuilder, origins: &[u32], tree_mode: u32) -> Result<(), HipError> {
+    check(unsafe { hk::hk_change_scene_instances(context.ctx, builder, origins.as_ptr(), origins.len() as u32, tree_mode) })
+}
