@@ -668,7 +668,7 @@ int ensure_wide(hk_ctx* c, bool with_spill) {
   }
   if (blas_slots > c->wide_blas_slots) {
     if (c->wide_blas) { HK_HIP(hipStreamSynchronize(c->stream)); (void)hipFree(c->wide_blas); c->wide_blas = nullptr; }
-    const size_t cap = std::max(blas_slots, c->node_cap);  // (room for the trees hk_add_meshes may append: it copies these records, it does not derive them again)
+    const size_t cap = std::max(blas_slots, c->mesh.node_cap);  // (room for the trees hk_add_meshes may append: it copies these records, it does not derive them again)
     HK_HIP(hipMalloc((void**)&c->wide_blas, cap * 128));
     c->wide_blas_slots = cap;
     c->wide_blas_dirty = true;
@@ -684,7 +684,7 @@ int ensure_wide(hk_ctx* c, bool with_spill) {
   }
   if (n_prim > c->wide_rank_primitives) {
     if (c->wide_blas_rank) { HK_HIP(hipStreamSynchronize(c->stream)); (void)hipFree(c->wide_blas_rank); c->wide_blas_rank = nullptr; }
-    const size_t cap = std::max<size_t>(std::max(n_prim, c->prim_cap), 1);
+    const size_t cap = std::max<size_t>(std::max(n_prim, c->mesh.prim_cap), 1);
     HK_HIP(hipMalloc((void**)&c->wide_blas_rank, cap * sizeof(uint32_t)));
     HK_HIP(hipMemsetAsync(c->wide_blas_rank, 0xFF, cap * sizeof(uint32_t), c->stream));  // (a primitive no mesh tree names: a rank that is at least deterministic)
     c->wide_rank_primitives = cap;

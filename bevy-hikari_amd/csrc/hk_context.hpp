@@ -5,6 +5,7 @@
 //   scene_refit.hip   instance motion and instance-set changes on the device (hk_refit_scene_instances, hk_rebuild_scene_trees, ...)
 //   scene_load.hip    mesh trees built on the device at scene load (hk_load_scene); scene_append.hip: meshes appended later (hk_add_meshes);
 //                     scene_remove.hip: meshes removed, the mesh level compacted (hk_remove_meshes)
+//   scene_move.hip    the scene moved to a new allocation in stream order, for the edits above and below (move_begin ... move_commit, retire)
 //   scene_instances.hip  the instance set changed from device state: after deformations and device poses (hk_change_scene_instances)
 //   probes.hip        measurement hooks (hk_measure_*, hk_debug_math)
 #pragma once
@@ -98,6 +99,7 @@ inline uint32_t hash_u32(uint32_t value) {  // utils.wgsl:15-24
   return state;
 }
 inline float as_f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // a material as the device holds it: four float4 (base colour, emissive, roughness / metallic / reflectance, the four texture ids)
 inline void material_rows(const HkMaterial& m, float4 rows[4]) {
   rows[0] = make_float4(m.base_color[0], m.base_color[1], m.base_color[2], m.base_color[3]);
@@ -111,6 +113,16 @@ inline void material_rows(const HkMaterial& m, float4 rows[4]) {
 
 // byte offsets of the arrays inside the instance-level region of the scene allocation
 struct DynOffsets { size_t tlas, instances, prev_models, light_lo, light_hi, emissives, alias, materials, tex_info, srgb_lut, flat; uint32_t flat_count, flat_orderings; };
+
+struct MeshSizes { size_t nodes, prims, verts; };   // sizes or capacities of the mesh-level lists, in elements (nodes: per ordering)
+// The mesh-level region of the scene allocation (mesh_region_layout).  Its sub-arrays keep CAPACITIES behind their contents: nodes per ordering
+// - the stride between two orderings, DScene::blas_stride - primitives, vertices.  A host layout leaves them equal to the mirrors' sizes; an
+// edit that does not fit moves the scene (scene_move.hip).
+struct MeshRegion {
+  size_t node_cap = 0, prim_cap = 0, vert_cap = 0;
+  size_t nodes = 0, v0 = 0, v1 = 0, v2 = 0, vn = 0, vuv = 0;  // byte offsets of the sub-arrays inside the region
+  size_t bytes = 0;                                           // of the region (covers the capacities)
+};
 
 struct hk_ctx {
   int device = 0;
@@ -201,7 +213,8 @@ struct hk_ctx {
 
   // device scene
   uint8_t* scene_mem = nullptr;  // every scene array in one allocation (so small scenes can be staged in LDS by one copy loop)
-  size_t dyn_capacity = 0, static_bytes = 0;
+  size_t dyn_capacity = 0;
+  MeshRegion mesh;               // the mesh-level region behind the slots
   // Scenes too big for the LDS copy keep TWO slots of the instance-level region, [slot 0][slot 1][mesh region]: an
   // instance-only update goes through pinned staging into the slot the frames in flight do NOT read, in stream
   // order, so neither the host nor the GPU waits (animated scenes must not stall on the host).
@@ -217,13 +230,8 @@ struct hk_ctx {
   hipEvent_t staging_done[2] = {nullptr, nullptr};
   bool staging_pending[2] = {false, false};
   uint64_t async_instance_uploads = 0;
-  size_t st_nodes = 0, st_v0 = 0, st_v1 = 0, st_v2 = 0, st_vn = 0, st_vuv = 0;  // offsets inside the mesh-level region
-  // Capacities of the mesh-level sub-arrays, in elements (hk_add_meshes, scene_append.hip): nodes per ordering - the stride between two
-  // orderings, DScene::blas_stride - primitives per triangle plane, vertices per vertex plane.  A host layout leaves them equal to the
-  // sizes of the mirrors; an append that does not fit moves the scene to a new allocation with room to spare (static_bytes covers the
-  // capacities).  What such a move replaces - or a grown build scratch - is freed once the event recorded behind the move has passed,
-  // polled at later calls: frames in flight go on reading it.
-  size_t node_cap = 0, prim_cap = 0, vert_cap = 0;
+  // What a move of the scene replaces (scene_move.hip) - or a grown build scratch - is freed once the event recorded behind the move has
+  // passed, polled at later calls: frames in flight go on reading it.
   struct Retired { void* p; hipEvent_t done; };
   std::vector<Retired> retired;
   uint32_t last_add[5] = {0, 0, 0, 0, 0};   // hk_debug_last_add
@@ -461,16 +469,17 @@ int sync_all(hk_ctx* c);
 int finalize_scene(hk_ctx* c);
 // the instance-level region laid out from the mirrors into `blob` (finalize_scene; hk_change_scene_instances, which lets the device
 // overwrite what the mirrors hold stale), and c->dyn_blob through pinned staging into the slot in use of a two-slot scene
-int build_dynamic_region(hk_ctx* c, Blob& blob, DynOffsets& o, size_t static_bytes);
+int build_dynamic_region(hk_ctx* c, Blob& blob, DynOffsets& o, size_t mesh_bytes);
 int upload_slot_staged(hk_ctx* c);
 void update_shared_transform(hk_ctx* c);
 void point_scene_at_slot(hk_ctx* c);
+void repoint_scene(hk_ctx* c);   // ... where the slot or the allocation changed under a scene in use: the refit's own previous-model plane stays
 size_t fold_leaf_navigators(std::vector<float4>& lo, std::vector<float4>& hi, size_t begin, size_t count);
 void thread_orderings(const std::vector<HkNode>& src, const std::vector<std::pair<uint32_t, uint32_t>>& ranges, int orderings, std::vector<std::vector<HkNode>>& out);
 // whether a scene of these mirror sizes keeps eight direction-threaded orderings (the estimate finalize_scene decides by)
 bool wants_threaded(const hk_ctx* c, size_t n_nodes, size_t n_prims, size_t n_verts);
-// offsets of the mesh-level sub-arrays (nodes, v0, v1, v2, vn, vuv) for these capacities; returns the bytes of the region
-size_t mesh_region_layout(size_t node_cap, size_t prim_cap, size_t vert_cap, uint32_t orderings, size_t off[6]);
+// the mesh-level region for these capacities: offsets of the sub-arrays (nodes, v0, v1, v2, vn, vuv) and its bytes
+MeshRegion mesh_region_layout(const MeshSizes& caps, uint32_t orderings);
 // ---- scene_load.hip
 struct LoadMesh {
   uint32_t id;
@@ -480,11 +489,31 @@ struct LoadMesh {
 // the trees of `meshes` built into their node ranges of every ordering, then read back into the builder and the mirror; `reference_if_unused`:
 // a range no instance uses is left in reference form, as the host layout leaves it (hk_load_scene)
 int build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMesh>& meshes, uint32_t mode, uint32_t* launches, bool reference_if_unused);
-// ---- scene_append.hip
+// ---- scene_move.hip: a two-slot scene moved to a new allocation in stream order.  move_begin makes what the move needs and writes nothing
+// of the context; the caller enqueues what fills the new allocation (move_planes lists it); move_commit switches the context over and
+// retires what was replaced; until then move_abort leaves the scene the context had.
 void retire(hk_ctx* c, void* p, hipEvent_t done);   // free `p` once `done` has passed (takes the event over)
 void poll_retired(hk_ctx* c, bool wait);            // ... checked here, only behind a wait for the context's streams (hipFree may wait by itself); wait: free everything
-int grow_instance_slots(hk_ctx* c, size_t dyn_capacity);   // a two-slot scene moved, device to device in one launch, to an allocation whose instance-level slots hold `dyn_capacity` bytes each (hk_change_scene_instances)
-int take_appended_materials(hk_ctx* c, const hk_scene_builder* b);  // hk_update_scene_instances: materials the builder holds beyond the context's (the caller takes them back if the upload is refused)
+MeshSizes move_room(const MeshSizes& need);         // the capacities a moved scene gets: half again the need, primitives and vertices in fours
+struct SceneMove {
+  MeshRegion mesh;               // of the new allocation `mem`, behind two instance-level slots of `dyn_capacity` bytes
+  size_t dyn_capacity = 0;
+  uint8_t *mem = nullptr, *extra = nullptr;   // extra: a device block of the caller's that lives as long as the move (hk_remove_meshes: its run table)
+  float4* wide = nullptr;        // new wide records / ranks of the mesh trees, NULL where the move does not take them along
+  uint32_t* rank = nullptr;
+  hipEvent_t done[4] = {nullptr, nullptr, nullptr, nullptr};  // behind the move, one per allocation above (the last only with `extra`)
+};
+// one sub-array that moves: its list (0 nodes, 1 primitives, 2 vertices), its element size 1 << shift, its capacities in elements
+struct MovePlane { const uint8_t* src; uint8_t* dst; uint32_t list, shift; size_t old_cap, new_cap; };
+constexpr uint32_t HK_MOVE_PLANES = 8 + 3 + 2 + 2;   // (move_begin: `refusal` is the caller's text for a failed allocation; the ranks' 0xFF fill is enqueued there)
+int move_begin(const hk_ctx* c, const MeshSizes& caps, size_t dyn_capacity, bool with_wide, bool with_rank, size_t extra_bytes, const char* refusal, SceneMove* m);
+uint32_t move_planes(const hk_ctx* c, const SceneMove& m, MovePlane out[HK_MOVE_PLANES]);
+void move_abort(const hk_ctx* c, SceneMove* m, bool enqueued);   // enqueued: work on c->stream may name the new allocations - it is waited for first
+int move_commit(hk_ctx* c, SceneMove* m, int slot);        // `slot`: the instance-level slot in use from here on
+int grow_instance_slots(hk_ctx* c, size_t dyn_capacity);   // (scene_append.hip) a two-slot scene moved, device to device in one launch, to an allocation whose instance-level slots hold `dyn_capacity` bytes each (hk_change_scene_instances)
+// ---- scene_instances.hip: materials the builder holds beyond the context's - their texture ids checked, nothing written; taken into the mirror
+int check_appended_materials(const hk_ctx* c, const hk_scene_builder* b);
+int take_appended_materials(hk_ctx* c, const hk_scene_builder* b);
 // ---- mesh_deform.hip, for hk_remove_meshes (scene_remove.hip): the records of the deformable meshes; then, `runs` being the surviving
 // intervals per list (nodes, primitives, vertices), every record rebased and the meshes that lie in no run dropped - their device
 // allocations go to `freed` for the caller to retire

@@ -338,9 +338,9 @@ int refit_mesh(hk_ctx* c, DeformMesh* d) {
   const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
   uint8_t* sbase = c->scene_mem + slots;
   const uint32_t p0 = d->mesh.primitive;
-  launch_mesh_triangles(c->stream, d->pos, (float4*)(sbase + c->st_v0) + p0, (float4*)(sbase + c->st_v1) + p0, (float4*)(sbase + c->st_v2) + p0, d->n_tris, d->tree.tri_lo,
+  launch_mesh_triangles(c->stream, d->pos, (float4*)(sbase + c->mesh.v0) + p0, (float4*)(sbase + c->mesh.v1) + p0, (float4*)(sbase + c->mesh.v2) + p0, d->n_tris, d->tree.tri_lo,
                         d->tree.tri_hi);
-  launch_mesh_tree_refit(c->stream, d->tree, (float4*)(sbase + c->st_nodes) + 2 * (size_t)d->mesh.node_offset, 2 * c->node_cap, c->threaded ? 8u : 1u);
+  launch_mesh_tree_refit(c->stream, d->tree, (float4*)(sbase + c->mesh.nodes) + 2 * (size_t)d->mesh.node_offset, 2 * c->mesh.node_cap, c->threaded ? 8u : 1u);
   HK_HIP(hipGetLastError());
   d->deformed = d->pending = d->have_boxes = true;
   c->deform_pending = true;
@@ -369,7 +369,7 @@ int deform(hk_ctx* c, DeformMesh* d, int k, Fill fill) {
   // waits, not host waits
   if ((rc = join_all(c))) return rc;
   const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
-  float4* vn = (float4*)(c->scene_mem + slots + c->st_vn) + d->mesh.vertex;
+  float4* vn = (float4*)(c->scene_mem + slots + c->mesh.vn) + d->mesh.vertex;
   HK_HIP(hipMemsetAsync(d->box, 0xFF, 12, c->stream));
   HK_HIP(hipMemsetAsync(d->box + 3, 0, 12, c->stream));
   fill(vn);
@@ -766,13 +766,13 @@ int deform_batch(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, bool de
       }
     }
     t.pos = d->pos;
-    t.vn = (float4*)(sbase + c->st_vn) + d->mesh.vertex;
+    t.vn = (float4*)(sbase + c->mesh.vn) + d->mesh.vertex;
     t.box = d->box;
-    t.v0 = (float4*)(sbase + c->st_v0) + d->mesh.primitive;
-    t.v1 = (float4*)(sbase + c->st_v1) + d->mesh.primitive;
-    t.v2 = (float4*)(sbase + c->st_v2) + d->mesh.primitive;
+    t.v0 = (float4*)(sbase + c->mesh.v0) + d->mesh.primitive;
+    t.v1 = (float4*)(sbase + c->mesh.v1) + d->mesh.primitive;
+    t.v2 = (float4*)(sbase + c->mesh.v2) + d->mesh.primitive;
     t.tree = d->tree;
-    t.nodes = (float4*)(sbase + c->st_nodes) + 2 * (size_t)d->mesh.node_offset;
+    t.nodes = (float4*)(sbase + c->mesh.nodes) + 2 * (size_t)d->mesh.node_offset;
     table[i] = t;
     const size_t threads[3] = {t.n_vertices, t.n_tris, (size_t)(2u * t.n_tris - 1u) * orderings};
     for (int s = 0; s < 3; ++s)
@@ -786,7 +786,7 @@ int deform_batch(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, bool de
     HK_HIP(hipStreamWaitEvent(c->stream, c->df_src_ready, 0));
   }
   c->scene_epoch += n;  // (scene memory is written from here on: hk_context.hpp, primary-ray pipelining - a refusal above leaves it alone)
-  launch_deform_batch(c->stream, table, n, bl[0], (uint32_t)blocks[0], bl[1], (uint32_t)blocks[1], bl[2], (uint32_t)blocks[2], 2 * c->node_cap, orderings,
+  launch_deform_batch(c->stream, table, n, bl[0], (uint32_t)blocks[0], bl[1], (uint32_t)blocks[1], bl[2], (uint32_t)blocks[2], 2 * c->mesh.node_cap, orderings,
                       producer ? c->df_src_read : nullptr, bl[3], (uint32_t)blocks[3]);
   HK_HIP(hipGetLastError());
   if (producer) HK_HIP(hipStreamWaitEvent(producer, c->df_src_read, 0));
@@ -872,17 +872,17 @@ int hk_rebuild_mesh_tree(hk_ctx* c, const HkMeshIndex* mesh, uint32_t mode) {
   uint8_t* sbase = c->scene_mem + slots;
   if (!d->have_boxes) {
     const uint32_t p0 = d->mesh.primitive;
-    launch_mesh_triangle_boxes(c->stream, (const float4*)(sbase + c->st_v0) + p0, (const float4*)(sbase + c->st_v1) + p0, (const float4*)(sbase + c->st_v2) + p0, n,
+    launch_mesh_triangle_boxes(c->stream, (const float4*)(sbase + c->mesh.v0) + p0, (const float4*)(sbase + c->mesh.v1) + p0, (const float4*)(sbase + c->mesh.v2) + p0, n,
                                d->tree.tri_lo, d->tree.tri_hi);
     d->have_boxes = true;
   }
-  float4* lo = (float4*)(sbase + c->st_nodes) + 2 * (size_t)d->mesh.node_offset;
+  float4* lo = (float4*)(sbase + c->mesh.nodes) + 2 * (size_t)d->mesh.node_offset;
   TreeBuild build;  // over the mesh's triangle boxes, into its node range of every ordering; the refit's topology is replaced
   build.mode = mode == HK_TREE_SAH ? 1 : 0;
   build.n = n;
   build.box_lo = d->tree.tri_lo; build.box_hi = d->tree.tri_hi;
   build.lo = lo; build.hi = lo + 1; build.stride = 2u;
-  build.orderings = c->threaded ? 8u : 1u; build.ord_stride = 2 * c->node_cap;
+  build.orderings = c->threaded ? 8u : 1u; build.ord_stride = 2 * c->mesh.node_cap;
   build.mesh_tree = true; build.keep = &d->tree;
   build.one_workgroup_top = c->mesh_rebuild_one_workgroup;
   build.scratch = c->lbvh_scratch;
@@ -932,7 +932,7 @@ int hk_debug_read_mesh_nodes(hk_ctx* c, HkNode* out, uint32_t cap, uint32_t* cou
   const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
   static_assert(sizeof(HkNode) == 32, "HkNode is two float4");
   for (uint32_t k = 0; k < o; ++k)  // (the orderings lie one node CAPACITY apart: hk_add_meshes)
-    HK_HIP(hipMemcpy(out + (size_t)k * n, c->scene_mem + slots + c->st_nodes + (size_t)k * c->node_cap * 32, (size_t)n * 32, hipMemcpyDeviceToHost));
+    HK_HIP(hipMemcpy(out + (size_t)k * n, c->scene_mem + slots + c->mesh.nodes + (size_t)k * c->mesh.node_cap * 32, (size_t)n * 32, hipMemcpyDeviceToHost));
   return HK_OK;
 }
 
@@ -962,9 +962,9 @@ int hk_debug_read_mesh_geometry(hk_ctx* c, const HkMeshIndex* mesh, float* posit
     if (!positions && !normals && !triangles && !box) return HK_OK;
     HK_REQUIRE(positions && normals && triangles && box && vertex_cap >= nv && triangle_cap >= nt, HK_E_INVALID, "need room for %u vertices and %u triangles", nv, nt);
     const uint8_t* sbase = c->scene_mem + (c->two_slots ? 2 : 1) * c->dyn_capacity;
-    HK_HIP(hipMemcpy(normals, (const float4*)(sbase + c->st_vn) + mesh->vertex, (size_t)nv * 16, hipMemcpyDeviceToHost));
+    HK_HIP(hipMemcpy(normals, (const float4*)(sbase + c->mesh.vn) + mesh->vertex, (size_t)nv * 16, hipMemcpyDeviceToHost));
     std::vector<float4> plane(nt);
-    const size_t planes[3] = {c->st_v0, c->st_v1, c->st_v2};
+    const size_t planes[3] = {c->mesh.v0, c->mesh.v1, c->mesh.v2};
     memset(positions, 0, (size_t)nv * 16);
     for (int k = 0; k < 3; ++k) {
       HK_HIP(hipMemcpy(plane.data(), (const float4*)(sbase + planes[k]) + mesh->primitive, (size_t)nt * 16, hipMemcpyDeviceToHost));
@@ -997,9 +997,9 @@ int hk_debug_read_mesh_geometry(hk_ctx* c, const HkMeshIndex* mesh, float* posit
   const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
   const uint8_t* sbase = c->scene_mem + slots;
   HK_HIP(hipMemcpy(positions, d->pos, (size_t)nv * 16, hipMemcpyDeviceToHost));
-  HK_HIP(hipMemcpy(normals, (const float4*)(sbase + c->st_vn) + d->mesh.vertex, (size_t)nv * 16, hipMemcpyDeviceToHost));
+  HK_HIP(hipMemcpy(normals, (const float4*)(sbase + c->mesh.vn) + d->mesh.vertex, (size_t)nv * 16, hipMemcpyDeviceToHost));
   std::vector<float4> plane(nt);
-  const size_t planes[3] = {c->st_v0, c->st_v1, c->st_v2};
+  const size_t planes[3] = {c->mesh.v0, c->mesh.v1, c->mesh.v2};
   for (int k = 0; k < 3; ++k) {
     HK_HIP(hipMemcpy(plane.data(), (const float4*)(sbase + planes[k]) + d->mesh.primitive, (size_t)nt * 16, hipMemcpyDeviceToHost));
     for (uint32_t t = 0; t < nt; ++t) memcpy(triangles + 12 * (size_t)t + 4 * k, &plane[t], 16);

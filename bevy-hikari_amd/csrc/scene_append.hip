@@ -3,119 +3,29 @@
 // CAPACITIES behind its sub-arrays: the new meshes' records go through pinned staging to the end of the planes, their trees are built
 // into the end of every ordering's node plane (the forest build of hk_load_scene) or - trees the host built - laid out for their ranges
 // alone, and nothing of the existing meshes or of the instance level is read or written.  When the room runs out the whole scene moves
-// once, device to device in stream order, to an allocation half again as large; the old one is freed when the frames in flight are past it.
+// once, device to device in stream order, to an allocation half again as large (scene_move.hip); the old one is freed behind the frames in flight.
 #include "hk_context.hpp"
 
 using namespace hk;
 using namespace hkd;
 
-namespace hk {
-void retire(hk_ctx* c, void* p, hipEvent_t done) { c->retired.push_back(hk_ctx::Retired{p, done}); }
-// hipFree may wait for the device by itself: this is called only where the context has just waited for its streams anyway (sync_all, the
-// wait of build_on_device, hk_destroy), never on the per-frame path - until then a retired allocation merely stays allocated
-void poll_retired(hk_ctx* c, bool wait) {
-  size_t kept = 0;
-  for (const hk_ctx::Retired& r : c->retired) {
-    if (!wait && hipEventQuery(r.done) != hipSuccess) {
-      c->retired[kept++] = r;
-      continue;
-    }
-    (void)hipFree(r.p);
-    (void)hipEventDestroy(r.done);
-  }
-  c->retired.resize(kept);
-}
-
-// hk_update_scene_instances: a spawned object is a mesh, a material and an instance - materials appended on the builder since the
-// context took its materials travel with the instance-level layout of that call (changed VALUES of existing ones: hk_update_materials)
-int take_appended_materials(hk_ctx* c, const hk_scene_builder* b) {
-  const HkMaterial* mats = nullptr;
-  uint32_t nm = 0;
-  builder_materials(b, &mats, &nm);
-  if (!c->have_materials || nm <= c->materials.size()) return HK_OK;
-  const uint32_t n_tex = (uint32_t)c->textures.size();
-  for (uint32_t i = (uint32_t)c->materials.size(); i < nm; ++i)
-    for (uint32_t id : {mats[i].base_color_texture, mats[i].emissive_texture, mats[i].metallic_roughness_texture, mats[i].occlusion_texture})
-      HK_REQUIRE(id == HK_NO_TEXTURE || id < n_tex, HK_E_INVALID, "material %u references texture %u but only %u textures are uploaded", i, id, n_tex);
-  c->materials.insert(c->materials.end(), mats + c->materials.size(), mats + nm);
-  return HK_OK;
-}
-}  // namespace hk
-
 namespace {
-struct Sizes { size_t nodes, prims, verts; };
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// The scene moved to an allocation with these capacities: both instance-level slots, every ordering's node plane, the triangle and vertex
-// planes and - where they exist - the wide records and ranks of the mesh trees, in one launch behind everything enqueued.  Nothing of the
-// context changes unless every allocation succeeded.  `dyn_capacity`: the bytes of an instance-level slot in the new allocation, at least
-// today's (hk_change_scene_instances grows them; an append keeps them) - the bytes of the slot in use go to the front of its new slot.
-int relocate(hk_ctx* c, const Sizes& cap, size_t dyn_capacity) {
-  const uint32_t orderings = c->threaded ? 8u : 1u;
-  const size_t old_slots = 2 * c->dyn_capacity, slots = 2 * dyn_capacity;
-  size_t off[6];
-  const size_t bytes = mesh_region_layout(cap.nodes, cap.prims, cap.verts, orderings, off);
-  const size_t old_off[6] = {c->st_nodes, c->st_v0, c->st_v1, c->st_v2, c->st_vn, c->st_vuv};
-  const size_t n_nodes = c->asset_nodes.size(), n_prims = c->primitives.size(), n_verts = c->vertices.size();
-  uint8_t* mem = nullptr;
-  float4* wide = nullptr;
-  uint32_t* rank = nullptr;
-  hipEvent_t done[3] = {nullptr, nullptr, nullptr};  // one per allocation replaced
-  auto undo = [&]() {
-    for (void* q : {(void*)mem, (void*)wide, (void*)rank})
-      if (q) (void)hipFree(q);
-    for (hipEvent_t e : done)
-      if (e) (void)hipEventDestroy(e);
-  };
-  const double t0 = now_ms();
-  bool ok = hipMalloc((void**)&mem, slots + bytes) == hipSuccess;
-  for (int k = 0; k < 3 && ok; ++k) ok = hipEventCreateWithFlags(&done[k], hipEventDisableTiming) == hipSuccess;
-  if (ok && c->wide_blas) ok = hipMalloc((void**)&wide, cap.nodes * 128) == hipSuccess;
-  if (ok && c->wide_blas_rank) ok = hipMalloc((void**)&rank, cap.prims * 4) == hipSuccess && hipMemsetAsync(rank, 0xFF, cap.prims * 4, c->stream) == hipSuccess;
-  if (!ok) {
-    const hipError_t e = hipGetLastError();
-    undo();
-    HK_REQUIRE(false, HK_E_HIP, "no room for the grown scene: %s", hipGetErrorString(e));
-  }
-  c->last_add_ms[0] = now_ms() - t0;
-  const double t1 = now_ms();
+// The scene copied into the allocation of `m` in ONE launch - both instance-level slots where they keep their size, else the slot in use
+// (the spare one is about to be written); of every plane what the mirrors hold - and the switch.  A failure leaves the scene the context had.
+int copy_and_commit(hk_ctx* c, SceneMove* m) {
+  const size_t held[3] = {c->asset_nodes.size(), c->primitives.size(), c->vertices.size()};
   CopySegments s;
-  const uint8_t *from = c->scene_mem + old_slots, *const old_mem = c->scene_mem;
-  uint8_t* to = mem + slots;
-  if (dyn_capacity == c->dyn_capacity) s.add(mem, old_mem, slots);
-  else s.add(mem + (size_t)c->slot * dyn_capacity, old_mem + (size_t)c->slot * c->dyn_capacity, c->dyn_capacity);  // (the spare slot is about to be written)
-  for (uint32_t o = 0; o < orderings; ++o) s.add(to + off[0] + (size_t)o * cap.nodes * 32, from + old_off[0] + (size_t)o * c->node_cap * 32, n_nodes * 32);
-  for (int k = 1; k <= 3; ++k) s.add(to + off[k], from + old_off[k], n_prims * 16);
-  s.add(to + off[4], from + old_off[4], n_verts * 16);
-  s.add(to + off[5], from + old_off[5], n_verts * 8);
-  if (wide) s.add(wide, c->wide_blas, std::min(c->wide_blas_slots, n_nodes) * 128);
-  if (rank) s.add(rank, c->wide_blas_rank, std::min(c->wide_rank_primitives, n_prims) * 4);
-  ok = !s.overflow;  // (more sub-arrays than the table holds: nothing is enqueued)
-  if (ok) launch_copy_segments(c->stream, s);
-  ok = ok && hipGetLastError() == hipSuccess;
-  for (int k = 0; k < 3 && ok; ++k) ok = hipEventRecord(done[k], c->stream) == hipSuccess;
-  if (!ok) {
+  if (m->dyn_capacity == c->dyn_capacity) s.add(m->mem, c->scene_mem, 2 * c->dyn_capacity);
+  else s.add(m->mem + (size_t)c->slot * m->dyn_capacity, c->scene_mem + (size_t)c->slot * c->dyn_capacity, c->dyn_capacity);
+  MovePlane planes[HK_MOVE_PLANES];
+  for (uint32_t k = 0, n = move_planes(c, *m, planes); k < n; ++k) s.add(planes[k].dst, planes[k].src, std::min(planes[k].old_cap, held[planes[k].list]) << planes[k].shift);
+  if (!s.overflow) launch_copy_segments(c->stream, s);  // (more sub-arrays than the table holds: nothing is enqueued)
+  if (s.overflow || hipGetLastError() != hipSuccess) {
     const hipError_t e = hipGetLastError();
-    (void)hipStreamSynchronize(c->stream);  // (the copy may be enqueued: its targets must outlive it)
-    undo();
+    move_abort(c, m, true);  // (the copy may be enqueued)
     HK_REQUIRE(false, HK_E_HIP, "the move of the scene failed: %s", hipGetErrorString(e));
   }
-  // ---- the switch: frames enqueued from here on read the new allocation, the ones in flight the old one until `done`
-  retire(c, c->scene_mem, done[0]);
-  if (wide) { retire(c, c->wide_blas, done[1]); c->wide_blas = wide; c->wide_blas_slots = cap.nodes; }
-  else (void)hipEventDestroy(done[1]);
-  if (rank) { retire(c, c->wide_blas_rank, done[2]); c->wide_blas_rank = rank; c->wide_rank_primitives = cap.prims; }
-  else (void)hipEventDestroy(done[2]);
-  c->scene_mem = mem;
-  c->dyn_capacity = dyn_capacity;
-  c->node_cap = cap.nodes; c->prim_cap = cap.prims; c->vert_cap = cap.verts;
-  c->st_nodes = off[0]; c->st_v0 = off[1]; c->st_v1 = off[2]; c->st_v2 = off[3]; c->st_vn = off[4]; c->st_vuv = off[5];
-  c->static_bytes = bytes;
-  const float4* prev = c->d_prev_models;
-  point_scene_at_slot(c);
-  if (prev == c->rf_prev_models) c->d_prev_models = prev;  // (the refit's own plane is not part of the slot)
-  c->last_add_ms[1] = now_ms() - t1;
-  return HK_OK;
+  return move_commit(c, m, c->slot);
 }
 
 // final form of the trees the host built, for the node span [first, first + count) that holds them: every ordering threaded, leaf boxes
@@ -159,14 +69,11 @@ int layout_host_trees(const hk_ctx* c, const std::vector<LoadMesh>& meshes, uint
 }
 
 }  // namespace
-// hk_change_scene_instances: the same move for larger instance-level slots, the mesh level keeping its capacities (the report of the last
-// hk_add_meshes stays that call's)
+// hk_change_scene_instances: the same move for larger instance-level slots, the mesh level keeping its capacities
 int hk::grow_instance_slots(hk_ctx* c, size_t dyn_capacity) {
-  double ms[4];
-  std::copy(c->last_add_ms, c->last_add_ms + 4, ms);
-  const int rc = relocate(c, Sizes{c->node_cap, c->prim_cap, c->vert_cap}, dyn_capacity);
-  std::copy(ms, ms + 4, c->last_add_ms);
-  return rc;
+  SceneMove m;
+  const int rc = move_begin(c, MeshSizes{c->mesh.node_cap, c->mesh.prim_cap, c->mesh.vert_cap}, dyn_capacity, c->wide_blas, c->wide_blas_rank, 0, "no room for the grown scene", &m);
+  return rc ? rc : copy_and_commit(c, &m);
 }
 namespace {
 
@@ -209,7 +116,7 @@ int hk_add_meshes(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode) {
   HK_REQUIRE(!builder_has_standin_trees(b), HK_E_NOT_READY,
              "the builder holds stand-in instance trees (hk_scene_builder_finish_instances): finish it with hk_scene_builder_finish before hk_add_meshes");
   // ---- the builder's first meshes are the context's
-  const Sizes old{c->asset_nodes.size(), c->primitives.size(), c->vertices.size()};
+  const MeshSizes old{c->asset_nodes.size(), c->primitives.size(), c->vertices.size()};
   const uint32_t n_meshes = builder_mesh_count(b);
   // (the builder concatenates in id order: the records are sorted, and a search finds a mesh without a copy of all of them)
   auto record = [b](uint32_t id) { HkMeshIndex m{}; (void)hk_scene_builder_mesh_index(b, id, &m); return m; };
@@ -255,7 +162,7 @@ int hk_add_meshes(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode) {
   for (uint32_t id = first_new; id < n_meshes; ++id) n_host_built += builder_pending_mesh(b, id, nullptr) ? 0u : 1u;
   if (c->mesh_dirty || !c->scene_mem) return full_layout(c, b, tree_mode, n_host_built);  // (uploaded, not laid out yet)
   if ((rc = finalize_scene(c))) return rc;
-  const Sizes now{nn, np, nv};
+  const MeshSizes now{nn, np, nv};
   if (!c->two_slots || wants_threaded(c, now.nodes, now.prims, now.verts) != c->threaded) return full_layout(c, b, tree_mode, n_host_built);
   clear_add_report(c);
 
@@ -277,9 +184,14 @@ int hk_add_meshes(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode) {
   const int orderings = c->threaded ? 8 : 1;
   if ((rc = join_all(c))) return rc;  // (the mesh-level region has one copy; a move goes behind every frame enqueued so far)
   uint32_t relocated = 0;
-  if (now.nodes > c->node_cap || now.prims > c->prim_cap || now.verts > c->vert_cap) {
-    auto room = [](size_t need, size_t unit) { return ((3 * need + 1) / 2 + unit - 1) / unit * unit; };
-    if ((rc = relocate(c, Sizes{room(now.nodes, 1), room(now.prims, 4), room(now.verts, 4)}, c->dyn_capacity))) return rc;  // (nothing was written: the scene is the one it had)
+  if (now.nodes > c->mesh.node_cap || now.prims > c->mesh.prim_cap || now.verts > c->mesh.vert_cap) {  // (refused: nothing was written, the scene is the one it had)
+    SceneMove m;
+    const double t0 = now_ms();
+    if ((rc = move_begin(c, move_room(now), c->dyn_capacity, c->wide_blas, c->wide_blas_rank, 0, "no room for the grown scene", &m))) return rc;
+    const double t1 = now_ms();
+    c->last_add_ms[0] = t1 - t0;
+    if ((rc = copy_and_commit(c, &m))) return rc;
+    c->last_add_ms[1] = now_ms() - t1;
     relocated = 1;
   }
   c->scene_epoch += 1;  // (scene memory is written from here on: hk_context.hpp, primary-ray pipelining)
@@ -309,14 +221,14 @@ int hk_add_meshes(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode) {
   if ((rc = stage(c, prim_bytes + vert_bytes + node_bytes + 16, &st, &k))) return fail(rc);
   memcpy(st, bp + old.prims, prim_bytes);
   memcpy(st + prim_bytes, bv + old.verts, vert_bytes);
-  launch_append_geometry(c->stream, (const uint4*)st, add_prims, (const uint4*)(st + prim_bytes), add_verts, (float4*)(sbase + c->st_v0) + old.prims,
-                         (float4*)(sbase + c->st_v1) + old.prims, (float4*)(sbase + c->st_v2) + old.prims, (float4*)(sbase + c->st_vn) + old.verts,
-                         (float2*)(sbase + c->st_vuv) + old.verts);
+  launch_append_geometry(c->stream, (const uint4*)st, add_prims, (const uint4*)(st + prim_bytes), add_verts, (float4*)(sbase + c->mesh.v0) + old.prims,
+                         (float4*)(sbase + c->mesh.v1) + old.prims, (float4*)(sbase + c->mesh.v2) + old.prims, (float4*)(sbase + c->mesh.vn) + old.verts,
+                         (float2*)(sbase + c->mesh.vuv) + old.verts);
   if (!host.empty()) {
     float4* laid = (float4*)(st + prim_bytes + vert_bytes);
     if ((rc = layout_host_trees(c, host, (uint32_t)old.nodes, span, orderings, laid))) return fail(rc);
     CopySegments s;  // (the deferred ranges of the span carry their stand-ins: the build below overwrites them in stream order)
-    for (int o = 0; o < orderings; ++o) s.add(sbase + c->st_nodes + ((size_t)o * c->node_cap + old.nodes) * 32, laid + 2 * (size_t)o * span, (size_t)span * 32);
+    for (int o = 0; o < orderings; ++o) s.add(sbase + c->mesh.nodes + ((size_t)o * c->mesh.node_cap + old.nodes) * 32, laid + 2 * (size_t)o * span, (size_t)span * 32);
     if (s.overflow) {
       set_error("more orderings than one copy launch takes");
       return fail(HK_E_INVALID);

@@ -20,6 +20,27 @@ bool finite16(const float* m) {
 }
 }  // namespace
 
+int hk::check_appended_materials(const hk_ctx* c, const hk_scene_builder* b) {
+  const HkMaterial* mats = nullptr;
+  uint32_t nm = 0;
+  builder_materials(b, &mats, &nm);
+  const uint32_t n_tex = (uint32_t)c->textures.size();
+  for (uint32_t i = (uint32_t)c->materials.size(); i < nm; ++i)
+    for (uint32_t id : {mats[i].base_color_texture, mats[i].emissive_texture, mats[i].metallic_roughness_texture, mats[i].occlusion_texture})
+      HK_REQUIRE(id == HK_NO_TEXTURE || id < n_tex, HK_E_INVALID, "material %u references texture %u but only %u textures are uploaded", i, id, n_tex);
+  return HK_OK;
+}
+// hk_update_scene_instances: materials appended on the builder travel with that call's layout (changed VALUES: hk_update_materials)
+int hk::take_appended_materials(hk_ctx* c, const hk_scene_builder* b) {
+  const HkMaterial* mats = nullptr;
+  uint32_t nm = 0;
+  builder_materials(b, &mats, &nm);
+  if (!c->have_materials || nm <= c->materials.size()) return HK_OK;
+  const int rc = check_appended_materials(c, b);
+  if (!rc) c->materials.insert(c->materials.end(), mats + c->materials.size(), mats + nm);
+  return rc;
+}
+
 // `finish`: the builder is finished here (once per change, whichever context sees it first: hk_multi_change_scene_instances)
 int hk::change_instances_impl(hk_ctx* c, hk_scene_builder* b, const uint32_t* origins, uint32_t n, uint32_t tree_mode, bool finish) {
   // ---- the whole call is validated before the builder is finished or anything is written
@@ -59,10 +80,7 @@ int hk::change_instances_impl(hk_ctx* c, hk_scene_builder* b, const uint32_t* or
     uint32_t nm = 0;
     builder_materials(b, &mats, &nm);
     HK_REQUIRE(nm >= c->materials.size(), HK_E_INVALID, "the builder has %u materials, the uploaded scene %zu", nm, c->materials.size());
-    const uint32_t n_tex = (uint32_t)c->textures.size();
-    for (uint32_t i = (uint32_t)c->materials.size(); i < nm; ++i)
-      for (uint32_t id : {mats[i].base_color_texture, mats[i].emissive_texture, mats[i].metallic_roughness_texture, mats[i].occlusion_texture})
-        HK_REQUIRE(id == HK_NO_TEXTURE || id < n_tex, HK_E_INVALID, "material %u references texture %u but only %u textures are uploaded", i, id, n_tex);
+    if (const int bad = check_appended_materials(c, b)) return bad;
   }
   HK_HIP(hipSetDevice(c->device));
   int rc;
@@ -146,7 +164,7 @@ int hk::change_instances_impl(hk_ctx* c, hk_scene_builder* b, const uint32_t* or
   DynOffsets o{};
   c->dyn_blob.bytes.clear();
   c->trees_pending_on_device = n >= 2u;   // (ordering 0 of the stand-in trees alone: the device builds every ordering)
-  rc = build_dynamic_region(c, c->dyn_blob, o, c->static_bytes);
+  rc = build_dynamic_region(c, c->dyn_blob, o, c->mesh.bytes);
   c->trees_pending_on_device = false;
   if (rc) return refuse(rc);
   // room: the refit's side arrays, the tree builds' scratch, the emitters' records (each waits only where it grows)
@@ -184,7 +202,7 @@ int hk::change_instances_impl(hk_ctx* c, hk_scene_builder* b, const uint32_t* or
   c->dyn_off = o;
   if ((rc = upload_slot_staged(c))) return rc;
   ++launches;
-  point_scene_at_slot(c);
+  point_scene_at_slot(c);   // (not repoint_scene: the refit's plane is indexed by the OLD instance set, the slot just uploaded holds the new level's previous models)
   c->instances_generation += 1;   // (the instance lists of the deformable meshes and of the pose path follow it)
   c->pd_all_ready = false;
   c->pd_boxes_host.clear();

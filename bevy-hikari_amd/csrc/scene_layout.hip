@@ -44,7 +44,7 @@ size_t fold_leaf_navigators(std::vector<float4>& lo, std::vector<float4>& hi, si
 // Convert the reference-layout scene to the device layout (hk_device.hpp header comment).
 //
 // One device allocation, two regions:
-//   [ instance-level region, `dyn_capacity` bytes ][ mesh-level region, `static_bytes` bytes ]
+//   [ instance-level region, `dyn_capacity` bytes ][ mesh-level region, `mesh.bytes` bytes ]
 // The instance-level region (TLAS nodes first, instances, light BVH, emissives, alias tables,
 // materials, texture descriptors) is what prepare_instances / prepare_material_assets rewrite when
 // something moves (instance.rs:352-437); it is small (0.6 MB at 2 000 instances) and is the only part
@@ -95,8 +95,8 @@ void thread_orderings(const std::vector<HkNode>& src, const std::vector<std::pai
 }
 
 // mesh-level region; fills c->node_prim_offset.  Needs the instances' mesh records to know which
-// primitive range a BLAS leaf indexes (GpuMeshIndex travels with the instance, mod.rs:147-156).
-int build_static_region(hk_ctx* c, Blob& blob, size_t& off_nodes, size_t& off_v0, size_t& off_v1, size_t& off_v2, size_t& off_vn, size_t& off_vuv) {
+// primitive range a BLAS leaf indexes (GpuMeshIndex travels with the instance, mod.rs:147-156).  `mesh`: the region the blob holds, exact.
+int build_static_region(hk_ctx* c, Blob& blob, MeshRegion& mesh) {
   const size_t n_nodes = c->asset_nodes.size(), n_prims = c->primitives.size(), n_verts = c->vertices.size();
   std::vector<int64_t>& node_prim_offset = c->node_prim_offset;
   node_prim_offset.assign(n_nodes, -1);
@@ -139,7 +139,7 @@ int build_static_region(hk_ctx* c, Blob& blob, size_t& off_nodes, size_t& off_v0
     for (const auto& r : ranges) fold_leaf_navigators(lo, hi, r.first, r.second);  // fold single-leaf navigators, once per distinct mesh range
     for (size_t i = 0; i < n_nodes; ++i) { nodes.push_back(lo[i]); nodes.push_back(hi[i]); }
   }
-  off_nodes = blob.add(nodes);  // offset 0: the region itself starts on a 32-B boundary
+  mesh.nodes = blob.add(nodes);  // offset 0: the region itself starts on a 32-B boundary
 
   std::vector<float4> v0(n_prims), v1(n_prims), v2(n_prims);
   for (size_t i = 0; i < n_prims; ++i) {
@@ -148,18 +148,17 @@ int build_static_region(hk_ctx* c, Blob& blob, size_t& off_nodes, size_t& off_v0
     v1[i] = make_float4(v[1].position[0], v[1].position[1], v[1].position[2], as_f(v[1].index));
     v2[i] = make_float4(v[2].position[0], v[2].position[1], v[2].position[2], as_f(v[2].index));
   }
-  off_v0 = blob.add(v0);
-  off_v1 = blob.add(v1);
-  off_v2 = blob.add(v2);
+  mesh.v0 = blob.add(v0); mesh.v1 = blob.add(v1); mesh.v2 = blob.add(v2);
   std::vector<float4> vn(n_verts);
   std::vector<float2> vuv(n_verts);
   for (size_t i = 0; i < n_verts; ++i) {
     vn[i] = make_float4(c->vertices[i].normal[0], c->vertices[i].normal[1], c->vertices[i].normal[2], 0.0f);
     vuv[i] = make_float2(c->vertices[i].u, c->vertices[i].v);
   }
-  off_vn = blob.add(vn);
-  off_vuv = blob.add(vuv);
+  mesh.vn = blob.add(vn); mesh.vuv = blob.add(vuv);
   blob.bytes.resize((blob.bytes.size() + 15) & ~(size_t)15, 0);
+  mesh.node_cap = n_nodes; mesh.prim_cap = n_prims; mesh.vert_cap = n_verts;
+  mesh.bytes = blob.bytes.size();
   return HK_OK;
 }
 
@@ -286,7 +285,7 @@ bool build_flat_bvh(const hk_ctx* c, uint32_t orderings, std::vector<float4>& ou
   return true;
 }
 
-int build_dynamic_region(hk_ctx* c, Blob& blob, DynOffsets& o, size_t static_bytes) {
+int build_dynamic_region(hk_ctx* c, Blob& blob, DynOffsets& o, size_t mesh_bytes) {
   const size_t n_tlas = c->instance_nodes.size();
   const int orderings = c->threaded ? 8 : 1;
   std::vector<std::vector<HkNode>> ordered;
@@ -437,9 +436,9 @@ int build_dynamic_region(hk_ctx* c, Blob& blob, DynOffsets& o, size_t static_byt
     if (shared && build_flat_bvh(c, 1u, flat, count)) {  // (a first build tells the node count: 2 T - 1)
       const size_t per_ordering = flat.size() * 16;
       uint32_t ord = want;
-      while (ord > 1 && (per_ordering * ord > budget || blob.bytes.size() + per_ordering * ord + static_bytes > HK_LDS_SCENE_BYTES)) ord >>= 1;
+      while (ord > 1 && (per_ordering * ord > budget || blob.bytes.size() + per_ordering * ord + mesh_bytes > HK_LDS_SCENE_BYTES)) ord >>= 1;
       if (ord > 1 && !build_flat_bvh(c, ord, flat, count)) ord = 0;
-      if (ord >= 1 && blob.bytes.size() + flat.size() * 16 + static_bytes <= HK_LDS_SCENE_BYTES && count <= 0xFFFFu) {
+      if (ord >= 1 && blob.bytes.size() + flat.size() * 16 + mesh_bytes <= HK_LDS_SCENE_BYTES && count <= 0xFFFFu) {
         o.flat = blob.add(flat);
         o.flat_count = count;
         o.flat_orderings = ord;
@@ -487,13 +486,13 @@ void point_scene_at_slot(hk_ctx* c) {
   const uint8_t* sbase = c->scene_mem + slots;
   DScene& s = c->scene;
   s.blob = (const float4*)base;  // (two slots: the scene is too big for the LDS copy, blob is not read)
-  s.blob_f4 = (uint32_t)((slots + c->static_bytes) / 16);
+  s.blob_f4 = (uint32_t)((slots + c->mesh.bytes) / 16);
   s.nodes = (const float4*)base;
-  s.blas_base = (uint32_t)(((size_t)(sbase - base) + c->st_nodes) / 32);
+  s.blas_base = (uint32_t)(((size_t)(sbase - base) + c->mesh.nodes) / 32);
   s.instances = (const DInstance*)(base + o.instances);
   c->d_prev_models = (const float4*)(base + o.prev_models);
-  s.tri_v0 = (const float4*)(sbase + c->st_v0); s.tri_v1 = (const float4*)(sbase + c->st_v1); s.tri_v2 = (const float4*)(sbase + c->st_v2);
-  s.vtx_normal = (const float4*)(sbase + c->st_vn); s.vtx_uv = (const float2*)(sbase + c->st_vuv);
+  s.tri_v0 = (const float4*)(sbase + c->mesh.v0); s.tri_v1 = (const float4*)(sbase + c->mesh.v1); s.tri_v2 = (const float4*)(sbase + c->mesh.v2);
+  s.vtx_normal = (const float4*)(sbase + c->mesh.vn); s.vtx_uv = (const float2*)(sbase + c->mesh.vuv);
   s.materials = (const float4*)(base + o.materials);
   s.tex_info = (const uint4*)(base + o.tex_info);
   s.srgb_lut = (const float*)(base + o.srgb_lut);
@@ -504,12 +503,17 @@ void point_scene_at_slot(hk_ctx* c) {
   s.noise = c->d_noise.p;
   s.tlas_count = (uint32_t)c->instance_nodes.size();
   s.tlas_stride = c->threaded ? (uint32_t)c->instance_nodes.size() : 0u;
-  s.blas_stride = c->threaded ? (uint32_t)c->node_cap : 0u;  // (the capacity: hk_add_meshes leaves room behind the last tree)
+  s.blas_stride = c->threaded ? (uint32_t)c->mesh.node_cap : 0u;  // (the capacity: hk_add_meshes leaves room behind the last tree)
   s.light_count = (uint32_t)c->emissive_nodes.size();
   s.flat = (const float4*)(base + o.flat);
   s.flat_count = o.flat_count;
   s.flat_mask = o.flat_orderings ? o.flat_orderings - 1u : 0u;
   update_shared_transform(c);
+}
+void repoint_scene(hk_ctx* c) {
+  const float4* prev = c->d_prev_models;
+  point_scene_at_slot(c);
+  if (prev == c->rf_prev_models) c->d_prev_models = prev;  // (the refit's own plane is not part of the slot)
 }
 
 bool wants_threaded(const hk_ctx* c, size_t n_nodes, size_t n_prims, size_t n_verts) {
@@ -518,13 +522,15 @@ bool wants_threaded(const hk_ctx* c, size_t n_nodes, size_t n_prims, size_t n_ve
   return !(c->flags & HK_CTX_EXACT_TRAVERSAL) && est > HK_LDS_SCENE_BYTES;
 }
 // (with the capacities equal to the sizes this is the layout build_static_region's blob has)
-size_t mesh_region_layout(size_t node_cap, size_t prim_cap, size_t vert_cap, uint32_t orderings, size_t off[6]) {
-  size_t at = 0;
-  off[0] = at; at += node_cap * orderings * 32;
-  for (int k = 1; k <= 3; ++k) { off[k] = at; at += prim_cap * 16; }
-  off[4] = at; at += vert_cap * 16;
-  off[5] = at; at += vert_cap * 8;
-  return (at + 15) & ~(size_t)15;
+MeshRegion mesh_region_layout(const MeshSizes& caps, uint32_t orderings) {
+  MeshRegion r{caps.nodes, caps.prims, caps.verts};
+  r.v0 = caps.nodes * orderings * 32;  // (nodes at offset 0)
+  r.v1 = r.v0 + caps.prims * 16;
+  r.v2 = r.v1 + caps.prims * 16;
+  r.vn = r.v2 + caps.prims * 16;
+  r.vuv = r.vn + caps.verts * 16;
+  r.bytes = (r.vuv + caps.verts * 8 + 15) & ~(size_t)15;
+  return r;
 }
 
 // The instance-level region as last laid out (c->dyn_blob) into the slot in use - the one frames in flight do NOT read - of a two-slot
@@ -598,13 +604,14 @@ int finalize_scene(hk_ctx* c) {
              "a mesh was deformed on the device (hk_update_mesh_vertices / hk_skin_mesh): upload the host's mirror of it (hk_upload_scene) "
              "before a change that lays the scene out again on the host");
   Blob st;  // (the mesh-level region first: whether the one-level BVH still fits the LDS copy depends on its size)
-  if (need_static && (rc = build_static_region(c, st, c->st_nodes, c->st_v0, c->st_v1, c->st_v2, c->st_vn, c->st_vuv))) return rc;
+  MeshRegion laid;
+  if (need_static && (rc = build_static_region(c, st, laid))) return rc;
   Blob& dyn = c->dyn_blob;
   dyn.bytes.clear();
   DynOffsets o{};
-  const double tb0_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  if ((rc = build_dynamic_region(c, dyn, o, need_static ? st.bytes.size() : c->static_bytes))) return rc;
-  if (c->trace_update) fprintf(stderr, "  build_dynamic_region %.2f ms (%zu bytes)\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - tb0_, dyn.bytes.size());
+  const double tb0_ = now_ms();
+  if ((rc = build_dynamic_region(c, dyn, o, need_static ? laid.bytes : c->mesh.bytes))) return rc;
+  if (c->trace_update) fprintf(stderr, "  build_dynamic_region %.2f ms (%zu bytes)\n", now_ms() - tb0_, dyn.bytes.size());
   c->dyn_off = o;
   c->rf_ready = false;
   c->rf_last_moved.clear();
@@ -613,26 +620,23 @@ int finalize_scene(hk_ctx* c) {
   if (need_static) {
     if (c->scene_mem) { (void)hipFree(c->scene_mem); c->scene_mem = nullptr; }
     c->dyn_capacity = dyn.bytes.size();  // exact: a small scene stays small enough for the LDS copy
-    c->static_bytes = st.bytes.size();
-    c->node_cap = n_nodes;  // (a host layout is exact: no room to spare)
-    c->prim_cap = c->primitives.size();
-    c->vert_cap = c->vertices.size();
-    c->two_slots = c->dyn_capacity + c->static_bytes > HK_LDS_SCENE_BYTES;
+    c->mesh = laid;  // (a host layout is exact: no room to spare)
+    c->two_slots = c->dyn_capacity + c->mesh.bytes > HK_LDS_SCENE_BYTES;
     c->slot = 0;
     // room for the previous model matrix of every instance, so that the first moving frame already fits its slot
     if (c->two_slots) c->dyn_capacity = (c->dyn_capacity + 64 * c->instances.size() + 31) & ~(size_t)31;
     const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
-    HK_HIP(hipMalloc((void**)&c->scene_mem, slots + c->static_bytes));
+    HK_HIP(hipMalloc((void**)&c->scene_mem, slots + c->mesh.bytes));
     HK_HIP(hipMemcpy(c->scene_mem + slots, st.bytes.data(), st.bytes.size(), hipMemcpyHostToDevice));
   } else if (!in_place) {  // instance count grew: move the mesh region behind larger slots, device to device
     const size_t cap = ((dyn.bytes.size() + dyn.bytes.size() / 2) + 31) & ~(size_t)31;
     const size_t old_slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
-    c->two_slots = c->two_slots || cap + c->static_bytes > HK_LDS_SCENE_BYTES;
+    c->two_slots = c->two_slots || cap + c->mesh.bytes > HK_LDS_SCENE_BYTES;
     c->slot = 0;
     const size_t slots = (c->two_slots ? 2 : 1) * cap;
     uint8_t* mem = nullptr;
-    HK_HIP(hipMalloc((void**)&mem, slots + c->static_bytes));
-    HK_HIP(hipMemcpy(mem + slots, c->scene_mem + old_slots, c->static_bytes, hipMemcpyDeviceToDevice));
+    HK_HIP(hipMalloc((void**)&mem, slots + c->mesh.bytes));
+    HK_HIP(hipMemcpy(mem + slots, c->scene_mem + old_slots, c->mesh.bytes, hipMemcpyDeviceToDevice));
     (void)hipFree(c->scene_mem);
     c->scene_mem = mem;
     c->dyn_capacity = cap;

@@ -12,7 +12,6 @@ using namespace hkd;
 namespace {
 constexpr uint32_t FOREST_BATCH_TRIANGLES = 1u << 19;  // triangles built at once: about 460 B of scratch each (240 MB), whatever the scene
 
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // reference form (hikari_hip.h HkNode: leaf boxes empty, every leaf behind a navigator of its own) of ordering 0 of a mesh tree as
 // k_forest_emit / k_lbvh_emit write it: the navigator of a leaf carries the leaf's entry, and the leaf slot the same record
@@ -76,7 +75,7 @@ int grow_scratch(hk_ctx* c, size_t need) {
 int hk::build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMesh>& meshes, uint32_t mode, uint32_t* launches, bool reference_if_unused) {
   const int build = mode == HK_TREE_SAH ? 1 : 0;
   const uint32_t orderings = c->threaded ? 8u : 1u;
-  const size_t n_nodes = c->asset_nodes.size(), n_prims = c->primitives.size(), stride = c->node_cap;
+  const size_t n_nodes = c->asset_nodes.size(), n_prims = c->primitives.size(), stride = c->mesh.node_cap;
   std::vector<const LoadMesh*> small, large;
   for (const LoadMesh& m : meshes) {
     HK_REQUIRE((size_t)m.index.node_offset + m.index.node_count <= n_nodes && (size_t)m.index.primitive + m.n_tris <= n_prims && m.index.node_count == 3u * m.n_tris - 2u,
@@ -104,8 +103,8 @@ int hk::build_on_device(hk_ctx* c, hk_scene_builder* b, const std::vector<LoadMe
   if ((rc = join_all(c))) return rc;  // (the mesh-level region has one copy)
   const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
   uint8_t* sbase = c->scene_mem + slots;
-  float4* nodes = (float4*)(sbase + c->st_nodes);
-  const float4 *v0 = (const float4*)(sbase + c->st_v0), *v1 = (const float4*)(sbase + c->st_v1), *v2 = (const float4*)(sbase + c->st_v2);
+  float4* nodes = (float4*)(sbase + c->mesh.nodes);
+  const float4 *v0 = (const float4*)(sbase + c->mesh.v0), *v1 = (const float4*)(sbase + c->mesh.v1), *v2 = (const float4*)(sbase + c->mesh.v2);
   for (size_t k = 0; k < batches.size(); ++k)
     HK_REQUIRE(launch_forest_build(c->stream, build, batches[k].data(), (uint32_t)batches[k].size(), batch_tris[k], v0, v1, v2, c->lbvh_scratch, nodes, orderings, 2 * stride,
                                    launches) == 0,

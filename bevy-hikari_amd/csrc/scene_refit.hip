@@ -29,30 +29,29 @@ int hk_update_scene_instances(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode
   HK_NO_PENDING_MESHES(b);  // (before the builder is finished: a refusal changes nothing)
   int rc;
   const bool trace = c->trace_update;
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t0 = now();
+  const double t0 = now_ms();
   if ((rc = hk_scene_builder_finish_instances(b))) return rc;
-  const double t1 = now();
+  const double t1 = now_ms();
   const size_t n_materials = c->materials.size();
   if ((rc = take_appended_materials(c, b))) return rc;  // (a spawned object is a mesh, a material and an instance; refused ids write nothing)
   if ((rc = upload_scene_instances_unchecked(c, b))) {  // (refused: the material mirror is what it was)
     c->materials.resize(n_materials);
     return rc;
   }
-  const double t2 = now();
+  const double t2 = now_ms();
   uint32_t ni = 0;
   const HkInstance* inst = nullptr;
   if ((rc = hk_scene_builder_instances(b, &inst, &ni))) return rc;
   c->trees_pending_on_device = ni >= 2;
   rc = finalize_scene(c);
   c->trees_pending_on_device = false;
-  const double t3 = now();
+  const double t3 = now_ms();
   if (!rc && ni >= 2) rc = hk_rebuild_scene_trees(c, tree_mode);  // (a tree of one leaf is what the host just laid out)
   // the region just uploaded carries stand-in trees with orderings 1..7 left zero (the device build was to overwrite
   // them in stream order).  If that build did not get enqueued, a threaded walk over zero nodes would never leave node 0: the
   // next use of the scene lays the region out again, from the host's (valid) stand-in trees, all orderings threaded.
   if (rc) c->dynamic_dirty = true;
-  if (trace) fprintf(stderr, "hk_update_scene_instances: finish_instances %.2f ms, mirrors %.2f ms, layout + upload %.2f ms, device build enqueue %.2f ms\n", t1 - t0, t2 - t1, t3 - t2, now() - t3);
+  if (trace) fprintf(stderr, "hk_update_scene_instances: finish_instances %.2f ms, mirrors %.2f ms, layout + upload %.2f ms, device build enqueue %.2f ms\n", t1 - t0, t2 - t1, t3 - t2, now_ms() - t3);
   return rc;
 }
 
@@ -174,9 +173,7 @@ int hk::begin_device_update(hk_ctx* c) {
     c->slot ^= 1;
     uint8_t* to = c->scene_mem + (size_t)c->slot * c->dyn_capacity;
     launch_copy_region(c->stream, to, from, c->dyn_capacity);
-    const float4* prev = c->d_prev_models;
-    point_scene_at_slot(c);
-    if (prev == c->rf_prev_models) c->d_prev_models = prev;  // (the refit's own plane is not part of the slot)
+    repoint_scene(c);
   }
   return HK_OK;
 }

@@ -1,11 +1,10 @@
 // scene_remove.hip - meshes removed from a loaded scene, the mesh-level region compacted on the device (hikari_hip.h hk_remove_meshes;
 // kernels in kernels_scene.hip; DESIGN 3 "Meshes that leave").  The twin of scene_append.hip: the scene moves, behind every stream, to a
-// NEW allocation sized for the survivors - the destination of every run lies in front of its source, so a move in place would need an
+// NEW allocation sized for the survivors (scene_move.hip) - the destination of every run lies in front of its source, so a move in place would need an
 // order across workgroups, frames in flight go on reading the old allocation, and a failure before the switch leaves the scene the
 // context had.  One launch moves the surviving runs of every plane however many meshes go; one small launch beside it copies the
 // instance-level slot and rebases the three words of every instance record that name mesh offsets; a copy launch in front of both takes
-// the plan from pinned to device memory.  Links and leaf ids are local to a
-// mesh: nothing inside a tree, a wide record or a rank changes.
+// the plan from pinned to device memory.  Links and leaf ids are local to a mesh: nothing inside a tree, a wide record or a rank changes.
 #include "hk_context.hpp"
 
 using namespace hk;
@@ -200,126 +199,75 @@ int hk_remove_meshes(hk_ctx* c, const HkMeshExtent* removed, uint32_t n) {
     HK_HIP(hipGetDeviceProperties(&prop, c->device));
     c->compute_units = prop.multiProcessorCount;
   }
-  const uint32_t orderings = c->threaded ? 8u : 1u;
-  auto room = [](size_t need, size_t unit) { return ((3 * need + 1) / 2 + unit - 1) / unit * unit; };  // (the append's)
-  const size_t cap_nodes = room(now_nodes, 1), cap_prims = room(now_prims, 4), cap_verts = room(now_verts, 4);
-  const size_t slots = 2 * c->dyn_capacity;
-  size_t off[6];
-  const size_t bytes = mesh_region_layout(cap_nodes, cap_prims, cap_verts, orderings, off);
-  const size_t old_off[6] = {c->st_nodes, c->st_v0, c->st_v1, c->st_v2, c->st_vn, c->st_vuv};
   // the wide records and ranks of the survivors are moved, not derived again - where they exist and describe the scene
   const bool move_wide = c->wide_blas && !c->wide_blas_dirty && c->wide_blas_slots >= n_nodes;
   const bool move_rank = move_wide && c->wide_blas_rank && c->wide_rank_primitives >= n_prims;
   // ---- the plan, in one pinned block: planes, then the three run lists
-  const size_t plane_bytes = HK_COMPACT_PLANES * sizeof(CompactPlane);
-  size_t run_first[3], table_bytes = plane_bytes;
+  size_t run_first[3], table_bytes = HK_COMPACT_PLANES * sizeof(CompactPlane);
   for (int l = 0; l < 3; ++l) { run_first[l] = table_bytes; table_bytes += runs[l].size() * sizeof(CompactRun); }
   table_bytes = (table_bytes + 15) & ~(size_t)15;
   uint8_t* st = nullptr;
   int sk = 0;
   if ((rc = stage(c, table_bytes, &st, &sk))) return rc;
   if ((rc = join_all(c))) return rc;  // (the mesh-level region has one copy: the move goes behind every frame enqueued so far)
-  uint8_t *mem = nullptr, *table = nullptr;
-  float4* wide = nullptr;
-  uint32_t* rank = nullptr;
-  hipEvent_t done[4] = {nullptr, nullptr, nullptr, nullptr};  // scene, wide, rank, table
-  auto undo = [&]() {
-    for (void* q : {(void*)mem, (void*)table, (void*)wide, (void*)rank})
-      if (q) (void)hipFree(q);
-    for (hipEvent_t e : done)
-      if (e) (void)hipEventDestroy(e);
-  };
-  bool ok = hipMalloc((void**)&mem, slots + bytes) == hipSuccess && hipMalloc((void**)&table, table_bytes) == hipSuccess;
-  for (int k = 0; k < 4 && ok; ++k) ok = hipEventCreateWithFlags(&done[k], hipEventDisableTiming) == hipSuccess;
-  for (int k = 0; k < 2 && ok; ++k)
-    if (!c->rm_ev[k]) ok = hipEventCreate(&c->rm_ev[k]) == hipSuccess;
-  if (ok && move_wide) ok = hipMalloc((void**)&wide, cap_nodes * 128) == hipSuccess;
-  if (ok && move_rank) {
-    ok = hipMalloc((void**)&rank, cap_prims * 4) == hipSuccess && hipMemsetAsync(rank, 0xFF, cap_prims * 4, c->stream) == hipSuccess;
-    enqueued += 1;
-  }
-  if (!ok) {
-    const hipError_t e = hipGetLastError();
-    undo();
-    HK_REQUIRE(false, HK_E_HIP, "no room for the compacted scene: %s", hipGetErrorString(e));
-  }
+  for (int k = 0; k < 2; ++k)
+    if (!c->rm_ev[k]) HK_HIP(hipEventCreate(&c->rm_ev[k]));
+  SceneMove m;  // (the slots keep their size; the plan's device copy lives as long as the move)
+  if ((rc = move_begin(c, move_room(MeshSizes{now_nodes, now_prims, now_verts}), c->dyn_capacity, move_wide, move_rank, table_bytes, "no room for the compacted scene", &m))) return rc;
+  enqueued += m.rank ? 1 : 0;  // (the fill of the new ranks)
   CompactArgs a{};
   CompactPlane* planes = (CompactPlane*)st;
   uint64_t moved_bytes = 0;
   bool inside = true;  // every source inside the old capacities, every destination inside the new ones
-  auto add_plane = [&](const void* src, void* dst, uint32_t list, uint32_t shift, size_t old_cap, size_t new_cap) {
-    if (a.n_planes >= HK_COMPACT_PLANES) { inside = false; return; }
-    const uint64_t plane_total = (uint64_t)survivors(runs[list]) << shift;
-    for (const CompactRun& r : runs[list]) inside = inside && (size_t)r.src + r.count <= old_cap && (size_t)r.dst + r.count <= new_cap;
-    inside = inside && ((uintptr_t)src & 15u) == 0 && ((uintptr_t)dst & 15u) == 0;
-    planes[a.n_planes++] = CompactPlane{(const uint8_t*)src, (uint8_t*)dst, list, shift, a.n_pieces};
+  MovePlane moving[HK_MOVE_PLANES];
+  static_assert(HK_MOVE_PLANES <= HK_COMPACT_PLANES, "the compaction's table holds every plane of a move");
+  for (uint32_t k = 0, n_moving = move_planes(c, m, moving); k < n_moving; ++k) {
+    const MovePlane& p = moving[k];
+    const uint64_t plane_total = (uint64_t)survivors(runs[p.list]) << p.shift;
+    for (const CompactRun& r : runs[p.list]) inside = inside && (size_t)r.src + r.count <= p.old_cap && (size_t)r.dst + r.count <= p.new_cap;
+    inside = inside && ((uintptr_t)p.src & 15u) == 0 && ((uintptr_t)p.dst & 15u) == 0;
+    planes[a.n_planes++] = CompactPlane{p.src, p.dst, p.list, p.shift, a.n_pieces};
     a.n_pieces += (plane_total + HK_COMPACT_PIECE - 1) / HK_COMPACT_PIECE;
     moved_bytes += plane_total;
-  };
-  const uint8_t* from = c->scene_mem + slots;
-  uint8_t* to = mem + slots;
-  for (uint32_t o = 0; o < orderings; ++o)
-    add_plane(from + old_off[0] + (size_t)o * c->node_cap * 32, to + off[0] + (size_t)o * cap_nodes * 32, 0u, 5u, c->node_cap, cap_nodes);
-  for (int k = 1; k <= 3; ++k) add_plane(from + old_off[k], to + off[k], 1u, 4u, c->prim_cap, cap_prims);
-  add_plane(from + old_off[4], to + off[4], 2u, 4u, c->vert_cap, cap_verts);
-  add_plane(from + old_off[5], to + off[5], 2u, 3u, c->vert_cap, cap_verts);
-  if (wide) add_plane(c->wide_blas, wide, 0u, 7u, c->wide_blas_slots, cap_nodes);
-  if (rank) add_plane(c->wide_blas_rank, rank, 1u, 2u, c->wide_rank_primitives, cap_prims);
+  }
   for (uint32_t k = a.n_planes; k < HK_COMPACT_PLANES; ++k) planes[k] = CompactPlane{nullptr, nullptr, 0u, 0u, ~0ull};
-  a.planes = (const CompactPlane*)table;
+  a.planes = (const CompactPlane*)m.extra;
   for (int l = 0; l < 3; ++l) {
     memcpy(st + run_first[l], runs[l].data(), runs[l].size() * sizeof(CompactRun));
-    a.runs[l] = (const CompactRun*)(table + run_first[l]);
+    a.runs[l] = (const CompactRun*)(m.extra + run_first[l]);
     a.n_runs[l] = (uint32_t)runs[l].size();
     a.total[l] = survivors(runs[l]);
   }
   const size_t first16 = c->dyn_off.instances / 16, n_inst = c->instances.size();
   inside = inside && c->dyn_off.instances % 16 == 0 && c->dyn_off.instances + n_inst * sizeof(DInstance) <= c->dyn_capacity && c->dyn_capacity % 16 == 0;
   if (!inside) {
-    undo();
-    HK_REQUIRE(false, HK_E_INVALID, "the compaction plan leaves the scene's capacities");  // (a bug of this file, never of the caller: nothing was enqueued)
+    move_abort(c, &m, m.rank != nullptr);  // (nothing but the ranks' fill was enqueued)
+    HK_REQUIRE(false, HK_E_INVALID, "the compaction plan leaves the scene's capacities");  // (a bug of this file, never of the caller)
   }
   // the table to device memory (a copy kernel reading the pinned block), the planes, the instance-level slot in use into both new slots
-  launch_copy_region(c->stream, table, st, table_bytes);
+  launch_copy_region(c->stream, m.extra, st, table_bytes);
   enqueued += 1;
-  ok = hipEventRecord(c->rm_ev[0], c->stream) == hipSuccess;
+  bool ok = hipEventRecord(c->rm_ev[0], c->stream) == hipSuccess;
   launch_compact_planes(c->stream, a, c->compute_units);
   enqueued += a.n_pieces ? 1 : 0;
   ok = ok && hipEventRecord(c->rm_ev[1], c->stream) == hipSuccess;
-  launch_compact_instances(c->stream, (uint4*)mem, (uint4*)(mem + c->dyn_capacity), (const uint4*)(c->scene_mem + (size_t)c->slot * c->dyn_capacity), c->dyn_capacity / 16, first16,
-                           (uint32_t)n_inst, a);
+  launch_compact_instances(c->stream, (uint4*)m.mem, (uint4*)(m.mem + c->dyn_capacity), (const uint4*)(c->scene_mem + (size_t)c->slot * c->dyn_capacity), c->dyn_capacity / 16,
+                           first16, (uint32_t)n_inst, a);
   enqueued += c->dyn_capacity / 16 ? 1 : 0;
-  ok = ok && hipGetLastError() == hipSuccess;
-  for (int k = 0; k < 4 && ok; ++k) ok = hipEventRecord(done[k], c->stream) == hipSuccess;
-  hk_ctx::DeformStage& ds = c->df_stage[(size_t)sk];
-  ok = ok && hipEventRecord(ds.done, c->stream) == hipSuccess;
-  if (!ok) {
+  if (!ok || hipGetLastError() != hipSuccess) {
     const hipError_t e = hipGetLastError();
-    (void)hipStreamSynchronize(c->stream);  // (the move may be enqueued: its targets and its tables must outlive it)
-    undo();
+    move_abort(c, &m, true);  // (the move may be enqueued)
     HK_REQUIRE(false, HK_E_HIP, "the compaction of the scene failed: %s", hipGetErrorString(e));
   }
-  ds.pending = true;
+  if ((rc = move_commit(c, &m, 0))) return rc;  // (slot 0: both slots hold the instance level as it stands)
+  hk_ctx::DeformStage& ds = c->df_stage[(size_t)sk];
+  if (hipEventRecord(ds.done, c->stream) == hipSuccess) ds.pending = true;
+  else (void)hipStreamSynchronize(c->stream);  // (no event: the pinned plan has been read once the stream is idle)
   c->rm_timed = true;
-  // ---- the switch: frames enqueued from here on read the new allocation, the ones in flight the old one until `done`
-  retire(c, c->scene_mem, done[0]);
-  if (wide) { retire(c, c->wide_blas, done[1]); c->wide_blas = wide; c->wide_blas_slots = cap_nodes; }
-  else (void)hipEventDestroy(done[1]);
-  if (rank) { retire(c, c->wide_blas_rank, done[2]); c->wide_blas_rank = rank; c->wide_rank_primitives = cap_prims; }
-  else (void)hipEventDestroy(done[2]);
-  retire(c, table, done[3]);
   if (c->wide_blas && !move_wide) c->wide_blas_dirty = true;  // (records that did not describe the scene: derived again for the new layout)
   if (c->wide_blas_rank && !move_rank) c->wide_blas_dirty = true;
-  c->scene_mem = mem;
-  c->slot = 0;  // (both slots hold the instance level as it stands)
-  c->node_cap = cap_nodes; c->prim_cap = cap_prims; c->vert_cap = cap_verts;
-  c->st_nodes = off[0]; c->st_v0 = off[1]; c->st_v1 = off[2]; c->st_v2 = off[3]; c->st_vn = off[4]; c->st_vuv = off[5];
-  c->static_bytes = bytes;
   c->scene_epoch += 1;  // (scene memory was written: hk_context.hpp, primary-ray pipelining)
   compact_host_state(c, gone, runs, freed);
-  const float4* prev = c->d_prev_models;
-  point_scene_at_slot(c);
-  if (prev == c->rf_prev_models) c->d_prev_models = prev;  // (the refit's own plane is not part of the slot)
   for (void* q : freed) {  // what the removed deformable meshes held: frames in flight may still use it
     hipEvent_t e = nullptr;
     if (hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess && hipEventRecord(e, c->stream) == hipSuccess) retire(c, q, e);
