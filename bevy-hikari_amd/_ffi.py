@@ -52,6 +52,7 @@ DEBUG_OPT_MAIN_PRIORITY, DEBUG_OPT_PREPASS_PIPELINE, DEBUG_OPT_MESH_REBUILD_ONE_
 DEBUG_OPT_LOAD_DEVICE_LIMIT = 12
 DEBUG_OPT_KNOWN_RESULTS = 13
 DEBUG_OPT_SPATIAL_KNOWN = 14
+DEBUG_OPT_MOTION_COUNT = 15
 TIMING_TRACE_STAGES = 18  # hk_set_timing_mask bit / HkStats slot: every trace launch of the queue-based indirect pass
 TRAVERSAL_WIDE = 0x100
 FRAME_EXTERNAL_GBUFFER, FRAME_ANTIALIAS, FRAME_BALANCE_BANDS, FRAME_GATHER, FRAME_TIME_BAND = 1, 2, 4, 8, 16
@@ -60,6 +61,7 @@ TAA_JASMINE, TAA_NONE = 0, 1
 UPSCALE_FSR1, UPSCALE_SMAA_TU4X = 0, 1
 NO_TEXTURE = 0xFFFFFFFF
 ADDRESS_CLAMP_TO_EDGE, ADDRESS_REPEAT, ADDRESS_MIRROR_REPEAT = 0, 1, 2
+TIMING_MOTION_VECTORS = 19  # hk_set_timing_mask bit / HkStats slot: the motion pass behind the primary rays
 TIMING_SLOTS = 24
 FORMAT_RGBA16F, FORMAT_RGBA32F, FORMAT_RGBA8_UNORM_SRGB, FORMAT_BGRA8_UNORM_SRGB = range(4)  # HkPresentTarget.format
 PRESENT_HDR, PRESENT_CLEAR = 1, 2
@@ -263,6 +265,7 @@ _DEBUG = {
     "debug_read_emitters": [_vp, P(f32), u32, P(u32), P(f32), u32, P(u32)],
     "debug_read_mesh_geometry": [_vp, P(HkMeshIndex), P(f32), P(f32), u32, P(f32), u32, P(f32), P(u32), P(u32)],
     "debug_last_deform": [_vp, P(u32)],
+    "debug_last_motion": [_vp, P(u32)],
     "debug_last_pose": [_vp, P(u32)],
     "debug_last_instance_change": [_vp, P(u32)],
     "debug_last_texture_update": [_vp, P(u32)],
@@ -339,6 +342,7 @@ _PRODUCT_ONLY = {
     "set_instance_transforms_device": [_vp, _vp, P(u32), u32, _vp, u32, _vp, _vp],
     "read_instance_transforms": [_vp, P(f32), u32],
     "rebuild_mesh_tree": [_vp, P(HkMeshIndex), u32],
+    "set_mesh_motion_vectors": [_vp, P(HkMeshIndex), u32],
     "present": [_vp, P(HkSettings), u32, P(HkPresentTarget), u32, u32],
     "cast_rays": [_vp, P(HkRay), u32, u32, P(HkRayHit)],
     "cast_rays_device": [_vp, _vp, u32, u32, _vp],
@@ -391,6 +395,7 @@ _PRODUCT_ONLY = {
     "multi_set_mesh_morph_targets": [_vp, P(HkMeshIndex), u32, u32, P(f32), P(f32), P(f32), P(f32)],
     "multi_deform_meshes": [_vp, P(HkMeshDeform), u32],
     "multi_rebuild_mesh_tree": [_vp, P(HkMeshIndex), u32],
+    "multi_set_mesh_motion_vectors": [_vp, P(HkMeshIndex), u32],
     "multi_set_band_bounds": [_vp, P(u32), u32],
     "multi_upload_textures": [_vp, P(HkImageDesc), u32],
     "multi_update_materials": [_vp, _vp, u32, P(u32)],

@@ -844,6 +844,7 @@ int hk_multi_set_mesh_morph_targets(hk_multi* m, const HkMeshIndex* mesh, uint32
 }
 int hk_multi_deform_meshes(hk_multi* m, const HkMeshDeform* items, uint32_t n) { HK_EACH(hk_deform_meshes(c, items, n)); }
 int hk_multi_rebuild_mesh_tree(hk_multi* m, const HkMeshIndex* mesh, uint32_t mode) { HK_EACH(hk_rebuild_mesh_tree(c, mesh, mode)); }
+int hk_multi_set_mesh_motion_vectors(hk_multi* m, const HkMeshIndex* mesh, uint32_t enable) { HK_EACH(hk_set_mesh_motion_vectors(c, mesh, enable)); }
 // the same explicit split on every band's context (all of them must agree: the schedules are derived per context)
 int hk_multi_set_band_bounds(hk_multi* m, const uint32_t* bounds, uint32_t n_bounds) { HK_EACH(hk_set_band_bounds(c, bounds, n_bounds)); }
 // the rows of the history reservoirs that change owner travel between the bands' contexts, then every band takes the new split

@@ -897,6 +897,13 @@ int post_end(hk_ctx* c, bool pipelined) {
   c->post_pending[parity] = true;
   return HK_OK;
 }
+// the motion pass behind a launch_prepass (mesh_deform.hip motion_pass), in its own timing slot: the primary rays' time stays theirs
+// (a timed frame is never pipelined: `st` is the context's stream whenever the timer is on)
+int timed_motion_pass(hk_ctx* c, hipStream_t st, const DFrame& fr, const GBuffer& g, float jitter_x, float jitter_y, int y0, int y1) {
+  if (!c->mv_live) return HK_OK;
+  ScopedTimer timer(c, HK_TIMING_MOTION_VECTORS);
+  return motion_pass(c, st, fr, g, jitter_x, jitter_y, y0, y1);
+}
 // run one dispatch on the side stream (timers record there too)
 int run_pass(hk_ctx* c, uint32_t pass, uint32_t arg, int y0, int y1);
 int run_pass_on_side(hk_ctx* c, uint32_t pass, uint32_t arg, int y0, int y1) {
@@ -928,7 +935,9 @@ int run_pass(hk_ctx* c, uint32_t pass, uint32_t arg, int y0, int y1) {
       Jitter j = prepass_jitter(c);
       hkd::WideTrees wide{};
       { const int rc_ = wide_for_fused(c, &wide); if (rc_) return rc_; }
+      { const int rc_ = motion_frame(c); if (rc_) return rc_; }
       launch_prepass(c->stream, c->scene, fr, c->view.inverse_view_proj, c->view.view_proj, c->pview.view_proj, c->d_prev_models, j.x, j.y, g, y0, y1, counters, &wide);
+      { const int rc_ = timed_motion_pass(c, c->stream, fr, g, j.x, j.y, y0, y1); if (rc_) return rc_; }
       break;
     }
     case HK_PASS_FULL_SCREEN_ALBEDO: launch_albedo(c->stream, c->scene, fr, g, c->buf[HK_BUF_ALBEDO], y0, y1); break;
@@ -1264,6 +1273,7 @@ int hk_debug_set_option(hk_ctx* c, uint32_t option, int64_t value) {
     case HK_DEBUG_OPT_PREPASS_PIPELINE: c->prepass_pipeline = value < 0 ? -1 : (value ? 1 : 0); break;
     case HK_DEBUG_OPT_KNOWN_RESULTS: c->known_results = value != 0; forget_empty_tiles(c); break;
     case HK_DEBUG_OPT_SPATIAL_KNOWN: c->spatial_known_on = value != 0; break;
+    case HK_DEBUG_OPT_MOTION_COUNT: c->mv_count = value != 0; break;
     case HK_DEBUG_OPT_MAIN_PRIORITY: c->main_priority = value < 0 ? -1 : (value ? 1 : 0); return pick_main_stream(c, true);
     default: HK_REQUIRE(false, HK_E_INVALID, "unknown option %u", option);
   }
@@ -1414,6 +1424,7 @@ int hk_frame_begin(hk_ctx* c, const HkFrame* f, const HkView* v, const HkPreviou
   c->pview = *pv;
   c->lights = *l;
   c->have_frame = true;
+  c->mv_frame += 1;
   for (bool& fresh : c->pieces_new_frame) fresh = true;   // (a new frame: the notes of an earlier frame's row pieces no longer count)
   // double-buffered planes follow frame.number % 2 (hikari_hip.h, HkBuffer): idempotent per frame number.
   // Work already enqueued captured its pointers at launch, so swapping here needs no synchronisation.
@@ -1660,6 +1671,8 @@ int hk_frame_stage(hk_ctx* c, uint32_t stage, const HkSettings* st, uint32_t fla
     // (post_done[parity]: the post stream waited for the main AND the side stream before it) closes all of it.  What they read - scene
     // memory - must not have been written since the last frame (those writes are behind the previous frame's spatial pass on the main
     // stream), and the wide trees must be current (k_build_wide would run on the main stream).
+    // (motion vectors: a live set that changed counts as a write to scene memory - in front of the decision below)
+    if (f1 > f0 && !(flags & HK_FRAME_EXTERNAL_GBUFFER) && (rc = motion_frame(c))) return rc;
     const uint32_t parity = c->mapped_parity & 1u;
     const bool wide_clean = !wide_allowed(c) || (!c->wide_tlas_dirty && !c->wide_blas_dirty && !c->wide_mesh_check);
     const bool pre_wanted = c->prepass_pipeline < 0 ? HK_PREPASS_PIPELINE_RULE : c->prepass_pipeline != 0;
@@ -1722,6 +1735,7 @@ int hk_frame_stage(hk_ctx* c, uint32_t stage, const HkSettings* st, uint32_t fla
           launch_prepass(pre_pipelined ? c->pre_stream : c->stream, c->scene, fr, c->view.inverse_view_proj, c->view.view_proj, c->pview.view_proj, c->d_prev_models, j.x, j.y, g, f0, f1,
                          counters, &wide);
         }
+        if ((rc = timed_motion_pass(c, pre_pipelined ? c->pre_stream : c->stream, fr, g, j.x, j.y, f0, f1))) return rc;
         HK_HIP(hipGetLastError());
         if (pre_pipelined) {
           HK_HIP(hipEventRecord(c->pre_done, c->pre_stream));

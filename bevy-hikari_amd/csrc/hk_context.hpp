@@ -342,6 +342,17 @@ struct hk_ctx {
   hipEvent_t df_src_ready = nullptr, df_src_read = nullptr;  // hk_deform_meshes_device: the producer's stream before the batch, the batch's vertex launch before the producer
   bool deform_pending = false;            // deformed meshes whose new boxes have not reached the instance level yet (flush_deform)
   bool meshes_deformed = false;           // a mesh was deformed on the device since the last hk_upload_meshes: its host copies are stale
+  // motion vectors of deforming meshes (hk_set_mesh_motion_vectors, mesh_deform.hip).  A mesh that opted in owns two position
+  // planes; it is LIVE in a frame if it was deformed since the frame before enqueued its primary rays.  mv_table: per instance the
+  // previous-position plane of its mesh, or NULL - rewritten in stream order at the first primary rays of every frame with a live mesh.
+  // mv_frame counts hk_frame_begin, mv_seen the frame whose primary rays last went through motion_frame (row pieces of one frame share it).
+  hkd::MotionEntry* mv_table = nullptr;
+  size_t mv_table_cap = 0;                // instances
+  unsigned int* mv_counter = nullptr;     // pixels rewritten by the frame's motion passes (HK_DEBUG_OPT_MOTION_COUNT)
+  bool mv_count = false;
+  uint32_t mv_enabled = 0, mv_live = 0;   // meshes that opted in / that are live in the frame most recently begun
+  uint64_t mv_frame = 0, mv_seen = 0;
+  uint32_t last_motion[2] = {0, 0};       // hk_debug_last_motion: launches of the motion pass in the last frame, meshes live
   // poses from device memory (hk_set_instance_transforms_device, scene_refit.hip).  poses_on_device: the device's poses were last set
   // from memory the host never saw - instances[].model / min / max / inverse_transpose_model and prev_models no longer describe the
   // device (every reader of them asks; hk_upload_instances clears it).  pd_boxes: the mesh box of every instance (Aabb centre, half
@@ -536,4 +547,9 @@ int stage(hk_ctx* c, size_t bytes, uint8_t** out, int* k);   // a pinned staging
 int check_source(hk_ctx* c, uint32_t item, const char* what, const void* p, size_t align, size_t extent);
 int repropagate_deformed(hk_ctx* c);   // after an instance refit: the deformed meshes' current boxes again (hk_refit_scene_instances)
 int flush_deform(hk_ctx* c);           // the instance level of the meshes deformed since the last flush, once (frames, tree rebuilds, reads)
+// motion vectors: motion_frame in front of a frame's first primary rays - which meshes are live, the instance table in stream
+// order on the main stream, scene_epoch bumped where the live set changed (so that these primary rays are not pipelined past the table);
+// motion_pass directly behind every launch_prepass, on its stream, over its rows - launches only while a mesh is live
+int motion_frame(hk_ctx* c);
+int motion_pass(hk_ctx* c, hipStream_t st, const hkd::DFrame& fr, const hkd::GBuffer& g, float jitter_x, float jitter_y, int y0, int y1);
 }  // namespace hk

@@ -432,6 +432,19 @@ __device__ __forceinline__ Pixel pixel_of_thread_rows(int width, int row_begin, 
   return p;
 }
 
+// Motion vectors of deforming meshes (kernels_motion.hip k_motion_velocity; host side mesh_deform.hip): per instance the plane of its mesh's
+// PREVIOUS local positions (one float4 per vertex, keyed by vertex id) and the vertices it holds, or NULL - the mesh has no motion this frame
+struct MotionEntry {
+  const float4* previous;
+  uint32_t n_vertices, pad;
+};
+static_assert(sizeof(MotionEntry) == 16, "one 16-B load per look-up; staged and copied in 16-B units");
+struct MotionTable {
+  const MotionEntry* entries;
+  uint32_t n_instances;
+  unsigned int* rewritten;   // pixels rewritten (hk_debug_last_motion), or NULL: not counted
+};
+
 }  // namespace hkd
 
 #define HK_LDS_SCENE_BYTES 32768u  // scenes up to this size are copied into LDS by the ray kernels (lds_bytes_for)
@@ -450,6 +463,11 @@ static inline dim3 grid_for(int width, int rows) {
 void launch_prepass(hipStream_t st, const hkd::DScene& sc, const hkd::DFrame& fr, const float* inverse_view_proj, const float* view_proj,
                     const float* prev_view_proj, const float4* prev_models, float jitter_x, float jitter_y, const hkd::GBuffer& g, int y0, int y1,
                     unsigned long long* counters, const hkd::WideTrees* wide = nullptr);
+// directly behind launch_prepass, same stream, same rows, while a mesh has live previous positions (kernels_motion.hip)
+void launch_motion_velocity(hipStream_t st, const hkd::DScene& sc, const hkd::DFrame& fr, const float* inverse_view_proj, const float* view_proj,
+                            const float* prev_view_proj, const float4* prev_models, float jitter_x, float jitter_y, const hkd::GBuffer& g, const hkd::MotionTable& mt,
+                            int y0, int y1);
+void launch_mesh_previous_fill(hipStream_t st, const float4* v0, const float4* v1, const float4* v2, uint32_t n_tris, float4* pos, uint32_t n_vertices);
 void launch_albedo(hipStream_t st, const hkd::DScene& sc, const hkd::DFrame& fr, const hkd::GBuffer& g, void* albedo, int y0, int y1);
 void launch_direct(hipStream_t st, bool emissive_lit, const hkd::DScene& sc, const hkd::DFrame& fr, const hkd::GBuffer& g, const hkd::LightTargets& t,
                    int y0, int y1, unsigned long long* counters);

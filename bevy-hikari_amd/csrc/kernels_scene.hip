@@ -431,8 +431,8 @@ __global__ __launch_bounds__(256) void k_gather_instance_boxes(RefitScene s, con
 // One thread per instance of a deformed mesh, ALL such meshes in one launch (`entries`: pinned, hk_kernels.hpp MeshInstanceEntry - the
 // instance, its mesh's box words and the slot of its emitter record): the mesh box (hk_box.hpp box_word, reduced by kernels_deform.hip) as
 // bevy's Aabb, the world AABB and emitter record with k_refit_instances' arithmetic (instance_world_box, emitter_position_radius: keep both
-// in step) - but the pose, its previous model and its `moved` flag stay as they are (a deformation is no motion: velocity_uv keeps the
-// reference's formula).  Emitters also get an update record for k_refit_emitters: their triangle areas and alias table follow the new triangles.
+// in step) - but the pose, its previous model and its `moved` flag stay as they are (a deformation is no motion of the INSTANCE: the prepass's
+// velocity_uv keeps the reference's formula; a mesh that opted in gets per-vertex motion vectors from kernels_motion.hip's pass behind it).  Emitters also get an update record for k_refit_emitters: their triangle areas and alias table follow the new triangles.
 __global__ __launch_bounds__(64) void k_mesh_instances(RefitScene s, const MeshInstanceEntry* __restrict__ entries, uint32_t n_entries, RefitUpdate* __restrict__ records) {
   const uint32_t u = blockIdx.x * 64u + threadIdx.x;
   if (u >= n_entries) return;

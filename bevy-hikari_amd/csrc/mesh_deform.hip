@@ -42,16 +42,30 @@ struct DeformMesh {
   float *morph_base_p = nullptr, *morph_base_n = nullptr, *morph_dp = nullptr, *morph_dn = nullptr, *morph_w = nullptr;
   uint32_t* morph_active = nullptr;
   uint32_t morph_vertices = 0, morph_targets = 0;
+  // motion vectors (hk_set_mesh_motion_vectors; DESIGN 4 "Motion vectors for deforming meshes"): a second position plane.  `pos` is the
+  // one the deformations write, `pos_prev` the other; the mesh's first deformation after a frame swaps them (motion_swap), so that
+  // pos_prev then holds what the mesh had when that frame's primary rays were enqueued.  pos_home: the plane inside `mem`.
+  void* motion_mem = nullptr;
+  float4 *pos_prev = nullptr, *pos_home = nullptr;
+  bool motion = false;          // opted in
+  bool motion_dirty = false;    // deformed (and swapped) since the last frame's primary rays
+  bool motion_live = false;     // pos_prev holds the previous positions of the frame most recently begun
 };
 
 namespace hk {
 void free_deform(hk_ctx* c) {
   for (DeformMesh* d : c->deform) {
-    for (void* q : {d->mem, d->skin_mem, (void*)d->joint_mats, d->nrm_mem, d->morph_mem})
+    for (void* q : {d->mem, d->skin_mem, (void*)d->joint_mats, d->nrm_mem, d->morph_mem, d->motion_mem})
       if (q) (void)hipFree(q);
     delete d;
   }
   c->deform.clear();
+  for (void* q : {(void*)c->mv_table, (void*)c->mv_counter})
+    if (q) (void)hipFree(q);
+  c->mv_table = nullptr;
+  c->mv_counter = nullptr;
+  c->mv_table_cap = 0;
+  c->mv_enabled = c->mv_live = 0;   // (a fresh scene drops all motion state)
   for (hk_ctx::DeformStage& s : c->df_stage) {
     if (s.p) (void)hipHostFree(s.p);
     if (s.done) (void)hipEventDestroy(s.done);
@@ -89,8 +103,13 @@ void rebase_deform_meshes(hk_ctx* c, const std::vector<CompactRun> runs[3], std:
     bool survives = false;
     for (const CompactRun& r : runs[0]) survives = survives || (d->mesh.node_offset >= r.src && d->mesh.node_offset - r.src < r.count);
     if (!survives) {
-      for (void* q : {d->mem, d->skin_mem, (void*)d->joint_mats, d->nrm_mem, d->morph_mem})
+      for (void* q : {d->mem, d->skin_mem, (void*)d->joint_mats, d->nrm_mem, d->morph_mem, d->motion_mem})
         if (q) freed.push_back(q);
+      if (d->motion) {  // (the survivors keep their planes and their state; the table is written again at the next frame with a live mesh)
+        c->mv_enabled -= 1;
+        c->mv_live -= d->motion_live ? 1u : 0u;
+        c->scene_epoch += 1;
+      }
       delete d;
       continue;
     }
@@ -207,7 +226,7 @@ int find_mesh(hk_ctx* c, const HkMeshIndex* m, DeformMesh** out) {
   d->tree.node_hi = (float4*)take((2 * n - 1) * 16);
   d->tree.tri_lo = (float4*)take(n * 16);
   d->tree.tri_hi = (float4*)take(n * 16);
-  d->pos = (float4*)take(nv * 16);
+  d->pos = d->pos_home = (float4*)take(nv * 16);
   d->box = (uint32_t*)take(32);
   c->deform.push_back(d);  // (owned by the context from here on, freed by free_deform)
   std::vector<uint32_t> host(5 * ni + 2 * n, 0);
@@ -360,6 +379,15 @@ void mark_deformed(hk_ctx* c, const std::vector<std::pair<uint32_t, uint32_t>>& 
   c->wide_tlas_dirty = true;
 }
 
+// motion vectors: the mesh's first deformation since the last frame's primary rays writes the OTHER plane - what `pos` held becomes the
+// previous positions of the next frame; later deformations before that frame overwrite the current plane.  No copy, no launch.
+// Called behind join_all, right in front of the launch that writes d->pos.
+void motion_swap(DeformMesh* d) {
+  if (!d->motion || d->motion_dirty) return;
+  std::swap(d->pos, d->pos_prev);
+  d->motion_dirty = true;
+}
+
 // one deformation: `fill` enqueues the vertex kernel (positions into d->pos, normals into the normal plane, the mesh box into d->box)
 template <typename Fill>
 int deform(hk_ctx* c, DeformMesh* d, int k, Fill fill) {
@@ -449,6 +477,68 @@ int hk::flush_deform(hk_ctx* c) {
   return propagate(c, [](const DeformMesh* d) { return d->pending; });
 }
 
+// Motion vectors, in front of a frame's first primary rays (hk_context.hpp): a mesh deformed since the last frame's rays is live, every
+// other one is not (a mesh not deformed between two frames has no motion in the second: its pixels take the rigid formula again).  A
+// live mesh's previous plane changes with every swap, so the instance table is staged and written again - on the main stream, behind
+// every earlier frame's pass - in each frame that has a live mesh; a frame without one launches and writes nothing.
+int hk::motion_frame(hk_ctx* c) {
+  if (c->mv_seen == c->mv_frame) return HK_OK;   // (later row pieces of the same frame)
+  c->mv_seen = c->mv_frame;
+  c->last_motion[0] = c->last_motion[1] = 0;
+  if (!c->mv_enabled) return HK_OK;
+  uint32_t live = 0;
+  bool changed = false;
+  for (DeformMesh* d : c->deform) {
+    if (!d->motion) continue;
+    changed = changed || d->motion_dirty != d->motion_live;
+    d->motion_live = d->motion_dirty;
+    d->motion_dirty = false;
+    live += d->motion_live ? 1u : 0u;
+  }
+  c->mv_live = c->last_motion[1] = live;
+  if (changed) c->scene_epoch += 1;
+  if (!live) return HK_OK;
+  int rc;
+  const size_t n = c->instances.size();
+  if (n > c->mv_table_cap) {  // (grows rarely: what is enqueued may still read the old table)
+    if ((rc = sync_all(c))) return rc;
+    if (c->mv_table) (void)hipFree(c->mv_table);
+    c->mv_table = nullptr;
+    c->mv_table_cap = 0;
+    HK_HIP(hipMalloc((void**)&c->mv_table, (n + n / 4 + 16) * sizeof(MotionEntry)));
+    c->mv_table_cap = n + n / 4 + 16;
+  }
+  if (c->mv_count && !c->mv_counter) HK_HIP(hipMalloc((void**)&c->mv_counter, sizeof(unsigned int)));
+  uint8_t* st = nullptr;
+  int k = 0;
+  if ((rc = stage(c, n * sizeof(MotionEntry), &st, &k))) return rc;
+  MotionEntry* entries = (MotionEntry*)st;
+  for (size_t i = 0; i < n; ++i) {
+    entries[i] = MotionEntry{nullptr, 0u, 0u};
+    for (const DeformMesh* d : c->deform)
+      if (d->motion_live && memcmp(&d->mesh, &c->instances[i].mesh, sizeof(HkMeshIndex)) == 0) entries[i] = MotionEntry{d->pos_prev, d->max_vertices, 0u};
+  }
+  launch_copy_region(c->stream, c->mv_table, st, n * sizeof(MotionEntry));
+  HK_HIP(hipGetLastError());
+  hk_ctx::DeformStage& stg = c->df_stage[(size_t)k];
+  HK_HIP(hipEventRecord(stg.done, c->stream));
+  stg.pending = true;
+  if (c->mv_count) HK_HIP(hipMemsetAsync(c->mv_counter, 0, sizeof(unsigned int), c->stream));
+  return HK_OK;
+}
+
+int hk::motion_pass(hk_ctx* c, hipStream_t st, const DFrame& fr, const GBuffer& g, float jitter_x, float jitter_y, int y0, int y1) {
+  if (!c->mv_live || y1 <= y0) return HK_OK;
+  MotionTable mt;
+  mt.entries = c->mv_table;
+  mt.n_instances = (uint32_t)std::min(c->instances.size(), c->mv_table_cap);
+  mt.rewritten = c->mv_count ? c->mv_counter : nullptr;
+  launch_motion_velocity(st, c->scene, fr, c->view.inverse_view_proj, c->view.view_proj, c->pview.view_proj, c->d_prev_models, jitter_x, jitter_y, g, mt, y0, y1);
+  HK_HIP(hipGetLastError());
+  c->last_motion[0] += 1;
+  return HK_OK;
+}
+
 extern "C" {
 
 int hk_update_mesh_vertices(hk_ctx* c, const HkMeshIndex* mesh, uint32_t n_vertices, const float* positions, const float* normals) {
@@ -467,6 +557,7 @@ int hk_update_mesh_vertices(hk_ctx* c, const HkMeshIndex* mesh, uint32_t n_verti
   if (normals) memcpy(st + nplane, normals, plane);
   d->n_vertices = n_vertices;
   return deform(c, d, k, [&](float4* vn) {
+    motion_swap(d);
     launch_mesh_stage(c->stream, (const float*)st, normals ? (const float*)(st + nplane) : nullptr, n_vertices, d->pos, vn, d->box);
   });
 }
@@ -571,6 +662,7 @@ int hk_skin_mesh(hk_ctx* c, const HkMeshIndex* mesh, const float* joint_matrices
   memcpy(st, joint_matrices, (size_t)n_joints * 64);
   d->n_vertices = d->skin_vertices;
   return deform(c, d, k, [&](float4* vn) {
+    motion_swap(d);
     launch_copy_region(c->stream, d->joint_mats, st, (size_t)n_joints * 64);  // (a copy kernel: the matrices are read per vertex)
     launch_mesh_skin(c->stream, d->bind_pos, d->bind_nrm, d->joints, d->weights, d->joint_mats, d->skin_vertices, d->pos, vn, d->box);
   });
@@ -786,6 +878,10 @@ int deform_batch(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, bool de
     HK_HIP(hipStreamWaitEvent(c->stream, c->df_src_ready, 0));
   }
   c->scene_epoch += n;  // (scene memory is written from here on: hk_context.hpp, primary-ray pipelining - a refusal above leaves it alone)
+  for (uint32_t i = 0; i < n; ++i) {  // (motion vectors: the plane this batch writes - the staged table is the host's until the launch)
+    motion_swap(meshes[i]);
+    table[i].pos = meshes[i]->pos;
+  }
   launch_deform_batch(c->stream, table, n, bl[0], (uint32_t)blocks[0], bl[1], (uint32_t)blocks[1], bl[2], (uint32_t)blocks[2], 2 * c->mesh.node_cap, orderings,
                       producer ? c->df_src_read : nullptr, bl[3], (uint32_t)blocks[3]);
   HK_HIP(hipGetLastError());
@@ -830,6 +926,71 @@ int hk_deform_meshes_device(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t
   if (n == 0) return HK_OK;
   HK_REQUIRE(items, HK_E_INVALID, "NULL items");
   return deform_batch(c, items, n, true, (hipStream_t)producer_stream);
+}
+
+// Motion vectors for one mesh, on or off (hikari_hip.h).  Enabling gives the mesh its second plane and fills the current one from the
+// triangle planes (DeformMesh::pos holds nothing before a mesh's first update): previous = current, no motion until a deformation.
+// Disabling brings `pos` back to the plane inside the mesh's own allocation and frees the other behind an event.
+int hk_set_mesh_motion_vectors(hk_ctx* c, const HkMeshIndex* mesh, uint32_t enable) {
+  HK_REQUIRE(c && mesh, HK_E_INVALID, "NULL argument");
+  DeformMesh* d = nullptr;
+  int rc;
+  if ((rc = begin(c, mesh, &d))) return rc;
+  if ((enable != 0) == d->motion) return HK_OK;
+  const size_t bytes = (size_t)d->max_vertices * 16;
+  if (enable) {
+    void* plane = nullptr;
+    if (hipMalloc(&plane, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      HK_REQUIRE(false, HK_E_NOMEM, "device allocation of %zu bytes failed", bytes);
+    }
+    if ((rc = join_all(c))) { (void)hipFree(plane); return rc; }
+    d->motion_mem = plane;
+    d->pos_prev = (float4*)plane;
+    const uint8_t* sbase = c->scene_mem + (c->two_slots ? 2 : 1) * c->dyn_capacity;
+    const uint32_t p0 = d->mesh.primitive;
+    launch_mesh_previous_fill(c->stream, (const float4*)(sbase + c->mesh.v0) + p0, (const float4*)(sbase + c->mesh.v1) + p0, (const float4*)(sbase + c->mesh.v2) + p0, d->n_tris,
+                              d->pos, d->max_vertices);
+    HK_HIP(hipGetLastError());
+    d->motion = true;
+    d->motion_dirty = d->motion_live = false;
+    c->mv_enabled += 1;
+  } else {
+    if ((rc = join_all(c))) return rc;
+    if (d->pos != d->pos_home) {  // (the current positions live in the plane that goes: read_mesh_geometry and the next refit find them at home)
+      HK_HIP(hipMemcpyAsync(d->pos_home, d->pos, bytes, hipMemcpyDeviceToDevice, c->stream));
+      d->pos = d->pos_home;
+    }
+    hipEvent_t done = nullptr;
+    HK_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    HK_HIP(hipEventRecord(done, c->stream));
+    retire(c, d->motion_mem, done);
+    d->motion_mem = nullptr;
+    d->pos_prev = nullptr;
+    c->mv_enabled -= 1;
+    c->mv_live -= d->motion_live ? 1u : 0u;
+    d->motion = d->motion_dirty = d->motion_live = false;
+  }
+  c->scene_epoch += 1;  // (the live set may change: the next primary rays take the serial order, behind the table's rewrite)
+  return HK_OK;
+}
+
+// Test hook (hikari_hip_debug.h): launches of the motion pass in the last frame, meshes live in it, pixels it rewrote (counted only with
+// HK_DEBUG_OPT_MOTION_COUNT set before the frame; waits for the frame)
+int hk_debug_last_motion(hk_ctx* c, uint32_t out[3]) {
+  HK_REQUIRE(c && out, HK_E_INVALID, "NULL argument");
+  out[0] = c->last_motion[0];
+  out[1] = c->last_motion[1];
+  out[2] = 0;
+  if (c->mv_count && c->mv_counter && c->last_motion[0]) {
+    HK_HIP(hipSetDevice(c->device));
+    int rc;
+    if ((rc = sync_all(c))) return rc;
+    unsigned int v = 0;
+    HK_HIP(hipMemcpy(&v, c->mv_counter, sizeof(v), hipMemcpyDeviceToHost));
+    out[2] = v;
+  }
+  return HK_OK;
 }
 
 // Test hook (hikari_hip_debug.h)

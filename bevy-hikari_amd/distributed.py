@@ -550,6 +550,10 @@ class MultiEngine:
         table, keep = deform_items(items)
         self.api.call("multi_deform_meshes", self.h, table, len(items))
 
+    def set_mesh_motion_vectors(self, mesh, enabled=True):
+        """hk_multi_set_mesh_motion_vectors: Engine.set_mesh_motion_vectors on every band's copy of the scene."""
+        self.api.call("multi_set_mesh_motion_vectors", self.h, C.byref(mesh), 1 if enabled else 0)
+
     def rebuild_mesh_tree(self, mesh, mode=F.TREE_SAH):
         """hk_multi_rebuild_mesh_tree: the mesh's tree built again on every band's copy of the scene."""
         self.api.call("multi_rebuild_mesh_tree", self.h, C.byref(mesh), mode)

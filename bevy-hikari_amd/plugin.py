@@ -1047,6 +1047,19 @@ class Engine:
         self.api.call("debug_last_deform", self.ctx, out)
         return tuple(int(v) for v in out)
 
+    def set_mesh_motion_vectors(self, mesh, enabled=True):
+        """Per-vertex motion vectors for one deforming mesh, on or off (hk_set_mesh_motion_vectors): the device keeps the mesh's previous
+        local positions (+16 B per vertex) and a pass behind the primary rays writes velocity_uv.xy of its pixels from them, in every
+        frame that follows a deformation of the mesh.  Off by default: velocity is then the reference's rigid formula."""
+        self.api.call("set_mesh_motion_vectors", self.ctx, C.byref(mesh), 1 if enabled else 0)
+
+    def last_motion(self):
+        """(launches of the motion pass in the last frame, meshes live in it, pixels rewritten - counted only with F.DEBUG_OPT_MOTION_COUNT
+        set) - hk_debug_last_motion (test hook)."""
+        out = (F.u32 * 3)()
+        self.api.call("debug_last_motion", self.ctx, out)
+        return tuple(int(v) for v in out)
+
     def rebuild_mesh_tree(self, mesh, mode=F.TREE_SAH):
         """A new tree over the current triangles of one uploaded mesh, built on the device in place (hk_rebuild_mesh_tree): F.TREE_SAH = the
         tree SceneBuilder.rebuild_mesh_tree builds, F.TREE_LBVH = the quick Morton-order tree.  Later deformations refit the new shape."""
@@ -1660,6 +1673,10 @@ class HikariPlugin:
     def deform_meshes(self, items, producer_stream=None):
         """Per frame, every deforming mesh of the scene in one call: Engine.deform_meshes."""
         self.engine.deform_meshes(items, producer_stream)
+
+    def set_mesh_motion_vectors(self, mesh, enabled=True):
+        """Per-vertex motion vectors for one deforming mesh, on or off: Engine.set_mesh_motion_vectors."""
+        self.engine.set_mesh_motion_vectors(mesh, enabled)
 
     def set_instance_transforms(self, builder, models, ids=None, producer_stream=None, status=None):
         """Per frame, instance poses that live in device memory: Engine.set_instance_transforms."""

@@ -500,6 +500,8 @@ class HikariPlugin {
     check(hk_deform_meshes_device(ctx_.get(), items.data(), (uint32_t)items.size(), producer_stream), "hk_deform_meshes_device");
   }
   void rebuild_mesh_tree(const HkMeshIndex& mesh, uint32_t mode = HK_TREE_SAH) { check(hk_rebuild_mesh_tree(ctx_.get(), &mesh, mode), "hk_rebuild_mesh_tree"); }
+  // per-vertex motion vectors for one deforming mesh (hk_set_mesh_motion_vectors): opt-in, +16 B per vertex
+  void set_mesh_motion_vectors(const HkMeshIndex& mesh, bool enabled = true) { check(hk_set_mesh_motion_vectors(ctx_.get(), &mesh, enabled ? 1u : 0u), "hk_set_mesh_motion_vectors"); }
   // instance poses from DEVICE memory: pose k (16 floats, column-major) at d_models + k * stride_bytes is instance ids[k]'s (ids empty: instance
   // k's, n of them); which instance moved is decided on the device.  d_status (device, or nullptr): 1 + the highest instance id whose pose was
   // unusable, or 0, in stream order.  refit_instances / hk_update_scene_instances are refused until update_instances brings the host's poses back
@@ -617,6 +619,7 @@ class HikariMultiGpuPlugin {
   }
   void deform_meshes(const std::vector<HkMeshDeform>& items) { check(hk_multi_deform_meshes(m_, items.data(), (uint32_t)items.size()), "hk_multi_deform_meshes"); }
   void rebuild_mesh_tree(const HkMeshIndex& mesh, uint32_t mode = HK_TREE_SAH) { check(hk_multi_rebuild_mesh_tree(m_, &mesh, mode), "hk_multi_rebuild_mesh_tree"); }
+  void set_mesh_motion_vectors(const HkMeshIndex& mesh, bool enabled = true) { check(hk_multi_set_mesh_motion_vectors(m_, &mesh, enabled ? 1u : 0u), "hk_multi_set_mesh_motion_vectors"); }
   // rows of last frame's reservoirs fetched across the band borders before reprojection (0 for a static camera)
   void set_history_rows(uint32_t rows) { check(hk_multi_set_history_rows(m_, rows), "hk_multi_set_history_rows"); }
   // bands of unequal height: explicit boundaries (scaled render rows, bands + 1 entries; empty = the equal split) ...

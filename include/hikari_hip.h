@@ -334,6 +334,8 @@ typedef struct HkHaloOp {
 /* slot 18 (beyond the HkPass ids): every TRACE launch of the queue-based indirect pass on its own (bounces + 1 launches per pass);
  * selected like a pass, by bit 18 of hk_set_timing_mask - and only so: HK_CTX_TIME_PASSES selects the HkPass slots 0 .. HK_PASS_COUNT - 1 */
 #define HK_TIMING_TRACE_STAGES 18u
+/* slot 19: the motion pass behind the primary rays (hk_set_mesh_motion_vectors), selected by bit 19 of hk_set_timing_mask alone */
+#define HK_TIMING_MOTION_VECTORS 19u
 typedef struct HkStats {
   uint64_t rays_primary;      /* G-buffer rays */
   uint64_t rays_tlas;         /* traverse_top invocations (light.wgsl:442) */
@@ -860,6 +862,23 @@ int hk_read_instance_transforms(hk_ctx* ctx, float* models, uint32_t n);
  * HK_MESH_REBUILD_MAX_TRIANGLES triangles (HK_E_UNSUPPORTED). */
 #define HK_MESH_REBUILD_MAX_TRIANGLES 4194304u
 int hk_rebuild_mesh_tree(hk_ctx* ctx, const HkMeshIndex* mesh, uint32_t mode);
+/* Motion vectors for one deforming mesh, on (enable != 0) or off.  By default velocity_uv.xy is the reference's formula: the previous
+ * INSTANCE transform applied to the CURRENT hit point, so a deformation counts as no motion and everything that reprojects through
+ * the plane (the temporal light passes, the spatial pass's history, SMAA Tu4x, TAA) fetches another surface point's history on a
+ * skinned or morphed mesh.  An enabled mesh keeps its PREVIOUS local positions on the device (one float4 per vertex, +16 B per vertex):
+ * the previous positions of frame k are the positions the mesh had when frame k - 1's primary rays were enqueued.  A pixel whose closest
+ * hit lies on such a mesh deformed since then gets
+ *   velocity = clip_to_uv(view_proj * world) - clip_to_uv(previous_view_proj * M_prev * (P0 + b.x (P1 - P0) + b.y (P2 - P0), 1))
+ * with P0..P2 the previous positions of the hit triangle's corners, b the hit's barycentrics and M_prev the instance's previous model
+ * (where it moved, else its model), in f32 without contraction - written by a pass of its own behind the primary rays, which runs only
+ * while some mesh has such positions.  Several deformations between two frames leave "previous" at the earlier frame's state; a mesh
+ * not deformed between two frames has no motion in the second; previous corners equal to the current ones bit for bit leave the pixel
+ * as the primary rays wrote it; at enable time previous = current.  The planes are keyed by vertex id: hk_rebuild_mesh_tree may permute
+ * triangles freely.  All deformation calls (single, batched, host and device sources) feed it; no deformation call gains a launch or a copy.
+ * Stream-ordered like a deformation; enabling allocates (no wait), disabling frees the plane once the work enqueued has passed.
+ * hk_upload_scene / hk_load_scene drop all motion state, hk_remove_meshes that of the removed meshes.
+ * Refused with nothing written: an unknown mesh record (HK_E_INVALID), no scene (HK_E_NOT_READY). */
+int hk_set_mesh_motion_vectors(hk_ctx* ctx, const HkMeshIndex* mesh, uint32_t enable);
 /* hk_upload_scene for a FINISHED builder that may hold deferred meshes (hk_scene_builder_add_mesh_deferred): synchronous, like an upload.
  * Every pending tree - of a mesh no instance uses yet, too - is built on the device, straight into the mesh-level region in every
  * ordering the scene keeps, single-leaf navigators folded (the form hk_rebuild_mesh_tree writes); all pending meshes below 32 768
@@ -1352,6 +1371,7 @@ int hk_multi_set_mesh_morph_targets(hk_multi* m, const HkMeshIndex* mesh, uint32
                                     const float* base_normals, const float* position_deltas, const float* normal_deltas);
 int hk_multi_deform_meshes(hk_multi* m, const HkMeshDeform* items, uint32_t n);
 int hk_multi_rebuild_mesh_tree(hk_multi* m, const HkMeshIndex* mesh, uint32_t mode);
+int hk_multi_set_mesh_motion_vectors(hk_multi* m, const HkMeshIndex* mesh, uint32_t enable);   /* every band's context; the bands' apron rows get the pass with their primary rays */
 int hk_multi_set_band_bounds(hk_multi* m, const uint32_t* bounds, uint32_t n_bounds);
 /* hk_migrate_bands for the one-process form: the rows that change owner travel as peer copies, then every band takes the new split */
 int hk_multi_migrate_bands(hk_multi* m, const uint32_t* new_bounds, uint32_t n_bounds, uint32_t next_frame_number, const HkSettings* settings);

@@ -57,6 +57,10 @@ int hk_debug_read_emitters(hk_ctx* ctx, float* records, uint32_t records_cap, ui
  * frame or a read, after single-mesh calls too), out[5] the kernel launches of the last derivation of wide records.  out[0..3] are zero
  * until a batch ran; a refused batch leaves them as they were. */
 int hk_debug_last_deform(hk_ctx* ctx, uint32_t out[6]);
+/* Motion vectors (hk_set_mesh_motion_vectors): out[0] launches of the motion pass in the frame whose primary rays were enqueued last,
+ * out[1] the meshes live in it (deformed since the frame before), out[2] the pixels the pass rewrote - counted, one atomic per wave,
+ * only while HK_DEBUG_OPT_MOTION_COUNT is set (the call then waits for the frame); 0 otherwise. */
+int hk_debug_last_motion(hk_ctx* ctx, uint32_t out[3]);
 /* What the last accepted hk_set_instance_transforms_device did: out[0] its kernel launches (the two pose kernels, the refit of the named
  * instances, of the named emitters, of the two trees; the slot copy of a two-slot scene and event records not counted), out[1] 1 if it
  * copied the builder's mesh boxes to the device (the first call for an instance list), else 0.  A refused call leaves them as they were. */
@@ -157,6 +161,7 @@ int hk_debug_comm_lanes(hk_ctx* ctx, uint32_t* lanes);
 #define HK_DEBUG_OPT_LOAD_DEVICE_LIMIT 12u /* hk_load_scene completes a deferred mesh of more than this many triangles on the host instead of the device (default 0: HK_MESH_REBUILD_MAX_TRIANGLES); tests reach that path without a mesh of four million triangles */
 #define HK_DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP 11u /* 1: hk_rebuild_mesh_tree (HK_TREE_SAH) runs the top levels of its build in one workgroup at any mesh size, as the instance tree's build does (default 0: on the whole chip from 32 768 triangles); the same tree either way - the A/B of tools/deform_probe.py */
 #define HK_DEBUG_OPT_KNOWN_RESULTS 13u /* 0: no launch is handed the empty-tile plane of the frame's primary rays - every wave computes its way to the background constants, and stores them whatever the planes hold (default 1; the A/B, tests/test_known_results_gpu.py and tests/test_background_stores_gpu.py) */
+#define HK_DEBUG_OPT_MOTION_COUNT 15u /* 1: the motion pass counts the pixels it rewrites (hk_debug_last_motion; default 0) */
 #define HK_DEBUG_OPT_SPATIAL_KNOWN 14u /* 0: no spatial_reuse launch is handed the table of the background's known records - every background wave loads, unpacks and re-packs its input - and the windowed form of the kernel is handed no empty-tile / kept-tile plane (default 1; the A/B and tests/test_spatial_background_gpu.py) */
 int hk_debug_set_option(hk_ctx* ctx, uint32_t option, int64_t value);
 /* Test hook of the empty-tile plane (one byte per 8x8 tile of the render image, row-major, (w + 7) / 8 x (h + 7) / 8; 1 = every primary

@@ -12,7 +12,7 @@ CSRC = os.path.join(ROOT, "bevy-hikari_amd", "csrc")
 # -ffp-contract=off: only the fmaf() calls written in the sources become v_fma_f32 (numeric contract).  gfx950 only.
 # -fvisibility=hidden: the library exports the entry points of include/hikari_hip.h / hikari_hip_debug.h (their #pragma GCC visibility) and nothing else.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
-SOURCES = ["kernels.hip", "kernels_denoise.hip", "kernels_aa.hip", "kernels_wavefront.hip", "kernels_query.hip", "kernels_scene.hip", "kernels_tree.hip", "context.hip", "scene_layout.hip", "scene_refit.hip", "kernels_deform.hip", "mesh_deform.hip", "scene_load.hip", "scene_move.hip", "scene_append.hip", "scene_remove.hip", "scene_instances.hip",
+SOURCES = ["kernels.hip", "kernels_denoise.hip", "kernels_aa.hip", "kernels_wavefront.hip", "kernels_query.hip", "kernels_scene.hip", "kernels_tree.hip", "context.hip", "scene_layout.hip", "scene_refit.hip", "kernels_deform.hip", "kernels_motion.hip", "mesh_deform.hip", "scene_load.hip", "scene_move.hip", "scene_append.hip", "scene_remove.hip", "scene_instances.hip",
            "probes.hip", "host_logic.cpp", "scene_builder.cpp", "comm.cpp"]
 
 
