@@ -3,6 +3,7 @@
 // (mesh.rs:76-166: a BVH build and a re-layout of the whole mesh level); here the new vertices are written into the mesh-level region,
 // the mesh tree is REFIT in every ordering that holds it (same links, every box the union of the triangle boxes below it), and the
 // new mesh box goes up to the instances, emitters and both instance-level trees - all stream-ordered behind the frames enqueued before.
+#include <array>
 #include <string>
 
 #include "hk_context.hpp"
@@ -52,10 +53,41 @@ struct DeformMesh {
   bool motion_live = false;     // pos_prev holds the previous positions of the frame most recently begun
 };
 
+namespace {
+// every device allocation of a deformable mesh: what free_deform frees and a removed mesh hands to its caller to retire
+std::array<void*, 6> allocations(const DeformMesh* d) { return {d->mem, d->skin_mem, (void*)d->joint_mats, d->nrm_mem, d->morph_mem, d->motion_mem}; }
+// the deformable mesh of a record (NULL: none made yet - find_mesh makes them, one per record)
+DeformMesh* lookup(const hk_ctx* c, const HkMeshIndex& m) {
+  for (DeformMesh* d : c->deform)
+    if (memcmp(&d->mesh, &m, sizeof(HkMeshIndex)) == 0) return d;
+  return nullptr;
+}
+// a device array that has to grow (rarely): what is enqueued may still read the old one, so wait for it, free, allocate `want`
+// elements of `elem` bytes
+template <typename T, typename N>
+int regrow(hk_ctx* c, T*& p, N& cap, size_t want, size_t elem) {
+  int rc;
+  if ((rc = sync_all(c))) return rc;
+  if (p) (void)hipFree(p);
+  p = nullptr;
+  cap = 0;
+  HK_HIP(hipMalloc((void**)&p, want * elem));
+  cap = (N)want;
+  return HK_OK;
+}
+// consecutive planes of one allocation, each starting on a 256-byte boundary
+inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct Carve {
+  uint8_t* p;
+  template <typename T>
+  T* take(size_t bytes) { T* q = (T*)p; p += al256(bytes); return q; }
+};
+}  // namespace
+
 namespace hk {
 void free_deform(hk_ctx* c) {
   for (DeformMesh* d : c->deform) {
-    for (void* q : {d->mem, d->skin_mem, (void*)d->joint_mats, d->nrm_mem, d->morph_mem, d->motion_mem})
+    for (void* q : allocations(d))
       if (q) (void)hipFree(q);
     delete d;
   }
@@ -89,9 +121,8 @@ void deform_mesh_records(const hk_ctx* c, std::vector<HkMeshIndex>& out) {
 // hk_change_scene_instances (scene_instances.hip): the box words of a mesh deformed on the device (NULL: the builder's box is current),
 // and - that call having carried every deformed mesh's box to the new instance level - nothing left to flush
 const uint32_t* deformed_mesh_box(const hk_ctx* c, const HkMeshIndex& m) {
-  for (const DeformMesh* d : c->deform)
-    if (d->deformed && memcmp(&d->mesh, &m, sizeof(HkMeshIndex)) == 0) return d->box;
-  return nullptr;
+  const DeformMesh* d = lookup(c, m);
+  return d && d->deformed ? d->box : nullptr;
 }
 void deform_flushed(hk_ctx* c) {
   for (DeformMesh* d : c->deform) d->pending = false;
@@ -103,7 +134,7 @@ void rebase_deform_meshes(hk_ctx* c, const std::vector<CompactRun> runs[3], std:
     bool survives = false;
     for (const CompactRun& r : runs[0]) survives = survives || (d->mesh.node_offset >= r.src && d->mesh.node_offset - r.src < r.count);
     if (!survives) {
-      for (void* q : {d->mem, d->skin_mem, (void*)d->joint_mats, d->nrm_mem, d->morph_mem, d->motion_mem})
+      for (void* q : allocations(d))
         if (q) freed.push_back(q);
       if (d->motion) {  // (the survivors keep their planes and their state; the table is written again at the next frame with a live mesh)
         c->mv_enabled -= 1;
@@ -187,8 +218,7 @@ int find_mesh(hk_ctx* c, const HkMeshIndex* m, DeformMesh** out) {
     if (in.mesh.vertex > m->vertex) next_vertex = std::min(next_vertex, in.mesh.vertex);
   }
   HK_REQUIRE(known, HK_E_INVALID, "no uploaded instance carries the mesh record (%u, %u, %u, %u)", m->vertex, m->primitive, m->node_offset, m->node_count);
-  for (DeformMesh* d : c->deform)
-    if (memcmp(&d->mesh, m, sizeof(HkMeshIndex)) == 0) { *out = d; return HK_OK; }
+  if ((*out = lookup(c, *m))) return HK_OK;
   HK_REQUIRE(m->node_count >= 1 && (m->node_count + 2) % 3 == 0, HK_E_UNSUPPORTED, "the mesh tree is not a binary tree in the flatten_custom layout (%u nodes)", m->node_count);
   const uint32_t n_tris = (m->node_count + 2) / 3;
   HK_REQUIRE((size_t)m->primitive + n_tris <= c->primitives.size() && (size_t)m->node_offset + m->node_count <= c->asset_nodes.size() && m->vertex < c->vertices.size(),
@@ -207,27 +237,26 @@ int find_mesh(hk_ctx* c, const HkMeshIndex* m, DeformMesh** out) {
   d->min_vertices = d->max_vertices = max_ref + 1;  // the vertices the mesh's triangles span: nothing beyond them is ever written
   const size_t n = n_tris, ni = std::max<size_t>(n - 1, 1), nv = d->max_vertices;
   (void)next_vertex;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const auto al = al256;
   const size_t bytes = al(5 * ni * 4) + al(2 * n * 4) + al(ni * 4) + al(ni) + 2 * al((2 * n - 1) * 16) + 2 * al(n * 16) + al(nv * 16) + al(32);
   if (hipMalloc(&d->mem, bytes) != hipSuccess) {
     delete d;
     HK_REQUIRE(false, HK_E_NOMEM, "device allocation of %zu bytes failed", bytes);
   }
-  uint8_t* p = (uint8_t*)d->mem;
-  auto take = [&](size_t b) { uint8_t* q = p; p += al(b); return q; };
-  uint32_t* topo = (uint32_t*)take(5 * ni * 4);
+  Carve cv{(uint8_t*)d->mem};
+  uint32_t* topo = cv.take<uint32_t>(5 * ni * 4);
   d->tree.n = n_tris;
   d->tree.parent = topo; d->tree.left = topo + ni; d->tree.right = topo + 2 * ni; d->tree.first = topo + 3 * ni; d->tree.last = topo + 4 * ni;
-  uint32_t* leaves = (uint32_t*)take(2 * n * 4);
+  uint32_t* leaves = cv.take<uint32_t>(2 * n * 4);
   d->tree.leaf_parent = leaves; d->tree.leaf_shape = leaves + n;
-  d->tree.arrived = (uint32_t*)take(ni * 4);
-  d->tree.swap = take(ni);
-  d->tree.node_lo = (float4*)take((2 * n - 1) * 16);
-  d->tree.node_hi = (float4*)take((2 * n - 1) * 16);
-  d->tree.tri_lo = (float4*)take(n * 16);
-  d->tree.tri_hi = (float4*)take(n * 16);
-  d->pos = d->pos_home = (float4*)take(nv * 16);
-  d->box = (uint32_t*)take(32);
+  d->tree.arrived = cv.take<uint32_t>(ni * 4);
+  d->tree.swap = cv.take<uint8_t>(ni);
+  d->tree.node_lo = cv.take<float4>((2 * n - 1) * 16);
+  d->tree.node_hi = cv.take<float4>((2 * n - 1) * 16);
+  d->tree.tri_lo = cv.take<float4>(n * 16);
+  d->tree.tri_hi = cv.take<float4>(n * 16);
+  d->pos = d->pos_home = cv.take<float4>(nv * 16);
+  d->box = cv.take<uint32_t>(32);
   c->deform.push_back(d);  // (owned by the context from here on, freed by free_deform)
   std::vector<uint32_t> host(5 * ni + 2 * n, 0);
   auto put = [&](const std::vector<uint32_t>& v, size_t at) { std::copy(v.begin(), v.end(), host.begin() + at); };
@@ -327,11 +356,11 @@ int corner_list(hk_ctx* c, DeformMesh* d) {
   std::vector<uint32_t> at(off, off + nv);
   for (size_t t = 0; t < nt; ++t)
     for (int k = 0; k < 3; ++k) tri[at[prims[t].vertices[k].index]++] = (uint32_t)t;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t bytes = al(nt * 16) + host.size() * 4;
+  const size_t bytes = al256(nt * 16) + host.size() * 4;
   HK_REQUIRE(hipMalloc(&d->nrm_mem, bytes) == hipSuccess, HK_E_NOMEM, "device allocation of %zu bytes failed", bytes);
-  d->face = (float4*)d->nrm_mem;
-  d->corner_off = (uint32_t*)((uint8_t*)d->nrm_mem + al(nt * 16));
+  Carve cv{(uint8_t*)d->nrm_mem};
+  d->face = cv.take<float4>(nt * 16);
+  d->corner_off = cv.take<uint32_t>(host.size() * 4);
   d->corner_tri = d->corner_off + nv + 1;
   if (hipMemcpy(d->corner_off, host.data(), host.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipFree(d->nrm_mem);
@@ -349,21 +378,6 @@ int begin(hk_ctx* c, const HkMeshIndex* m, DeformMesh** d) {
   if ((rc = finalize_scene(c))) return rc;
   if ((rc = find_mesh(c, m, d))) return rc;
   return mesh_instances(c, *d);
-}
-
-// the device work after the vertices of `d` are in `d->pos` (and its normals in the normal plane): triangles, the mesh tree in every
-// ordering.  The instance level follows once for all meshes deformed before the next frame (flush_deform).
-int refit_mesh(hk_ctx* c, DeformMesh* d) {
-  const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
-  uint8_t* sbase = c->scene_mem + slots;
-  const uint32_t p0 = d->mesh.primitive;
-  launch_mesh_triangles(c->stream, d->pos, (float4*)(sbase + c->mesh.v0) + p0, (float4*)(sbase + c->mesh.v1) + p0, (float4*)(sbase + c->mesh.v2) + p0, d->n_tris, d->tree.tri_lo,
-                        d->tree.tri_hi);
-  launch_mesh_tree_refit(c->stream, d->tree, (float4*)(sbase + c->mesh.nodes) + 2 * (size_t)d->mesh.node_offset, 2 * c->mesh.node_cap, c->threaded ? 8u : 1u);
-  HK_HIP(hipGetLastError());
-  d->deformed = d->pending = d->have_boxes = true;
-  c->deform_pending = true;
-  return HK_OK;
 }
 
 // what every deformation leaves behind on the host side, whatever it wrote: the mirrors are stale, the wide records of the mesh trees
@@ -388,6 +402,21 @@ void motion_swap(DeformMesh* d) {
   d->motion_dirty = true;
 }
 
+// the device work after the vertices of `d` are in `d->pos` (and its normals in the normal plane): triangles, the mesh tree in every
+// ordering.  The instance level follows once for all meshes deformed before the next frame (flush_deform).
+int refit_mesh(hk_ctx* c, DeformMesh* d) {
+  const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
+  uint8_t* sbase = c->scene_mem + slots;
+  const uint32_t p0 = d->mesh.primitive;
+  launch_mesh_triangles(c->stream, d->pos, (float4*)(sbase + c->mesh.v0) + p0, (float4*)(sbase + c->mesh.v1) + p0, (float4*)(sbase + c->mesh.v2) + p0, d->n_tris, d->tree.tri_lo,
+                        d->tree.tri_hi);
+  launch_mesh_tree_refit(c->stream, d->tree, (float4*)(sbase + c->mesh.nodes) + 2 * (size_t)d->mesh.node_offset, 2 * c->mesh.node_cap, c->threaded ? 8u : 1u);
+  HK_HIP(hipGetLastError());
+  d->deformed = d->pending = d->have_boxes = true;
+  c->deform_pending = true;
+  return HK_OK;
+}
+
 // one deformation: `fill` enqueues the vertex kernel (positions into d->pos, normals into the normal plane, the mesh box into d->box)
 template <typename Fill>
 int deform(hk_ctx* c, DeformMesh* d, int k, Fill fill) {
@@ -410,6 +439,231 @@ int deform(hk_ctx* c, DeformMesh* d, int k, Fill fill) {
   return HK_OK;
 }
 
+// Many meshes in one call (hikari_hip.h): what the single calls do for each item, as five launches over all of them
+// (kernels_deform.hip launch_deform_batch).  Everything the device reads of the call - the item table, the workgroup tables of the
+// three launch shapes, every item's positions / normals / joint matrices / morph weights - travels in ONE pinned staging block.
+// hk_deform_meshes_device is the same batch with `device` set: the items' data stays where the caller has it (validated first: memory the
+// device can read, aligned, strided), only the tables are staged, `producer` (or NULL) is ordered against the context's stream by two
+// events, and flagged items recompute their normals in a sixth launch.
+// Three steps: plan_batch validates and sizes, stage_batch fills the staging block, enqueue_batch launches.  The WHOLE batch is validated
+// before anything is enqueued or written: nothing but plan_batch refuses an item.
+inline bool is_skin(uint32_t kind) { return kind == HK_DEFORM_SKIN || kind == HK_DEFORM_MORPH_SKIN; }
+inline bool is_morph(uint32_t kind) { return kind == HK_DEFORM_MORPH || kind == HK_DEFORM_MORPH_SKIN; }
+inline size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
+struct DeformPlan {
+  std::vector<DeformMesh*> meshes;   // per item
+  uint32_t orderings = 1, total_vertices = 0, total_tris = 0;
+  size_t data_bytes = 0;             // the items' data in the staging block (host sources only)
+  size_t blocks[4] = {0, 0, 0, 0};   // vertex, triangle, node workgroups; the vertex workgroups of the items that recompute normals
+  // the staging block (stage_batch): item table | vertex, triangle, node and normal workgroups | the items' data
+  int stage = 0;
+  DeformItem* table = nullptr;
+  SegmentBlock* bl[4] = {nullptr, nullptr, nullptr, nullptr};
+};
+
+int plan_batch(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, bool device, DeformPlan& p) {
+  int rc;
+  c->df_batch += 1;
+  p.meshes.assign(n, nullptr);
+  p.orderings = c->threaded ? 8u : 1u;
+  for (uint32_t i = 0; i < n; ++i) {
+    const HkMeshDeformDevice& it = items[i];
+    HK_REQUIRE(it.kind <= HK_DEFORM_MORPH_SKIN, HK_E_INVALID, "item %u: unknown kind %u", i, it.kind);
+    const bool skins = is_skin(it.kind), morphs = is_morph(it.kind);
+    HK_REQUIRE(it.data && it.count, HK_E_INVALID, "item %u: NULL data or a count of zero", i);
+    HK_REQUIRE(it.kind != HK_DEFORM_SKIN || !it.normals, HK_E_INVALID, "item %u: a skin item takes no normals", i);
+    HK_REQUIRE(it.kind != HK_DEFORM_MORPH || !it.normals, HK_E_INVALID, "item %u: a morph item takes no normals (its data are the weights)", i);
+    HK_REQUIRE(it.kind != HK_DEFORM_MORPH_SKIN || it.normals, HK_E_INVALID, "item %u: a morph + skin item names its weights in `normals`: NULL", i);
+    const bool recompute = (it.flags & HK_DEFORM_RECOMPUTE_NORMALS) != 0;
+    if (device) {
+      HK_REQUIRE(!(it.flags & ~HK_DEFORM_RECOMPUTE_NORMALS), HK_E_INVALID, "item %u: unknown flag bits 0x%x", i, it.flags & ~HK_DEFORM_RECOMPUTE_NORMALS);
+      HK_REQUIRE(!recompute || !morphs, HK_E_INVALID, "item %u: a morph item cannot recompute its normals (HK_DEFORM_RECOMPUTE_NORMALS is for vertex items)", i);
+      HK_REQUIRE(!recompute || it.kind == HK_DEFORM_VERTICES, HK_E_INVALID, "item %u: a skin item cannot recompute its normals (the skin transforms them)", i);
+      HK_REQUIRE(!recompute || !it.normals, HK_E_INVALID, "item %u: normals given together with HK_DEFORM_RECOMPUTE_NORMALS", i);
+      if (skins) {
+        HK_REQUIRE(it.data_stride == 0 || it.data_stride == 64, HK_E_INVALID, "item %u: joint matrices are contiguous (a stride of 0 or 64 bytes, not %u)", i, it.data_stride);
+        HK_REQUIRE(!morphs || it.normals_stride == 0 || it.normals_stride == 4, HK_E_INVALID, "item %u: morph weights are contiguous (a stride of 0 or 4 bytes, not %u)", i,
+                   it.normals_stride);
+      } else if (morphs) {
+        HK_REQUIRE(it.data_stride == 0 || it.data_stride == 4, HK_E_INVALID, "item %u: morph weights are contiguous (a stride of 0 or 4 bytes, not %u)", i, it.data_stride);
+      } else {
+        for (const uint32_t stride : {it.data_stride, it.normals ? it.normals_stride : 0u})
+          HK_REQUIRE(stride == 0 || (stride >= 12 && stride % 4 == 0), HK_E_INVALID, "item %u: a stride of %u bytes (0, or a multiple of 4 from 12 on)", i, stride);
+      }
+    }
+    DeformMesh* d = nullptr;
+    if (skins || morphs) {
+      d = lookup(c, it.mesh);
+      HK_REQUIRE(!morphs || (d && d->morph_vertices), HK_E_INVALID, "item %u: no morph set for this mesh (hk_set_mesh_morph_targets)", i);
+      HK_REQUIRE(it.kind != HK_DEFORM_MORPH || it.count == d->morph_targets, HK_E_INVALID, "item %u: the morph set has %u targets but %u weights were given", i,
+                 d->morph_targets, it.count);
+      HK_REQUIRE(!skins || (d && d->skin_vertices), HK_E_INVALID, "item %u: no skin set for this mesh (hk_set_mesh_skin)", i);
+      HK_REQUIRE(!(skins && morphs) || d->skin_vertices == d->morph_vertices, HK_E_INVALID, "item %u: the skin has %u vertices, the morph set %u", i, d->skin_vertices,
+                 d->morph_vertices);
+      HK_REQUIRE(!skins || d->max_joint < it.count, HK_E_INVALID, "item %u: the skin names joint %u but only %u joint matrices were given", i, d->max_joint, it.count);
+    }
+    if ((rc = find_mesh(c, &it.mesh, &d)) || (rc = mesh_instances(c, d))) {
+      const std::string why = hk_last_error();
+      set_error("item %u: %s", i, why.c_str());
+      return rc;
+    }
+    HK_REQUIRE(it.kind != HK_DEFORM_VERTICES || (it.count >= d->min_vertices && it.count <= d->max_vertices), HK_E_INVALID,
+               "item %u: the mesh has between %u and %u vertices, not %u", i, d->min_vertices, d->max_vertices, it.count);
+    HK_REQUIRE(d->batch != c->df_batch, HK_E_INVALID, "item %u: the mesh record (%u, %u, %u, %u) is named twice in one batch", i, it.mesh.vertex, it.mesh.primitive,
+               it.mesh.node_offset, it.mesh.node_count);
+    d->batch = c->df_batch;
+    p.meshes[i] = d;
+    const uint32_t nv = morphs ? d->morph_vertices : skins ? d->skin_vertices : it.count;
+    if (device) {  // (the counts are known to be the mesh's: the extents below are what the kernels will read)
+      if (skins) {
+        if ((rc = check_source(c, i, "joint matrices", it.data, 16, (size_t)it.count * 64))) return rc;
+        if (morphs && (rc = check_source(c, i, "morph weights", it.normals, 4, (size_t)d->morph_targets * 4))) return rc;
+      } else if (morphs) {
+        if ((rc = check_source(c, i, "morph weights", it.data, 4, (size_t)d->morph_targets * 4))) return rc;
+      } else {
+        if ((rc = check_source(c, i, "positions", it.data, 4, (size_t)(nv - 1) * stride_of(it.data_stride) + 12))) return rc;
+        if (it.normals && (rc = check_source(c, i, "normals", it.normals, 4, (size_t)(nv - 1) * stride_of(it.normals_stride) + 12))) return rc;
+      }
+      if (recompute) p.blocks[3] += (nv + 255u) / 256u;
+    } else {  // (host sources travel in the staging block: morph weights, then the palette or the vertex planes)
+      if (morphs) p.data_bytes += al16((size_t)d->morph_targets * 4);
+      if (skins) p.data_bytes += (size_t)it.count * 64;
+      else if (!morphs) p.data_bytes += al16((size_t)it.count * 12) * (it.normals ? 2 : 1);
+    }
+    p.total_vertices += nv;
+    p.total_tris += d->n_tris;
+    p.blocks[0] += (nv + 255u) / 256u;
+    p.blocks[1] += (d->n_tris + 255u) / 256u;
+    p.blocks[2] += ((size_t)(2u * d->n_tris - 1u) * p.orderings + 255u) / 256u;
+  }
+  return HK_OK;
+}
+
+int stage_batch(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, bool device, bool producer, DeformPlan& p) {
+  int rc;
+  // what has to grow first (a mesh's first recomputed normals, the first skinning of a mesh, a longer palette): behind a wait
+  for (uint32_t i = 0; i < n; ++i) {
+    DeformMesh* d = p.meshes[i];
+    if ((items[i].flags & HK_DEFORM_RECOMPUTE_NORMALS) && !d->nrm_mem && ((rc = sync_all(c)) || (rc = corner_list(c, d)))) return rc;
+    if (is_skin(items[i].kind) && items[i].count > d->joint_cap && (rc = regrow(c, d->joint_mats, d->joint_cap, items[i].count, 64))) return rc;
+  }
+  if (producer)
+    for (hipEvent_t* e : {&c->df_src_ready, &c->df_src_read})
+      if (!*e) HK_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  const size_t table_bytes = al256(n * sizeof(DeformItem));
+  const size_t block_bytes = al256((p.blocks[0] + p.blocks[1] + p.blocks[2] + p.blocks[3]) * sizeof(SegmentBlock));
+  uint8_t* st = nullptr;
+  if ((rc = stage(c, table_bytes + block_bytes + p.data_bytes, &st, &p.stage))) return rc;
+  p.table = (DeformItem*)st;
+  p.bl[0] = (SegmentBlock*)(st + table_bytes);
+  for (int s = 1; s < 4; ++s) p.bl[s] = p.bl[s - 1] + p.blocks[s - 1];
+  uint8_t* data = st + table_bytes + block_bytes;
+  auto staged = [&](const void* src, size_t bytes, size_t advance) {  // a host source into the block; a device source stays where it is
+    if (device) return src;
+    memcpy(data, src, bytes);
+    data += advance;
+    return (const void*)(data - advance);
+  };
+  uint8_t* sbase = c->scene_mem + (c->two_slots ? 2 : 1) * c->dyn_capacity;
+  size_t at[4] = {0, 0, 0, 0};
+  for (uint32_t i = 0; i < n; ++i) {
+    const HkMeshDeformDevice& it = items[i];
+    DeformMesh* d = p.meshes[i];
+    DeformItem t{};
+    t.pos_stride = t.nrm_stride = 3u;
+    t.kind = it.kind;
+    t.n_tris = d->n_tris;
+    const bool skins = is_skin(it.kind), morphs = is_morph(it.kind);
+    if (morphs) {  // (the weights: `data` of a morph item, `normals` of a morph + skin item)
+      const size_t bytes = (size_t)d->morph_targets * 4;
+      t.n_vertices = d->morph_vertices;
+      t.n_targets = d->morph_targets;
+      t.morph_src = (const float*)staged(skins ? it.normals : it.data, bytes, al16(bytes));
+      t.morph_base_p = d->morph_base_p; t.morph_base_n = d->morph_base_n; t.morph_dp = d->morph_dp; t.morph_dn = d->morph_dn;
+      t.morph_w = d->morph_w; t.morph_active = d->morph_active;
+    }
+    if (skins) {
+      t.n_vertices = d->skin_vertices;
+      t.n_joints = it.count;
+      t.palette = (const float4*)staged(it.data, (size_t)it.count * 64, (size_t)it.count * 64);
+      t.joint_mats = d->joint_mats;
+      t.bind_pos = d->bind_pos; t.bind_nrm = d->bind_nrm; t.weights = d->weights; t.joints = d->joints;
+    } else if (!morphs) {
+      const size_t plane = (size_t)it.count * 12;  // (of a host source: packed)
+      t.n_vertices = it.count;
+      t.positions = (const float*)staged(it.data, plane, al16(plane));
+      if (it.normals) t.normals = (const float*)staged(it.normals, plane, al16(plane));
+      t.pos_stride = stride_of(it.data_stride) / 4u;
+      t.nrm_stride = stride_of(it.normals_stride) / 4u;
+      if (it.flags & HK_DEFORM_RECOMPUTE_NORMALS) {
+        t.face = d->face;
+        t.corner_off = d->corner_off;
+        t.corner_tri = d->corner_tri;
+        for (uint32_t first = 0; first < t.n_vertices; first += 256) p.bl[3][at[3]++] = SegmentBlock{i, first};
+      }
+    }
+    t.vn = (float4*)(sbase + c->mesh.vn) + d->mesh.vertex;   // (t.pos: enqueue_batch, behind the motion swap)
+    t.box = d->box;
+    t.v0 = (float4*)(sbase + c->mesh.v0) + d->mesh.primitive;
+    t.v1 = (float4*)(sbase + c->mesh.v1) + d->mesh.primitive;
+    t.v2 = (float4*)(sbase + c->mesh.v2) + d->mesh.primitive;
+    t.tree = d->tree;
+    t.nodes = (float4*)(sbase + c->mesh.nodes) + 2 * (size_t)d->mesh.node_offset;
+    p.table[i] = t;
+    const size_t threads[3] = {t.n_vertices, t.n_tris, (size_t)(2u * t.n_tris - 1u) * p.orderings};
+    for (int s = 0; s < 3; ++s)
+      for (size_t first = 0; first < threads[s]; first += 256) p.bl[s][at[s]++] = SegmentBlock{i, (uint32_t)first};
+  }
+  return HK_OK;
+}
+
+int enqueue_batch(hk_ctx* c, uint32_t n, hipStream_t producer, const DeformPlan& p) {
+  int rc;
+  if ((rc = join_all(c))) return rc;  // behind every frame enqueued so far on every stream that reads the scene (stream waits), as a single deformation is
+  if (producer) {  // what the producer has enqueued on the sources so far comes first; it may write them again once the vertex launch has read them
+    HK_HIP(hipEventRecord(c->df_src_ready, producer));
+    HK_HIP(hipStreamWaitEvent(c->stream, c->df_src_ready, 0));
+  }
+  c->scene_epoch += n;  // (scene memory is written from here on: hk_context.hpp, primary-ray pipelining - a refusal above leaves it alone)
+  for (uint32_t i = 0; i < n; ++i) {  // (motion vectors: the plane this batch writes - the staged table is the host's until the launch)
+    motion_swap(p.meshes[i]);
+    p.table[i].pos = p.meshes[i]->pos;
+  }
+  launch_deform_batch(c->stream, p.table, n, p.bl[0], (uint32_t)p.blocks[0], p.bl[1], (uint32_t)p.blocks[1], p.bl[2], (uint32_t)p.blocks[2], 2 * c->mesh.node_cap, p.orderings,
+                      producer ? c->df_src_read : nullptr, p.bl[3], (uint32_t)p.blocks[3]);
+  HK_HIP(hipGetLastError());
+  if (producer) HK_HIP(hipStreamWaitEvent(producer, c->df_src_read, 0));
+  hk_ctx::DeformStage& stg = c->df_stage[(size_t)p.stage];
+  HK_HIP(hipEventRecord(stg.done, c->stream));
+  stg.pending = true;
+  std::vector<std::pair<uint32_t, uint32_t>> keys(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    DeformMesh* d = p.meshes[i];
+    d->n_vertices = p.table[i].n_vertices;
+    d->deformed = d->pending = d->have_boxes = true;
+    keys[i] = std::make_pair(d->mesh.node_offset, d->mesh.node_count);
+  }
+  c->deform_pending = true;
+  std::sort(keys.begin(), keys.end());
+  mark_deformed(c, keys);
+  c->last_deform[0] = n;
+  c->last_deform[1] = p.total_vertices;
+  c->last_deform[2] = p.total_tris;
+  c->last_deform[3] = p.blocks[3] ? 6u : 5u;  // begin, vertices, triangles, (normals,) boxes, emit
+  return HK_OK;
+}
+
+int deform_batch(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, bool device, hipStream_t producer) {
+  HK_REQUIRE(c->have_meshes && c->have_materials && c->have_instances, HK_E_NOT_READY, "hk_upload_scene must come first");
+  HK_HIP(hipSetDevice(c->device));
+  int rc;
+  if ((rc = finalize_scene(c))) return rc;
+  DeformPlan p;
+  if ((rc = plan_batch(c, items, n, device, p))) return rc;
+  if ((rc = stage_batch(c, items, n, device, producer != nullptr, p))) return rc;
+  return enqueue_batch(c, n, producer, p);
+}
+
 // the new boxes of the meshes selected by `which` to their instances and emitters - ONE launch each over the instances / the emitters of
 // all those meshes, however many - then ONE refit of the instance tree and the light tree
 template <typename Which>
@@ -429,15 +683,7 @@ int propagate(hk_ctx* c, Which which) {
   MeshInstanceEntry* entries = nullptr;
   int k = -1;
   if (n_entries) {
-    if (n_emitters > c->df_records_cap) {  // (grows rarely: what is enqueued may still read the old array)
-      if ((rc = sync_all(c))) return rc;
-      if (c->df_records) (void)hipFree(c->df_records);
-      c->df_records = nullptr;
-      c->df_records_cap = 0;
-      const size_t cap = n_emitters + n_emitters / 4 + 16;
-      HK_HIP(hipMalloc((void**)&c->df_records, cap * sizeof(RefitUpdate)));
-      c->df_records_cap = cap;
-    }
+    if (n_emitters > c->df_records_cap && (rc = regrow(c, c->df_records, c->df_records_cap, n_emitters + n_emitters / 4 + 16, sizeof(RefitUpdate)))) return rc;
     uint8_t* st = nullptr;
     if ((rc = stage(c, n_entries * sizeof(MeshInstanceEntry), &st, &k))) return rc;
     entries = (MeshInstanceEntry*)st;
@@ -500,23 +746,15 @@ int hk::motion_frame(hk_ctx* c) {
   if (!live) return HK_OK;
   int rc;
   const size_t n = c->instances.size();
-  if (n > c->mv_table_cap) {  // (grows rarely: what is enqueued may still read the old table)
-    if ((rc = sync_all(c))) return rc;
-    if (c->mv_table) (void)hipFree(c->mv_table);
-    c->mv_table = nullptr;
-    c->mv_table_cap = 0;
-    HK_HIP(hipMalloc((void**)&c->mv_table, (n + n / 4 + 16) * sizeof(MotionEntry)));
-    c->mv_table_cap = n + n / 4 + 16;
-  }
+  if (n > c->mv_table_cap && (rc = regrow(c, c->mv_table, c->mv_table_cap, n + n / 4 + 16, sizeof(MotionEntry)))) return rc;
   if (c->mv_count && !c->mv_counter) HK_HIP(hipMalloc((void**)&c->mv_counter, sizeof(unsigned int)));
   uint8_t* st = nullptr;
   int k = 0;
   if ((rc = stage(c, n * sizeof(MotionEntry), &st, &k))) return rc;
   MotionEntry* entries = (MotionEntry*)st;
   for (size_t i = 0; i < n; ++i) {
-    entries[i] = MotionEntry{nullptr, 0u, 0u};
-    for (const DeformMesh* d : c->deform)
-      if (d->motion_live && memcmp(&d->mesh, &c->instances[i].mesh, sizeof(HkMeshIndex)) == 0) entries[i] = MotionEntry{d->pos_prev, d->max_vertices, 0u};
+    const DeformMesh* d = lookup(c, c->instances[i].mesh);
+    entries[i] = d && d->motion_live ? MotionEntry{d->pos_prev, d->max_vertices, 0u} : MotionEntry{nullptr, 0u, 0u};
   }
   launch_copy_region(c->stream, c->mv_table, st, n * sizeof(MotionEntry));
   HK_HIP(hipGetLastError());
@@ -609,7 +847,7 @@ int hk_set_mesh_morph_targets(hk_ctx* c, const HkMeshIndex* mesh, uint32_t n_ver
   if ((rc = begin(c, mesh, &d))) return rc;
   HK_REQUIRE(n_vertices >= d->min_vertices && n_vertices <= d->max_vertices, HK_E_INVALID, "the mesh has between %u and %u vertices, not %u", d->min_vertices,
              d->max_vertices, n_vertices);
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const auto al = al256;
   const size_t plane = (size_t)n_vertices * 12, deltas = plane * n_targets;
   const size_t bytes = 2 * al(plane) + (normal_deltas ? 2 : 1) * al(deltas) + al((size_t)n_targets * 4) + al(((size_t)n_targets + 1) * 4);
   if ((rc = sync_all(c))) return rc;  // (a set given again: the kernels enqueued so far may still read the old one)
@@ -621,14 +859,13 @@ int hk_set_mesh_morph_targets(hk_ctx* c, const HkMeshIndex* mesh, uint32_t n_ver
     d->morph_mem = nullptr;
     HK_REQUIRE(false, HK_E_NOMEM, "device allocation of %zu bytes failed", bytes);
   }
-  uint8_t* p = (uint8_t*)d->morph_mem;
-  auto take = [&](size_t b) { uint8_t* q = p; p += al(b); return q; };
-  d->morph_base_p = (float*)take(plane);
-  d->morph_base_n = (float*)take(plane);
-  d->morph_dp = (float*)take(deltas);
-  d->morph_dn = normal_deltas ? (float*)take(deltas) : nullptr;
-  d->morph_w = (float*)take((size_t)n_targets * 4);
-  d->morph_active = (uint32_t*)take(((size_t)n_targets + 1) * 4);
+  Carve cv{(uint8_t*)d->morph_mem};
+  d->morph_base_p = cv.take<float>(plane);
+  d->morph_base_n = cv.take<float>(plane);
+  d->morph_dp = cv.take<float>(deltas);
+  d->morph_dn = normal_deltas ? cv.take<float>(deltas) : nullptr;
+  d->morph_w = cv.take<float>((size_t)n_targets * 4);
+  d->morph_active = cv.take<uint32_t>(((size_t)n_targets + 1) * 4);
   HK_HIP(hipMemcpy(d->morph_base_p, base_positions, plane, hipMemcpyHostToDevice));
   HK_HIP(hipMemcpy(d->morph_base_n, base_normals, plane, hipMemcpyHostToDevice));
   HK_HIP(hipMemcpy(d->morph_dp, position_deltas, deltas, hipMemcpyHostToDevice));
@@ -641,21 +878,12 @@ int hk_set_mesh_morph_targets(hk_ctx* c, const HkMeshIndex* mesh, uint32_t n_ver
 int hk_skin_mesh(hk_ctx* c, const HkMeshIndex* mesh, const float* joint_matrices, uint32_t n_joints) {
   if (c) c->scene_epoch += 1;   // (scene memory is written: hk_context.hpp, primary-ray pipelining)
   HK_REQUIRE(c && mesh && joint_matrices && n_joints, HK_E_INVALID, "NULL argument or no joints");
-  DeformMesh* d = nullptr;
-  for (DeformMesh* q : c->deform)
-    if (memcmp(&q->mesh, mesh, sizeof(HkMeshIndex)) == 0) d = q;
+  DeformMesh* d = lookup(c, *mesh);
   HK_REQUIRE(d && d->skin_vertices, HK_E_INVALID, "no skin set for this mesh (hk_set_mesh_skin)");
   HK_REQUIRE(d->max_joint < n_joints, HK_E_INVALID, "the skin names joint %u but only %u joint matrices were given", d->max_joint, n_joints);
   int rc;
   if ((rc = begin(c, mesh, &d))) return rc;
-  if (n_joints > d->joint_cap) {
-    if ((rc = sync_all(c))) return rc;
-    if (d->joint_mats) (void)hipFree(d->joint_mats);
-    d->joint_mats = nullptr;
-    d->joint_cap = 0;
-    HK_HIP(hipMalloc((void**)&d->joint_mats, (size_t)n_joints * 64));
-    d->joint_cap = n_joints;
-  }
+  if (n_joints > d->joint_cap && (rc = regrow(c, d->joint_mats, d->joint_cap, n_joints, 64))) return rc;
   uint8_t* st = nullptr;
   int k = 0;
   if ((rc = stage(c, (size_t)n_joints * 64, &st, &k))) return rc;
@@ -668,244 +896,6 @@ int hk_skin_mesh(hk_ctx* c, const HkMeshIndex* mesh, const float* joint_matrices
   });
 }
 
-// Many meshes in one call (hikari_hip.h): what the single calls above do for each item, as five launches over all of them
-// (kernels_deform.hip launch_deform_batch).  Everything the device reads of the call - the item table, the workgroup tables of the
-// three launch shapes, every item's positions / normals / joint matrices / morph weights - travels in ONE pinned staging block.
-// hk_deform_meshes_device is the same batch with `device` set: the items' data stays where the caller has it (validated first: memory the
-// device can read, aligned, strided), only the tables are staged, `producer` (or NULL) is ordered against the context's stream by two
-// events, and flagged items recompute their normals in a sixth launch.
-}  // extern "C"
-namespace {
-int deform_batch(hk_ctx* c, const HkMeshDeformDevice* items, uint32_t n, bool device, hipStream_t producer) {
-  HK_REQUIRE(c->have_meshes && c->have_materials && c->have_instances, HK_E_NOT_READY, "hk_upload_scene must come first");
-  HK_HIP(hipSetDevice(c->device));
-  int rc;
-  if ((rc = finalize_scene(c))) return rc;
-  // ---- the whole batch is validated before anything is enqueued or written
-  c->df_batch += 1;
-  std::vector<DeformMesh*> meshes(n, nullptr);
-  const uint32_t orderings = c->threaded ? 8u : 1u;
-  auto al16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  size_t data_bytes = 0, blocks[4] = {0, 0, 0, 0};  // vertex, triangle, node workgroups; the vertex workgroups of the items that recompute normals
-  uint32_t total_vertices = 0, total_tris = 0;
-  bool grow = false;
-  for (uint32_t i = 0; i < n; ++i) {
-    const HkMeshDeformDevice& it = items[i];
-    HK_REQUIRE(it.kind <= HK_DEFORM_MORPH_SKIN, HK_E_INVALID, "item %u: unknown kind %u", i, it.kind);
-    const bool skins = it.kind == HK_DEFORM_SKIN || it.kind == HK_DEFORM_MORPH_SKIN, morphs = it.kind == HK_DEFORM_MORPH || it.kind == HK_DEFORM_MORPH_SKIN;
-    HK_REQUIRE(it.data && it.count, HK_E_INVALID, "item %u: NULL data or a count of zero", i);
-    HK_REQUIRE(it.kind != HK_DEFORM_SKIN || !it.normals, HK_E_INVALID, "item %u: a skin item takes no normals", i);
-    HK_REQUIRE(it.kind != HK_DEFORM_MORPH || !it.normals, HK_E_INVALID, "item %u: a morph item takes no normals (its data are the weights)", i);
-    HK_REQUIRE(it.kind != HK_DEFORM_MORPH_SKIN || it.normals, HK_E_INVALID, "item %u: a morph + skin item names its weights in `normals`: NULL", i);
-    const bool recompute = (it.flags & HK_DEFORM_RECOMPUTE_NORMALS) != 0;
-    if (device) {
-      HK_REQUIRE(!(it.flags & ~HK_DEFORM_RECOMPUTE_NORMALS), HK_E_INVALID, "item %u: unknown flag bits 0x%x", i, it.flags & ~HK_DEFORM_RECOMPUTE_NORMALS);
-      HK_REQUIRE(!recompute || !morphs, HK_E_INVALID, "item %u: a morph item cannot recompute its normals (HK_DEFORM_RECOMPUTE_NORMALS is for vertex items)", i);
-      HK_REQUIRE(!recompute || it.kind == HK_DEFORM_VERTICES, HK_E_INVALID, "item %u: a skin item cannot recompute its normals (the skin transforms them)", i);
-      HK_REQUIRE(!recompute || !it.normals, HK_E_INVALID, "item %u: normals given together with HK_DEFORM_RECOMPUTE_NORMALS", i);
-      if (skins) {
-        HK_REQUIRE(it.data_stride == 0 || it.data_stride == 64, HK_E_INVALID, "item %u: joint matrices are contiguous (a stride of 0 or 64 bytes, not %u)", i, it.data_stride);
-        HK_REQUIRE(!morphs || it.normals_stride == 0 || it.normals_stride == 4, HK_E_INVALID, "item %u: morph weights are contiguous (a stride of 0 or 4 bytes, not %u)", i,
-                   it.normals_stride);
-      } else if (morphs) {
-        HK_REQUIRE(it.data_stride == 0 || it.data_stride == 4, HK_E_INVALID, "item %u: morph weights are contiguous (a stride of 0 or 4 bytes, not %u)", i, it.data_stride);
-      } else {
-        for (const uint32_t stride : {it.data_stride, it.normals ? it.normals_stride : 0u})
-          HK_REQUIRE(stride == 0 || (stride >= 12 && stride % 4 == 0), HK_E_INVALID, "item %u: a stride of %u bytes (0, or a multiple of 4 from 12 on)", i, stride);
-      }
-    }
-    DeformMesh* d = nullptr;
-    if (skins || morphs) {
-      for (DeformMesh* q : c->deform)
-        if (memcmp(&q->mesh, &it.mesh, sizeof(HkMeshIndex)) == 0) d = q;
-      HK_REQUIRE(!morphs || (d && d->morph_vertices), HK_E_INVALID, "item %u: no morph set for this mesh (hk_set_mesh_morph_targets)", i);
-      HK_REQUIRE(it.kind != HK_DEFORM_MORPH || it.count == d->morph_targets, HK_E_INVALID, "item %u: the morph set has %u targets but %u weights were given", i,
-                 d->morph_targets, it.count);
-      HK_REQUIRE(!skins || (d && d->skin_vertices), HK_E_INVALID, "item %u: no skin set for this mesh (hk_set_mesh_skin)", i);
-      HK_REQUIRE(!(skins && morphs) || d->skin_vertices == d->morph_vertices, HK_E_INVALID, "item %u: the skin has %u vertices, the morph set %u", i, d->skin_vertices,
-                 d->morph_vertices);
-      HK_REQUIRE(!skins || d->max_joint < it.count, HK_E_INVALID, "item %u: the skin names joint %u but only %u joint matrices were given", i, d->max_joint, it.count);
-    }
-    if ((rc = find_mesh(c, &it.mesh, &d)) || (rc = mesh_instances(c, d))) {
-      const std::string why = hk_last_error();
-      set_error("item %u: %s", i, why.c_str());
-      return rc;
-    }
-    HK_REQUIRE(it.kind != HK_DEFORM_VERTICES || (it.count >= d->min_vertices && it.count <= d->max_vertices), HK_E_INVALID,
-               "item %u: the mesh has between %u and %u vertices, not %u", i, d->min_vertices, d->max_vertices, it.count);
-    HK_REQUIRE(d->batch != c->df_batch, HK_E_INVALID, "item %u: the mesh record (%u, %u, %u, %u) is named twice in one batch", i, it.mesh.vertex, it.mesh.primitive,
-               it.mesh.node_offset, it.mesh.node_count);
-    d->batch = c->df_batch;
-    meshes[i] = d;
-    const uint32_t nv = morphs ? d->morph_vertices : skins ? d->skin_vertices : it.count;
-    if (device) {  // (the counts are known to be the mesh's: the extents below are what the kernels will read)
-      if (skins) {
-        if ((rc = check_source(c, i, "joint matrices", it.data, 16, (size_t)it.count * 64))) return rc;
-        if (morphs && (rc = check_source(c, i, "morph weights", it.normals, 4, (size_t)d->morph_targets * 4))) return rc;
-      } else if (morphs) {
-        if ((rc = check_source(c, i, "morph weights", it.data, 4, (size_t)d->morph_targets * 4))) return rc;
-      } else {
-        if ((rc = check_source(c, i, "positions", it.data, 4, (size_t)(nv - 1) * stride_of(it.data_stride) + 12))) return rc;
-        if (it.normals && (rc = check_source(c, i, "normals", it.normals, 4, (size_t)(nv - 1) * stride_of(it.normals_stride) + 12))) return rc;
-      }
-      if (recompute) {
-        blocks[3] += (nv + 255u) / 256u;
-        grow = grow || !d->nrm_mem;
-      }
-    }
-    total_vertices += nv;
-    total_tris += d->n_tris;
-    blocks[0] += (nv + 255u) / 256u;
-    blocks[1] += (d->n_tris + 255u) / 256u;
-    blocks[2] += ((size_t)(2u * d->n_tris - 1u) * orderings + 255u) / 256u;
-    if (morphs && !device) data_bytes += al16((size_t)d->morph_targets * 4);
-    if (skins) {
-      if (!device) data_bytes += (size_t)it.count * 64;
-      grow = grow || it.count > d->joint_cap;
-    } else if (morphs) {
-    } else if (!device) {
-      data_bytes += al16((size_t)it.count * 12) * (it.normals ? 2 : 1);
-    }
-  }
-  // ---- what has to grow (the first skinning of a mesh, a longer palette, a mesh's first recomputed normals): one wait for all of it
-  if (grow) {
-    if ((rc = sync_all(c))) return rc;
-    for (uint32_t i = 0; i < n; ++i) {
-      DeformMesh* d = meshes[i];
-      if (device && (items[i].flags & HK_DEFORM_RECOMPUTE_NORMALS) && !d->nrm_mem && (rc = corner_list(c, d))) return rc;
-      if ((items[i].kind != HK_DEFORM_SKIN && items[i].kind != HK_DEFORM_MORPH_SKIN) || items[i].count <= d->joint_cap) continue;
-      if (d->joint_mats) (void)hipFree(d->joint_mats);
-      d->joint_mats = nullptr;
-      d->joint_cap = 0;
-      HK_HIP(hipMalloc((void**)&d->joint_mats, (size_t)items[i].count * 64));
-      d->joint_cap = items[i].count;
-    }
-  }
-  if (producer)
-    for (hipEvent_t* e : {&c->df_src_ready, &c->df_src_read})
-      if (!*e) HK_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-  // ---- the staging block: item table | vertex, triangle, node and normal workgroups | the items' data (host sources only)
-  const size_t table_bytes = (n * sizeof(DeformItem) + 255) & ~(size_t)255;
-  const size_t block_bytes = ((blocks[0] + blocks[1] + blocks[2] + blocks[3]) * sizeof(SegmentBlock) + 255) & ~(size_t)255;
-  uint8_t* st = nullptr;
-  int k = 0;
-  if ((rc = stage(c, table_bytes + block_bytes + data_bytes, &st, &k))) return rc;
-  DeformItem* table = (DeformItem*)st;
-  SegmentBlock* bl[4] = {(SegmentBlock*)(st + table_bytes), (SegmentBlock*)(st + table_bytes) + blocks[0], (SegmentBlock*)(st + table_bytes) + blocks[0] + blocks[1],
-                         (SegmentBlock*)(st + table_bytes) + blocks[0] + blocks[1] + blocks[2]};
-  uint8_t* data = st + table_bytes + block_bytes;
-  const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
-  uint8_t* sbase = c->scene_mem + slots;
-  size_t at[4] = {0, 0, 0, 0};
-  std::vector<std::pair<uint32_t, uint32_t>> keys(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    const HkMeshDeformDevice& it = items[i];
-    DeformMesh* d = meshes[i];
-    DeformItem t{};
-    t.pos_stride = t.nrm_stride = 3u;
-    t.kind = it.kind;
-    t.n_tris = d->n_tris;
-    const bool skins = it.kind == HK_DEFORM_SKIN || it.kind == HK_DEFORM_MORPH_SKIN, morphs = it.kind == HK_DEFORM_MORPH || it.kind == HK_DEFORM_MORPH_SKIN;
-    if (morphs) {  // (the weights: `data` of a morph item, `normals` of a morph + skin item)
-      const void* weights = skins ? it.normals : it.data;
-      t.n_vertices = d->morph_vertices;
-      t.n_targets = d->morph_targets;
-      if (device) {
-        t.morph_src = (const float*)weights;
-      } else {
-        memcpy(data, weights, (size_t)d->morph_targets * 4);
-        t.morph_src = (const float*)data;
-        data += al16((size_t)d->morph_targets * 4);
-      }
-      t.morph_base_p = d->morph_base_p; t.morph_base_n = d->morph_base_n; t.morph_dp = d->morph_dp; t.morph_dn = d->morph_dn;
-      t.morph_w = d->morph_w; t.morph_active = d->morph_active;
-    }
-    if (skins) {
-      t.n_vertices = d->skin_vertices;
-      t.n_joints = it.count;
-      if (device) {
-        t.palette = (const float4*)it.data;
-      } else {
-        memcpy(data, it.data, (size_t)it.count * 64);
-        t.palette = (const float4*)data;
-        data += (size_t)it.count * 64;
-      }
-      t.joint_mats = d->joint_mats;
-      t.bind_pos = d->bind_pos; t.bind_nrm = d->bind_nrm; t.weights = d->weights; t.joints = d->joints;
-    } else if (morphs) {
-    } else if (device) {
-      t.n_vertices = it.count;
-      t.positions = (const float*)it.data;
-      t.normals = (const float*)it.normals;
-      t.pos_stride = stride_of(it.data_stride) / 4u;
-      t.nrm_stride = stride_of(it.normals_stride) / 4u;
-      if (it.flags & HK_DEFORM_RECOMPUTE_NORMALS) {
-        t.face = d->face;
-        t.corner_off = d->corner_off;
-        t.corner_tri = d->corner_tri;
-        for (uint32_t first = 0; first < t.n_vertices; first += 256) bl[3][at[3]++] = SegmentBlock{i, first};
-      }
-    } else {
-      const size_t plane = (size_t)it.count * 12;
-      t.n_vertices = it.count;
-      memcpy(data, it.data, plane);
-      t.positions = (const float*)data;
-      data += al16(plane);
-      if (it.normals) {
-        memcpy(data, it.normals, plane);
-        t.normals = (const float*)data;
-        data += al16(plane);
-      }
-    }
-    t.pos = d->pos;
-    t.vn = (float4*)(sbase + c->mesh.vn) + d->mesh.vertex;
-    t.box = d->box;
-    t.v0 = (float4*)(sbase + c->mesh.v0) + d->mesh.primitive;
-    t.v1 = (float4*)(sbase + c->mesh.v1) + d->mesh.primitive;
-    t.v2 = (float4*)(sbase + c->mesh.v2) + d->mesh.primitive;
-    t.tree = d->tree;
-    t.nodes = (float4*)(sbase + c->mesh.nodes) + 2 * (size_t)d->mesh.node_offset;
-    table[i] = t;
-    const size_t threads[3] = {t.n_vertices, t.n_tris, (size_t)(2u * t.n_tris - 1u) * orderings};
-    for (int s = 0; s < 3; ++s)
-      for (size_t first = 0; first < threads[s]; first += 256) bl[s][at[s]++] = SegmentBlock{i, (uint32_t)first};
-    keys[i] = std::make_pair(d->mesh.node_offset, d->mesh.node_count);
-  }
-  // ---- enqueue: behind every frame enqueued so far on every stream that reads the scene (stream waits), as a single deformation is
-  if ((rc = join_all(c))) return rc;
-  if (producer) {  // what the producer has enqueued on the sources so far comes first; it may write them again once the vertex launch has read them
-    HK_HIP(hipEventRecord(c->df_src_ready, producer));
-    HK_HIP(hipStreamWaitEvent(c->stream, c->df_src_ready, 0));
-  }
-  c->scene_epoch += n;  // (scene memory is written from here on: hk_context.hpp, primary-ray pipelining - a refusal above leaves it alone)
-  for (uint32_t i = 0; i < n; ++i) {  // (motion vectors: the plane this batch writes - the staged table is the host's until the launch)
-    motion_swap(meshes[i]);
-    table[i].pos = meshes[i]->pos;
-  }
-  launch_deform_batch(c->stream, table, n, bl[0], (uint32_t)blocks[0], bl[1], (uint32_t)blocks[1], bl[2], (uint32_t)blocks[2], 2 * c->mesh.node_cap, orderings,
-                      producer ? c->df_src_read : nullptr, bl[3], (uint32_t)blocks[3]);
-  HK_HIP(hipGetLastError());
-  if (producer) HK_HIP(hipStreamWaitEvent(producer, c->df_src_read, 0));
-  hk_ctx::DeformStage& stg = c->df_stage[(size_t)k];
-  HK_HIP(hipEventRecord(stg.done, c->stream));
-  stg.pending = true;
-  for (uint32_t i = 0; i < n; ++i) {
-    DeformMesh* d = meshes[i];
-    d->n_vertices = table[i].n_vertices;
-    d->deformed = d->pending = d->have_boxes = true;
-  }
-  c->deform_pending = true;
-  std::sort(keys.begin(), keys.end());
-  mark_deformed(c, keys);
-  c->last_deform[0] = n;
-  c->last_deform[1] = total_vertices;
-  c->last_deform[2] = total_tris;
-  c->last_deform[3] = blocks[3] ? 6u : 5u;  // begin, vertices, triangles, (normals,) boxes, emit
-  return HK_OK;
-}
-}  // namespace
-
-extern "C" {
 int hk_deform_meshes(hk_ctx* c, const HkMeshDeform* items, uint32_t n) {
   HK_REQUIRE(c, HK_E_INVALID, "NULL context");
   if (n == 0) return HK_OK;
@@ -1019,14 +1009,7 @@ int hk_rebuild_mesh_tree(hk_ctx* c, const HkMeshIndex* mesh, uint32_t mode) {
   if ((rc = begin(c, mesh, &d))) return rc;
   const uint32_t n = d->n_tris;
   const size_t need = lbvh_scratch_bytes(n);
-  if (need > c->lbvh_scratch_cap) {  // (grows rarely: what is enqueued may still use the old one)
-    if ((rc = sync_all(c))) return rc;
-    if (c->lbvh_scratch) (void)hipFree(c->lbvh_scratch);
-    c->lbvh_scratch = nullptr;
-    c->lbvh_scratch_cap = 0;
-    HK_HIP(hipMalloc(&c->lbvh_scratch, need + need / 4));
-    c->lbvh_scratch_cap = need + need / 4;
-  }
+  if (need > c->lbvh_scratch_cap && (rc = regrow(c, c->lbvh_scratch, c->lbvh_scratch_cap, need + need / 4, 1))) return rc;
   if ((rc = join_all(c))) return rc;  // (the mesh-level region has one copy: behind every frame enqueued so far, as a deformation)
   c->scene_epoch += 1;                // (scene memory is written from here on: hk_context.hpp, primary-ray pipelining)
   const size_t slots = (c->two_slots ? 2 : 1) * c->dyn_capacity;
@@ -1104,9 +1087,7 @@ int hk_debug_read_mesh_geometry(hk_ctx* c, const HkMeshIndex* mesh, float* posit
   HK_HIP(hipSetDevice(c->device));
   int rc;
   if ((rc = finalize_scene(c))) return rc;
-  DeformMesh* d = nullptr;
-  for (DeformMesh* q : c->deform)
-    if (memcmp(&q->mesh, mesh, sizeof(HkMeshIndex)) == 0) d = q;
+  DeformMesh* d = lookup(c, *mesh);
   if (!(d && d->deformed)) {  // never deformed here: what the planes hold for the mesh as the host's mirror describes it
     HK_REQUIRE(mesh->node_count >= 1 && (mesh->node_count + 2) % 3 == 0, HK_E_INVALID, "the mesh record names a tree of %u nodes", mesh->node_count);
     const uint32_t nt = (mesh->node_count + 2) / 3;

@@ -113,6 +113,71 @@ def test_emitter_records_and_light_tree_follow_the_pulsing_sphere():
     assert leaves(la) == leaves(lb)
 
 
+@pytest.mark.parametrize("calls", ["single", "batch"])
+@pytest.mark.parametrize("default_traversal", [False, True], ids=["reference_walk", "product_default"])
+def test_deformations_at_the_edges_of_a_wave_and_a_workgroup(default_traversal, calls):
+    """The vertex counts at which the wave-wide box reduction and the workgroup tables can go wrong (the crowds of test_deform_batch_gpu.py
+    avoid every multiple of 64): 3 (a tree of one leaf), 4 (one inner node), 64 (exactly one wave), 256 (exactly one workgroup), 257 (one
+    vertex into a second workgroup).  Every mesh through hk_update_mesh_vertices with normals, then without, then the skinned ones through
+    hk_skin_mesh - or each round as one hk_deform_meshes batch; after each round the mesh nodes of every ordering and every mesh's geometry
+    equal the uploaded builder mirror's, and so does one frame."""
+    sizes = [1, 2, 62, 254, 255]
+    (scene, sun, meshes), (twin_scene, _, twin_meshes) = S.crowd_scene("small", sizes), S.crowd_scene("small", sizes)
+    assert [len(m["rest"]) for m in meshes.values()] == [3, 4, 64, 256, 257]
+    assert [m["kind"] for m in meshes.values()] == ["skin", "vertices", "skin", "vertices", "skin"]
+    if default_traversal:
+        with product_default_traversal():
+            gpu, twin = hk.HikariPlugin(device=0, flags=0), hk.HikariPlugin(device=0, flags=0)
+    else:
+        gpu, twin = hk.HikariPlugin(device=0, flags=F.CTX_DETERMINISTIC_SCATTER), hk.HikariPlugin(device=0, flags=F.CTX_DETERMINISTIC_SCATTER)
+    gpu.set_scene(scene)
+    twin.set_scene(twin_scene)
+    for m in meshes.values():
+        if m["kind"] == "skin":
+            gpu.engine.set_mesh_skin(m["index"], m["rest"], m["normals"], m["joints"], m["weights"])
+
+    def same_scene(what):
+        a, na, oa = gpu.engine.read_mesh_nodes()
+        b, nb, ob = twin.engine.read_mesh_nodes()
+        assert (na, oa) == (nb, ob) and oa == (8 if default_traversal else 1)
+        assert bytes(a) == bytes(b), f"{what}: mesh-level nodes differ from the uploaded mirror's"
+        for name, m in meshes.items():
+            g, w = gpu.engine.read_mesh_geometry(m["index"]), twin.engine.read_mesh_geometry(twin_meshes[name]["index"])
+            for key in ("positions", "normals", "triangles", "box"):
+                assert g[key].tobytes() == w[key].tobytes(), f"{what}: {key} of mesh {name} ({len(m['rest'])} vertices) differ from the mirror's"
+
+    rounds = (("with normals", 2, lambda q, qn: (q, qn)), ("without normals", 3, lambda q, qn: (q, None)))
+    def deform(items):
+        if calls == "batch":
+            return gpu.engine.deform_meshes(items)
+        for kind, *args in items:
+            (gpu.engine.skin_mesh if kind == "skin" else gpu.engine.update_mesh_vertices)(*args)
+
+    for what, frame, take in rounds:
+        items = []
+        for name, m in meshes.items():
+            data = take(*S.swaying_ribbon(m["rest"], m["normals"], frame, 0.37 * len(m["rest"])))
+            items.append(("vertices", m["index"]) + data)
+            twin_scene.builder.set_mesh_vertices(twin_meshes[name]["id"], *data)
+        deform(items)
+        twin.set_scene(twin_scene.builder.finish())
+        same_scene(f"vertex updates {what}")
+    items = []
+    for name, m in meshes.items():
+        if m["kind"] == "skin":
+            joints = m["pose"](4)[0]
+            items.append(("skin", m["index"], joints))
+            twin_scene.builder.set_mesh_vertices(twin_meshes[name]["id"], *S.skin_reference(m["rest"], m["normals"], m["joints"], m["weights"], joints))
+    deform(items)
+    twin.set_scene(twin_scene.builder.finish())
+    same_scene("skins")
+    cam, lights, s = synthetic_camera(64, 48), hk.lights_uniform(directional=sun), hk.HikariSettings(**SETTINGS)
+    for p in (gpu, twin):
+        p.render(cam, s, lights=lights, frame_number=1)
+    bad = diff_buffers(snapshot(gpu), snapshot(twin))
+    assert bad == {}, bad
+
+
 @pytest.mark.parametrize("deform_first", [True, False])
 def test_instance_motion_and_deformation_compose(deform_first):
     gpu, twin, dev_scene, twin_scene, dev_meshes, twin_meshes, sun = make_pair("yard", F.CTX_DETERMINISTIC_SCATTER)
