@@ -53,6 +53,7 @@ DEBUG_OPT_LOAD_DEVICE_LIMIT = 12
 DEBUG_OPT_KNOWN_RESULTS = 13
 DEBUG_OPT_SPATIAL_KNOWN = 14
 DEBUG_OPT_MOTION_COUNT = 15
+DEBUG_OPT_ADD_SOURCE_TIMES = 16
 TIMING_TRACE_STAGES = 18  # hk_set_timing_mask bit / HkStats slot: every trace launch of the queue-based indirect pass
 TRAVERSAL_WIDE = 0x100
 FRAME_EXTERNAL_GBUFFER, FRAME_ANTIALIAS, FRAME_BALANCE_BANDS, FRAME_GATHER, FRAME_TIME_BAND = 1, 2, 4, 8, 16
@@ -179,6 +180,11 @@ class HkMeshDeformDevice(C.Structure):
                 ("data_stride", u32), ("normals_stride", u32), ("flags", u32), ("_pad", u32)]
 
 
+class HkMeshSource(C.Structure):
+    _fields_ = [("mesh_id", u32), ("flags", u32), ("positions", C.c_void_p), ("normals", C.c_void_p), ("uvs", C.c_void_p), ("indices", C.c_void_p),
+                ("positions_stride", u32), ("normals_stride", u32), ("uvs_stride", u32), ("_pad", u32)]
+
+
 class HkTextureSource(C.Structure):
     _fields_ = [("index", u32), ("format", u32), ("data", C.c_void_p), ("stride_x", u64), ("stride_y", u64), ("stride_c", u64),
                 ("channels", u32), ("x0", u32), ("y0", u32), ("width", u32), ("height", u32), ("flags", u32),
@@ -210,7 +216,7 @@ assert C.sizeof(HkVertex) == 32 and C.sizeof(HkPrimitive) == 48 and C.sizeof(HkN
 assert C.sizeof(HkMaterial) == 80 and C.sizeof(HkEmissive) == 64 and C.sizeof(HkFrame) == 256 and C.sizeof(HkView) == 416
 assert C.sizeof(HkPreviousView) == 128 and C.sizeof(HkAliasEntry) == 8
 assert C.sizeof(HkRay) == 32 and C.sizeof(HkRayHit) == 48 and C.sizeof(HkMeshDeform) == 40 and C.sizeof(HkMeshDeformDevice) == 56
-assert C.sizeof(HkTextureSource) == 80
+assert C.sizeof(HkTextureSource) == 80 and C.sizeof(HkMeshSource) == 56
 
 
 class HikariError(RuntimeError):
@@ -259,6 +265,8 @@ _DEBUG = {
     "debug_last_load": [_vp, P(u32)],
     "debug_last_add": [_vp, P(u32)],
     "debug_last_add_times": [_vp, P(C.c_double)],
+    "debug_last_add_sources": [_vp, P(u32)],
+    "debug_last_add_source_times": [_vp, P(C.c_double)],
     "debug_last_remove": [_vp, P(C.c_uint64)],
     "debug_last_remove_ms": [_vp, P(f32)],
     "debug_last_load_times": [_vp, P(C.c_double)],
@@ -293,6 +301,9 @@ _PRODUCT_ONLY = {
     "scene_builder_add_mesh_deferred": [_vp, P(f32), P(f32), P(f32), u32, P(u32), u32, u32, P(u32)],
     "scene_builder_pending_mesh_trees": [_vp, P(u32)],
     "scene_builder_build_pending_mesh_trees": [_vp],
+    "scene_builder_declare_mesh": [_vp, u32, u32, u32, P(u32)],
+    "scene_builder_resolve_mesh": [_vp, u32, P(f32), P(f32), P(f32), P(u32)],
+    "scene_builder_unresolved_meshes": [_vp, P(u32)],
     "scene_builder_add_material": [_vp, P(HkMaterial), P(u32)],
     "scene_builder_add_instance": [_vp, u32, u32, P(f32), P(u32)],
     "scene_builder_finish": [_vp],
@@ -322,6 +333,7 @@ _PRODUCT_ONLY = {
     "upload_scene_instances": [_vp, _vp],
     "load_scene": [_vp, _vp, u32],
     "add_meshes": [_vp, _vp, u32],
+    "add_meshes_device": [_vp, _vp, P(HkMeshSource), u32, u32, _vp],
     "remove_meshes": [_vp, P(HkMeshExtent), u32],
     "refit_scene_instances": [_vp, _vp, P(u32)],
     "rebuild_scene_trees": [_vp, u32],

@@ -1221,8 +1221,9 @@ void hk_destroy(hk_ctx* c) {
     if (q) (void)hipFree(q);
   c->d_tex_data.release();
   if (c->tx_thresholds) (void)hipFree(c->tx_thresholds);
-  for (hipEvent_t e : {c->tx_src_ready, c->tx_src_read})
+  for (hipEvent_t e : {c->tx_src_ready, c->tx_src_read, c->add_src_ready, c->add_src_read, c->add_ev[0], c->add_ev[1]})
     if (e) (void)hipEventDestroy(e);
+  if (c->add_block) (void)hipFree(c->add_block);
   c->d_noise.release();
   if (c->d_counters) (void)hipFree(c->d_counters);
   if (c->spatial_known) (void)hipFree(c->spatial_known);
@@ -1274,6 +1275,7 @@ int hk_debug_set_option(hk_ctx* c, uint32_t option, int64_t value) {
     case HK_DEBUG_OPT_KNOWN_RESULTS: c->known_results = value != 0; forget_empty_tiles(c); break;
     case HK_DEBUG_OPT_SPATIAL_KNOWN: c->spatial_known_on = value != 0; break;
     case HK_DEBUG_OPT_MOTION_COUNT: c->mv_count = value != 0; break;
+    case HK_DEBUG_OPT_ADD_SOURCE_TIMES: c->time_add_sources = value != 0; break;
     case HK_DEBUG_OPT_MAIN_PRIORITY: c->main_priority = value < 0 ? -1 : (value ? 1 : 0); return pick_main_stream(c, true);
     default: HK_REQUIRE(false, HK_E_INVALID, "unknown option %u", option);
   }

@@ -235,6 +235,15 @@ struct hk_ctx {
   struct Retired { void* p; hipEvent_t done; };
   std::vector<Retired> retired;
   uint32_t last_add[5] = {0, 0, 0, 0, 0};   // hk_debug_last_add
+  // hk_add_meshes_device (scene_append.hip): the device block its launch assembles the sources' records into - kept like the build scratch,
+  // grown behind an event - the producer's stream before that launch and the launch before the producer, and what the last add took
+  void* add_block = nullptr;
+  size_t add_block_cap = 0;
+  hipEvent_t add_src_ready = nullptr, add_src_read = nullptr;
+  hipEvent_t add_ev[2] = {nullptr, nullptr};     // around that launch, made and recorded only while HK_DEBUG_OPT_ADD_SOURCE_TIMES is set (hk_debug_last_add_source_times)
+  bool time_add_sources = false;
+  uint32_t last_add_sources[4] = {0, 0, 0, 0};   // hk_debug_last_add_sources
+  double last_add_source_ms[3] = {0, 0, 0};      // hk_debug_last_add_source_times
   double last_add_ms[4] = {0, 0, 0, 0};     // hk_debug_last_add_times
   uint64_t last_remove[6] = {0, 0, 0, 0, 0, 0};   // hk_debug_last_remove (scene_remove.hip)
   hipEvent_t rm_ev[2] = {nullptr, nullptr};       // around the compaction launch of the last hk_remove_meshes (hk_debug_last_remove_ms)

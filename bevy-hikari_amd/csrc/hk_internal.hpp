@@ -52,6 +52,28 @@ int builder_complete_mesh_on_host(hk_scene_builder* b, uint32_t mesh_id);  // ..
              "the builder holds %u deferred meshes whose trees are stand-ins (hk_scene_builder_add_mesh_deferred): build them with " \
              "hk_scene_builder_build_pending_mesh_trees, or use hk_load_scene, which builds them on the device",                     \
              ::hk::builder_pending_mesh_count(b))
+// meshes declared by their counts (hk_scene_builder_declare_mesh) whose arrays have not arrived: zeros of the final sizes.  Nothing may
+// upload, build or instance such a mesh; hk_add_meshes_device and hk_scene_builder_resolve_mesh fill it, both through
+// builder_store_mesh_geometry (reference records as add_mesh makes them; `standin`: the stand-in tree over the real boxes as well)
+struct DeclaredMesh {
+  uint32_t n_vertices, n_triangles, n_indices, topology;  // n_indices 0: the identity list over the vertices
+};
+uint32_t builder_unresolved_mesh_count(const hk_scene_builder* b, uint32_t* first = nullptr);  // first: the lowest such id
+bool builder_unresolved_mesh(const hk_scene_builder* b, uint32_t mesh_id, DeclaredMesh* out);
+int builder_store_mesh_geometry(hk_scene_builder* b, uint32_t mesh_id, const HkVertex* vertices, uint32_t n_vertices, const HkPrimitive* primitives, uint32_t n_primitives,
+                                bool standin);
+#define HK_NO_UNRESOLVED_MESHES(b)                                                                                                                \
+  do {                                                                                                                                            \
+    uint32_t first_unresolved_ = 0;                                                                                                               \
+    const uint32_t n_unresolved_ = ::hk::builder_unresolved_mesh_count(b, &first_unresolved_);                                                     \
+    HK_REQUIRE(n_unresolved_ == 0u, HK_E_NOT_READY,                                                                                               \
+               "mesh %u (and %u more) is declared and not filled yet (hk_scene_builder_declare_mesh): hk_add_meshes_device or "                   \
+               "hk_scene_builder_resolve_mesh comes first",                                                                                       \
+               first_unresolved_, n_unresolved_ - 1u);                                                                                            \
+  } while (0)
+#define HK_NO_UNRESOLVED_MESH(b, id)                                                                                                              \
+  HK_REQUIRE(!::hk::builder_unresolved_mesh(b, id, nullptr), HK_E_NOT_READY,                                                                     \
+             "mesh %u is declared and not filled yet (hk_scene_builder_declare_mesh): hk_add_meshes_device or hk_scene_builder_resolve_mesh comes first", id)
 int upload_scene_unchecked(hk_ctx* c, const hk_scene_builder* b);            // hk_upload_scene without the checks of the builder's trees (scene_layout.hip)
 int upload_scene_instances_unchecked(hk_ctx* c, const hk_scene_builder* b);  // hk_upload_scene_instances without that check (context.hip)
 bool builder_instance_decl(const hk_scene_builder* b, uint32_t i, InstanceDecl* out);

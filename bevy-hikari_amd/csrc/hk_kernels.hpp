@@ -219,6 +219,21 @@ struct TextureItem {
 };
 constexpr uint32_t HK_TEXTURE_ITEM_ENCODE = 1u;   // rgb are linear light of an sRGB texture: encoded through the thresholds
 constexpr uint32_t HK_TEXTURE_ITEM_PACKED = 2u;   // four channels side by side, every element aligned to all four: one 4 / 8 / 16 B load
+// One source of hk_add_meshes_device (kernels_scene.hip k_assemble_meshes): a declared mesh's arrays in the caller's DEVICE memory and where
+// its reference records go in the call's device block.  The table lies in the pinned staging block of the call; a workgroup
+// (SegmentBlock: segment = source, first = a triangle, or a vertex for the workgroups behind the triangles') takes 256 of them.
+struct MeshSourceItem {
+  const uint8_t *positions, *normals;  // 3 floats per vertex at + v * stride
+  const uint8_t* uvs;                  // 2 floats per vertex, or NULL: (0, 0)
+  const uint32_t* indices;             // or NULL: the identity list
+  uint4* prims;                        // HkPrimitive records: 3 x 16 B per triangle {position, index}
+  uint4* verts;                        // HkVertex records: 2 x 16 B per vertex {position, u} {normal, v}
+  uint32_t n_vertices, n_tris;
+  uint32_t stride_p, stride_n, stride_uv;
+  uint32_t strip;                      // 1: triangle t names (t, t + 1, t + 2) of the list, the first two swapped for odd t
+  uint32_t pad[2];
+};
+static_assert(sizeof(MeshSourceItem) == 80, "the item table is laid out by the host");
 // One instance of a deformed mesh (kernels_scene.hip k_mesh_instances): the mesh's box words, and the emitter record to write if it emits
 struct MeshInstanceEntry {
   uint32_t instance;
@@ -533,10 +548,16 @@ void launch_compact_planes(hipStream_t st, const CompactArgs& a, int compute_uni
 // ... and beside it: the instance-level slot `src` (n16 pieces of 16 B) copied to both slots of the new allocation, the vertex, primitive
 // and node_offset words of the n_instances DInstance records that begin at piece `first16` rebased by the same runs
 void launch_compact_instances(hipStream_t st, uint4* dst0, uint4* dst1, const uint4* src, size_t n16, size_t first16, uint32_t n_instances, const CompactArgs& a);
-// hk_add_meshes: n_prims HkPrimitive (48 B) and n_verts HkVertex (32 B) records in pinned memory into the triangle planes and the vertex
-// planes, from element 0 of the plane pointers given
+// hk_add_meshes: n_prims HkPrimitive (48 B) and n_verts HkVertex (32 B) records - in pinned memory, or in the device block
+// hk_add_meshes_device assembled them into - into the triangle planes and the vertex planes, from element 0 of the plane pointers given
 void launch_append_geometry(hipStream_t st, const uint4* prims, uint32_t n_prims, const uint4* verts, uint32_t n_verts, float4* v0, float4* v1, float4* v2, float4* vn,
                             float2* vuv);
+// hk_add_meshes_device: the HkPrimitive / HkVertex records of every source assembled from the caller's device memory in ONE launch of
+// n_blocks workgroups whatever the number of sources (`items`, `blocks`: pinned; the first n_tri_blocks workgroups take triangles, the
+// others vertices).  Values move as bits.  An index >= n_vertices reads vertex 0 instead and atomicMin-s the source's number into *status
+// (device memory, HK_U32_MAX beforehand).  `sources_read` (or NULL) is recorded behind it.  Returns the kernels it launched.
+uint32_t launch_assemble_meshes(hipStream_t st, const hkd::MeshSourceItem* items, const hkd::SegmentBlock* blocks, uint32_t n_tri_blocks, uint32_t n_blocks, uint32_t* status,
+                                hipEvent_t sources_read);
 void launch_gather_instance_boxes(hipStream_t st, const hkd::RefitScene& s, const float4* tlas, uint32_t tlas_count);
 // the first n_emitter_updates records are the moved emitters (the largest of their meshes has emitter_triangles triangles)
 void launch_refit(hipStream_t st, const hkd::RefitScene& s, const hkd::RefitUpdate* updates, uint32_t n_updates, uint32_t n_emitter_updates, uint32_t emitter_triangles,

@@ -677,6 +677,53 @@ __global__ __launch_bounds__(256) void k_update_textures(uint32_t* __restrict__ 
   }
 }
 
+// hk_add_meshes_device: the reference records (hikari_hip.h HkPrimitive, HkVertex) of many meshes from the caller's arrays.  One workgroup
+// per 256 consecutive triangles - the first n_tri_blocks workgroups - or 256 consecutive vertices of ONE source (hk_kernels.hpp
+// MeshSourceItem, SegmentBlock), so kind, topology and strides are uniform per workgroup.  Per triangle: 12 B of indices (consecutive
+// lanes read consecutive words of a list; a strip's lanes overlap), three 12-B position gathers wherever the indices point, three 16-B
+// stores to consecutive 48-B records; per vertex 32 B read at the caller's strides and two 16-B stores.  Pure moves: words, no float
+// arithmetic.  An index the mesh does not have is never followed: vertex 0 is read instead and the source is flagged.
+__global__ __launch_bounds__(256) void k_assemble_meshes(const MeshSourceItem* __restrict__ items, const SegmentBlock* __restrict__ blocks, uint32_t n_tri_blocks,
+                                                         uint32_t* __restrict__ status) {
+  const SegmentBlock bl = blocks[blockIdx.x];
+  const MeshSourceItem& it = items[bl.segment];  // (uniform: read field by field, nothing of it lives in private memory)
+  const uint32_t e = bl.first + threadIdx.x;
+  if (blockIdx.x < n_tri_blocks) {
+    if (e >= it.n_tris) return;
+    size_t a = 3u * (size_t)e, b = a + 1u, c = a + 2u;
+    if (it.strip) {
+      a = (size_t)e + (e & 1u);
+      b = (size_t)e + 1u - (e & 1u);
+      c = (size_t)e + 2u;
+    }
+    uint32_t id[3] = {(uint32_t)a, (uint32_t)b, (uint32_t)c};
+    if (it.indices) {
+      id[0] = it.indices[a];
+      id[1] = it.indices[b];
+      id[2] = it.indices[c];
+    }
+    if (id[0] >= it.n_vertices || id[1] >= it.n_vertices || id[2] >= it.n_vertices) atomicMin(status, bl.segment);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const uint32_t v = id[k] < it.n_vertices ? id[k] : 0u;
+      const uint32_t* p = (const uint32_t*)(it.positions + (size_t)v * it.stride_p);
+      it.prims[3u * (size_t)e + k] = make_uint4(p[0], p[1], p[2], id[k]);
+    }
+    return;
+  }
+  if (e >= it.n_vertices) return;
+  const uint32_t* p = (const uint32_t*)(it.positions + (size_t)e * it.stride_p);
+  const uint32_t* n = (const uint32_t*)(it.normals + (size_t)e * it.stride_n);
+  uint32_t u = 0u, v = 0u;  // (+0.0f)
+  if (it.uvs) {
+    const uint32_t* t = (const uint32_t*)(it.uvs + (size_t)e * it.stride_uv);
+    u = t[0];
+    v = t[1];
+  }
+  it.verts[2u * (size_t)e] = make_uint4(p[0], p[1], p[2], u);
+  it.verts[2u * (size_t)e + 1u] = make_uint4(n[0], n[1], n[2], v);
+}
+
 }  // namespace hkd
 
 namespace hk {
@@ -738,6 +785,13 @@ void launch_append_geometry(hipStream_t st, const uint4* prims, uint32_t n_prims
   const uint32_t n = std::max(n_prims, n_verts);
   if (!n) return;
   hipLaunchKernelGGL(k_append_geometry, dim3(std::min((n + 255u) / 256u, 4096u)), dim3(256), 0, st, prims, n_prims, verts, n_verts, v0, v1, v2, vn, vuv);
+}
+uint32_t launch_assemble_meshes(hipStream_t st, const MeshSourceItem* items, const SegmentBlock* blocks, uint32_t n_tri_blocks, uint32_t n_blocks, uint32_t* status,
+                                hipEvent_t sources_read) {
+  if (!n_blocks) return 0u;
+  hipLaunchKernelGGL(k_assemble_meshes, dim3(n_blocks), dim3(256), 0, st, items, blocks, n_tri_blocks, status);
+  if (sources_read) (void)hipEventRecord(sources_read, st);
+  return 1u;
 }
 void launch_gather_instance_boxes(hipStream_t st, const RefitScene& s, const float4* tlas, uint32_t tlas_count) {
   if (!tlas_count) return;

@@ -249,6 +249,10 @@ struct BuilderMesh {
   std::vector<HkNode> nodes;
   float aabb_center[3], aabb_half[3];
   bool pending = false;  // added by hk_scene_builder_add_mesh_deferred: `nodes` is a valid stand-in of the final size until the tree is built
+  // declared by hk_scene_builder_declare_mesh and not filled yet: vertices and primitives are zeros of the final counts (and `pending` is set);
+  // the declaration's index count (0: the identity list) and topology, which whoever fills the mesh assembles by
+  bool unresolved = false;
+  uint32_t decl_indices = 0, decl_topology = 0;
 };
 struct BuilderInstance {
   uint32_t mesh, material;
@@ -519,6 +523,99 @@ int hk_scene_builder_pending_mesh_trees(const hk_scene_builder* b, uint32_t* cou
   return HK_OK;
 }
 
+
+// A mesh known by its counts alone (hikari_hip.h): zeros of the final sizes and the deferred mesh's stand-in, so that every offset and
+// HkMeshIndex record is final at the next finish; hk_add_meshes_device or hk_scene_builder_resolve_mesh fills it.
+static uint32_t declared_triangles(uint32_t n_vertices, uint32_t n_indices, uint32_t topology) {
+  const uint32_t n = n_indices ? n_indices : n_vertices;  // mod.rs:408-411
+  if (topology == HK_TOPOLOGY_TRIANGLE_LIST) return n / 3u;
+  return n >= 3u ? n - 2u : 0u;
+}
+// build_flat_placeholder over n shapes that are all the point 0, emitted directly: the halved index list in the flatten_custom layout
+// (every box is the zero box then, so no tree is kept and no union is formed - a declaration costs its node array alone)
+static uint32_t emit_zero_standin(uint32_t begin, uint32_t end, std::vector<HkNode>& out, uint32_t next_free) {
+  HkNode n{};
+  if (end - begin == 1u) {  // pack_node(Box::empty(), leaf)
+    const float inf = std::numeric_limits<float>::infinity();
+    for (int k = 0; k < 3; ++k) { n.min[k] = inf; n.max[k] = -inf; }
+    n.entry_index = begin | HK_BVH_LEAF_FLAG;
+    n.exit_index = next_free + 1u;
+    out.push_back(n);
+    return next_free + 1u;
+  }
+  const uint32_t mid = begin + (end - begin) / 2u;
+  const uint32_t halves[3] = {begin, mid, end};
+  for (int h = 0; h < 2; ++h) {  // create_flat_branch: the navigator, then the subtree it skips
+    const uint32_t at = next_free;
+    out.push_back(n);
+    next_free = emit_zero_standin(halves[h], halves[h + 1], out, at + 1u);
+    out[at].entry_index = at + 1u;
+    out[at].exit_index = next_free;
+  }
+  return next_free;
+}
+int hk_scene_builder_declare_mesh(hk_scene_builder* b, uint32_t n_vertices, uint32_t n_indices, uint32_t topology, uint32_t* mesh_id) {
+  HK_REQUIRE(b, HK_E_INVALID, "builder is NULL");
+  HK_REQUIRE(n_vertices > 0, HK_E_INVALID, "mesh needs position, normal and uv attributes");
+  HK_REQUIRE(topology == HK_TOPOLOGY_TRIANGLE_LIST || topology == HK_TOPOLOGY_TRIANGLE_STRIP, HK_E_UNSUPPORTED, "incompatible primitive topology");
+  HK_REQUIRE(topology != HK_TOPOLOGY_TRIANGLE_LIST || (n_indices ? n_indices : n_vertices) % 3u == 0u, HK_E_UNSUPPORTED,
+             "incompatible primitive topology (index count not a multiple of 3)");
+  const uint32_t n_tris = declared_triangles(n_vertices, n_indices, topology);
+  HK_REQUIRE(n_tris > 0, HK_E_INVALID, "mesh has no primitive");
+  BuilderMesh mesh;
+  mesh.vertices.assign(n_vertices, HkVertex{});
+  mesh.primitives.assign(n_tris, HkPrimitive{});
+  mesh.nodes.reserve(3 * (size_t)n_tris);
+  emit_zero_standin(0u, n_tris, mesh.nodes, 0u);
+  for (int k = 0; k < 3; ++k) mesh.aabb_center[k] = mesh.aabb_half[k] = 0.0f;
+  mesh.pending = true;
+  mesh.unresolved = true;
+  mesh.decl_indices = n_indices;
+  mesh.decl_topology = topology;
+  b->meshes.push_back(std::move(mesh));
+  b->meshes_dirty = true;
+  b->finished = false;
+  if (mesh_id) *mesh_id = (uint32_t)b->meshes.size() - 1;
+  return HK_OK;
+}
+int hk_scene_builder_resolve_mesh(hk_scene_builder* b, uint32_t mesh_id, const float* positions, const float* normals, const float* uvs, const uint32_t* indices) {
+  HK_REQUIRE(b && positions && normals, HK_E_INVALID, "NULL argument");
+  HK_REQUIRE(mesh_id < b->meshes.size() && b->meshes[mesh_id].unresolved, HK_E_INVALID, "mesh %u is not a declared mesh that waits for its arrays", mesh_id);
+  const BuilderMesh& m = b->meshes[mesh_id];
+  HK_REQUIRE((indices != nullptr) == (m.decl_indices != 0u), HK_E_INVALID, "mesh %u was declared with %u indices: the index array must be %s", mesh_id, m.decl_indices,
+             m.decl_indices ? "given" : "NULL");
+  const uint32_t nv = (uint32_t)m.vertices.size(), nt = (uint32_t)m.primitives.size(), ni = m.decl_indices ? m.decl_indices : nv;
+  for (uint32_t i = 0; indices && i < ni; ++i) HK_REQUIRE(indices[i] < nv, HK_E_INVALID, "vertex index out of range");
+  std::vector<HkVertex> vertices(nv);
+  for (uint32_t i = 0; i < nv; ++i) {
+    HkVertex& v = vertices[i];
+    for (int k = 0; k < 3; ++k) {
+      v.position[k] = positions[3 * (size_t)i + k];
+      v.normal[k] = normals[3 * (size_t)i + k];
+    }
+    v.u = uvs ? uvs[2 * (size_t)i] : 0.0f;
+    v.v = uvs ? uvs[2 * (size_t)i + 1] : 0.0f;
+  }
+  std::vector<HkPrimitive> primitives(nt);
+  const bool strip = m.decl_topology == HK_TOPOLOGY_TRIANGLE_STRIP;
+  for (uint32_t t = 0; t < nt; ++t) {  // mod.rs:414-449: a strip's odd triangles flip winding
+    const size_t at = strip ? t : 3 * (size_t)t;
+    size_t id[3] = {at, at + 1, at + 2};
+    if (strip && (t & 1u)) std::swap(id[0], id[1]);
+    for (int k = 0; k < 3; ++k) {
+      const uint32_t i = indices ? indices[id[k]] : (uint32_t)id[k];
+      memcpy(primitives[t].vertices[k].position, vertices[i].position, 12);
+      primitives[t].vertices[k].index = i;
+    }
+  }
+  return builder_store_mesh_geometry(b, mesh_id, vertices.data(), nv, primitives.data(), nt, true);
+}
+int hk_scene_builder_unresolved_meshes(const hk_scene_builder* b, uint32_t* count) {
+  HK_REQUIRE(b && count, HK_E_INVALID, "NULL argument");
+  *count = builder_unresolved_mesh_count(b);
+  return HK_OK;
+}
+
 int hk_scene_builder_add_material(hk_scene_builder* b, const HkMaterial* material, uint32_t* material_id) {
   HK_REQUIRE(b && material, HK_E_INVALID, "bad argument");
   b->materials.push_back(*material);
@@ -530,6 +627,8 @@ int hk_scene_builder_add_material(hk_scene_builder* b, const HkMaterial* materia
 int hk_scene_builder_add_instance(hk_scene_builder* b, uint32_t mesh_id, uint32_t material_id, const float transform[16], uint32_t* instance_id) {
   HK_REQUIRE(b && transform, HK_E_INVALID, "bad argument");
   HK_REQUIRE(mesh_id < b->meshes.size() && material_id < b->materials.size(), HK_E_INVALID, "unknown mesh or material id");
+  HK_REQUIRE(!b->meshes[mesh_id].unresolved, HK_E_NOT_READY,
+             "mesh %u is declared and not filled yet (hk_scene_builder_declare_mesh): its box is unknown, its instances follow hk_add_meshes_device or hk_scene_builder_resolve_mesh", mesh_id);
   BuilderInstance inst;
   inst.mesh = mesh_id;
   inst.material = material_id;
@@ -607,6 +706,7 @@ bool refit_nodes(std::vector<HkNode>& nodes, const std::vector<HkPrimitive>& pri
 int hk_scene_builder_set_mesh_vertices(hk_scene_builder* b, uint32_t mesh_id, const float* positions, const float* normals) {
   HK_REQUIRE(b && positions, HK_E_INVALID, "NULL argument");
   HK_REQUIRE(mesh_id < b->meshes.size(), HK_E_INVALID, "unknown mesh id");
+  HK_NO_UNRESOLVED_MESH(b, mesh_id);
   BuilderMesh mesh = b->meshes[mesh_id];  // (a copy: an error leaves the builder as it was)
   for (size_t i = 0; i < mesh.vertices.size(); ++i)
     for (int k = 0; k < 3; ++k) {
@@ -640,6 +740,7 @@ int hk_scene_builder_set_mesh_vertices(hk_scene_builder* b, uint32_t mesh_id, co
 int hk_scene_builder_recompute_mesh_normals(hk_scene_builder* b, uint32_t mesh_id) {
   HK_REQUIRE(b, HK_E_INVALID, "builder is NULL");
   HK_REQUIRE(mesh_id < b->meshes.size(), HK_E_INVALID, "unknown mesh id");
+  HK_NO_UNRESOLVED_MESH(b, mesh_id);
   BuilderMesh& mesh = b->meshes[mesh_id];
   const size_t nv = mesh.vertices.size();
   for (const HkPrimitive& p : mesh.primitives)
@@ -686,6 +787,7 @@ static int canonical_mesh_tree(const BuilderMesh& mesh, std::vector<HkNode>& nod
 int hk_scene_builder_rebuild_mesh_tree(hk_scene_builder* b, uint32_t mesh_id) {
   HK_REQUIRE(b, HK_E_INVALID, "builder is NULL");
   HK_REQUIRE(mesh_id < b->meshes.size(), HK_E_INVALID, "unknown mesh id");
+  HK_NO_UNRESOLVED_MESH(b, mesh_id);
   std::vector<HkNode> nodes;  // (a copy: an error leaves the builder as it was)
   const int rc = canonical_mesh_tree(b->meshes[mesh_id], nodes);
   if (rc) return rc;
@@ -702,6 +804,7 @@ int hk_scene_builder_rebuild_mesh_tree(hk_scene_builder* b, uint32_t mesh_id) {
 // the concatenated array; the node count does not depend on the tree, so no offset moves and a finished builder stays finished.
 int hk_scene_builder_build_pending_mesh_trees(hk_scene_builder* b) {
   HK_REQUIRE(b, HK_E_INVALID, "builder is NULL");
+  HK_NO_UNRESOLVED_MESHES(b);  // (before the first tree: a refusal writes nothing)
   for (uint32_t id = 0; id < b->meshes.size(); ++id) {
     if (!b->meshes[id].pending) continue;
     const int rc = builder_complete_mesh_on_host(b, id);
@@ -929,6 +1032,79 @@ bool builder_pending_mesh(const hk_scene_builder* b, uint32_t mesh_id, HkMeshInd
   return true;
 }
 uint32_t builder_mesh_count(const hk_scene_builder* b) { return b ? (uint32_t)b->meshes.size() : 0u; }
+uint32_t builder_unresolved_mesh_count(const hk_scene_builder* b, uint32_t* first) {
+  uint32_t n = 0;
+  if (b)
+    for (size_t id = b->meshes.size(); id-- > 0;)
+      if (b->meshes[id].unresolved) {
+        n += 1u;
+        if (first) *first = (uint32_t)id;
+      }
+  return n;
+}
+bool builder_unresolved_mesh(const hk_scene_builder* b, uint32_t mesh_id, DeclaredMesh* out) {
+  if (!b || mesh_id >= b->meshes.size() || !b->meshes[mesh_id].unresolved) return false;
+  const BuilderMesh& m = b->meshes[mesh_id];
+  if (out) *out = DeclaredMesh{(uint32_t)m.vertices.size(), (uint32_t)m.primitives.size(), m.decl_indices, m.decl_topology};
+  return true;
+}
+// what fills a declared mesh, whoever assembled the records (hk_scene_builder_resolve_mesh on the host, hk_add_meshes_device's kernel): the
+// mesh's own arrays and, in a finished builder, its ranges of the concatenated ones in place - the counts are the declaration's, so no
+// offset moves and a finished builder stays finished; the mesh box with add_mesh's arithmetic over ALL vertices; `standin`: the deferred
+// mesh's stand-in over the real triangle boxes (a caller that builds the tree at once leaves the declaration's).  Clears `unresolved`.
+int builder_store_mesh_geometry(hk_scene_builder* b, uint32_t mesh_id, const HkVertex* vertices, uint32_t n_vertices, const HkPrimitive* primitives, uint32_t n_primitives,
+                                bool standin) {
+  HK_REQUIRE(b && vertices && primitives && mesh_id < b->meshes.size() && b->meshes[mesh_id].unresolved, HK_E_INVALID, "mesh %u is not a declared mesh that waits for its arrays",
+             mesh_id);
+  BuilderMesh& m = b->meshes[mesh_id];
+  HK_REQUIRE(n_vertices == m.vertices.size() && n_primitives == m.primitives.size(), HK_E_INVALID, "%u vertices and %u triangles for a mesh declared with %zu and %zu", n_vertices,
+             n_primitives, m.vertices.size(), m.primitives.size());
+  std::vector<HkNode> standin_nodes;  // (before anything is written: a refusal leaves the mesh as it was)
+  if (standin) {
+    std::vector<float> boxes;
+    boxes.reserve((size_t)n_primitives * 6);
+    for (uint32_t t = 0; t < n_primitives; ++t) {
+      Box bx = Box::empty();
+      for (int k = 0; k < 3; ++k) bx.grow(primitives[t].vertices[k].position);
+      boxes.insert(boxes.end(), bx.mn, bx.mn + 3);
+      boxes.insert(boxes.end(), bx.mx, bx.mx + 3);
+    }
+    standin_nodes = build_flat_placeholder(boxes);
+    HK_REQUIRE(standin_nodes.size() == m.nodes.size(), HK_E_INVALID, "a stand-in of %zu nodes for a mesh of %zu", standin_nodes.size(), m.nodes.size());
+  }
+  std::copy(vertices, vertices + n_vertices, m.vertices.begin());
+  std::copy(primitives, primitives + n_primitives, m.primitives.begin());
+  float mn[3], mx[3];
+  for (int k = 0; k < 3; ++k) mn[k] = mx[k] = vertices[0].position[k];
+  for (uint32_t i = 0; i < n_vertices; ++i)
+    for (int k = 0; k < 3; ++k) {
+      mn[k] = std::min(mn[k], vertices[i].position[k]);
+      mx[k] = std::max(mx[k], vertices[i].position[k]);
+    }
+  for (int k = 0; k < 3; ++k) {  // bevy Aabb::from_min_max
+    m.aabb_center[k] = 0.5f * (mx[k] + mn[k]);
+    m.aabb_half[k] = 0.5f * (mx[k] - mn[k]);
+  }
+  if (standin) m.nodes.swap(standin_nodes);
+  m.unresolved = false;
+  const bool in_place = mesh_id < b->concat_meshes && mesh_id < b->mesh_index.size();
+  if (in_place) {
+    const HkMeshIndex& mi = b->mesh_index[mesh_id];
+    if (mi.node_count == m.nodes.size() && (size_t)mi.node_offset + mi.node_count <= b->asset_nodes.size() && (size_t)mi.vertex + n_vertices <= b->vertices.size() &&
+        (size_t)mi.primitive + n_primitives <= b->primitives.size()) {
+      std::copy(vertices, vertices + n_vertices, b->vertices.begin() + mi.vertex);
+      std::copy(primitives, primitives + n_primitives, b->primitives.begin() + mi.primitive);
+      if (standin) std::copy(m.nodes.begin(), m.nodes.end(), b->asset_nodes.begin() + mi.node_offset);
+      return HK_OK;
+    }
+  }
+  b->concat_meshes = std::min<size_t>(b->concat_meshes, mesh_id);  // (the next finish concatenates again from this mesh on)
+  if (!b->meshes_dirty) {
+    b->meshes_dirty = true;
+    b->finished = false;
+  }
+  return HK_OK;
+}
 int builder_store_mesh_nodes(hk_scene_builder* b, uint32_t mesh_id, const HkNode* nodes, uint32_t count) {
   HK_REQUIRE(b && nodes && mesh_id < b->meshes.size(), HK_E_INVALID, "unknown mesh id");
   BuilderMesh& m = b->meshes[mesh_id];
@@ -946,6 +1122,7 @@ int builder_store_mesh_nodes(hk_scene_builder* b, uint32_t mesh_id, const HkNode
 }
 int builder_complete_mesh_on_host(hk_scene_builder* b, uint32_t mesh_id) {
   HK_REQUIRE(b && mesh_id < b->meshes.size(), HK_E_INVALID, "unknown mesh id");
+  HK_NO_UNRESOLVED_MESH(b, mesh_id);
   std::vector<HkNode> nodes;
   const int rc = canonical_mesh_tree(b->meshes[mesh_id], nodes);
   if (rc) return rc;

@@ -724,6 +724,7 @@ int hk_upload_scene(hk_ctx* c, const hk_scene_builder* b) {
   if (c) c->scene_epoch += 1;   // (scene memory is written: hk_context.hpp, primary-ray pipelining)
   HK_REQUIRE(c && b, HK_E_INVALID, "NULL argument");
   HK_NO_STANDINS(b);  // (frames from stand-in trees would differ silently in tie-breaks and visit order)
+  HK_NO_UNRESOLVED_MESHES(b);
   HK_NO_PENDING_MESHES(b);
   return hk::upload_scene_unchecked(c, b);
 }

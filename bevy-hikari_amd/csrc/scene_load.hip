@@ -169,6 +169,7 @@ int hk_load_scene(hk_ctx* c, hk_scene_builder* b, uint32_t tree_mode) {
   HK_REQUIRE(tree_mode == HK_TREE_SAH || tree_mode == HK_TREE_LBVH, HK_E_INVALID, "unknown tree build mode %u", tree_mode);
   HK_REQUIRE(!builder_has_standin_trees(b), HK_E_NOT_READY,
              "the builder holds stand-in instance trees (hk_scene_builder_finish_instances): finish it with hk_scene_builder_finish before hk_load_scene");
+  HK_NO_UNRESOLVED_MESHES(b);  // (declared meshes hold zeros: hk_add_meshes_device or hk_scene_builder_resolve_mesh fills them)
   const HkNode* an = nullptr;
   uint32_t nan_ = 0;
   int rc;

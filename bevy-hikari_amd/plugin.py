@@ -398,6 +398,34 @@ class SceneBuilder:
         finished - scene() returns the final arrays."""
         self.api.call("scene_builder_build_pending_mesh_trees", self.h)
 
+    def declare_mesh(self, n_vertices, n_indices=0, topology=F.TOPOLOGY_TRIANGLE_LIST):
+        """hk_scene_builder_declare_mesh: a mesh known by its counts, whose arrays are still to come - from device memory
+        (Engine.add_meshes(builder, sources=...)) or from the host (resolve_mesh).  n_indices == 0: the identity list over the vertices.
+        Until then nothing uploads the builder and no instance may name the mesh."""
+        out = F.u32()
+        self.api.call("scene_builder_declare_mesh", self.h, int(n_vertices), int(n_indices), topology, C.byref(out))
+        self.mesh_vertices.append(int(n_vertices))
+        return out.value
+
+    def resolve_mesh(self, mesh_id, positions, normals, uvs=None, indices=None):
+        """hk_scene_builder_resolve_mesh: a declared mesh filled from host arrays with add_mesh's arithmetic (uvs None: (0, 0); indices None
+        iff it was declared without).  A finished builder stays finished; the mesh then is an ordinary deferred mesh."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        uv = None if uvs is None else np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1, 2)
+        idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        want = self.mesh_vertices[mesh_id] if mesh_id < len(self.mesh_vertices) else None
+        if want is not None and (len(pos) != want or len(nrm) != want or (uv is not None and len(uv) != want)):
+            raise ValueError(f"mesh {mesh_id} was declared with {want} vertices")
+        fp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(F.f32))
+        self.api.call("scene_builder_resolve_mesh", self.h, mesh_id, fp(pos), fp(nrm), fp(uv), None if idx is None else idx.ctypes.data_as(C.POINTER(F.u32)))
+
+    def unresolved_meshes(self):
+        """How many declared meshes still wait for their arrays (hk_scene_builder_unresolved_meshes)."""
+        n = F.u32()
+        self.api.call("scene_builder_unresolved_meshes", self.h, C.byref(n))
+        return n.value
+
     def add_material(self, material):
         out = F.u32()
         self.api.call("scene_builder_add_material", self.h, C.byref(material), C.byref(out))
@@ -753,6 +781,46 @@ def deform_items_device(items, device):
     return table, keep
 
 
+def mesh_sources_device(sources, device):
+    """The HkMeshSource table of Engine.add_meshes' `sources` - {mesh_id: dict(positions=, normals=, uvs=None, indices=None)} of torch
+    tensors on cuda:`device` - and the tensors it points into.  float32 tensors whose rows are contiguous are named where they lie, pointer
+    and row stride from the tensor (a column slice state[:, 0:3] costs no copy, as in deform_items_device); indices are a contiguous int32 /
+    uint32 tensor (another integer type is refused); any other float layout is converted on the device first - on torch's CURRENT stream,
+    so Engine.add_meshes calls this under the producer's stream: the C call orders itself against that stream alone."""
+    import torch
+
+    def rows(t, width):
+        if not _is_device_tensor(t) or t.device.index != device:
+            raise ValueError(f"a source must be a torch tensor on cuda:{device}")
+        t = t.reshape(-1, width) if t.dim() != 2 else t
+        if t.shape[1] != width:
+            raise ValueError(f"expected rows of {width} floats, not {tuple(t.shape)}")
+        if t.dtype != torch.float32 or (len(t) > 1 and (t.stride(1) != 1 or t.stride(0) < width)) or (len(t) <= 1 and not t.is_contiguous()):
+            t = t.to(torch.float32).contiguous()
+        return t
+
+    stride = lambda t: 4 * t.stride(0) if len(t) > 1 else 0
+    table, keep = (F.HkMeshSource * max(len(sources), 1))(), []
+    for k, (mesh_id, src) in enumerate(sources.items()):
+        if set(src) - {"positions", "normals", "uvs", "indices"}:
+            raise ValueError(f"unknown source arrays {sorted(set(src) - {'positions', 'normals', 'uvs', 'indices'})}")
+        pos, nrm = rows(src["positions"], 3), rows(src["normals"], 3)
+        uv = None if src.get("uvs") is None else rows(src["uvs"], 2)
+        idx = src.get("indices")
+        if idx is not None:
+            if not _is_device_tensor(idx) or idx.device.index != device:
+                raise ValueError(f"a source must be a torch tensor on cuda:{device}")
+            if idx.dtype not in (torch.int32, torch.uint32):   # (a wider type would have to be narrowed, and a value >= 2^31 would wrap silently)
+                raise ValueError(f"indices must be an int32 or uint32 tensor, not {idx.dtype}")
+            idx = idx.reshape(-1)
+            if not idx.is_contiguous():
+                idx = idx.contiguous()
+        keep += [pos, nrm, uv, idx]
+        table[k] = F.HkMeshSource(int(mesh_id), 0, pos.data_ptr(), nrm.data_ptr(), None if uv is None else uv.data_ptr(), None if idx is None else idx.data_ptr(),
+                                  stride(pos), stride(nrm), 0 if uv is None else stride(uv), 0)
+    return table, keep
+
+
 class Engine:
     """One context of the C ABI (`hk_ctx`).  `api` defaults to the product library."""
     _producer = None  # deform_meshes: a torch stream standing in for torch's legacy default stream (made at the first such call)
@@ -823,12 +891,39 @@ class Engine:
         self.api.call("debug_last_load", self.ctx, out)
         return tuple(int(v) for v in out)
 
-    def add_meshes(self, builder, mode=F.TREE_SAH):
+    def add_meshes(self, builder, mode=F.TREE_SAH, sources=None, producer_stream=None):
         """hk_add_meshes: the meshes added to the loaded, FINISHED `builder` since this context took its mesh level from it are appended to
         the device scene - deferred ones (SceneBuilder.add_mesh(build_tree=False)) get their trees built on the device and written back -
         without laying the scene out again.  Their instances follow through update_instances_on_device.  Returns nothing: the call's cost
-        follows the new meshes, and builder.scene() - a copy of every array of the builder - would make it follow the scene."""
-        self.api.call("add_meshes", self.ctx, builder.h, mode)
+        follows the new meshes, and builder.scene() - a copy of every array of the builder - would make it follow the scene.
+        `sources` (hk_add_meshes_device): {mesh_id: dict(positions=, normals=, uvs=None, indices=None)} of torch tensors on the context's
+        device for the meshes the builder declared by their counts (SceneBuilder.declare_mesh) - every such mesh exactly once.  Their
+        records are assembled on the device and the builder gets the geometry back: afterwards it holds what add_mesh(build_tree=False) of
+        the same values and this call would have left.  The context is ordered behind `producer_stream` (default: torch's current stream)
+        and that stream behind the context's read of the tensors, which may be overwritten right after the call."""
+        if sources is None:
+            self.api.call("add_meshes", self.ctx, builder.h, mode)
+            return
+        import torch
+
+        producer = torch.cuda.current_stream(self.device) if producer_stream is None else producer_stream
+        with torch.cuda.stream(producer):   # (conversions of tensors that cannot be named where they lie run where the call orders itself)
+            table, keep = mesh_sources_device(sources, self.device)
+        self._producer_call(producer, lambda handle: self.api.call("add_meshes_device", self.ctx, builder.h, table, len(sources), mode, handle))
+
+    def last_add_sources(self):
+        """(sources taken from device memory, their triangles, kernel launches that assembled them, bytes of HkPrimitive / HkVertex records
+        staged host to device) of the last add_meshes (test hook)."""
+        out = (F.u32 * 4)()
+        self.api.call("debug_last_add_sources", self.ctx, out)
+        return tuple(int(v) for v in out)
+
+    def last_add_source_times(self):
+        """ms of the last add_meshes with sources: (the assembling launch between two events - only while F.DEBUG_OPT_ADD_SOURCE_TIMES is
+        set, else 0 - the wait with the read-back, the builder's store) - hk_debug_last_add_source_times (measurement hook)."""
+        out = (C.c_double * 3)()
+        self.api.call("debug_last_add_source_times", self.ctx, out)
+        return tuple(float(v) for v in out)
 
     def last_add(self):
         """(meshes built on the device, their triangles, kernel launches of the build, meshes whose trees the host had built, 1 if the scene
@@ -1658,9 +1753,10 @@ class HikariPlugin:
         """set_scene for a finished SceneBuilder with deferred meshes: their trees are built on the device (Engine.load_scene)."""
         return self.engine.load_scene(builder, mode, textures)
 
-    def add_meshes(self, builder, mode=F.TREE_SAH):
-        """Meshes added to the loaded builder since (glTF assets that arrive frame by frame): appended on the device (Engine.add_meshes)."""
-        self.engine.add_meshes(builder, mode)
+    def add_meshes(self, builder, mode=F.TREE_SAH, sources=None, producer_stream=None):
+        """Meshes added to the loaded builder since (glTF assets that arrive frame by frame): appended on the device (Engine.add_meshes);
+        `sources`: the arrays of the meshes declared by their counts, as torch tensors on the device."""
+        self.engine.add_meshes(builder, mode, sources, producer_stream)
 
     def remove_meshes(self, extents):
         """Meshes that left the builder (SceneBuilder.remove_mesh): the device scene is compacted (Engine.remove_meshes)."""

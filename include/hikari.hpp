@@ -288,6 +288,27 @@ class SceneBuilder {  // the Prepare-stage host work: mesh -> BLAS, TLAS, emissi
     return n;
   }
   void build_pending_mesh_trees() { check(hk_scene_builder_build_pending_mesh_trees(h_), "hk_scene_builder_build_pending_mesh_trees"); }
+  // a mesh DECLARED by its counts (n_indices 0: the identity list): its arrays follow from device memory (Context / HikariPlugin
+  // add_meshes_device) or from the host (resolve_mesh); until then nothing uploads the builder and no instance may name the mesh
+  uint32_t declare_mesh(uint32_t n_vertices, uint32_t n_indices = 0, uint32_t topology = HK_TOPOLOGY_TRIANGLE_LIST) {
+    uint32_t id = 0;
+    check(hk_scene_builder_declare_mesh(h_, n_vertices, n_indices, topology, &id), "hk_scene_builder_declare_mesh");
+    return id;
+  }
+  // (the C call takes no counts: n_vertices and n_indices are the DECLARATION's, and the vectors are checked against them here)
+  void resolve_mesh(uint32_t mesh_id, uint32_t n_vertices, uint32_t n_indices, const std::vector<float>& positions, const std::vector<float>& normals,
+                    const std::vector<float>& uvs, const std::vector<uint32_t>& indices) {
+    if (positions.size() != 3 * (size_t)n_vertices || normals.size() != 3 * (size_t)n_vertices || (!uvs.empty() && uvs.size() != 2 * (size_t)n_vertices) ||
+        indices.size() != n_indices)
+      throw std::invalid_argument("resolve_mesh: the arrays do not have the declared counts");
+    check(hk_scene_builder_resolve_mesh(h_, mesh_id, positions.data(), normals.data(), uvs.empty() ? nullptr : uvs.data(), indices.empty() ? nullptr : indices.data()),
+          "hk_scene_builder_resolve_mesh");
+  }
+  uint32_t unresolved_meshes() const {
+    uint32_t n = 0;
+    check(hk_scene_builder_unresolved_meshes(h_, &n), "hk_scene_builder_unresolved_meshes");
+    return n;
+  }
   uint32_t add_material(const HkMaterial& m) {
     uint32_t id = 0;
     check(hk_scene_builder_add_material(h_, &m, &id), "hk_scene_builder_add_material");
@@ -349,6 +370,11 @@ class Context {
   }
   // meshes added to the loaded, finished builder since: appended to the device scene without laying it out again (hk_add_meshes)
   void add_meshes(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { check(hk_add_meshes(c_, b.handle(), tree_mode), "hk_add_meshes"); }
+  // ... with the arrays of the meshes the builder declared by their counts in DEVICE memory: assembled on the device, and the builder gets
+  // the geometry back (hk_add_meshes_device; producer_stream: a hipStream_t the sources are written on, or NULL)
+  void add_meshes_device(SceneBuilder& b, const std::vector<HkMeshSource>& sources, uint32_t tree_mode = HK_TREE_SAH, void* producer_stream = nullptr) {
+    check(hk_add_meshes_device(c_, b.handle(), sources.data(), (uint32_t)sources.size(), tree_mode, producer_stream), "hk_add_meshes_device");
+  }
   // meshes that left the builder (SceneBuilder::remove_mesh): the device scene's mesh level compacted behind the frames in flight (hk_remove_meshes)
   void remove_meshes(const std::vector<HkMeshExtent>& removed) { check(hk_remove_meshes(c_, removed.data(), (uint32_t)removed.size()), "hk_remove_meshes"); }
   ~Context() { hk_destroy(c_); }
@@ -448,6 +474,9 @@ class HikariPlugin {
   void load_scene(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { ctx_.load_scene(b, tree_mode); }  // ... with deferred meshes: trees built on the device
   void remove_meshes(const std::vector<HkMeshExtent>& removed) { ctx_.remove_meshes(removed); }  // meshes that leave: compacted on the device
   void add_meshes(SceneBuilder& b, uint32_t tree_mode = HK_TREE_SAH) { ctx_.add_meshes(b, tree_mode); }  // meshes that arrive later: appended on the device
+  void add_meshes_device(SceneBuilder& b, const std::vector<HkMeshSource>& sources, uint32_t tree_mode = HK_TREE_SAH, void* producer_stream = nullptr) {
+    ctx_.add_meshes_device(b, sources, tree_mode, producer_stream);  // ... their arrays in device memory (hk_add_meshes_device)
+  }
   // after SceneBuilder::set_instance_transform + finish: rewrite the instance-level device arrays only
   void update_instances(const SceneBuilder& b) {
     check(hk_upload_scene_instances(ctx_.get(), b.handle()), "hk_upload_scene_instances");

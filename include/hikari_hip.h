@@ -543,6 +543,27 @@ int hk_scene_builder_add_mesh_deferred(hk_scene_builder* b, const float* positio
                                        uint32_t* mesh_id);
 int hk_scene_builder_pending_mesh_trees(const hk_scene_builder* b, uint32_t* count);
 int hk_scene_builder_build_pending_mesh_trees(hk_scene_builder* b);
+/* A mesh DECLARED by its counts: its arrays are still to come - from device memory (hk_add_meshes_device) or, the host twin and the
+ * fallback, from hk_scene_builder_resolve_mesh.  n_indices == 0 is the identity list over the vertices (mod.rs:408-411); the triangle
+ * count is the one hk_scene_builder_add_mesh arrives at (a list n / 3, a strip n - 2).  The mesh holds n_vertices zero vertices, that
+ * many zero primitives and the deferred mesh's stand-in tree of the final 3t - 2 nodes, and carries two marks: pending (its tree is a
+ * stand-in) and UNRESOLVED (its geometry is zeros).  The next finish gives it its final HkMeshIndex - the record a twin that used
+ * hk_scene_builder_add_mesh_deferred gets.  Validation is add_mesh's where it applies: n_vertices == 0 or no triangle HK_E_INVALID; an
+ * unknown topology, or a list whose count is no multiple of 3, HK_E_UNSUPPORTED; the builder is unchanged then.
+ * While a mesh is unresolved: hk_scene_builder_add_instance naming it returns HK_E_NOT_READY (its box is unknown: instances follow the
+ * add, the documented flow of hk_add_meshes); hk_upload_scene, hk_load_scene, hk_add_meshes, hk_scene_builder_build_pending_mesh_trees
+ * (and the hk_multi_ forms), as well as the mesh edits of the builder that name it, return HK_E_NOT_READY naming the mesh, with nothing
+ * written; hk_scene_builder_remove_mesh works and takes both marks along.
+ * hk_scene_builder_resolve_mesh fills a declared mesh from HOST arrays with add_mesh's own arithmetic (positions, normals: 3 floats per
+ * vertex; uvs: 2, or NULL = (0, 0); indices: the declared count, NULL iff it was declared with none): vertices, primitives (a strip's
+ * odd triangles flipped), the mesh box as Aabb::from_min_max over ALL vertices, the stand-in over the real triangle boxes.  In a finished
+ * builder the concatenated arrays are patched in place and the builder stays finished.  The mesh then is an ordinary deferred mesh.
+ * HK_E_INVALID with the builder unchanged: NULL, a mesh that is not unresolved, indices given or missing against the declaration, an
+ * index >= n_vertices.  hk_scene_builder_unresolved_meshes counts the meshes that still wait. */
+int hk_scene_builder_declare_mesh(hk_scene_builder* b, uint32_t n_vertices, uint32_t n_indices, uint32_t topology, uint32_t* mesh_id);
+int hk_scene_builder_resolve_mesh(hk_scene_builder* b, uint32_t mesh_id, const float* positions, const float* normals, const float* uvs,
+                                  const uint32_t* indices);
+int hk_scene_builder_unresolved_meshes(const hk_scene_builder* b, uint32_t* count);
 /* the HkMeshIndex of a mesh after a finish (what its instances carry, and what the hk_*_mesh_* calls take) */
 int hk_scene_builder_mesh_index(const hk_scene_builder* b, uint32_t mesh_id, HkMeshIndex* out);
 /* Meshes that leave (the twin of hk_scene_builder_remove_instance).  hk_scene_builder_mesh_extent: the mesh's ranges in the arrays of the
@@ -925,6 +946,47 @@ int hk_load_scene(hk_ctx* ctx, hk_scene_builder* b, uint32_t tree_mode);
  * pointers are switched leaves the scene the context had; one after it leaves the context WITHOUT a scene, never with stand-in trees.
  * HkStats: scene_mesh_builds does not move, scene_device_tree_builds counts the meshes built. */
 int hk_add_meshes(hk_ctx* ctx, hk_scene_builder* b, uint32_t tree_mode);
+/* hk_add_meshes for meshes whose geometry lives in DEVICE memory (an iso-surface extracted on the GPU, a procedural terrain): the host
+ * declares them by their counts (hk_scene_builder_declare_mesh), finishes the builder, and names their arrays here.  No array crosses to
+ * the host on the caller's side and no HkPrimitive is assembled on a CPU thread; the builder GETS THE MESH BACK, as it gets the trees back.
+ * After HK_OK the context, the builder and the mirrors are byte for byte what hk_add_meshes leaves for a twin builder that got the same
+ * values through hk_scene_builder_add_mesh_deferred - every ordering's node plane, the triangle and vertex planes, wide records and
+ * ranks where the scene has them, the builder's getters - so nothing is stale and every later call (deformations, rebuilds, instance
+ * changes, removals, a second context or the bands taking the same builder through plain hk_add_meshes) works unchanged.  Meshes added to
+ * the builder the ordinary way since the last add travel in the same call; n == 0 with no unresolved mesh IS hk_add_meshes.  Accepted in
+ * every state hk_add_meshes is accepted in.
+ *   sources[i]: mesh_id - a declared, still unresolved mesh of the builder; every unresolved mesh must be named by exactly one source.
+ *   positions / normals (required) / uvs (or NULL = (0, 0)): device memory, 3 / 3 / 2 floats per vertex at pointer + v * stride; a
+ *   stride of 0 means packed (12 / 12 / 8), otherwise it is at least that and a multiple of 4 - a column slice of a wider row costs no
+ *   copy.  indices: n_indices x uint32, contiguous; NULL iff the mesh was declared with n_indices == 0.  flags and _pad must be 0.
+ * Phase 0, on the host, checks the whole batch before anything is enqueued (the failing source's index is in hk_last_error()): every
+ * check of hk_add_meshes; the mesh ids; pointers 4-byte aligned, memory of the context's device or mapped host memory, the whole extent
+ * - (n_vertices - 1) * stride + 12 (or + 8), n_indices * 4 - inside its allocation; strides; flags.  HK_E_INVALID, nothing written.
+ * Phase 1, on the device, is ONE launch however many sources there are: the context's stream waits for an event recorded on
+ * producer_stream (NULL: the caller has ordered itself, the rule of hk_deform_meshes_device), k_assemble_meshes writes the HkVertex and
+ * HkPrimitive records of all sources into a device block of the context's and a status word, and an event behind it goes back to the
+ * producer stream, which may then write the sources again.  Values move as bits.  An index >= n_vertices is never followed (vertex 0 is
+ * read instead) and flags its source.  The host waits for the stream - hk_add_meshes goes behind every enqueued frame and waits for its
+ * own build anyway - and reads status and block back in one copy: a flagged source returns HK_E_INVALID naming the lowest one, with the
+ * scene, the mirrors and the builder unchanged and the meshes still unresolved.
+ * Phase 2: the builder takes the records (the mesh box from the read-back positions with add_mesh's arithmetic); unresolved is cleared,
+ * pending stays.  Phase 3 is the body of hk_add_meshes itself: where it appends on the device, the ranges of these meshes are fed from the
+ * device block and only the records of meshes the host added go through pinned staging; where it lays the scene out again (the LDS copy,
+ * a changed ordering count) the builder is complete and nothing is special.  Trees, write-back, relocation and the host's completion of
+ * meshes above HK_MESH_REBUILD_MAX_TRIANGLES are hk_add_meshes'.
+ * There is no hk_multi_ form: a device pointer lives on one device.  A second context, or the other bands, take the completed builder
+ * through hk_add_meshes / hk_multi_add_meshes. */
+typedef struct HkMeshSource {
+  uint32_t mesh_id;
+  uint32_t flags;               /* must be 0 */
+  const void* positions;        /* DEVICE memory */
+  const void* normals;
+  const void* uvs;              /* or NULL */
+  const void* indices;          /* or NULL */
+  uint32_t positions_stride, normals_stride, uvs_stride;   /* bytes; 0 = packed */
+  uint32_t _pad;
+} HkMeshSource;                 /* 56 bytes */
+int hk_add_meshes_device(hk_ctx* ctx, hk_scene_builder* b, const HkMeshSource* sources, uint32_t n, uint32_t tree_mode, void* producer_stream);
 /* Meshes removed from the loaded scene: the mesh-level region compacted on the device (scene_remove.hip; DESIGN 3 "Meshes that leave").
  * removed[0..n) are the extents hk_scene_builder_remove_mesh returned since the builder's last finish - all in the context's CURRENT
  * layout, so one call per builder finish, in order; entries with node_count 0 are skipped, and with nothing left to do the call returns

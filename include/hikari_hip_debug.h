@@ -30,6 +30,14 @@ int hk_debug_last_add(hk_ctx* ctx, uint32_t out[5]);
  * relocation (the larger scene, wide records, events), out[1] its copy launch and the switch of the scene pointers, out[2] the growth of
  * the context's mirrors, out[3] staging, host layout, the device build with its wait and the read-back.  Zero where a step did not run. */
 int hk_debug_last_add_times(hk_ctx* ctx, double out[4]);
+/* Test hook: what the last hk_add_meshes / hk_add_meshes_device of this context took from device memory - out[0] the sources, out[1] their
+ * triangles, out[2] the kernel launches that assembled their records (phase 1: one, however many sources), out[3] the bytes of HkPrimitive
+ * and HkVertex records the call staged host to device: those of the meshes the host added only (the full layout of a one-slot scene
+ * uploads the whole mesh level again, and says so here).  hk_add_meshes leaves out[0..2] zero. */
+int hk_debug_last_add_sources(hk_ctx* ctx, uint32_t out[4]);
+/* Measurement hook (tools/mesh_source_probe.py): the last hk_add_meshes_device, in ms - out[0] the assembling launch between two HIP
+ * events (only while HK_DEBUG_OPT_ADD_SOURCE_TIMES is set, else 0), out[1] the host's wait for the stream with the read-back of status and records, out[2] the builder's store. */
+int hk_debug_last_add_source_times(hk_ctx* ctx, double out[3]);
 /* Test hook: what the last hk_remove_meshes of this context did - out[0] meshes removed, out[1] their triangles, out[2] what the call enqueued,
  * counted where it is enqueued: kernel launches (the propagate of deformed boxes that goes first included) and the fill of the new rank
  * plane (it does not follow the number of meshes), out[3] the runs per plane (the surviving intervals), out[4] the path (0 the device
@@ -161,6 +169,7 @@ int hk_debug_comm_lanes(hk_ctx* ctx, uint32_t* lanes);
 #define HK_DEBUG_OPT_LOAD_DEVICE_LIMIT 12u /* hk_load_scene completes a deferred mesh of more than this many triangles on the host instead of the device (default 0: HK_MESH_REBUILD_MAX_TRIANGLES); tests reach that path without a mesh of four million triangles */
 #define HK_DEBUG_OPT_MESH_REBUILD_ONE_WORKGROUP 11u /* 1: hk_rebuild_mesh_tree (HK_TREE_SAH) runs the top levels of its build in one workgroup at any mesh size, as the instance tree's build does (default 0: on the whole chip from 32 768 triangles); the same tree either way - the A/B of tools/deform_probe.py */
 #define HK_DEBUG_OPT_KNOWN_RESULTS 13u /* 0: no launch is handed the empty-tile plane of the frame's primary rays - every wave computes its way to the background constants, and stores them whatever the planes hold (default 1; the A/B, tests/test_known_results_gpu.py and tests/test_background_stores_gpu.py) */
+#define HK_DEBUG_OPT_ADD_SOURCE_TIMES 16u /* 1: hk_add_meshes_device records two timed events around its assembling launch (hk_debug_last_add_source_times out[0]; default 0: a product call makes and records none) */
 #define HK_DEBUG_OPT_MOTION_COUNT 15u /* 1: the motion pass counts the pixels it rewrites (hk_debug_last_motion; default 0) */
 #define HK_DEBUG_OPT_SPATIAL_KNOWN 14u /* 0: no spatial_reuse launch is handed the table of the background's known records - every background wave loads, unpacks and re-packs its input - and the windowed form of the kernel is handed no empty-tile / kept-tile plane (default 1; the A/B and tests/test_spatial_background_gpu.py) */
 int hk_debug_set_option(hk_ctx* ctx, uint32_t option, int64_t value);
